@@ -13,17 +13,23 @@ whole job over all ranks (each rank owns its own reads: weak scaling, no data-pa
 collective; one RCCL all-reduce of the {raw, compressed, reads} totals at the end).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--method M] [--reads R] [--fixed-len L]
+                    [--full] [--dump-outputs DIR]
 
 Defaults:
   N = 1   headline = BASELINE.json config 4: exception split + static NA12878_zd Huffman
           (shuffman_vbe21_zd, the method that meets "ratio >= VBZ"), 8192 NA12878-like reads.
-          The same run then measures config 2 (svb12_zd), config 3 (zstd_svb_zd, full VBZ) and
-          config 5's shape on one GPU as sub-records under "configs", each with its own roofline
-          and cpu_baseline, and the PCIe-inclusive host-buffer rate ("e2e_host").
+          A plain run measures the headline alone.  With --full the same run also times the
+          reference on the host CPU ("cpu_baseline") and measures config 2 (svb12_zd), config 3
+          (zstd_svb_zd, full VBZ) and config 5's shape on one GPU as sub-records under "configs",
+          each with its own roofline and cpu_baseline, and the PCIe-inclusive host-buffer rate
+          ("e2e_host").
   N > 1   BASELINE.json config 5: fixed 200 000-sample reads, best method (shuffman_vbe21_zd),
           4096 reads per GPU per step, launched by the driver with torch.distributed.run
           (one rank per GPU).  No sub-records, no CPU leg.
 Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's batch) as DIR/<name>.npy
+(see dump_outputs); the inputs depend on --seed, --reads, --fixed-len and --method only.
 """
 import argparse
 import json
@@ -157,9 +163,10 @@ class Batch:
         return caps, d_out, d_out_off, d_out_off[:-1].contiguous()
 
 
-def run_method(torch, press, shard, b, m, steps, warmup, world, dist, seed, check=True):
+def run_method(torch, press, shard, b, m, steps, warmup, world, dist, seed, check=True, keep_outputs=False):
     """warmup, verify, then time EXACTLY `steps` steps between barrier + synchronize pairs.
-    -> the record of this method (value over all ranks)."""
+    -> the record of this method (value over all ranks); with keep_outputs, "_outputs" holds the
+    last step's stream arena and its per-read offsets (b.d_len, b.d_back, b.d_outn hold the rest)."""
     if m.startswith("shuffman"):
         press.load_table()
     caps, d_out, d_out_off, d_in_off = b.arena(torch, press, m)
@@ -251,7 +258,7 @@ def run_method(torch, press, shard, b, m, steps, warmup, world, dist, seed, chec
     r_depress = roof(1, kern[1], kdepress_ms, depress_ms, "depress")
     dominant, other = (r_depress, r_press) if kdepress_ms >= kpress_ms else (r_press, r_depress)
     ratio = raw_all / comp_all
-    return {
+    rec = {
         "value": round(raw_all / (elapsed / steps) / 1e6, 1),
         "unit": "MB/s",
         "ms_per_step": round(elapsed / steps * 1e3, 4),
@@ -276,6 +283,56 @@ def run_method(torch, press, shard, b, m, steps, warmup, world, dist, seed, chec
                   "ms_per_step_max": round(max(r[3] for r in per_rank) / steps * 1e3, 4),
                   "reads": reads_all},
     }
+    if keep_outputs:
+        rec["_outputs"] = (d_out, np.concatenate([[0], np.cumsum(caps)]))
+    return rec
+
+
+def dump_outputs(torch, b, outputs, path, seed, budget=48 << 20):
+    """What a caller of the timed path receives from its last step, as float64 / float32 .npy files in `path`:
+    every read's stream length, sample count and two checksums of its stream bytes (all reads), and the
+    streams and decompressed samples themselves of a fixed sample of reads drawn with `seed` (at most
+    `budget` bytes of them).  Two builds given the same arguments can be compared file for file."""
+    d_out, out_off = outputs
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    lens = b.d_len.cpu().numpy()
+    # per read, on the device: sum of the stream's bytes and sum of byte * (position % 251 + 1), exact in float64
+    cks = np.zeros((b.R, 2), dtype=np.float64)
+    d_lens = b.d_len.to(torch.int64)
+    for g0 in range(0, b.R, 256):
+        g1 = min(b.R, g0 + 256)
+        lo, hi = int(out_off[g0]), int(out_off[g1])
+        starts = torch.from_numpy(out_off[g0:g1] - lo).to(b.dev)
+        rid = torch.repeat_interleave(torch.arange(g1 - g0, device=b.dev),
+                                      torch.from_numpy(np.diff(out_off[g0:g1 + 1])).to(b.dev))
+        pos = torch.arange(hi - lo, device=b.dev) - starts[rid]
+        byte = d_out[lo:hi].to(torch.float64) * (pos < d_lens[g0:g1][rid])
+        s0 = torch.zeros(g1 - g0, dtype=torch.float64, device=b.dev).index_add_(0, rid, byte)
+        s1 = torch.zeros(g1 - g0, dtype=torch.float64, device=b.dev).index_add_(0, rid, byte * (pos % 251 + 1))
+        cks[g0:g1, 0] = s0.cpu().numpy()
+        cks[g0:g1, 1] = s1.cpu().numpy()
+    # the sample: reads in a seeded order, each taken if its samples and stream (float32) fit what is left
+    rng = np.random.default_rng(seed)
+    pick, used = [], 0
+    for r in rng.permutation(b.R):
+        need = 4 * (int(b.n[r]) + int(lens[r]))
+        if used + need <= budget:
+            pick.append(int(r))
+            used += need
+    pick.sort()
+    streams = [d_out[int(out_off[r]): int(out_off[r]) + int(lens[r])].cpu().numpy() for r in pick]
+    samples = [b.d_back[int(b.starts[r]): int(b.starts[r]) + int(b.n[r])].cpu().numpy() for r in pick]
+    arrays = {
+        "stream_bytes": lens.astype(np.float64),
+        "sample_count": b.d_outn.cpu().numpy().astype(np.float64),
+        "stream_checksum": cks,
+        "sample_reads": np.array(pick, dtype=np.float64),
+        "sample_streams": np.concatenate(streams).astype(np.float32),
+        "sample_samples": np.concatenate(samples).astype(np.float32),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def main():
@@ -289,8 +346,12 @@ def main():
     ap.add_argument("--fixed-len", type=int, default=None,
                     help="fixed read length (config 5: %d, the default for --gpus > 1)" % CONFIG5_LEN)
     ap.add_argument("--seed", type=int, default=20261004)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
-    ap.add_argument("--no-sub", action="store_true", help="headline only: no sub-records, no e2e leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also the cpu_baseline legs and (default workload, one GPU) the sub-records and e2e legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline legs")
+    ap.add_argument("--no-sub", action="store_true", help="with --full: no sub-records, no e2e leg")
     ap.add_argument("--no-check", action="store_true", help=argparse.SUPPRESS)  # diagnostic kernel builds only
     ap.add_argument("--full-batches", type=int, default=61,
                     help="config4_500k_equiv: distinct 8192-read batches (61 = 499 712 reads; 0 = skip)")
@@ -328,7 +389,9 @@ def main():
     first_read, R = shard.weak_shard(reads, rank)
     b = Batch(torch, press, synth, args.seed, first_read, R, dev, fixed_len)
     out = run_method(torch, press, shard, b, m, args.steps, args.warmup, world, dist, args.seed,
-                     check=not args.no_check)
+                     check=not args.no_check, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, b, out.pop("_outputs"), args.dump_outputs, args.seed)
 
     if rank == 0:
         line = {
@@ -346,8 +409,8 @@ def main():
             "data": "synthetic",
         }
         line.update({k: v for k, v in out.items() if k not in ("value", "unit", "ms_per_step")})
-        sub = world == 1 and not args.no_sub and not explicit
-        if world == 1 and not args.no_cpu:
+        sub = args.full and world == 1 and not args.no_sub and not explicit
+        if args.full and world == 1 and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline(m, b)
         if sub:
             # the other single-GPU configurations of BASELINE.json, measured the same way in this run

@@ -49,6 +49,24 @@ def rc_stored_raw(method, stream, n):
     nlow = n - 1 - nex
     return nlow > 0 and len(stream) - 2 - sec == nlow
 
+def fuzz_inputs(count=150, seed=11):
+    """The randomised reads of test_oracle_vs_reference_fuzz (and of its golden vectors, reference_fuzz.json):
+    -> [(n, exception rate, int16 samples)], the same on every run."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for it in range(count):
+        n = int(rng.choice([1, 2, 3, 7, 8, 9, 15, 16, 17, 31, 33, 64, 100, 1000, 5000]))
+        exr = float(rng.choice([0, 0.001, 0.01, 0.05, 0.15]))
+        d = rng.integers(-60, 60, size=n)
+        ex = rng.random(n) < exr
+        d[ex] = rng.integers(-40000, 40000, size=int(ex.sum()))
+        s = (np.cumsum(d) + 500).astype(np.int64).astype(np.uint16).view(np.int16)
+        if it % 7 == 0:
+            s = ((s >> 5) << 5).astype(np.int16)
+        out.append((n, exr, s))
+    return out
+
+
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 
 

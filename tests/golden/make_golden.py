@@ -6,7 +6,8 @@ Run in the build container only (needs /root/reference and `make -C oracle ref`)
     python tests/golden/make_golden.py
 
 Reads the reference at fixture-build time only; commits DATA (inputs + expected
-outputs), never reference code:
+outputs), never reference code.  `make_golden.py fuzz` and `make_golden.py blow5 [FILE ...]`
+write only the last two files below:
 
 * three_reads.i16.bin / three_reads.json - the raw signals of the reference's own
   fixture data/three-reads.blow5 (decoded with the reference's slow5lib via
@@ -18,7 +19,12 @@ outputs), never reference code:
 * svb32_issue42.bin - the known-answer stream of press/streamvbyte/tests/unit.c:283
   (36 494 compressed bytes <-> 29 159 values);
 * synth_kats.json - synthetic NA12878-like reads (honours_amd.synth, seeds only) with
-  expected length + sha256 per method.
+  expected length + sha256 per method;
+* reference_fuzz.json - per randomised read of _libs.fuzz_inputs() and method: the reference's
+  bound, return code, stream length + sha256 and (range coders) the sha256 of its decode;
+* blow5_reference_reads.json - the files tests/test_blow5.py writes (and FILEs given, e.g. made
+  by the device), each read by the reference's slow5lib (oracle/_ref/ref_dump_blow5): the read ids
+  and sha256 of the samples it returned, and the index it wrote where there was none.
 """
 import hashlib
 import json
@@ -184,9 +190,88 @@ def main():
     print("golden vectors written to", HERE, file=sys.stdout)
 
 
+def fuzz():
+    quiet_stderr()
+    ref, oracle = _libs.reference(), _libs.oracle()
+    cases = []
+    for n, exr, s in _libs.fuzz_inputs():
+        z = np.zeros(n, dtype=np.uint16)
+        oracle.lib.po_zigdelta_u16(s.ctypes.data, n, z.ctypes.data)
+        ms = {}
+        for m in _libs.METHODS:
+            if m.startswith("shuffman") and int((z[1:] <= 255).sum()) == 0:
+                continue  # (no one-byte value: no Huffman stream)
+            bound = int(ref.bound(m, n))
+            rr, rc = ref.press(m, s, cap=bound + 8 * n + 1024)
+            e = {"bound": bound, "ret": rr, "len": len(rc), "sha256_32": sha(rc)}
+            if rr == 0 and m in _libs.RC_FAMILY and not _libs.rc_stored_raw(m, rc, n):
+                er, ed = ref.depress(m, rc, n)
+                e["depress_ret"], e["depress_sha256_32"] = er, sha(ed.tobytes())
+            ms[m] = e
+        cases.append({"n": n, "exr": exr, "signal": sha(s.tobytes()), "methods": ms})
+    json.dump({"source": "the reference (press/, built by oracle/Makefile) on tests/_libs.fuzz_inputs()",
+               "cases": cases}, open(os.path.join(HERE, "reference_fuzz.json"), "w"), separators=(",", ":"))
+    print("reference_fuzz.json:", len(cases), "cases")
+
+
+def blow5(extra):
+    """the files of test_reframe_without_gpu, test_index_is_the_one_slow5lib_writes (and, for signal method 1,
+    test_gpu_transcode_is_read_by_the_reference: the device's svb-zd fields are the source's bytes) as those tests
+    make them, and `extra` files, through the reference's slow5lib"""
+    import pathlib
+    import shutil
+    import tempfile
+
+    import test_blow5 as tb
+    from honours_amd import press
+
+    assert os.path.exists(os.path.join(_libs.ORACLE_DIR, "_ref", "ref_dump_blow5")), "make -C oracle ref first"
+    runs = {}
+    tmp = pathlib.Path(tempfile.mkdtemp())
+
+    def dump(path, ids=()):
+        key = tb.ref_dump_key(path, ids)
+        had_index = os.path.exists(path + ".idx")
+        got = tb._ref_dump(path, tmp, ids)
+        e = {"ids": list(got), "samples_sha256_32": [sha(v.tobytes()) for v in got.values()]}
+        if ids and not had_index:
+            e["index_built"] = open(path + ".idx", "rb").read().hex()
+        runs[key] = e
+        return got
+
+    bl = tb.BLOW5
+    fields = [f for _, f in tb.parse_blow5_py(bl)]
+    for rec in (0, 1):
+        dst = str(tmp / ("reframed%d.blow5" % rec))
+        assert press.blow5_transcode(bl, dst, record_method=rec, signal_method=1, passthrough=True) == 3
+        dump(dst)
+        dst = str(tmp / ("indexed%d.blow5" % rec))
+        ids = press.blow5_write_like(dst, bl, [fields[k % 3] for k in range(40)], record_method=rec, signal_method=1,
+                                     index=True)
+        pick = [ids[37], ids[0], ids[20], ids[5]]
+        dump(dst, pick)
+        os.remove(dst + ".idx")
+        dump(dst, pick[:1])
+        dst2 = str(tmp / ("t%d.blow5" % rec))
+        assert press.blow5_transcode(bl, dst2, record_method=rec, signal_method=1, passthrough=True, index=True) == 3
+        dump(dst2, [i for i, _ in tb.parse_blow5_py(bl)][::-1])
+    for path in extra:
+        dump(path)
+    shutil.rmtree(tmp)
+    json.dump({"source": "files written by honours_amd (tests/test_blow5.py) read by the reference's slow5lib "
+                         "(oracle/_ref/ref_dump_blow5)", "runs": runs},
+              open(os.path.join(HERE, "blow5_reference_reads.json"), "w"), indent=1)
+    print("blow5_reference_reads.json:", len(runs), "runs")
+
+
 if __name__ == "__main__":
     try:
-        main()
+        if sys.argv[1:2] == ["fuzz"]:
+            fuzz()
+        elif sys.argv[1:2] == ["blow5"]:
+            blow5(sys.argv[2:])
+        else:
+            main()
     except BaseException:
         import traceback
         traceback.print_exc(file=sys.stdout)  # stderr is silenced (reference diagnostics)

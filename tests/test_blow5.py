@@ -5,6 +5,7 @@ dumps from it (tests/golden/three_reads.i16.bin, made by oracle/ref_dump_blow5 -
 
 The signal bytes in the file are real known answers for the codec: nobody in this repository
 produced them."""
+import hashlib
 import json
 import os
 import struct
@@ -18,6 +19,8 @@ from honours_amd import press
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 BLOW5 = os.path.join(GOLD, "three-reads.blow5")
+# what the reference's slow5lib read from the files these tests write (tests/golden/make_golden.py blow5)
+REF_READS = os.path.join(GOLD, "blow5_reference_reads.json")
 
 
 def parse_blow5_py(path):
@@ -36,6 +39,35 @@ def parse_blow5_py(path):
         p = 2 + idl + 4 + 32
         ln, = struct.unpack("<Q", rec[p:p + 8])
         out.append((rec[2:2 + idl].decode(), rec[p + 8:p + 8 + ln]))
+    return out
+
+
+def read_blow5_py(path):
+    """independent read of a whole file with zlib or uncompressed records and svb-zd or raw signals (the layout of
+    slow5.c:787-870, 3903-3965; the svb-zd fields decoded by the oracle) -> [(read_id, int16 samples)]"""
+    d = open(path, "rb").read()
+    assert d[:6] == b"BLOW5\x01" and d[9] in (0, 1) and d[14] in (0, 1)
+    rec_method, sig_method = d[9], d[14]
+    hs, = struct.unpack("<I", d[64:68])
+    off = 68 + hs
+    out = []
+    while d[off:off + 5] != b"5WOLB":
+        rs, = struct.unpack("<Q", d[off:off + 8])
+        rec = d[off + 8:off + 8 + rs]
+        rec = zlib.decompress(rec) if rec_method == 1 else rec
+        off += 8 + rs
+        idl, = struct.unpack("<H", rec[:2])
+        p = 2 + idl + 4 + 32
+        ln, = struct.unpack("<Q", rec[p:p + 8])
+        rid = rec[2:2 + idl].decode()
+        if sig_method == 1:
+            field = rec[p + 8:p + 8 + ln]
+            n, = struct.unpack("<I", field[:4])
+            ret, sig = _libs.oracle().depress("slow5_svb_zd", field, n)
+            assert ret == 0, rid
+        else:
+            sig = np.frombuffer(rec[p + 8:p + 8 + 2 * ln], dtype=np.int16).copy()
+        out.append((rid, sig))
     return out
 
 
@@ -156,13 +188,26 @@ def test_gpu_wide_jumps_and_ragged(oracle):
         assert ro != 0 and rg != 0
 
 
+def ref_dump_key(path, ids=()):
+    """a file (and, when read by id, its index and the ids asked for) as blow5_reference_reads.json names it"""
+    def h(b):
+        return hashlib.sha256(b).hexdigest()[:32]
+    key = h(open(path, "rb").read())
+    if ids:
+        idx = path + ".idx"
+        key += ":" + (h(open(idx, "rb").read()) if os.path.exists(idx) else "noindex") + ":" + h(",".join(ids).encode())
+    return key
+
+
 def _ref_dump(path, tmp_path, ids=()):
     """the reference's slow5lib reads `path` (oracle/_ref/ref_dump_blow5) -> {read_id: samples}; with ids: those
-    reads through the index (slow5_idx_load + slow5_get)"""
+    reads through the index (slow5_idx_load + slow5_get; slow5lib writes <path>.idx first when there is none).
+    Where oracle/_ref is not built, what the reference read from this very file is taken from REF_READS: the file
+    (and its index) must be byte for byte one the reference read, and the samples decoded here the ones it got."""
     import subprocess
     tool = os.path.join(_libs.ORACLE_DIR, "_ref", "ref_dump_blow5")
     if not os.path.exists(tool):
-        pytest.skip("oracle/_ref/ref_dump_blow5 is not built here")
+        return _golden_dump(path, ids)
     out = str(tmp_path / "dump.bin")
     subprocess.run([tool, path, out] + list(ids), check=True, stderr=subprocess.DEVNULL)
     d = open(out, "rb").read()
@@ -175,6 +220,22 @@ def _ref_dump(path, tmp_path, ids=()):
         p += 12 + idl
         res[rid] = np.frombuffer(d[p:p + 2 * n], dtype=np.int16)
         p += 2 * n
+    return res
+
+
+def _golden_dump(path, ids=()):
+    runs = json.load(open(REF_READS))["runs"]
+    key = ref_dump_key(path, ids)
+    assert key in runs, "%s is not a file the reference's slow5lib was seen to read (%s)" % (path, key)
+    want = runs[key]
+    mine = dict(read_blow5_py(path))
+    res = {}
+    for rid, h in zip(want["ids"], want["samples_sha256_32"]):
+        res[rid] = mine[rid]
+        assert hashlib.sha256(mine[rid].tobytes()).hexdigest()[:32] == h, rid
+    if ids and want.get("index_built"):
+        with open(path + ".idx", "wb") as f:  # (the index the reference's slow5lib wrote for the file)
+            f.write(bytes.fromhex(want["index_built"]))
     return res
 
 

@@ -134,42 +134,46 @@ def test_table_matches_bitlength_list(oracle):
     assert sum(2.0 ** -l for l in lens) == 1.0
 
 
-@pytest.mark.skipif(not _libs.have_reference(), reason="oracle/_ref not built (no /root/reference here)")
-def test_oracle_vs_reference_fuzz(oracle):
-    """restatement == reference on randomised inputs, every method, incl. bounds"""
-    ref = _libs.reference()
+def test_oracle_vs_reference_fuzz(oracle, golden_dir):
+    """restatement == reference on randomised inputs, every method, incl. bounds: against the reference's
+    bounds, streams and (range coders) decoded samples of the same inputs in reference_fuzz.json, and
+    against the reference itself where oracle/_ref is built"""
+    gold = json.load(open(os.path.join(golden_dir, "reference_fuzz.json")))["cases"]
+    ref = _libs.reference() if _libs.have_reference() else None
     devnull = os.open(os.devnull, os.O_WRONLY)
     saved = os.dup(2)
     os.dup2(devnull, 2)  # the reference prints diagnostics (press.c:3262)
     try:
-        rng = np.random.default_rng(11)
-        for it in range(150):
-            n = int(rng.choice([1, 2, 3, 7, 8, 9, 15, 16, 17, 31, 33, 64, 100, 1000, 5000]))
-            exr = float(rng.choice([0, 0.001, 0.01, 0.05, 0.15]))
-            d = rng.integers(-60, 60, size=n)
-            ex = rng.random(n) < exr
-            d[ex] = rng.integers(-40000, 40000, size=int(ex.sum()))
-            s = (np.cumsum(d) + 500).astype(np.int64).astype(np.uint16).view(np.int16)
-            if it % 7 == 0:
-                s = ((s >> 5) << 5).astype(np.int16)
+        inputs = _libs.fuzz_inputs()
+        assert len(inputs) == len(gold)
+        for (n, exr, s), g in zip(inputs, gold):
+            assert g["n"] == n and g["signal"] == sha(s.tobytes())
             z = np.zeros(n, dtype=np.uint16)
             oracle.lib.po_zigdelta_u16(s.ctypes.data, n, z.ctypes.data)
             for m in _libs.METHODS:
                 if m.startswith("shuffman") and int((z[1:] <= 255).sum()) == 0:
+                    assert m not in g["methods"]
                     continue
-                cap = int(ref.bound(m, n)) + 8 * n + 1024
-                rr, rc = ref.press(m, s, cap=cap)
+                e = g["methods"][m]
+                assert oracle.bound(m, n) == e["bound"], (m, n)
+                cap = e["bound"] + 8 * n + 1024
                 oo, oc = oracle.press(m, s, cap=cap)
-                assert (rr, rc) == (oo, oc), (m, n, exr)
-                assert oracle.bound(m, n) == ref.bound(m, n)
-                if rr == 0:
-                    dr, dd = oracle.depress(m, rc, n)
+                assert (oo, len(oc), sha(oc)) == (e["ret"], e["len"], e["sha256_32"]), (m, n, exr)
+                if ref is not None:
+                    rr, rc = ref.press(m, s, cap=cap)
+                    assert (rr, rc) == (oo, oc), (m, n, exr)
+                    assert oracle.bound(m, n) == ref.bound(m, n)
+                if oo == 0:
+                    dr, dd = oracle.depress(m, oc, n)
                     if m in _libs.RC_FAMILY:
                         # only the encoder is compared on streams TurboRC stored raw
-                        if _libs.rc_stored_raw(m, rc, n):
+                        if _libs.rc_stored_raw(m, oc, n):
                             continue
-                        er, ed = ref.depress(m, rc, n)
-                        assert dr == 0 and er == 0 and np.array_equal(dd, ed) and np.array_equal(dd, s), (m, n)
+                        assert e["depress_ret"] == 0 and dr == 0 and sha(dd.tobytes()) == e["depress_sha256_32"], (m, n)
+                        if ref is not None:
+                            er, ed = ref.depress(m, oc, n)
+                            assert er == 0 and np.array_equal(dd, ed), (m, n)
+                        assert np.array_equal(dd, s), (m, n)
                         continue
                     assert dr == 0 and np.array_equal(dd, s), (m, n)
     finally:
