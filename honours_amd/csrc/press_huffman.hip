@@ -30,16 +30,17 @@
 //   k_huf_serial what is listed after that (a code whose lengths share a factor never synchronises): one wave
 //                per such read walks it serially from the first unsettled subsequence - slow, enough for ANY
 //                table and stream; the rounds before it are only faster.
-//   k_huf_chain  one workgroup per read: the codes in front of every tile (scan of the wave totals), the sample
-//                value there, what the read delivers, and whether k_huf_emit can write its samples.
+//   k_huf_chain  one workgroup per read: what the read delivers, whether k_huf_emit can write its samples, and per
+//                unit of k_huf_emit a plan (HufUnit, 32 bytes): where its payload lies, the codes in front of it (scan of
+//                the wave totals) and what it delivers, its slice of the exceptions and the sample value in front of it.
 //   k_huf_emit   lane i decodes its subsequence once more from its true start, now with the two-symbol
 //                table, into the wave's LDS staging buffer at its final order (scan of the counts); the
 //                count k_huf_sync found ends the loop.  Every wave is on its own (no barrier in the loop), and
 //                its loop is a pipeline two units deep: the next unit's payload and records are on their way
-//                while this one is decoded.
+//                while this one is decoded.  A unit's setup is one 32-byte plan; nothing of it is computed there.
 //                The one-byte values do not leave the chip: k_huf_sync also summed the sample deltas they
 //                stand for (per wave, from the same look-up), k_huf_chain made those the sample
-//                value in front of every tile, so the wave turns its staging buffer into samples itself
+//                value in front of every unit, so the wave turns its staging buffer into samples itself
 //                (zig-zag, running sum, the few exceptions merged in - trans.c:260) and stores int16.
 //                Reads whose lists do not interleave cleanly (a stream that delivers fewer values than
 //                its exceptions assume) keep the two-step way: values to DecodeArgs::low, then
@@ -702,63 +703,59 @@ __global__ __launch_bounds__(64) void k_huf_serial(DecodeArgs a)
 // the delta a 16-bit zig-zag value stands for, mod 2^16 (trans.c:80)
 __device__ __forceinline__ uint32_t unzz16(uint32_t z) { return ((z >> 1) ^ (0u - (z & 1u))) & 0xFFFFu; }
 
-// One workgroup per read: the codes and the sum of the deltas in front of every tile, what the read delivers
-// (huffman.c:1243: at most `want` values), the running sum of the exceptions' deltas (into the upper half of
-// ex_val) and whether k_huf_emit may write the samples itself.
+// exceptions e < nex with key(e) = pos[e] - e below ka / below kb (the keys do not decrease: the positions are strictly
+// increasing); both searches step together, so that their loads are in flight together
+__device__ __forceinline__ void keys_below2(const uint32_t *pos, uint32_t nex, uint32_t ka, uint32_t kb, uint32_t &ea, uint32_t &eb)
+{
+	uint32_t la = 0, lb = 0;
+	for (uint32_t step = nex ? 1u << (31 - __builtin_clz(nex)) : 0u; step; step >>= 1) {
+		const uint32_t ia = la + step - 1, ib = lb + step - 1;
+		const uint32_t pa = ia < nex ? pos[ia] : 0u, pb = ib < nex ? pos[ib] : 0u;
+		if (ia < nex && pa - ia < ka)
+			la += step;
+		if (ib < nex && pb - ib < kb)
+			lb += step;
+	}
+	ea = la;
+	eb = lb;
+}
+
+// One workgroup per read: what the read delivers (huffman.c:1243: at most `want` values), the running sum of the
+// exceptions' deltas (into the upper half of ex_val), whether k_huf_emit may write the samples itself, and for every
+// unit (a quarter tile) the plan k_huf_emit follows (HufUnit): where its payload lies, the codes in front of it and
+// what it delivers, its exceptions and the sample value in front of its first sample.
+template <int RU>
 __global__ __launch_bounds__(HT) void k_huf_chain(DecodeArgs a)
 {
+	constexpr uint32_t UB = 64 * HufGeo<RU>::OWN / 8; // payload bytes of a unit
+	constexpr uint32_t UPT = HT / 64;                 // units per tile
 	__shared__ uint32_t s_w[HT / 64], s_wd[HT / 64];
+	__shared__ unsigned long long s_cum;
 
 	const uint32_t r = blockIdx.x;
 	const uint32_t tid = threadIdx.x;
 	const uint32_t k0 = uniform(a.hread[2 * r]), nt = uniform(a.hread[2 * r + 1]);
 	if (!nt)
 		return;
-	// exclusive prefix of the tiles' counts and delta sums
-	uint64_t cum = 0;
-	uint32_t dcum = 0;
-	for (uint32_t b = 0; b < nt; b += HT) {
-		const uint32_t u = b + tid;
-		uint32_t c = 0, dt = 0;
-		if (u < nt) { // the tile's totals: its four waves'
-			const uint4 *wp = reinterpret_cast<const uint4 *>(a.hwave + (uint64_t) (k0 + u) * (HT / 64));
-			const uint4 w01 = wp[0], w23 = wp[1];
-			c = w01.x + w01.z + w23.x + w23.z;
-			dt = (w01.y + w01.w + w23.y + w23.w) & 0xFFFFu;
-		}
-		const uint32_t inc = wave_scan(c);
-		const uint32_t dinc = wave_scan(dt);
-		if ((tid & 63) == 63) {
-			s_w[tid >> 6] = inc;
-			s_wd[tid >> 6] = dinc;
-		}
-		__syncthreads();
-		uint32_t before = 0, total = 0, dbefore = 0, dtotal = 0;
-#pragma unroll
-		for (int w2 = 0; w2 < HT / 64; w2++) {
-			const uint32_t x = s_w[w2], y = s_wd[w2];
-			if (w2 < (int) (tid >> 6)) {
-				before += x;
-				dbefore += y;
-			}
-			total += x;
-			dtotal += y;
-		}
-		if (u < nt) {
-			const uint64_t bs = cum + before + inc - c;
-			a.htrec[k0 + u].base = bs > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t) bs;
-			a.htrec[k0 + u].dbase = (dcum + dbefore + dinc - dt) & 0xFFFFu;
-		}
-		cum += total;
-		dcum += dtotal;
-		__syncthreads();
+	const uint32_t nu = nt * UPT;
+	const uint2 *hw = a.hwave + (uint64_t) k0 * UPT;
+	// all codes of the read: the unit plans below need what it delivers
+	if (tid == 0)
+		s_cum = 0;
+	__syncthreads();
+	{
+		uint64_t c = 0;
+		for (uint32_t u = tid; u < nu; u += HT)
+			c += hw[u].x;
+		if (c)
+			atomicAdd(&s_cum, (unsigned long long) c);
 	}
 	const uint32_t want = uniform(a.htiles[k0].want);
-	const uint32_t nlow = cum < want ? (uint32_t) cum : want; // what huffman_decode_memory delivered
 	// running sum of the exceptions' deltas: ex_val[e] = value | (sum of the deltas of exceptions < e) << 16
 	const uint32_t nex = uniform(a.meta[r].nex);
 	const uint64_t o0 = a.htiles[k0].low;
 	uint32_t *val = a.ex_val + o0;
+	const uint32_t *pos = a.ex_pos + o0;
 	uint32_t xcum = 0;
 	for (uint32_t b = 0; b < nex; b += HT) {
 		const uint32_t e = b + tid;
@@ -781,12 +778,81 @@ __global__ __launch_bounds__(HT) void k_huf_chain(DecodeArgs a)
 		xcum += total;
 		__syncthreads();
 	}
+	__syncthreads(); // (s_cum; and the exceptions' prefixes are read by other threads below)
+	const uint64_t cumall = s_cum;
+	const uint32_t nlow = cumall < want ? (uint32_t) cumall : want; // what huffman_decode_memory delivered
 	// k_huf_emit writes the samples itself if the lists interleave into exactly 1 + nlow + nex samples:
 	// every exception sits among (or right behind) the delivered values
-	const bool fused = nlow >= 1 && (nex == 0 || a.ex_pos[o0 + nex - 1] < nlow + nex);
-	for (uint32_t u = tid; u < nt; u += HT)
-		a.htrec[k0 + u].fused = fused ? 1u : 0u;
-	static_assert(HT / 64 == 4, "a tile's wave totals are two 16-byte loads");
+	const bool fused = nlow >= 1 && (nex == 0 || pos[nex - 1] < nlow + nex);
+	const uint32_t zd0 = uniform(a.meta[r].zd0) & 0xFFFFu, q = uniform(a.meta[r].q);
+	// the tiles of a read are consecutive payload pieces (k_huff_tiles): unit u's payload starts u * UB bytes behind the
+	// first tile's
+	const uint64_t src0 = a.htiles[k0].src;
+	const int64_t nby0 = (int64_t) ((a.htiles[k0].nbits + 7u) >> 3);
+	// exclusive prefix of the units' counts and delta sums -> a plan per unit
+	uint64_t cum = 0;
+	uint32_t dcum = 0;
+	for (uint32_t b = 0; b < nu; b += HT) {
+		const uint32_t u = b + tid;
+		uint32_t c = 0, dt = 0;
+		if (u < nu) {
+			const uint2 w = hw[u];
+			c = w.x;
+			dt = w.y & 0xFFFFu;
+		}
+		const uint32_t inc = wave_scan(c);
+		const uint32_t dinc = wave_scan(dt);
+		if ((tid & 63) == 63) {
+			s_w[tid >> 6] = inc;
+			s_wd[tid >> 6] = dinc;
+		}
+		__syncthreads();
+		uint32_t before = 0, total = 0, dbefore = 0, dtotal = 0;
+#pragma unroll
+		for (int w2 = 0; w2 < HT / 64; w2++) {
+			const uint32_t x = s_w[w2], y = s_wd[w2];
+			if (w2 < (int) (tid >> 6)) {
+				before += x;
+				dbefore += y;
+			}
+			total += x;
+			dtotal += y;
+		}
+		if (u < nu) {
+			const uint64_t ob = cum + before + inc - c;
+			const uint32_t L0 = ob > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t) ob;
+			// the unit delivers values [L0, L0 + quota) of the read, cut at `want`
+			const uint32_t quota = L0 >= want ? 0u : (c < want - L0 ? c : want - L0);
+			const uint32_t L1 = L0 + quota;
+			// its exceptions: key in [L0, L1); the unit with the read's last value also takes those behind it
+			uint32_t Ea = 0, Eb = 0;
+			if (fused && quota) {
+				keys_below2(pos, nex, L0, L1, Ea, Eb);
+				if (L1 == nlow)
+					Eb = nex;
+			}
+			// the sample value in front of the unit's first sample (the read's first unit: zd[0], sample 0 itself)
+			uint32_t bz = zd0;
+			if (L0) {
+				bz = unzz16(zd0) + ((dcum + dbefore + dinc - dt) & 0xFFFFu);
+				if (Ea) {
+					const uint32_t pv = val[Ea - 1];
+					bz += (pv >> 16) + unzz16(pv & 0xFFFFu);
+				}
+				bz &= 0xFFFFu;
+			}
+			const uint64_t src = src0 + (uint64_t) u * UB;
+			const int64_t nby = nby0 - (int64_t) u * UB;
+			const uint32_t nbyc = nby <= 0 ? 0u : (nby > (int64_t) HUF_U_NBY ? HUF_U_NBY : (uint32_t) nby);
+			uint4 *d = reinterpret_cast<uint4 *>(a.hunit + (uint64_t) k0 * UPT + u);
+			d[0] = make_uint4((uint32_t) src, (uint32_t) (src >> 32) | (bz << 16), (uint32_t) o0, (uint32_t) (o0 >> 32));
+			d[1] = make_uint4(L0, quota | (nbyc << 14) | ((q & 15u) << 26) | (fused ? 1u << 30 : 0u), Ea, Eb - Ea);
+		}
+		cum += total;
+		dcum += dtotal;
+		__syncthreads();
+	}
+	static_assert(HUF_U_QUOTA >= 64u * 255u, "a unit's quota");
 	if (tid == 0) {
 		a.meta[r].nlow = nlow;
 		if (fused)
@@ -889,20 +955,6 @@ __device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *p, uint32_t 
 	return lo;
 }
 
-// exceptions e with pos[e] - e < key (wave-uniform arguments and result)
-__device__ __forceinline__ uint32_t keys_below(const uint32_t *pos, uint32_t nex, uint32_t key)
-{
-	uint32_t lo = 0, hi = nex;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (uniform(pos[mid]) - mid < key)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
 // the deltas of the 8 samples at i0 (16 bits each, two per register) with the exceptions
 // [e_first, e_first + e_cnt) merged in; samples outside [Ia, Ib) are left zero.  lowat(l) = delta of one-byte
 // value number l.
@@ -944,7 +996,7 @@ __device__ __forceinline__ void gather8(LOWAT lowat, const uint32_t *pos, const 
 struct EmitRead { // what a wave needs of its read to write samples (wave-uniform)
 	const uint32_t *pos, *val;
 	int16_t *out;
-	uint32_t nex, zd0, q, nlow;
+	uint32_t zd0, q;
 };
 
 // emit_samples' groups of 8 samples start at multiples of 8 samples: 16-byte stores at 16-byte addresses
@@ -971,53 +1023,6 @@ struct EmitPlan { // where a wave's samples lie and what they start from (wave-u
 	uint32_t base;     // value of the sample in front of Ia
 	uint32_t pe;       // lane e < ecnt <= 64: position of exception Ea + e
 };
-
-// What emit_samples needs besides the values themselves.  B0 = sum of the deltas of the values in front of L0
-// (mod 2^16); key = pos[lane] - lane of the read's first 64 exceptions, loaded by the caller BEFORE the wave
-// decodes its codes (the load is under way meanwhile).
-__device__ __forceinline__ EmitPlan emit_plan(const EmitRead &R, uint32_t L0, uint32_t quota, uint32_t B0, uint32_t lane,
-					      uint32_t kraw, uint32_t vraw)
-{
-	const uint32_t key = kraw == 0xFFFFFFFFu ? kraw : kraw - lane; // kraw: pos[lane] of the read's first 64 exceptions
-	EmitPlan P;
-	P.L0 = L0;
-	P.L1 = L0 + quota;
-	const uint32_t nex = R.nex;
-	const bool lastw = P.L1 == R.nlow;
-	// exceptions in front of the wave's first / behind its last sample
-	uint32_t Ea = 0, Eb = 0;
-	if (nex && nex <= 64) {
-		Ea = (uint32_t) __popcll(__ballot(key < P.L0));
-		Eb = (uint32_t) __popcll(__ballot(key < P.L1));
-	} else if (nex) {
-		Ea = keys_below(R.pos, nex, P.L0);
-		Eb = keys_below(R.pos, nex, P.L1);
-	}
-	if (lastw)
-		Eb = nex;
-	P.Ea = Ea;
-	P.ecnt = Eb - Ea;
-	P.Ia = L0 ? L0 + Ea + 1 : 0u;
-	P.Ib = P.L1 + Eb + 1;
-	P.base = 0;
-	if (L0) {
-		P.base = unzz16(R.zd0) + B0;
-		if (Ea) {
-			// (a read of at most 64 exceptions - nearly every read - has them all in kraw / vraw, one per lane,
-			// asked for before the decode loop: no load here that the sample phase would have to wait for)
-			const uint32_t pv = nex <= 64 ? (uint32_t) __builtin_amdgcn_readlane((int) vraw, (int) (Ea - 1)) : uniform(R.val[Ea - 1]);
-			P.base += (pv >> 16) + unzz16(pv & 0xFFFFu);
-		}
-	}
-	// the wave's exceptions, one per lane (more than 64: searched where needed)
-	if (nex <= 64) {
-		const uint32_t pl = (uint32_t) __shfl((int) kraw, (int) ((Ea + lane) & 63u), 64);
-		P.pe = lane < P.ecnt ? pl : 0xFFFFFFFFu;
-	} else {
-		P.pe = (P.ecnt <= 64 && lane < P.ecnt) ? R.pos[Ea + lane] : 0xFFFFFFFFu;
-	}
-	return P;
-}
 
 // The deltas of the wave's values [L0, L1) are in the LDS staging buffer (src[l - L0]): write the samples they and
 // their exceptions make, 16 samples per lane and round (1024 per round; 8 per lane cost twice the wave scans and rounds).
@@ -1090,7 +1095,7 @@ __device__ __forceinline__ void emit_samples16(const uint8_t *src, const EmitRea
 				v[h] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, v[h]) << qq);
 		}
 #if defined(EMIT_ABL) && EMIT_ABL == 1
-		if (R.nlow == 0x7FFFFFFFu)
+		if (R.q == 0x7FFFFFFFu)
 #endif
 #pragma unroll
 		for (int hh = 0; hh < 2; hh++) {
@@ -1190,13 +1195,13 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 	uint32_t *col = img[wv] + lane;
 	uint8_t *stg = stg_all.s[wv];
 	__syncthreads(); // the tables; from here on every wave is on its own: columns and staging are private, and
-	                 // what the other waves of its tile hold in front of it comes with the tile's records
+	                 // what the other waves of its tile hold in front of it comes with the unit's plan
 	// persistent workgroups: the tables are loaded once.
 	//
 	// The loop is a pipeline two units deep, so that no wave waits for a unit's records or payload: while unit N is
-	// decoded, the payload / per-lane record / read record of unit N + 1 are on their way into registers (their
-	// addresses come from the tile records of N + 1, asked for one unit earlier), and the ticket of unit N + 2 is
-	// drawn and its tile records asked for.  What arrives is used BETWEEN the decode loop and the sample phase of unit
+	// decoded, the payload / per-lane record / exception position of unit N + 1 are on their way into registers (their
+	// addresses come from the plan of N + 1, asked for one unit earlier), and the ticket of unit N + 2 is drawn and its
+	// plan asked for.  What arrives is used BETWEEN the decode loop and the sample phase of unit
 	// N - never right behind the sample phase's stores: vector-memory operations complete in order, and a wait for a
 	// load issued behind stores is a wait for the stores.  (Stamps before: records + payload 15 %, scan 8 % of a
 	// wave's time; an ablation without decode loop and sample phase left 0.33 of the kernel's 0.98 ms.)
@@ -1219,56 +1224,47 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 		}
 		return uniform(u);
 	};
-	static_assert(sizeof(HufTile) == 32 && sizeof(HufTRec) == 32 && sizeof(ReadMeta) == 32 && offsetof(HufTile, nbits) == 16 &&
-			      offsetof(HufTile, read) == 24 && offsetof(HufTRec, base) == 8 && offsetof(HufTRec, fused) == 28,
-		      "the records are read as eight dwords each");
-	// a unit's tile records (HufTile, HufTRec, the totals of the tile's four waves: 32 bytes each, wave-uniform) are
-	// loaded ONE DWORD PER LANE - lanes 0 .. 7 the HufTile, 8 .. 15 the HufTRec, 16 .. 23 the totals - into a single
-	// vector register and read out with v_readlane when they have arrived (as 16-byte loads of every lane, held in
-	// flight across a unit, they took 48 registers and the kernel no longer fit four waves per SIMD)
-	auto fetch_tile = [&](uint32_t u) -> uint32_t {
+	static_assert(offsetof(HufUnit, obase) == 16 && offsetof(HufUnit, ecnt) == 28, "the plan is read as eight dwords");
+	static_assert(63 * (OWN / 8) + 4 * NDW <= HUF_U_NBY, "HufUnit::qnf's byte count tells whether every lane's bytes lie inside");
+	// a unit's plan (HufUnit, 32 bytes, wave-uniform) is loaded ONE DWORD PER LANE - lanes 0 .. 7 - into a single vector
+	// register and read out with v_readlane when it has arrived (as 16-byte loads of every lane, held in flight across a
+	// unit, the records of a unit took 48 registers and the kernel no longer fit four waves per SIMD)
+	auto fetch_unit = [&](uint32_t u) -> uint32_t {
 		uint32_t v = 0;
-		if (u < nunits && lane < 24) {
-			const uint32_t k = u / (HT / 64);
-			const uint32_t *p = lane < 8 ? reinterpret_cast<const uint32_t *>(a.htiles + k)
-					  : lane < 16 ? reinterpret_cast<const uint32_t *>(a.htrec + k)
-						      : reinterpret_cast<const uint32_t *>(a.hwave + (uint64_t) k * (HT / 64));
-			v = p[lane & 7];
-		}
+		if (u < nunits && lane < 8)
+			v = reinterpret_cast<const uint32_t *>(a.hunit + u)[lane];
 		return v;
 	};
-	struct Unit { // what a unit needs of its tile (wave-uniform)
-		uint32_t u, nbits_t, read, want, fused, cb, db, base, dbase;
+	struct Unit { // what k_huf_chain planned for a unit (wave-uniform)
+		uint32_t u, obase, quota, nby, fused, q, bz, ea, ecnt;
 		uint64_t srco, roff;
 	};
 	auto resolve = [&](uint32_t u, uint32_t tv) -> Unit {
 		auto at = [&](int i) -> uint32_t { return (uint32_t) __builtin_amdgcn_readlane((int) tv, i); };
 		Unit U;
 		U.u = u;
-		U.srco = ((uint64_t) at(1) << 32) | at(0); // HufTile::src
-		U.roff = ((uint64_t) at(3) << 32) | at(2); // ::low: the read's slot - samples in a.sig, one-byte values in
-		                                          // a.low, exceptions
-		U.nbits_t = at(4);                        // ::nbits
-		U.read = at(6);                           // ::read
-		U.want = at(7);                           // ::want
-		U.base = at(8 + 2);                       // HufTRec::base, ::dbase: codes of the read in front of the tile
-		U.dbase = at(8 + 3);                      // and the sum of their deltas
-		U.fused = at(8 + 7);                      // ::fused
-		const uint32_t wq = u % (HT / 64); // what the tile's waves in front of this one hold
-		U.cb = (wq > 0 ? at(16) : 0u) + (wq > 1 ? at(18) : 0u) + (wq > 2 ? at(20) : 0u);
-		U.db = (wq > 0 ? at(17) : 0u) + (wq > 1 ? at(19) : 0u) + (wq > 2 ? at(21) : 0u);
+		const uint32_t hb = at(1), qnf = at(5);
+		U.srco = ((uint64_t) (hb & 0xFFFFu) << 32) | at(0); // the unit's payload
+		U.bz = hb >> 16;
+		U.roff = ((uint64_t) at(3) << 32) | at(2); // the read's slot - samples in a.sig, one-byte values in a.low, exceptions
+		U.obase = at(4);
+		U.quota = qnf & HUF_U_QUOTA;
+		U.nby = (qnf >> 14) & HUF_U_NBY;
+		U.q = (qnf >> 26) & 15u;
+		U.fused = qnf >> 30;
+		U.ea = at(6);
+		U.ecnt = at(7);
 		return U;
 	};
-	struct Stage2 { // a unit's per-lane loads: payload (in registers when every lane's 36 bytes lie inside it), record, read
+	struct Stage2 { // a unit's per-lane loads: payload (in registers when every lane's 36 bytes lie inside it), record,
+		        // the position of the lane's exception
 		uint32_t pay[NDW];
-		uint32_t rec;
-		uint4 m0, m1;
+		uint32_t rec, pe;
 		bool fast;
 	};
 	auto issue2 = [&](const Unit &U, Stage2 &S) {
-		const uint32_t tid = (U.u % (HT / 64)) * 64 + lane; // the lane's subsequence of the tile
-		const int32_t rb0 = (int32_t) tid * (OWN / 8), nby = (int32_t) ((U.nbits_t + 7) >> 3);
-		S.fast = !any64(rb0 + 4 * NDW > nby);
+		const int32_t rb0 = (int32_t) lane * (OWN / 8);
+		S.fast = U.nby >= 63 * (OWN / 8) + 4 * NDW;
 		const uint8_t *q = a.in + U.srco + rb0;
 		if (S.fast) {
 			uint4 t[NDW / 4 ? NDW / 4 : 1];
@@ -1286,10 +1282,9 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 				S.pay[4 * j + 3] = t[j].w;
 			}
 		}
-		S.rec = a.hrec[(uint64_t) (U.u / (HT / 64)) * HT + tid];
-		const uint4 *mp = reinterpret_cast<const uint4 *>(a.meta + U.read);
-		S.m0 = mp[0];
-		S.m1 = mp[1];
+		S.rec = a.hrec[(uint64_t) U.u * 64 + lane];
+		// the unit's exceptions, one per lane (more than 64: searched where needed)
+		S.pe = (U.ecnt <= 64 && lane < U.ecnt) ? a.ex_pos[U.roff + U.ea + lane] : 0xFFFFFFFFu;
 	};
 	auto land2 = [&](const Unit &U, const Stage2 &S) { // the payload into the wave's columns (which must be free)
 		wave_lds_sync();
@@ -1298,8 +1293,7 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 			for (int j = 0; j < NDW; j++)
 				col[j * 64] = S.pay[j];
 		} else { // a payload's last bytes: the careful loader (its loads are waited for here)
-			const uint32_t tid = (U.u % (HT / 64)) * 64 + lane;
-			col_load<NDW>(col, a.in + U.srco, (int32_t) tid * (OWN / 8), 0, (int32_t) ((U.nbits_t + 7) >> 3));
+			col_load<NDW>(col, a.in + U.srco, (int32_t) lane * (OWN / 8), 0, (int32_t) U.nby);
 		}
 		wave_lds_sync();
 	};
@@ -1307,35 +1301,29 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 	const uint32_t u_first = draw();
 	if (u_first >= nunits)
 		return;
-	Unit U = resolve(u_first, fetch_tile(u_first)), Un = {}, Unn = {};
+	Unit U = resolve(u_first, fetch_unit(u_first)), Un = {}, Unn = {};
 	Stage2 S, Sn = {};
 	issue2(U, S);
 	land2(U, S);
 	uint32_t u_nxt = draw();
 	if (u_nxt < nunits)
-		Un = resolve(u_nxt, fetch_tile(u_nxt));
+		Un = resolve(u_nxt, fetch_unit(u_nxt));
 	for (;;) {
-		// ---- the units behind this one: the ticket of N + 2 and its tile records; the per-lane loads of N + 1
+		// ---- the units behind this one: the ticket of N + 2 and its plan; the per-lane loads of N + 1
 		const uint32_t u_nn = draw();
-		const uint32_t tv_nn = fetch_tile(u_nn);
+		const uint32_t tv_nn = fetch_unit(u_nn);
 		const bool more = u_nxt < nunits;
 		if (more)
 			issue2(Un, Sn);
 		HSTAMP(0); // tickets, loads of the next units
 		// ---- this unit
-		const uint32_t tid = (U.u % (HT / 64)) * 64 + lane; // the lane's subsequence of the tile
 		const uint32_t rec = S.rec;
-		const uint32_t want = U.want;
+		const uint32_t quota = U.quota;
+		const uint32_t obase = U.obase;
 		const uint64_t roff = U.roff;
-		uint8_t *low = a.low + roff;
 		const uint32_t cnt = (rec >> 8) & 0xFFu;
 		const uint32_t inc = wave_scan(cnt);
-		const uint64_t obase = (uint64_t) U.base + U.cb;
-		const uint32_t B0 = U.dbase + (U.db & 0xFFFFu);
 		const bool fused = U.fused != 0;
-		const uint32_t wsum = uniform((uint32_t) __shfl((int) inc, 63, 64));
-		// the wave delivers values [obase, obase + wsum) of the read, cut at `want`
-		const uint32_t quota = obase >= want ? 0u : (wsum < want - (uint32_t) obase ? wsum : want - (uint32_t) obase);
 		const uint32_t ex = inc - cnt; // codes of the wave in front of this lane
 		const uint32_t f = rec & 0xFFu;
 		const uint32_t p0 = f == R_END ? 0u : f;
@@ -1343,25 +1331,7 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 		// (at most 64 codes per lane: the staging buffer takes them all; the clamp only keeps records that are not
 		// this library's own from writing outside it)
 		nmine = ex >= EMIT_STG ? 0u : (nmine < EMIT_STG - ex ? nmine : EMIT_STG - ex);
-		uint8_t *dst = low + obase;
-		EmitRead R = {};
-		if (fused) {
-			R.pos = a.ex_pos + roff;
-			R.val = a.ex_val + roff;
-			R.out = a.sig + roff;
-			R.nex = uniform(S.m0.x);  // ReadMeta::nex
-			R.zd0 = uniform(S.m0.z);  // ::zd0
-			R.q = uniform(S.m0.w);    // ::q
-			R.nlow = uniform(S.m1.z); // ::nlow
-		}
-		(void) tid;
-		// symbols go to the wave's staging buffer in their final order
-		// (the read's first exceptions: asked for now, needed behind the decode loop)
-		// (the position as loaded: any arithmetic on it here would put the wait for it - and for every load issued before
-		// it, the next unit's among them - in front of the decode loop)
-		const uint32_t kraw = (fused && quota && lane < R.nex) ? R.pos[lane] : 0xFFFFFFFFu;
-		const uint32_t vraw = (fused && quota && lane < R.nex) ? R.val[lane] : 0u; // (their values and delta prefixes)
-		HSTAMP(2); // scan, read record
+		HSTAMP(2); // scan
 		{
 #if defined(EMIT_ABL) && EMIT_ABL == 3 // (timing experiments only: wrong results)
 			if (a.nreads == 0x7FFFFFFFu)
@@ -1369,6 +1339,7 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 			emit_codes<TRIE>(col, lut, lut2, a.huff, p0, nmine, stg + ex);
 			HSTAMP(3); // decode
 			// what was asked for at the top has arrived (the columns are free, and no store of this unit is in the way)
+			const uint32_t pe = S.pe;
 			if (more)
 				land2(Un, Sn);
 			else
@@ -1378,7 +1349,21 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 			HSTAMP(1); // the next units' loads land
 			if (fused) {
 				if (quota) {
-					const EmitPlan P = emit_plan(R, (uint32_t) obase, quota, B0, lane, kraw, vraw);
+					EmitRead R;
+					R.pos = a.ex_pos + roff;
+					R.val = a.ex_val + roff;
+					R.out = a.sig + roff;
+					R.zd0 = U.bz; // (used for sample 0 only: by the read's first unit, whose bz is zd[0])
+					R.q = U.q;
+					EmitPlan P;
+					P.L0 = obase;
+					P.L1 = obase + quota;
+					P.Ea = U.ea;
+					P.ecnt = U.ecnt;
+					P.Ia = obase ? obase + U.ea + 1 : 0u;
+					P.Ib = P.L1 + U.ea + U.ecnt + 1;
+					P.base = obase ? U.bz : 0u;
+					P.pe = pe;
 					HSTAMP(4); // plan
 #if defined(EMIT_ABL) && EMIT_ABL == 2
 					if (a.nreads == 0x7FFFFFFFu)
@@ -1388,6 +1373,7 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 				}
 			} else {
 				// the one-byte stream, for k_low_decode_chunked: 16-byte stores
+				uint8_t *dst = a.low + roff + obase;
 				for (uint32_t o = lane * 16; o < quota; o += 64 * 16) {
 					uint4 v = *reinterpret_cast<const uint4 *>(stg + o);
 					v = make_uint4(zz_bytes(v.x), zz_bytes(v.y), zz_bytes(v.z), zz_bytes(v.w));
@@ -1525,7 +1511,7 @@ static void run_huff_decode(const DecodeArgs &a, hipStream_t s)
 	for (int round = 0; round < HUF_FIX_LAUNCHES; round++)
 		hipLaunchKernelGGL((k_huf_fix<RU, TRIE>), dim3(FIX_WG >= 1024 ? 512 : FIX_WG >= 512 ? 768 : 1280), dim3(FIX_WG), 0, s, a, round, round + 1 == HUF_FIX_LAUNCHES ? 1 : 0);
 	hipLaunchKernelGGL((k_huf_serial<RU, TRIE>), dim3(a.nreads), dim3(64), 0, s, a);
-	hipLaunchKernelGGL(k_huf_chain, dim3(a.nreads), dim3(HT), 0, s, a);
+	hipLaunchKernelGGL(k_huf_chain<RU>, dim3(a.nreads), dim3(HT), 0, s, a);
 	hipLaunchKernelGGL((k_huf_emit<RU, TRIE>), dim3(ge), dim3(WGE), 0, s, a); // (ctl->units: zero since the control block was cleared)
 }
 

@@ -78,15 +78,20 @@ constexpr uint32_t HUF_TWO = 1u << 29;
 
 // parallel Huffman decode (press_huffman.hip): tiles of HUF_HT subsequences
 constexpr int HUF_HT = 256;        // subsequences per tile (a lane each)
-struct HufTRec {             // what k_huf_chain leaves per tile (32 bytes: k_huf_emit takes it in two 16-byte loads)
-	uint32_t rsv0[2];
-	uint32_t base;       // codes of the read in front of the tile
-	uint32_t dbase;      // sum of their deltas, mod 2^16
-	uint32_t rsv1[3];
-	uint32_t fused;      // 1 = k_huf_emit writes the read's samples itself, 0 = its one-byte
-	                     // values go to DecodeArgs::low and k_low_decode_chunked merges them
+struct HufUnit {              // what k_huf_chain leaves per unit (a quarter tile: one wave's work in k_huf_emit), 32 bytes
+	uint32_t src_lo;     // arena byte offset of the unit's first payload byte, bits 0 .. 31
+	uint32_t src_hi_bz;  // ... bits 32 .. 47 (offsets into device memory) | bz << 16: the sample value in front of the
+	                     // unit's first sample, mod 2^16 (for the read's first unit, which writes sample 0: zd[0])
+	uint64_t roff;       // the read's slot (DecodeArgs::off)
+	uint32_t obase;      // codes of the read in front of the unit (clamped to 2^32 - 1)
+	uint32_t qnf;        // quota | nby << 14 | q << 26 | fused << 30: the codes the unit delivers (cut at the read's
+	                     // count), payload bytes from src on (clamped to HUF_U_NBY: more than a unit reads), the
+	                     // ex-zd shift, 1 = k_huf_emit writes the read's samples itself (0: its one-byte values go to
+	                     // DecodeArgs::low and k_low_decode_chunked merges them)
+	uint32_t ea, ecnt;   // the unit's exceptions [ea, ea + ecnt) of the read (fused reads with a quota; else 0)
 };
-static_assert(sizeof(HufTRec) == 32, "HufTRec");
+static_assert(sizeof(HufUnit) == 32, "HufUnit");
+constexpr uint32_t HUF_U_QUOTA = 0x3FFFu, HUF_U_NBY = 0xFFFu; // (a unit delivers at most 64 x 255 codes)
 constexpr uint32_t HUF_FUSED = 0x80000000u; // in DecodeArgs::hread[2r + 1]: the read needs no k_low_decode_chunked
 
 // ---- chunked (v2) svb kernels: a read is cut into chunks of CHUNK samples, one workgroup
@@ -182,7 +187,7 @@ struct DecodeArgs {
 	uint32_t max_chunks;
 	// Huffman tiles (press_huffman.hip)
 	HufTile *htiles;          // [max_htiles]
-	HufTRec *htrec;           // [max_htiles]
+	HufUnit *hunit;           // [max_htiles * 4] per unit (quarter tile): k_huf_chain's plan for k_huf_emit
 	uint32_t *hrec;           // [max_htiles * HUF_HT] one record per subsequence: start | codes << 8 | sum of their deltas << 16
 	uint32_t *hlist;          // [2 * hlist_cap] two lists of subsequences to decode again (k_huf_fix)
 	uint8_t *hend;            // [max_htiles * HUF_HT] per subsequence: where the next one's first code starts (0 .. 30, 31: none)
