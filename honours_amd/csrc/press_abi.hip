@@ -45,6 +45,15 @@ static int fail(int code, const char *fmt, ...)
 
 extern "C" const char *press_hip_last_error(void) { return g_err; }
 
+int ph::set_error(int code, const char *fmt, ...)
+{
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(g_err, sizeof g_err, fmt, ap);
+	va_end(ap);
+	return code;
+}
+
 // ------------------------------------------------------------------ context
 
 namespace {
@@ -1233,6 +1242,70 @@ extern "C" int press_hip_press_batch(int method, const int16_t *sig, const uint6
 			   (uint8_t *) g.dense.p);
 	if ((rc = staged_pieces<false>((uint8_t *) g.dense.p, dense, pc, s)))
 		return rc;
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
+#ifndef TRAIN_WG_PER_CU
+#define TRAIN_WG_PER_CU 2 // workgroups per CU of k_symbol_count's persistent grid
+#endif
+
+extern "C" int press_hip_symbol_counts(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				       uint64_t total_samples, uint64_t *counts, int device_resident)
+{
+	API_LOCK;
+	int rc = ctx_init();
+	if (rc)
+		return rc;
+	if (nreads == 0)
+		return 0;
+	if (!sig || !off || !n || !counts)
+		return fail(PRESS_HIP_EARG, "NULL argument");
+	hipStream_t s = g.stream();
+	const uint32_t mc = max_chunks_of(total_samples, nreads);
+	int cus = 0;
+	HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g.device));
+	uint32_t grid = (uint32_t) std::max(cus, 1) * TRAIN_WG_PER_CU;
+	if (g.chunks.reserve(train_scratch_bytes(mc)) || g.ctl.reserve(2 * sizeof(ChunkCtl)))
+		return PRESS_HIP_EHIP;
+	uint32_t *nchunks = &((ChunkCtl *) g.ctl.p)->nchunks;
+
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return fail(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		launch_symbol_counts(sig, off, n, nreads, counts, g.chunks.p, nchunks, mc, std::min(grid, mc), s);
+		hipError_t e = hipGetLastError();
+		if (e != hipSuccess)
+			return fail(PRESS_HIP_EHIP, "kernel launch: %s", hipGetErrorString(e));
+		return 0;
+	}
+
+	// host pointers: stage, run, copy the counts back, synchronise
+	uint64_t nch = 0;
+	for (uint32_t r = 0; r < nreads; r++) {
+		if (off[r] & 7)
+			return fail(PRESS_HIP_EARG, "off[%u] = %llu is not a multiple of 8 samples", r,
+				    (unsigned long long) off[r]);
+		if (off[r] + n[r] > total_samples)
+			return fail(PRESS_HIP_EARG, "read %u ends beyond total_samples", r);
+		nch += n[r] >= 2 ? (n[r] + CHUNK - 1) / CHUNK : 0;
+	}
+	if (nch == 0)
+		return 0;
+	if (g.sig.reserve(total_samples * 2 + 64) || g.off.reserve((size_t) nreads * 8) ||
+	    g.nsamp.reserve((size_t) nreads * 4) || g.lens.reserve(257 * 8))
+		return PRESS_HIP_EHIP;
+	HIPCHK(hipMemcpyAsync(g.off.p, off, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(g.nsamp.p, n, (size_t) nreads * 4, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(g.lens.p, counts, 257 * 8, hipMemcpyHostToDevice, s));
+	if ((rc = h2d(g.sig.p, sig, total_samples * 2, s)))
+		return rc;
+	launch_symbol_counts((const int16_t *) g.sig.p, (const uint64_t *) g.off.p, (const uint32_t *) g.nsamp.p, nreads,
+			     (uint64_t *) g.lens.p, g.chunks.p, nchunks, mc, (uint32_t) std::min<uint64_t>(grid, nch), s);
+	hipError_t e = hipGetLastError();
+	if (e != hipSuccess)
+		return fail(PRESS_HIP_EHIP, "kernel launch: %s", hipGetErrorString(e));
+	HIPCHK(hipMemcpyAsync(counts, g.lens.p, 257 * 8, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	return 0;
 }

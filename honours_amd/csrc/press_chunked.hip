@@ -26,6 +26,7 @@
 
 #include "press_internal.h"
 #include "press_packed.h"
+#include "press_wave.h"
 
 namespace ph {
 
@@ -45,27 +46,6 @@ constexpr uint64_t G_MASK = (1ull << 62) - 1;
 constexpr uint64_t CFAIL64 = ~0ull;
 constexpr uint32_t CFAIL32 = 0xFFFFFFFFu;
 
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
-// wave-uniform values: tell the compiler (scalar registers, scalar branches)
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t) __builtin_amdgcn_readfirstlane((int) v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v)
-{
-	return ((uint64_t) uni((uint32_t) (v >> 32)) << 32) | uni((uint32_t) v);
-}
-
-// 16 bytes of a stream that is read once: non-temporal policy (tools/ubench_stream.hip: a read-only sweep reaches
-// 7.1 TB/s with it against 6.3 TB/s with the default policy, a copy 6.0 against 5.2-5.6)
-#ifndef PRESS_NO_NT
-__device__ __forceinline__ uint4 ld16_stream(const void *p)
-{
-	typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-	const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
-	return make_uint4(v.x, v.y, v.z, v.w);
-}
-#else
-__device__ __forceinline__ uint4 ld16_stream(const void *p) { return *reinterpret_cast<const uint4 *>(p); }
-#endif
 // 8 bytes at any byte address of a stream that is read once
 #ifndef PRESS_NO_NT
 __device__ __forceinline__ unsigned long long ld8_stream(const void *p)
@@ -102,23 +82,6 @@ __device__ __forceinline__ uint32_t wave_incl_scan32(uint32_t v)
 			v += t;
 	}
 	return v;
-}
-
-// value of the previous lane (lane 0 receives `lane0`)
-__device__ __forceinline__ uint32_t prev_lane(uint32_t v, uint32_t lane0)
-{
-	// DPP wave_shr:1 - lane l reads lane l-1; lane 0 keeps `old`
-	return (uint32_t) __builtin_amdgcn_update_dpp((int) lane0, (int) v, 0x138, 0xf, 0xf, false);
-}
-
-// zig-zag delta of the two samples packed in `cur`, given the dword holding the two
-// samples before them (trans.c:75,215 on packed 16-bit lanes)
-__device__ __forceinline__ uint32_t zd_pair(uint32_t cur, uint32_t prevdw)
-{
-	const uint32_t sh = __builtin_amdgcn_alignbit(cur, prevdw, 16); // [prev.hi, cur.lo]
-	const s16x2 d = __builtin_bit_cast(s16x2, cur) - __builtin_bit_cast(s16x2, sh);
-	const s16x2 z = (d << 1) ^ (d >> 15);
-	return __builtin_bit_cast(uint32_t, z);
 }
 
 // the same, and which of the two differences do not fit 16 bits (bit 15 / bit 31 of `ov`): slow5lib

@@ -309,5 +309,13 @@ void launch_rcc_encode(const BatchArgs &a, hipStream_t s);  // order 1 (rcc_vbe2
 void launch_rcc_decode(const DecodeArgs &a, hipStream_t s);
 void launch_rcm_encode(const BatchArgs &a, hipStream_t s);  // order 1-0 context mixing (rccm_vbbe21_zd)
 void launch_rcm_decode(const DecodeArgs &a, hipStream_t s);
+// symbol counts of a batch for fitting a Huffman table (press_train.hip): adds into counts[257]; chunks takes
+// train_scratch_bytes(max_chunks), nchunks is one device word (zeroed here)
+uint64_t train_scratch_bytes(uint32_t max_chunks);
+void launch_symbol_counts(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, uint64_t *counts,
+			  void *chunks, uint32_t *nchunks, uint32_t max_chunks, uint32_t grid, hipStream_t s);
+
+// sets press_hip_last_error() (press_abi.hip) and returns code
+int set_error(int code, const char *fmt, ...);
 
 } // namespace ph

@@ -80,7 +80,8 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_blow5_write", "press_hip_blow5_finish", "press_hip_blow5_write_batch", "press_hip_blow5_index",
      "press_hip_blow5_threads",
      "press_hip_shutdown", "press_hip_scratch_buffers", "press_hip_host_alloc", "press_hip_host_free",
-     "press_hip_zstd_host_frames"]))
+     "press_hip_zstd_host_frames", "press_hip_symbol_counts", "press_hip_table_from_counts",
+     "press_hip_write_table_file"]))
 
 
 class PressError(RuntimeError):
@@ -480,6 +481,139 @@ def kernel_times(which):
     lib.press_hip_kernel_times.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
     n = lib.press_hip_kernel_times(which, buf, 128)
     return [buf[i] for i in range(n)]
+
+
+# ---------------------------------------------------------------------------- fitting a Huffman table
+
+NBINS = 257  # the 256 one-byte zd values the shuffman_* methods code, then the exceptions
+
+
+def _train_api(lib):
+    lib.press_hip_symbol_counts.restype = ctypes.c_int
+    lib.press_hip_symbol_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                            ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
+    lib.press_hip_table_from_counts.restype = ctypes.c_int
+    lib.press_hip_table_from_counts.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+    lib.press_hip_write_table_file.restype = ctypes.c_int
+    lib.press_hip_write_table_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+
+
+def symbol_counts(sig, off, n, counts):
+    """Enqueue the counting of a batch on the device, ADDING into counts (CUDA tensors: sig int16, off int64
+    read starts in multiples of 8 samples, n int32 sample counts, counts int64 of NBINS entries holding
+    uint64 values)."""
+    lib = load_library()
+    _train_api(lib)
+    if counts.numel() != NBINS or counts.element_size() != 8 or not counts.is_contiguous():
+        raise PressError("counts must be a contiguous 64-bit tensor of %d entries" % NBINS)
+    rc = lib.press_hip_symbol_counts(sig.data_ptr(), off.data_ptr(), n.data_ptr(), off.numel(), sig.numel(),
+                                     counts.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def symbol_counts_host(reads, counts=None):
+    """Counts of a list of int16 arrays (host buffers, synchronous) -> numpy uint64[NBINS]; added to
+    `counts` when it is given."""
+    lib = load_library()
+    _train_api(lib)
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    out = np.zeros(NBINS, dtype=np.uint64) if counts is None else np.ascontiguousarray(counts, dtype=np.uint64).copy()
+    rc = lib.press_hip_symbol_counts(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total,
+                                     out.ctypes.data, 0)
+    if rc:
+        raise PressError(last_error())
+    return out
+
+
+def table_from_counts(counts, max_bits=24):
+    """The reference's Huffman construction over counts[0..255] (a longer counts array: the rest is ignored),
+    limited to max_bits -> (len uint32[256], bits uint64[256]); bit k of bits[s] is the k-th emitted bit."""
+    lib = load_library()
+    _train_api(lib)
+    c = np.ascontiguousarray(np.asarray(counts, dtype=np.uint64)[:256])
+    if c.size != 256:
+        raise PressError("table_from_counts needs 256 counts")
+    ln = np.zeros(256, dtype=np.uint32)
+    bits = np.zeros(256, dtype=np.uint64)
+    if lib.press_hip_table_from_counts(c.ctypes.data, int(max_bits), ln.ctypes.data, bits.ctypes.data):
+        raise PressError(last_error())
+    return ln, bits
+
+
+def write_table(path, ln, bits, data_bytes):
+    """The table file (the format of NA12878_zd.huffman) that use_table() / press_hip_load_table_file read."""
+    lib = load_library()
+    _train_api(lib)
+    ln = np.ascontiguousarray(ln, dtype=np.uint32)
+    bits = np.ascontiguousarray(bits, dtype=np.uint64)
+    if lib.press_hip_write_table_file(path.encode(), ln.ctypes.data, bits.ctypes.data, int(data_bytes) & 0xFFFFFFFF):
+        raise PressError(last_error())
+
+
+def _blow5_counts(path, counts, max_reads=4096, arena_bytes=1 << 28):
+    """Counts of every read of a BLOW5 file, into the device tensor `counts`: the signal fields go to the device
+    as stored (svb-zd: decoded there by the slow5_svb_zd depress); the samples stay on the device."""
+    import torch
+
+    dev = counts.device
+    rd = Blow5Reader(path)
+    try:
+        arena = np.empty(arena_bytes, dtype=np.uint8)
+        boff = np.zeros(max_reads, dtype=np.uint64)
+        blen = np.zeros(max_reads, dtype=np.uint64)
+        bns = np.zeros(max_reads, dtype=np.uint32)
+        while True:
+            got = rd.next_arena(arena, boff, blen, bns, max_reads)
+            if got == 0:
+                break
+            ns = bns[:got].copy()
+            off, total = _layout(ns)
+            d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+            d_n = torch.from_numpy(ns.view(np.int32)).to(dev)
+            end = int(boff[got - 1] + blen[got - 1])
+            d_sig = torch.zeros(total + 64, dtype=torch.int16, device=dev)
+            if rd.signal_method == 1:
+                d_in = torch.from_numpy(arena[:end + 64].copy()).to(dev)
+                d_in_off = torch.from_numpy(boff[:got].view(np.int64).copy()).to(dev)
+                d_in_len = torch.from_numpy(blen[:got].view(np.int64).copy()).to(dev)
+                d_out_n = torch.zeros(got, dtype=torch.int32, device=dev)
+                depress_batch("slow5_svb_zd", d_in, d_in_off, d_in_len, d_sig, d_off, d_n, d_out_n)
+                symbol_counts(d_sig, d_off, d_n, counts)
+                if not torch.equal(d_out_n, d_n):
+                    raise PressError("a signal of %s does not decode" % path)
+            elif rd.signal_method == 0:  # int16 samples as stored
+                sig = np.zeros(total + 64, dtype=np.int16)
+                for k in range(got):
+                    sig[int(off[k]):int(off[k]) + int(ns[k])] = arena[int(boff[k]):int(boff[k] + blen[k])].view(np.int16)
+                d_sig.copy_(torch.from_numpy(sig))
+                symbol_counts(d_sig, d_off, d_n, counts)
+            else:
+                raise PressError("%s: signal method %d" % (path, rd.signal_method))
+    finally:
+        rd.close()
+
+
+def train_table(src, path, max_bits=24):
+    """Fit a static-Huffman table to `src` (a list of int16 arrays, or the path of a BLOW5 file) and write it to
+    `path` for use_table() / press_hip_load_table_file / the reference's read_code_table.  -> the counts
+    (numpy uint64[NBINS]; counts[256] = the exceptions, which the table does not code)."""
+    if isinstance(src, (str, os.PathLike)):
+        import torch
+
+        use_torch_stream()
+        counts = torch.zeros(NBINS, dtype=torch.int64, device="cuda")
+        _blow5_counts(os.fspath(src), counts)
+        counts = counts.cpu().numpy().view(np.uint64)
+    else:
+        counts = symbol_counts_host(src)
+    ln, bits = table_from_counts(counts, max_bits)
+    write_table(path, ln, bits, int(counts[:256].sum()))
+    return counts
 
 
 # ---------------------------------------------------------------------------- BLOW5 input (host side)

@@ -231,6 +231,27 @@ int press_hip_load_table_file(const char *path);
  * and the shuffman_* drop-in symbols return 1 for such a table. */
 int press_hip_set_table(const uint32_t len[256], const uint64_t bits[256]);
 
+/*
+ * Fitting a table to the caller's reads (press/gen_huffman.c's job, from the samples).
+ * press_hip_symbol_counts ADDS the batch's symbol counts to counts[257]: for each read and i in [1, n[r]),
+ * the zig-zag of the 16-bit wrapped delta s[i] - s[i-1] (the values the shuffman_* methods code):
+ * counts[0..255] the one-byte values, counts[256] the exceptions (values above 255).  Sample 0 of a read
+ * is stored raw and not counted.  Layout and alignment as press_hip_press_batch; device_resident != 0:
+ * device pointers (counts too), the call only enqueues; == 0: host pointers, synchronous.  The counts are
+ * exact integers: the same on every run.
+ */
+int press_hip_symbol_counts(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			    uint64_t total_samples, uint64_t *counts, int device_resident);
+/* The reference's Huffman construction (huffman.c:373 calculate_huffman_codes as gen_huffman runs it) over
+ * counts[0..255]: bit-exact with it whenever its longest code has at most max_bits (8..24) bits; otherwise the
+ * construction over max(1, c >> k) for the first k = 0, 1, 2, ... whose codes fit.  Every symbol gets a code.
+ * Host code, no GPU needed. */
+int press_hip_table_from_counts(const uint64_t counts[256], uint32_t max_bits, uint32_t len[256], uint64_t bits[256]);
+/* write_code_table (huffman.c:440): the file format of press/NA12878_zd.huffman, which read_code_table and
+ * press_hip_load_table_file read; data_bytes goes into the header's "bytes encoded" field (gen_huffman writes
+ * the sum of the counts mod 2^32).  Host code, no GPU needed. */
+int press_hip_write_table_file(const char *path, const uint32_t len[256], const uint64_t bits[256], uint32_t data_bytes);
+
 /* X_bound of the reference for `method` (what press/test.c allocates) */
 uint64_t press_hip_bound(int method, uint32_t n);
 
