@@ -1127,6 +1127,32 @@ static int check_method(int method)
 	return 0;
 }
 
+// EARG unless the sample ranges [off[r], off[r] + n[r]) of the non-empty reads are pairwise disjoint (host
+// pointers only: the check reads off and n).  Press keeps per-read scratch at the read's sample offset, depress
+// writes the read's samples there.  `order` returns the reads in ascending offset order.
+static int check_disjoint(const uint64_t *off, const uint32_t *n, uint32_t nreads, const char *what,
+			  std::vector<uint32_t> &order)
+{
+	order.resize(nreads);
+	bool sorted = true;
+	for (uint32_t r = 0; r < nreads; r++) {
+		order[r] = r;
+		sorted = sorted && (r == 0 || off[r] >= off[r - 1]);
+	}
+	if (!sorted)
+		std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return off[x] < off[y]; });
+	uint64_t end = 0;
+	for (uint32_t i = 0; i < nreads; i++) {
+		const uint32_t r = order[i];
+		if (n[r] == 0)
+			continue;
+		if (off[r] < end)
+			return fail(PRESS_HIP_EARG, "%s of read %u overlaps another read's", what, r);
+		end = off[r] + n[r];
+	}
+	return 0;
+}
+
 extern "C" int press_hip_press_batch(int method, const int16_t *sig, const uint64_t *off, const uint32_t *n,
 				     uint32_t nreads, uint64_t total_samples, uint8_t *out,
 				     const uint64_t *out_off, uint64_t *out_len, int device_resident)
@@ -1184,6 +1210,11 @@ extern "C" int press_hip_press_batch(int method, const int16_t *sig, const uint6
 			return fail(PRESS_HIP_EARG, "read %u ends beyond total_samples", r);
 		if (out_off[r + 1] < out_off[r])
 			return fail(PRESS_HIP_EARG, "out_off must be non-decreasing");
+	}
+	{
+		std::vector<uint32_t> order;
+		if ((rc = check_disjoint(off, n, nreads, "the sample range", order)))
+			return rc;
 	}
 	const uint64_t a0 = out_off[0], a1 = out_off[nreads];
 	if (g.sig.reserve(total_samples * 2 + 64) || g.off.reserve((size_t) nreads * 8) ||
@@ -1385,6 +1416,9 @@ extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint
 			pc.push_back({ const_cast<uint8_t *>(in) + in_off[r], dense, in_len[r] });
 		dense += in_len[r];
 	}
+	std::vector<uint32_t> order; // the reads in ascending slot order (for the staged copy back)
+	if ((rc = check_disjoint(off, n, nreads, "the sample room", order)))
+		return rc;
 	if (g.sig.reserve(total_samples * 2 + 64) || g.off.reserve((size_t) nreads * 8) ||
 	    g.nsamp.reserve((size_t) nreads * 4) || g.arena.reserve(dense + 64) || g.arena_off.reserve((size_t) nreads * 8) ||
 	    g.lens2.reserve((size_t) nreads * 8) || g.outn.reserve((size_t) nreads * 4))
@@ -1422,23 +1456,16 @@ extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint
 		return 0;
 	}
 	// only the decoded samples of every read reach the caller's buffer (its padding between the
-	// reads is left alone); reads in ascending slot order for the staged copy
-	std::vector<uint32_t> order(nreads);
-	for (uint32_t r = 0; r < nreads; r++)
-		order[r] = r;
-	bool sorted = true;
-	for (uint32_t r = 1; r < nreads && sorted; r++)
-		sorted = off[r] >= off[r - 1];
-	if (!sorted)
-		std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return off[x] < off[y]; });
+	// reads is left alone); reads in ascending slot order for the staged copy (the rooms are disjoint, and
+	// out_n[r] <= n[r])
 	pc.clear();
 	uint64_t end = 0;
 	for (uint32_t i = 0; i < nreads; i++) {
 		const uint32_t r = order[i];
 		if (out_n[r] == UINT32_MAX || out_n[r] == 0)
 			continue;
-		if (off[r] * 2 < end)
-			return fail(PRESS_HIP_EARG, "sample slots overlap");
+		if (out_n[r] > n[r])
+			return fail(PRESS_HIP_EHIP, "read %u decoded %u samples into a room of %u", r, out_n[r], n[r]);
 		pc.push_back({ (uint8_t *) (sig + off[r]), off[r] * 2, (uint64_t) out_n[r] * 2 });
 		end = (off[r] + out_n[r]) * 2;
 	}

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void k_chunk_prep(const uint64_t *off, const u
 						    uint32_t nreads, ChunkDesc *chunks, uint64_t *gran,
 						    ChunkCtl *ctl, uint32_t max_chunks, uint64_t *out_len,
 						    uint32_t *out_n, uint32_t *first_chunk, ReadMeta *meta = nullptr,
-						    const uint8_t *in = nullptr, uint32_t hdr = 0)
+						    const uint8_t *in = nullptr, uint32_t hdr = 0, uint8_t *out = nullptr)
 {
 	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
 	uint32_t n = 0, nch = 0;
@@ -226,11 +226,19 @@ __global__ __launch_bounds__(256) void k_chunk_prep(const uint64_t *off, const u
 			ok = ((uint32_t) h[0] | ((uint32_t) h[1] << 8) | ((uint32_t) h[2] << 16) | ((uint32_t) h[3] << 24)) == n;
 		}
 	}
+	// an empty read has no chunk: its verdict is given here.  With a header (slow5 svb-zd) the stream is the
+	// count alone (slow5_press.c:1046), and a stream of any other length is refused (slow5_press.c:1098)
 	if (n == 0) {
-		if (!DEC)
-			out_len[r] = 0;
-		else
-			out_n[r] = 0;
+		if (!DEC) {
+			if (hdr) {
+				ok = hdr <= slot_off[r + 1] - sbase;
+				for (uint32_t b = 0; ok && b < hdr; b++)
+					out[sbase + b] = 0;
+			}
+			out_len[r] = ok ? hdr : CFAIL64;
+		} else {
+			out_n[r] = ok && (!hdr || in_len[r] == hdr) ? 0u : CFAIL32;
+		}
 	}
 	const uint64_t o = off[r];
 	if (first_chunk)
@@ -2122,7 +2130,7 @@ static void run_encode(const BatchArgs &a, hipStream_t s)
 	hipLaunchKernelGGL((k_chunk_prep<false, KEY2>), dim3((a.nreads + 255) / 256), dim3(256), 0, s, a.off,
 			   a.nsamp, a.out_off, (const uint64_t *) nullptr, a.nreads, a.chunks, a.gran, a.ctl,
 			   a.max_chunks, a.out_len, (uint32_t *) nullptr, a.first_chunk, (ReadMeta *) nullptr,
-			   (const uint8_t *) nullptr, S5 ? 4u : 0u);
+			   (const uint8_t *) nullptr, S5 ? 4u : 0u, a.out);
 	// persistent grid: as many workgroups as are resident (4 per CU)
 	const uint32_t grid = a.max_chunks < PERSISTENT_GRID ? a.max_chunks : PERSISTENT_GRID;
 	ktime_begin(0, s);

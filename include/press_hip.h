@@ -236,7 +236,8 @@ int press_hip_set_table(const uint32_t len[256], const uint64_t bits[256]);
  * press_hip_symbol_counts ADDS the batch's symbol counts to counts[257]: for each read and i in [1, n[r]),
  * the zig-zag of the 16-bit wrapped delta s[i] - s[i-1] (the values the shuffman_* methods code):
  * counts[0..255] the one-byte values, counts[256] the exceptions (values above 255).  Sample 0 of a read
- * is stored raw and not counted.  Layout and alignment as press_hip_press_batch; device_resident != 0:
+ * is stored raw and not counted.  Layout and alignment as press_hip_press_batch, except that reads may
+ * overlap or repeat (the counter only reads them: a read listed twice is counted twice); device_resident != 0:
  * device pointers (counts too), the call only enqueues; == 0: host pointers, synchronous.  The counts are
  * exact integers: the same on every run.
  */
@@ -252,21 +253,48 @@ int press_hip_table_from_counts(const uint64_t counts[256], uint32_t max_bits, u
  * the sum of the counts mod 2^32).  Host code, no GPU needed. */
 int press_hip_write_table_file(const char *path, const uint32_t len[256], const uint64_t bits[256], uint32_t data_bytes);
 
-/* X_bound of the reference for `method` (what press/test.c allocates) */
+/* X_bound of the reference for `method` (what press/test.c allocates).  For n = 0 the exception, Huffman,
+ * ex-zd and range-coder methods give the reference's own n - 1 wrap-around (press.c:3411): 8 589 934 593
+ * bytes.  It stays so for the drop-in symbols; it is not a size for an empty read's slot (see below). */
 uint64_t press_hip_bound(int method, uint32_t n);
 
 /*
  * Compress nreads reads.
  *   sig      int16 samples; read r = sig[off[r] .. off[r]+n[r]).  off (nreads entries)
  *            must be multiples of 8 samples and sig 16-byte aligned: every sample load
- *            is a coalesced 16-byte access
+ *            is a coalesced 16-byte access.  Reads may lie anywhere in sig, in any order
+ *            and with gaps of anything between them, but their sample ranges must not
+ *            overlap: per-read scratch (the exception lists, the range coders' byte
+ *            streams) is placed at the read's sample offset off[r].  The host path refuses
+ *            overlapping reads (PRESS_HIP_EARG) before anything is launched; the
+ *            device-resident path cannot read off[] and takes it as a precondition.
+ *            Empty reads (n[r] = 0) overlap nothing.
  *   n        samples per read (nreads entries)
  *   total_samples  extent of sig in samples: max(off[r]+n[r]) rounded up as the caller
  *            likes; sizes the library's scratch (with device-resident offsets the
  *            library cannot read them without a synchronisation)
  *   out      output arena; read r may use out[out_off[r] .. out_off[r+1]) - its
- *            capacity; out_off has nreads+1 entries
+ *            capacity; out_off has nreads+1 entries, non-decreasing, each any byte
+ *            offset (no alignment; 64-bit: arenas past 4 GiB are fine).  Nothing outside
+ *            the slots is written, and a failed read leaves its neighbours alone.
+ *            The smallest slot a read takes:
+ *              svb12, svb12_zd, svb_zd, slow5_svb_zd: the format's worst case, checked up
+ *                front - h + k + w * n with keys k = ceil(n / 8) (svb12, svb12_zd) or
+ *                ceil(n / 4) (svb_zd, slow5_svb_zd), h = 4 and w = 3 for slow5_svb_zd
+ *                (the u32 count; a 32-bit delta may take 3 bytes), h = 0 and w = 2 else;
+ *              the exception, Huffman, ex-zd and range-coder methods: the stream's own
+ *                length (the reference's bytes; a range-coder stream stored raw included);
+ *              the zstd kinds: the frame's own length.
+ *            press_hip_bound(m, n) is the reference's X_bound: too small for
+ *            exception-heavy reads (press.c:2575), and 8 GiB for n = 0 (above).
  *   out_len  per read: bytes produced, or PRESS_HIP_FAILED (capacity too small, ...)
+ * An empty read (n[r] = 0) gives, as the reference does:
+ *   svb12, svb12_zd, svb_zd: an empty stream (0 bytes);
+ *   slow5_svb_zd: its u32 count alone, 00 00 00 00 (slow5_press.c:1046), PRESS_HIP_FAILED
+ *     in a slot under 4 bytes;
+ *   the zstd kinds over svb: a frame holding the u32 count 0;
+ *   the exception, Huffman, ex-zd and range-coder methods, and zstd over ex-zd:
+ *     PRESS_HIP_FAILED (the reference refuses n = 0).
  * device_resident != 0: every pointer is a device pointer, the call only enqueues
  * work on the current stream (no synchronisation; scratch is (re)allocated only when a
  * batch is larger than any before it); == 0: host pointers, synchronous.
@@ -277,11 +305,25 @@ int press_hip_press_batch(int method, const int16_t *sig, const uint64_t *off, c
 
 /*
  * Decompress nreads streams.
- *   in/in_off/in_len  stream r = in[in_off[r] .. in_off[r]+in_len[r])
+ *   in/in_off/in_len  stream r = in[in_off[r] .. in_off[r]+in_len[r]); in_off any byte
+ *                     offset, streams in any order, and 64 readable bytes behind the
+ *                     last stream (the decoders load whole words)
  *   sig/off/n         output layout as above; n[r] is the room for read r in samples
  *                     AND, for the svb methods, the sample count (their streams do
- *                     not carry it, press.c:1689)
+ *                     not carry it, press.c:1689).  For the formats that carry their
+ *                     own count the room may be larger than the read.  The rooms
+ *                     [off[r], off[r] + n[r]) must not overlap: the host path refuses
+ *                     overlapping rooms (PRESS_HIP_EARG) before anything is launched,
+ *                     whatever nreads; device resident, it is a precondition.
+ *                     Samples are written to [off[r], off[r] + roundup8(n[r])) at most
+ *                     (device resident) or [off[r], off[r] + out_n[r]) (host buffers;
+ *                     page-locked ones: see the note on press_hip_host_alloc)
  *   out_n             per read: samples decoded, or UINT32_MAX on a malformed stream
+ * An empty read: slow5_svb_zd takes exactly the 4-byte count 0 and refuses any other stream
+ * for n = 0 (the reference needs the count, slow5_press.c:1086, 1098).  svb12, svb12_zd
+ * and svb_zd give 0 samples for n = 0 whatever the stream, as the reference does (their
+ * streams carry no count).  The other methods decode what the stream holds, into a room
+ * of n[r] samples.
  */
 int press_hip_depress_batch(int method, const uint8_t *in, const uint64_t *in_off,
 			    const uint64_t *in_len, uint32_t nreads, int16_t *sig,
