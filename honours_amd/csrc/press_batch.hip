@@ -1,0 +1,540 @@
+// press_batch.hip - the batch entry points of include/press_hip.h (press, depress, symbol counts) and the page-locked
+// staging engine behind their host-pointer form.
+
+#include <algorithm>
+#include <thread>
+#include <vector>
+
+#include "press_host.h"
+
+using namespace ph;
+
+// ------------------------------------------------------------------ host <-> device staging
+//
+// The host-pointer form of the batch calls (device_resident = 0) is what a caller like
+// press/test.c uses: its buffers are ordinary (pageable) memory.  Copies go through two
+// page-locked staging buffers of STAGE_BYTES: while the DMA engine moves one, the host fills
+// (or drains) the other, several threads sharing the memcpy.  Buffers obtained from
+// press_hip_host_alloc() are page-locked themselves and are copied by ONE DMA, no staging.
+// Compressed streams travel densely: a gather kernel packs the slots' contents before the
+// D2H (slots are sized by X_bound, several times their content), and the decoder's input is
+// packed on the host while it is staged.
+
+namespace {
+
+constexpr size_t STAGE_BYTES = 32u << 20;
+constexpr size_t DIRECT_MAX = 256u << 10; // below this a plain hipMemcpyAsync (HIP's own staging) is cheaper
+
+struct Staging {
+	void *buf[2] = { nullptr, nullptr };
+	hipEvent_t ev[2];
+	bool busy[2] = { false, false };
+	bool made = false;
+} stg;
+
+int staging_init()
+{
+	if (stg.made)
+		return 0;
+	for (int k = 0; k < 2; k++) {
+		HIPCHK(hipHostMalloc(&stg.buf[k], STAGE_BYTES, hipHostMallocDefault));
+		HIPCHK(hipEventCreateWithFlags(&stg.ev[k], hipEventDisableTiming));
+	}
+	stg.made = true;
+	return 0;
+}
+
+} // namespace
+
+void ph::staging_release()
+{
+	if (!stg.made)
+		return;
+	for (int k = 0; k < 2; k++) {
+		(void) hipEventDestroy(stg.ev[k]);
+		(void) hipHostFree(stg.buf[k]);
+		stg.buf[k] = nullptr;
+		stg.busy[k] = false;
+	}
+	stg.made = false;
+}
+
+namespace {
+
+int staging_wait(int k)
+{
+	if (stg.busy[k]) {
+		HIPCHK(hipEventSynchronize(stg.ev[k]));
+		stg.busy[k] = false;
+	}
+	return 0;
+}
+
+bool is_pinned(const void *p)
+{
+	hipPointerAttribute_t a;
+	if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+		(void) hipGetLastError(); // ordinary memory is reported as an error: not one of ours
+		return false;
+	}
+	return a.type == hipMemoryTypeHost;
+}
+
+// memcpy shared by a few threads (one core moves ~10 GB/s, the link 50+)
+void par_memcpy(void *dst, const void *src, size_t n)
+{
+	constexpr size_t MIN_PART = 2u << 20;
+	unsigned nt = (unsigned) (n / MIN_PART);
+	if (nt > 6)
+		nt = 6;
+	if (nt < 2) {
+		memcpy(dst, src, n);
+		return;
+	}
+	const size_t part = (n / nt + 63) & ~(size_t) 63;
+	std::vector<std::thread> th;
+	for (unsigned t = 1; t < nt; t++) {
+		const size_t o = (size_t) t * part;
+		if (o >= n)
+			break;
+		const size_t l = o + part > n ? n - o : part;
+		th.emplace_back([=] { memcpy((char *) dst + o, (const char *) src + o, l); });
+	}
+	memcpy(dst, src, part < n ? part : n);
+	for (auto &t : th)
+		t.join();
+}
+
+// host -> device, asynchronous on s as far as the source allows (returns when src may be reused
+// unless src is page-locked)
+int h2d(void *dst, const void *src, size_t n, hipStream_t s)
+{
+	if (!n)
+		return 0;
+	if (n <= DIRECT_MAX || is_pinned(src)) {
+		HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s));
+		return 0;
+	}
+	int rc = staging_init();
+	if (rc)
+		return rc;
+	int k = 0;
+	for (size_t o = 0; o < n; o += STAGE_BYTES, k ^= 1) {
+		const size_t l = n - o < STAGE_BYTES ? n - o : STAGE_BYTES;
+		if ((rc = staging_wait(k)))
+			return rc;
+		par_memcpy(stg.buf[k], (const char *) src + o, l);
+		HIPCHK(hipMemcpyAsync((char *) dst + o, stg.buf[k], l, hipMemcpyHostToDevice, s));
+		HIPCHK(hipEventRecord(stg.ev[k], s));
+		stg.busy[k] = true;
+	}
+	return 0;
+}
+
+// Pieces of host memory <-> one dense device range, through the staging buffers.
+struct Piece {
+	uint8_t *host;   // where the piece lives on the host
+	uint64_t dense;  // its offset in the dense range
+	uint64_t len;
+};
+
+// pieces must be sorted by `dense` and must not overlap.  TO_DEV: host pieces -> dev[0, total);
+// else dev[0, total) -> host pieces.  Synchronous for the host memory involved.
+template <bool TO_DEV>
+int staged_pieces(uint8_t *dev, uint64_t total, const std::vector<Piece> &pc, hipStream_t s)
+{
+	if (!total)
+		return 0;
+	int rc = staging_init();
+	if (rc)
+		return rc;
+	size_t ip = 0; // first piece that may reach into the current chunk
+	auto host_side = [&](int k, uint64_t o, uint64_t l) { // move the pieces' bytes of chunk [o, o + l)
+		while (ip < pc.size() && pc[ip].dense + pc[ip].len <= o)
+			ip++;
+		for (size_t i = ip; i < pc.size() && pc[i].dense < o + l; i++) {
+			const uint64_t a = pc[i].dense > o ? pc[i].dense : o;
+			const uint64_t b = pc[i].dense + pc[i].len < o + l ? pc[i].dense + pc[i].len : o + l;
+			if (b <= a)
+				continue;
+			uint8_t *h = pc[i].host + (a - pc[i].dense);
+			uint8_t *g = (uint8_t *) stg.buf[k] + (a - o);
+			if (TO_DEV)
+				par_memcpy(g, h, b - a);
+			else
+				par_memcpy(h, g, b - a);
+		}
+	};
+	int k = 0;
+	if (TO_DEV) {
+		for (uint64_t o = 0; o < total; o += STAGE_BYTES, k ^= 1) {
+			const uint64_t l = total - o < STAGE_BYTES ? total - o : STAGE_BYTES;
+			if ((rc = staging_wait(k)))
+				return rc;
+			host_side(k, o, l);
+			HIPCHK(hipMemcpyAsync(dev + o, stg.buf[k], l, hipMemcpyHostToDevice, s));
+			HIPCHK(hipEventRecord(stg.ev[k], s));
+			stg.busy[k] = true;
+		}
+		return 0;
+	}
+	// device -> host: the DMA of chunk i+1 runs while the host drains chunk i
+	uint64_t po = 0, pl = 0;
+	int pk = -1;
+	for (uint64_t o = 0; o < total; o += STAGE_BYTES, k ^= 1) {
+		const uint64_t l = total - o < STAGE_BYTES ? total - o : STAGE_BYTES;
+		if ((rc = staging_wait(k)))
+			return rc;
+		HIPCHK(hipMemcpyAsync(stg.buf[k], dev + o, l, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipEventRecord(stg.ev[k], s));
+		stg.busy[k] = true;
+		if (pk >= 0) {
+			if ((rc = staging_wait(pk)))
+				return rc;
+			host_side(pk, po, pl);
+		}
+		pk = k;
+		po = o;
+		pl = l;
+	}
+	if (pk >= 0) {
+		if ((rc = staging_wait(pk)))
+			return rc;
+		host_side(pk, po, pl);
+	}
+	return 0;
+}
+
+// dense[dense_off[r] ..) = arena[slot_off[r] .. + len[r]) - the streams of a batch packed back to back
+// (16-byte aligned) for ONE copy to the host.  One workgroup per (read, 1/8 of its 4-KiB pieces).
+__global__ __launch_bounds__(256) void k_gather_streams(const uint8_t *arena, const uint64_t *slot_off,
+							const uint64_t *len, const uint64_t *dense_off, uint8_t *dense)
+{
+	const uint32_t r = blockIdx.x;
+	const uint64_t l = len[r];
+	if (l == PRESS_HIP_FAILED || l == 0)
+		return;
+	const uint8_t *src = arena + slot_off[r];
+	uint8_t *dst = dense + dense_off[r];
+	const uint64_t n16 = l / 16;
+	for (uint64_t c = (uint64_t) blockIdx.y * 256 + threadIdx.x; c < n16; c += 256ull * gridDim.y) {
+		uint4 v;
+		__builtin_memcpy(&v, src + 16 * c, 16); // the slot may sit at any byte address
+		*reinterpret_cast<uint4 *>(dst + 16 * c) = v;
+	}
+	if (blockIdx.y == 0 && threadIdx.x < (l & 15))
+		dst[16 * n16 + threadIdx.x] = src[16 * n16 + threadIdx.x];
+}
+
+} // namespace
+
+// EARG unless the sample ranges [off[r], off[r] + n[r]) of the non-empty reads are pairwise disjoint (host
+// pointers only: the check reads off and n).  Press keeps per-read scratch at the read's sample offset, depress
+// writes the read's samples there.  `order` returns the reads in ascending offset order.
+static int check_disjoint(const uint64_t *off, const uint32_t *n, uint32_t nreads, const char *what,
+			  std::vector<uint32_t> &order)
+{
+	order.resize(nreads);
+	bool sorted = true;
+	for (uint32_t r = 0; r < nreads; r++) {
+		order[r] = r;
+		sorted = sorted && (r == 0 || off[r] >= off[r - 1]);
+	}
+	if (!sorted)
+		std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return off[x] < off[y]; });
+	uint64_t end = 0;
+	for (uint32_t i = 0; i < nreads; i++) {
+		const uint32_t r = order[i];
+		if (n[r] == 0)
+			continue;
+		if (off[r] < end)
+			return set_error(PRESS_HIP_EARG, "%s of read %u overlaps another read's", what, r);
+		end = off[r] + n[r];
+	}
+	return 0;
+}
+
+// The head of every host-pointer call: the sample layout checked, room for sig, off and n on the device, off and n
+// on their way there.
+static int stage_layout(const uint64_t *off, const uint32_t *n, uint32_t nreads, uint64_t total_samples, hipStream_t s)
+{
+	for (uint32_t r = 0; r < nreads; r++) {
+		if (off[r] & 7)
+			return set_error(PRESS_HIP_EARG, "off[%u] = %llu is not a multiple of 8 samples", r,
+					 (unsigned long long) off[r]);
+		if (off[r] + n[r] > total_samples)
+			return set_error(PRESS_HIP_EARG, "read %u ends beyond total_samples", r);
+	}
+	if (g.sig.reserve(total_samples * 2 + 64) || g.off.reserve((size_t) nreads * 8) || g.nsamp.reserve((size_t) nreads * 4))
+		return PRESS_HIP_EHIP;
+	HIPCHK(hipMemcpyAsync(g.off.p, off, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(g.nsamp.p, n, (size_t) nreads * 4, hipMemcpyHostToDevice, s));
+	return 0;
+}
+
+extern "C" int press_hip_press_batch(int method, const int16_t *sig, const uint64_t *off, const uint32_t *n,
+				     uint32_t nreads, uint64_t total_samples, uint8_t *out,
+				     const uint64_t *out_off, uint64_t *out_len, int device_resident)
+{
+	API_ENTER;
+	int rc = check_method(method);
+	if (rc)
+		return rc;
+	if (nreads == 0)
+		return 0;
+	if (!sig || !off || !n || !out || !out_off || !out_len)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_plan(method, total_samples, nreads, false);
+	if ((rc = plan.reserve()))
+		return rc;
+	BatchArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		a.sig = sig;
+		a.off = off;
+		a.nsamp = n;
+		a.out = out;
+		a.out_off = out_off;
+		a.out_len = out_len;
+		return launch_press(plan, a, s);
+	}
+
+	// host pointers: stage, run, copy back, synchronise
+	for (uint32_t r = 0; r < nreads; r++)
+		if (out_off[r + 1] < out_off[r])
+			return set_error(PRESS_HIP_EARG, "out_off must be non-decreasing");
+	{
+		std::vector<uint32_t> order;
+		if ((rc = check_disjoint(off, n, nreads, "the sample range", order)))
+			return rc;
+	}
+	if ((rc = stage_layout(off, n, nreads, total_samples, s)))
+		return rc;
+	const uint64_t a0 = out_off[0], a1 = out_off[nreads];
+	if (g.arena.reserve(a1 - a0 + 64) || g.arena_off.reserve(((size_t) nreads + 1) * 8) || g.lens.reserve((size_t) nreads * 8))
+		return PRESS_HIP_EHIP;
+	std::vector<uint64_t> rel(nreads + 1);
+	for (uint32_t r = 0; r <= nreads; r++)
+		rel[r] = out_off[r] - a0;
+	HIPCHK(hipMemcpyAsync(g.arena_off.p, rel.data(), ((size_t) nreads + 1) * 8, hipMemcpyHostToDevice, s));
+	if ((rc = h2d(g.sig.p, sig, total_samples * 2, s)))
+		return rc;
+	a.sig = (const int16_t *) g.sig.p;
+	a.off = (const uint64_t *) g.off.p;
+	a.nsamp = (const uint32_t *) g.nsamp.p;
+	a.out = (uint8_t *) g.arena.p;
+	a.out_off = (const uint64_t *) g.arena_off.p;
+	a.out_len = (uint64_t *) g.lens.p;
+	if ((rc = launch_press(plan, a, s)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(out_len, g.lens.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (nreads <= 4) { // per-read calls: one small copy each
+		for (uint32_t r = 0; r < nreads; r++) {
+			if (out_len[r] == PRESS_HIP_FAILED || out_len[r] == 0)
+				continue;
+			HIPCHK(hipMemcpyAsync(out + out_off[r], (uint8_t *) g.arena.p + rel[r], out_len[r],
+					      hipMemcpyDeviceToHost, s));
+		}
+		HIPCHK(hipStreamSynchronize(s));
+		return 0;
+	}
+	// the streams packed back to back on the device, ONE pass over the link, scattered into the
+	// caller's slots by the host
+	std::vector<uint64_t> doff(nreads);
+	std::vector<Piece> pc;
+	pc.reserve(nreads);
+	uint64_t dense = 0;
+	for (uint32_t r = 0; r < nreads; r++) {
+		doff[r] = dense;
+		if (out_len[r] == PRESS_HIP_FAILED || out_len[r] == 0)
+			continue;
+		pc.push_back({ out + out_off[r], dense, out_len[r] });
+		dense += (out_len[r] + 15) & ~15ull;
+	}
+	if (!dense)
+		return 0;
+	if (g.dense.reserve(dense + 64) || g.dense_off.reserve((size_t) nreads * 8))
+		return PRESS_HIP_EHIP;
+	HIPCHK(hipMemcpyAsync(g.dense_off.p, doff.data(), (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	hipLaunchKernelGGL(k_gather_streams, dim3(nreads, 8), dim3(256), 0, s, (const uint8_t *) g.arena.p,
+			   (const uint64_t *) g.arena_off.p, (const uint64_t *) g.lens.p, (const uint64_t *) g.dense_off.p,
+			   (uint8_t *) g.dense.p);
+	if ((rc = staged_pieces<false>((uint8_t *) g.dense.p, dense, pc, s)))
+		return rc;
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
+#ifndef TRAIN_WG_PER_CU
+#define TRAIN_WG_PER_CU 2 // workgroups per CU of k_symbol_count's persistent grid
+#endif
+
+extern "C" int press_hip_symbol_counts(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				       uint64_t total_samples, uint64_t *counts, int device_resident)
+{
+	API_ENTER;
+	int rc;
+	if (nreads == 0)
+		return 0;
+	if (!sig || !off || !n || !counts)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	hipStream_t s = g.stream();
+	const uint32_t mc = (uint32_t) (total_samples / CHUNK + nreads + 1); // (as ScratchPlan::max_chunks)
+	int cus = 0;
+	HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g.device));
+	uint32_t grid = (uint32_t) std::max(cus, 1) * TRAIN_WG_PER_CU;
+	if (g.chunks.reserve(train_scratch_bytes(mc)) || g.ctl.reserve(2 * sizeof(ChunkCtl)))
+		return PRESS_HIP_EHIP;
+	uint32_t *nchunks = &((ChunkCtl *) g.ctl.p)->nchunks;
+
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		launch_symbol_counts(sig, off, n, nreads, counts, g.chunks.p, nchunks, mc, std::min(grid, mc), s);
+		return launch_status();
+	}
+
+	// host pointers: stage, run, copy the counts back, synchronise
+	if ((rc = stage_layout(off, n, nreads, total_samples, s)))
+		return rc;
+	uint64_t nch = 0;
+	for (uint32_t r = 0; r < nreads; r++)
+		nch += n[r] >= 2 ? (n[r] + CHUNK - 1) / CHUNK : 0;
+	if (nch == 0)
+		return 0;
+	if (g.lens.reserve(257 * 8))
+		return PRESS_HIP_EHIP;
+	HIPCHK(hipMemcpyAsync(g.lens.p, counts, 257 * 8, hipMemcpyHostToDevice, s));
+	if ((rc = h2d(g.sig.p, sig, total_samples * 2, s)))
+		return rc;
+	launch_symbol_counts((const int16_t *) g.sig.p, (const uint64_t *) g.off.p, (const uint32_t *) g.nsamp.p, nreads,
+			     (uint64_t *) g.lens.p, g.chunks.p, nchunks, mc, (uint32_t) std::min<uint64_t>(grid, nch), s);
+	if ((rc = launch_status()))
+		return rc;
+	HIPCHK(hipMemcpyAsync(counts, g.lens.p, 257 * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
+extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint64_t *in_off,
+				       const uint64_t *in_len, uint32_t nreads, int16_t *sig,
+				       const uint64_t *off, const uint32_t *n, uint64_t total_samples,
+				       uint32_t *out_n, int device_resident)
+{
+	API_ENTER;
+	int rc = check_method(method);
+	if (rc)
+		return rc;
+	if (nreads == 0)
+		return 0;
+	if (!in || !in_off || !in_len || !sig || !off || !n || !out_n)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_plan(method, total_samples, nreads, true);
+	if ((rc = plan.reserve()))
+		return rc;
+	DecodeArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		a.in = in;
+		a.in_off = in_off;
+		a.in_len = in_len;
+		a.sig = sig;
+		a.off = off;
+		a.nsamp = n;
+		a.out_n = out_n;
+		return launch_depress(plan, a, s);
+	}
+
+	uint64_t dense = 0;
+	std::vector<uint64_t> doff(nreads);
+	std::vector<Piece> pc;
+	pc.reserve(nreads);
+	for (uint32_t r = 0; r < nreads; r++) {
+		doff[r] = dense;
+		if (in_len[r])
+			pc.push_back({ const_cast<uint8_t *>(in) + in_off[r], dense, in_len[r] });
+		dense += in_len[r];
+	}
+	std::vector<uint32_t> order; // the reads in ascending slot order (for the staged copy back)
+	if ((rc = check_disjoint(off, n, nreads, "the sample room", order)))
+		return rc;
+	if ((rc = stage_layout(off, n, nreads, total_samples, s)))
+		return rc;
+	if (g.arena.reserve(dense + 64) || g.arena_off.reserve((size_t) nreads * 8) || g.lens2.reserve((size_t) nreads * 8) ||
+	    g.outn.reserve((size_t) nreads * 4))
+		return PRESS_HIP_EHIP;
+	HIPCHK(hipMemcpyAsync(g.arena_off.p, doff.data(), (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(g.lens2.p, in_len, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	// the streams, packed back to back while they are staged (the caller's slots may be far apart)
+	if (nreads <= 4) {
+		for (const Piece &q : pc)
+			HIPCHK(hipMemcpyAsync((uint8_t *) g.arena.p + q.dense, q.host, q.len, hipMemcpyHostToDevice, s));
+	} else if ((rc = staged_pieces<true>((uint8_t *) g.arena.p, dense, pc, s))) {
+		return rc;
+	}
+	a.in = (const uint8_t *) g.arena.p;
+	a.in_off = (const uint64_t *) g.arena_off.p;
+	a.in_len = (const uint64_t *) g.lens2.p;
+	a.sig = (int16_t *) g.sig.p;
+	a.off = (const uint64_t *) g.off.p;
+	a.nsamp = (const uint32_t *) g.nsamp.p;
+	a.out_n = (uint32_t *) g.outn.p;
+	if ((rc = launch_depress(plan, a, s)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	if (nreads <= 4) {
+		for (uint32_t r = 0; r < nreads; r++) {
+			if (out_n[r] == UINT32_MAX || out_n[r] == 0)
+				continue;
+			HIPCHK(hipMemcpyAsync(sig + off[r], (int16_t *) g.sig.p + off[r], (size_t) out_n[r] * 2,
+					      hipMemcpyDeviceToHost, s));
+		}
+		HIPCHK(hipStreamSynchronize(s));
+		return 0;
+	}
+	// only the decoded samples of every read reach the caller's buffer (its padding between the
+	// reads is left alone); reads in ascending slot order for the staged copy (the rooms are disjoint, and
+	// out_n[r] <= n[r])
+	pc.clear();
+	uint64_t end = 0;
+	for (uint32_t i = 0; i < nreads; i++) {
+		const uint32_t r = order[i];
+		if (out_n[r] == UINT32_MAX || out_n[r] == 0)
+			continue;
+		if (out_n[r] > n[r])
+			return set_error(PRESS_HIP_EHIP, "read %u decoded %u samples into a room of %u", r, out_n[r], n[r]);
+		pc.push_back({ (uint8_t *) (sig + off[r]), off[r] * 2, (uint64_t) out_n[r] * 2 });
+		end = (off[r] + out_n[r]) * 2;
+	}
+	if (is_pinned(sig)) { // page-locked: the decoded ranges go straight to the caller, one DMA per run of reads
+		size_t i = 0;
+		while (i < pc.size()) {
+			size_t k = i;
+			// reads whose gaps are only the alignment padding travel together (the padding is overwritten)
+			while (k + 1 < pc.size() && pc[k + 1].dense - (pc[k].dense + pc[k].len) < 128)
+				k++;
+			const uint64_t b0 = pc[i].dense, b1 = pc[k].dense + pc[k].len;
+			HIPCHK(hipMemcpyAsync((uint8_t *) sig + b0, (uint8_t *) g.sig.p + b0, b1 - b0, hipMemcpyDeviceToHost, s));
+			i = k + 1;
+		}
+		HIPCHK(hipStreamSynchronize(s));
+		return 0;
+	}
+	if ((rc = staged_pieces<false>((uint8_t *) g.sig.p, end, pc, s)))
+		return rc;
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+

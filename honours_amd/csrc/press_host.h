@@ -1,0 +1,194 @@
+// press_host.h - shared between the host-side units of libpress_hip.so (press_ctx, press_methods,
+// press_batch, press_table, press_dropin .hip).  Host only: the kernel files include press_internal.h alone.
+#pragma once
+
+#include <stdio.h>
+#include <string.h>
+
+#include <mutex>
+
+#include "../../include/press_hip.h"
+#include "press_internal.h"
+
+namespace ph {
+
+// ------------------------------------------------------------------ errors (press_ctx.hip)
+
+#define HIPCHK(call)                                                                             \
+	do {                                                                                     \
+		hipError_t e_ = (call);                                                          \
+		if (e_ != hipSuccess)                                                            \
+			return set_error(PRESS_HIP_EHIP, "%s: %s", #call, hipGetErrorString(e_)); \
+	} while (0)
+
+// ------------------------------------------------------------------ context (press_ctx.hip)
+
+struct DevBuf;
+extern DevBuf *g_bufs; // every DevBuf links itself in here: press_hip_shutdown() cannot forget one
+
+struct DevBuf {
+	void *p = nullptr;
+	size_t cap = 0;
+	DevBuf *next;
+	DevBuf() : next(g_bufs) { g_bufs = this; }
+	DevBuf(const DevBuf &) = delete;
+	DevBuf &operator=(const DevBuf &) = delete;
+	// grow-only; contents are not preserved
+	int reserve(size_t n)
+	{
+		if (n <= cap)
+			return 0;
+		release();
+		size_t want = n + n / 8 + 4096;
+		hipError_t e = hipMalloc(&p, want);
+		if (e != hipSuccess)
+			return set_error(PRESS_HIP_EHIP, "hipMalloc(%zu): %s", want, hipGetErrorString(e));
+		cap = want;
+		return 0;
+	}
+	void release()
+	{
+		if (p)
+			(void) hipFree(p);
+		p = nullptr;
+		cap = 0;
+	}
+};
+
+struct Ctx {
+	bool ready = false;
+	int device = -1;
+	hipStream_t own = nullptr;
+	hipStream_t user = nullptr;
+	bool use_user = false;
+	// scratch shared by both modes
+	DevBuf meta, ex_pos, ex_val, low, huff, chunks, gran, ctl, first_chunk, htiles, hunit, hrec, hlist, hread, hwave, hbits, hend, hmin, cbits;
+	DevBuf ztmp, zoff, zoff4, zlen, zhist, ztab, zfirst, zblk, zsbits, zbpos, zbflag, zkcnt, zrd, znb, zn, zdcopy, zdhuf, zdunit, zdtree, zdlong, zdctl, zdseq, zdxblk; // zstd frames
+	// staging for host-pointer calls
+	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
+	uint32_t zs_nhost = 0; // frames the last zstd depress batch left to libzstd
+	uint32_t *zs_pin = nullptr; // page-locked: that count comes back while the device goes on with the batch
+	hipEvent_t zs_ev = nullptr;
+	// static Huffman table currently on the device
+	bool have_table = false;
+	bool table_trie = false; // some code of the table is beyond the second-level tables (HUF_NEEDS_TRIE)
+	uint32_t tlen[256];
+	uint64_t tbits[256];
+	uint32_t tmin = 64, tmax = 1; // its shortest / longest code
+
+	hipStream_t stream() const { return use_user ? user : own; }
+};
+
+extern Ctx g;
+// One context per process (one process per GPU): calls from several host threads are serialised.
+extern std::recursive_mutex g_mu;
+#define API_LOCK std::lock_guard<std::recursive_mutex> api_lock_(ph::g_mu)
+
+// Every entry point that touches the device comes through here: HIP's current device is per
+// host thread, so it is selected again on every call (cheap), not only by the first caller.
+int ctx_init();
+#define API_ENTER API_LOCK; if (int rc_ = ph::ctx_init()) return rc_ // head of an entry point that needs the device
+void staging_release(); // page-locked staging buffers of the host-pointer calls (press_batch.hip)
+
+// ---- zstd, loaded lazily (third party; the reference links -lzstd, press/Makefile:3) ----
+struct Zstd {
+	bool tried = false;
+	size_t (*compress)(void *, size_t, const void *, size_t, int) = nullptr;
+	size_t (*decompress)(void *, size_t, const void *, size_t) = nullptr;
+	size_t (*bound)(size_t) = nullptr;
+	unsigned (*is_error)(size_t) = nullptr;
+};
+extern Zstd zstd_fn;
+bool zstd_open();
+uint64_t zstd_bound_(uint64_t n);
+
+// ------------------------------------------------------------------ methods (dispatch and bounds: press_methods.hip)
+
+enum Family : uint8_t { FAM_SVB, FAM_EX, FAM_ZSTD };
+struct Method {
+	int id;
+	Family family;
+	bool key2, zd, slow5; // FAM_SVB: 2-bit keys (svb32), zig-zag delta, BLOW5's framing
+	int exfmt, ent;       // FAM_EX: ExFmt; entropy stage 0 plain, 1 static Huffman, 2 / 3 / 4 range coder
+	int inner;            // FAM_ZSTD: the method whose streams the frames hold ...
+	uint32_t kdiv;        // ... and its samples per key byte (ZsBufs::kdiv)
+};
+#define M_SVB(id, key2, zd, slow5) { id, FAM_SVB, key2, zd, slow5, 0, 0, 0, 0 }
+#define M_EX(id, fmt, ent) { id, FAM_EX, false, false, false, fmt, ent, 0, 0 }
+#define M_ZSTD(id, inner, kdiv) { id, FAM_ZSTD, false, false, false, 0, 0, inner, kdiv }
+constexpr Method METHODS[] = {
+	M_SVB(PRESS_HIP_SVB12, false, false, false),
+	M_SVB(PRESS_HIP_SVB12_ZD, false, true, false),
+	M_SVB(PRESS_HIP_SVB_ZD, true, true, false),
+	M_ZSTD(PRESS_HIP_ZSTD_SVB_ZD, PRESS_HIP_SVB_ZD, 4),
+	M_ZSTD(PRESS_HIP_ZSTD_SVB12_ZD, PRESS_HIP_SVB12_ZD, 8),
+	M_EX(PRESS_HIP_VBE21_ZD, EXF_VBE21, 0),
+	M_EX(PRESS_HIP_VBBE21_ZD, EXF_VBBE21, 0),
+	M_EX(PRESS_HIP_VBSBE21_ZD, EXF_VBSBE21, 0),
+	M_EX(PRESS_HIP_VBSSE21_ZD, EXF_VBSSE21, 0),
+	M_EX(PRESS_HIP_SHUFF_VBE21_ZD, EXF_VBE21, 1),
+	M_EX(PRESS_HIP_SHUFF_VBBE21_ZD, EXF_VBBE21, 1),
+	M_EX(PRESS_HIP_SHUFF_VBSBE21_ZD, EXF_VBSBE21, 1),
+	M_EX(PRESS_HIP_SHUFF_VBSSE21_ZD, EXF_VBSSE21, 1),
+	M_EX(PRESS_HIP_HASGAM_ZDQ, EXF_EXZD, 0),
+	M_ZSTD(PRESS_HIP_ZSTD_HASGAM_ZDQ, PRESS_HIP_HASGAM_ZDQ, 0),
+	M_SVB(PRESS_HIP_SLOW5_SVB_ZD, true, true, true),
+	M_EX(PRESS_HIP_RC_VBE21_ZD, EXF_VBE21, 2),
+	M_EX(PRESS_HIP_RCC_VBE21_ZD, EXF_VBE21, 3),
+	M_EX(PRESS_HIP_RCCM_VBBE21_ZD, EXF_VBBE21, 4),
+};
+constexpr bool methods_in_order()
+{
+	for (int i = 0; i < PRESS_HIP_NMETHODS; i++)
+		if (METHODS[i].id != i || (METHODS[i].family == FAM_ZSTD && METHODS[METHODS[i].inner].family == FAM_ZSTD))
+			return false;
+	return true;
+}
+static_assert(sizeof METHODS / sizeof METHODS[0] == PRESS_HIP_NMETHODS, "one row per method id");
+static_assert(methods_in_order(), "METHODS[i].id == i, and a zstd composition wraps a plain method");
+inline bool method_ok(int m) { return m >= 0 && m < PRESS_HIP_NMETHODS; }
+inline bool is_shuff(const Method &m) { return m.family == FAM_EX && m.ent == 1; }
+inline bool is_rc(const Method &m) { return m.family == FAM_EX && m.ent >= 2; }
+
+// ---- bounds: the reference's formulas ----
+inline uint32_t svb16_keylen(uint32_t n) { return (n >> 3) + (((n & 7) + 7) >> 3); }
+inline uint64_t bound_svb32(uint32_t n) { return (uint64_t) (n + 3) / 4 + (uint64_t) n * 4 + 16; }    // streamvbyte.h:35
+inline uint64_t bound_svb16(uint32_t n) { return (uint64_t) svb16_keylen(n) + (uint64_t) n * 4 + 16; } // streamvbyte.h:42
+inline uint64_t bound_vb1e2(uint32_t m) { return (uint64_t) (1 + m * 0.2 * 6 + m * 0.8); }            // press.c:2575
+inline uint64_t bound_vbzd(uint32_t n) { return 2 + bound_vb1e2(n - 1); }                             // press.c:3411
+
+// ------------------------------------------------------------------ scratch plan (press_methods.hip)
+
+// What one batch call needs of the context's DevBufs, and the counts its kernels are launched with: made once at the top
+// of the call, reserved, and then the only source of the pointers and counts in BatchArgs / DecodeArgs / ZsBufs.
+struct ScratchPlan {
+	const Method *m;
+	uint32_t max_chunks;
+	uint32_t max_htiles, hlist_cap, huf_minlen; // static-Huffman decode, else 0
+	ZsBufs z; // zstd frames: kdiv, max_blocks, lit_base and the cap_* (else 0); bind() adds the pointers
+	struct Row {
+		DevBuf Ctx::*buf;
+		size_t bytes;
+	} rows[42]; // at most one per scratch DevBuf of Ctx
+	int nrows;
+	ScratchPlan &need(DevBuf Ctx::*buf, size_t bytes); // a buffer named twice keeps the larger size
+	int reserve() const;
+	void *ptr(DevBuf Ctx::*buf) const; // the buffer's device pointer; NULL for a buffer the plan has no row for
+	void bind(BatchArgs &a) const;      // a zeroed, with every scratch pointer and count of the plan
+	void bind(DecodeArgs &a) const;
+	ZsBufs zs() const;                 // z with its pointers
+};
+ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool decode);
+
+int check_method(int method); // EARG / ENOTABLE
+int launch_status();          // EHIP if a kernel launch since the last call failed
+int launch_press(const ScratchPlan &p, const BatchArgs &a, hipStream_t s);
+int launch_depress(const ScratchPlan &p, const DecodeArgs &a, hipStream_t s);
+
+// ------------------------------------------------------------------ static Huffman table (press_table.hip)
+
+int upload_table(const uint32_t len[256], const uint64_t bits[256]); // -> HuffDev in g.huff, cached by content
+int table_from_encoder(SymbolEncoder *se);                           // the caller's huffman.h objects -> upload_table
+int table_from_tree(huffman_node *root);
+
+} // namespace ph

@@ -1,5 +1,5 @@
 // press_internal.h - shared between the kernel files (press_*.hip) and the C-ABI
-// host layer (press_abi.hip).  Not installed; the public interface is include/press_hip.h.
+// host layer (press_host.h and its units).  Not installed; the public interface is include/press_hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -315,7 +315,7 @@ uint64_t train_scratch_bytes(uint32_t max_chunks);
 void launch_symbol_counts(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, uint64_t *counts,
 			  void *chunks, uint32_t *nchunks, uint32_t max_chunks, uint32_t grid, hipStream_t s);
 
-// sets press_hip_last_error() (press_abi.hip) and returns code
+// sets press_hip_last_error() (press_ctx.hip) and returns code
 int set_error(int code, const char *fmt, ...);
 
 } // namespace ph

@@ -1,0 +1,304 @@
+// press_methods.hip - everything that interprets a row of the method table (press_host.h): the reference's X_bound,
+// the scratch plan of a batch and its dispatch to the kernel launchers of press_*.hip.
+
+#include <vector>
+
+#include "press_host.h"
+#include "zs_table.h"
+
+using namespace ph;
+
+extern "C" uint64_t press_hip_bound(int method, uint32_t n)
+{
+	if (!method_ok(method))
+		return 0;
+	const Method &m = METHODS[method];
+	switch (m.family) {
+	case FAM_SVB:
+		if (m.slow5)
+			return (uint64_t) (n + 3) / 4 + (uint64_t) n * 4 + 4; // slow5_press.c:1037 (streamvbyte.h:31) + u32 count
+		return m.key2 ? bound_svb32(n) : bound_svb16(n);              // press.c:1585 / press.c:1568,1678
+	case FAM_EX:
+		if (m.exfmt == EXF_EXZD)
+			return bound_svb32((uint32_t) bound_vbzd(n));         // press.c:8461
+		return bound_vbzd(n);                                         // press.c:3411,4409
+	case FAM_ZSTD: // the inner stream, the svb kinds' behind its u32 count (press.c:1860, 2020, 8549)
+		return zstd_bound_((m.kdiv ? 4 : 0) + press_hip_bound(m.inner, n));
+	}
+	return 0;
+}
+
+// ------------------------------------------------------------------ scratch plan
+//
+// Which of the context's device buffers a batch needs, how large, and the counts derived from its shape.  reserve(),
+// the bind()s and press_hip_workspace_bytes() all read the one list of rows make_plan() writes: a buffer cannot be bound
+// without being sized, nor sized in two places.
+
+namespace ph {
+
+ScratchPlan &ScratchPlan::need(DevBuf Ctx::*buf, size_t bytes)
+{
+	int i = 0;
+	while (i < nrows && rows[i].buf != buf)
+		i++;
+	if (i == nrows)
+		rows[nrows++] = { buf, 0 };
+	rows[i].bytes = bytes > rows[i].bytes ? bytes : rows[i].bytes;
+	return *this;
+}
+
+int ScratchPlan::reserve() const
+{
+	for (int i = 0; i < nrows; i++)
+		if ((g.*rows[i].buf).reserve(rows[i].bytes))
+			return PRESS_HIP_EHIP;
+	return 0;
+}
+
+void *ScratchPlan::ptr(DevBuf Ctx::*buf) const
+{
+	for (int i = 0; i < nrows; i++)
+		if (rows[i].buf == buf)
+			return (g.*buf).p;
+	return nullptr;
+}
+
+ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool decode)
+{
+	ScratchPlan p{};
+	p.m = &METHODS[method];
+	const bool zs = p.m->family == FAM_ZSTD;
+	const Method &k = zs ? METHODS[p.m->inner] : *p.m; // the method whose kernels make / read the samples
+	const size_t nr = (size_t) nreads + 1;
+	p.max_chunks = (uint32_t) (total_samples / CHUNK + nreads + 1);
+	const size_t mc = p.max_chunks;
+	p.need(&Ctx::meta, nr * sizeof(ReadMeta));
+	if (zs) {
+		p.z.kdiv = p.m->kdiv;
+		p.z.max_blocks = (uint32_t) (total_samples * 2 / zs::BLOCK_LITS + nreads + 1);
+		const size_t mb = p.z.max_blocks;
+		// what a batch of this library's frames needs, with room for others; a frame that does not
+		// fit (tiny blocks, thousands of trees) goes to libzstd on the host
+		p.z.cap_copy = p.z.max_blocks + (uint32_t) (total_samples / 256) + 16 * nreads + 64;
+		p.z.cap_units = p.z.max_blocks / 8 + 2 * nreads + 64;
+		p.z.cap_trees = 4 * nreads + 64;
+		p.z.cap_long = (uint32_t) (total_samples / 8192) + nreads + 64; // (blocks of at least 32 KiB of literals)
+		// frames with sequences (libzstd's own): their literals in the second half of ztmp.  Bytes per sample the
+		// inner stream can take at most: device, zs_content_max
+		p.z.lit_base = (p.m->kdiv ? total_samples * 9 / 4 : total_samples * 9) + ((uint64_t) nreads + 1) * 128 + 64;
+		// (level 1 on signal data: a handful per block; higher levels: one per ~20 content bytes)
+		const uint64_t cs = total_samples / 4 + 64ull * nreads + 1024;
+		p.z.cap_seq = cs > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t) cs;
+		p.z.cap_xblk = p.z.max_blocks / 4 + 4 * nreads + 64;
+		p.need(&Ctx::ztmp, decode ? 2 * p.z.lit_base : p.z.lit_base).need(&Ctx::zoff, nr * 8).need(&Ctx::zoff4, nr * 8)
+			.need(&Ctx::zlen, nr * 8).need(&Ctx::zrd, nr * sizeof(ZsRead));
+		if (decode)
+			p.need(&Ctx::zn, nr * 4).need(&Ctx::zdseq, (size_t) p.z.cap_seq * sizeof(ZsSeq))
+				.need(&Ctx::zdxblk, (size_t) p.z.cap_xblk * sizeof(ZsXBlk)).need(&Ctx::zdcopy, (size_t) p.z.cap_copy * sizeof(ZsCopy))
+				.need(&Ctx::zdhuf, (size_t) p.z.cap_units * 8 * sizeof(ZsHuf)).need(&Ctx::zdunit, (size_t) p.z.cap_units * sizeof(ZsUnit))
+				.need(&Ctx::zdtree, (size_t) p.z.cap_trees * sizeof(ZsTree)).need(&Ctx::zdlong, (size_t) p.z.cap_long * sizeof(ZsLong))
+				.need(&Ctx::zdctl, sizeof(ZsDCtl));
+		else // (ex_pos / ex_val of the svb kinds: the lists of key bytes that are not zero)
+			p.need(&Ctx::zhist, nr * 1024).need(&Ctx::ztab, nr * sizeof(zs::Table)).need(&Ctx::zfirst, nr * 4)
+				.need(&Ctx::zblk, mb * 4).need(&Ctx::zsbits, mb * 16).need(&Ctx::zbpos, mb * 4).need(&Ctx::zbflag, mb)
+				.need(&Ctx::zkcnt, mc * 4).need(&Ctx::znb, 64)
+				.need(&Ctx::ex_pos, (total_samples + 64) * 4).need(&Ctx::ex_val, (total_samples + 64) * 4);
+	}
+	p.need(&Ctx::chunks, mc * sizeof(ChunkDesc)).need(&Ctx::gran, 2 * mc * sizeof(uint64_t)).need(&Ctx::ctl, 2 * sizeof(ChunkCtl))
+		.need(&Ctx::first_chunk, nr * 4);
+	if (k.family != FAM_EX)
+		return p;
+	p.need(&Ctx::ex_pos, (total_samples + 64) * 4).need(&Ctx::ex_val, (total_samples + 64) * 4);
+	if (!decode && is_shuff(k))
+		p.need(&Ctx::cbits, mc * sizeof(ChunkBits));
+	if (is_rc(k))
+		p.need(&Ctx::low, total_samples + 64); // the one-byte values between the two stages
+	if (decode && is_shuff(k)) {
+		// Huffman tiles of a batch (press_huffman.hip, k_huff_tiles): a read of n samples has at most
+		// n - 1 codes of at most maxlen bits, cut into tiles of HUF_HT subsequences
+		const uint32_t minlen = g.tmin, maxlen = g.tmax;
+		const uint64_t tb = (uint64_t) HUF_HT * (minlen >= 4 ? 256u : minlen >= 2 ? 128u : 64u);
+		const uint64_t ht = total_samples * maxlen / tb + nreads + 1;
+		const size_t mt = p.max_htiles = ht > 0xFFFFFFull ? 0xFFFFFFu : (uint32_t) ht;
+		// broken links a repair round can list (3 % of the subsequences on signal data; what does not fit is left to
+		// the serial pass): a table that never synchronises lists every subsequence; k_huf_sync's workgroups take
+		// slots 1024 at a time
+		const size_t hl = mt * HUF_HT + (1u << 20);
+		p.hlist_cap = (uint32_t) hl;
+		p.huf_minlen = minlen | (g.table_trie ? HUF_NEEDS_TRIE : 0u);
+		p.need(&Ctx::low, total_samples + 64).need(&Ctx::htiles, mt * sizeof(HufTile))
+			.need(&Ctx::hunit, mt * (HUF_HT / 64) * sizeof(HufUnit)).need(&Ctx::hrec, mt * HUF_HT * 4)
+			.need(&Ctx::hlist, hl * 8).need(&Ctx::hread, nr * 8)
+			.need(&Ctx::hwave, mt * (HUF_HT / 64) * 8).need(&Ctx::hbits, mt * (HUF_HT / 64) * 8)
+			.need(&Ctx::hend, mt * HUF_HT + 64).need(&Ctx::hmin, nr * 4);
+	}
+	return p;
+}
+
+// Most fields of the argument blocks carry the name of the buffer behind them (ZsBufs: without its z)
+#define BIND(x, f, buf) x.f = (decltype(x.f)) ptr(&Ctx::buf)
+#define B(f) BIND(a, f, f)
+#define BZ(f) BIND(z, f, z##f)
+
+void ScratchPlan::bind(BatchArgs &a) const
+{
+	memset(&a, 0, sizeof a);
+	B(meta), B(ex_pos), B(ex_val), B(chunks), B(gran), B(ctl), B(first_chunk), B(cbits);
+	BIND(a, low_tmp, low);
+	a.huff = (const HuffDev *) g.huff.p; // (the table's, not the batch's: upload_table)
+	a.max_chunks = max_chunks;
+}
+
+void ScratchPlan::bind(DecodeArgs &a) const
+{
+	memset(&a, 0, sizeof a);
+	B(meta), B(ex_pos), B(ex_val), B(low), B(chunks), B(gran), B(ctl), B(first_chunk);
+	B(htiles), B(hunit), B(hrec), B(hlist), B(hread), B(hwave), B(hbits), B(hend), B(hmin);
+	a.huff = (const HuffDev *) g.huff.p;
+	a.max_chunks = max_chunks;
+	a.max_htiles = max_htiles;
+	a.hlist_cap = hlist_cap;
+	a.huf_minlen = huf_minlen;
+}
+
+ZsBufs ScratchPlan::zs() const
+{
+	ZsBufs z = this->z;
+	BIND(z, ztmp, ztmp), BIND(z, zoff, zoff), BIND(z, zoff4, zoff4), BIND(z, zlen, zlen), BIND(z, zn, zn);
+	BZ(hist), BZ(tab), BZ(sbits), BZ(bpos), BZ(bflag), BZ(kcnt), BZ(rd);
+	BZ(dcopy), BZ(dhuf), BZ(dunit), BZ(dtree), BZ(dlong), BZ(dctl), BZ(dseq), BZ(dxblk);
+	BIND(z, first_blk, zfirst), BIND(z, blk_read, zblk), BIND(z, nblocks, znb);
+	return z;
+}
+
+} // namespace ph
+
+// What the two batch calls keep for a batch of this shape: the buffers are shared and grow-only, so each holds the
+// larger of what press and depress ask of it.  Host arithmetic, no device needed.
+extern "C" uint64_t press_hip_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads)
+{
+	API_LOCK; // (the Huffman decoder's rows depend on the table in force)
+	if (!method_ok(method))
+		return 0;
+	ScratchPlan p = make_plan(method, total_samples, nreads, false);
+	const ScratchPlan d = make_plan(method, total_samples, nreads, true);
+	for (int i = 0; i < d.nrows; i++)
+		p.need(d.rows[i].buf, d.rows[i].bytes);
+	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
+	for (int i = 0; i < p.nrows; i++)
+		b += p.rows[i].bytes;
+	return b;
+}
+
+int ph::check_method(int method)
+{
+	if (!method_ok(method))
+		return set_error(PRESS_HIP_EARG, "method %d is not available in the batch API", method);
+	if (is_shuff(METHODS[method]) && !g.have_table)
+		return set_error(PRESS_HIP_ENOTABLE, "static-Huffman method without a table (press_hip_load_table_file)");
+	return 0;
+}
+
+int ph::launch_status()
+{
+	hipError_t e = hipGetLastError();
+	return e == hipSuccess ? 0 : set_error(PRESS_HIP_EHIP, "kernel launch: %s", hipGetErrorString(e));
+}
+
+int ph::launch_press(const ScratchPlan &p, const BatchArgs &a, hipStream_t s)
+{
+	const Method &m = *p.m;
+	if (m.family == FAM_SVB) {
+		launch_svb_encode_chunked(a, m.key2, m.zd, s, m.slow5);
+	} else if (m.family == FAM_EX) {
+		launch_ex_encode_chunked(a, m.exfmt, m.ent, s);
+	} else {
+		const ZsBufs z = p.zs();
+		launch_zstd_encode(a, z, s);
+	}
+	return launch_status();
+}
+
+// Frames the device walk leaves to libzstd (dictionaries, 12-bit tables, several frames in one stream ...): their
+// content is made on the host and put where the device would have put it.  How many there are comes back through a
+// page-locked word behind an event (zs_count_host_frames, queued between the two stages of a batch): the host waits for
+// that word only, while the device already runs the second stage - a batch of this library's own frames, or of
+// ZSTD_compress's, has no such frame and is never waited for; with one, the second stage is run again (*patched).
+static int zs_count_host_frames(const ZsBufs &z, hipStream_t s)
+{
+	if (!g.zs_pin) {
+		HIPCHK(hipHostMalloc((void **) &g.zs_pin, 64, hipHostMallocDefault));
+		HIPCHK(hipEventCreateWithFlags(&g.zs_ev, hipEventDisableTiming));
+	}
+	HIPCHK(hipMemcpyAsync(g.zs_pin, &z.dctl->nhost, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipEventRecord(g.zs_ev, s));
+	return 0;
+}
+static int zs_host_frames(const DecodeArgs &a, const ZsBufs &z, hipStream_t s, bool *patched)
+{
+	*patched = false;
+	HIPCHK(hipEventSynchronize(g.zs_ev));
+	const uint32_t nhost = *g.zs_pin;
+	g.zs_nhost = nhost;
+	if (!nhost || !zstd_open())
+		return 0; // without libzstd those reads fail
+	HIPCHK(hipStreamSynchronize(s)); // (the second stage is running on what the device had)
+	*patched = true;
+	const uint32_t nr = a.nreads;
+	std::vector<ZsRead> rd(nr);
+	std::vector<uint64_t> ioff(nr), ilen(nr), zoff(nr + 1);
+	std::vector<uint32_t> caps(nr);
+	HIPCHK(hipMemcpy(rd.data(), z.rd, (size_t) nr * sizeof(ZsRead), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(ioff.data(), a.in_off, (size_t) nr * 8, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(ilen.data(), a.in_len, (size_t) nr * 8, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(zoff.data(), z.zoff, ((size_t) nr + 1) * 8, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(caps.data(), a.nsamp, (size_t) nr * 4, hipMemcpyDeviceToHost));
+	std::vector<uint8_t> frame, buf;
+	for (uint32_t r = 0; r < nr; r++) {
+		if (rd[r].mode != 3)
+			continue;
+		uint64_t cap;
+		if (z.kdiv) {
+			cap = 4ull + (caps[r] + (uint64_t) z.kdiv - 1) / z.kdiv + 2ull * caps[r];
+		} else { // device: zs_content_max
+			const uint64_t vb = bound_vbzd(caps[r] ? caps[r] : 1);
+			cap = (vb + 3) / 4 + vb * 4 + 16;
+		}
+		frame.resize(ilen[r] + 8);
+		buf.resize(cap + 8);
+		HIPCHK(hipMemcpy(frame.data(), a.in + ioff[r], ilen[r], hipMemcpyDeviceToHost));
+		const size_t got = zstd_fn.decompress(buf.data(), cap, frame.data(), ilen[r]);
+		if (zstd_fn.is_error(got)) {
+			rd[r].mode = 2;
+			continue;
+		}
+		HIPCHK(hipMemcpy(z.ztmp + zoff[r], buf.data(), got, hipMemcpyHostToDevice));
+		rd[r].mode = 0;
+		rd[r].nd = (uint32_t) got;
+	}
+	HIPCHK(hipMemcpy(z.rd, rd.data(), (size_t) nr * sizeof(ZsRead), hipMemcpyHostToDevice));
+	return 0;
+}
+
+int ph::launch_depress(const ScratchPlan &p, const DecodeArgs &a, hipStream_t s)
+{
+	const Method &m = *p.m;
+	if (m.family == FAM_SVB) {
+		launch_svb_decode_chunked(a, m.key2, m.zd, s, m.slow5);
+	} else if (m.family == FAM_EX) {
+		launch_ex_decode_chunked(a, m.exfmt, m.ent, s);
+	} else {
+		const ZsBufs z = p.zs();
+		launch_zstd_decode_frames(a, z, s);
+		int rc = zs_count_host_frames(z, s);
+		if (rc)
+			return rc;
+		launch_zstd_decode_streams(a, z, s);
+		bool patched;
+		if ((rc = zs_host_frames(a, z, s, &patched)))
+			return rc;
+		if (patched)
+			launch_zstd_decode_streams(a, z, s);
+	}
+	return launch_status();
+}

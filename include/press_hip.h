@@ -369,7 +369,10 @@ uint32_t press_hip_zstd_host_frames(void);
 void *press_hip_host_alloc(uint64_t bytes); /* hipHostMalloc; NULL on failure */
 void press_hip_host_free(void *p);
 
-/* bytes of device scratch the two calls above keep for a batch of this shape (informational) */
+/* bytes of device scratch the two calls above keep for a batch of this shape.  Exact: for every buffer the larger of
+ * what press and depress request (the buffers are shared and grow-only), plus the device table for the static-Huffman
+ * methods (whose decoder's share depends on the table in force) - the requested bytes, before the growth slack of
+ * n / 8 + 4096 each allocation adds.  Host arithmetic, no GPU needed; 0 for a method id out of range. */
 uint64_t press_hip_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads);
 
 /* Measurement aid (bench.py): when enabled, every batch call brackets its dominant kernel

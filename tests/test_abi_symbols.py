@@ -85,13 +85,40 @@ def test_scratch_registry_without_gpu():
     nbytes = ctypes.c_uint64(1)
     nbuf = lib.press_hip_scratch_buffers(ctypes.byref(nbytes))
     # as many as the context declares (DevBuf a, b, c; lines of struct Ctx)
-    src = open(os.path.join(os.path.dirname(build.CSRC), "csrc", "press_abi.hip")).read()
+    src = open(os.path.join(os.path.dirname(build.CSRC), "csrc", "press_host.h")).read()
     declared = sum(len(l.split(";")[0].split(",")) for l in re.findall(r"^\tDevBuf ([a-z][^;]*;)", src, re.M))
     assert nbuf == declared >= 40, (nbuf, declared)
     import torch
     if not torch.cuda.is_available():
         assert nbytes.value == 0
     lib.press_hip_shutdown()  # harmless without a context
+
+
+def test_workspace_bytes_without_gpu():
+    """press_hip_workspace_bytes is the scratch plan summed (host arithmetic, no device): for every buffer the larger
+    of what press and depress reserve, plus the device table for the Huffman methods.  It never shrinks when the batch
+    grows, holds ReadMeta (32 bytes a read) and the two exception lists (2 x 4 bytes a sample; Huffman: and the
+    one-byte values), and for the svb methods stays a few MB at the sample count of test_c2_samples_past_2g."""
+    import ctypes
+
+    lib = press.load_library()
+    lib.press_hip_workspace_bytes.restype = ctypes.c_uint64
+    lib.press_hip_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
+    totals = [1000, 100_000, 10_000_000, 930_000_000, (1 << 31) + (1 << 20)]
+    reads = [1, 5, 64, 8192]
+    svb = ("svb12", "svb12_zd", "svb_zd", "slow5_svb_zd")
+    for m, mid in press.METHODS.items():
+        ws = {(t, r): int(lib.press_hip_workspace_bytes(mid, t, r)) for t in totals for r in reads}
+        for (t, r), w in ws.items():
+            assert w >= 32 * (r + 1), (m, t, r, w)
+            if m.startswith("shuffman_"):
+                assert w >= 9 * t, (m, t, r, w)
+            elif not m.startswith("zstd_") and m not in svb:  # exception split, ex-zd, range coders
+                assert w >= 8 * t, (m, t, r, w)
+            assert all(w <= ws[(t2, r)] for t2 in totals if t2 >= t), (m, t, r)
+            assert all(w <= ws[(t, r2)] for r2 in reads if r2 >= r), (m, t, r)
+        if m in svb:
+            assert ws[((1 << 31) + (1 << 20), 5)] < 10 ** 9, (m, ws[((1 << 31) + (1 << 20), 5)])
 
 
 def test_one_libzstd_per_process():

@@ -645,7 +645,7 @@ def test_c2_samples_past_2g(lib, oracle, m, vram):
     """a sig of 2^31 + 2^20 samples, reads below, across and beyond the 2^31-sample line (2^32 bytes): press
     against the oracle, depress into the same tensor, symbol counts against numpy.  The exception, Huffman and
     range-coder methods are left out on purpose: their scratch is 8 to 9 bytes per sample of extent
-    (press_abi.hip reserve_scratch), about 19 GB here."""
+    (press_methods.hip make_plan), about 19 GB here."""
     import torch
 
     bat = L.battery()

@@ -367,6 +367,39 @@ def test_shutdown_releases_every_buffer(oracle):
     assert ret == 0 and got == oracle.press("shuffman_vbe21_zd", reads[0])[1]
 
 
+@pytest.mark.parametrize("m", ["svb12_zd", "vbe21_zd", "shuffman_vbe21_zd", "rc_vbe21_zd", "zstd_svb_zd"])
+def test_scratch_plan_is_what_is_allocated(m):
+    """press_hip_workspace_bytes() is exact: from an empty library, one device-resident press and one depress of a
+    batch leave every scratch buffer at the size the plan asks for plus DevBuf's growth slack (n + n / 8 + 4096 per
+    buffer), and nothing else - device-resident calls touch no staging buffer"""
+    import ctypes
+
+    import torch
+
+    lib = press.load_library()
+    lib.press_hip_scratch_buffers.restype = ctypes.c_uint32
+    lib.press_hip_scratch_buffers.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+    dev = torch.device("cuda:0")
+    nreads = 16
+    sig_al, starts, n_np = synth.synth_batch_torch(5, 0, nreads, dev, align=8)
+    sig_al = torch.cat([sig_al, torch.zeros(64, dtype=torch.int16, device=dev)])
+    torch.cuda.synchronize()
+    lib.press_hip_shutdown()
+    try:
+        if m.startswith("shuffman"):
+            press.load_table()
+        press.use_torch_stream()
+        streams, d_back, outn = _device_batch(m, sig_al, starts, n_np, dev)
+        assert np.array_equal(outn, n_np.astype(np.int32)) and torch.equal(d_back, sig_al), m
+        nbytes = ctypes.c_uint64()
+        nbuf = lib.press_hip_scratch_buffers(ctypes.byref(nbytes))
+        ws = int(lib.press_hip_workspace_bytes(press.METHODS[m], sig_al.numel(), nreads))
+        print(m, "workspace_bytes", ws, "allocated", nbytes.value, "buffers", nbuf)
+        assert ws <= nbytes.value <= ws + ws // 8 + 4096 * nbuf, (m, ws, nbytes.value, nbuf)
+    finally:
+        press.load_table()  # (the rest of the module runs with the table)
+
+
 # ---------------------------------------------------------------- static Huffman: tables other than NA12878
 
 def _canonical_table(lens):

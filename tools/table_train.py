@@ -8,7 +8,7 @@
 * a batch with shifted statistics (the deltas of synthetic reads x 1.5): a table fitted to it against the
   NA12878 table - bytes and press / depress MB/s of shuffman_vbe21_zd (device-resident batch calls);
 * whether the fitted table needs the decoder's trie (HUF_NEEDS_TRIE: a long code whose first 12 bits get no
-  second-level table, the rule of upload_table in press_abi.hip).
+  second-level table, the rule of upload_table in press_table.hip).
 """
 import argparse
 import json
