@@ -256,7 +256,8 @@ static int check_disjoint(const uint64_t *off, const uint32_t *n, uint32_t nread
 
 // The head of every host-pointer call: the sample layout checked, room for sig, off and n on the device, off and n
 // on their way there.
-static int stage_layout(const uint64_t *off, const uint32_t *n, uint32_t nreads, uint64_t total_samples, hipStream_t s)
+static int stage_layout(const uint64_t *off, const uint32_t *n, uint32_t nreads, uint64_t total_samples, hipStream_t s,
+			bool with_sig = true)
 {
 	for (uint32_t r = 0; r < nreads; r++) {
 		if (off[r] & 7)
@@ -265,12 +266,21 @@ static int stage_layout(const uint64_t *off, const uint32_t *n, uint32_t nreads,
 		if (off[r] + n[r] > total_samples)
 			return set_error(PRESS_HIP_EARG, "read %u ends beyond total_samples", r);
 	}
-	if (g.sig.reserve(total_samples * 2 + 64) || g.off.reserve((size_t) nreads * 8) || g.nsamp.reserve((size_t) nreads * 4))
+	if ((with_sig && g.sig.reserve(total_samples * 2 + 64)) || g.off.reserve((size_t) nreads * 8) || g.nsamp.reserve((size_t) nreads * 4))
 		return PRESS_HIP_EHIP;
 	HIPCHK(hipMemcpyAsync(g.off.p, off, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
 	HIPCHK(hipMemcpyAsync(g.nsamp.p, n, (size_t) nreads * 4, hipMemcpyHostToDevice, s));
 	return 0;
 }
+
+static int fetch_streams(uint8_t *out, const uint64_t *out_off, const std::vector<uint64_t> &rel, uint64_t *out_len,
+			 uint32_t nreads, hipStream_t s);
+static int fetch_samples(int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t *out_n, uint32_t nreads,
+			 const std::vector<uint32_t> &order, hipStream_t s);
+// the source streams of a host-pointer depress packed back to back into `arena` while they are staged (the caller's slots
+// may be far apart), their offsets and lengths into `offs` and g.lens2
+static int stage_streams(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t nreads, DevBuf &arena,
+			 DevBuf &offs, std::vector<uint64_t> &doff, hipStream_t s);
 
 extern "C" int press_hip_press_batch(int method, const int16_t *sig, const uint64_t *off, const uint32_t *n,
 				     uint32_t nreads, uint64_t total_samples, uint8_t *out,
@@ -332,6 +342,14 @@ extern "C" int press_hip_press_batch(int method, const int16_t *sig, const uint6
 	a.out_len = (uint64_t *) g.lens.p;
 	if ((rc = launch_press(plan, a, s)))
 		return rc;
+	return fetch_streams(out, out_off, rel, out_len, nreads, s);
+}
+
+// The tail of a host-pointer press: out_len, then the streams of g.arena (slot r at rel[r]) into the caller's slots.
+static int fetch_streams(uint8_t *out, const uint64_t *out_off, const std::vector<uint64_t> &rel, uint64_t *out_len,
+			 uint32_t nreads, hipStream_t s)
+{
+	int rc;
 	HIPCHK(hipMemcpyAsync(out_len, g.lens.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	if (nreads <= 4) { // per-read calls: one small copy each
@@ -456,33 +474,14 @@ extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint
 		return launch_depress(plan, a, s);
 	}
 
-	uint64_t dense = 0;
-	std::vector<uint64_t> doff(nreads);
-	std::vector<Piece> pc;
-	pc.reserve(nreads);
-	for (uint32_t r = 0; r < nreads; r++) {
-		doff[r] = dense;
-		if (in_len[r])
-			pc.push_back({ const_cast<uint8_t *>(in) + in_off[r], dense, in_len[r] });
-		dense += in_len[r];
-	}
 	std::vector<uint32_t> order; // the reads in ascending slot order (for the staged copy back)
 	if ((rc = check_disjoint(off, n, nreads, "the sample room", order)))
 		return rc;
 	if ((rc = stage_layout(off, n, nreads, total_samples, s)))
 		return rc;
-	if (g.arena.reserve(dense + 64) || g.arena_off.reserve((size_t) nreads * 8) || g.lens2.reserve((size_t) nreads * 8) ||
-	    g.outn.reserve((size_t) nreads * 4))
-		return PRESS_HIP_EHIP;
-	HIPCHK(hipMemcpyAsync(g.arena_off.p, doff.data(), (size_t) nreads * 8, hipMemcpyHostToDevice, s));
-	HIPCHK(hipMemcpyAsync(g.lens2.p, in_len, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
-	// the streams, packed back to back while they are staged (the caller's slots may be far apart)
-	if (nreads <= 4) {
-		for (const Piece &q : pc)
-			HIPCHK(hipMemcpyAsync((uint8_t *) g.arena.p + q.dense, q.host, q.len, hipMemcpyHostToDevice, s));
-	} else if ((rc = staged_pieces<true>((uint8_t *) g.arena.p, dense, pc, s))) {
+	std::vector<uint64_t> doff;
+	if ((rc = stage_streams(in, in_off, in_len, nreads, g.arena, g.arena_off, doff, s)))
 		return rc;
-	}
 	a.in = (const uint8_t *) g.arena.p;
 	a.in_off = (const uint64_t *) g.arena_off.p;
 	a.in_len = (const uint64_t *) g.lens2.p;
@@ -492,6 +491,14 @@ extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint
 	a.out_n = (uint32_t *) g.outn.p;
 	if ((rc = launch_depress(plan, a, s)))
 		return rc;
+	return fetch_samples(sig, off, n, out_n, nreads, order, s);
+}
+
+// The tail of a host-pointer depress: out_n, then the decoded samples of g.sig into the caller's rooms (`order`: the
+// reads in ascending room order, check_disjoint).
+static int fetch_samples(int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t *out_n, uint32_t nreads,
+			 const std::vector<uint32_t> &order, hipStream_t s)
+{
 	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	if (nreads <= 4) {
@@ -507,8 +514,10 @@ extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint
 	// only the decoded samples of every read reach the caller's buffer (its padding between the
 	// reads is left alone); reads in ascending slot order for the staged copy (the rooms are disjoint, and
 	// out_n[r] <= n[r])
-	pc.clear();
+	std::vector<Piece> pc;
+	pc.reserve(nreads);
 	uint64_t end = 0;
+	int rc;
 	for (uint32_t i = 0; i < nreads; i++) {
 		const uint32_t r = order[i];
 		if (out_n[r] == UINT32_MAX || out_n[r] == 0)
@@ -538,3 +547,145 @@ extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint
 	return 0;
 }
 
+
+static int stage_streams(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t nreads, DevBuf &arena,
+			 DevBuf &offs, std::vector<uint64_t> &doff, hipStream_t s)
+{
+	int rc;
+	uint64_t dense = 0;
+	doff.resize(nreads); // (the caller's: it is read by a copy that may still be queued when this returns)
+	std::vector<Piece> pc;
+	pc.reserve(nreads);
+	for (uint32_t r = 0; r < nreads; r++) {
+		doff[r] = dense;
+		if (in_len[r])
+			pc.push_back({ const_cast<uint8_t *>(in) + in_off[r], dense, in_len[r] });
+		dense += in_len[r];
+	}
+	if (arena.reserve(dense + 64) || offs.reserve((size_t) nreads * 8) || g.lens2.reserve((size_t) nreads * 8) ||
+	    g.outn.reserve((size_t) nreads * 4))
+		return PRESS_HIP_EHIP;
+	HIPCHK(hipMemcpyAsync(offs.p, doff.data(), (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(g.lens2.p, in_len, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	if (nreads <= 4) {
+		for (const Piece &q : pc)
+			HIPCHK(hipMemcpyAsync((uint8_t *) arena.p + q.dense, q.host, q.len, hipMemcpyHostToDevice, s));
+	} else if ((rc = staged_pieces<true>((uint8_t *) arena.p, dense, pc, s))) {
+		return rc;
+	}
+	return 0;
+}
+
+// ------------------------------------------------------------------ recode: streams in, streams out
+//
+// The two halves run one after the other on the stream, inside one call and one lock: the decode of `src` into the
+// caller's samples (or the library's own, sig == NULL), the verdicts out_n turned into the sample counts of the press
+// half (a refused read: 0), the press of `dst`.  The halves share the chunk table, the granules and the per-read records,
+// which is fine in sequence - except for a fused pair (recode_fused), where the svb decode kernel writes the press half's
+// chunk descriptors while it reads its own: that press has a table, a first-chunk list and a control block to itself.
+
+static int launch_recode(const RecodePlan &rp, DecodeArgs &da, BatchArgs &pa, hipStream_t s)
+{
+	int rc;
+	pa.sig = da.sig;
+	pa.off = da.off;
+	pa.nsamp = (const uint32_t *) g.rn.p;
+	const Method &sm = *rp.d.m, &dm = *rp.p.m;
+	if (rp.fused) {
+		pa.chunks = (ChunkDesc *) g.pchunks.p;
+		pa.first_chunk = (uint32_t *) g.pfirst.p;
+		pa.ctl = (ChunkCtl *) g.pctl.p;
+		launch_recode_fused(da, pa, sm.key2, sm.slow5, dm.exfmt, dm.ent, s);
+	} else {
+		if ((rc = launch_depress(rp.d, da, s)))
+			return rc;
+		launch_recode_counts(da.out_n, (uint32_t *) g.rn.p, da.nreads, s);
+		if (rp.keep_heads)
+			launch_recode_refused(da.out_n, pa, (uint8_t *) g.rkeep.p, true, s);
+		if ((rc = launch_press(rp.p, pa, s)))
+			return rc;
+	}
+	launch_recode_refused(da.out_n, pa, rp.keep_heads ? (uint8_t *) g.rkeep.p : nullptr, false, s);
+	return launch_status();
+}
+
+extern "C" int press_hip_recode_batch(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
+				      const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+				      uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+				      int16_t *sig, uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	if (!method_ok(src_method) || !method_ok(dst_method)) // (before any device call)
+		return set_error(PRESS_HIP_EARG, "method %d -> %d is not available in the batch API", src_method, dst_method);
+	int rc = ctx_init();
+	if (rc || (rc = check_method(src_method)) || (rc = check_method(dst_method)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	if (!in || !in_off || !in_len || !n || !off || !out || !out_off || !out_len || !out_n)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	hipStream_t s = g.stream();
+	const RecodePlan rp = make_recode_plan(src_method, dst_method, total_samples, nreads, sig != nullptr);
+	if ((rc = rp.all.reserve()))
+		return rc;
+	DecodeArgs da;
+	BatchArgs pa;
+	rp.d.bind(da);
+	rp.p.bind(pa);
+	da.nreads = pa.nreads = nreads;
+
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		da.in = in;
+		da.in_off = in_off;
+		da.in_len = in_len;
+		da.sig = sig ? sig : (int16_t *) g.rsig.p;
+		da.off = off;
+		da.nsamp = n;
+		da.out_n = out_n;
+		pa.out = out;
+		pa.out_off = out_off;
+		pa.out_len = out_len;
+		return launch_recode(rp, da, pa, s);
+	}
+
+	// host pointers: both calls' checks, the streams and the layout staged, the two halves, the copies back
+	for (uint32_t r = 0; r < nreads; r++)
+		if (out_off[r + 1] < out_off[r])
+			return set_error(PRESS_HIP_EARG, "out_off must be non-decreasing");
+	std::vector<uint32_t> order;
+	if ((rc = check_disjoint(off, n, nreads, "the sample room", order)))
+		return rc;
+	if ((rc = stage_layout(off, n, nreads, total_samples, s, sig != nullptr)))
+		return rc;
+	std::vector<uint64_t> doff;
+	if ((rc = stage_streams(in, in_off, in_len, nreads, g.rin, g.rin_off, doff, s)))
+		return rc;
+	const uint64_t a0 = out_off[0], a1 = out_off[nreads];
+	if (g.arena.reserve(a1 - a0 + 64) || g.arena_off.reserve(((size_t) nreads + 1) * 8) || g.lens.reserve((size_t) nreads * 8))
+		return PRESS_HIP_EHIP;
+	std::vector<uint64_t> rel(nreads + 1);
+	for (uint32_t r = 0; r <= nreads; r++)
+		rel[r] = out_off[r] - a0;
+	HIPCHK(hipMemcpyAsync(g.arena_off.p, rel.data(), ((size_t) nreads + 1) * 8, hipMemcpyHostToDevice, s));
+	da.in = (const uint8_t *) g.rin.p;
+	da.in_off = (const uint64_t *) g.rin_off.p;
+	da.in_len = (const uint64_t *) g.lens2.p;
+	da.sig = sig ? (int16_t *) g.sig.p : (int16_t *) g.rsig.p;
+	da.off = (const uint64_t *) g.off.p;
+	da.nsamp = (const uint32_t *) g.nsamp.p;
+	da.out_n = (uint32_t *) g.outn.p;
+	pa.out = (uint8_t *) g.arena.p;
+	pa.out_off = (const uint64_t *) g.arena_off.p;
+	pa.out_len = (uint64_t *) g.lens.p;
+	if ((rc = launch_recode(rp, da, pa, s)))
+		return rc;
+	if (sig) {
+		if ((rc = fetch_samples(sig, off, n, out_n, nreads, order, s)))
+			return rc;
+	} else {
+		HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	}
+	return fetch_streams(out, out_off, rel, out_len, nreads, s);
+}

@@ -847,12 +847,26 @@ __device__ __forceinline__ void wave_lds_sync()
 //     (byte-wise gather, one copy of the code);
 //   * both write their per-lane and per-sub-tile running sums to a small wave-private LDS
 //     table, which also frees the registers a per-sub-tile array would take.
-template <bool KEY2, bool ZD, bool S5 = false>
-__global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a)
+//
+// FUSE (recode, press_hip_recode_batch): the samples go on to an exception-split press in the same call, and phase 3
+// holds what that press's pass A (k_ex_scan_chunked<false, HUFF>) would read them again for.  So the wave leaves, in the
+// PRESS-side descriptor of its chunk (f.first_chunk[read] + j: the two chunk tables hand out their ids by atomics of their
+// own), the quarter's exception count and flagged sub-tiles, the OR of the samples and zd[0] in ReadMeta and - FUSE 2, a
+// static-Huffman destination - the quarter's code bits; pass A is then not launched.  An exception there is the 16-BIT
+// wrapped zig-zag delta above 255, never sample 0: a plain sub-tile holds none (its values are single bytes, which the
+// 32-bit delta of slow5's stream is only where the wrapped one is the same byte); the others recompute it from the
+// deltas they have undone.
+__device__ __forceinline__ uint32_t exc_mask(const uint4 &z, uint32_t i0);
+__device__ __forceinline__ uint32_t low_mask(const uint4 &z, uint32_t i0, uint32_t n);
+template <bool KEY2, bool ZD, bool S5 = false, int FUSE = 0>
+__global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a, FuseArgs f)
 {
+	static_assert(!FUSE || ZD, "the fused counts are those of the zig-zag delta methods");
 #ifdef DEC_STAMPS
 	const uint64_t t_start = __builtin_amdgcn_s_memtime();
 #endif
+	// FUSE 2: code length of every one-byte value, 1 << 16 for a value without a code, [256] = 0 (as k_ex_scan_chunked)
+	__shared__ uint32_t s_len[FUSE == 2 ? 257 : 1];
 	__shared__ uint32_t s_ticket;
 	__shared__ uint32_t s_wsum[4];
 	__shared__ uint32_t s_sbase;
@@ -864,12 +878,20 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a)
 	const int w = (int) uni(threadIdx.x >> 6);
 	if (blockIdx.x >= uni(a.ctl->nchunks))
 		return; // (the grid is an upper bound: surplus workgroups draw no ticket - blockIdx only COUNTS the workgroups)
+	if (FUSE == 2) { // (visible behind the ticket's barrier)
+		const uint32_t l = f.huff->enc[threadIdx.x] >> 24;
+		s_len[threadIdx.x] = l ? l : 0x10000u;
+		if (threadIdx.x == 0)
+			s_len[256] = 0;
+	}
 #ifdef DEC_BLOCKIDX_TICKET
 	// DIAGNOSTIC BUILD ONLY (tools/build_variants.sh "tkb:-DDEC_BLOCKIDX_TICKET"): what the ticket in front of every
 	// workgroup costs.  Chunk ids from blockIdx rely on workgroups starting in the order of their ids, which HIP does not
 	// promise - the look-back can deadlock where they do not.  Measured: 0.58-0.61 instead of 0.66-0.69 ms.
 	const uint32_t t = blockIdx.x;
 	(void) s_ticket;
+	if (FUSE == 2)
+		__syncthreads();
 #else
 	if (threadIdx.x == 0)
 		s_ticket = atomicAdd(&a.ctl->ticket, 1u);
@@ -1028,6 +1050,10 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a)
 	for (int k = 0; k < CK; k++)
 		asm volatile("" : "+v"(dat[k].x), "+v"(dat[k].y));
 
+	// FUSE: the read's press-side chunk (none for a read k_svb_keyprefix has refused: its count went to the press as 0)
+	const bool fz = FUSE && uni(a.out_n[d.read]) != CFAIL32;
+	uint32_t f_kmask = 0, f_etot = 0, f_ored = 0, f_bits = 0, f_s0 = 0;
+
 	// ---- phase 3: expand again, prefix inside the lane, add the bases, store
 #pragma unroll
 	for (int k = 0; k < CK; k++) {
@@ -1048,6 +1074,18 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a)
 			}
 			if (i0 < n)
 				st16_stream(out + i0, make_uint4(v[0], v[1], v[2], v[3]));
+			if (FUSE && i0 < n) { // one-byte values only: no exception; their code lengths straight from the stream's bytes
+				f_ored |= v[0] | v[1] | v[2] | v[3];
+				if (k == 0)
+					f_s0 = v[0];
+				if (FUSE == 2) {
+#pragma unroll
+					for (int h = 0; h < 8; h++) {
+						const uint32_t b = ((h < 4 ? dat[k].x : dat[k].y) >> (8 * (h & 3))) & 0xFFu;
+						f_bits += s_len[h == 0 && i0 == 0 ? 256u : b]; // (sample 0 is stored raw)
+					}
+				}
+			}
 		}
 	}
 	for (uint32_t m = kmask; m; m &= m - 1) {
@@ -1059,12 +1097,40 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a)
 #pragma unroll
 			for (int q = 0; q < 4; q++)
 				v[q] = unzz_pair_hib(v[q], hib, q);
+			uint4 z = make_uint4(0, 0, 0, 0);
+			if (FUSE) { // zig-zag of the 16-bit deltas again: what the press side calls zd (zeros at or beyond n: gather_slow)
+				const s16x2 d0 = __builtin_bit_cast(s16x2, v[0]), d1 = __builtin_bit_cast(s16x2, v[1]),
+					    d2 = __builtin_bit_cast(s16x2, v[2]), d3 = __builtin_bit_cast(s16x2, v[3]);
+				z = make_uint4(__builtin_bit_cast(uint32_t, (d0 << 1) ^ (d0 >> 15)), __builtin_bit_cast(uint32_t, (d1 << 1) ^ (d1 >> 15)),
+					       __builtin_bit_cast(uint32_t, (d2 << 1) ^ (d2 >> 15)), __builtin_bit_cast(uint32_t, (d3 << 1) ^ (d3 >> 15)));
+			}
 			(void) lane_prefix8(v);
 			const uint32_t b16 = (sb + uni(s_sub[w][k]) + s_xl[w][k][lane]) & 0xFFFFu;
 			const uint32_t b2 = b16 | (b16 << 16);
 #pragma unroll
 			for (int q = 0; q < 4; q++)
 				v[q] = pk_add16(v[q], b2);
+			if (FUSE) {
+				const uint32_t nv = i0 + 8 <= n ? 8u : (i0 < n ? n - i0 : 0u);
+				if (k == 0)
+					f_s0 = v[0];
+#pragma unroll
+				for (int h = 0; h < 4; h++) // samples at or beyond n count nothing
+					f_ored |= nv >= (uint32_t) (2 * h + 2) ? v[h] : nv == (uint32_t) (2 * h + 1) ? (v[h] & 0xFFFFu) : 0u;
+				const uint32_t em = exc_mask(z, i0);
+				if (__ballot(em != 0)) {
+					f_kmask |= 1u << k;
+					const uint32_t inc = wave_incl_scan_dpp(__popc(em));
+					f_etot += (uint32_t) __builtin_amdgcn_readlane((int) inc, 63);
+				}
+				if (FUSE == 2) {
+					const uint32_t zz[4] = { z.x, z.y, z.z, z.w };
+					const uint32_t lowm = low_mask(z, i0, n);
+#pragma unroll
+					for (int h = 0; h < 8; h++)
+						f_bits += s_len[((lowm >> h) & 1u) ? ((zz[h >> 1] >> (16 * (h & 1))) & 0xFFu) : 256u];
+				}
+			}
 		}
 		if (i0 + 8 <= n) {
 			st16_stream(out + i0, make_uint4(v[0], v[1], v[2], v[3]));
@@ -1073,6 +1139,33 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a)
 			for (uint32_t q = 0; q < 8; q++)
 				if (q < n - i0)
 					out[i0 + q] = (int16_t) (v[q >> 1] >> (16 * (q & 1)));
+		}
+	}
+	if (FUSE && fz) { // what pass A leaves for this quarter (k_ex_scan_chunked's tail)
+		const uint32_t pt = uni(f.first_chunk[d.read]) + d.j;
+		if (FUSE == 2) {
+			const uint32_t nocode = (f_bits >> 16) ? 0x80000000u : 0u; // a value the table has no code for
+			const uint32_t inc = wave_incl_scan_dpp(f_bits & 0xFFFFu);
+			if (lane == 63)
+				f.cbits[pt].q[w] = inc;
+			f_ored = ((f_ored | (f_ored >> 16)) & 0xFFFFu) | nocode;
+		} else {
+			f_ored = (f_ored | (f_ored >> 16)) & 0xFFFFu;
+		}
+		if (ws < n) {
+#pragma unroll
+			for (int dd = 32; dd >= 1; dd >>= 1)
+				f_ored |= (uint32_t) __shfl_xor((int) f_ored, dd, 64);
+			ReadMeta *m = f.meta + d.read;
+			if (lane == 0) {
+				atomicOr(&m->ored, f_ored);
+				f.chunks[pt].ecnt[w] = f_etot;
+				f.chunks[pt].kmask[w] = (uint16_t) f_kmask;
+				if (ws == 0) { // zd[0]: the zig-zag of sample 0 itself
+					const int32_t s0 = (int16_t) f_s0;
+					m->zd0 = (uint32_t) ((s0 << 1) ^ (s0 >> 15)) & 0xFFFFu;
+				}
+			}
 		}
 	}
 	STAMP(6);
@@ -2168,25 +2261,117 @@ static void run_decode(const DecodeArgs &a, hipStream_t s)
 	hipLaunchKernelGGL((k_svb_keyscan<KEY2, S5>), dim3((a.max_chunks + 3) / 4), dim3(CWG), 0, s, a);
 	hipLaunchKernelGGL((k_svb_keyprefix<KEY2, S5>), dim3((a.nreads + 3) / 4), dim3(256), 0, s, a);
 	ktime_begin(1, s);
-	hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, ZD, S5>), dim3(a.max_chunks), dim3(CWG), 0, s, a);
+	hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, ZD, S5>), dim3(a.max_chunks), dim3(CWG), 0, s, a, FuseArgs{});
 	ktime_end(1, s);
 }
 
-// exception-split encode: chunked scan, section per read, chunked pass B
-void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s)
+static uint64_t n_pass_a = 0; // launches of k_ex_scan_chunked<false, ..> so far (press_hip_debug_pass_a_launches)
+extern "C" uint64_t press_hip_debug_pass_a_launches(void) { return n_pass_a; }
+
+// exception-split encode: chunk table and ReadMeta of the batch ...
+static void ex_encode_prep(const BatchArgs &a, hipStream_t s)
 {
-	const bool huff = ent == 1;
-	if (!a.nreads || !a.max_chunks)
-		return;
 	(void) hipMemsetAsync(a.ctl, 0, sizeof(ChunkCtl), s);
 	hipLaunchKernelGGL((k_chunk_prep<false, false>), dim3((a.nreads + 255) / 256), dim3(256), 0, s, a.off,
 			   a.nsamp, a.out_off, (const uint64_t *) nullptr, a.nreads, a.chunks, a.gran, a.ctl,
 			   a.max_chunks, a.out_len, (uint32_t *) nullptr, a.first_chunk, a.meta);
+}
+
+static void ex_encode_tail(const BatchArgs &a, int fmt, int ent, hipStream_t s);
+
+// ... chunked scan (pass A), section per read, chunked pass B
+void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s)
+{
+	if (!a.nreads || !a.max_chunks)
+		return;
+	ex_encode_prep(a, s);
 	// surplus workgroups (max_chunks bounds the real count from above) exit at once
-	if (huff)
+	n_pass_a++;
+	if (ent == 1)
 		hipLaunchKernelGGL((k_ex_scan_chunked<false, true>), dim3(a.max_chunks), dim3(CWG), 0, s, a);
 	else
 		hipLaunchKernelGGL((k_ex_scan_chunked<false>), dim3(a.max_chunks), dim3(CWG), 0, s, a);
+	ex_encode_tail(a, fmt, ent, s);
+}
+
+// Recode, fused (press_hip_recode_batch): the svb decode of `d` leaves pass A's results in the chunk table of the press
+// `p`, whose sample counts p.nsamp are the decoder's verdicts (0 for a read it refuses) - known before the main kernel
+// runs, k_svb_keyprefix gives them.  d.sig == p.sig, d.off == p.off; the two sides have a chunk table, a first-chunk list
+// and a control block each.
+template <bool KEY2, bool S5>
+static void run_recode(const DecodeArgs &d, const BatchArgs &p, int fmt, int ent, hipStream_t s)
+{
+	(void) hipMemsetAsync(d.ctl, 0, sizeof(ChunkCtl), s);
+	hipLaunchKernelGGL((k_chunk_prep<true, KEY2>), dim3((d.nreads + 255) / 256), dim3(256), 0, s, d.off,
+			   d.nsamp, d.in_off, d.in_len, d.nreads, d.chunks, d.gran, d.ctl, d.max_chunks,
+			   (uint64_t *) nullptr, d.out_n, d.first_chunk, (ReadMeta *) nullptr, d.in,
+			   S5 ? 4u : 0u);
+	hipLaunchKernelGGL((k_svb_keyscan<KEY2, S5>), dim3((d.max_chunks + 3) / 4), dim3(CWG), 0, s, d);
+	hipLaunchKernelGGL((k_svb_keyprefix<KEY2, S5>), dim3((d.nreads + 3) / 4), dim3(256), 0, s, d);
+	launch_recode_counts(d.out_n, const_cast<uint32_t *>(p.nsamp), d.nreads, s);
+	ex_encode_prep(p, s);
+	const FuseArgs f = { p.chunks, p.first_chunk, p.cbits, p.meta, p.huff };
+	ktime_begin(1, s);
+	if (ent == 1)
+		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 2>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
+	else
+		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 1>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
+	ktime_end(1, s);
+	ex_encode_tail(p, fmt, ent, s);
+}
+
+void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent, hipStream_t s)
+{
+	if (!d.nreads || !d.max_chunks)
+		return;
+	if (slow5)
+		run_recode<true, true>(d, p, fmt, ent, s);
+	else if (key2bit)
+		run_recode<true, false>(d, p, fmt, ent, s);
+	else
+		run_recode<false, false>(d, p, fmt, ent, s);
+}
+
+// n[r] = out_n[r], 0 for a read the decoder refused: the sample counts of the press half of a recode
+__global__ __launch_bounds__(256) void k_recode_counts(const uint32_t *out_n, uint32_t *n, uint32_t nreads)
+{
+	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+	if (r < nreads)
+		n[r] = out_n[r] == CFAIL32 ? 0u : out_n[r];
+}
+void launch_recode_counts(const uint32_t *out_n, uint32_t *n, uint32_t nreads, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_recode_counts, dim3((nreads + 255) / 256), dim3(256), 0, s, out_n, n, nreads);
+}
+
+// A refused read's slot stays as it was.  The press half sees it as an empty read, for which the formats that store a
+// count (slow5_svb_zd, the zstd frames over svb) write a stream of a few bytes: the head of such a slot is kept
+// aside (save) and put back, with out_len = PRESS_HIP_FAILED for every refused read (!save).
+__global__ __launch_bounds__(256) void k_recode_refused(const uint32_t *out_n, uint8_t *out, const uint64_t *out_off,
+							  uint64_t *out_len, uint8_t *keep, uint32_t nreads, int save)
+{
+	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+	if (r >= nreads || out_n[r] != CFAIL32)
+		return;
+	if (keep) {
+		const uint64_t cap = out_off[r + 1] - out_off[r];
+		const uint32_t nb = cap < RECODE_KEEP ? (uint32_t) cap : RECODE_KEEP;
+		uint8_t *slot = out + out_off[r], *k = keep + (size_t) r * RECODE_KEEP;
+		for (uint32_t b = 0; b < nb; b++)
+			(save ? k[b] : slot[b]) = save ? slot[b] : k[b];
+	}
+	if (!save)
+		out_len[r] = CFAIL64;
+}
+void launch_recode_refused(const uint32_t *out_n, const BatchArgs &p, uint8_t *keep, bool save, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_recode_refused, dim3((p.nreads + 255) / 256), dim3(256), 0, s, out_n, p.out, p.out_off, p.out_len,
+			   keep, p.nreads, save ? 1 : 0);
+}
+
+static void ex_encode_tail(const BatchArgs &a, int fmt, int ent, hipStream_t s)
+{
+	const bool huff = ent == 1;
 	if (fmt == EXF_EXZD) {
 		// second scan on the shifted samples for reads with q > 0
 		hipLaunchKernelGGL(k_ex_redo_flag, dim3((a.nreads + 255) / 256), dim3(256), 0, s, a);

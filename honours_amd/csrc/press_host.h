@@ -64,8 +64,10 @@ struct Ctx {
 	// scratch shared by both modes
 	DevBuf meta, ex_pos, ex_val, low, huff, chunks, gran, ctl, first_chunk, htiles, hunit, hrec, hlist, hread, hwave, hbits, hend, hmin, cbits;
 	DevBuf ztmp, zoff, zoff4, zlen, zhist, ztab, zfirst, zblk, zsbits, zbpos, zbflag, zkcnt, zrd, znb, zn, zdcopy, zdhuf, zdunit, zdtree, zdlong, zdctl, zdseq, zdxblk; // zstd frames
+	DevBuf rsig, rn, rkeep, pchunks, pfirst, pctl; // recode: samples nobody asked for, the press half's counts, refused reads' slot heads, its chunk table
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
+	DevBuf rin, rin_off; // ... of recode: the source streams
 	uint32_t zs_nhost = 0; // frames the last zstd depress batch left to libzstd
 	uint32_t *zs_pin = nullptr; // page-locked: that count comes back while the device goes on with the batch
 	hipEvent_t zs_ev = nullptr;
@@ -169,7 +171,7 @@ struct ScratchPlan {
 	struct Row {
 		DevBuf Ctx::*buf;
 		size_t bytes;
-	} rows[42]; // at most one per scratch DevBuf of Ctx
+	} rows[48]; // at most one per scratch DevBuf of Ctx
 	int nrows;
 	ScratchPlan &need(DevBuf Ctx::*buf, size_t bytes); // a buffer named twice keeps the larger size
 	int reserve() const;
@@ -179,6 +181,19 @@ struct ScratchPlan {
 	ZsBufs zs() const;                 // z with its pointers
 };
 ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool decode);
+
+// press_hip_recode_batch: src's streams -> samples -> dst's streams in one call.  d and p are the plans the two batch calls
+// would make (their bind()s and counts serve the two halves); `all` is what the call reserves: every buffer at the larger
+// of what press and depress of either method ask of it (a caller that mixes the three calls on one batch shape never sees
+// a buffer grow), the press half's sample counts, the samples when the caller keeps none, and for a fused pair the press
+// half's own chunk table.
+struct RecodePlan {
+	ScratchPlan d, p, all;
+	bool fused;      // pass A's results come from the svb decode kernel (recode_fused)
+	bool keep_heads; // dst writes a stream for an empty read: a refused read's slot head is kept aside
+};
+bool recode_fused(int src, int dst);
+RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples);
 
 int check_method(int method); // EARG / ENOTABLE
 int launch_status();          // EHIP if a kernel launch since the last call failed

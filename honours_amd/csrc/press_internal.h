@@ -289,6 +289,20 @@ void launch_zstd_encode(const BatchArgs &a, const ZsBufs &z, hipStream_t s); // 
 void launch_zstd_decode_frames(const DecodeArgs &a, const ZsBufs &z, hipStream_t s);
 void launch_zstd_decode_streams(const DecodeArgs &a, const ZsBufs &z, hipStream_t s);
 
+// Recode (press_hip_recode_batch): where the fused svb decode leaves pass A's results - the chunk table, first-chunk
+// list, code-bit counts and ReadMeta of the PRESS half of the call, and its table (k_svb_decode_chunked<.., FUSE>)
+struct FuseArgs {
+	ChunkDesc *chunks;
+	const uint32_t *first_chunk;
+	ChunkBits *cbits;
+	ReadMeta *meta;
+	const HuffDev *huff;
+};
+constexpr uint32_t RECODE_KEEP = 64; // bytes of a refused read's slot kept aside (an empty read's stream is 4 / 16 bytes)
+void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent, hipStream_t s);
+void launch_recode_counts(const uint32_t *out_n, uint32_t *n, uint32_t nreads, hipStream_t s);
+void launch_recode_refused(const uint32_t *out_n, const BatchArgs &p, uint8_t *keep, bool save, hipStream_t s);
+
 // Optional timing of the dominant kernel of a batch call with HIP events recorded on the
 // launch stream (bench.py's roofline figure): launchers call these around that kernel.
 void ktime_begin(int which, hipStream_t s); // which: 0 = press, 1 = depress

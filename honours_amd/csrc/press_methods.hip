@@ -135,6 +135,40 @@ ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool 
 	return p;
 }
 
+// Fused pairs: BLOW5's and the reference's svb-zd streams into any exception-split method.  (svb12 has no deltas; the zstd
+// kinds and the svb destinations take the general path.)
+bool recode_fused(int src, int dst)
+{
+	if (!method_ok(src) || !method_ok(dst))
+		return false;
+	return METHODS[src].family == FAM_SVB && METHODS[src].zd && METHODS[dst].family == FAM_EX;
+}
+
+RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples)
+{
+	RecodePlan r{};
+	r.d = make_plan(src, total_samples, nreads, true);
+	r.p = make_plan(dst, total_samples, nreads, false);
+	r.fused = recode_fused(src, dst);
+	const Method &m = METHODS[dst];
+	r.keep_heads = (m.family == FAM_SVB && m.slow5) || (m.family == FAM_ZSTD && m.kdiv);
+	r.all = r.d;
+	const ScratchPlan others[3] = { r.p, make_plan(src, total_samples, nreads, false), make_plan(dst, total_samples, nreads, true) };
+	for (const ScratchPlan &o : others)
+		for (int i = 0; i < o.nrows; i++)
+			r.all.need(o.rows[i].buf, o.rows[i].bytes);
+	const size_t nr = (size_t) nreads + 1;
+	r.all.need(&Ctx::rn, nr * 4);
+	if (!keep_samples)
+		r.all.need(&Ctx::rsig, total_samples * 2 + 64);
+	if (r.keep_heads)
+		r.all.need(&Ctx::rkeep, nr * RECODE_KEEP);
+	if (r.fused)
+		r.all.need(&Ctx::pchunks, (size_t) r.p.max_chunks * sizeof(ChunkDesc)).need(&Ctx::pfirst, nr * 4)
+			.need(&Ctx::pctl, 2 * sizeof(ChunkCtl));
+	return r;
+}
+
 // Most fields of the argument blocks carry the name of the buffer behind them (ZsBufs: without its z)
 #define BIND(x, f, buf) x.f = (decltype(x.f)) ptr(&Ctx::buf)
 #define B(f) BIND(a, f, f)
@@ -189,6 +223,21 @@ extern "C" uint64_t press_hip_workspace_bytes(int method, uint64_t total_samples
 		b += p.rows[i].bytes;
 	return b;
 }
+
+extern "C" uint64_t press_hip_recode_workspace_bytes(int src_method, int dst_method, uint64_t total_samples, uint32_t nreads,
+						     int keep_samples)
+{
+	API_LOCK;
+	if (!method_ok(src_method) || !method_ok(dst_method))
+		return 0;
+	const RecodePlan r = make_recode_plan(src_method, dst_method, total_samples, nreads, keep_samples != 0);
+	uint64_t b = is_shuff(METHODS[src_method]) || is_shuff(METHODS[dst_method]) ? sizeof(HuffDev) : 0;
+	for (int i = 0; i < r.all.nrows; i++)
+		b += r.all.rows[i].bytes;
+	return b;
+}
+
+extern "C" int press_hip_recode_fused(int src_method, int dst_method) { return recode_fused(src_method, dst_method) ? 1 : 0; }
 
 int ph::check_method(int method)
 {

@@ -73,6 +73,7 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_get_stream",
      "press_hip_synchronize", "press_hip_load_table_file", "press_hip_set_table", "press_hip_bound",
      "press_hip_press_batch", "press_hip_depress_batch", "press_hip_workspace_bytes",
+     "press_hip_recode_batch", "press_hip_recode_workspace_bytes", "press_hip_recode_fused",
      "press_hip_kernel_timing", "press_hip_kernel_times",
      "press_hip_slow5_ptr_compress_svb_zd", "press_hip_slow5_ptr_depress_svb_zd",
      "press_hip_blow5_open", "press_hip_blow5_close", "press_hip_blow5_methods", "press_hip_blow5_next",
@@ -116,6 +117,18 @@ def load_library(path=LIB_PATH):
                                                  ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                  ctypes.c_int]
+        _lib.press_hip_recode_batch.restype = ctypes.c_int
+        _lib.press_hip_recode_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_recode_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_recode_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+                                                          ctypes.c_int]
+        _lib.press_hip_recode_fused.restype = ctypes.c_int
+        _lib.press_hip_recode_fused.argtypes = [ctypes.c_int, ctypes.c_int]
+        _lib.press_hip_debug_pass_a_launches.restype = ctypes.c_uint64
+        _lib.press_hip_debug_pass_a_launches.argtypes = []
         libc = ctypes.CDLL(None)
         libc.fopen.restype = ctypes.c_void_p
         libc.fopen.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
@@ -336,6 +349,63 @@ def depress_batch(method, comp, in_off, in_len, sig, off, n, out_n):
                                      out_n.data_ptr(), 1)
     if rc:
         raise PressError(last_error())
+
+
+def recode_batch(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, out_n, sig=None, total_samples=None):
+    """Enqueue the recoding of a batch of `src` streams into `dst` streams (CUDA tensors as in depress_batch and
+    press_batch).  sig: the int16 tensor that also receives the decoded samples, or None - they then stay in library
+    scratch and total_samples (the extent of the layout off / n) must be given."""
+    lib = load_library()
+    nreads = off.numel()
+    if sig is None and total_samples is None:
+        raise PressError("recode_batch without sig needs total_samples")
+    total = sig.numel() if total_samples is None else int(total_samples)
+    rc = lib.press_hip_recode_batch(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
+                                    n.data_ptr(), off.data_ptr(), nreads, total, out.data_ptr(), out_off.data_ptr(),
+                                    out_len.data_ptr(), None if sig is None else sig.data_ptr(), out_n.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def recode_fused(src, dst):
+    """True where the press half's first pass comes out of the decode kernel (press_hip_recode_fused)"""
+    return bool(load_library().press_hip_recode_fused(_mid(src), _mid(dst)))
+
+
+def pass_a_launches():
+    """test aid: launches of the exception-split press's first pass over the samples so far in this process"""
+    return int(load_library().press_hip_debug_pass_a_launches())
+
+
+def recode_batch_host(src, dst, streams, ns, caps=None, want_samples=False):
+    """Recode with host buffers: streams = list of bytes of method `src`, ns = sample counts / rooms ->
+    list of bytes of method `dst` (None: the read failed); with want_samples -> (streams, list of int16 arrays)."""
+    lib = load_library()
+    nreads = len(streams)
+    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+    in_off = np.zeros(nreads, dtype=np.uint64)
+    if nreads > 1:
+        in_off[1:] = np.cumsum(in_len)[:-1]
+    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
+    ns = np.asarray(ns, dtype=np.uint32)
+    off, total = _layout(ns)
+    if caps is None:
+        caps = [int(lib.press_hip_bound(_mid(dst), int(x))) + 1024 if x else 64 for x in ns]
+    out_off = np.zeros(nreads + 1, dtype=np.uint64)
+    out_off[1:] = np.cumsum((np.asarray(caps, dtype=np.uint64) + 15) // 16 * 16)
+    out = np.zeros(int(out_off[-1]) + 64, dtype=np.uint8)
+    out_len = np.zeros(nreads, dtype=np.uint64)
+    out_n = np.zeros(nreads, dtype=np.uint32)
+    sig = np.zeros(total + 64, dtype=np.int16) if want_samples else None
+    rc = lib.press_hip_recode_batch(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
+                                    ns.ctypes.data, off.ctypes.data, nreads, total, out.ctypes.data, out_off.ctypes.data,
+                                    out_len.ctypes.data, sig.ctypes.data if want_samples else None, out_n.ctypes.data, 0)
+    if rc:
+        raise PressError(last_error())
+    res = [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
+    if not want_samples:
+        return res
+    return res, [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)]
 
 
 def _layout(ns):

@@ -331,7 +331,36 @@ int press_hip_depress_batch(int method, const uint8_t *in, const uint64_t *in_of
 			    uint32_t *out_n, int device_resident);
 
 /*
- * PRESS_HIP_ZSTD_SVB_ZD, _ZSTD_SVB12_ZD and _ZSTD_HASGAM_ZDQ in the two calls above (SURVEY.md 8f-3,
+ * Recode nreads streams of src_method into streams of dst_method: what press_hip_depress_batch(src_method) followed by
+ * press_hip_press_batch(dst_method) give on the same buffers - out, out_len, out_n and sig byte for byte - in one call,
+ * for every pair of methods.
+ *   in/in_off/in_len/n/off/total_samples/out_n   as in press_hip_depress_batch
+ *   out/out_off/out_len                          as in press_hip_press_batch; the sample counts of that half are out_n
+ *   sig      the decoded samples as press_hip_depress_batch leaves them (decode for the basecaller, archive in the better
+ *            format), or NULL: they then live in library scratch, total_samples int16 at the caller's off[]
+ * A read whose source stream is refused gets out_n[r] = UINT32_MAX and out_len[r] = PRESS_HIP_FAILED; its slot and its
+ * neighbours stay untouched.  Whatever the two calls refuse is refused here (the method checks, PRESS_HIP_ENOTABLE, the
+ * alignment rules, overlapping rooms on the host path).  device_resident != 0: the call only enqueues (the zstd sources
+ * keep the host wait described below); == 0: host pointers through the page-locked staging, synchronous.
+ * press_hip_recode_fused(src, dst) == 1 (svb12_zd, svb_zd, slow5_svb_zd into any exception-split, static-Huffman, ex-zd
+ * or range-coder method): the press half's first pass over the samples - its exception and code-bit counts - is left
+ * behind by the svb decode kernel, which holds those very values in registers; the other pairs run the two halves as
+ * they are.  Host arithmetic, no GPU needed.
+ * press_hip_recode_workspace_bytes: the device scratch the call keeps for a batch of this shape, exact as
+ * press_hip_workspace_bytes is: every buffer at the larger of what the batch calls of either method ask of it, the press
+ * half's counts, the press half's own chunk table for a fused pair, and - keep_samples == 0, i.e. sig == NULL - the
+ * samples.  0 for a method id out of range.
+ */
+int press_hip_recode_batch(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
+			   const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+			   uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+			   int16_t *sig, uint32_t *out_n, int device_resident);
+uint64_t press_hip_recode_workspace_bytes(int src_method, int dst_method, uint64_t total_samples, uint32_t nreads,
+					  int keep_samples);
+int press_hip_recode_fused(int src_method, int dst_method);
+
+/*
+ * PRESS_HIP_ZSTD_SVB_ZD, _ZSTD_SVB12_ZD and _ZSTD_HASGAM_ZDQ in the calls above (SURVEY.md 8f-3,
  * replaces the ZSTD_compress / ZSTD_decompress calls of press.c:1860-1910, 2020-2070, 8549-8589 for batches):
  *   press    writes one standard zstd frame (RFC 8878) per read whose content is the buffer
  *            the reference hands to ZSTD_compress ([u32 n][svb stream], or the ex-zd stream): a raw
