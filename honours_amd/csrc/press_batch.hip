@@ -389,6 +389,143 @@ static int fetch_streams(uint8_t *out, const uint64_t *out_off, const std::vecto
 	return 0;
 }
 
+// ------------------------------------------------------------------ packed press: the library lays the arena out
+
+// what both packed calls check before any device call
+static int packed_args_ok(int method, uint32_t align)
+{
+	if (!method_ok(method))
+		return set_error(PRESS_HIP_EARG, "method %d is not available in the batch API", method);
+	if (align == 0 || align > 4096 || (align & (align - 1)))
+		return set_error(PRESS_HIP_EARG, "align = %u is not a power of two in 1 .. 4096", align);
+	return 0;
+}
+
+// the head of their host-pointer form: the checks of press_hip_press_batch, then samples and layout on the device
+static int packed_stage(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, uint64_t total_samples,
+			BatchArgs &a, hipStream_t s)
+{
+	int rc;
+	std::vector<uint32_t> order;
+	if ((rc = check_disjoint(off, n, nreads, "the sample range", order)))
+		return rc;
+	if ((rc = stage_layout(off, n, nreads, total_samples, s)))
+		return rc;
+	if ((rc = h2d(g.sig.p, sig, total_samples * 2, s)))
+		return rc;
+	a.sig = (const int16_t *) g.sig.p;
+	a.off = (const uint64_t *) g.off.p;
+	a.nsamp = (const uint32_t *) g.nsamp.p;
+	return 0;
+}
+
+extern "C" int press_hip_press_sizes(int method, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				     uint64_t total_samples, uint64_t *need, int device_resident)
+{
+	API_LOCK;
+	int rc = packed_args_ok(method, 1);
+	if (rc || (rc = ctx_init()) || (rc = check_method(method)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	if (!sig || !off || !n || !need)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_packed_plan(method, total_samples, nreads);
+	if ((rc = plan.reserve()))
+		return rc;
+	BatchArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	PackArgs pk = { device_resident ? need : (uint64_t *) g.pneed.p, nullptr, (uint64_t *) g.pslot.p, 0, 1 };
+	a.out_off = pk.slot;
+	a.out_len = pk.need; // (an empty read's verdict of k_chunk_prep; the size kernel has the last word)
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		a.sig = sig;
+		a.off = off;
+		a.nsamp = n;
+		return launch_press_packed(plan, a, pk, PACK_SIZE, s);
+	}
+	if ((rc = packed_stage(sig, off, n, nreads, total_samples, a, s)) || (rc = launch_press_packed(plan, a, pk, PACK_SIZE, s)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(need, pk.need, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
+extern "C" int press_hip_press_packed(int method, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				      uint64_t total_samples, uint8_t *out, uint64_t out_cap, uint32_t align,
+				      uint64_t *out_off, uint64_t *out_len, int device_resident)
+{
+	API_LOCK;
+	int rc = packed_args_ok(method, align);
+	if (rc || (rc = ctx_init()) || (rc = check_method(method)))
+		return rc;
+	if (!out_off)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	if (nreads == 0) { // an empty batch has a layout too
+		if (device_resident)
+			HIPCHK(hipMemsetAsync(out_off, 0, 8, g.stream()));
+		else
+			out_off[0] = 0;
+		return 0;
+	}
+	if (!sig || !off || !n || !out_len || (!out && out_cap))
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_packed_plan(method, total_samples, nreads);
+	if ((rc = plan.reserve()))
+		return rc;
+	BatchArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	PackArgs pk = { (uint64_t *) g.pneed.p, out_off, (uint64_t *) g.pslot.p, out_cap, align };
+	a.out_off = pk.slot;
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		a.sig = sig;
+		a.off = off;
+		a.nsamp = n;
+		a.out = out;
+		a.out_len = out_len;
+		return launch_press_packed(plan, a, pk, PACK_SIZE | PACK_WRITE, s);
+	}
+
+	// host pointers: stage, size and lay out, read the arena's size back, press into an arena of that size, copy its
+	// prefix back in one piece
+	if (g.arena_off.reserve(((size_t) nreads + 1) * 8) || g.lens.reserve((size_t) nreads * 8))
+		return PRESS_HIP_EHIP;
+	pk.layout = (uint64_t *) g.arena_off.p;
+	a.out_len = (uint64_t *) g.lens.p;
+	if ((rc = packed_stage(sig, off, n, nreads, total_samples, a, s)) || (rc = launch_press_packed(plan, a, pk, PACK_SIZE, s)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(out_off, pk.layout, ((size_t) nreads + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s)); // the one synchronisation besides the last: the arena's size
+	const uint64_t bytes = out_off[nreads] < out_cap ? out_off[nreads] : out_cap; // what a read that fits can touch
+	if (g.arena.reserve(bytes + 64))
+		return PRESS_HIP_EHIP;
+	// (padding and the gaps of the range coders travel with the streams: they reach the caller as zeros)
+	if (bytes)
+		HIPCHK(hipMemsetAsync(g.arena.p, 0, bytes, s));
+	a.out = (uint8_t *) g.arena.p;
+	if ((rc = launch_press_packed(plan, a, pk, PACK_WRITE, s)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(out_len, g.lens.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	if (bytes <= DIRECT_MAX || is_pinned(out)) { // small, or page-locked: one DMA
+		if (bytes)
+			HIPCHK(hipMemcpyAsync(out, g.arena.p, bytes, hipMemcpyDeviceToHost, s));
+	} else {
+		const std::vector<Piece> pc = { { out, 0, bytes } };
+		if ((rc = staged_pieces<false>((uint8_t *) g.arena.p, bytes, pc, s)))
+			return rc;
+	}
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
 #ifndef TRAIN_WG_PER_CU
 #define TRAIN_WG_PER_CU 2 // workgroups per CU of k_symbol_count's persistent grid
 #endif

@@ -185,14 +185,18 @@ __device__ __forceinline__ ChunkU load_chunk(const ChunkDesc *dp)
 // One thread per read: a wave adds up its reads' chunk counts, takes a contiguous range of
 // chunk ids with ONE atomic (ids need only be contiguous and ascending within a read),
 // writes the descriptors and clears the look-back granules of its chunks.
-template <bool DEC, bool KEY2>
+// EXACT (the packed press of the svb kinds, press_hip_press_packed): slot_off is the layout the library made from the
+// streams' own lengths need[], so a slot is not the format's worst case: the read is written iff it lies inside out_cap.
+template <bool DEC, bool KEY2, bool EXACT = false>
 __global__ __launch_bounds__(256) void k_chunk_prep(const uint64_t *off, const uint32_t *nsamp,
 						    const uint64_t *slot_off, const uint64_t *in_len,
 						    uint32_t nreads, ChunkDesc *chunks, uint64_t *gran,
 						    ChunkCtl *ctl, uint32_t max_chunks, uint64_t *out_len,
 						    uint32_t *out_n, uint32_t *first_chunk, ReadMeta *meta = nullptr,
-						    const uint8_t *in = nullptr, uint32_t hdr = 0, uint8_t *out = nullptr)
+						    const uint8_t *in = nullptr, uint32_t hdr = 0, uint8_t *out = nullptr,
+						    const uint64_t *need = nullptr, uint64_t out_cap = 0)
 {
+	static_assert(!EXACT || !DEC, "the exact slots are press's");
 	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
 	uint32_t n = 0, nch = 0;
 	if (r < nreads) {
@@ -217,7 +221,9 @@ __global__ __launch_bounds__(256) void k_chunk_prep(const uint64_t *off, const u
 	const uint64_t sbase = slot_off[r];
 	// hdr = 4: the slow5 svb-zd stream (u32 sample count in front, values of up to 3 bytes)
 	uint32_t ok;
-	if (!DEC) {
+	if (EXACT) {
+		ok = need[r] <= out_cap && sbase <= out_cap - need[r];
+	} else if (!DEC) {
 		ok = (uint64_t) hdr + klen + (hdr ? 3ull : 2ull) * n <= slot_off[r + 1] - sbase;
 	} else {
 		ok = (uint64_t) hdr + klen <= in_len[r];
@@ -231,7 +237,8 @@ __global__ __launch_bounds__(256) void k_chunk_prep(const uint64_t *off, const u
 	if (n == 0) {
 		if (!DEC) {
 			if (hdr) {
-				ok = hdr <= slot_off[r + 1] - sbase;
+				if (!EXACT)
+					ok = hdr <= slot_off[r + 1] - sbase;
 				for (uint32_t b = 0; ok && b < hdr; b++)
 					out[sbase + b] = 0;
 			}
@@ -2249,6 +2256,45 @@ void launch_svb_encode_chunked(const BatchArgs &a, bool key2bit, bool zd, hipStr
 		run_encode<false, false>(a, s);
 }
 
+// Packed press of the svb kinds: the counting pass gives every stream's length, the scan the offsets; then the chunk
+// table is made against them (k_chunk_prep<.., EXACT>) and the encoder runs as it is - it stores no byte behind a
+// stream's end, so its neighbour may start there.
+template <bool KEY2, bool ZD, bool S5 = false>
+static void run_encode_packed(const BatchArgs &a, const PackArgs &pk, hipStream_t s)
+{
+	(void) hipMemsetAsync(a.ctl, 0, sizeof(ChunkCtl), s);
+	hipLaunchKernelGGL((k_chunk_prep<false, KEY2, true>), dim3((a.nreads + 255) / 256), dim3(256), 0, s, a.off,
+			   a.nsamp, (const uint64_t *) pk.layout, (const uint64_t *) nullptr, a.nreads, a.chunks, a.gran, a.ctl,
+			   a.max_chunks, a.out_len, (uint32_t *) nullptr, a.first_chunk, (ReadMeta *) nullptr,
+			   (const uint8_t *) nullptr, S5 ? 4u : 0u, a.out, (const uint64_t *) pk.need, pk.out_cap);
+	const uint32_t grid = a.max_chunks < PERSISTENT_GRID ? a.max_chunks : PERSISTENT_GRID;
+	ktime_begin(0, s);
+	hipLaunchKernelGGL((k_svb_encode_chunked<KEY2, ZD, S5>), dim3(grid), dim3(CWG), 0, s, a);
+	ktime_end(0, s);
+}
+
+void launch_svb_encode_packed(const BatchArgs &a, bool key2bit, bool zd, bool slow5, const PackArgs &pk, int phases,
+			      hipStream_t s)
+{
+	if (!a.nreads || !a.max_chunks)
+		return;
+	if (phases & PACK_SIZE) {
+		launch_pack_svb_sizes(a, key2bit, zd, slow5, pk.need, s);
+		if (pk.layout)
+			launch_pack_scan(pk, a.nreads, s);
+	}
+	if (!(phases & PACK_WRITE))
+		return;
+	if (slow5)
+		run_encode_packed<true, true, true>(a, pk, s);
+	else if (key2bit)
+		run_encode_packed<true, true>(a, pk, s);
+	else if (zd)
+		run_encode_packed<false, true>(a, pk, s);
+	else
+		run_encode_packed<false, false>(a, pk, s);
+}
+
 template <bool KEY2, bool ZD, bool S5 = false>
 static void run_decode(const DecodeArgs &a, hipStream_t s)
 {
@@ -2278,6 +2324,18 @@ static void ex_encode_prep(const BatchArgs &a, hipStream_t s)
 }
 
 static void ex_encode_tail(const BatchArgs &a, int fmt, int ent, hipStream_t s);
+static void ex_encode_lists(const BatchArgs &a, int fmt, hipStream_t s);
+static void ex_encode_streams(const BatchArgs &a, int fmt, int ent, hipStream_t s);
+
+// pass A (surplus workgroups - max_chunks bounds the real count from above - exit at once)
+static void ex_pass_a(const BatchArgs &a, int ent, hipStream_t s)
+{
+	n_pass_a++;
+	if (ent == 1)
+		hipLaunchKernelGGL((k_ex_scan_chunked<false, true>), dim3(a.max_chunks), dim3(CWG), 0, s, a);
+	else
+		hipLaunchKernelGGL((k_ex_scan_chunked<false>), dim3(a.max_chunks), dim3(CWG), 0, s, a);
+}
 
 // ... chunked scan (pass A), section per read, chunked pass B
 void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s)
@@ -2285,13 +2343,32 @@ void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t 
 	if (!a.nreads || !a.max_chunks)
 		return;
 	ex_encode_prep(a, s);
-	// surplus workgroups (max_chunks bounds the real count from above) exit at once
-	n_pass_a++;
-	if (ent == 1)
-		hipLaunchKernelGGL((k_ex_scan_chunked<false, true>), dim3(a.max_chunks), dim3(CWG), 0, s, a);
-	else
-		hipLaunchKernelGGL((k_ex_scan_chunked<false>), dim3(a.max_chunks), dim3(CWG), 0, s, a);
+	ex_pass_a(a, ent, s);
 	ex_encode_tail(a, fmt, ent, s);
+}
+
+// Packed press of the exception-split family.  PACK_SIZE: the chain up to the exception lists, with a.out_off = pk.slot
+// still all zeros (k_chunk_prep only notes a base it is given; the family's kernels do not look at cap_ok); k_ex_sizes -
+// the size half of k_ex_section - then knows every stream's length (the range coders': a bound), the scan lays the
+// arena out and the chunks learn their read's base.  PACK_WRITE: the section and the encoder as they are, against
+// pk.slot.  Pass A runs once.
+void launch_ex_encode_packed(const BatchArgs &a, int fmt, int ent, const PackArgs &pk, int phases, hipStream_t s)
+{
+	if (!a.nreads || !a.max_chunks)
+		return;
+	if (phases & PACK_SIZE) {
+		(void) hipMemsetAsync(pk.slot, 0, ((size_t) a.nreads + 1) * 8, s);
+		ex_encode_prep(a, s);
+		ex_pass_a(a, ent, s);
+		ex_encode_lists(a, fmt, s);
+		launch_ex_sizes(a, fmt, ent, pk.need, s);
+		if (pk.layout) {
+			launch_pack_scan(pk, a.nreads, s);
+			launch_pack_patch(a, pk.slot, s);
+		}
+	}
+	if (phases & PACK_WRITE)
+		ex_encode_streams(a, fmt, ent, s);
 }
 
 // Recode, fused (press_hip_recode_batch): the svb decode of `d` leaves pass A's results in the chunk table of the press
@@ -2371,7 +2448,13 @@ void launch_recode_refused(const uint32_t *out_n, const BatchArgs &p, uint8_t *k
 
 static void ex_encode_tail(const BatchArgs &a, int fmt, int ent, hipStream_t s)
 {
-	const bool huff = ent == 1;
+	ex_encode_lists(a, fmt, s);
+	ex_encode_streams(a, fmt, ent, s);
+}
+
+// what follows pass A: the exceptions of every read counted and listed ...
+static void ex_encode_lists(const BatchArgs &a, int fmt, hipStream_t s)
+{
 	if (fmt == EXF_EXZD) {
 		// second scan on the shifted samples for reads with q > 0
 		hipLaunchKernelGGL(k_ex_redo_flag, dim3((a.nreads + 255) / 256), dim3(256), 0, s, a);
@@ -2379,6 +2462,12 @@ static void ex_encode_tail(const BatchArgs &a, int fmt, int ent, hipStream_t s)
 	}
 	hipLaunchKernelGGL(k_ex_prefix, dim3((a.nreads + 3) / 4), dim3(256), 0, s, a, fmt == EXF_EXZD ? 1 : 0);
 	hipLaunchKernelGGL(k_ex_list, dim3((a.max_chunks + 3) / 4), dim3(CWG), 0, s, a);
+}
+
+// ... and the streams: section per read, chunked pass B
+static void ex_encode_streams(const BatchArgs &a, int fmt, int ent, hipStream_t s)
+{
+	const bool huff = ent == 1;
 	launch_ex_section(a, fmt, ent, s);
 	if (ent >= 2) { // range coder: the one-byte values go to a temporary, one lane (order 1: one workgroup) per read codes them
 		hipLaunchKernelGGL(k_low_encode_chunked<false>, dim3(a.max_chunks), dim3(CWG), 0, s, a);

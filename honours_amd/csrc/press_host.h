@@ -65,6 +65,7 @@ struct Ctx {
 	DevBuf meta, ex_pos, ex_val, low, huff, chunks, gran, ctl, first_chunk, htiles, hunit, hrec, hlist, hread, hwave, hbits, hend, hmin, cbits;
 	DevBuf ztmp, zoff, zoff4, zlen, zhist, ztab, zfirst, zblk, zsbits, zbpos, zbflag, zkcnt, zrd, znb, zn, zdcopy, zdhuf, zdunit, zdtree, zdlong, zdctl, zdseq, zdxblk; // zstd frames
 	DevBuf rsig, rn, rkeep, pchunks, pfirst, pctl; // recode: samples nobody asked for, the press half's counts, refused reads' slot heads, its chunk table
+	DevBuf pneed, pslot; // packed press: the reads' sizes, the slot table its writing kernels see (PackArgs)
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams
@@ -195,10 +196,15 @@ struct RecodePlan {
 bool recode_fused(int src, int dst);
 RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples);
 
+// press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
+ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);
+
 int check_method(int method); // EARG / ENOTABLE
 int launch_status();          // EHIP if a kernel launch since the last call failed
 int launch_press(const ScratchPlan &p, const BatchArgs &a, hipStream_t s);
 int launch_depress(const ScratchPlan &p, const DecodeArgs &a, hipStream_t s);
+// phases: PACK_SIZE | PACK_WRITE (press_internal.h); a.out_off must be pk.slot
+int launch_press_packed(const ScratchPlan &p, const BatchArgs &a, const PackArgs &pk, int phases, hipStream_t s);
 
 // ------------------------------------------------------------------ static Huffman table (press_table.hip)
 

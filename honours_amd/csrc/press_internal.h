@@ -284,6 +284,30 @@ struct ZsBufs {
 	uint32_t kdiv;        // samples per key byte of the inner stream: 4 (svb-zd), 8 (svb16-zd), 0: ex-zd (no keys)
 };
 void launch_zstd_encode(const BatchArgs &a, const ZsBufs &z, hipStream_t s); // press_zstd.hip
+
+// Packed press (press_hip_press_sizes / press_hip_press_packed, press_packed.hip): the library lays the arena out.
+// Every family's chain is cut in two: PACK_SIZE runs it up to the point where a read's length is known, writes need[]
+// and - with a layout - scans it into the offsets; PACK_WRITE runs the rest against those offsets.  The two halves
+// share the batch's scratch (chunk table, ReadMeta, the zstd plan), so nothing else may run between them.
+struct PackArgs {
+	uint64_t *need;    // [nreads] bytes read r takes (the range coders: an upper bound), PRESS_HIP_FAILED: refused
+	uint64_t *layout;  // [nreads + 1] the caller's out_off, written by the scan; NULL: sizes only
+	uint64_t *slot;    // [nreads + 1] the slot table the writing kernels see: layout[r] for a read that fits out_cap,
+	                   // and for one that does not the next fitting read's offset - a slot of no bytes, which every
+	                   // kernel refuses (k_pk_scan)
+	uint64_t out_cap;
+	uint32_t align;    // a power of two
+};
+constexpr int PACK_SIZE = 1, PACK_WRITE = 2;
+// most a range coder emits beyond the nlow bytes of its input (include/press_hip.h, press_hip_press_sizes)
+constexpr uint32_t RC_PACK_SLACK = 32;
+void launch_pack_svb_sizes(const BatchArgs &a, bool key2bit, bool zd, bool slow5, uint64_t *need, hipStream_t s); // press_packed.hip
+void launch_pack_scan(const PackArgs &pk, uint32_t nreads, hipStream_t s);
+void launch_pack_patch(const BatchArgs &a, const uint64_t *slot, hipStream_t s);
+void launch_ex_sizes(const BatchArgs &a, int fmt, int ent, uint64_t *need, hipStream_t s); // press_sections.hip
+void launch_svb_encode_packed(const BatchArgs &a, bool key2bit, bool zd, bool slow5, const PackArgs &pk, int phases, hipStream_t s);
+void launch_ex_encode_packed(const BatchArgs &a, int fmt, int ent, const PackArgs &pk, int phases, hipStream_t s);
+void launch_zstd_encode_packed(const BatchArgs &a, const ZsBufs &z, const PackArgs &pk, int phases, hipStream_t s);
 // decode in two steps: frames -> svb-zd streams in ztmp (reads the device leaves to libzstd
 // are counted in dctl->nhost and patched in by the caller), then the svb-zd decode
 void launch_zstd_decode_frames(const DecodeArgs &a, const ZsBufs &z, hipStream_t s);

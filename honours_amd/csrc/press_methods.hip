@@ -135,6 +135,14 @@ ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool 
 	return p;
 }
 
+ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads)
+{
+	ScratchPlan p = make_plan(method, total_samples, nreads, false);
+	const size_t nr = (size_t) nreads + 1;
+	p.need(&Ctx::pneed, nr * 8).need(&Ctx::pslot, nr * 8);
+	return p;
+}
+
 // Fused pairs: BLOW5's and the reference's svb-zd streams into any exception-split method.  (svb12 has no deltas; the zstd
 // kinds and the svb destinations take the general path.)
 bool recode_fused(int src, int dst)
@@ -237,6 +245,25 @@ extern "C" uint64_t press_hip_recode_workspace_bytes(int src_method, int dst_met
 	return b;
 }
 
+// as press_hip_workspace_bytes (a caller that mixes the calls on one batch shape never sees a buffer grow), and the
+// two tables of the packed plan
+extern "C" uint64_t press_hip_packed_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads)
+{
+	API_LOCK;
+	if (!method_ok(method))
+		return 0;
+	ScratchPlan p = make_packed_plan(method, total_samples, nreads);
+	const ScratchPlan d = make_plan(method, total_samples, nreads, true);
+	for (int i = 0; i < d.nrows; i++)
+		p.need(d.rows[i].buf, d.rows[i].bytes);
+	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
+	for (int i = 0; i < p.nrows; i++)
+		b += p.rows[i].bytes;
+	return b;
+}
+
+extern "C" int press_hip_packed_exact(int method) { return method_ok(method) && !is_rc(METHODS[method]) ? 1 : 0; }
+
 extern "C" int press_hip_recode_fused(int src_method, int dst_method) { return recode_fused(src_method, dst_method) ? 1 : 0; }
 
 int ph::check_method(int method)
@@ -264,6 +291,20 @@ int ph::launch_press(const ScratchPlan &p, const BatchArgs &a, hipStream_t s)
 	} else {
 		const ZsBufs z = p.zs();
 		launch_zstd_encode(a, z, s);
+	}
+	return launch_status();
+}
+
+int ph::launch_press_packed(const ScratchPlan &p, const BatchArgs &a, const PackArgs &pk, int phases, hipStream_t s)
+{
+	const Method &m = *p.m;
+	if (m.family == FAM_SVB) {
+		launch_svb_encode_packed(a, m.key2, m.zd, m.slow5, pk, phases, s);
+	} else if (m.family == FAM_EX) {
+		launch_ex_encode_packed(a, m.exfmt, m.ent, pk, phases, s);
+	} else {
+		const ZsBufs z = p.zs();
+		launch_zstd_encode_packed(a, z, pk, phases, s);
 	}
 	return launch_status();
 }

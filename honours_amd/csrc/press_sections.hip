@@ -290,6 +290,52 @@ __global__ __launch_bounds__(64) void k_ex_section(BatchArgs a, int fmt, int huf
 		a.out_len[r] = (uint64_t) hdr + seclen + nlow; // the Huffman pass B knows its own length
 }
 
+// The size half of k_ex_section for the packed press (press_hip_press_sizes / press_hip_press_packed): need[r] = the
+// bytes read r takes, PRESS_HIP_FAILED where k_ex_section refuses the read whatever its slot; nothing else is written.
+//   plain          hdr + seclen + nlow
+//   static Huffman hdr + seclen + 4 + the read's code bits (ChunkBits of its last chunk, k_ex_prefix) in whole bytes
+//   range coders   hdr + seclen + nlow + RC_PACK_SLACK: the smallest slot certain to hold the coded stream
+// One wave per read, after k_ex_list.
+__global__ __launch_bounds__(64) void k_ex_sizes(BatchArgs a, int fmt, int huff, uint64_t *need)
+{
+	const uint32_t r = blockIdx.x;
+	const uint32_t lane = threadIdx.x;
+	const uint64_t o0 = a.off[r];
+	const uint32_t n = a.nsamp[r];
+	const ReadMeta *m = a.meta + r;
+	const uint32_t nex = m->nex, ored = m->ored;
+	const uint32_t hdr = (fmt == EXF_EXZD) ? 12u : 2u;
+	uint64_t size = FAIL64;
+	if (n != 0 && !(huff == 2 && (ored >> 31))) { // (the empty read; a value the table has no code for)
+		uint32_t len_pos = 0, len_val = 0, bits_pos = 0, bits_val = 0;
+		uint64_t seclen = 4;
+		if (fmt == EXF_VBE21) {
+			seclen += 6ull * nex;
+		} else if (nex == 1) {
+			seclen += (fmt == EXF_EXZD) ? 8 : 6;
+		} else if (nex > 1) {
+			w_exsec_sizes(fmt, a.ex_pos + o0, a.ex_val + o0, nex, lane, len_pos, len_val, bits_pos, bits_val);
+			seclen += 8ull + len_pos + len_val;
+		}
+		const uint64_t nlow = (uint64_t) (n - 1) - nex;
+		size = hdr + seclen + nlow;
+		if (huff == 2) {
+			const uint32_t last = a.first_chunk[r] + (n + CHUNK - 1) / CHUNK - 1;
+			const ChunkBits *cb = a.cbits + last;
+			const uint64_t bits = cb->before + cb->q[0] + cb->q[1] + cb->q[2] + cb->q[3];
+			size = hdr + seclen + 4 + (bits + 7) / 8;
+		} else if (huff == 3) {
+			size += RC_PACK_SLACK;
+		}
+		if (huff && fmt != EXF_VBE21 && seclen > 65535) // the uint16_t section length (press.c:4520, 6917)
+			size = FAIL64;
+		if (fmt == EXF_EXZD && hdr + seclen + nlow > 2ull * n + 1024) // ex_zd.c:411
+			size = FAIL64;
+	}
+	if (lane == 0)
+		need[r] = size;
+}
+
 // vbe21's exception section (press.c:2703-2715: nex x u32 position, nex x u16 raw value) is a
 // plain copy of the lists: one wave per read instead of k_ex_section's single lane, so that a
 // read with thousands of exceptions costs microseconds, not milliseconds.
@@ -545,6 +591,11 @@ void launch_ex_section(const BatchArgs &a, int fmt, int ent, hipStream_t s)
 	hipLaunchKernelGGL(k_ex_section, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent >= 2 ? 3 : 0);
 	if (fmt == EXF_VBE21)
 		hipLaunchKernelGGL(k_ex_fill_vbe21, dim3(a.nreads), dim3(64), 0, s, a);
+}
+
+void launch_ex_sizes(const BatchArgs &a, int fmt, int ent, uint64_t *need, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_ex_sizes, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent >= 2 ? 3 : 0, need);
 }
 
 // k_ex_parse and, for the Huffman variants, the stream decode into a.low (timed as the

@@ -391,7 +391,10 @@ __device__ __forceinline__ uint32_t huf_size(uint4 sb)
 	return 6 + (sb.x / 8 + 1) + (sb.y / 8 + 1) + (sb.z / 8 + 1) + (sb.w / 8 + 1);
 }
 
-// one wave per read: the plan of the frame - key blocks written, data blocks placed
+// one wave per read: the plan of the frame - key blocks written, data blocks placed.
+// SIZES (the packed press): the frame's size alone, into a.out_len, as if the slot took anything; the read's record and
+// the arena are left alone, and the writing form runs afterwards against the slots made from those sizes.
+template <bool SIZES = false>
 __global__ __launch_bounds__(256) void k_zs_plan(BatchArgs a, ZsBufs z)
 {
 	const int lane = threadIdx.x & 63;
@@ -408,8 +411,8 @@ __global__ __launch_bounds__(256) void k_zs_plan(BatchArgs a, ZsBufs z)
 	const uint64_t L = (uint64_t) plen + nk + nd;
 	const uint32_t np = (plen + RLE_MAX - 1) / RLE_MAX; // raw blocks of the prefix
 	const uint8_t *S = z.ztmp + z.zoff[r];
-	const uint64_t cap = a.out_off[r + 1] - a.out_off[r];
-	uint8_t *out = a.out + a.out_off[r];
+	const uint64_t cap = SIZES ? ~0ull : a.out_off[r + 1] - a.out_off[r];
+	uint8_t *out = SIZES ? nullptr : a.out + a.out_off[r];
 	const uint32_t *kpos = a.ex_pos + a.off[r];
 	const uint32_t *kval = a.ex_val + a.off[r];
 	const zs::Table *t = (const zs::Table *) z.tab + r;
@@ -490,11 +493,13 @@ __global__ __launch_bounds__(256) void k_zs_plan(BatchArgs a, ZsBufs z)
 		size = ZFAIL;
 	}
 	if (lane == 0) {
-		rd->mode = mode;
-		rd->dbase = dbase;
+		if (!SIZES) {
+			rd->mode = mode;
+			rd->dbase = dbase;
+		}
 		a.out_len[r] = size;
 	}
-	if (mode)
+	if (mode || SIZES)
 		return;
 	// ---- frame header, the count, the key blocks
 	if (lane == 0) {
@@ -727,10 +732,9 @@ __global__ __launch_bounds__(256) void k_zs_rawframes(BatchArgs a, ZsBufs z)
 
 } // namespace
 
-void launch_zstd_encode(const BatchArgs &a, const ZsBufs &z, hipStream_t s)
+// the inner streams into ztmp, their blocks, tables and code bits: everything a frame's size depends on
+static void zs_encode_front(const BatchArgs &a, const ZsBufs &z, hipStream_t s)
 {
-	if (!a.nreads)
-		return;
 	hipLaunchKernelGGL(k_zs_layout, dim3(1), dim3(1024), 0, s, a.nsamp, a.nreads, z.zoff, z.zoff4, z.kdiv);
 	BatchArgs sv = a; // the inner stream of every read into ztmp (svb: behind the place of its count)
 	sv.out = z.ztmp;
@@ -751,11 +755,42 @@ void launch_zstd_encode(const BatchArgs &a, const ZsBufs &z, hipStream_t s)
 			   z.blk_read);
 	hipLaunchKernelGGL(k_zs_table, dim3((a.nreads + 3) / 4), dim3(256), 0, s, a, z);
 	hipLaunchKernelGGL(k_zs_bits, dim3(z.max_blocks), dim3(256), 0, s, z);
-	hipLaunchKernelGGL(k_zs_plan, dim3((a.nreads + 3) / 4), dim3(256), 0, s, a, z);
+}
+
+// ... and the frames into the slots a.out_off
+static void zs_encode_back(const BatchArgs &a, const ZsBufs &z, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_zs_plan<false>, dim3((a.nreads + 3) / 4), dim3(256), 0, s, a, z);
 	ktime_begin(0, s);
 	hipLaunchKernelGGL(k_zs_encode, dim3(z.max_blocks), dim3(256), 0, s, a, z);
 	ktime_end(0, s);
 	hipLaunchKernelGGL(k_zs_rawframes, dim3(a.nreads), dim3(256), 0, s, a, z);
+}
+
+void launch_zstd_encode(const BatchArgs &a, const ZsBufs &z, hipStream_t s)
+{
+	if (!a.nreads)
+		return;
+	zs_encode_front(a, z, s);
+	zs_encode_back(a, z, s);
+}
+
+// Packed press: the plan runs twice (one wave per read) - for the sizes, and after the scan against the slots pk.slot
+// (a.out_off), which hold every frame that fits the arena and nothing of one that does not.
+void launch_zstd_encode_packed(const BatchArgs &a, const ZsBufs &z, const PackArgs &pk, int phases, hipStream_t s)
+{
+	if (!a.nreads)
+		return;
+	if (phases & PACK_SIZE) {
+		zs_encode_front(a, z, s);
+		BatchArgs sz = a;
+		sz.out_len = pk.need;
+		hipLaunchKernelGGL(k_zs_plan<true>, dim3((a.nreads + 3) / 4), dim3(256), 0, s, sz, z);
+		if (pk.layout)
+			launch_pack_scan(pk, a.nreads, s);
+	}
+	if (phases & PACK_WRITE)
+		zs_encode_back(a, z, s);
 }
 
 // ==================================================================== decode

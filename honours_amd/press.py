@@ -74,6 +74,7 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_synchronize", "press_hip_load_table_file", "press_hip_set_table", "press_hip_bound",
      "press_hip_press_batch", "press_hip_depress_batch", "press_hip_workspace_bytes",
      "press_hip_recode_batch", "press_hip_recode_workspace_bytes", "press_hip_recode_fused",
+     "press_hip_press_sizes", "press_hip_press_packed", "press_hip_packed_exact", "press_hip_packed_workspace_bytes",
      "press_hip_kernel_timing", "press_hip_kernel_times",
      "press_hip_slow5_ptr_compress_svb_zd", "press_hip_slow5_ptr_depress_svb_zd",
      "press_hip_blow5_open", "press_hip_blow5_close", "press_hip_blow5_methods", "press_hip_blow5_next",
@@ -127,6 +128,17 @@ def load_library(path=LIB_PATH):
                                                           ctypes.c_int]
         _lib.press_hip_recode_fused.restype = ctypes.c_int
         _lib.press_hip_recode_fused.argtypes = [ctypes.c_int, ctypes.c_int]
+        _lib.press_hip_press_sizes.restype = ctypes.c_int
+        _lib.press_hip_press_sizes.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_press_packed.restype = ctypes.c_int
+        _lib.press_hip_press_packed.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                                ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_packed_exact.restype = ctypes.c_int
+        _lib.press_hip_packed_exact.argtypes = [ctypes.c_int]
+        _lib.press_hip_packed_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_packed_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
         _lib.press_hip_debug_pass_a_launches.restype = ctypes.c_uint64
         _lib.press_hip_debug_pass_a_launches.argtypes = []
         libc = ctypes.CDLL(None)
@@ -340,6 +352,40 @@ def press_batch(method, sig, off, n, out, out_off, out_len):
         raise PressError(last_error())
 
 
+def press_sizes(method, sig, off, n):
+    """Enqueue the sizing of a batch (CUDA tensors as in press_batch) -> int64 CUDA tensor of nreads entries: the
+    bytes every read takes under `method` (the range coders: the slot that is certain to hold it), -1 = refused.
+    Nothing is compressed."""
+    import torch
+
+    lib = load_library()
+    nreads = off.numel()
+    need = torch.empty(nreads, dtype=torch.int64, device=sig.device)
+    rc = lib.press_hip_press_sizes(_mid(method), sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
+                                   need.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+    return need
+
+
+def press_packed(method, sig, off, n, out, out_off, out_len, align=1):
+    """Enqueue the compression of a batch into an arena the library lays out (press_hip_press_packed).  CUDA tensors
+    as in press_batch, but out_off (int64, nreads+1) is WRITTEN: read r's stream is out[out_off[r] ..
+    out_off[r] + out_len[r]), out_off[-1] is what the batch needs; out.numel() is the arena's capacity - a read
+    that does not fit it gets out_len = -1 and is not written."""
+    lib = load_library()
+    nreads = off.numel()
+    rc = lib.press_hip_press_packed(_mid(method), sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
+                                    out.data_ptr(), out.numel(), int(align), out_off.data_ptr(), out_len.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def packed_exact(method):
+    """True where press_sizes gives the stream's own length (every method but the range coders)"""
+    return bool(load_library().press_hip_packed_exact(_mid(method)))
+
+
 def depress_batch(method, comp, in_off, in_len, sig, off, n, out_n):
     """Enqueue the decompression of a batch (CUDA tensors; out_n int32, -1 = failed)."""
     lib = load_library()
@@ -439,6 +485,36 @@ def press_batch_host(method, reads, caps=None):
         raise PressError(last_error())
     return [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes()
             for o, l in zip(out_off[:-1], out_len)]
+
+
+def press_packed_host(method, reads, align=1):
+    """Packed batch call with host buffers: reads = list of int16 arrays -> (list of bytes / None, arena bytes).
+    No capacities are needed: the arena is sized by press_hip_press_sizes (the exact lengths; the range coders'
+    slots) and the library lays it out.  The convenience costs two passes: the samples are staged and the front of
+    the chain (the svb counting pass, pass A, the zstd inner encode) runs in the sizes call and again in the packed call.
+    A caller who minds calls press_hip_press_packed once with a guessed out_cap and again only where out_off[nreads]
+    exceeds it."""
+    lib = load_library()
+    nreads = len(reads)
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    need = np.zeros(nreads, dtype=np.uint64)
+    if lib.press_hip_press_sizes(_mid(method), sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total,
+                                 need.ctypes.data, 0):
+        raise PressError(last_error())
+    step = np.where(need == np.uint64(FAILED), np.uint64(0), need)
+    cap = int(((step + np.uint64(align - 1)) // np.uint64(align) * np.uint64(align)).sum())
+    out = np.zeros(cap + 64, dtype=np.uint8)  # (+ 64: what a later depress_batch may read behind the last stream)
+    out_off = np.zeros(nreads + 1, dtype=np.uint64)
+    out_len = np.zeros(nreads, dtype=np.uint64)
+    if lib.press_hip_press_packed(_mid(method), sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total,
+                                  out.ctypes.data, cap, int(align), out_off.ctypes.data, out_len.ctypes.data, 0):
+        raise PressError(last_error())
+    return [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes()
+            for o, l in zip(out_off[:-1], out_len)], int(out_off[-1])
 
 
 def depress_batch_host(method, streams, ns):

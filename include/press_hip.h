@@ -304,6 +304,57 @@ int press_hip_press_batch(int method, const int16_t *sig, const uint64_t *off, c
 			  const uint64_t *out_off, uint64_t *out_len, int device_resident);
 
 /*
+ * Packed press: the library lays the output arena out itself.  The streams go back to back, no read fails for want of
+ * a slot, and the arena is as large as the data - the caller needs no slot table and no bound.
+ *
+ * press_hip_press_sizes writes nothing but need[r]: the bytes read r takes under `method`.  For the 16 methods with
+ * press_hip_packed_exact(method) == 1 that is the exact stream length, the out_len[r] press_hip_press_batch gives in a
+ * slot that is large enough; summed, a dataset's compressed size.  PRESS_HIP_FAILED for a read the method refuses
+ * whatever the slot: n = 0 for the exception, Huffman, ex-zd and range-coder methods, a value the table has no code
+ * for, the uint16_t section length of the entropy-coded b/sb/ss forms, ex-zd's 2n + 1024 rule.  Empty reads of the
+ * other methods keep the sizes given above (0; 4 for slow5_svb_zd; a frame for zstd over svb).
+ * The three range coders (press_hip_packed_exact == 0): their stream's length is known only by coding it, and
+ *     need[r] = hdr + seclen + nlow + S,  S = 32
+ * is the smallest slot certain to hold it: hdr + seclen (header and exception section) is exact, nlow (the one-byte
+ * values) is the size of the stream stored raw, which the coder falls back to once its output reaches
+ * g = nlow * 255 / 256 - 8 bytes (rcutil_.h:161).  That test runs once per input byte, and a byte emits at most one
+ * 32-bit word per renormalisation: 4 words (rc, rcc: before bits 7, 5, 3, 1) or 8 (rccm: before every bit).  So the
+ * most a coder has written when it gives up is max(g - 1, 0) + 32 <= nlow + 23 bytes, or 32 bytes for the inputs
+ * (nlow < 10) whose g is not positive; a coder that never gives up ends below g and flushes at most 12 bytes (one
+ * renormalisation and two words).  Every case is at most nlow + 32.  S is derived, not measured.
+ *
+ * press_hip_press_packed compresses.  out_off (nreads + 1 entries) is WRITTEN:
+ *     out_off[0] = 0
+ *     out_off[r] = the end of read r-1's stream (its need), rounded up to `align`
+ *     out_off[nreads] = the end of the last stream, not rounded
+ * Read r's stream is out[out_off[r] .. out_off[r] + out_len[r]); a refused read takes 0 bytes.  The layout does not
+ * depend on out_cap, so out_off[nreads] always says what the batch needs.  Read r is written iff
+ * out_off[r] + need[r] <= out_cap; otherwise out_len[r] = PRESS_HIP_FAILED and no byte of it is written.  Device
+ * resident, nothing at or beyond out_cap and no padding byte is ever written.  The streams are byte for byte those of
+ * press_hip_press_batch.  The range coders' arena keeps gaps: out_len[r] <= need[r], and the bytes between a stream's
+ * end and out_off[r] + need[r] are unspecified.
+ *   align    a power of two, 1 .. 4096; anything else is PRESS_HIP_EARG (as a bad method id: before any device call)
+ *   sig / off / n / total_samples / device_resident   as press_hip_press_batch, with its checks
+ * device_resident != 0: every pointer is a device pointer, out_off and need included; the call only enqueues, there is
+ * no synchronisation and no host wait.  == 0: host pointers, synchronous: the samples are staged and the layout is
+ * made, out_off[nreads] is read back - the call's one synchronisation besides the last -, the device arena is reserved
+ * at min(out_off[nreads], out_cap) bytes, not at a bound, and after the press that prefix of the arena goes to `out` in
+ * ONE contiguous transfer (page-locked `out`, or up to 256 KiB: one DMA; pageable: through the staging buffers); on
+ * this path padding, range-coder gaps and the room of a read that did not fit arrive as zeros.
+ * press_hip_depress_batch wants 64 readable bytes behind the last stream: allocate out_cap + 64 for an arena that is
+ * decoded later.
+ * press_hip_packed_workspace_bytes: the device scratch the two calls keep for a batch of this shape, exact as
+ * press_hip_workspace_bytes is and never below it; 0 for a method id out of range.
+ */
+int press_hip_press_sizes(int method, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			  uint64_t total_samples, uint64_t *need, int device_resident);
+int press_hip_press_packed(int method, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			   uint64_t total_samples, uint8_t *out, uint64_t out_cap, uint32_t align,
+			   uint64_t *out_off, uint64_t *out_len, int device_resident);
+int press_hip_packed_exact(int method); /* 1: need == stream length (16 methods); 0: range coders, bad ids */
+uint64_t press_hip_packed_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads);
+
+/*
  * Decompress nreads streams.
  *   in/in_off/in_len  stream r = in[in_off[r] .. in_off[r]+in_len[r]); in_off any byte
  *                     offset, streams in any order, and 64 readable bytes behind the
