@@ -826,3 +826,207 @@ extern "C" int press_hip_recode_batch(int src_method, int dst_method, const uint
 	}
 	return fetch_streams(out, out_off, rel, out_len, nreads, s);
 }
+
+// ------------------------------------------------------------------ packed recode: streams in, a library-made arena out
+//
+// launch_recode with the press half cut in two (PackArgs, press_internal.h).  PACK_SIZE: the decode, the press half's
+// sample counts, the destination's chain up to its sizes WITHOUT its scan; then the reads the source refused lose their
+// size and their slot (launch_pack_scan_refused) - only then are the offsets final - and the exception family's chunks
+// learn their bases.  PACK_WRITE: the rest of the destination's chain, and out_len = FAILED for the refused reads
+// (k_recode_refused without a keep: it touches out_len alone).  pa.out_off must be pk.slot.
+static int launch_recode_packed(const RecodePlan &rp, DecodeArgs &da, BatchArgs &pa, PackArgs pk, int phases, hipStream_t s)
+{
+	int rc;
+	pa.sig = da.sig;
+	pa.off = da.off;
+	pa.nsamp = (const uint32_t *) g.rn.p;
+	if (pk.out_cap == PRESS_HIP_FAILED) // (k_chunk_prep<.., EXACT> compares need[r] = FAILED with it)
+		pk.out_cap--;
+	const Method &sm = *rp.d.m, &dm = *rp.p.m;
+	if (rp.fused) {
+		pa.chunks = (ChunkDesc *) g.pchunks.p;
+		pa.first_chunk = (uint32_t *) g.pfirst.p;
+		pa.ctl = (ChunkCtl *) g.pctl.p;
+		launch_recode_fused_packed(da, pa, sm.key2, sm.slow5, dm.exfmt, dm.ent, pk, phases, s);
+	} else {
+		if (phases & PACK_SIZE) {
+			if ((rc = launch_depress(rp.d, da, s)))
+				return rc;
+			launch_recode_counts(da.out_n, (uint32_t *) g.rn.p, da.nreads, s);
+			PackArgs sz = pk;
+			sz.layout = nullptr; // (the scan comes behind the refused reads' correction)
+			if ((rc = launch_press_packed(rp.p, pa, sz, PACK_SIZE, s)))
+				return rc;
+			launch_pack_scan_refused(pk, da.out_n, da.nreads, s);
+			if (pk.layout && dm.family == FAM_EX)
+				launch_pack_patch(pa, pk.slot, s);
+		}
+		if ((phases & PACK_WRITE) && (rc = launch_press_packed(rp.p, pa, pk, PACK_WRITE, s)))
+			return rc;
+	}
+	if (phases & PACK_WRITE)
+		launch_recode_refused(da.out_n, pa, nullptr, false, s);
+	return launch_status();
+}
+
+// what both packed recodes check before any device call
+static int recode_packed_args_ok(int src_method, int dst_method, uint32_t align)
+{
+	if (!method_ok(src_method) || !method_ok(dst_method))
+		return set_error(PRESS_HIP_EARG, "method %d -> %d is not available in the batch API", src_method, dst_method);
+	return packed_args_ok(dst_method, align);
+}
+
+// the head of their host-pointer form: the checks of press_hip_recode_batch, then the streams and the layout on the device
+static int recode_packed_stage(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, const uint32_t *n,
+			       const uint64_t *off, uint32_t nreads, uint64_t total_samples, bool keep_samples, DecodeArgs &da,
+			       std::vector<uint32_t> &order, std::vector<uint64_t> &doff, hipStream_t s)
+{
+	int rc;
+	if ((rc = check_disjoint(off, n, nreads, "the sample room", order)))
+		return rc;
+	if ((rc = stage_layout(off, n, nreads, total_samples, s, keep_samples)))
+		return rc;
+	if ((rc = stage_streams(in, in_off, in_len, nreads, g.rin, g.rin_off, doff, s)))
+		return rc;
+	da.in = (const uint8_t *) g.rin.p;
+	da.in_off = (const uint64_t *) g.rin_off.p;
+	da.in_len = (const uint64_t *) g.lens2.p;
+	da.sig = keep_samples ? (int16_t *) g.sig.p : (int16_t *) g.rsig.p;
+	da.off = (const uint64_t *) g.off.p;
+	da.nsamp = (const uint32_t *) g.nsamp.p;
+	da.out_n = (uint32_t *) g.outn.p;
+	return 0;
+}
+
+extern "C" int press_hip_recode_sizes(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
+				      const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+				      uint64_t total_samples, uint64_t *need, int16_t *sig, uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	int rc = recode_packed_args_ok(src_method, dst_method, 1);
+	if (rc || (rc = ctx_init()) || (rc = check_method(src_method)) || (rc = check_method(dst_method)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	if (!in || !in_off || !in_len || !n || !off || !need || !out_n)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	hipStream_t s = g.stream();
+	const RecodePlan rp = make_recode_packed_plan(src_method, dst_method, total_samples, nreads, sig != nullptr);
+	if ((rc = rp.all.reserve()))
+		return rc;
+	DecodeArgs da;
+	BatchArgs pa;
+	rp.d.bind(da);
+	rp.p.bind(pa);
+	da.nreads = pa.nreads = nreads;
+	PackArgs pk = { device_resident ? need : (uint64_t *) g.pneed.p, nullptr, (uint64_t *) g.pslot.p, 0, 1 };
+	pa.out_off = pk.slot;
+	pa.out_len = pk.need; // (as press_hip_press_sizes)
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		da.in = in;
+		da.in_off = in_off;
+		da.in_len = in_len;
+		da.sig = sig ? sig : (int16_t *) g.rsig.p;
+		da.off = off;
+		da.nsamp = n;
+		da.out_n = out_n;
+		return launch_recode_packed(rp, da, pa, pk, PACK_SIZE, s);
+	}
+	std::vector<uint32_t> order;
+	std::vector<uint64_t> doff;
+	if ((rc = recode_packed_stage(in, in_off, in_len, n, off, nreads, total_samples, sig != nullptr, da, order, doff, s)) ||
+	    (rc = launch_recode_packed(rp, da, pa, pk, PACK_SIZE, s)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(need, pk.need, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	if (sig)
+		return fetch_samples(sig, off, n, out_n, nreads, order, s);
+	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
+extern "C" int press_hip_recode_packed(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
+				       const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+				       uint64_t total_samples, uint8_t *out, uint64_t out_cap, uint32_t align, uint64_t *out_off,
+				       uint64_t *out_len, int16_t *sig, uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	int rc = recode_packed_args_ok(src_method, dst_method, align);
+	if (rc || (rc = ctx_init()) || (rc = check_method(src_method)) || (rc = check_method(dst_method)))
+		return rc;
+	if (!out_off)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	if (nreads == 0) { // an empty batch has a layout too
+		if (device_resident)
+			HIPCHK(hipMemsetAsync(out_off, 0, 8, g.stream()));
+		else
+			out_off[0] = 0;
+		return 0;
+	}
+	if (!in || !in_off || !in_len || !n || !off || !out_len || !out_n || (!out && out_cap))
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	hipStream_t s = g.stream();
+	const RecodePlan rp = make_recode_packed_plan(src_method, dst_method, total_samples, nreads, sig != nullptr);
+	if ((rc = rp.all.reserve()))
+		return rc;
+	DecodeArgs da;
+	BatchArgs pa;
+	rp.d.bind(da);
+	rp.p.bind(pa);
+	da.nreads = pa.nreads = nreads;
+	PackArgs pk = { (uint64_t *) g.pneed.p, out_off, (uint64_t *) g.pslot.p, out_cap, align };
+	pa.out_off = pk.slot;
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		da.in = in;
+		da.in_off = in_off;
+		da.in_len = in_len;
+		da.sig = sig ? sig : (int16_t *) g.rsig.p;
+		da.off = off;
+		da.nsamp = n;
+		da.out_n = out_n;
+		pa.out = out;
+		pa.out_len = out_len;
+		return launch_recode_packed(rp, da, pa, pk, PACK_SIZE | PACK_WRITE, s);
+	}
+
+	// host pointers: stage, decode and size, read the arena's size back, write into an arena of that size, copy its prefix
+	// back in one piece
+	if (g.arena_off.reserve(((size_t) nreads + 1) * 8) || g.lens.reserve((size_t) nreads * 8))
+		return PRESS_HIP_EHIP;
+	pk.layout = (uint64_t *) g.arena_off.p;
+	pa.out_len = (uint64_t *) g.lens.p;
+	std::vector<uint32_t> order;
+	std::vector<uint64_t> doff;
+	if ((rc = recode_packed_stage(in, in_off, in_len, n, off, nreads, total_samples, sig != nullptr, da, order, doff, s)) ||
+	    (rc = launch_recode_packed(rp, da, pa, pk, PACK_SIZE, s)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(out_off, pk.layout, ((size_t) nreads + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s)); // the one synchronisation besides the last: the arena's size
+	const uint64_t bytes = out_off[nreads] < out_cap ? out_off[nreads] : out_cap;
+	if (g.arena.reserve(bytes + 64))
+		return PRESS_HIP_EHIP;
+	if (bytes) // (padding and the gaps of the range coders reach the caller as zeros)
+		HIPCHK(hipMemsetAsync(g.arena.p, 0, bytes, s));
+	pa.out = (uint8_t *) g.arena.p;
+	if ((rc = launch_recode_packed(rp, da, pa, pk, PACK_WRITE, s)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(out_len, g.lens.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	if (bytes <= DIRECT_MAX || is_pinned(out)) {
+		if (bytes)
+			HIPCHK(hipMemcpyAsync(out, g.arena.p, bytes, hipMemcpyDeviceToHost, s));
+	} else {
+		const std::vector<Piece> pc = { { out, 0, bytes } };
+		if ((rc = staged_pieces<false>((uint8_t *) g.arena.p, bytes, pc, s)))
+			return rc;
+	}
+	if (sig)
+		return fetch_samples(sig, off, n, out_n, nreads, order, s);
+	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}

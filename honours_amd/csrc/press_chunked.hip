@@ -2409,6 +2409,54 @@ void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, 
 		run_recode<false, false>(d, p, fmt, ent, s);
 }
 
+// Packed recode, fused: run_recode with the press half cut where launch_ex_encode_packed cuts it.  PACK_SIZE: the slot
+// table zeroed, the decode with pass A's results, the exception lists and the sizes; the reads the source refused lose
+// their size, the scan lays the arena out and the PRESS half's chunk table (p.chunks / p.first_chunk) learns the bases.
+// PACK_WRITE: the section and the encoder as they are.  Pass A stays skipped.
+template <bool KEY2, bool S5>
+static void run_recode_packed(const DecodeArgs &d, const BatchArgs &p, int fmt, int ent, const PackArgs &pk, hipStream_t s)
+{
+	(void) hipMemsetAsync(d.ctl, 0, sizeof(ChunkCtl), s);
+	hipLaunchKernelGGL((k_chunk_prep<true, KEY2>), dim3((d.nreads + 255) / 256), dim3(256), 0, s, d.off,
+			   d.nsamp, d.in_off, d.in_len, d.nreads, d.chunks, d.gran, d.ctl, d.max_chunks,
+			   (uint64_t *) nullptr, d.out_n, d.first_chunk, (ReadMeta *) nullptr, d.in,
+			   S5 ? 4u : 0u);
+	hipLaunchKernelGGL((k_svb_keyscan<KEY2, S5>), dim3((d.max_chunks + 3) / 4), dim3(CWG), 0, s, d);
+	hipLaunchKernelGGL((k_svb_keyprefix<KEY2, S5>), dim3((d.nreads + 3) / 4), dim3(256), 0, s, d);
+	launch_recode_counts(d.out_n, const_cast<uint32_t *>(p.nsamp), d.nreads, s);
+	(void) hipMemsetAsync(pk.slot, 0, ((size_t) p.nreads + 1) * 8, s);
+	ex_encode_prep(p, s);
+	const FuseArgs f = { p.chunks, p.first_chunk, p.cbits, p.meta, p.huff };
+	ktime_begin(1, s);
+	if (ent == 1)
+		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 2>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
+	else
+		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 1>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
+	ktime_end(1, s);
+	ex_encode_lists(p, fmt, s);
+	launch_ex_sizes(p, fmt, ent, pk.need, s);
+	launch_pack_scan_refused(pk, d.out_n, d.nreads, s);
+	if (pk.layout)
+		launch_pack_patch(p, pk.slot, s);
+}
+
+void launch_recode_fused_packed(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent,
+				const PackArgs &pk, int phases, hipStream_t s)
+{
+	if (!d.nreads || !d.max_chunks)
+		return;
+	if (phases & PACK_SIZE) {
+		if (slow5)
+			run_recode_packed<true, true>(d, p, fmt, ent, pk, s);
+		else if (key2bit)
+			run_recode_packed<true, false>(d, p, fmt, ent, pk, s);
+		else
+			run_recode_packed<false, false>(d, p, fmt, ent, pk, s);
+	}
+	if (phases & PACK_WRITE)
+		ex_encode_streams(p, fmt, ent, s);
+}
+
 // n[r] = out_n[r], 0 for a read the decoder refused: the sample counts of the press half of a recode
 __global__ __launch_bounds__(256) void k_recode_counts(const uint32_t *out_n, uint32_t *n, uint32_t nreads)
 {

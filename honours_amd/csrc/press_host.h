@@ -196,6 +196,10 @@ struct RecodePlan {
 bool recode_fused(int src, int dst);
 RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples);
 
+// press_hip_recode_sizes / press_hip_recode_packed: the recode plan and the two per-read tables of PackArgs (the slot heads
+// of keep_heads stay in the plan and unused: a refused read of the packed form has no slot)
+RecodePlan make_recode_packed_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples);
+
 // press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
 ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);
 

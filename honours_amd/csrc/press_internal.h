@@ -304,6 +304,9 @@ constexpr uint32_t RC_PACK_SLACK = 32;
 void launch_pack_svb_sizes(const BatchArgs &a, bool key2bit, bool zd, bool slow5, uint64_t *need, hipStream_t s); // press_packed.hip
 void launch_pack_scan(const PackArgs &pk, uint32_t nreads, hipStream_t s);
 void launch_pack_patch(const BatchArgs &a, const uint64_t *slot, hipStream_t s);
+// packed recode: need[] = FAILED for the reads the source refused (out_n), then - with pk.layout - the scan, and a slot
+// table in which such a read has no byte whatever lies behind it
+void launch_pack_scan_refused(const PackArgs &pk, const uint32_t *out_n, uint32_t nreads, hipStream_t s);
 void launch_ex_sizes(const BatchArgs &a, int fmt, int ent, uint64_t *need, hipStream_t s); // press_sections.hip
 void launch_svb_encode_packed(const BatchArgs &a, bool key2bit, bool zd, bool slow5, const PackArgs &pk, int phases, hipStream_t s);
 void launch_ex_encode_packed(const BatchArgs &a, int fmt, int ent, const PackArgs &pk, int phases, hipStream_t s);
@@ -324,6 +327,9 @@ struct FuseArgs {
 };
 constexpr uint32_t RECODE_KEEP = 64; // bytes of a refused read's slot kept aside (an empty read's stream is 4 / 16 bytes)
 void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent, hipStream_t s);
+// the packed form (press_hip_recode_sizes / press_hip_recode_packed): phases as launch_ex_encode_packed, p.out_off == pk.slot
+void launch_recode_fused_packed(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent,
+				 const PackArgs &pk, int phases, hipStream_t s);
 void launch_recode_counts(const uint32_t *out_n, uint32_t *n, uint32_t nreads, hipStream_t s);
 void launch_recode_refused(const uint32_t *out_n, const BatchArgs &p, uint8_t *keep, bool save, hipStream_t s);
 

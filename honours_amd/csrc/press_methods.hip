@@ -177,6 +177,14 @@ RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t n
 	return r;
 }
 
+RecodePlan make_recode_packed_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples)
+{
+	RecodePlan r = make_recode_plan(src, dst, total_samples, nreads, keep_samples);
+	const size_t nr = (size_t) nreads + 1;
+	r.all.need(&Ctx::pneed, nr * 8).need(&Ctx::pslot, nr * 8);
+	return r;
+}
+
 // Most fields of the argument blocks carry the name of the buffer behind them (ZsBufs: without its z)
 #define BIND(x, f, buf) x.f = (decltype(x.f)) ptr(&Ctx::buf)
 #define B(f) BIND(a, f, f)
@@ -259,6 +267,20 @@ extern "C" uint64_t press_hip_packed_workspace_bytes(int method, uint64_t total_
 	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
 	for (int i = 0; i < p.nrows; i++)
 		b += p.rows[i].bytes;
+	return b;
+}
+
+// as press_hip_recode_workspace_bytes, and the two tables of the packed plan
+extern "C" uint64_t press_hip_recode_packed_workspace_bytes(int src_method, int dst_method, uint64_t total_samples,
+							    uint32_t nreads, int keep_samples)
+{
+	API_LOCK;
+	if (!method_ok(src_method) || !method_ok(dst_method))
+		return 0;
+	const RecodePlan r = make_recode_packed_plan(src_method, dst_method, total_samples, nreads, keep_samples != 0);
+	uint64_t b = is_shuff(METHODS[src_method]) || is_shuff(METHODS[dst_method]) ? sizeof(HuffDev) : 0;
+	for (int i = 0; i < r.all.nrows; i++)
+		b += r.all.rows[i].bytes;
 	return b;
 }
 

@@ -158,6 +158,50 @@ __global__ __launch_bounds__(1024) void k_pk_scan(const uint64_t *need, uint32_t
 	}
 }
 
+// ------------------------------------------------------------------ packed recode: reads the SOURCE refused
+//
+// The press half of a recode sees such a read as an empty one (launch_recode_counts), for which some destinations have a
+// size - 4 bytes of slow5_svb_zd, a frame of zstd over svb.  It takes no byte: need[r] = FAILED before the scan.
+__global__ __launch_bounds__(256) void k_pk_refused(const uint32_t *out_n, uint64_t *need, uint32_t nreads)
+{
+	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+	if (r < nreads && out_n[r] == 0xFFFFFFFFu)
+		need[r] = PFAIL;
+}
+
+// ... and no slot: k_pk_scan gives a refused read slot[r] = layout[r], which is a slot of no bytes only while read r + 1
+// starts there - not when r + 1 does not fit out_cap and slot[r + 1] is a later read's offset, and a writer that has a
+// stream for an empty read would put it into that room.  The slot table is made again from layout[] with the source's
+// refusals counted as reads that do not fit (slot[r] = slot[r + 1]); everything else as k_pk_scan's second half.  A
+// read in front keeps at least its need[]: the room of a refused read falls to it as that of a read that does not fit.
+__global__ __launch_bounds__(1024) void k_pk_refused_slots(const uint64_t *need, const uint32_t *out_n, uint32_t nreads,
+							   uint64_t out_cap, const uint64_t *layout, uint64_t *slot)
+{
+	__shared__ uint64_t wsum[16];
+	__shared__ uint64_t s_total;
+	uint64_t behind = layout[nreads];
+	if (threadIdx.x == 0)
+		slot[nreads] = behind;
+	const uint32_t rounds = (nreads + 1023) / 1024;
+	for (uint32_t k = rounds; k-- > 0;) {
+		const uint32_t r = k * 1024 + (1023 - threadIdx.x);
+		uint64_t v = PFAIL;
+		if (r < nreads && out_n[r] != 0xFFFFFFFFu) {
+			const uint64_t sz = need[r], o = layout[r];
+			if (sz == PFAIL || (sz <= out_cap && o <= out_cap - sz))
+				v = o;
+		}
+		uint64_t m = wg_incl_scan64<true>(v, wsum);
+		m = m < behind ? m : behind;
+		if (r < nreads)
+			slot[r] = m;
+		if (threadIdx.x == 1023)
+			s_total = m;
+		__syncthreads();
+		behind = s_total;
+	}
+}
+
 // ChunkDesc::out_base of every chunk of a read: k_chunk_prep ran before the offsets existed.  One wave per read.
 __global__ __launch_bounds__(256) void k_pk_patch(ChunkDesc *chunks, const uint32_t *first_chunk, const uint32_t *nsamp,
 						  const uint64_t *slot, uint32_t nreads, uint32_t max_chunks)
@@ -198,6 +242,17 @@ void launch_pack_scan(const PackArgs &pk, uint32_t nreads, hipStream_t s)
 {
 	hipLaunchKernelGGL(k_pk_scan, dim3(1), dim3(1024), 0, s, (const uint64_t *) pk.need, nreads, (uint64_t) pk.align - 1,
 			   pk.out_cap, pk.layout, pk.slot);
+}
+
+// need[] of the reads the source refused, and - with a layout - the scan and the slot table of a packed recode
+void launch_pack_scan_refused(const PackArgs &pk, const uint32_t *out_n, uint32_t nreads, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_pk_refused, dim3((nreads + 255) / 256), dim3(256), 0, s, out_n, pk.need, nreads);
+	if (!pk.layout)
+		return;
+	launch_pack_scan(pk, nreads, s);
+	hipLaunchKernelGGL(k_pk_refused_slots, dim3(1), dim3(1024), 0, s, (const uint64_t *) pk.need, out_n, nreads, pk.out_cap,
+			   (const uint64_t *) pk.layout, pk.slot);
 }
 
 void launch_pack_patch(const BatchArgs &a, const uint64_t *slot, hipStream_t s)

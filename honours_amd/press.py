@@ -74,6 +74,7 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_synchronize", "press_hip_load_table_file", "press_hip_set_table", "press_hip_bound",
      "press_hip_press_batch", "press_hip_depress_batch", "press_hip_workspace_bytes",
      "press_hip_recode_batch", "press_hip_recode_workspace_bytes", "press_hip_recode_fused",
+     "press_hip_recode_sizes", "press_hip_recode_packed", "press_hip_recode_packed_workspace_bytes",
      "press_hip_press_sizes", "press_hip_press_packed", "press_hip_packed_exact", "press_hip_packed_workspace_bytes",
      "press_hip_kernel_timing", "press_hip_kernel_times",
      "press_hip_slow5_ptr_compress_svb_zd", "press_hip_slow5_ptr_depress_svb_zd",
@@ -139,6 +140,18 @@ def load_library(path=LIB_PATH):
         _lib.press_hip_packed_exact.argtypes = [ctypes.c_int]
         _lib.press_hip_packed_workspace_bytes.restype = ctypes.c_uint64
         _lib.press_hip_packed_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
+        _lib.press_hip_recode_sizes.restype = ctypes.c_int
+        _lib.press_hip_recode_sizes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_recode_packed.restype = ctypes.c_int
+        _lib.press_hip_recode_packed.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                                 ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_recode_packed_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_recode_packed_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                                                 ctypes.c_uint32, ctypes.c_int]
         _lib.press_hip_debug_pass_a_launches.restype = ctypes.c_uint64
         _lib.press_hip_debug_pass_a_launches.argtypes = []
         libc = ctypes.CDLL(None)
@@ -413,6 +426,44 @@ def recode_batch(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, 
         raise PressError(last_error())
 
 
+def recode_sizes(src, dst, comp, in_off, in_len, n, off, out_n, sig=None, total_samples=None):
+    """Enqueue the sizing of a recode (CUDA tensors as in recode_batch) -> int64 CUDA tensor of nreads entries: the
+    bytes every read's `dst` stream takes (as press_sizes), -1 for a read either method refuses.  out_n and - if given -
+    sig receive what the decode of `src` gives; no stream is written."""
+    import torch
+
+    lib = load_library()
+    nreads = off.numel()
+    if sig is None and total_samples is None:
+        raise PressError("recode_sizes without sig needs total_samples")
+    total = sig.numel() if total_samples is None else int(total_samples)
+    need = torch.empty(nreads, dtype=torch.int64, device=comp.device)
+    rc = lib.press_hip_recode_sizes(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
+                                    n.data_ptr(), off.data_ptr(), nreads, total, need.data_ptr(),
+                                    None if sig is None else sig.data_ptr(), out_n.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+    return need
+
+
+def recode_packed(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, out_n, sig=None, total_samples=None,
+                  align=1):
+    """Enqueue the recoding of a batch into an arena the library lays out (press_hip_recode_packed).  CUDA tensors as
+    in recode_batch, but out_off (int64, nreads+1) is WRITTEN, as by press_packed: out_off[-1] is what the batch needs,
+    out.numel() the arena's capacity.  A read whose source stream is refused takes no byte."""
+    lib = load_library()
+    nreads = off.numel()
+    if sig is None and total_samples is None:
+        raise PressError("recode_packed without sig needs total_samples")
+    total = sig.numel() if total_samples is None else int(total_samples)
+    rc = lib.press_hip_recode_packed(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
+                                     n.data_ptr(), off.data_ptr(), nreads, total, out.data_ptr(), out.numel(), int(align),
+                                     out_off.data_ptr(), out_len.data_ptr(), None if sig is None else sig.data_ptr(),
+                                     out_n.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
 def recode_fused(src, dst):
     """True where the press half's first pass comes out of the decode kernel (press_hip_recode_fused)"""
     return bool(load_library().press_hip_recode_fused(_mid(src), _mid(dst)))
@@ -452,6 +503,44 @@ def recode_batch_host(src, dst, streams, ns, caps=None, want_samples=False):
     if not want_samples:
         return res
     return res, [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)]
+
+
+def recode_packed_host(src, dst, streams, ns, align=1, want_samples=False):
+    """Packed recode with host buffers: streams = list of bytes of method `src`, ns = sample counts / rooms ->
+    (list of bytes of method `dst` / None, arena bytes); with want_samples -> (streams, arena bytes, list of int16
+    arrays).  No capacities: press_hip_recode_sizes gives the arena's size, so it is as large as the streams, not as a
+    bound.  As with press_packed_host the convenience costs the front of the chain twice (here the decode too)."""
+    lib = load_library()
+    nreads = len(streams)
+    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+    in_off = np.zeros(nreads, dtype=np.uint64)
+    if nreads > 1:
+        in_off[1:] = np.cumsum(in_len)[:-1]
+    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
+    ns = np.asarray(ns, dtype=np.uint32)
+    off, total = _layout(ns)
+    need = np.zeros(nreads, dtype=np.uint64)
+    out_n = np.zeros(nreads, dtype=np.uint32)
+    if lib.press_hip_recode_sizes(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
+                                  ns.ctypes.data, off.ctypes.data, nreads, total, need.ctypes.data, None,
+                                  out_n.ctypes.data, 0):
+        raise PressError(last_error())
+    step = np.where(need == np.uint64(FAILED), np.uint64(0), need)
+    cap = int(((step + np.uint64(align - 1)) // np.uint64(align) * np.uint64(align)).sum())
+    out = np.zeros(cap + 64, dtype=np.uint8)  # (+ 64: what a later depress_batch may read behind the last stream)
+    out_off = np.zeros(nreads + 1, dtype=np.uint64)
+    out_len = np.zeros(nreads, dtype=np.uint64)
+    sig = np.zeros(total + 64, dtype=np.int16) if want_samples else None
+    if lib.press_hip_recode_packed(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
+                                   ns.ctypes.data, off.ctypes.data, nreads, total, out.ctypes.data, cap, int(align),
+                                   out_off.ctypes.data, out_len.ctypes.data, sig.ctypes.data if want_samples else None,
+                                   out_n.ctypes.data, 0):
+        raise PressError(last_error())
+    res = [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
+    if not want_samples:
+        return res, int(out_off[-1])
+    return res, int(out_off[-1]), [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy()
+                                   for o, k in zip(off, out_n)]
 
 
 def _layout(ns):

@@ -411,6 +411,49 @@ uint64_t press_hip_recode_workspace_bytes(int src_method, int dst_method, uint64
 int press_hip_recode_fused(int src_method, int dst_method);
 
 /*
+ * Packed recode: press_hip_recode_batch into an arena the library lays out.  A recoding caller holds compressed bytes and
+ * rooms n[r], not the sample counts the destination will be asked to code: it cannot make a slot table, and it needs none.
+ *
+ * press_hip_recode_packed gives what press_hip_depress_batch(src_method) followed by press_hip_press_packed(dst_method)
+ * over the decoded samples with the sample counts out_n give - out_off, out_len, out_n, sig and the arena byte for byte -
+ * for every pair of methods; the streams are those of press_hip_recode_batch in slots that are large enough.
+ *   in/in_off/in_len/n/off/total_samples/sig/out_n   as in press_hip_recode_batch (sig == NULL: library scratch)
+ *   out/out_cap/align/out_off/out_len                as in press_hip_press_packed: out_off is WRITTEN, the layout does not
+ *            depend on out_cap, out_off[nreads] is what the batch needs, read r is written iff
+ *            out_off[r] + need[r] <= out_cap, nothing at or beyond out_cap and - device resident - no padding byte is written;
+ *            the range coders keep need = hdr + seclen + nlow + 32 and their gaps (press_hip_packed_exact(dst_method))
+ * What that sequence cannot express - a read whose SOURCE stream is refused: out_n[r] = UINT32_MAX,
+ * need[r] = out_len[r] = PRESS_HIP_FAILED, 0 bytes of the layout, and no byte written for it wherever out_cap lies and
+ * whether or not the read behind it fits - also under the destinations that have a stream for an empty read
+ * (slow5_svb_zd's u32 count, the zstd frames over svb).  A source read that decodes to 0 samples is not refused: it gets
+ * the destination's empty-read result (press_hip_press_sizes).  A read the source decodes and the destination refuses
+ * keeps its decoded out_n, with need = out_len = PRESS_HIP_FAILED and 0 bytes.
+ * press_hip_recode_sizes writes only need[] (as press_hip_press_sizes, with the rule above), out_n[] and - sig given -
+ * the samples: "what would this archive weigh under dst_method", with no arena.
+ * A bad method id or align is PRESS_HIP_EARG before any device call; whatever the two halves refuse is refused here
+ * (PRESS_HIP_ENOTABLE, the alignment of sig, overlapping rooms on the host path).  nreads == 0: PRESS_HIP_OK, and
+ * press_hip_recode_packed writes out_off[0] = 0.
+ * device_resident != 0: every pointer is a device pointer, out_off and need included; the call only enqueues (the zstd
+ * sources keep their host wait, see below, and add no other).  == 0: host pointers, synchronous: streams and layout are
+ * staged, the batch is decoded and sized, out_off[nreads] is read back - the one synchronisation besides the last -, the
+ * device arena is reserved at min(out_off[nreads], out_cap) + 64 bytes, written, and that prefix goes to `out` in one
+ * transfer; padding, range-coder gaps and the room of a read that did not fit arrive as zeros.  out_n and the samples
+ * come back as from press_hip_recode_batch.
+ * press_hip_recode_packed_workspace_bytes: press_hip_recode_workspace_bytes plus the two per-read tables of the packed
+ * plan, (nreads + 1) * 8 bytes each; exact in the same sense, never below it, 0 for a method id out of range.  Host
+ * arithmetic, no GPU needed.
+ */
+int press_hip_recode_sizes(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
+			   const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+			   uint64_t total_samples, uint64_t *need, int16_t *sig, uint32_t *out_n, int device_resident);
+int press_hip_recode_packed(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
+			    const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+			    uint64_t total_samples, uint8_t *out, uint64_t out_cap, uint32_t align,
+			    uint64_t *out_off, uint64_t *out_len, int16_t *sig, uint32_t *out_n, int device_resident);
+uint64_t press_hip_recode_packed_workspace_bytes(int src_method, int dst_method, uint64_t total_samples,
+						 uint32_t nreads, int keep_samples);
+
+/*
  * PRESS_HIP_ZSTD_SVB_ZD, _ZSTD_SVB12_ZD and _ZSTD_HASGAM_ZDQ in the calls above (SURVEY.md 8f-3,
  * replaces the ZSTD_compress / ZSTD_decompress calls of press.c:1860-1910, 2020-2070, 8549-8589 for batches):
  *   press    writes one standard zstd frame (RFC 8878) per read whose content is the buffer

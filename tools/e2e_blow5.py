@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""bench.py's e2e_blow5 leg alone:  python3 tools/e2e_blow5.py [--recode] [reads] [reads per batch]
+"""bench.py's e2e_blow5 leg alone:  python3 tools/e2e_blow5.py [--recode [--packed]] [reads] [reads per batch]
 
 --recode: every batch goes through ONE press_hip_recode_batch call (BLOW5's svb-zd fields in, the target method's
-streams out, the samples kept for the check) instead of press_hip_depress_batch + press_hip_press_batch."""
+streams out, the samples kept for the check) instead of press_hip_depress_batch + press_hip_press_batch.
+--packed (with --recode): that call is press_hip_recode_packed: the leg's slot table is only the room the library lays
+the streams out in, back to back, and is overwritten with their offsets."""
 import json
 import os
 import sys
@@ -15,8 +17,9 @@ class RecodeCalls:
     """honours_amd.press as bench.e2e_blow5 uses it, with a depress_batch that only remembers its arguments and a
     press_batch that hands both halves to press.recode_batch"""
 
-    def __init__(self, press):
+    def __init__(self, press, packed=False):
         self._press = press
+        self._packed = packed
         self._pending = None
 
     def __getattr__(self, name):
@@ -31,12 +34,15 @@ class RecodeCalls:
         src, comp, in_off, in_len, dsig, doff, dn, out_n = self._pending
         self._pending = None
         assert dsig.data_ptr() == sig.data_ptr() and doff.data_ptr() == off.data_ptr()
-        self._press.recode_batch(src, method, comp, in_off, in_len, dn, doff, out, out_off, out_len, out_n, sig=dsig)
+        call = self._press.recode_packed if self._packed else self._press.recode_batch
+        call(src, method, comp, in_off, in_len, dn, doff, out, out_off, out_len, out_n, sig=dsig)
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--recode"]
-    recode = len(argv) != len(sys.argv) - 1
+    argv = [a for a in sys.argv[1:] if a not in ("--recode", "--packed")]
+    recode, packed = "--recode" in sys.argv[1:], "--packed" in sys.argv[1:]
+    if packed and not recode:
+        sys.exit("--packed needs --recode")
     reads = int(argv[0]) if len(argv) > 0 else 2048
     per = int(argv[1]) if len(argv) > 1 else 512
     import torch
@@ -51,9 +57,9 @@ def main():
     press.load_library()
     press.use_torch_stream()
     b = bench.Batch(torch, press, synth, 20261004, 0, reads, dev, None)
-    rec = bench.e2e_blow5(torch, RecodeCalls(press) if recode else press, b, "shuffman_vbe21_zd", nreads=reads, batch_reads=per)
+    rec = bench.e2e_blow5(torch, RecodeCalls(press, packed) if recode else press, b, "shuffman_vbe21_zd", nreads=reads, batch_reads=per)
     if rec is not None:
-        rec["calls"] = "press_hip_recode_batch" if recode else "press_hip_depress_batch + press_hip_press_batch"
+        rec["calls"] = "press_hip_recode_packed" if packed else "press_hip_recode_batch" if recode else "press_hip_depress_batch + press_hip_press_batch"
     print(json.dumps(rec))
 
 

@@ -1,20 +1,24 @@
 #!/usr/bin/env python3
-"""press_hip_recode_batch against the two calls it replaces, device resident, on bench.py's 8192-read batch.
+"""press_hip_recode_packed and press_hip_recode_sizes against press_hip_recode_batch, device resident, on bench.py's
+8192-read batch.
 
     python3 tools/recode_bench.py [--reads 8192] [--baseline-lib PATH] [--seconds 0.5] [--once] [--out FILE]
 
-Legs, per pair (slow5_svb_zd -> shuffman_vbe21_zd, svb_zd -> vbe21_zd), alternated call block by call block within
-this one process after a warm-up, HIP events around every whole call, at least --seconds of timed calls per leg:
+Legs, per pair (slow5_svb_zd -> shuffman_vbe21_zd fused, svb_zd -> vbe21_zd fused, vbe21_zd -> slow5_svb_zd: an svb
+destination, vbe21_zd -> zstd_svb_zd: a zstd one), alternated call block by call block within this one process after a
+warm-up, HIP events around every whole call, at least --seconds of timed calls per leg:
 
-  baseline   press_hip_depress_batch + press_hip_press_batch of --baseline-lib (a libpress_hip.so built from the parent
-             commit: the yardstick), and the same leg a second time (baseline2) for the run-to-run spread
-  two_calls  the same two calls of this build (a cross-check, never the yardstick)
-  recode     press_hip_recode_batch of this build, the samples kept (sig given)
-  recode_ns  ... the samples left in library scratch (sig = NULL)
-
-The recode counts as faster only where it beats the baseline by more than |baseline - baseline2|.  --once: one call per
-leg and no timing (for rocprofv3 --kernel-trace --stats and tools/traffic.py, which want few launches).  Every leg's
-streams are compared with the first leg's before anything is timed.
+  baseline    press_hip_recode_batch of --baseline-lib (a libpress_hip.so built from the parent commit: the yardstick),
+              and the same leg a second time (baseline2) for the run-to-run spread
+  recode      press_hip_recode_batch of this build (the same code: a cross-check of the yardstick)
+  packed_a1   press_hip_recode_packed of this build, align 1
+  packed_a16  ... align 16
+  sizes       press_hip_recode_sizes of this build
+All with the samples kept (sig given).  A leg differs from the baseline only where the medians are further apart than
+|baseline - baseline2|.  Beside the times: the arena bytes of each layout (out_off[nreads]) against the sum of
+press_hip_bound over the reads, which is what a caller's slot table is made of.  --once: one call per leg and no timing
+(for rocprofv3 --kernel-trace --stats and tools/traffic.py, which want few launches).  Every leg's streams are compared
+with the first leg's before anything is timed.
 """
 import argparse
 import ctypes
@@ -26,7 +30,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-PAIRS = [("slow5_svb_zd", "shuffman_vbe21_zd"), ("svb_zd", "vbe21_zd")]
+PAIRS = [("slow5_svb_zd", "shuffman_vbe21_zd"), ("svb_zd", "vbe21_zd"), ("vbe21_zd", "slow5_svb_zd"), ("vbe21_zd", "zstd_svb_zd")]
 
 
 class Lib:
@@ -43,6 +47,11 @@ class Lib:
         self.has_recode = hasattr(l, "press_hip_recode_batch")
         if self.has_recode:
             l.press_hip_recode_batch.argtypes = [I, I, V, V, V, V, V, U32, U64, V, V, V, V, V, I]
+        if hasattr(l, "press_hip_recode_packed"):
+            l.press_hip_recode_sizes.argtypes = [I, I, V, V, V, V, V, U32, U64, V, V, V, I]
+            l.press_hip_recode_packed.argtypes = [I, I, V, V, V, V, V, U32, U64, V, U64, U32, V, V, V, V, I]
+        l.press_hip_bound.restype = U64
+        l.press_hip_bound.argtypes = [I, U32]
         self.ok(l.press_hip_set_device(torch.cuda.current_device()))
         self.ok(l.press_hip_set_stream(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
         self.ok(l.press_hip_load_table_file(table.encode()))
@@ -86,40 +95,58 @@ def main():
         d_outn = torch.zeros(R, dtype=torch.int32, device=dev)
         d_sig = torch.zeros_like(b.sig)
 
-        def two(lib):
+        d_poff = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+        d_need = torch.zeros(R, dtype=torch.int64, device=dev)
+
+        def rec(lib):
             def call():
-                lib.ok(lib.l.press_hip_depress_batch(sid, p(d_src), p(d_in_off), p(d_src_len), R, p(d_sig), p(b.d_off), p(b.d_n),
-                                                     total, p(d_outn), 1))
-                lib.ok(lib.l.press_hip_press_batch(did, p(d_sig), p(b.d_off), p(d_outn), R, total, p(d_out), p(d_out_off),
-                                                   p(d_len), 1))
+                lib.ok(lib.l.press_hip_recode_batch(sid, did, p(d_src), p(d_in_off), p(d_src_len), p(b.d_n), p(b.d_off), R, total,
+                                                    p(d_out), p(d_out_off), p(d_len), p(d_sig), p(d_outn), 1))
             return call
 
-        def rec(keep):
+        def packed(align):
             def call():
-                new.ok(new.l.press_hip_recode_batch(sid, did, p(d_src), p(d_in_off), p(d_src_len), p(b.d_n), p(b.d_off), R, total,
-                                                    p(d_out), p(d_out_off), p(d_len), p(d_sig) if keep else None, p(d_outn), 1))
+                new.ok(new.l.press_hip_recode_packed(sid, did, p(d_src), p(d_in_off), p(d_src_len), p(b.d_n), p(b.d_off), R,
+                                                     total, p(d_out), d_out.numel() - 64, align, p(d_poff), p(d_len), p(d_sig),
+                                                     p(d_outn), 1))
             return call
 
-        legs = ([("baseline", two(base)), ("baseline2", two(base))] if base else []) + \
-            [("two_calls", two(new)), ("recode", rec(True)), ("recode_ns", rec(False))]
+        def sizes():
+            new.ok(new.l.press_hip_recode_sizes(sid, did, p(d_src), p(d_in_off), p(d_src_len), p(b.d_n), p(b.d_off), R, total,
+                                                p(d_need), p(d_sig), p(d_outn), 1))
+
+        legs = ([("baseline", rec(base)), ("baseline2", rec(base))] if base and base.has_recode else []) + \
+            [("recode", rec(new)), ("packed_a1", packed(1)), ("packed_a16", packed(16)), ("sizes", sizes)]
         # warm-up and agreement: every leg's out_len, out_n and stream bytes as the first leg's
         ref = None
+        slot_off = d_out_off.cpu().numpy()
+        arena_bytes = {}
         for name, call in legs:
             d_out.zero_()
             d_len.zero_()
             for _ in range(1 if a.once else 3):
                 call()
             torch.cuda.synchronize()
+            assert bool((d_outn.cpu().numpy() == b.n).all()), name
+            if name == "sizes":
+                assert np.array_equal(d_need.cpu().numpy(), ref[0]), (name, "differs from", legs[0][0])
+                continue
             lens = d_len.cpu().numpy()
             assert (lens > 0).all() and (lens < caps).all(), (name, "a read failed")
-            assert bool((d_outn.cpu().numpy() == b.n).all()), name
-            got = (lens.copy(), d_out.cpu().numpy().copy())
+            offs = d_poff.cpu().numpy() if name.startswith("packed") else slot_off
+            if name.startswith("packed"):
+                arena_bytes[name] = int(offs[-1])
+            host = d_out.cpu().numpy()
+            got = (lens.copy(), np.concatenate([host[int(o):int(o) + int(l)] for o, l in zip(offs[:-1], lens)]))
             if ref is None:
                 ref = got
             else:
                 assert np.array_equal(ref[0], got[0]) and np.array_equal(ref[1], got[1]), (name, "differs from", legs[0][0])
         assert torch.equal(d_sig, b.sig), "the decoded samples differ"
-        rec_pair = {"stream_bytes_in": int(d_src_len.sum().item()), "stream_bytes_out": int(ref[0].sum()), "legs": {}}
+        bound = int(sum(int(new.l.press_hip_bound(did, int(x))) for x in b.n))
+        rec_pair = {"fused": bool(press.recode_fused(src, dst)), "stream_bytes_in": int(d_src_len.sum().item()),
+                    "stream_bytes_out": int(ref[0].sum()), "arena_bytes": arena_bytes, "sum_of_press_hip_bound": bound,
+                    "legs": {}}
         if not a.once:
             times = {name: [] for name, _ in legs}
             spent = {name: 0.0 for name, _ in legs}
@@ -140,12 +167,12 @@ def main():
                                           "p10_ms": float(np.percentile(ms, 10)), "p90_ms": float(np.percentile(ms, 90)),
                                           "timed_s": float(ms.sum() / 1000.0)}
             L = rec_pair["legs"]
-            if base:
+            if "baseline" in L:
                 spread = abs(L["baseline"]["median_ms"] - L["baseline2"]["median_ms"])
-                gain = L["baseline"]["median_ms"] - L["recode"]["median_ms"]
                 rec_pair["baseline_spread_ms"] = spread
-                rec_pair["recode_gain_ms"] = gain
-                rec_pair["recode_is_faster"] = bool(gain > spread)
+                for name in ("recode", "packed_a1", "packed_a16", "sizes"):
+                    rec_pair[name + "_minus_baseline_ms"] = L[name]["median_ms"] - L["baseline"]["median_ms"]
+                    rec_pair[name + "_differs"] = bool(abs(rec_pair[name + "_minus_baseline_ms"]) > spread)
         result["pairs"]["%s->%s" % (src, dst)] = rec_pair
     line = json.dumps(result)
     print(line)
