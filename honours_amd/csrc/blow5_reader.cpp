@@ -246,6 +246,7 @@ struct RecView {
 	uint64_t sig_bytes;
 	uint64_t sig_pos; // offset of the signal field in the inflated record (its u64 length sits 8 bytes before)
 	uint32_t nsamples;
+	const uint8_t *dor; // f64 digitisation, offset, range as stored (the sampling rate follows)
 };
 
 int parse_record(const press_hip_blow5 *f, RecView *v)
@@ -261,6 +262,7 @@ int parse_record(const press_hip_blow5 *f, RecView *v)
 		return b5_fail(PRESS_HIP_EARG, "BLOW5: record too short");
 	v->id = r.data() + p;
 	v->id_len = idl;
+	v->dor = r.data() + p + idl + 4;
 	p += (size_t) idl + 4 + 32;
 	uint64_t len;
 	memcpy(&len, r.data() + p, 8);
@@ -353,11 +355,10 @@ int press_hip_blow5_methods(const press_hip_blow5 *f, int *record_method, int *s
 	return 0;
 }
 
-int press_hip_blow5_next(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena, uint64_t arena_cap,
-			 uint64_t *sig_off, uint64_t *sig_len, uint32_t *n_samples, char *read_ids, uint32_t *got)
+// the loop of press_hip_blow5_next and press_hip_blow5_next_pa (dor: NULL, or three doubles per read)
+static int next_signals(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena, uint64_t arena_cap, uint64_t *sig_off,
+			uint64_t *sig_len, uint32_t *n_samples, char *read_ids, double *dor, uint32_t *got)
 {
-	if (!f || !arena || !sig_off || !sig_len || !n_samples || !got)
-		return b5_fail(PRESS_HIP_EARG, "BLOW5: NULL argument");
 	uint32_t k = 0;
 	uint64_t used = 0;
 	while (k < max_reads) {
@@ -385,6 +386,8 @@ int press_hip_blow5_next(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena,
 		sig_off[k] = at;
 		sig_len[k] = v.sig_bytes;
 		n_samples[k] = v.nsamples;
+		if (dor)
+			memcpy(dor + 3 * (size_t) k, v.dor, 24);
 		if (read_ids) {
 			char *dst = read_ids + (size_t) k * PRESS_HIP_BLOW5_ID_LEN;
 			const uint32_t c = v.id_len < PRESS_HIP_BLOW5_ID_LEN - 1 ? v.id_len : PRESS_HIP_BLOW5_ID_LEN - 1;
@@ -397,6 +400,25 @@ int press_hip_blow5_next(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena,
 	}
 	*got = k;
 	return 0;
+}
+
+int press_hip_blow5_next(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena, uint64_t arena_cap,
+			 uint64_t *sig_off, uint64_t *sig_len, uint32_t *n_samples, char *read_ids, uint32_t *got)
+{
+	if (!f || !arena || !sig_off || !sig_len || !n_samples || !got)
+		return b5_fail(PRESS_HIP_EARG, "BLOW5: NULL argument");
+	return next_signals(f, max_reads, arena, arena_cap, sig_off, sig_len, n_samples, read_ids, nullptr, got);
+}
+
+// ... and the calibration of every read: dor[3k ..] = digitisation, offset, range of read k as the record stores them
+// (press_hip_pa_cal makes press_hip_depress_pa_batch's two floats of them)
+int press_hip_blow5_next_pa(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena, uint64_t arena_cap,
+			    uint64_t *sig_off, uint64_t *sig_len, uint32_t *n_samples, char *read_ids, double *dor,
+			    uint32_t *got)
+{
+	if (!f || !arena || !sig_off || !sig_len || !n_samples || !dor || !got)
+		return b5_fail(PRESS_HIP_EARG, "BLOW5: NULL argument");
+	return next_signals(f, max_reads, arena, arena_cap, sig_off, sig_len, n_samples, read_ids, dor, got);
 }
 
 

@@ -275,8 +275,13 @@ static int stage_layout(const uint64_t *off, const uint32_t *n, uint32_t nreads,
 
 static int fetch_streams(uint8_t *out, const uint64_t *out_off, const std::vector<uint64_t> &rel, uint64_t *out_len,
 			 uint32_t nreads, hipStream_t s);
+static int fetch_elems(void *dst, const void *dev, size_t es, const uint64_t *off, const uint32_t *n, uint32_t *out_n,
+		       uint32_t nreads, const std::vector<uint32_t> &order, hipStream_t s);
 static int fetch_samples(int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t *out_n, uint32_t nreads,
-			 const std::vector<uint32_t> &order, hipStream_t s);
+			 const std::vector<uint32_t> &order, hipStream_t s)
+{
+	return fetch_elems(sig, g.sig.p, sizeof(int16_t), off, n, out_n, nreads, order, s);
+}
 // the source streams of a host-pointer depress packed back to back into `arena` while they are staged (the caller's slots
 // may be far apart), their offsets and lengths into `offs` and g.lens2
 static int stage_streams(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t nreads, DevBuf &arena,
@@ -631,19 +636,21 @@ extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint
 	return fetch_samples(sig, off, n, out_n, nreads, order, s);
 }
 
-// The tail of a host-pointer depress: out_n, then the decoded samples of g.sig into the caller's rooms (`order`: the
-// reads in ascending room order, check_disjoint).
-static int fetch_samples(int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t *out_n, uint32_t nreads,
-			 const std::vector<uint32_t> &order, hipStream_t s)
+// The tail of a host-pointer depress: out_n, then the decoded elements (es bytes each: int16 samples of g.sig, floats of
+// g.pa_out) of the device arena `dev` into the caller's rooms in `dst` (`order`: the reads in ascending room order,
+// check_disjoint).
+static int fetch_elems(void *dst, const void *dev, size_t es, const uint64_t *off, const uint32_t *n, uint32_t *out_n,
+		       uint32_t nreads, const std::vector<uint32_t> &order, hipStream_t s)
 {
+	uint8_t *const sig = (uint8_t *) dst;
+	const uint8_t *const dsig = (const uint8_t *) dev;
 	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	if (nreads <= 4) {
 		for (uint32_t r = 0; r < nreads; r++) {
 			if (out_n[r] == UINT32_MAX || out_n[r] == 0)
 				continue;
-			HIPCHK(hipMemcpyAsync(sig + off[r], (int16_t *) g.sig.p + off[r], (size_t) out_n[r] * 2,
-					      hipMemcpyDeviceToHost, s));
+			HIPCHK(hipMemcpyAsync(sig + off[r] * es, dsig + off[r] * es, (size_t) out_n[r] * es, hipMemcpyDeviceToHost, s));
 		}
 		HIPCHK(hipStreamSynchronize(s));
 		return 0;
@@ -661,8 +668,8 @@ static int fetch_samples(int16_t *sig, const uint64_t *off, const uint32_t *n, u
 			continue;
 		if (out_n[r] > n[r])
 			return set_error(PRESS_HIP_EHIP, "read %u decoded %u samples into a room of %u", r, out_n[r], n[r]);
-		pc.push_back({ (uint8_t *) (sig + off[r]), off[r] * 2, (uint64_t) out_n[r] * 2 });
-		end = (off[r] + out_n[r]) * 2;
+		pc.push_back({ sig + off[r] * es, off[r] * es, (uint64_t) out_n[r] * es });
+		end = (off[r] + out_n[r]) * es;
 	}
 	if (is_pinned(sig)) { // page-locked: the decoded ranges go straight to the caller, one DMA per run of reads
 		size_t i = 0;
@@ -672,16 +679,73 @@ static int fetch_samples(int16_t *sig, const uint64_t *off, const uint32_t *n, u
 			while (k + 1 < pc.size() && pc[k + 1].dense - (pc[k].dense + pc[k].len) < 128)
 				k++;
 			const uint64_t b0 = pc[i].dense, b1 = pc[k].dense + pc[k].len;
-			HIPCHK(hipMemcpyAsync((uint8_t *) sig + b0, (uint8_t *) g.sig.p + b0, b1 - b0, hipMemcpyDeviceToHost, s));
+			HIPCHK(hipMemcpyAsync(sig + b0, dsig + b0, b1 - b0, hipMemcpyDeviceToHost, s));
 			i = k + 1;
 		}
 		HIPCHK(hipStreamSynchronize(s));
 		return 0;
 	}
-	if ((rc = staged_pieces<false>((uint8_t *) g.sig.p, end, pc, s)))
+	if ((rc = staged_pieces<false>(const_cast<uint8_t *>(dsig), end, pc, s)))
 		return rc;
 	HIPCHK(hipStreamSynchronize(s));
 	return 0;
+}
+
+// Picoamperes: press_hip_depress_batch with the float arena `pa` in the place of sig.  A fused method's decode kernel
+// writes the floats itself; the others decode into g.rsig and k_pa_convert follows (launch_depress_pa).
+extern "C" int press_hip_depress_pa_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+					  uint32_t nreads, float *pa, const uint64_t *off, const uint32_t *n,
+					  uint64_t total_samples, const float *cal, uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	if (!method_ok(method)) // (before any device call)
+		return set_error(PRESS_HIP_EARG, "method %d is not available in the batch API", method);
+	if (nreads && (!in || !in_off || !in_len || !pa || !off || !n || !cal || !out_n))
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	int rc = ctx_init();
+	if (rc || (rc = check_method(method)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_pa_plan(method, total_samples, nreads, !device_resident);
+	if ((rc = plan.reserve()))
+		return rc;
+	DecodeArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	a.sig = (int16_t *) plan.ptr(&Ctx::rsig); // (NULL for a fused method: its kernel has no use for it)
+
+	if (device_resident) {
+		if ((uintptr_t) pa & 15)
+			return set_error(PRESS_HIP_EARG, "pa must be 16-byte aligned");
+		a.in = in;
+		a.in_off = in_off;
+		a.in_len = in_len;
+		a.off = off;
+		a.nsamp = n;
+		a.out_n = out_n;
+		return launch_depress_pa(plan, a, pa, cal, s);
+	}
+
+	std::vector<uint32_t> order;
+	if ((rc = check_disjoint(off, n, nreads, "the sample room", order)))
+		return rc;
+	if ((rc = stage_layout(off, n, nreads, total_samples, s, false)))
+		return rc;
+	std::vector<uint64_t> doff;
+	if ((rc = stage_streams(in, in_off, in_len, nreads, g.arena, g.arena_off, doff, s)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(g.pa_cal.p, cal, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	a.in = (const uint8_t *) g.arena.p;
+	a.in_off = (const uint64_t *) g.arena_off.p;
+	a.in_len = (const uint64_t *) g.lens2.p;
+	a.off = (const uint64_t *) g.off.p;
+	a.nsamp = (const uint32_t *) g.nsamp.p;
+	a.out_n = (uint32_t *) g.outn.p;
+	if ((rc = launch_depress_pa(plan, a, (float *) g.pa_out.p, (const float *) g.pa_cal.p, s)))
+		return rc;
+	return fetch_elems(pa, g.pa_out.p, sizeof(float), off, n, out_n, nreads, order, s);
 }
 
 

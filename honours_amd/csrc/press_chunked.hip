@@ -72,6 +72,31 @@ __device__ __forceinline__ void st16_stream(void *p, uint4 v)
 __device__ __forceinline__ void st16_stream(void *p, uint4 v) { *reinterpret_cast<uint4 *>(p) = v; }
 #endif
 
+// Picoamperes (press_hip_depress_pa_batch): pa = ((float) s + c0) * c1, the reference's signal_in_picoamps (sigtk
+// misc.c:28).  The add and the multiply round one after the other: no contraction into a fused multiply-add here,
+// whatever the build's default.
+__device__ __forceinline__ float to_pa(int32_t smp, float c0, float c1)
+{
+#pragma clang fp contract(off)
+	const float t = (float) smp + c0;
+	return t * c1;
+}
+// the k-th of the 8 samples a lane holds as packed pairs
+__device__ __forceinline__ float pa_of(const uint32_t (&v)[4], int k, float c0, float c1)
+{
+	return to_pa((k & 1) ? (int32_t) v[k >> 1] >> 16 : (int32_t) (int16_t) (v[k >> 1] & 0xFFFFu), c0, c1);
+}
+// ... all 8 to p (32-byte aligned): two 16-byte stores
+__device__ __forceinline__ void st_pa8(float *p, const uint32_t (&v)[4], float c0, float c1)
+{
+	uint32_t x[8];
+#pragma unroll
+	for (int k = 0; k < 8; k++)
+		x[k] = __float_as_uint(pa_of(v, k, c0, c1));
+	st16_stream(p, make_uint4(x[0], x[1], x[2], x[3]));
+	st16_stream(p + 4, make_uint4(x[4], x[5], x[6], x[7]));
+}
+
 __device__ __forceinline__ uint32_t wave_incl_scan32(uint32_t v)
 {
 	const int lane = threadIdx.x & 63;
@@ -863,12 +888,19 @@ __device__ __forceinline__ void wave_lds_sync()
 // wrapped zig-zag delta above 255, never sample 0: a plain sub-tile holds none (its values are single bytes, which the
 // 32-bit delta of slow5's stream is only where the wrapped one is the same byte); the others recompute it from the
 // deltas they have undone.
+//
+// OUT = float (press_hip_depress_pa_batch): the other second consumer.  Phase 3 converts the 8 samples a lane holds to
+// picoamperes with the read's two calibration floats (f.cal, loaded once per workgroup) and writes them to f.pa as two
+// 16-byte stores; the ragged tail writes its floats one by one and none at or beyond n.  a.sig is not used: no int16
+// copy of the samples is made.
 __device__ __forceinline__ uint32_t exc_mask(const uint4 &z, uint32_t i0);
 __device__ __forceinline__ uint32_t low_mask(const uint4 &z, uint32_t i0, uint32_t n);
-template <bool KEY2, bool ZD, bool S5 = false, int FUSE = 0>
+template <bool KEY2, bool ZD, bool S5 = false, int FUSE = 0, typename OUT = int16_t>
 __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a, FuseArgs f)
 {
 	static_assert(!FUSE || ZD, "the fused counts are those of the zig-zag delta methods");
+	constexpr bool PA = sizeof(OUT) == sizeof(float);
+	static_assert(!PA || !FUSE, "one second consumer at a time");
 #ifdef DEC_STAMPS
 	const uint64_t t_start = __builtin_amdgcn_s_memtime();
 #endif
@@ -924,7 +956,9 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a, FuseAr
 	}
 	const uint8_t *in = a.in + d.out_base + (S5 ? 4 : 0);
 	const uint64_t in_len = uni64(a.in_len[d.read]) - (S5 ? 4 : 0);
-	int16_t *out = a.sig + d.sig_off;
+	OUT *out = (PA ? (OUT *) f.pa : (OUT *) a.sig) + d.sig_off;
+	const float c0 = PA ? __uint_as_float(uni(__float_as_uint(f.cal[2 * (size_t) d.read]))) : 0.f;
+	const float c1 = PA ? __uint_as_float(uni(__float_as_uint(f.cal[2 * (size_t) d.read + 1]))) : 0.f;
 	const uint32_t klen = KEY2 ? (n + 3) / 4 : (n >> 3) + (((n & 7) + 7) >> 3);
 	const uint64_t dlen = in_len - klen; // bytes in the data section (cap_ok: klen <= in_len)
 	const uint8_t *data = in + klen;
@@ -1079,8 +1113,12 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a, FuseAr
 				for (int q = 0; q < 4; q++)
 					v[q] = pk_add16(v[q], b2);
 			}
-			if (i0 < n)
-				st16_stream(out + i0, make_uint4(v[0], v[1], v[2], v[3]));
+			if (i0 < n) {
+				if constexpr (PA)
+					st_pa8(out + i0, v, c0, c1);
+				else
+					st16_stream(out + i0, make_uint4(v[0], v[1], v[2], v[3]));
+			}
 			if (FUSE && i0 < n) { // one-byte values only: no exception; their code lengths straight from the stream's bytes
 				f_ored |= v[0] | v[1] | v[2] | v[3];
 				if (k == 0)
@@ -1139,7 +1177,16 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a, FuseAr
 				}
 			}
 		}
-		if (i0 + 8 <= n) {
+		if constexpr (PA) {
+			if (i0 + 8 <= n) {
+				st_pa8(out + i0, v, c0, c1);
+			} else if (i0 < n) {
+#pragma unroll
+				for (int q = 0; q < 8; q++)
+					if ((uint32_t) q < n - i0)
+						out[i0 + q] = pa_of(v, q, c0, c1);
+			}
+		} else if (i0 + 8 <= n) {
 			st16_stream(out + i0, make_uint4(v[0], v[1], v[2], v[3]));
 		} else if (i0 < n) {
 #pragma unroll
@@ -2295,8 +2342,8 @@ void launch_svb_encode_packed(const BatchArgs &a, bool key2bit, bool zd, bool sl
 		run_encode_packed<false, false>(a, pk, s);
 }
 
-template <bool KEY2, bool ZD, bool S5 = false>
-static void run_decode(const DecodeArgs &a, hipStream_t s)
+template <bool KEY2, bool ZD, bool S5 = false, typename OUT = int16_t>
+static void run_decode(const DecodeArgs &a, hipStream_t s, const FuseArgs &f = FuseArgs{})
 {
 	(void) hipMemsetAsync(a.ctl, 0, sizeof(ChunkCtl), s);
 	hipLaunchKernelGGL((k_chunk_prep<true, KEY2>), dim3((a.nreads + 255) / 256), dim3(256), 0, s, a.off,
@@ -2307,7 +2354,7 @@ static void run_decode(const DecodeArgs &a, hipStream_t s)
 	hipLaunchKernelGGL((k_svb_keyscan<KEY2, S5>), dim3((a.max_chunks + 3) / 4), dim3(CWG), 0, s, a);
 	hipLaunchKernelGGL((k_svb_keyprefix<KEY2, S5>), dim3((a.nreads + 3) / 4), dim3(256), 0, s, a);
 	ktime_begin(1, s);
-	hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, ZD, S5>), dim3(a.max_chunks), dim3(CWG), 0, s, a, FuseArgs{});
+	hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, ZD, S5, 0, OUT>), dim3(a.max_chunks), dim3(CWG), 0, s, a, f);
 	ktime_end(1, s);
 }
 
@@ -2387,7 +2434,7 @@ static void run_recode(const DecodeArgs &d, const BatchArgs &p, int fmt, int ent
 	hipLaunchKernelGGL((k_svb_keyprefix<KEY2, S5>), dim3((d.nreads + 3) / 4), dim3(256), 0, s, d);
 	launch_recode_counts(d.out_n, const_cast<uint32_t *>(p.nsamp), d.nreads, s);
 	ex_encode_prep(p, s);
-	const FuseArgs f = { p.chunks, p.first_chunk, p.cbits, p.meta, p.huff };
+	const FuseArgs f = { p.chunks, p.first_chunk, p.cbits, p.meta, p.huff, nullptr, nullptr };
 	ktime_begin(1, s);
 	if (ent == 1)
 		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 2>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
@@ -2426,7 +2473,7 @@ static void run_recode_packed(const DecodeArgs &d, const BatchArgs &p, int fmt, 
 	launch_recode_counts(d.out_n, const_cast<uint32_t *>(p.nsamp), d.nreads, s);
 	(void) hipMemsetAsync(pk.slot, 0, ((size_t) p.nreads + 1) * 8, s);
 	ex_encode_prep(p, s);
-	const FuseArgs f = { p.chunks, p.first_chunk, p.cbits, p.meta, p.huff };
+	const FuseArgs f = { p.chunks, p.first_chunk, p.cbits, p.meta, p.huff, nullptr, nullptr };
 	ktime_begin(1, s);
 	if (ent == 1)
 		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 2>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
@@ -2578,6 +2625,80 @@ void launch_svb_decode_chunked(const DecodeArgs &a, bool key2bit, bool zd, hipSt
 		run_decode<false, true>(a, s);
 	else
 		run_decode<false, false>(a, s);
+}
+
+// the same chain with the float writer (press_hip_depress_pa_batch, the fused methods): a.sig is not used
+void launch_svb_decode_pa(const DecodeArgs &a, float *pa, const float *cal, bool key2bit, bool zd, bool slow5, hipStream_t s)
+{
+	if (!a.nreads || !a.max_chunks)
+		return;
+	FuseArgs f{};
+	f.pa = pa;
+	f.cal = cal;
+	if (slow5)
+		run_decode<true, true, true, float>(a, s, f);
+	else if (key2bit)
+		run_decode<true, true, false, float>(a, s, f);
+	else if (zd)
+		run_decode<false, true, false, float>(a, s, f);
+	else
+		run_decode<false, false, false, float>(a, s, f);
+}
+
+// ------------------------------------------------------------------ picoamperes of decoded samples (the other methods)
+//
+// press_hip_depress_pa_batch for a method whose decoder is not fused: the decoder has left int16 samples in library
+// scratch at the caller's off[]; every read is cut into tiles of CHUNK samples, one workgroup per tile.
+
+// One thread per read: the read's tiles (its ROOM's: out_n is not known on the host, and a tile beyond the decoded
+// count ends at once) get contiguous ids, taken by one atomic per wave as in k_chunk_prep; tiles[id] = { read, j }.
+__global__ __launch_bounds__(256) void k_pa_tiles(const uint32_t *nsamp, uint32_t nreads, uint2 *tiles, uint32_t *ntiles,
+						   uint32_t max_tiles)
+{
+	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+	const uint32_t nt = r < nreads ? (uint32_t) (((uint64_t) nsamp[r] + CHUNK - 1) / CHUNK) : 0u;
+	const uint32_t inc = wave_incl_scan32(nt);
+	uint32_t base = 0;
+	if ((threadIdx.x & 63) == 63 && inc)
+		base = atomicAdd(ntiles, inc);
+	base = (uint32_t) __builtin_amdgcn_readlane((int) base, 63);
+	const uint32_t first = base + inc - nt;
+	for (uint32_t j = 0; j < nt && first + j < max_tiles; j++) // (max_tiles bounds the sum)
+		tiles[first + j] = make_uint2(r, j);
+}
+
+// One workgroup per tile: [0, roundup8(out_n[r])) of the read, 8 samples per lane and step - a 16-byte load, two 16-byte
+// stores.  A refused read gets nothing.
+__global__ __launch_bounds__(256) void k_pa_convert(const int16_t *sig, const uint64_t *off, const uint32_t *out_n,
+						     const float *cal, float *pa, const uint2 *tiles, const uint32_t *ntiles)
+{
+	if (blockIdx.x >= uni(*ntiles))
+		return; // (the grid is an upper bound)
+	const uint32_t r = uni(tiles[blockIdx.x].x), j = uni(tiles[blockIdx.x].y);
+	const uint32_t on = uni(out_n[r]);
+	if (on == CFAIL32)
+		return;
+	const uint64_t cnt = ((uint64_t) on + 7) & ~7ull;
+	const uint64_t first = (uint64_t) j * CHUNK;
+	const uint64_t end = first + CHUNK < cnt ? first + CHUNK : cnt;
+	const uint64_t o = uni64(off[r]);
+	const float c0 = __uint_as_float(uni(__float_as_uint(cal[2 * (size_t) r])));
+	const float c1 = __uint_as_float(uni(__float_as_uint(cal[2 * (size_t) r + 1])));
+	for (uint64_t i = first + threadIdx.x * 8; i < end; i += 256 * 8) {
+		const uint4 q = ld16_stream(sig + o + i);
+		const uint32_t v[4] = { q.x, q.y, q.z, q.w };
+		st_pa8(pa + o + i, v, c0, c1);
+	}
+}
+
+void launch_pa_convert(const DecodeArgs &a, float *pa, const float *cal, uint2 *tiles, uint32_t *ntiles, hipStream_t s)
+{
+	if (!a.nreads || !a.max_chunks)
+		return;
+	(void) hipMemsetAsync(ntiles, 0, sizeof(uint32_t), s);
+	hipLaunchKernelGGL(k_pa_tiles, dim3((a.nreads + 255) / 256), dim3(256), 0, s, a.nsamp, a.nreads, tiles, ntiles, a.max_chunks);
+	hipLaunchKernelGGL(k_pa_convert, dim3(a.max_chunks), dim3(256), 0, s, (const int16_t *) a.sig, a.off, (const uint32_t *) a.out_n,
+			   cal, pa, (const uint2 *) tiles, (const uint32_t *) ntiles);
 }
 
 } // namespace ph

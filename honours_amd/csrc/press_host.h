@@ -66,6 +66,7 @@ struct Ctx {
 	DevBuf ztmp, zoff, zoff4, zlen, zhist, ztab, zfirst, zblk, zsbits, zbpos, zbflag, zkcnt, zrd, znb, zn, zdcopy, zdhuf, zdunit, zdtree, zdlong, zdctl, zdseq, zdxblk; // zstd frames
 	DevBuf rsig, rn, rkeep, pchunks, pfirst, pctl; // recode: samples nobody asked for, the press half's counts, refused reads' slot heads, its chunk table
 	DevBuf pneed, pslot; // packed press: the reads' sizes, the slot table its writing kernels see (PackArgs)
+	DevBuf pa_tile, pa_ctl, pa_cal, pa_out; // picoamperes: the converter's tile table and its count; host path: the staged calibration, the float arena
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams
@@ -200,6 +201,11 @@ RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t n
 // of keep_heads stay in the plan and unused: a refused read of the packed form has no slot)
 RecodePlan make_recode_packed_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples);
 
+// press_hip_depress_pa_batch: the decode plan of the method; unless the method is fused (depress_pa_fused) the samples and
+// the converter's tile table; host pointers: the staged calibration and the float arena
+bool depress_pa_fused(int method);
+ScratchPlan make_pa_plan(int method, uint64_t total_samples, uint32_t nreads, bool host);
+
 // press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
 ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);
 
@@ -207,6 +213,8 @@ int check_method(int method); // EARG / ENOTABLE
 int launch_status();          // EHIP if a kernel launch since the last call failed
 int launch_press(const ScratchPlan &p, const BatchArgs &a, hipStream_t s);
 int launch_depress(const ScratchPlan &p, const DecodeArgs &a, hipStream_t s);
+// p from make_pa_plan; a.sig: the samples' scratch of a method that is not fused (unused for a fused one)
+int launch_depress_pa(const ScratchPlan &p, const DecodeArgs &a, float *pa, const float *cal, hipStream_t s);
 // phases: PACK_SIZE | PACK_WRITE (press_internal.h); a.out_off must be pk.slot
 int launch_press_packed(const ScratchPlan &p, const BatchArgs &a, const PackArgs &pk, int phases, hipStream_t s);
 

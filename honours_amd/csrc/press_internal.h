@@ -324,6 +324,9 @@ struct FuseArgs {
 	ChunkBits *cbits;
 	ReadMeta *meta;
 	const HuffDev *huff;
+	// k_svb_decode_chunked<.., float> (press_hip_depress_pa_batch): the float arena at the caller's off[], two floats per read
+	float *pa;
+	const float *cal;
 };
 constexpr uint32_t RECODE_KEEP = 64; // bytes of a refused read's slot kept aside (an empty read's stream is 4 / 16 bytes)
 void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent, hipStream_t s);
@@ -342,6 +345,10 @@ void ktime_mute(bool m); // a composite launcher times its own kernel instead of
 // launchers.  All asynchronous on `s`.
 void launch_svb_encode_chunked(const BatchArgs &a, bool key2bit, bool zd, hipStream_t s, bool slow5 = false); // chunks + look-back
 void launch_svb_decode_chunked(const DecodeArgs &a, bool key2bit, bool zd, hipStream_t s, bool slow5 = false);
+// picoamperes (press_hip_depress_pa_batch): the svb decode with the float writer (a.sig unused), and for the other
+// methods the converter of the samples their decoder left at a.sig (tiles: max_chunks entries, ntiles: one word)
+void launch_svb_decode_pa(const DecodeArgs &a, float *pa, const float *cal, bool key2bit, bool zd, bool slow5, hipStream_t s);
+void launch_pa_convert(const DecodeArgs &a, float *pa, const float *cal, uint2 *tiles, uint32_t *ntiles, hipStream_t s);
 void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip

@@ -143,6 +143,21 @@ ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads
 	return p;
 }
 
+// The svb family's decode kernel writes picoamperes itself; the zstd compositions over it take the general path (their
+// second stage is launched by press_zstd.hip with arguments of its own).
+bool depress_pa_fused(int method) { return method_ok(method) && METHODS[method].family == FAM_SVB; }
+
+ScratchPlan make_pa_plan(int method, uint64_t total_samples, uint32_t nreads, bool host)
+{
+	ScratchPlan p = make_plan(method, total_samples, nreads, true);
+	if (!depress_pa_fused(method))
+		p.need(&Ctx::rsig, total_samples * 2 + 64).need(&Ctx::pa_tile, (size_t) p.max_chunks * sizeof(uint2))
+			.need(&Ctx::pa_ctl, 64);
+	if (host)
+		p.need(&Ctx::pa_cal, (size_t) nreads * 8).need(&Ctx::pa_out, total_samples * 4 + 64);
+	return p;
+}
+
 // Fused pairs: BLOW5's and the reference's svb-zd streams into any exception-split method.  (svb12 has no deltas; the zstd
 // kinds and the svb destinations take the general path.)
 bool recode_fused(int src, int dst)
@@ -284,6 +299,38 @@ extern "C" uint64_t press_hip_recode_packed_workspace_bytes(int src_method, int 
 	return b;
 }
 
+// as press_hip_workspace_bytes, and what the device-resident press_hip_depress_pa_batch adds for a method that is not fused
+extern "C" uint64_t press_hip_depress_pa_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads)
+{
+	API_LOCK;
+	if (!method_ok(method))
+		return 0;
+	ScratchPlan p = make_pa_plan(method, total_samples, nreads, false);
+	const ScratchPlan e = make_plan(method, total_samples, nreads, false);
+	for (int i = 0; i < e.nrows; i++)
+		p.need(e.rows[i].buf, e.rows[i].bytes);
+	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
+	for (int i = 0; i < p.nrows; i++)
+		b += p.rows[i].bytes;
+	return b;
+}
+
+extern "C" int press_hip_depress_pa_fused(int method) { return depress_pa_fused(method) ? 1 : 0; }
+
+// cal[2r] = (float) offset, cal[2r + 1] = (float) range / (float) digitisation: the reference's casts and its
+// single-precision division (sigtk misc.c:17-26)
+extern "C" int press_hip_pa_cal(const double *dor, uint32_t nreads, float *cal)
+{
+	if (nreads && (!dor || !cal))
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	for (uint32_t r = 0; r < nreads; r++) {
+		const float dig = (float) dor[3 * (size_t) r], rng = (float) dor[3 * (size_t) r + 2];
+		cal[2 * (size_t) r] = (float) dor[3 * (size_t) r + 1];
+		cal[2 * (size_t) r + 1] = rng / dig;
+	}
+	return 0;
+}
+
 extern "C" int press_hip_packed_exact(int method) { return method_ok(method) && !is_rc(METHODS[method]) ? 1 : 0; }
 
 extern "C" int press_hip_recode_fused(int src_method, int dst_method) { return recode_fused(src_method, dst_method) ? 1 : 0; }
@@ -390,6 +437,20 @@ static int zs_host_frames(const DecodeArgs &a, const ZsBufs &z, hipStream_t s, b
 	}
 	HIPCHK(hipMemcpy(z.rd, rd.data(), (size_t) nr * sizeof(ZsRead), hipMemcpyHostToDevice));
 	return 0;
+}
+
+int ph::launch_depress_pa(const ScratchPlan &p, const DecodeArgs &a, float *pa, const float *cal, hipStream_t s)
+{
+	const Method &m = *p.m;
+	if (depress_pa_fused(m.id)) {
+		launch_svb_decode_pa(a, pa, cal, m.key2, m.zd, m.slow5, s);
+		return launch_status();
+	}
+	const int rc = launch_depress(p, a, s);
+	if (rc)
+		return rc;
+	launch_pa_convert(a, pa, cal, (uint2 *) p.ptr(&Ctx::pa_tile), (uint32_t *) p.ptr(&Ctx::pa_ctl), s);
+	return launch_status();
 }
 
 int ph::launch_depress(const ScratchPlan &p, const DecodeArgs &a, hipStream_t s)

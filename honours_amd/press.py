@@ -73,6 +73,8 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_get_stream",
      "press_hip_synchronize", "press_hip_load_table_file", "press_hip_set_table", "press_hip_bound",
      "press_hip_press_batch", "press_hip_depress_batch", "press_hip_workspace_bytes",
+     "press_hip_pa_cal", "press_hip_depress_pa_batch", "press_hip_depress_pa_fused",
+     "press_hip_depress_pa_workspace_bytes", "press_hip_blow5_next_pa",
      "press_hip_recode_batch", "press_hip_recode_workspace_bytes", "press_hip_recode_fused",
      "press_hip_recode_sizes", "press_hip_recode_packed", "press_hip_recode_packed_workspace_bytes",
      "press_hip_press_sizes", "press_hip_press_packed", "press_hip_packed_exact", "press_hip_packed_workspace_bytes",
@@ -119,6 +121,16 @@ def load_library(path=LIB_PATH):
                                                  ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                  ctypes.c_int]
+        _lib.press_hip_pa_cal.restype = ctypes.c_int
+        _lib.press_hip_pa_cal.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+        _lib.press_hip_depress_pa_batch.restype = ctypes.c_int
+        _lib.press_hip_depress_pa_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_depress_pa_fused.restype = ctypes.c_int
+        _lib.press_hip_depress_pa_fused.argtypes = [ctypes.c_int]
+        _lib.press_hip_depress_pa_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_depress_pa_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
         _lib.press_hip_recode_batch.restype = ctypes.c_int
         _lib.press_hip_recode_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
@@ -410,6 +422,33 @@ def depress_batch(method, comp, in_off, in_len, sig, off, n, out_n):
         raise PressError(last_error())
 
 
+def pa_cal(dor):
+    """(nreads, 3) float64 {digitisation, offset, range} as BLOW5 stores them -> (nreads, 2) float32 calibration
+    {offset, range / digitisation} for depress_pa_batch (press_hip_pa_cal: host arithmetic, no GPU)"""
+    dor = np.ascontiguousarray(dor, dtype=np.float64).reshape(-1, 3)
+    cal = np.zeros((dor.shape[0], 2), dtype=np.float32)
+    if load_library().press_hip_pa_cal(dor.ctypes.data, dor.shape[0], cal.ctypes.data):
+        raise PressError(last_error())
+    return cal
+
+
+def depress_pa_batch(method, comp, in_off, in_len, pa, off, n, cal, out_n):
+    """Enqueue the decompression of a batch straight to picoamperes (CUDA tensors as in depress_batch; pa float32 in
+    the place of sig, cal float32 of 2 * nreads: pa_cal): pa[off[r] + i] = ((float) s[i] + cal[2r]) * cal[2r + 1]."""
+    lib = load_library()
+    nreads = off.numel()
+    rc = lib.press_hip_depress_pa_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), nreads,
+                                        pa.data_ptr(), off.data_ptr(), n.data_ptr(), pa.numel(), cal.data_ptr(),
+                                        out_n.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def depress_pa_fused(method):
+    """True where the decode kernel writes the floats itself (press_hip_depress_pa_fused)"""
+    return bool(load_library().press_hip_depress_pa_fused(_mid(method)))
+
+
 def recode_batch(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, out_n, sig=None, total_samples=None):
     """Enqueue the recoding of a batch of `src` streams into `dst` streams (CUDA tensors as in depress_batch and
     press_batch).  sig: the int16 tensor that also receives the decoded samples, or None - they then stay in library
@@ -625,6 +664,32 @@ def depress_batch_host(method, streams, ns):
     if rc:
         raise PressError(last_error())
     return [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy()
+            for o, k in zip(off, out_n)]
+
+
+def depress_pa_batch_host(method, streams, ns, cals):
+    """Batch decode to picoamperes with host buffers: streams = list of bytes, ns = sample counts / capacities,
+    cals = (nreads, 2) float32 (pa_cal) -> list of float32 arrays (None: the read failed)."""
+    lib = load_library()
+    nreads = len(streams)
+    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+    in_off = np.zeros(nreads, dtype=np.uint64)
+    if nreads > 1:
+        in_off[1:] = np.cumsum(in_len)[:-1]
+    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
+    ns = np.asarray(ns, dtype=np.uint32)
+    cal = np.ascontiguousarray(cals, dtype=np.float32).reshape(-1)
+    if cal.size != 2 * nreads:
+        raise PressError("depress_pa_batch_host: two calibration floats per read")
+    off, total = _layout(ns)
+    pa = np.zeros(total + 64, dtype=np.float32)
+    out_n = np.zeros(nreads, dtype=np.uint32)
+    rc = lib.press_hip_depress_pa_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
+                                        nreads, pa.ctypes.data, off.ctypes.data, ns.ctypes.data, total,
+                                        cal.ctypes.data, out_n.ctypes.data, 0)
+    if rc:
+        raise PressError(last_error())
+    return [None if int(k) == 0xFFFFFFFF else pa[int(o): int(o) + int(k)].copy()
             for o, k in zip(off, out_n)]
 
 
@@ -891,6 +956,30 @@ class Blow5Reader:
         for k in range(got.value):
             rid = ids.raw[k * self.ID_LEN:(k + 1) * self.ID_LEN].split(b"\0")[0].decode()
             out.append((rid, int(ns[k]), arena[int(off[k]):int(off[k]) + int(ln[k])].tobytes()))
+        return out
+
+    def next_batch_pa(self, max_reads=4096, arena_bytes=1 << 28):
+        """-> list of (read_id, n_samples, signal field bytes, (digitisation, offset, range)); empty at the end of the
+        file.  The three doubles as the record stores them: pa_cal makes depress_pa_batch's calibration of them."""
+        lib = load_library()
+        lib.press_hip_blow5_next_pa.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+        arena = np.empty(arena_bytes, dtype=np.uint8)
+        off = np.zeros(max_reads, dtype=np.uint64)
+        ln = np.zeros(max_reads, dtype=np.uint64)
+        ns = np.zeros(max_reads, dtype=np.uint32)
+        dor = np.zeros((max_reads, 3), dtype=np.float64)
+        ids = ctypes.create_string_buffer(max_reads * self.ID_LEN)
+        got = ctypes.c_uint32()
+        if lib.press_hip_blow5_next_pa(self._h, max_reads, arena.ctypes.data, arena_bytes, off.ctypes.data,
+                                       ln.ctypes.data, ns.ctypes.data, ids, dor.ctypes.data, ctypes.byref(got)):
+            raise PressError(lib.press_hip_blow5_last_error().decode())
+        out = []
+        for k in range(got.value):
+            rid = ids.raw[k * self.ID_LEN:(k + 1) * self.ID_LEN].split(b"\0")[0].decode()
+            out.append((rid, int(ns[k]), arena[int(off[k]):int(off[k]) + int(ln[k])].tobytes(),
+                        (float(dor[k, 0]), float(dor[k, 1]), float(dor[k, 2]))))
         return out
 
     def set_threads(self, n):

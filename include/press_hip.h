@@ -382,6 +382,45 @@ int press_hip_depress_batch(int method, const uint8_t *in, const uint64_t *in_of
 			    uint32_t *out_n, int device_resident);
 
 /*
+ * Decompress nreads streams straight to current in picoamperes: press_hip_depress_batch with float output.
+ *
+ * The conversion is the reference's signal_in_picoamps (sigtk misc.c:15-32, the TO_PICOAMPS macro; pyslow5's pA = True),
+ * bit for bit.  Read r has two floats of calibration,
+ *     cal[2r]     = (float) offset
+ *     cal[2r + 1] = (float) range / (float) digitisation       (the casts first, the division in single precision)
+ * which press_hip_pa_cal makes of the three doubles a BLOW5 record stores (host arithmetic, no GPU), and
+ *     pa[off[r] + i] = ((float) s[i] + cal[2r]) * cal[2r + 1]
+ * where s is what press_hip_depress_batch decodes.  The add and the multiply round separately, to nearest, in IEEE
+ * single precision - never fused -, so the floats depend on the sample and the two floats alone and are the same for
+ * every method.  cal is not validated: NaN and inf propagate.
+ *   in/in_off/in_len/off/n/total_samples/out_n   as in press_hip_depress_batch, with its checks, its room rules, its
+ *            empty-read rules, PRESS_HIP_ENOTABLE and the zstd kinds' host wait; out_n is what that call gives
+ *   pa       takes the place of sig: off[] counts floats.  Device resident it must be 16-byte aligned (PRESS_HIP_EARG),
+ *            and floats are written to [off[r], off[r] + roundup8(n[r])) at most; what lies at or beyond out_n[r] in
+ *            that range is unspecified - except that a read one of the four svb methods (svb12, svb12_zd, svb_zd,
+ *            slow5_svb_zd) decodes is written as [off[r], off[r] + out_n[r]) and nothing else.  Nothing outside the
+ *            rooms is written.  Host buffers receive exactly out_n[r] floats per read.  A refused read
+ *            (out_n[r] = UINT32_MAX) leaves its neighbours' rooms alone; what its own room holds is unspecified, as
+ *            with press_hip_depress_batch.
+ *   cal      2 * nreads floats; a device pointer when device resident
+ * A bad method id or a NULL argument is PRESS_HIP_EARG before any device call; nreads == 0 is PRESS_HIP_OK.
+ * device_resident != 0: the call only enqueues.  == 0: host pointers, synchronous; streams, layout and cal are staged,
+ * the floats are decoded into a device arena and the decoded ranges come back as press_hip_depress_batch's samples do.
+ * press_hip_depress_pa_fused(method) == 1 (the four svb methods): the decode kernel converts the samples it holds in
+ * registers and writes the floats itself - no int16 copy of the samples exists anywhere.  == 0: the method's decoder
+ * runs unchanged into library scratch and a second kernel converts [0, roundup8(out_n[r])) of every decoded read.
+ * press_hip_depress_pa_workspace_bytes: the device scratch the device-resident call keeps for a batch of this shape,
+ * exact as press_hip_workspace_bytes is and never below it: for a fused method the same, for the others plus the
+ * samples (total_samples * 2 + 64 bytes) and the converter's tile table.  0 for a method id out of range.
+ */
+int press_hip_pa_cal(const double *dor, uint32_t nreads, float *cal); /* dor: nreads x {digitisation, offset, range} */
+int press_hip_depress_pa_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+			       uint32_t nreads, float *pa, const uint64_t *off, const uint32_t *n,
+			       uint64_t total_samples, const float *cal, uint32_t *out_n, int device_resident);
+int press_hip_depress_pa_fused(int method); /* 1: the decode kernel writes the floats itself; 0: via int16 scratch, bad ids */
+uint64_t press_hip_depress_pa_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads);
+
+/*
  * Recode nreads streams of src_method into streams of dst_method: what press_hip_depress_batch(src_method) followed by
  * press_hip_press_batch(dst_method) give on the same buffers - out, out_len, out_n and sig byte for byte - in one call,
  * for every pair of methods.
@@ -532,6 +571,11 @@ int press_hip_blow5_methods(const press_hip_blow5 *f, int *record_method, int *s
  * max_reads x PRESS_HIP_BLOW5_ID_LEN chars.  *got = reads delivered; 0 at the end of the file. */
 int press_hip_blow5_next(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena, uint64_t arena_cap,
 			 uint64_t *sig_off, uint64_t *sig_len, uint32_t *n_samples, char *read_ids, uint32_t *got);
+/* ... and the calibration of every read: dor[3k ..] = digitisation, offset, range as record k stores them
+ * (three doubles; press_hip_pa_cal turns them into press_hip_depress_pa_batch's cal) */
+int press_hip_blow5_next_pa(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena, uint64_t arena_cap,
+			    uint64_t *sig_off, uint64_t *sig_len, uint32_t *n_samples, char *read_ids, double *dor,
+			    uint32_t *got);
 const char *press_hip_blow5_last_error(void);
 /* Whole inflated records (for a transcoder): sig_pos / sig_len locate the signal field in
  * record k, the u64 length field sits 8 bytes in front of it. */
