@@ -748,6 +748,170 @@ extern "C" int press_hip_depress_pa_batch(int method, const uint8_t *in, const u
 	return fetch_elems(pa, g.pa_out.p, sizeof(float), off, n, out_n, nreads, order, s);
 }
 
+// Normalised floats: press_hip_depress_pa_batch's general path for every method, with a calibration the device derives
+// between the decoder and the converter (launch_depress_norm).
+extern "C" int press_hip_depress_norm_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+					    uint32_t nreads, float *out, const uint64_t *off, const uint32_t *n,
+					    uint64_t total_samples, int32_t *stats, uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	if (!method_ok(method)) // (before any device call)
+		return set_error(PRESS_HIP_EARG, "method %d is not available in the batch API", method);
+	if (nreads && (!in || !in_off || !in_len || !out || !off || !n || !out_n))
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	int rc = ctx_init();
+	if (rc || (rc = check_method(method)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_norm_plan(method, total_samples, nreads, !device_resident);
+	if ((rc = plan.reserve()))
+		return rc;
+	DecodeArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	a.sig = (int16_t *) plan.ptr(&Ctx::rsig);
+
+	if (device_resident) {
+		if ((uintptr_t) out & 15)
+			return set_error(PRESS_HIP_EARG, "out must be 16-byte aligned");
+		a.in = in;
+		a.in_off = in_off;
+		a.in_len = in_len;
+		a.off = off;
+		a.nsamp = n;
+		a.out_n = out_n;
+		return launch_depress_norm(plan, a, out, stats, s);
+	}
+
+	std::vector<uint32_t> order;
+	if ((rc = check_disjoint(off, n, nreads, "the sample room", order)))
+		return rc;
+	if ((rc = stage_layout(off, n, nreads, total_samples, s, false)))
+		return rc;
+	std::vector<uint64_t> doff;
+	if ((rc = stage_streams(in, in_off, in_len, nreads, g.arena, g.arena_off, doff, s)))
+		return rc;
+	a.in = (const uint8_t *) g.arena.p;
+	a.in_off = (const uint64_t *) g.arena_off.p;
+	a.in_len = (const uint64_t *) g.lens2.p;
+	a.off = (const uint64_t *) g.off.p;
+	a.nsamp = (const uint32_t *) g.nsamp.p;
+	a.out_n = (uint32_t *) g.outn.p;
+	if ((rc = launch_depress_norm(plan, a, (float *) g.pa_out.p, (int32_t *) g.st_stats.p, s)))
+		return rc;
+	if (stats)
+		HIPCHK(hipMemcpyAsync(stats, g.st_stats.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	return fetch_elems(out, g.pa_out.p, sizeof(float), off, n, out_n, nreads, order, s);
+}
+
+// the scratch of a stats call that decodes nothing, and its DecodeArgs (sig / off / nsamp / out_n are the caller's)
+static int stats_scratch(uint32_t nreads, uint64_t total_samples, DecodeArgs &a)
+{
+	a = DecodeArgs{};
+	a.nreads = nreads;
+	a.max_chunks = (uint32_t) (total_samples / CHUNK + nreads + 1); // (as ScratchPlan::max_chunks)
+	if (g.pa_tile.reserve((size_t) a.max_chunks * sizeof(uint2)) || g.pa_ctl.reserve(64) || g.st_rows.reserve(stat_rows_bytes(nreads)) ||
+	    g.st_read.reserve(stat_state_bytes(nreads)))
+		return PRESS_HIP_EHIP;
+	return 0;
+}
+
+static void stats_launch(const DecodeArgs &a, int32_t *stats, hipEvent_t *ev, hipStream_t s)
+{
+	launch_pa_tiles(a, (uint2 *) g.pa_tile.p, (uint32_t *) g.pa_ctl.p, s);
+	launch_signal_stats(a, (const uint2 *) g.pa_tile.p, (const uint32_t *) g.pa_ctl.p, g.st_read.p, (uint32_t *) g.st_rows.p, stats,
+			    nullptr, ev, s);
+}
+
+extern "C" int press_hip_signal_stats(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				      uint64_t total_samples, int32_t *stats, int device_resident)
+{
+	API_LOCK;
+	if (nreads && (!sig || !off || !n || !stats)) // (before any device call)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	int rc = ctx_init();
+	if (rc)
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	DecodeArgs a;
+	if ((rc = stats_scratch(nreads, total_samples, a)))
+		return rc;
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		a.sig = const_cast<int16_t *>(sig);
+		a.off = off;
+		a.nsamp = n;
+		a.out_n = const_cast<uint32_t *>(n); // (every sample of a read counts; nothing is written)
+		stats_launch(a, stats, nullptr, s);
+		return launch_status();
+	}
+
+	// host pointers: stage, run, copy the stats back, synchronise
+	std::vector<uint32_t> order;
+	if ((rc = check_disjoint(off, n, nreads, "the sample range", order)))
+		return rc;
+	if ((rc = stage_layout(off, n, nreads, total_samples, s)))
+		return rc;
+	if (g.st_stats.reserve((size_t) nreads * 8))
+		return PRESS_HIP_EHIP;
+	if ((rc = h2d(g.sig.p, sig, total_samples * 2, s)))
+		return rc;
+	a.sig = (int16_t *) g.sig.p;
+	a.off = (const uint64_t *) g.off.p;
+	a.nsamp = (const uint32_t *) g.nsamp.p;
+	a.out_n = (uint32_t *) g.nsamp.p;
+	stats_launch(a, (int32_t *) g.st_stats.p, nullptr, s);
+	if ((rc = launch_status()))
+		return rc;
+	HIPCHK(hipMemcpyAsync(stats, g.st_stats.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
+// Profiling aid: the device-resident press_hip_signal_stats with an event behind every kernel; synchronous.
+// ms[0 .. 8): count / pick / count / pick of the median, then of the MAD.
+extern "C" int press_hip_signal_stats_timed(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+					    uint64_t total_samples, int32_t *stats, float *ms)
+{
+	API_LOCK;
+	if (!sig || !off || !n || !stats || !ms || !nreads)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	int rc = ctx_init();
+	if (rc)
+		return rc;
+	if ((uintptr_t) sig & 15)
+		return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+	hipStream_t s = g.stream();
+	DecodeArgs a;
+	if ((rc = stats_scratch(nreads, total_samples, a)))
+		return rc;
+	a.sig = const_cast<int16_t *>(sig);
+	a.off = off;
+	a.nsamp = n;
+	a.out_n = const_cast<uint32_t *>(n);
+	hipEvent_t ev[9] = {};
+	for (int i = 0; i < 9 && !rc; i++)
+		if (hipEventCreate(&ev[i]) != hipSuccess)
+			rc = set_error(PRESS_HIP_EHIP, "hipEventCreate failed");
+	if (!rc) {
+		stats_launch(a, stats, ev, s);
+		if (!(rc = launch_status()) && hipStreamSynchronize(s) != hipSuccess)
+			rc = set_error(PRESS_HIP_EHIP, "hipStreamSynchronize failed");
+		for (int i = 0; i < 8 && !rc; i++)
+			if (hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]) != hipSuccess)
+				rc = set_error(PRESS_HIP_EHIP, "hipEventElapsedTime failed");
+	}
+	for (int i = 0; i < 9; i++)
+		if (ev[i])
+			(void) hipEventDestroy(ev[i]);
+	return rc;
+}
+
 
 static int stage_streams(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t nreads, DevBuf &arena,
 			 DevBuf &offs, std::vector<uint64_t> &doff, hipStream_t s)

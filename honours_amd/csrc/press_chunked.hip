@@ -2691,14 +2691,27 @@ __global__ __launch_bounds__(256) void k_pa_convert(const int16_t *sig, const ui
 	}
 }
 
-void launch_pa_convert(const DecodeArgs &a, float *pa, const float *cal, uint2 *tiles, uint32_t *ntiles, hipStream_t s)
+// the two halves of launch_pa_convert, for a caller that reads the tile table between them (press_stats.hip)
+void launch_pa_tiles(const DecodeArgs &a, uint2 *tiles, uint32_t *ntiles, hipStream_t s)
 {
 	if (!a.nreads || !a.max_chunks)
 		return;
 	(void) hipMemsetAsync(ntiles, 0, sizeof(uint32_t), s);
 	hipLaunchKernelGGL(k_pa_tiles, dim3((a.nreads + 255) / 256), dim3(256), 0, s, a.nsamp, a.nreads, tiles, ntiles, a.max_chunks);
+}
+
+void launch_pa_apply(const DecodeArgs &a, float *pa, const float *cal, const uint2 *tiles, const uint32_t *ntiles, hipStream_t s)
+{
+	if (!a.nreads || !a.max_chunks)
+		return;
 	hipLaunchKernelGGL(k_pa_convert, dim3(a.max_chunks), dim3(256), 0, s, (const int16_t *) a.sig, a.off, (const uint32_t *) a.out_n,
-			   cal, pa, (const uint2 *) tiles, (const uint32_t *) ntiles);
+			   cal, pa, tiles, ntiles);
+}
+
+void launch_pa_convert(const DecodeArgs &a, float *pa, const float *cal, uint2 *tiles, uint32_t *ntiles, hipStream_t s)
+{
+	launch_pa_tiles(a, tiles, ntiles, s);
+	launch_pa_apply(a, pa, cal, tiles, ntiles, s);
 }
 
 } // namespace ph

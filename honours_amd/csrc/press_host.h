@@ -67,6 +67,7 @@ struct Ctx {
 	DevBuf rsig, rn, rkeep, pchunks, pfirst, pctl; // recode: samples nobody asked for, the press half's counts, refused reads' slot heads, its chunk table
 	DevBuf pneed, pslot; // packed press: the reads' sizes, the slot table its writing kernels see (PackArgs)
 	DevBuf pa_tile, pa_ctl, pa_cal, pa_out; // picoamperes: the converter's tile table and its count; host path: the staged calibration, the float arena
+	DevBuf st_rows, st_read, st_cal, st_stats; // median / MAD: the reads' count rows, the pick state, the normaliser's two floats; host path: stats
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams
@@ -206,6 +207,10 @@ RecodePlan make_recode_packed_plan(int src, int dst, uint64_t total_samples, uin
 bool depress_pa_fused(int method);
 ScratchPlan make_pa_plan(int method, uint64_t total_samples, uint32_t nreads, bool host);
 
+// press_hip_depress_norm_batch: make_pa_plan of a method that is not fused, for every method, and what the median / MAD
+// selection keeps: the count rows, the pick state and the normaliser's floats; host pointers: and stats
+ScratchPlan make_norm_plan(int method, uint64_t total_samples, uint32_t nreads, bool host);
+
 // press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
 ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);
 
@@ -215,6 +220,8 @@ int launch_press(const ScratchPlan &p, const BatchArgs &a, hipStream_t s);
 int launch_depress(const ScratchPlan &p, const DecodeArgs &a, hipStream_t s);
 // p from make_pa_plan; a.sig: the samples' scratch of a method that is not fused (unused for a fused one)
 int launch_depress_pa(const ScratchPlan &p, const DecodeArgs &a, float *pa, const float *cal, hipStream_t s);
+// p from make_norm_plan; a.sig: the samples' scratch; stats may be NULL
+int launch_depress_norm(const ScratchPlan &p, const DecodeArgs &a, float *out, int32_t *stats, hipStream_t s);
 // phases: PACK_SIZE | PACK_WRITE (press_internal.h); a.out_off must be pk.slot
 int launch_press_packed(const ScratchPlan &p, const BatchArgs &a, const PackArgs &pk, int phases, hipStream_t s);
 

@@ -349,6 +349,15 @@ void launch_svb_decode_chunked(const DecodeArgs &a, bool key2bit, bool zd, hipSt
 // methods the converter of the samples their decoder left at a.sig (tiles: max_chunks entries, ntiles: one word)
 void launch_svb_decode_pa(const DecodeArgs &a, float *pa, const float *cal, bool key2bit, bool zd, bool slow5, hipStream_t s);
 void launch_pa_convert(const DecodeArgs &a, float *pa, const float *cal, uint2 *tiles, uint32_t *ntiles, hipStream_t s);
+// ... in two halves: the tile table of a.nsamp, then the converter over it
+void launch_pa_tiles(const DecodeArgs &a, uint2 *tiles, uint32_t *ntiles, hipStream_t s);
+void launch_pa_apply(const DecodeArgs &a, float *pa, const float *cal, const uint2 *tiles, const uint32_t *ntiles, hipStream_t s);
+// press_stats.hip: median and MAD of a.out_n[r] samples at a.sig + a.off[r] over launch_pa_tiles' table (eight launches);
+// stats: 2 int32 per read, cal: k_pa_convert's two floats per read, either may be NULL; ev: NULL or 9 events (profiling)
+uint64_t stat_rows_bytes(uint32_t nreads);
+uint64_t stat_state_bytes(uint32_t nreads);
+void launch_signal_stats(const DecodeArgs &a, const uint2 *tiles, const uint32_t *ntiles, void *state, uint32_t *rows,
+			 int32_t *stats, float *cal, hipEvent_t *ev, hipStream_t s);
 void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip

@@ -158,6 +158,18 @@ ScratchPlan make_pa_plan(int method, uint64_t total_samples, uint32_t nreads, bo
 	return p;
 }
 
+// Normalised floats: every method decodes into rsig (the median needs the whole read before the first float)
+ScratchPlan make_norm_plan(int method, uint64_t total_samples, uint32_t nreads, bool host)
+{
+	ScratchPlan p = make_plan(method, total_samples, nreads, true);
+	p.need(&Ctx::rsig, total_samples * 2 + 64).need(&Ctx::pa_tile, (size_t) p.max_chunks * sizeof(uint2)).need(&Ctx::pa_ctl, 64)
+		.need(&Ctx::st_rows, stat_rows_bytes(nreads)).need(&Ctx::st_read, stat_state_bytes(nreads))
+		.need(&Ctx::st_cal, (size_t) nreads * 8);
+	if (host)
+		p.need(&Ctx::st_stats, (size_t) nreads * 8).need(&Ctx::pa_out, total_samples * 4 + 64);
+	return p;
+}
+
 // Fused pairs: BLOW5's and the reference's svb-zd streams into any exception-split method.  (svb12 has no deltas; the zstd
 // kinds and the svb destinations take the general path.)
 bool recode_fused(int src, int dst)
@@ -315,6 +327,37 @@ extern "C" uint64_t press_hip_depress_pa_workspace_bytes(int method, uint64_t to
 	return b;
 }
 
+// ... and what the device-resident press_hip_depress_norm_batch adds
+extern "C" uint64_t press_hip_depress_norm_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads)
+{
+	API_LOCK;
+	if (!method_ok(method))
+		return 0;
+	ScratchPlan p = make_norm_plan(method, total_samples, nreads, false);
+	const ScratchPlan e = make_plan(method, total_samples, nreads, false);
+	for (int i = 0; i < e.nrows; i++)
+		p.need(e.rows[i].buf, e.rows[i].bytes);
+	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
+	for (int i = 0; i < p.nrows; i++)
+		b += p.rows[i].bytes;
+	return b;
+}
+
+// c0 = (float) -med, c1 = 1 / ((float) mad * 1.4826f) in single precision, the product rounded before the division
+// (volatile: whatever the compiler is told about contraction or excess precision); 1 for mad = 0
+extern "C" int press_hip_norm_cal(const int32_t *stats, uint32_t nreads, float *cal)
+{
+	if (nreads && (!stats || !cal))
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	for (uint32_t r = 0; r < nreads; r++) {
+		const int32_t med = stats[2 * (size_t) r], mad = stats[2 * (size_t) r + 1];
+		volatile float scale = (float) mad * 1.4826f;
+		cal[2 * (size_t) r] = (float) -(int64_t) med;
+		cal[2 * (size_t) r + 1] = mad > 0 ? 1.0f / scale : 1.0f;
+	}
+	return 0;
+}
+
 extern "C" int press_hip_depress_pa_fused(int method) { return depress_pa_fused(method) ? 1 : 0; }
 
 // cal[2r] = (float) offset, cal[2r + 1] = (float) range / (float) digitisation: the reference's casts and its
@@ -450,6 +493,20 @@ int ph::launch_depress_pa(const ScratchPlan &p, const DecodeArgs &a, float *pa, 
 	if (rc)
 		return rc;
 	launch_pa_convert(a, pa, cal, (uint2 *) p.ptr(&Ctx::pa_tile), (uint32_t *) p.ptr(&Ctx::pa_ctl), s);
+	return launch_status();
+}
+
+int ph::launch_depress_norm(const ScratchPlan &p, const DecodeArgs &a, float *out, int32_t *stats, hipStream_t s)
+{
+	const int rc = launch_depress(p, a, s);
+	if (rc)
+		return rc;
+	uint2 *tiles = (uint2 *) p.ptr(&Ctx::pa_tile);
+	uint32_t *ntiles = (uint32_t *) p.ptr(&Ctx::pa_ctl);
+	float *cal = (float *) p.ptr(&Ctx::st_cal);
+	launch_pa_tiles(a, tiles, ntiles, s);
+	launch_signal_stats(a, tiles, ntiles, p.ptr(&Ctx::st_read), (uint32_t *) p.ptr(&Ctx::st_rows), stats, cal, nullptr, s);
+	launch_pa_apply(a, out, cal, tiles, ntiles, s);
 	return launch_status();
 }
 

@@ -75,6 +75,8 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_press_batch", "press_hip_depress_batch", "press_hip_workspace_bytes",
      "press_hip_pa_cal", "press_hip_depress_pa_batch", "press_hip_depress_pa_fused",
      "press_hip_depress_pa_workspace_bytes", "press_hip_blow5_next_pa",
+     "press_hip_signal_stats", "press_hip_norm_cal", "press_hip_depress_norm_batch",
+     "press_hip_depress_norm_workspace_bytes", "press_hip_signal_stats_timed",
      "press_hip_recode_batch", "press_hip_recode_workspace_bytes", "press_hip_recode_fused",
      "press_hip_recode_sizes", "press_hip_recode_packed", "press_hip_recode_packed_workspace_bytes",
      "press_hip_press_sizes", "press_hip_press_packed", "press_hip_packed_exact", "press_hip_packed_workspace_bytes",
@@ -131,6 +133,20 @@ def load_library(path=LIB_PATH):
         _lib.press_hip_depress_pa_fused.argtypes = [ctypes.c_int]
         _lib.press_hip_depress_pa_workspace_bytes.restype = ctypes.c_uint64
         _lib.press_hip_depress_pa_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
+        _lib.press_hip_signal_stats.restype = ctypes.c_int
+        _lib.press_hip_signal_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_signal_stats_timed.restype = ctypes.c_int
+        _lib.press_hip_signal_stats_timed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        _lib.press_hip_norm_cal.restype = ctypes.c_int
+        _lib.press_hip_norm_cal.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+        _lib.press_hip_depress_norm_batch.restype = ctypes.c_int
+        _lib.press_hip_depress_norm_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_depress_norm_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_depress_norm_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
         _lib.press_hip_recode_batch.restype = ctypes.c_int
         _lib.press_hip_recode_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
@@ -449,6 +465,42 @@ def depress_pa_fused(method):
     return bool(load_library().press_hip_depress_pa_fused(_mid(method)))
 
 
+def signal_stats(sig, off, n, stats):
+    """Enqueue the per-read median and MAD of a batch of samples (CUDA tensors: sig int16, off int64 read starts in
+    multiples of 8 samples, n int32 sample counts, stats int32 of 2 * nreads): stats[2r] = the n[r] // 2-th smallest
+    sample, stats[2r + 1] = the n[r] // 2-th smallest |sample - median| (press_hip_signal_stats)."""
+    nreads = off.numel()
+    if stats.numel() < 2 * nreads or stats.element_size() != 4 or not stats.is_contiguous():
+        raise PressError("stats must be a contiguous 32-bit tensor of 2 * nreads entries")
+    if load_library().press_hip_signal_stats(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
+                                             stats.data_ptr(), 1):
+        raise PressError(last_error())
+
+
+def norm_cal(stats):
+    """(nreads, 2) int32 {median, MAD} -> (nreads, 2) float32 {-median, 1 / (MAD * 1.4826f)} ({., 1} for MAD = 0): the
+    calibration with which depress_pa_batch writes the normalised signal (press_hip_norm_cal: host arithmetic, no GPU)"""
+    stats = np.ascontiguousarray(stats, dtype=np.int32).reshape(-1, 2)
+    cal = np.zeros((stats.shape[0], 2), dtype=np.float32)
+    if load_library().press_hip_norm_cal(stats.ctypes.data, stats.shape[0], cal.ctypes.data):
+        raise PressError(last_error())
+    return cal
+
+
+def depress_norm_batch(method, comp, in_off, in_len, out, off, n, out_n, stats=None):
+    """Enqueue the decompression of a batch straight to the normalised signal (CUDA tensors as in depress_pa_batch, out
+    float32 in the place of pa): out[off[r] + i] = (s[i] - median) / (1.4826 * MAD) in signal_stats' and norm_cal's
+    arithmetic over the read's decoded samples.  stats: int32 of 2 * nreads that receives {median, MAD}, or None."""
+    nreads = off.numel()
+    if stats is not None and (stats.numel() < 2 * nreads or stats.element_size() != 4 or not stats.is_contiguous()):
+        raise PressError("stats must be a contiguous 32-bit tensor of 2 * nreads entries")
+    rc = load_library().press_hip_depress_norm_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
+                                                     nreads, out.data_ptr(), off.data_ptr(), n.data_ptr(), out.numel(),
+                                                     None if stats is None else stats.data_ptr(), out_n.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
 def recode_batch(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, out_n, sig=None, total_samples=None):
     """Enqueue the recoding of a batch of `src` streams into `dst` streams (CUDA tensors as in depress_batch and
     press_batch).  sig: the int16 tensor that also receives the decoded samples, or None - they then stay in library
@@ -691,6 +743,43 @@ def depress_pa_batch_host(method, streams, ns, cals):
         raise PressError(last_error())
     return [None if int(k) == 0xFFFFFFFF else pa[int(o): int(o) + int(k)].copy()
             for o, k in zip(off, out_n)]
+
+
+def depress_norm_batch_host(method, streams, ns):
+    """Batch decode to the normalised signal with host buffers: streams = list of bytes, ns = sample counts /
+    capacities -> (list of float32 arrays (None: the read failed), (nreads, 2) int32 {median, MAD})."""
+    lib = load_library()
+    nreads = len(streams)
+    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+    in_off = np.zeros(nreads, dtype=np.uint64)
+    if nreads > 1:
+        in_off[1:] = np.cumsum(in_len)[:-1]
+    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
+    ns = np.asarray(ns, dtype=np.uint32)
+    off, total = _layout(ns)
+    out = np.zeros(total + 64, dtype=np.float32)
+    out_n = np.zeros(nreads, dtype=np.uint32)
+    stats = np.zeros((nreads, 2), dtype=np.int32)
+    rc = lib.press_hip_depress_norm_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
+                                          nreads, out.ctypes.data, off.ctypes.data, ns.ctypes.data, total,
+                                          stats.ctypes.data, out_n.ctypes.data, 0)
+    if rc:
+        raise PressError(last_error())
+    return ([None if int(k) == 0xFFFFFFFF else out[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)], stats)
+
+
+def signal_stats_host(reads):
+    """{median, MAD} of a list of int16 arrays (host buffers, synchronous) -> (nreads, 2) int32"""
+    lib = load_library()
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    stats = np.zeros((len(reads), 2), dtype=np.int32)
+    if lib.press_hip_signal_stats(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, stats.ctypes.data, 0):
+        raise PressError(last_error())
+    return stats
 
 
 class HostBatch:

@@ -421,6 +421,61 @@ int press_hip_depress_pa_fused(int method); /* 1: the decode kernel writes the f
 uint64_t press_hip_depress_pa_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads);
 
 /*
+ * Robust normalisation on the device: per-read median and median absolute deviation, and decoding straight to
+ * (x - median) / (1.4826 * MAD).
+ *
+ * Both statistics are the reference's (sigtk stat.h:56-73, mediani16 / medianf: ks_ksmall(n, copy, n / 2) - the k-th
+ * smallest value, never an average; events.c:171-194, madf).  For a read of c samples s[0 .. c), k = c / 2:
+ *     med  = the k-th smallest (0-based) of s                        an int16 value, as int32
+ *     d[i] = |(int32) s[i] - med|   in 0 .. 65535
+ *     mad  = the k-th smallest of d                                  an integer, as int32, NOT yet scaled by 1.4826
+ *     c0   = (float) (-(int32) med)
+ *     c1   = 1.0f / ((float) mad * 1.4826f) for mad > 0, 1.0f for mad == 0     (the product rounded to single
+ *            precision, then a correctly rounded division)
+ *     norm[i] = ((float) s[i] + c0) * c1                             the add and the multiply rounded separately
+ * All of it is exact and the same from run to run: order statistics of 16-bit integers, found by a radix select whose
+ * only sums are integer counts, and press_hip_depress_pa_batch's arithmetic with a calibration the device derives.  The
+ * calibration of the read cancels in norm[], so none is asked for.  c == 0 and a refused read: med = mad = 0,
+ * {c0, c1} = {0.0f, 1.0f}.
+ *
+ * press_hip_signal_stats: stats[2r] = med, stats[2r + 1] = mad of the n[r] samples at sig + off[r].
+ *   sig / off / n / total_samples / device_resident   as press_hip_press_batch: layout, alignment (off[] multiples of 8
+ *            samples, a device sig 16-byte aligned: PRESS_HIP_EARG), non-overlap (host pointers: checked)
+ *   stats    2 * nreads int32; a device pointer when device resident
+ *   device_resident != 0: the call only enqueues.  == 0: samples and layout are staged, the call is synchronous.
+ * press_hip_norm_cal: host arithmetic, no GPU: cal[2r], cal[2r + 1] = c0, c1 of stats[2r], stats[2r + 1] -
+ *   what press_hip_depress_pa_batch takes as cal to reproduce norm[] from the same samples.
+ * press_hip_depress_norm_batch: press_hip_depress_pa_batch without cal.  Every read is decoded, med / mad are taken over
+ *   its out_n[r] decoded samples, and norm[] is written into `out`.
+ *   in/in_off/in_len/off/n/total_samples/out_n   as in press_hip_depress_batch, with its checks, its room rules, its
+ *            empty-read rules, PRESS_HIP_ENOTABLE and the zstd kinds' host wait
+ *   out      off[] counts floats.  Device resident it must be 16-byte aligned (PRESS_HIP_EARG); floats are written to
+ *            [off[r], off[r] + roundup8(n[r])) at most, what lies at or beyond out_n[r] in that range is unspecified,
+ *            nothing outside the rooms is written and a refused read (out_n[r] = UINT32_MAX) gets no float at all.
+ *            Host buffers receive exactly out_n[r] floats per read.
+ *   stats    2 * nreads int32 as above ({0, 0} for an empty or refused read), or NULL
+ * A bad method id or a NULL argument (stats of this call excepted) is PRESS_HIP_EARG before any device call;
+ * nreads == 0 is PRESS_HIP_OK.
+ * There is no fused variant: the median needs the whole read before the first float can be written, so all 19 methods
+ * decode unchanged into library scratch (as press_hip_depress_pa_fused(method) == 0 does), eight small launches select
+ * med and mad from it, and press_hip_depress_pa_batch's converter writes the floats.
+ * press_hip_depress_norm_workspace_bytes: the device scratch the device-resident call keeps for a batch of this shape,
+ * exact as press_hip_depress_pa_workspace_bytes is and never below it for a method that is not fused: plus a row of
+ * counters (1 KiB), 16 bytes of state and two floats per read.  0 for a method id out of range.
+ * press_hip_signal_stats_timed: a profiling aid - the device-resident press_hip_signal_stats, synchronous, with a HIP
+ * event behind each of its eight kernels: ms[0 .. 8) = count, pick, count, pick of the median, then of the MAD.
+ */
+int press_hip_signal_stats(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			   uint64_t total_samples, int32_t *stats, int device_resident);
+int press_hip_norm_cal(const int32_t *stats, uint32_t nreads, float *cal);
+int press_hip_depress_norm_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+				 uint32_t nreads, float *out, const uint64_t *off, const uint32_t *n,
+				 uint64_t total_samples, int32_t *stats, uint32_t *out_n, int device_resident);
+uint64_t press_hip_depress_norm_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads);
+int press_hip_signal_stats_timed(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				 uint64_t total_samples, int32_t *stats, float *ms);
+
+/*
  * Recode nreads streams of src_method into streams of dst_method: what press_hip_depress_batch(src_method) followed by
  * press_hip_press_batch(dst_method) give on the same buffers - out, out_len, out_n and sig byte for byte - in one call,
  * for every pair of methods.
