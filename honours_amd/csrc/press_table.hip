@@ -174,6 +174,10 @@ int ph::upload_table(const uint32_t len[256], const uint64_t bits[256])
 		h.minlen = len[s] < h.minlen ? len[s] : h.minlen;
 		h.maxlen = len[s] > h.maxlen ? len[s] : h.maxlen;
 	}
+	// Batches already enqueued on the current stream read the table that is on the device now: wait for them before it is
+	// overwritten (the copy below is null-stream work, which a non-blocking stream is not ordered against).  The copy is
+	// complete when hipMemcpy returns, so whatever is enqueued afterwards, on any stream, sees the new table.
+	HIPCHK(hipStreamSynchronize(g.stream()));
 	if (g.huff.reserve(sizeof(HuffDev)))
 		return PRESS_HIP_EHIP;
 	HIPCHK(hipMemcpy(g.huff.p, &h, sizeof h, hipMemcpyHostToDevice));

@@ -214,7 +214,8 @@ const char *press_hip_last_error(void);
 int press_hip_set_device(int device);
 /* stream (hipStream_t, as void*) the batch calls enqueue on; NULL is HIP's default
  * (null) stream.  Until this is called the library uses a private non-blocking stream;
- * press_hip_reset_stream() returns to it. */
+ * press_hip_reset_stream() returns to it.  Scratch and the Huffman table belong to the context, not to a
+ * stream: a caller who switches streams while batches are in flight orders the two streams itself. */
 int press_hip_set_stream(void *stream);
 int press_hip_reset_stream(void);
 void *press_hip_get_stream(void);
@@ -222,7 +223,12 @@ void *press_hip_get_stream(void);
 int press_hip_synchronize(void);
 
 /* static Huffman table for the batch API: file in the format of press/NA12878_zd.huffman
- * (huffman.c:549; it may list fewer than 256 symbols) */
+ * (huffman.c:549; it may list fewer than 256 symbols).
+ * A table change is ordered against the current stream: press_hip_load_table_file, press_hip_set_table and the
+ * table a shuffman_* drop-in symbol brings along wait on the host for everything enqueued on the current stream
+ * before the device table is overwritten, and the new table is in place when they return.  Batches enqueued
+ * before the call use the old table, batches enqueued after it the new one.  Setting the table that is already
+ * in force (same lengths and bits) is recognised on the host and neither waits nor copies. */
 int press_hip_load_table_file(const char *path);
 /* or 256 {length, code bits} pairs; bit k of bits[s] is the k-th emitted bit.
  * len[s] == 0: symbol s has no code - a read fails (press: PRESS_HIP_FAILED / return 1) only if that
