@@ -873,6 +873,161 @@ extern "C" int press_hip_signal_stats(const int16_t *sig, const uint64_t *off, c
 	return 0;
 }
 
+// Quantiles of a batch: press_hip_signal_stats' layout and staging, nq ranks in four launches (press_quant.hip)
+extern "C" int press_hip_signal_quantiles(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+					  uint64_t total_samples, const uint32_t *rank_num, const uint32_t *rank_den, uint32_t nq,
+					  int32_t *q, int device_resident)
+{
+	API_LOCK;
+	if (nq < 1 || nq > QMAX) // (before any device call)
+		return set_error(PRESS_HIP_EARG, "nq = %u: 1 .. %u quantiles", nq, QMAX);
+	if (!rank_num || !rank_den || (nreads && (!sig || !off || !n || !q)))
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	for (uint32_t i = 0; i < nq; i++)
+		if (rank_den[i] == 0 || rank_num[i] > rank_den[i])
+			return set_error(PRESS_HIP_EARG, "rank %u: %u / %u is not in [0, 1]", i, rank_num[i], rank_den[i]);
+	int rc = ctx_init();
+	if (rc)
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	DecodeArgs a;
+	if ((rc = stats_scratch(nreads, total_samples, a)))
+		return rc;
+	if (g.st_rows.reserve(quant_rows_bytes(nreads, nq)) || g.st_read.reserve(quant_state_bytes(nreads)))
+		return PRESS_HIP_EHIP;
+	if (device_resident) {
+		if ((uintptr_t) sig & 15)
+			return set_error(PRESS_HIP_EARG, "sig must be 16-byte aligned");
+		a.sig = const_cast<int16_t *>(sig);
+		a.off = off;
+		a.nsamp = n;
+		a.out_n = const_cast<uint32_t *>(n); // (every sample of a read counts; nothing is written)
+		launch_pa_tiles(a, (uint2 *) g.pa_tile.p, (uint32_t *) g.pa_ctl.p, s);
+		launch_signal_quantiles(a, (const uint2 *) g.pa_tile.p, (const uint32_t *) g.pa_ctl.p, g.st_read.p, (uint32_t *) g.st_rows.p,
+					rank_num, rank_den, nq, q, nullptr, nullptr, s);
+		return launch_status();
+	}
+
+	// host pointers: stage, run, copy the quantiles back, synchronise
+	std::vector<uint32_t> order;
+	if ((rc = check_disjoint(off, n, nreads, "the sample range", order)))
+		return rc;
+	if ((rc = stage_layout(off, n, nreads, total_samples, s)))
+		return rc;
+	if (g.st_stats.reserve((size_t) nreads * nq * 4))
+		return PRESS_HIP_EHIP;
+	if ((rc = h2d(g.sig.p, sig, total_samples * 2, s)))
+		return rc;
+	a.sig = (int16_t *) g.sig.p;
+	a.off = (const uint64_t *) g.off.p;
+	a.nsamp = (const uint32_t *) g.nsamp.p;
+	a.out_n = (uint32_t *) g.nsamp.p;
+	launch_pa_tiles(a, (uint2 *) g.pa_tile.p, (uint32_t *) g.pa_ctl.p, s);
+	launch_signal_quantiles(a, (const uint2 *) g.pa_tile.p, (const uint32_t *) g.pa_ctl.p, g.st_read.p, (uint32_t *) g.st_rows.p, rank_num,
+				rank_den, nq, (int32_t *) g.st_stats.p, nullptr, nullptr, s);
+	if ((rc = launch_status()))
+		return rc;
+	HIPCHK(hipMemcpyAsync(q, g.st_stats.p, (size_t) nreads * nq * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
+// Chunk rows: press_hip_depress_norm_batch's decode and staging; the calibration is the rule's two quantiles or, without a
+// rule, median and MAD; the writer of press_rows.hip takes the place of the float converter (launch_depress_chunks).
+extern "C" int press_hip_depress_chunks_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+					      uint32_t nreads, void *rows, uint64_t nrows_cap, int dtype, uint32_t T, uint32_t overlap,
+					      const uint64_t *row_first, const uint64_t *off, const uint32_t *n, uint64_t total_samples,
+					      const press_hip_scale_rule *rule, int32_t *q, uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	if (!method_ok(method)) // (before any device call)
+		return set_error(PRESS_HIP_EARG, "method %d is not available in the batch API", method);
+	if (dtype != PRESS_HIP_F32 && dtype != PRESS_HIP_F16 && dtype != PRESS_HIP_BF16)
+		return set_error(PRESS_HIP_EARG, "dtype %d: PRESS_HIP_F32, PRESS_HIP_F16 or PRESS_HIP_BF16", dtype);
+	if (T == 0 || T % 8 || overlap >= T)
+		return set_error(PRESS_HIP_EARG, "T must be a positive multiple of 8 and overlap below T");
+	if (rule && !scale_rule_ok(rule))
+		return set_error(PRESS_HIP_EARG, "the scale rule is not valid (ranks num <= den, den > 0; finite floats; scale_min > 0)");
+	if (nreads && (!in || !in_off || !in_len || !row_first || !off || !n || !out_n || (!rows && nrows_cap)))
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	int rc = ctx_init();
+	if (rc || (rc = check_method(method)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const size_t es = dtype == PRESS_HIP_F32 ? 4 : 2;
+	ChunkArgs c = { rows, nrows_cap, dtype, T, overlap, row_first, total_samples, rule, q };
+	DecodeArgs a;
+
+	if (device_resident) {
+		if ((uintptr_t) rows & 15)
+			return set_error(PRESS_HIP_EARG, "rows must be 16-byte aligned");
+		const ScratchPlan plan = make_chunks_plan(method, total_samples, nreads, false, 0);
+		if ((rc = plan.reserve()))
+			return rc;
+		plan.bind(a);
+		a.nreads = nreads;
+		a.sig = (int16_t *) plan.ptr(&Ctx::rsig);
+		a.in = in;
+		a.in_off = in_off;
+		a.in_len = in_len;
+		a.off = off;
+		a.nsamp = n;
+		a.out_n = out_n;
+		return launch_depress_chunks(plan, a, c, s);
+	}
+
+	// host pointers: row_first must be the plan of n[] (it decides what is written where); stage, run, one transfer of
+	// the written prefix of the rows, q and out_n, synchronise
+	const uint32_t S = T - overlap;
+	uint64_t at = 0;
+	for (uint32_t r = 0; r < nreads; r++) {
+		if (row_first[r] != at)
+			return set_error(PRESS_HIP_EARG, "row_first[%u] is not press_hip_chunk_plan's", r);
+		at += chunk_rows_of(n[r], T, S);
+	}
+	if (row_first[nreads] != at)
+		return set_error(PRESS_HIP_EARG, "row_first[%u] is not press_hip_chunk_plan's", nreads);
+	const uint64_t written = at < nrows_cap ? at : nrows_cap;
+	const ScratchPlan plan = make_chunks_plan(method, total_samples, nreads, true, written * T * es);
+	if ((rc = plan.reserve()))
+		return rc;
+	plan.bind(a);
+	a.nreads = nreads;
+	a.sig = (int16_t *) plan.ptr(&Ctx::rsig);
+	std::vector<uint32_t> order;
+	if ((rc = check_disjoint(off, n, nreads, "the sample room", order)))
+		return rc;
+	if ((rc = stage_layout(off, n, nreads, total_samples, s, false)))
+		return rc;
+	std::vector<uint64_t> doff;
+	if ((rc = stage_streams(in, in_off, in_len, nreads, g.arena, g.arena_off, doff, s)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(g.ch_first.p, row_first, ((size_t) nreads + 1) * 8, hipMemcpyHostToDevice, s));
+	a.in = (const uint8_t *) g.arena.p;
+	a.in_off = (const uint64_t *) g.arena_off.p;
+	a.in_len = (const uint64_t *) g.lens2.p;
+	a.off = (const uint64_t *) g.off.p;
+	a.nsamp = (const uint32_t *) g.nsamp.p;
+	a.out_n = (uint32_t *) g.outn.p;
+	c.rows = g.ch_rows.p;
+	c.nrows_cap = written;
+	c.row_first = (const uint64_t *) g.ch_first.p;
+	c.q = (int32_t *) g.st_stats.p;
+	if ((rc = launch_depress_chunks(plan, a, c, s)))
+		return rc;
+	if (q)
+		HIPCHK(hipMemcpyAsync(q, g.st_stats.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	if (written)
+		HIPCHK(hipMemcpyAsync(rows, g.ch_rows.p, written * T * es, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
 // Profiling aid: the device-resident press_hip_signal_stats with an event behind every kernel; synchronous.
 // ms[0 .. 8): count / pick / count / pick of the median, then of the MAD.
 extern "C" int press_hip_signal_stats_timed(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,

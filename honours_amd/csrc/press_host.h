@@ -68,6 +68,7 @@ struct Ctx {
 	DevBuf pneed, pslot; // packed press: the reads' sizes, the slot table its writing kernels see (PackArgs)
 	DevBuf pa_tile, pa_ctl, pa_cal, pa_out; // picoamperes: the converter's tile table and its count; host path: the staged calibration, the float arena
 	DevBuf st_rows, st_read, st_cal, st_stats; // median / MAD: the reads' count rows, the pick state, the normaliser's two floats; host path: stats
+	DevBuf ch_rows, ch_first; // chunk rows, host path: the row arena, the staged row_first
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams
@@ -211,6 +212,11 @@ ScratchPlan make_pa_plan(int method, uint64_t total_samples, uint32_t nreads, bo
 // selection keeps: the count rows, the pick state and the normaliser's floats; host pointers: and stats
 ScratchPlan make_norm_plan(int method, uint64_t total_samples, uint32_t nreads, bool host);
 
+// press_hip_depress_chunks_batch: make_norm_plan's rows, the count rows and the pick state at the larger of what the
+// median / MAD and the two quantiles keep; host pointers: the staged row_first and the row arena (rows_bytes) in the place
+// of the float arena
+ScratchPlan make_chunks_plan(int method, uint64_t total_samples, uint32_t nreads, bool host, uint64_t rows_bytes);
+
 // press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
 ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);
 
@@ -222,6 +228,20 @@ int launch_depress(const ScratchPlan &p, const DecodeArgs &a, hipStream_t s);
 int launch_depress_pa(const ScratchPlan &p, const DecodeArgs &a, float *pa, const float *cal, hipStream_t s);
 // p from make_norm_plan; a.sig: the samples' scratch; stats may be NULL
 int launch_depress_norm(const ScratchPlan &p, const DecodeArgs &a, float *out, int32_t *stats, hipStream_t s);
+// p from make_chunks_plan; a.sig: the samples' scratch.  What the caller has checked: dtype, T, overlap, the rule.
+struct ChunkArgs {
+	void *rows;
+	uint64_t nrows_cap;
+	int dtype;
+	uint32_t T, overlap;
+	const uint64_t *row_first;
+	uint64_t total_samples;
+	const press_hip_scale_rule *rule; // host; NULL: median / MAD
+	int32_t *q;                       // 2 per read, or NULL
+};
+int launch_depress_chunks(const ScratchPlan &p, const DecodeArgs &a, const ChunkArgs &c, hipStream_t s);
+bool scale_rule_ok(const press_hip_scale_rule *rule); // ranks and floats as include/press_hip.h asks
+uint64_t chunk_rows_of(uint32_t c, uint32_t T, uint32_t S); // rows of a read of c samples in press_hip_chunk_plan, S = T - overlap
 // phases: PACK_SIZE | PACK_WRITE (press_internal.h); a.out_off must be pk.slot
 int launch_press_packed(const ScratchPlan &p, const BatchArgs &a, const PackArgs &pk, int phases, hipStream_t s);
 

@@ -358,6 +358,23 @@ uint64_t stat_rows_bytes(uint32_t nreads);
 uint64_t stat_state_bytes(uint32_t nreads);
 void launch_signal_stats(const DecodeArgs &a, const uint2 *tiles, const uint32_t *ntiles, void *state, uint32_t *rows,
 			 int32_t *stats, float *cal, hipEvent_t *ev, hipStream_t s);
+// press_quant.hip: nq (1 .. QMAX) quantiles of a.out_n[r] samples at a.sig + a.off[r] over launch_pa_tiles' table (four
+// launches whatever nq is); q: nq int32 per read, may be NULL; cal (nq == 2, else ignored): NULL, or the two floats per
+// read that `rule` makes of {q[0], q[1]} (press_hip_scale_cal)
+constexpr uint32_t QMAX = 4;
+struct ScaleRule { // the floats of press_hip_scale_rule
+	float shift_mul, shift_min, scale_mul, scale_min;
+};
+uint64_t quant_rows_bytes(uint32_t nreads, uint32_t nq);
+uint64_t quant_state_bytes(uint32_t nreads);
+void launch_signal_quantiles(const DecodeArgs &a, const uint2 *tiles, const uint32_t *ntiles, void *state, uint32_t *rows,
+			     const uint32_t *num, const uint32_t *den, uint32_t nq, int32_t *q, float *cal, const ScaleRule *rule,
+			     hipStream_t s);
+// press_rows.hip: the planned rows below nrows_cap, [*, T] of dtype, from the samples at a.sig + a.off[r] (a.nsamp: the
+// rooms the plan was made of, a.out_n: the decoded counts) and two floats per read
+enum { PRESS_ROWS_F32 = 0, PRESS_ROWS_F16 = 1, PRESS_ROWS_BF16 = 2 }; // PRESS_HIP_F32 / F16 / BF16
+void launch_chunk_rows(const DecodeArgs &a, const float *cal, const uint64_t *row_first, void *rows, uint64_t nrows_cap, int dtype,
+		       uint32_t T, uint32_t overlap, uint64_t total_samples, hipStream_t s);
 void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip

@@ -1,6 +1,7 @@
 // press_methods.hip - everything that interprets a row of the method table (press_host.h): the reference's X_bound,
 // the scratch plan of a batch and its dispatch to the kernel launchers of press_*.hip.
 
+#include <cmath>
 #include <vector>
 
 #include "press_host.h"
@@ -167,6 +168,16 @@ ScratchPlan make_norm_plan(int method, uint64_t total_samples, uint32_t nreads, 
 		.need(&Ctx::st_cal, (size_t) nreads * 8);
 	if (host)
 		p.need(&Ctx::st_stats, (size_t) nreads * 8).need(&Ctx::pa_out, total_samples * 4 + 64);
+	return p;
+}
+
+// Chunk rows: the normalised call's plan; one set of count rows and state serves either calibration
+ScratchPlan make_chunks_plan(int method, uint64_t total_samples, uint32_t nreads, bool host, uint64_t rows_bytes)
+{
+	ScratchPlan p = make_norm_plan(method, total_samples, nreads, false);
+	p.need(&Ctx::st_rows, quant_rows_bytes(nreads, 2)).need(&Ctx::st_read, quant_state_bytes(nreads));
+	if (host)
+		p.need(&Ctx::st_stats, (size_t) nreads * 8).need(&Ctx::ch_first, ((size_t) nreads + 1) * 8).need(&Ctx::ch_rows, rows_bytes + 64);
 	return p;
 }
 
@@ -343,6 +354,82 @@ extern "C" uint64_t press_hip_depress_norm_workspace_bytes(int method, uint64_t 
 	return b;
 }
 
+// ... and what the device-resident press_hip_depress_chunks_batch keeps: the rows are the caller's, so T and overlap
+// only have to be valid
+extern "C" uint64_t press_hip_depress_chunks_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads, uint32_t T,
+							     uint32_t overlap)
+{
+	API_LOCK;
+	if (!method_ok(method) || T == 0 || T % 8 || overlap >= T)
+		return 0;
+	ScratchPlan p = make_chunks_plan(method, total_samples, nreads, false, 0);
+	const ScratchPlan e = make_plan(method, total_samples, nreads, false);
+	for (int i = 0; i < e.nrows; i++)
+		p.need(e.rows[i].buf, e.rows[i].bytes);
+	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
+	for (int i = 0; i < p.nrows; i++)
+		b += p.rows[i].bytes;
+	return b;
+}
+
+static bool rank_ok(uint32_t num, uint32_t den) { return den > 0 && num <= den; }
+
+bool ph::scale_rule_ok(const press_hip_scale_rule *rule)
+{
+	return rank_ok(rule->lo_num, rule->lo_den) && rank_ok(rule->hi_num, rule->hi_den) && std::isfinite(rule->shift_mul) &&
+	       std::isfinite(rule->shift_min) && std::isfinite(rule->scale_mul) && std::isfinite(rule->scale_min) && rule->scale_min > 0.0f;
+}
+
+// shift = max(shift_min, shift_mul * (float) (q_lo + q_hi)), scale = max(scale_min, scale_mul * (float) (q_hi - q_lo)) in
+// single precision, every product rounded before it is compared (volatile: whatever the compiler is told about contraction
+// or excess precision); cal = { -shift, 1 / scale }
+extern "C" int press_hip_scale_cal(const int32_t *q, uint32_t nreads, const press_hip_scale_rule *rule, float *cal)
+{
+	if (!rule || (nreads && (!q || !cal)))
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	if (!scale_rule_ok(rule))
+		return set_error(PRESS_HIP_EARG, "the scale rule is not valid (ranks num <= den, den > 0; finite floats; scale_min > 0)");
+	for (uint32_t r = 0; r < nreads; r++) {
+		const int32_t lo = q[2 * (size_t) r], hi = q[2 * (size_t) r + 1];
+		volatile float sh = rule->shift_mul * (float) ((int64_t) lo + hi);
+		volatile float sc = rule->scale_mul * (float) ((int64_t) hi - lo);
+		const float shift = fmaxf(rule->shift_min, sh), scale = fmaxf(rule->scale_min, sc);
+		cal[2 * (size_t) r] = -shift;
+		cal[2 * (size_t) r + 1] = 1.0f / scale;
+	}
+	return 0;
+}
+
+// rows of a read of c samples: 0, 1, or 1 + ceil((c - T) / S)
+uint64_t ph::chunk_rows_of(uint32_t c, uint32_t T, uint32_t S)
+{
+	return c == 0 ? 0 : c <= T ? 1 : 1 + ((uint64_t) (c - T) + S - 1) / S;
+}
+
+extern "C" int press_hip_chunk_plan(const uint32_t *n, uint32_t nreads, uint32_t T, uint32_t overlap, uint64_t *row_first,
+				    uint32_t *row_read, uint32_t *row_start)
+{
+	if (T == 0 || T % 8 || overlap >= T)
+		return set_error(PRESS_HIP_EARG, "T must be a positive multiple of 8 and overlap below T");
+	if (!row_first || (nreads && !n))
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	const uint32_t S = T - overlap;
+	uint64_t at = 0;
+	for (uint32_t r = 0; r < nreads; r++) {
+		row_first[r] = at;
+		const uint64_t k = chunk_rows_of(n[r], T, S);
+		for (uint64_t j = 0; j < k; j++) {
+			if (row_read)
+				row_read[at + j] = r;
+			if (row_start)
+				row_start[at + j] = j + 1 == k && n[r] > T ? n[r] - T : (uint32_t) (j * S);
+		}
+		at += k;
+	}
+	row_first[nreads] = at;
+	return 0;
+}
+
 // c0 = (float) -med, c1 = 1 / ((float) mad * 1.4826f) in single precision, the product rounded before the division
 // (volatile: whatever the compiler is told about contraction or excess precision); 1 for mad = 0
 extern "C" int press_hip_norm_cal(const int32_t *stats, uint32_t nreads, float *cal)
@@ -507,6 +594,28 @@ int ph::launch_depress_norm(const ScratchPlan &p, const DecodeArgs &a, float *ou
 	launch_pa_tiles(a, tiles, ntiles, s);
 	launch_signal_stats(a, tiles, ntiles, p.ptr(&Ctx::st_read), (uint32_t *) p.ptr(&Ctx::st_rows), stats, cal, nullptr, s);
 	launch_pa_apply(a, out, cal, tiles, ntiles, s);
+	return launch_status();
+}
+
+// The decode, the tile table, the calibration (a rule: two quantiles in four launches; none: median and MAD in eight),
+// the row writer.
+int ph::launch_depress_chunks(const ScratchPlan &p, const DecodeArgs &a, const ChunkArgs &c, hipStream_t s)
+{
+	const int rc = launch_depress(p, a, s);
+	if (rc)
+		return rc;
+	uint2 *tiles = (uint2 *) p.ptr(&Ctx::pa_tile);
+	uint32_t *ntiles = (uint32_t *) p.ptr(&Ctx::pa_ctl);
+	float *cal = (float *) p.ptr(&Ctx::st_cal);
+	launch_pa_tiles(a, tiles, ntiles, s);
+	if (c.rule) {
+		const uint32_t num[2] = { c.rule->lo_num, c.rule->hi_num }, den[2] = { c.rule->lo_den, c.rule->hi_den };
+		const ScaleRule ru = { c.rule->shift_mul, c.rule->shift_min, c.rule->scale_mul, c.rule->scale_min };
+		launch_signal_quantiles(a, tiles, ntiles, p.ptr(&Ctx::st_read), (uint32_t *) p.ptr(&Ctx::st_rows), num, den, 2, c.q, cal, &ru, s);
+	} else {
+		launch_signal_stats(a, tiles, ntiles, p.ptr(&Ctx::st_read), (uint32_t *) p.ptr(&Ctx::st_rows), c.q, cal, nullptr, s);
+	}
+	launch_chunk_rows(a, cal, c.row_first, c.rows, c.nrows_cap, c.dtype, c.T, c.overlap, c.total_samples, s);
 	return launch_status();
 }
 

@@ -77,6 +77,8 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_depress_pa_workspace_bytes", "press_hip_blow5_next_pa",
      "press_hip_signal_stats", "press_hip_norm_cal", "press_hip_depress_norm_batch",
      "press_hip_depress_norm_workspace_bytes", "press_hip_signal_stats_timed",
+     "press_hip_signal_quantiles", "press_hip_scale_cal", "press_hip_chunk_plan", "press_hip_depress_chunks_batch",
+     "press_hip_depress_chunks_workspace_bytes",
      "press_hip_recode_batch", "press_hip_recode_workspace_bytes", "press_hip_recode_fused",
      "press_hip_recode_sizes", "press_hip_recode_packed", "press_hip_recode_packed_workspace_bytes",
      "press_hip_press_sizes", "press_hip_press_packed", "press_hip_packed_exact", "press_hip_packed_workspace_bytes",
@@ -147,6 +149,24 @@ def load_library(path=LIB_PATH):
                                                       ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         _lib.press_hip_depress_norm_workspace_bytes.restype = ctypes.c_uint64
         _lib.press_hip_depress_norm_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
+        _lib.press_hip_signal_quantiles.restype = ctypes.c_int
+        _lib.press_hip_signal_quantiles.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                    ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                    ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_scale_cal.restype = ctypes.c_int
+        _lib.press_hip_scale_cal.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        _lib.press_hip_chunk_plan.restype = ctypes.c_int
+        _lib.press_hip_chunk_plan.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        _lib.press_hip_depress_chunks_batch.restype = ctypes.c_int
+        _lib.press_hip_depress_chunks_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_depress_chunks_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_depress_chunks_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
+                                                                  ctypes.c_uint32, ctypes.c_uint32]
         _lib.press_hip_recode_batch.restype = ctypes.c_int
         _lib.press_hip_recode_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
@@ -501,6 +521,106 @@ def depress_norm_batch(method, comp, in_off, in_len, out, off, n, out_n, stats=N
         raise PressError(last_error())
 
 
+class ScaleRule(ctypes.Structure):
+    """press_hip_scale_rule: the ranks num / den of q_lo and q_hi, and
+    shift = max(shift_min, shift_mul * (q_lo + q_hi)), scale = max(scale_min, scale_mul * (q_hi - q_lo))"""
+    _fields_ = [("lo_num", ctypes.c_uint32), ("lo_den", ctypes.c_uint32), ("hi_num", ctypes.c_uint32), ("hi_den", ctypes.c_uint32),
+                ("shift_mul", ctypes.c_float), ("shift_min", ctypes.c_float), ("scale_mul", ctypes.c_float),
+                ("scale_min", ctypes.c_float)]
+
+
+CHUNK_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}  # PRESS_HIP_F32 / F16 / BF16
+
+
+def _ranks(ranks):
+    ranks = [(int(a), int(b)) for a, b in ranks]
+    return (np.array([a for a, _ in ranks], dtype=np.uint32), np.array([b for _, b in ranks], dtype=np.uint32))
+
+
+def _rule_ptr(rule):
+    if rule is not None and not isinstance(rule, ScaleRule):
+        raise PressError("rule must be a press.ScaleRule or None")
+    return None if rule is None else ctypes.addressof(rule)
+
+
+def signal_quantiles(sig, off, n, ranks, q):
+    """Enqueue per-read order statistics of a batch of samples (CUDA tensors as in signal_stats; ranks: 1 .. 4 pairs
+    (num, den), host values; q int32 of len(ranks) * nreads): q[nq * r + i] = the min(n - 1, n * num_i // den_i)-th
+    smallest sample of read r (press_hip_signal_quantiles)."""
+    nreads = off.numel()
+    num, den = _ranks(ranks)
+    if q.numel() < num.size * nreads or q.element_size() != 4 or not q.is_contiguous():
+        raise PressError("q must be a contiguous 32-bit tensor of len(ranks) * nreads entries")
+    if load_library().press_hip_signal_quantiles(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
+                                                 num.ctypes.data, den.ctypes.data, num.size, q.data_ptr(), 1):
+        raise PressError(last_error())
+
+
+def signal_quantiles_host(reads, ranks):
+    """quantiles of a list of int16 arrays (host buffers, synchronous) -> (nreads, len(ranks)) int32"""
+    lib = load_library()
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    num, den = _ranks(ranks)
+    q = np.zeros((len(reads), num.size), dtype=np.int32)
+    if lib.press_hip_signal_quantiles(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, num.ctypes.data,
+                                      den.ctypes.data, num.size, q.ctypes.data, 0):
+        raise PressError(last_error())
+    return q
+
+
+def scale_cal(q, rule):
+    """(nreads, 2) int32 {q_lo, q_hi} and a ScaleRule -> (nreads, 2) float32 {-shift, 1 / scale}: the calibration with
+    which depress_pa_batch writes the scaled signal (press_hip_scale_cal: host arithmetic, no GPU)"""
+    q = np.ascontiguousarray(q, dtype=np.int32).reshape(-1, 2)
+    cal = np.zeros((q.shape[0], 2), dtype=np.float32)
+    if load_library().press_hip_scale_cal(q.ctypes.data, q.shape[0], _rule_ptr(rule), cal.ctypes.data):
+        raise PressError(last_error())
+    return cal
+
+
+def chunk_plan(ns, T, overlap):
+    """the rows of reads of ns samples cut into rows of T that overlap by `overlap` (press_hip_chunk_plan: host
+    arithmetic, no GPU) -> (row_first uint64[nreads + 1], row_read uint32[rows], row_start uint32[rows])"""
+    lib = load_library()
+    ns = np.ascontiguousarray(ns, dtype=np.uint32)
+    row_first = np.zeros(ns.size + 1, dtype=np.uint64)
+    if lib.press_hip_chunk_plan(ns.ctypes.data, ns.size, int(T), int(overlap), row_first.ctypes.data, None, None):
+        raise PressError(last_error())
+    row_read = np.zeros(int(row_first[-1]), dtype=np.uint32)
+    row_start = np.zeros(int(row_first[-1]), dtype=np.uint32)
+    if lib.press_hip_chunk_plan(ns.ctypes.data, ns.size, int(T), int(overlap), row_first.ctypes.data, row_read.ctypes.data,
+                                row_start.ctypes.data):
+        raise PressError(last_error())
+    return row_first, row_read, row_start
+
+
+def depress_chunks_batch(method, comp, in_off, in_len, rows, row_first, off, n, total_samples, out_n, overlap, rule=None, q=None):
+    """Enqueue the decompression of a batch straight to scaled chunk rows (CUDA tensors as in depress_norm_batch; rows
+    [nrows_cap, T] float32, float16 or bfloat16, contiguous; row_first int64 of nreads + 1: chunk_plan over n; off / n /
+    total_samples lay out the library's sample scratch).  rule: a ScaleRule (quantile scaling) or None (median / MAD);
+    q: int32 of 2 * nreads that receives {q_lo, q_hi} or {median, MAD}, or None."""
+    import torch
+    nreads = off.numel()
+    dt = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}.get(rows.dtype)
+    if dt is None or rows.dim() != 2 or not rows.is_contiguous():
+        raise PressError("rows must be a contiguous [nrows, T] tensor of float32, float16 or bfloat16")
+    if q is not None and (q.numel() < 2 * nreads or q.element_size() != 4 or not q.is_contiguous()):
+        raise PressError("q must be a contiguous 32-bit tensor of 2 * nreads entries")
+    if row_first.numel() < nreads + 1 or row_first.element_size() != 8:
+        raise PressError("row_first must be a 64-bit tensor of nreads + 1 entries")
+    rc = load_library().press_hip_depress_chunks_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
+                                                       nreads, rows.data_ptr(), rows.shape[0], dt, rows.shape[1], int(overlap),
+                                                       row_first.data_ptr(), off.data_ptr(), n.data_ptr(), int(total_samples),
+                                                       _rule_ptr(rule), None if q is None else q.data_ptr(),
+                                                       out_n.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
 def recode_batch(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, out_n, sig=None, total_samples=None):
     """Enqueue the recoding of a batch of `src` streams into `dst` streams (CUDA tensors as in depress_batch and
     press_batch).  sig: the int16 tensor that also receives the decoded samples, or None - they then stay in library
@@ -766,6 +886,36 @@ def depress_norm_batch_host(method, streams, ns):
     if rc:
         raise PressError(last_error())
     return ([None if int(k) == 0xFFFFFFFF else out[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)], stats)
+
+
+def depress_chunks_batch_host(method, streams, ns, T, overlap, dtype="float16", rule=None):
+    """Batch decode to scaled chunk rows with host buffers: streams = list of bytes, ns = sample counts / capacities
+    (what Blow5Reader.next_batch gives) -> (rows, q, row_read, row_start, out_n): rows a numpy [nrows, T] array of
+    float32 / float16, or of uint16 bit patterns for "bfloat16"; q (nreads, 2) int32 {q_lo, q_hi} (rule: a ScaleRule) or
+    {median, MAD} (None); row_read / row_start: per row the read and the sample it starts at (chunk_plan); out_n uint32
+    per read, the decoded count or 0xFFFFFFFF for a read that failed - its rows are zeros and its q {0, 0}."""
+    lib = load_library()
+    nreads = len(streams)
+    if dtype not in CHUNK_DTYPES:
+        raise PressError("dtype: one of %s" % ", ".join(CHUNK_DTYPES))
+    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+    in_off = np.zeros(nreads, dtype=np.uint64)
+    if nreads > 1:
+        in_off[1:] = np.cumsum(in_len)[:-1]
+    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
+    ns = np.asarray(ns, dtype=np.uint32)
+    off, total = _layout(ns)
+    row_first, row_read, row_start = chunk_plan(ns, T, overlap)
+    rows = np.zeros((int(row_first[-1]), int(T)), dtype={"float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}[dtype])
+    out_n = np.zeros(nreads, dtype=np.uint32)
+    q = np.zeros((nreads, 2), dtype=np.int32)
+    rc = lib.press_hip_depress_chunks_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads,
+                                            rows.ctypes.data, rows.shape[0], CHUNK_DTYPES[dtype], int(T), int(overlap),
+                                            row_first.ctypes.data, off.ctypes.data, ns.ctypes.data, total, _rule_ptr(rule),
+                                            q.ctypes.data, out_n.ctypes.data, 0)
+    if rc:
+        raise PressError(last_error())
+    return rows, q, row_read, row_start, out_n
 
 
 def signal_stats_host(reads):

@@ -482,6 +482,86 @@ int press_hip_signal_stats_timed(const int16_t *sig, const uint64_t *off, const 
 				 uint64_t total_samples, int32_t *stats, float *ms);
 
 /*
+ * Quantile scaling and chunk rows: compressed reads straight to the [rows, T] half-precision tensor a basecaller takes.
+ *
+ * press_hip_signal_quantiles: up to 4 order statistics per read.
+ *     q[nq * r + i] = the k-th smallest (0-based) of the n[r] samples at sig + off[r],
+ *                     k = min(c - 1, floor(c * rank_num[i] / rank_den[i])), c = n[r]; 0 for c == 0
+ *   sig / off / n / total_samples / device_resident   as press_hip_signal_stats, with its checks
+ *   rank_num, rank_den   HOST arrays of nq entries in both modes (parameters, not data).  nq is 1 .. 4, den > 0 and
+ *            num <= den, else PRESS_HIP_EARG before any device call.  Ranks may repeat and need not be ordered; 1 / 2 is
+ *            press_hip_signal_stats' median, 1 / 1 the maximum.
+ *   q        nq * nreads int32; a device pointer when device resident.  Nothing beyond it is written.
+ *   Four launches whatever nq is (the radix select of the median, its high digit counted once for all ranks); every sum
+ *   is one of integers, so the result is the same on every run.
+ *
+ * press_hip_scale_cal: host arithmetic, no GPU.  A rule names two ranks and four floats; q holds {q_lo, q_hi} per read:
+ *     shift = fmaxf(shift_min, shift_mul * (float) (q_lo + q_hi))      (the integer sum is exact in float)
+ *     scale = fmaxf(scale_min, scale_mul * (float) (q_hi - q_lo))
+ *     cal[2r] = -shift        cal[2r + 1] = 1.0f / scale               (correctly rounded)
+ *     y[i] = ((float) s[i] + cal[2r]) * cal[2r + 1]
+ *   Every operation is rounded once, to nearest, in IEEE single precision, and never fused: y is what
+ *   press_hip_depress_pa_batch writes with this cal.  A rule is valid when both ranks have den > 0 and num <= den, all four
+ *   floats are finite and scale_min > 0; anything else, or a NULL rule, is PRESS_HIP_EARG.  The library has no default
+ *   rule.
+ *
+ * press_hip_chunk_plan: host arithmetic, no GPU: the rows of a batch.  T is a positive multiple of 8 and overlap < T, else
+ *   PRESS_HIP_EARG.  With S = T - overlap a read of c = n[r] samples takes 0 rows for c == 0, 1 row starting at sample 0
+ *   for c <= T, otherwise 1 + ceil((c - T) / S) rows: row j starts at j * S, except the last, which starts at c - T (so no
+ *   row of such a read runs past its end, and the last two may overlap by more than `overlap`).
+ *   row_first   nreads + 1 entries: the exclusive sum of the row counts; row_first[nreads] is the number of rows
+ *   row_read, row_start   per row the read and the start, for stitching a model's output; either may be NULL (call once
+ *            with both NULL to size them by row_first[nreads])
+ *
+ * press_hip_depress_chunks_batch: decode, calibrate, write rows.
+ *   in/in_off/in_len/off/n/total_samples/out_n   as in press_hip_depress_norm_batch: all 19 methods, the same checks, room
+ *            and empty-read rules, PRESS_HIP_ENOTABLE and the zstd kinds' host wait.  off[] lays out the library's own
+ *            sample scratch; the caller never sees samples.
+ *   rule     a HOST pointer in both modes, read before the call returns.  Given (and valid, else PRESS_HIP_EARG):
+ *            {q_lo, q_hi} are taken over the out_n[r] decoded samples (four launches) and y is press_hip_scale_cal's.
+ *            NULL: the calibration is press_hip_depress_norm_batch's, median and MAD.
+ *   q        2 * nreads int32 that receive {q_lo, q_hi}, or {med, mad} without a rule; {0, 0} for an empty or refused
+ *            read; may be NULL.  A device pointer when device resident.
+ *   dtype    PRESS_HIP_F32, PRESS_HIP_F16 or PRESS_HIP_BF16; T, overlap as in press_hip_chunk_plan.  A bad value is
+ *            PRESS_HIP_EARG before any device call.
+ *   row_first   press_hip_chunk_plan's over the same n[] (the ROOMS, so the layout is known on the host without a
+ *            synchronisation); a device pointer when device resident, where it is a precondition; host pointers: checked
+ *            (PRESS_HIP_EARG)
+ *   rows     row-major [*, T] of dtype; device resident it must be 16-byte aligned (PRESS_HIP_EARG).  Row
+ *            row_first[r] + j holds at column t round_to_dtype(y[start_j + t]); a column whose sample index is at or
+ *            beyond out_n[r] is +0, and so is every column of every row of a refused read.  round_to_dtype is one
+ *            further rounding of the float32 y to nearest even: overflow goes to infinity, float16 subnormals are
+ *            kept; bfloat16 is returned as its 16-bit pattern, a NaN (0 * inf: only with a scale_min so small that
+ *            1 / scale overflows) stays a quiet NaN.
+ *   nrows_cap   rows the arena has room for.  Never written: rows at or beyond nrows_cap, rows at or beyond
+ *            row_first[nreads], any byte outside rows[0 .. min(nrows_cap, row_first[nreads]) * T).  The layout does not
+ *            depend on the cap.
+ * nreads == 0 is PRESS_HIP_OK.  device_resident != 0: the call only enqueues.  == 0: host pointers, synchronous; it
+ * stages as press_hip_depress_norm_batch does and the written prefix of rows comes back in one transfer, with q and out_n.
+ * press_hip_depress_chunks_workspace_bytes: the device scratch the device-resident call keeps for a batch of this shape,
+ * exact as press_hip_depress_norm_workspace_bytes is and never below it: the count rows are two per read.  0 for a method
+ * id out of range or a bad T / overlap.
+ */
+typedef struct press_hip_scale_rule {
+	uint32_t lo_num, lo_den, hi_num, hi_den; /* ranks of q_lo and q_hi */
+	float shift_mul, shift_min, scale_mul, scale_min;
+} press_hip_scale_rule;
+enum { PRESS_HIP_F32 = 0, PRESS_HIP_F16 = 1, PRESS_HIP_BF16 = 2 };
+int press_hip_signal_quantiles(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			       uint64_t total_samples, const uint32_t *rank_num, const uint32_t *rank_den, uint32_t nq,
+			       int32_t *q, int device_resident);
+int press_hip_scale_cal(const int32_t *q /* 2 * nreads: q_lo, q_hi */, uint32_t nreads, const press_hip_scale_rule *rule,
+			float *cal /* 2 * nreads */);
+int press_hip_chunk_plan(const uint32_t *n, uint32_t nreads, uint32_t T, uint32_t overlap, uint64_t *row_first /* nreads + 1 */,
+			 uint32_t *row_read, uint32_t *row_start /* may be NULL */);
+int press_hip_depress_chunks_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+				   uint32_t nreads, void *rows, uint64_t nrows_cap, int dtype, uint32_t T, uint32_t overlap,
+				   const uint64_t *row_first, const uint64_t *off, const uint32_t *n, uint64_t total_samples,
+				   const press_hip_scale_rule *rule, int32_t *q, uint32_t *out_n, int device_resident);
+uint64_t press_hip_depress_chunks_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads, uint32_t T,
+						  uint32_t overlap);
+
+/*
  * Recode nreads streams of src_method into streams of dst_method: what press_hip_depress_batch(src_method) followed by
  * press_hip_press_batch(dst_method) give on the same buffers - out, out_len, out_n and sig byte for byte - in one call,
  * for every pair of methods.
