@@ -1935,15 +1935,22 @@ __global__ __launch_bounds__(CWG, HENC_WAVES) void k_huff_encode_chunked(BatchAr
 __global__ __launch_bounds__(256) void k_chunk_prep_meta(const uint64_t *off, const uint64_t *in_off,
 							 const ReadMeta *meta, uint32_t nreads, ChunkDesc *chunks,
 							 uint64_t *gran, ChunkCtl *ctl, uint32_t max_chunks,
-							 uint32_t *out_n, const uint32_t *hread)
+							 uint32_t *out_n, const uint32_t *hread, const uint32_t *ex_pos)
 {
 	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
 	uint32_t n = 0, nch = 0;
 	if (r < nreads && !meta[r].status) {
-		n = 1u + meta[r].nlow + meta[r].nex;
+		const uint32_t nex = meta[r].nex;
+		n = 1u + meta[r].nlow + nex;
 		nch = (n + CHUNK - 1) / CHUNK;
 		if (hread && (hread[2 * r + 1] & HUF_FUSED))
 			nch = 0; // k_huf_emit wrote this read's samples already
+		// a Huffman payload that ran out early delivered fewer values than k_ex_parse tested the positions against:
+		// the read stands only if its last exception is still reached, pos[nex - 1] + 1 <= nlow + nex.  (A fused read
+		// has passed this very test: k_huf_chain sets HUF_FUSED only under pos[nex - 1] < nlow + nex with the same
+		// nlow, so the two branches are complementary - change one and the other has to follow.)
+		else if (hread && nex && (uint64_t) ex_pos[off[r] + nex - 1] + 1 > (uint64_t) meta[r].nlow + nex)
+			n = nch = 0;
 	}
 	const uint32_t inc = wave_incl_scan32(nch);
 	uint32_t base = 0;
@@ -2595,7 +2602,7 @@ void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t
 	launch_ex_parse_huff(a, fmt, ent, s); // (k_ex_parse clears both control blocks)
 	hipLaunchKernelGGL(k_chunk_prep_meta, dim3((a.nreads + 255) / 256), dim3(256), 0, s, a.off, a.in_off,
 			   a.meta, a.nreads, a.chunks, a.gran, a.ctl, a.max_chunks, a.out_n,
-			   ent == 1 ? (const uint32_t *) a.hread : (const uint32_t *) nullptr);
+			   ent == 1 ? (const uint32_t *) a.hread : (const uint32_t *) nullptr, a.ex_pos);
 	hipLaunchKernelGGL(k_ex_ranks, dim3((a.max_chunks * 8 + 255) / 256), dim3(256), 0, s, a);
 	if (!huff)
 		ktime_begin(1, s);

@@ -782,7 +782,8 @@ __global__ __launch_bounds__(HT) void k_huf_chain(DecodeArgs a)
 	const uint64_t cumall = s_cum;
 	const uint32_t nlow = cumall < want ? (uint32_t) cumall : want; // what huffman_decode_memory delivered
 	// k_huf_emit writes the samples itself if the lists interleave into exactly 1 + nlow + nex samples:
-	// every exception sits among (or right behind) the delivered values
+	// every exception sits among (or right behind) the delivered values.  (k_chunk_prep_meta refuses a read that is not
+	// fused for the complement of this condition: the two lines go together.)
 	const bool fused = nlow >= 1 && (nex == 0 || pos[nex - 1] < nlow + nex);
 	const uint32_t zd0 = uniform(a.meta[r].zd0) & 0xFFFFu, q = uniform(a.meta[r].q);
 	// the tiles of a read are consecutive payload pieces (k_huff_tiles): unit u's payload starts u * UB bytes behind the

@@ -452,6 +452,7 @@ __global__ __launch_bounds__(64) void k_ex_parse(DecodeArgs a, int fmt, int huff
 	if (len < (uint64_t) hdr + 4 || cap == 0)
 		return;
 	uint32_t mq = 0, zd0;
+	uint32_t lim = cap; // the most samples the read may hold: the room, for ex-zd also the header's n
 	if (fmt == EXF_EXZD) {
 		// ex_zd.c:495-519: version 0, u64 n, q <= 5
 		if (in[0] != 0 || get32(in + 5) != 0 || in[9] > 5)
@@ -459,6 +460,7 @@ __global__ __launch_bounds__(64) void k_ex_parse(DecodeArgs a, int fmt, int huff
 		const uint32_t n = get32(in + 1);
 		if (n == 0 || n > cap)
 			return;
+		lim = n;
 		mq = in[9];
 		zd0 = get16(in + 10);
 	} else {
@@ -475,6 +477,7 @@ __global__ __launch_bounds__(64) void k_ex_parse(DecodeArgs a, int fmt, int huff
 	if ((uint64_t) nex >= cap)
 		return; // more exceptions than zd[1..] can hold
 	uint64_t seclen = 4;
+	uint32_t last = 0; // the last exception's position (vbe21: k_ex_parse_fill_vbe21 reads the list)
 	if (nex == 0) {
 	} else if (fmt == EXF_VBE21) {
 		if (left < 6ull * nex)
@@ -492,6 +495,7 @@ __global__ __launch_bounds__(64) void k_ex_parse(DecodeArgs a, int fmt, int huff
 		}
 		if (p0 >= cap - 1)
 			return; // positions lie inside zd[1..cap)
+		last = p0;
 		seclen += need;
 	} else {
 		if (left < 4)
@@ -532,6 +536,7 @@ __global__ __launch_bounds__(64) void k_ex_parse(DecodeArgs a, int fmt, int huff
 		}
 		if (__ballot(wrong || bp.bad || bv.bad))
 			return;
+		last = prev_last;
 		seclen += 8ull + lp + lv;
 	}
 	if (!l0)
@@ -552,14 +557,22 @@ __global__ __launch_bounds__(64) void k_ex_parse(DecodeArgs a, int fmt, int huff
 	} else {
 		nlow = len - hdr - seclen;
 	}
-	if (1ull + nlow + nex > cap)
+	if (1ull + nlow + nex > lim)
+		return;
+	// every exception is placed: with strictly increasing positions the last one decides - the nex - 1 exceptions and the
+	// one-byte values in front of it must reach its position, pos[nex - 1] + 1 <= nlow + nex.  (Static Huffman: nlow is the count the stream announces,
+	// k_chunk_prep_meta repeats the test with what the payload delivered.  Range coders: nlow is the room's rest, so a
+	// position inside zd[1..cap) is always reached - the range test above is the whole test for them.)
+	// (vbe21: k_ex_parse_fill_vbe21 reads the list and applies the same line to its last position)
+	if (huff != 3 && nex && fmt != EXF_VBE21 && (uint64_t) last + 1 > (uint64_t) nlow + nex)
 		return;
 	m->nlow = (uint32_t) nlow;
 	m->status = 0;
 }
 
 // vbe21: exception lists out of the section and their validation (strictly increasing positions
-// inside zd[1..cap)), one wave per read; a violation fails the read like k_ex_parse would.
+// inside zd[1..cap), the last one reached by the read's values), one wave per read; a violation
+// fails the read like k_ex_parse would.
 __global__ __launch_bounds__(64) void k_ex_parse_fill_vbe21(DecodeArgs a)
 {
 	const uint32_t r = blockIdx.x;
@@ -579,6 +592,8 @@ __global__ __launch_bounds__(64) void k_ex_parse_fill_vbe21(DecodeArgs a)
 		val[k] = get16(p + 4ull * nex + 2ull * k);
 		if (pk >= cap - 1 || (k && pk <= get32(p + 4ull * (k - 1))))
 			bad = true;
+		if (k == nex - 1 && (uint64_t) pk + 1 > (uint64_t) m->nlow + nex)
+			bad = true; // the last exception lies behind everything the read holds (k_ex_parse, the other formats)
 	}
 	if (__ballot(bad) && threadIdx.x == 0)
 		m->status = 1;

@@ -375,7 +375,23 @@ uint64_t press_hip_packed_workspace_bytes(int method, uint64_t total_samples, ui
  *                     Samples are written to [off[r], off[r] + roundup8(n[r])) at most
  *                     (device resident) or [off[r], off[r] + out_n[r]) (host buffers;
  *                     page-locked ones: see the note on press_hip_host_alloc)
- *   out_n             per read: samples decoded, or UINT32_MAX on a malformed stream
+ *   out_n             per read: samples decoded, or UINT32_MAX on a malformed stream.  A refused
+ *                     read writes nothing outside its own room and leaves the other reads
+ *                     alone.  For the twelve methods with an exception section (the four
+ *                     vb*e21_zd forms plain, shuffman_* and rc* / rccm*, and ex-zd) a stream
+ *                     is well formed iff: header, nex and the lists or
+ *                     the two length-prefixed blocks lie inside the stream, and each block
+ *                     holds nex values (bit-packed: 1 + ceil(nex * bits / 8) <= its length,
+ *                     bits <= 32; svb32 / svb16: the key bytes and the data bytes they
+ *                     announce); the positions are strictly increasing 32-bit numbers and
+ *                     every exception is placed, pos[nex - 1] - (nex - 1) <= nlow, nlow
+ *                     being the one-byte values the stream holds (plain), announces and
+ *                     delivers (Huffman) or n[r] - 1 - nex (range coders); and the read's
+ *                     1 + nlow + nex samples fit n[r] - for ex-zd also the header's n, which
+ *                     is 1 .. n[r] with version 0 and q <= 5.  Blocks longer than needed,
+ *                     widths and svb byte lengths larger than minimal are well formed;
+ *                     value + 256 is taken modulo 2^16.  A Huffman payload that ends early
+ *                     gives the shorter read if its exceptions are still placed.
  * An empty read: slow5_svb_zd takes exactly the 4-byte count 0 and refuses any other stream
  * for n = 0 (the reference needs the count, slow5_press.c:1086, 1098).  svb12, svb12_zd
  * and svb_zd give 0 samples for n = 0 whatever the stream, as the reference does (their

@@ -28,6 +28,7 @@ static void put_u32(uint8_t *p, uint32_t v) { int i; for (i = 0; i < 4; i++) p[i
 static void put_u64(uint8_t *p, uint64_t v) { int i; for (i = 0; i < 8; i++) p[i] = (uint8_t) (v >> (8 * i)); }
 static uint16_t get_u16(const uint8_t *p) { return (uint16_t) (p[0] | (p[1] << 8)); }
 static uint32_t get_u32(const uint8_t *p) { return (uint32_t) p[0] | ((uint32_t) p[1] << 8) | ((uint32_t) p[2] << 16) | ((uint32_t) p[3] << 24); }
+static uint32_t get_be32(const uint8_t *p) { return ((uint32_t) p[0] << 24) | ((uint32_t) p[1] << 16) | ((uint32_t) p[2] << 8) | p[3]; }
 static uint64_t get_u64(const uint8_t *p) { return (uint64_t) get_u32(p) | ((uint64_t) get_u32(p + 4) << 32); }
 
 /* trans.c:75 - zigzag of a 16-bit difference, result truncated to 16 bits */
@@ -350,11 +351,45 @@ static uint64_t exsec_write(enum exfmt f, const struct exlist *e, uint8_t *out)
 	return o;
 }
 
+/* a bit-packed block of nex values inside in[0..len): the width byte, a width of at most 32, all the bits */
+static int bitblock_ok(const uint8_t *in, uint64_t len, uint32_t nex)
+{
+	if (len < 1 || in[0] > 32)
+		return 0;
+	return 1 + ((uint64_t) nex * in[0] + 7) / 8 <= len;
+}
+
+/* an svb32 block of nex values inside in[0..len): the key bytes, and the data bytes the keys announce */
+static int svb32block_ok(const uint8_t *in, uint64_t len, uint32_t nex)
+{
+	uint64_t need = ((uint64_t) nex + 3) / 4;
+	uint32_t i;
+	if (need > len)
+		return 0;
+	for (i = 0; i < nex; i++)
+		need += ((in[i >> 2] >> (2 * (i & 3))) & 3u) + 1u;
+	return need <= len;
+}
+
+/* ... and an svb16 block (one key bit per value) */
+static int svb16block_ok(const uint8_t *in, uint64_t len, uint32_t nex)
+{
+	uint64_t need = svb16_keylen(nex);
+	uint32_t i;
+	if (need > len)
+		return 0;
+	for (i = 0; i < nex; i++)
+		need += ((in[i >> 3] >> (i & 7)) & 1u) + 1u;
+	return need <= len;
+}
+
 /*
- * Parse "u32 nex || section" at in[0..nin).  Fills e (raw values) and returns
- * the section length including the nex field, or 0 on a malformed stream.
+ * Parse "u32 nex || section" at in[0..nin) of a read with room for maxex exceptions
+ * (zd[1..] of the room).  Fills e (raw values) and returns the section length
+ * including the nex field, or 0 on a malformed stream.  Total over arbitrary bytes:
+ * nothing outside in[0..nin) is read (DESIGN.md 6.0.20 lists the rules).
  */
-static uint64_t exsec_read(enum exfmt f, const uint8_t *in, uint64_t nin, struct exlist *e)
+static uint64_t exsec_read(enum exfmt f, const uint8_t *in, uint64_t nin, uint64_t maxex, struct exlist *e)
 {
 	uint64_t o = 4;
 	uint32_t nex, i;
@@ -363,7 +398,7 @@ static uint64_t exsec_read(enum exfmt f, const uint8_t *in, uint64_t nin, struct
 	if (nin < 4)
 		return 0;
 	nex = get_u32(in);
-	if ((uint64_t) nex > nin) /* every exception costs at least a byte */
+	if ((uint64_t) nex > maxex) /* count against room (two width-0 blocks hold any count in 10 bytes) */
 		return 0;
 	e->pos = malloc(((size_t) nex + 1) * sizeof *e->pos);
 	e->val = malloc(((size_t) nex + 1) * sizeof *e->val);
@@ -387,10 +422,10 @@ static uint64_t exsec_read(enum exfmt f, const uint8_t *in, uint64_t nin, struct
 		e->pos[0] = get_u32(in + o);
 		o += 4;
 		if (f == EX_EXZD) {
-			e->val[0] = get_u32(in + o) + 256;
+			e->val[0] = (uint32_t) (uint16_t) (get_u32(in + o) + 256);
 			o += 4;
 		} else {
-			e->val[0] = (uint32_t) get_u16(in + o) + 256;
+			e->val[0] = (uint32_t) (uint16_t) (get_u16(in + o) + 256);
 			o += 2;
 		}
 		return o;
@@ -403,10 +438,15 @@ static uint64_t exsec_read(enum exfmt f, const uint8_t *in, uint64_t nin, struct
 		o += 4;
 		if (nin < o + len)
 			return 0;
-		if (f == EX_VBBE21)
+		if (f == EX_VBBE21) {
+			if (!bitblock_ok(in + o, len, nex))
+				return 0;
 			(void) po_uint_unpack(in + o, nex, 32, e->pos);
-		else
+		} else {
+			if (!svb32block_ok(in + o, len, nex))
+				return 0;
 			(void) po_svb32_decode(in + o, nex, e->pos);
+		}
 		o += len;
 		for (i = 1; i < nex; i++) /* trans.c:186 */
 			e->pos[i] += e->pos[i - 1] + 1;
@@ -420,11 +460,18 @@ static uint64_t exsec_read(enum exfmt f, const uint8_t *in, uint64_t nin, struct
 		if (nin < o + len)
 			return 0;
 		if (f == EX_EXZD) {
+			if (!svb32block_ok(in + o, len, nex))
+				return 0;
 			(void) po_svb32_decode(in + o, nex, e->val);
 			for (i = 0; i < nex; i++)
-				e->val[i] += 256;
+				e->val[i] = (uint32_t) (uint16_t) (e->val[i] + 256);
 		} else {
-			uint16_t *v = malloc((size_t) nex * sizeof *v);
+			uint16_t *v;
+			if (f == EX_VBSSE21 ? !svb16block_ok(in + o, len, nex) : !bitblock_ok(in + o, len, nex))
+				return 0;
+			v = malloc((size_t) nex * sizeof *v);
+			if (!v)
+				return 0;
 			if (f == EX_VBSSE21)
 				(void) po_svb16_decode(in + o, nex, 0, (int16_t *) v);
 			else
@@ -610,7 +657,7 @@ int po_shuff_decode(const uint8_t *in, uint64_t nin, uint8_t *out, uint32_t cap,
 	int32_t p = 0;
 	if (!g_tab.loaded || nin <= 4)
 		return 1;
-	want = ((uint32_t) in[0] << 24) | ((uint32_t) in[1] << 16) | ((uint32_t) in[2] << 8) | in[3];
+	want = get_be32(in);
 	for (i = 4; i < nin && got < want; i++) {
 		unsigned b;
 		for (b = 0; b < 8 && got < want; b++) {
@@ -1133,7 +1180,7 @@ static int vb_family_depress(int method, const uint8_t *in, uint64_t nbytes, uin
 	int ret = -1;
 	if (nbytes < 6 || n == 0)
 		return -1;
-	seclen = exsec_read(f, in + 2, nbytes - 2, &e);
+	seclen = exsec_read(f, in + 2, nbytes - 2, (uint64_t) n - 1, &e);
 	if (!seclen) {
 		exlist_free(&e);
 		return -1;
@@ -1152,6 +1199,11 @@ static int vb_family_depress(int method, const uint8_t *in, uint64_t nbytes, uin
 		lowp = low;
 	} else if (is_shuff(method)) {
 		uint32_t got = 0;
+		const uint64_t hl = nbytes - 2 - seclen;
+		/* the announced count is what a decoder sizes its buffer by: it has to fit the room with the exceptions.
+		 * (A stream of at most 4 bytes has no payload byte behind the count: po_shuff_decode refuses it below.) */
+		if (hl > 4 && 1 + (uint64_t) get_be32(in + 2 + seclen) + e.n > n)
+			goto done;
 		low = malloc((size_t) n + 1);
 		ret = po_shuff_decode(in + 2 + seclen, nbytes - 2 - seclen, low, n, &got);
 		if (ret)
@@ -1246,7 +1298,7 @@ static int exzd_depress(const uint8_t *in, uint64_t nbytes, uint32_t cap, int16_
 	q = in[9];
 	if (q > 5 || n64 == 0 || n64 > cap)
 		return -1;
-	seclen = exsec_read(EX_EXZD, in + 12, nbytes - 12, &e);
+	seclen = exsec_read(EX_EXZD, in + 12, nbytes - 12, n64 - 1, &e);
 	if (!seclen) {
 		exlist_free(&e);
 		return -1;
