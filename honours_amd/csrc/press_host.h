@@ -1,4 +1,4 @@
-// press_host.h - shared between the host-side units of libpress_hip.so (press_ctx, press_methods,
+// press_host.h - shared between the host-side units of libpress_hip.so (press_ctx, press_methods, press_staging,
 // press_batch, press_table, press_dropin .hip).  Host only: the kernel files include press_internal.h alone.
 #pragma once
 
@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <mutex>
+#include <vector>
 
 #include "../../include/press_hip.h"
 #include "press_internal.h"
@@ -94,7 +95,58 @@ extern std::recursive_mutex g_mu;
 // host thread, so it is selected again on every call (cheap), not only by the first caller.
 int ctx_init();
 #define API_ENTER API_LOCK; if (int rc_ = ph::ctx_init()) return rc_ // head of an entry point that needs the device
-void staging_release(); // page-locked staging buffers of the host-pointer calls (press_batch.hip)
+
+// ------------------------------------------------------------------ caller I/O and its staging (press_staging.hip)
+
+// The three kinds of caller I/O of a batch call.  An entry point launches on the caller's own pointers (device
+// resident) or on what a Staged call returns for them: the same structs, filled by different plumbing.
+struct SamplesIn {
+	const int16_t *sig;
+	const uint64_t *off;
+	const uint32_t *n;
+};
+struct StreamsIn { // streams in and the rooms of what they decode to
+	const uint8_t *in;
+	const uint64_t *in_off, *in_len, *off;
+	const uint32_t *n;
+	uint32_t *out_n;
+	int16_t *sig; // the samples' room; NULL where the call has none
+};
+struct SlotsOut {
+	uint8_t *out;
+	const uint64_t *out_off;
+	uint64_t *out_len;
+};
+
+// The layout checks of the host-pointer form (they read the caller's tables): EARG with the text in last_error
+int check_disjoint(const uint64_t *off, const uint32_t *n, uint32_t nreads, const char *what, std::vector<uint32_t> &order);
+int check_layout(const uint64_t *off, const uint32_t *n, uint32_t nreads, uint64_t total_samples); // off[] multiples of 8, reads inside total_samples
+int check_slots(const uint64_t *out_off, uint32_t nreads);                                        // out_off non-decreasing
+
+// One host-pointer call: what it moves to the device before the launch and back behind it, through the context's
+// staging DevBufs.  The tables its queued copies read are members: they live until the call's last synchronisation.
+struct Staged {
+	const uint32_t nreads;
+	const hipStream_t s;
+	Staged(uint32_t nreads_, hipStream_t s_) : nreads(nreads_), s(s_) {}
+	// off and n checked and copied, room for the samples (with_sig); what: the ranges must be disjoint, it names them
+	// in the refusal (NULL: reads may overlap)
+	int layout(const uint64_t *off, const uint32_t *n, uint64_t total_samples, const char *what, bool with_sig);
+	int samples(const SamplesIn &h, uint64_t total_samples, SamplesIn &d); // behind layout(): the samples -> d
+	int slots(const SlotsOut &h, SlotsOut &d);                              // an arena for the slots (checked: check_slots) -> d
+	// layout() of the rooms, then the streams dense in `arena`, their table in `offs` -> d; d.sig: g.sig with sig_room,
+	// else h.sig as it is
+	int streams(const StreamsIn &h, uint64_t total_samples, bool sig_room, DevBuf &arena, DevBuf &offs, StreamsIn &d);
+	// the tails; all but fetch_prefix end with the stream synchronised
+	int fetch_streams(const SlotsOut &h);                                      // out_len, the streams of slots()' arena
+	int fetch_elems(void *dst, const void *dev, size_t es, const StreamsIn &h); // out_n, the decoded elements of `dev`
+	int fetch_samples(const StreamsIn &h);                                     // ... the samples of g.sig into h.sig
+	int fetch_prefix(void *dst, void *dev, uint64_t bytes);                    // a dense arena's first bytes
+private:
+	std::vector<uint32_t> order;    // the reads in ascending sample offset (check_disjoint)
+	std::vector<uint64_t> doff, rel; // dense offsets of the streams; the slots relative to the first
+};
+void staging_release(); // the page-locked staging buffers
 
 // ---- zstd, loaded lazily (third party; the reference links -lzstd, press/Makefile:3) ----
 struct Zstd {
@@ -178,6 +230,7 @@ struct ScratchPlan {
 	} rows[48]; // at most one per scratch DevBuf of Ctx
 	int nrows;
 	ScratchPlan &need(DevBuf Ctx::*buf, size_t bytes); // a buffer named twice keeps the larger size
+	ScratchPlan &merge(const ScratchPlan &o);          // every row of o: the larger size of every buffer
 	int reserve() const;
 	void *ptr(DevBuf Ctx::*buf) const; // the buffer's device pointer; NULL for a buffer the plan has no row for
 	void bind(BatchArgs &a) const;      // a zeroed, with every scratch pointer and count of the plan

@@ -48,6 +48,13 @@ ScratchPlan &ScratchPlan::need(DevBuf Ctx::*buf, size_t bytes)
 	return *this;
 }
 
+ScratchPlan &ScratchPlan::merge(const ScratchPlan &o)
+{
+	for (int i = 0; i < o.nrows; i++)
+		need(o.rows[i].buf, o.rows[i].bytes);
+	return *this;
+}
+
 int ScratchPlan::reserve() const
 {
 	for (int i = 0; i < nrows; i++)
@@ -199,10 +206,7 @@ RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t n
 	const Method &m = METHODS[dst];
 	r.keep_heads = (m.family == FAM_SVB && m.slow5) || (m.family == FAM_ZSTD && m.kdiv);
 	r.all = r.d;
-	const ScratchPlan others[3] = { r.p, make_plan(src, total_samples, nreads, false), make_plan(dst, total_samples, nreads, true) };
-	for (const ScratchPlan &o : others)
-		for (int i = 0; i < o.nrows; i++)
-			r.all.need(o.rows[i].buf, o.rows[i].bytes);
+	r.all.merge(r.p).merge(make_plan(src, total_samples, nreads, false)).merge(make_plan(dst, total_samples, nreads, true));
 	const size_t nr = (size_t) nreads + 1;
 	r.all.need(&Ctx::rn, nr * 4);
 	if (!keep_samples)
@@ -261,21 +265,25 @@ ZsBufs ScratchPlan::zs() const
 
 } // namespace ph
 
-// What the two batch calls keep for a batch of this shape: the buffers are shared and grow-only, so each holds the
-// larger of what press and depress ask of it.  Host arithmetic, no device needed.
+// The *_workspace_bytes: a call's plan summed, with the device table for a Huffman method.  The buffers are shared and
+// grow-only, so each call's figure folds in (merge) the plans of the calls a caller mixes it with on one batch shape: no
+// buffer grows then.  Host arithmetic, no device needed.
+static uint64_t plan_bytes(const ScratchPlan &p, bool huffman)
+{
+	uint64_t b = huffman ? sizeof(HuffDev) : 0;
+	for (int i = 0; i < p.nrows; i++)
+		b += p.rows[i].bytes;
+	return b;
+}
+static bool is_shuff(int method) { return is_shuff(METHODS[method]); }
+
+// the larger of what press and depress ask of every buffer
 extern "C" uint64_t press_hip_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads)
 {
 	API_LOCK; // (the Huffman decoder's rows depend on the table in force)
 	if (!method_ok(method))
 		return 0;
-	ScratchPlan p = make_plan(method, total_samples, nreads, false);
-	const ScratchPlan d = make_plan(method, total_samples, nreads, true);
-	for (int i = 0; i < d.nrows; i++)
-		p.need(d.rows[i].buf, d.rows[i].bytes);
-	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
-	for (int i = 0; i < p.nrows; i++)
-		b += p.rows[i].bytes;
-	return b;
+	return plan_bytes(make_plan(method, total_samples, nreads, false).merge(make_plan(method, total_samples, nreads, true)), is_shuff(method));
 }
 
 extern "C" uint64_t press_hip_recode_workspace_bytes(int src_method, int dst_method, uint64_t total_samples, uint32_t nreads,
@@ -284,28 +292,17 @@ extern "C" uint64_t press_hip_recode_workspace_bytes(int src_method, int dst_met
 	API_LOCK;
 	if (!method_ok(src_method) || !method_ok(dst_method))
 		return 0;
-	const RecodePlan r = make_recode_plan(src_method, dst_method, total_samples, nreads, keep_samples != 0);
-	uint64_t b = is_shuff(METHODS[src_method]) || is_shuff(METHODS[dst_method]) ? sizeof(HuffDev) : 0;
-	for (int i = 0; i < r.all.nrows; i++)
-		b += r.all.rows[i].bytes;
-	return b;
+	return plan_bytes(make_recode_plan(src_method, dst_method, total_samples, nreads, keep_samples != 0).all,
+			  is_shuff(src_method) || is_shuff(dst_method));
 }
 
-// as press_hip_workspace_bytes (a caller that mixes the calls on one batch shape never sees a buffer grow), and the
-// two tables of the packed plan
+// as press_hip_workspace_bytes, and the two tables of the packed plan
 extern "C" uint64_t press_hip_packed_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads)
 {
 	API_LOCK;
 	if (!method_ok(method))
 		return 0;
-	ScratchPlan p = make_packed_plan(method, total_samples, nreads);
-	const ScratchPlan d = make_plan(method, total_samples, nreads, true);
-	for (int i = 0; i < d.nrows; i++)
-		p.need(d.rows[i].buf, d.rows[i].bytes);
-	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
-	for (int i = 0; i < p.nrows; i++)
-		b += p.rows[i].bytes;
-	return b;
+	return plan_bytes(make_packed_plan(method, total_samples, nreads).merge(make_plan(method, total_samples, nreads, true)), is_shuff(method));
 }
 
 // as press_hip_recode_workspace_bytes, and the two tables of the packed plan
@@ -315,11 +312,8 @@ extern "C" uint64_t press_hip_recode_packed_workspace_bytes(int src_method, int 
 	API_LOCK;
 	if (!method_ok(src_method) || !method_ok(dst_method))
 		return 0;
-	const RecodePlan r = make_recode_packed_plan(src_method, dst_method, total_samples, nreads, keep_samples != 0);
-	uint64_t b = is_shuff(METHODS[src_method]) || is_shuff(METHODS[dst_method]) ? sizeof(HuffDev) : 0;
-	for (int i = 0; i < r.all.nrows; i++)
-		b += r.all.rows[i].bytes;
-	return b;
+	return plan_bytes(make_recode_packed_plan(src_method, dst_method, total_samples, nreads, keep_samples != 0).all,
+			  is_shuff(src_method) || is_shuff(dst_method));
 }
 
 // as press_hip_workspace_bytes, and what the device-resident press_hip_depress_pa_batch adds for a method that is not fused
@@ -328,14 +322,7 @@ extern "C" uint64_t press_hip_depress_pa_workspace_bytes(int method, uint64_t to
 	API_LOCK;
 	if (!method_ok(method))
 		return 0;
-	ScratchPlan p = make_pa_plan(method, total_samples, nreads, false);
-	const ScratchPlan e = make_plan(method, total_samples, nreads, false);
-	for (int i = 0; i < e.nrows; i++)
-		p.need(e.rows[i].buf, e.rows[i].bytes);
-	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
-	for (int i = 0; i < p.nrows; i++)
-		b += p.rows[i].bytes;
-	return b;
+	return plan_bytes(make_pa_plan(method, total_samples, nreads, false).merge(make_plan(method, total_samples, nreads, false)), is_shuff(method));
 }
 
 // ... and what the device-resident press_hip_depress_norm_batch adds
@@ -344,14 +331,7 @@ extern "C" uint64_t press_hip_depress_norm_workspace_bytes(int method, uint64_t 
 	API_LOCK;
 	if (!method_ok(method))
 		return 0;
-	ScratchPlan p = make_norm_plan(method, total_samples, nreads, false);
-	const ScratchPlan e = make_plan(method, total_samples, nreads, false);
-	for (int i = 0; i < e.nrows; i++)
-		p.need(e.rows[i].buf, e.rows[i].bytes);
-	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
-	for (int i = 0; i < p.nrows; i++)
-		b += p.rows[i].bytes;
-	return b;
+	return plan_bytes(make_norm_plan(method, total_samples, nreads, false).merge(make_plan(method, total_samples, nreads, false)), is_shuff(method));
 }
 
 // ... and what the device-resident press_hip_depress_chunks_batch keeps: the rows are the caller's, so T and overlap
@@ -362,14 +342,8 @@ extern "C" uint64_t press_hip_depress_chunks_workspace_bytes(int method, uint64_
 	API_LOCK;
 	if (!method_ok(method) || T == 0 || T % 8 || overlap >= T)
 		return 0;
-	ScratchPlan p = make_chunks_plan(method, total_samples, nreads, false, 0);
-	const ScratchPlan e = make_plan(method, total_samples, nreads, false);
-	for (int i = 0; i < e.nrows; i++)
-		p.need(e.rows[i].buf, e.rows[i].bytes);
-	uint64_t b = is_shuff(*p.m) ? sizeof(HuffDev) : 0;
-	for (int i = 0; i < p.nrows; i++)
-		b += p.rows[i].bytes;
-	return b;
+	return plan_bytes(make_chunks_plan(method, total_samples, nreads, false, 0).merge(make_plan(method, total_samples, nreads, false)),
+			  is_shuff(method));
 }
 
 static bool rank_ok(uint32_t num, uint32_t den) { return den > 0 && num <= den; }

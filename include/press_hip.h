@@ -203,6 +203,16 @@ enum press_hip_method {
 #define PRESS_HIP_EHIP     (-3)  /* a HIP runtime call failed */
 #define PRESS_HIP_ENOTABLE (-4)  /* static-Huffman method without a table */
 #define PRESS_HIP_FAILED   UINT64_MAX /* per-read length on failure (capacity, malformed stream) */
+/*
+ * Argument checks of the batch calls below (press, packed press, symbol counts, the depress family, the signal
+ * statistics, recode).  Every one of them first checks what needs no device: the method ids, a NULL among the pointers
+ * a non-empty batch reads or writes, align, dtype, T / overlap, the rule, the ranks, and for device_resident != 0 the
+ * 16-byte alignment of its sample / float / row arena.  These are PRESS_HIP_EARG with or without a GPU, and before any
+ * scratch is (re)allocated.  Then the device is initialised (PRESS_HIP_EHIP if that fails) and a Huffman method's table
+ * looked for (PRESS_HIP_ENOTABLE).  nreads == 0 is PRESS_HIP_OK and touches nothing (the packed calls write
+ * out_off[0] = 0).  The layout checks of the host-pointer form (offsets, total_samples, overlaps, out_off, row_first) read
+ * the caller's tables and come behind that.
+ */
 
 /* last HIP / library error as text (thread local) */
 const char *press_hip_last_error(void);
