@@ -777,3 +777,111 @@ extern "C" int press_hip_recode_packed(int src_method, int dst_method, const uin
 		return rc;
 	return recode_fetch_decoded(st, host, true);
 }
+
+// ------------------------------------------------------------------ verify: the digest of samples, of decoded streams; decode and compare
+//
+// The three calls share make_verify_plan and the launchers beside launch_depress_pa (press_methods.hip); the decoding
+// two write their samples into g.rsig at the caller's off[] and hand nothing of them out.
+
+extern "C" int press_hip_signal_crc32(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				      uint64_t total_samples, uint32_t *crc, int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(NONE, NONE, nreads && (!sig || !off || !n || !crc), nreads, device_resident ? sig : nullptr, "sig");
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_verify_plan(NONE, total_samples, nreads, !device_resident);
+	if ((rc = plan.reserve()))
+		return rc;
+	DecodeArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	SamplesIn in = { sig, off, n };
+	Staged st(nreads, s);
+	if (!device_resident && ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in))))
+		return rc;
+	bind_io(a, in);
+	if ((rc = launch_signal_crc(plan, a, device_resident ? crc : (uint32_t *) g.vf_out.p, s)) || device_resident)
+		return rc;
+	HIPCHK(hipMemcpyAsync(crc, g.vf_out.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
+extern "C" int press_hip_depress_crc_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+					   uint32_t nreads, const uint64_t *off, const uint32_t *n, uint64_t total_samples,
+					   uint32_t *crc, uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(method, NONE, nreads && (!in || !in_off || !in_len || !off || !n || !crc || !out_n), nreads, nullptr, "");
+	if (rc || (rc = device_ready(method, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_verify_plan(method, total_samples, nreads, !device_resident);
+	if ((rc = plan.reserve()))
+		return rc;
+	DecodeArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	const StreamsIn host = { in, in_off, in_len, off, n, out_n, (int16_t *) plan.ptr(&Ctx::rsig) };
+	StreamsIn io = host;
+	Staged st(nreads, s);
+	if (!device_resident && (rc = st.streams(host, total_samples, false, g.arena, g.arena_off, io)))
+		return rc;
+	bind_io(a, io);
+	if ((rc = launch_depress_crc(plan, a, device_resident ? crc : (uint32_t *) g.vf_out.p, s)) || device_resident)
+		return rc;
+	HIPCHK(hipMemcpyAsync(crc, g.vf_out.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
+extern "C" int press_hip_verify_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+				      uint32_t nreads, const int16_t *sig, const uint64_t *off, const uint32_t *n,
+				      uint64_t total_samples, uint32_t *first_bad, uint32_t *out_n, uint32_t *nbad,
+				      int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(method, NONE, !nbad || (nreads && (!in || !in_off || !in_len || !sig || !off || !n || !first_bad || !out_n)), nreads,
+			 device_resident ? sig : nullptr, "sig");
+	if (rc || (rc = device_ready(method, NONE)))
+		return rc;
+	if (nreads == 0) {
+		if (!device_resident)
+			*nbad = 0;
+		return 0;
+	}
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_verify_plan(method, total_samples, nreads, !device_resident);
+	if ((rc = plan.reserve()))
+		return rc;
+	DecodeArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	const StreamsIn host = { in, in_off, in_len, off, n, out_n, nullptr };
+	StreamsIn io = host;
+	SamplesIn want = { sig, off, n };
+	uint32_t *fb = first_bad, *nb = nbad;
+	Staged st(nreads, s);
+	if (!device_resident) { // host pointers: the streams as depress stages them, the samples where press stages them
+		if ((rc = st.streams(host, total_samples, true, g.arena, g.arena_off, io)) || (rc = st.samples(want, total_samples, want)))
+			return rc;
+		fb = (uint32_t *) g.vf_out.p;
+		nb = fb + nreads;
+	}
+	io.sig = (int16_t *) plan.ptr(&Ctx::rsig); // the decode goes to the library's samples
+	bind_io(a, io);
+	if ((rc = launch_verify(plan, a, want.sig, fb, nb, s)) || device_resident)
+		return rc;
+	HIPCHK(hipMemcpyAsync(first_bad, fb, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(nbad, nb, 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}

@@ -70,6 +70,7 @@ struct Ctx {
 	DevBuf pa_tile, pa_ctl, pa_cal, pa_out; // picoamperes: the converter's tile table and its count; host path: the staged calibration, the float arena
 	DevBuf st_rows, st_read, st_cal, st_stats; // median / MAD: the reads' count rows, the pick state, the normaliser's two floats; host path: stats
 	DevBuf ch_rows, ch_first; // chunk rows, host path: the row arena, the staged row_first
+	DevBuf vf_raw, vf_out; // verify / CRC-32: a word per read between the two kernels; host path: the staged crc or first_bad, and nbad
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams
@@ -270,6 +271,11 @@ ScratchPlan make_norm_plan(int method, uint64_t total_samples, uint32_t nreads, 
 // of the float arena
 ScratchPlan make_chunks_plan(int method, uint64_t total_samples, uint32_t nreads, bool host, uint64_t rows_bytes);
 
+// press_hip_verify_batch / press_hip_depress_crc_batch: the decode plan of the method, the samples, the tile table and a
+// word per read; host pointers: the staged per-read result and nbad (vf_out: nreads words, then nbad).  method < 0
+// (press_hip_signal_crc32): no decode and no samples, the tile table and the words alone
+ScratchPlan make_verify_plan(int method, uint64_t total_samples, uint32_t nreads, bool host);
+
 // press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
 ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);
 
@@ -293,6 +299,11 @@ struct ChunkArgs {
 	int32_t *q;                       // 2 per read, or NULL
 };
 int launch_depress_chunks(const ScratchPlan &p, const DecodeArgs &a, const ChunkArgs &c, hipStream_t s);
+// p from make_verify_plan.  launch_signal_crc: a.sig the caller's samples, a.out_n their counts.  launch_depress_crc and
+// launch_verify: a.sig the samples' scratch; sig: the samples the streams are meant to hold, at a.off[]
+int launch_signal_crc(const ScratchPlan &p, const DecodeArgs &a, uint32_t *crc, hipStream_t s);
+int launch_depress_crc(const ScratchPlan &p, const DecodeArgs &a, uint32_t *crc, hipStream_t s);
+int launch_verify(const ScratchPlan &p, const DecodeArgs &a, const int16_t *sig, uint32_t *first_bad, uint32_t *nbad, hipStream_t s);
 bool scale_rule_ok(const press_hip_scale_rule *rule); // ranks and floats as include/press_hip.h asks
 uint64_t chunk_rows_of(uint32_t c, uint32_t T, uint32_t S); // rows of a read of c samples in press_hip_chunk_plan, S = T - overlap
 // phases: PACK_SIZE | PACK_WRITE (press_internal.h); a.out_off must be pk.slot

@@ -375,6 +375,13 @@ void launch_signal_quantiles(const DecodeArgs &a, const uint2 *tiles, const uint
 enum { PRESS_ROWS_F32 = 0, PRESS_ROWS_F16 = 1, PRESS_ROWS_BF16 = 2 }; // PRESS_HIP_F32 / F16 / BF16
 void launch_chunk_rows(const DecodeArgs &a, const float *cal, const uint64_t *row_first, void *rows, uint64_t nrows_cap, int dtype,
 		       uint32_t T, uint32_t overlap, uint64_t total_samples, hipStream_t s);
+// press_verify.hip, over launch_pa_tiles' table of the same batch (a.nsamp: the rooms, a.out_n: the counts):
+// crc[r] = zlib's CRC-32 of the a.out_n[r] samples at a.sig + a.off[r], 0 for a refused read; raw: one word per read
+void launch_crc(const DecodeArgs &a, const uint2 *tiles, const uint32_t *ntiles, uint32_t *raw, uint32_t *crc, hipStream_t s);
+// first_bad[r] of the samples at a.sig + a.off[r] against those at sig + a.off[r] (include/press_hip.h,
+// press_hip_verify_batch); *nbad = the reads that are not verified
+void launch_verify_cmp(const DecodeArgs &a, const int16_t *sig, const uint2 *tiles, const uint32_t *ntiles, uint32_t *first_bad,
+		       uint32_t *nbad, hipStream_t s);
 void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip

@@ -188,6 +188,22 @@ ScratchPlan make_chunks_plan(int method, uint64_t total_samples, uint32_t nreads
 	return p;
 }
 
+// Verify and CRC-32: the general picoampere plan (decode, samples, tile table) for every method, and a word per read
+ScratchPlan make_verify_plan(int method, uint64_t total_samples, uint32_t nreads, bool host)
+{
+	ScratchPlan p{};
+	if (method >= 0) {
+		p = make_plan(method, total_samples, nreads, true);
+		p.need(&Ctx::rsig, total_samples * 2 + 64);
+	} else {
+		p.max_chunks = (uint32_t) (total_samples / CHUNK + nreads + 1); // (as make_plan)
+	}
+	p.need(&Ctx::pa_tile, (size_t) p.max_chunks * sizeof(uint2)).need(&Ctx::pa_ctl, 64).need(&Ctx::vf_raw, (size_t) nreads * 4 + 4);
+	if (host)
+		p.need(&Ctx::vf_out, (size_t) nreads * 4 + 4);
+	return p;
+}
+
 // Fused pairs: BLOW5's and the reference's svb-zd streams into any exception-split method.  (svb12 has no deltas; the zstd
 // kinds and the svb destinations take the general path.)
 bool recode_fused(int src, int dst)
@@ -344,6 +360,15 @@ extern "C" uint64_t press_hip_depress_chunks_workspace_bytes(int method, uint64_
 		return 0;
 	return plan_bytes(make_chunks_plan(method, total_samples, nreads, false, 0).merge(make_plan(method, total_samples, nreads, false)),
 			  is_shuff(method));
+}
+
+// ... and what the device-resident press_hip_verify_batch and press_hip_depress_crc_batch add
+extern "C" uint64_t press_hip_verify_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads)
+{
+	API_LOCK;
+	if (!method_ok(method))
+		return 0;
+	return plan_bytes(make_verify_plan(method, total_samples, nreads, false).merge(make_plan(method, total_samples, nreads, false)), is_shuff(method));
 }
 
 static bool rank_ok(uint32_t num, uint32_t den) { return den > 0 && num <= den; }
@@ -590,6 +615,34 @@ int ph::launch_depress_chunks(const ScratchPlan &p, const DecodeArgs &a, const C
 		launch_signal_stats(a, tiles, ntiles, p.ptr(&Ctx::st_read), (uint32_t *) p.ptr(&Ctx::st_rows), c.q, cal, nullptr, s);
 	}
 	launch_chunk_rows(a, cal, c.row_first, c.rows, c.nrows_cap, c.dtype, c.T, c.overlap, c.total_samples, s);
+	return launch_status();
+}
+
+// The tile table of the rooms, then the digest of the a.out_n[r] samples at a.sig
+int ph::launch_signal_crc(const ScratchPlan &p, const DecodeArgs &a, uint32_t *crc, hipStream_t s)
+{
+	uint2 *tiles = (uint2 *) p.ptr(&Ctx::pa_tile);
+	uint32_t *ntiles = (uint32_t *) p.ptr(&Ctx::pa_ctl);
+	launch_pa_tiles(a, tiles, ntiles, s);
+	launch_crc(a, tiles, ntiles, (uint32_t *) p.ptr(&Ctx::vf_raw), crc, s);
+	return launch_status();
+}
+
+int ph::launch_depress_crc(const ScratchPlan &p, const DecodeArgs &a, uint32_t *crc, hipStream_t s)
+{
+	const int rc = launch_depress(p, a, s);
+	return rc ? rc : launch_signal_crc(p, a, crc, s);
+}
+
+int ph::launch_verify(const ScratchPlan &p, const DecodeArgs &a, const int16_t *sig, uint32_t *first_bad, uint32_t *nbad, hipStream_t s)
+{
+	const int rc = launch_depress(p, a, s);
+	if (rc)
+		return rc;
+	uint2 *tiles = (uint2 *) p.ptr(&Ctx::pa_tile);
+	uint32_t *ntiles = (uint32_t *) p.ptr(&Ctx::pa_ctl);
+	launch_pa_tiles(a, tiles, ntiles, s);
+	launch_verify_cmp(a, sig, tiles, ntiles, first_bad, nbad, s);
 	return launch_status();
 }
 

@@ -90,7 +90,9 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_blow5_threads",
      "press_hip_shutdown", "press_hip_scratch_buffers", "press_hip_host_alloc", "press_hip_host_free",
      "press_hip_zstd_host_frames", "press_hip_symbol_counts", "press_hip_table_from_counts",
-     "press_hip_write_table_file"]))
+     "press_hip_write_table_file",
+     "press_hip_crc32_combine", "press_hip_signal_crc32", "press_hip_depress_crc_batch", "press_hip_verify_batch",
+     "press_hip_verify_workspace_bytes"]))
 
 
 class PressError(RuntimeError):
@@ -200,6 +202,22 @@ def load_library(path=LIB_PATH):
         _lib.press_hip_recode_packed_workspace_bytes.restype = ctypes.c_uint64
         _lib.press_hip_recode_packed_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
                                                                  ctypes.c_uint32, ctypes.c_int]
+        _lib.press_hip_crc32_combine.restype = ctypes.c_uint32
+        _lib.press_hip_crc32_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
+        _lib.press_hip_signal_crc32.restype = ctypes.c_int
+        _lib.press_hip_signal_crc32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_depress_crc_batch.restype = ctypes.c_int
+        _lib.press_hip_depress_crc_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_verify_batch.restype = ctypes.c_int
+        _lib.press_hip_verify_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int]
+        _lib.press_hip_verify_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_verify_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
         _lib.press_hip_debug_pass_a_launches.restype = ctypes.c_uint64
         _lib.press_hip_debug_pass_a_launches.argtypes = []
         libc = ctypes.CDLL(None)
@@ -932,6 +950,122 @@ def signal_stats_host(reads):
     return stats
 
 
+# ---------------------------------------------------------------------------- verifying: CRC-32 and compare-after-decode
+
+VERIFIED = 0xFFFFFFFF  # PRESS_HIP_VERIFIED: first_bad of a read that decodes to the samples it is meant to hold
+
+
+def crc32_combine(a, b, len_b):
+    """zlib.crc32(A + B) from zlib.crc32(A), zlib.crc32(B) and len(B) in bytes (press_hip_crc32_combine: host
+    arithmetic, no GPU)"""
+    return int(load_library().press_hip_crc32_combine(int(a) & 0xFFFFFFFF, int(b) & 0xFFFFFFFF, int(len_b)))
+
+
+def _u32_table(t, nreads, name):
+    if t.numel() < nreads or t.element_size() != 4 or not t.is_contiguous():
+        raise PressError("%s must be a contiguous 32-bit tensor of nreads entries" % name)
+
+
+def signal_crc32(sig, off, n, crc):
+    """Enqueue the per-read CRC-32 of a batch of samples (CUDA tensors as in signal_stats; crc: 32-bit, nreads entries):
+    crc[r] = zlib.crc32 of the n[r] int16 samples at sig[off[r]:] as bytes (press_hip_signal_crc32)."""
+    nreads = off.numel()
+    _u32_table(crc, nreads, "crc")
+    if load_library().press_hip_signal_crc32(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
+                                             crc.data_ptr(), 1):
+        raise PressError(last_error())
+
+
+def signal_crc32_host(reads):
+    """CRC-32 of a list of int16 arrays (host buffers, synchronous) -> uint32[nreads]"""
+    lib = load_library()
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    crc = np.zeros(len(reads), dtype=np.uint32)
+    if lib.press_hip_signal_crc32(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, crc.ctypes.data, 0):
+        raise PressError(last_error())
+    return crc
+
+
+def depress_crc_batch(method, comp, in_off, in_len, off, n, total_samples, crc, out_n):
+    """Enqueue the decompression of a batch into library scratch and the CRC-32 of what was decoded (CUDA tensors as in
+    depress_batch; off / n / total_samples lay out the library's sample scratch; crc: 32-bit, nreads entries, 0 for a
+    refused read).  No sample reaches the caller (press_hip_depress_crc_batch)."""
+    nreads = off.numel()
+    _u32_table(crc, nreads, "crc")
+    rc = load_library().press_hip_depress_crc_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
+                                                    nreads, off.data_ptr(), n.data_ptr(), int(total_samples),
+                                                    crc.data_ptr(), out_n.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def _streams_arena(streams):
+    nreads = len(streams)
+    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+    in_off = np.zeros(nreads, dtype=np.uint64)
+    if nreads > 1:
+        in_off[1:] = np.cumsum(in_len)[:-1]
+    return np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy(), in_off, in_len
+
+
+def depress_crc_batch_host(method, streams, ns):
+    """Decode and digest with host buffers: streams = list of bytes, ns = sample counts / rooms ->
+    (crc uint32[nreads], out_n uint32[nreads]; 0 and 0xFFFFFFFF for a refused read)"""
+    lib = load_library()
+    nreads = len(streams)
+    comp, in_off, in_len = _streams_arena(streams)
+    ns = np.asarray(ns, dtype=np.uint32)
+    off, total = _layout(ns)
+    crc = np.zeros(nreads, dtype=np.uint32)
+    out_n = np.zeros(nreads, dtype=np.uint32)
+    if lib.press_hip_depress_crc_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads,
+                                       off.ctypes.data, ns.ctypes.data, total, crc.ctypes.data, out_n.ctypes.data, 0):
+        raise PressError(last_error())
+    return crc, out_n
+
+
+def verify_batch(method, comp, in_off, in_len, sig, off, n, first_bad, out_n, nbad):
+    """Enqueue decode-and-compare of a batch (CUDA tensors: the streams as in depress_batch; sig / off / n the samples
+    they are meant to hold, laid out as press_batch takes them; first_bad, out_n: 32-bit, nreads entries; nbad: one
+    32-bit word).  first_bad[r] = VERIFIED, or the first sample that differs (0: the stream is refused; min(out_n, n)
+    where only the counts differ); nbad = the reads that are not VERIFIED (press_hip_verify_batch)."""
+    nreads = off.numel()
+    _u32_table(first_bad, nreads, "first_bad")
+    _u32_table(nbad, 1, "nbad")
+    rc = load_library().press_hip_verify_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), nreads,
+                                               sig.data_ptr(), off.data_ptr(), n.data_ptr(), sig.numel(),
+                                               first_bad.data_ptr(), out_n.data_ptr(), nbad.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def verify_batch_host(method, streams, reads):
+    """Decode and compare with host buffers: streams = list of bytes, reads = the int16 arrays they are meant to hold
+    -> (first_bad uint32[nreads], out_n uint32[nreads], nbad)"""
+    lib = load_library()
+    nreads = len(streams)
+    if len(reads) != nreads:
+        raise PressError("verify_batch_host: one stream per read")
+    comp, in_off, in_len = _streams_arena(streams)
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    first_bad = np.zeros(nreads, dtype=np.uint32)
+    out_n = np.zeros(nreads, dtype=np.uint32)
+    nbad = ctypes.c_uint32(0)
+    if lib.press_hip_verify_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads,
+                                  sig.ctypes.data, off.ctypes.data, ns.ctypes.data, total, first_bad.ctypes.data,
+                                  out_n.ctypes.data, ctypes.byref(nbad), 0):
+        raise PressError(last_error())
+    return first_bad, out_n, int(nbad.value)
+
+
 class HostBatch:
     """A batch in HOST memory laid out once, so that press() / depress() are nothing but the C calls
     (press_hip_press_batch / press_hip_depress_batch with device_resident = 0): what a C caller that
@@ -1320,13 +1454,17 @@ def blow5_write_like(dst, like, fields, record_method=1, signal_method=1, index=
     return out_ids
 
 
-def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, passthrough=False, index=False):
+def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, passthrough=False, index=False, verify=False):
     """BLOW5 -> BLOW5 with the signal fields re-coded: codec(list of int16 arrays) -> list of svb-zd
     streams (default: the device, press_batch_host("slow5_svb_zd")); signal_method 0 writes the raw
     samples.  Signals of the source are decoded on the device when it stores them as svb-zd.
     passthrough: keep the signal fields as they are (source and target signal method must agree;
     no GPU involved - only the record framing / record compression changes).
     index: also write slow5lib's <dst>.idx (the reference's slow5_get then works on the transcoded file).
+    verify: before a batch is written, its outgoing svb-zd fields are decoded on the device and compared with the
+    samples they were made of (verify_batch_host); a field that does not give them back raises PressError with the
+    read's id and the first bad sample, and nothing more is written.  Nothing to check with passthrough or
+    signal_method 0, which writes the samples themselves.
     Returns the number of reads written."""
     lib = load_library()
     _blow5_writer_api(lib)
@@ -1374,6 +1512,13 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
                 pass
             elif signal_method == 1:
                 out = (codec or (lambda reads: press_batch_host("slow5_svb_zd", reads)))(sigs)
+                if verify:
+                    first_bad, _, nbad = verify_batch_host("slow5_svb_zd", out, sigs)
+                    if nbad:
+                        k = int(np.flatnonzero(first_bad != VERIFIED)[0])
+                        idl = int(recs[k][0]) | (int(recs[k][1]) << 8)
+                        raise PressError("read %s: the svb-zd field written for it does not decode to its samples (first bad sample %d)"
+                                         % (recs[k][2:2 + idl].tobytes().split(b"\0")[0].decode(errors="replace"), int(first_bad[k])))
             else:
                 out = [np.ascontiguousarray(s, dtype=np.int16).tobytes() for s in sigs]
             _blow5_write_batch(lib, w, [r[:int(sp[k]) - 8] for k, r in enumerate(recs)],

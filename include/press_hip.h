@@ -660,6 +660,69 @@ uint64_t press_hip_recode_packed_workspace_bytes(int src_method, int dst_method,
 						 uint32_t nreads, int keep_samples);
 
 /*
+ * Verifying on the device: "does what I wrote decode to what I had?" - by comparison while the samples are still there,
+ * and by a per-read digest that can be kept and checked on another machine or years later.
+ *
+ * The digest: crc[r] is zlib's CRC-32 of read r's samples as they lie in memory - 2 * count bytes, little-endian int16;
+ * polynomial 0xEDB88320 (reflected), initial value and final xor 0xFFFFFFFF; 0 for an empty read.  It is what
+ * zlib.crc32(samples.tobytes()) gives, exactly: the value is an integer and does not depend on the run.
+ *
+ * press_hip_crc32_combine: host arithmetic, no GPU: crc32(A || B) from crc32(A), crc32(B) and |B| in bytes (any 64-bit
+ * length: the exponent is reduced, never truncated), so that digests of pieces make the digest of the whole.
+ *
+ * press_hip_signal_crc32: crc[r] of the n[r] samples at sig + off[r].
+ *   sig / off / n / total_samples / device_resident   as press_hip_press_batch, with its checks: off[] multiples of 8
+ *            samples, a device sig 16-byte aligned (PRESS_HIP_EARG), non-overlap (host pointers: checked).  Loads stay
+ *            inside [off[r], off[r] + roundup8(n[r])); what lies beyond n[r] does not take part.
+ *   crc      nreads words; a device pointer when device resident.  Nothing beyond it is written.
+ *
+ * press_hip_depress_crc_batch: decode any of the 19 methods into library scratch and digest what was decoded; nothing of
+ * the samples reaches the caller.
+ *   in/in_off/in_len/off/n/total_samples/out_n   exactly as in press_hip_depress_batch: its checks, room rules, empty-read
+ *            rules, PRESS_HIP_ENOTABLE and the zstd kinds' host wait.  off[] and n[] place the reads in the library's
+ *            scratch; the rooms must not overlap.
+ *   crc      crc[r] is the digest of the out_n[r] decoded samples, and 0 for a refused read (out_n[r] == UINT32_MAX)
+ *
+ * press_hip_verify_batch: decode into library scratch and compare with the caller's samples.
+ *   in/in_off/in_len/out_n   as in press_hip_depress_batch
+ *   sig / off / n   the samples the streams are meant to hold, laid out as press_hip_press_batch takes them: 16-byte
+ *            aligned, off[] in multiples of 8.  n[r] is the expected count AND the decoder's room.  sig is never written;
+ *            loads from it stay inside [off[r], off[r] + roundup8(n[r])), as the press kernels' do, and nothing beyond n[r]
+ *            takes part in the comparison.
+ *   first_bad   per read, with c = out_n[r]:
+ *              0 if the stream is refused (c == UINT32_MAX); a count-carrying stream that holds more samples than n[r]
+ *                is refused by the decoder, as in press_hip_depress_batch, and so gives 0;
+ *              otherwise the smallest i < min(c, n[r]) with decoded[i] != sig[off[r] + i];
+ *              without such an i and with c != n[r]: min(c, n[r]);
+ *              otherwise PRESS_HIP_VERIFIED.
+ *   nbad     *nbad = the number of reads with first_bad[r] != PRESS_HIP_VERIFIED: written, not accumulated.  Device
+ *            resident it is a device word.
+ * Such reads exist among the library's own output: the three range coders store tiny or incompressible reads raw
+ * (rcutil_.h:161) and nothing tells their decoder - a valid output of press_hip_press_batch that does not round-trip.
+ *
+ * A bad method id or a NULL argument is PRESS_HIP_EARG before any device call; nreads == 0 is PRESS_HIP_OK (host
+ * pointers: with *nbad = 0).  device_resident != 0: the three calls only enqueue on the current stream - no
+ * synchronisation and no host wait beyond the zstd decode's.  == 0: host pointers, synchronous: the streams are staged as
+ * press_hip_depress_batch stages them, the caller's samples as press_hip_press_batch stages them, the decode goes to the
+ * library's sample scratch, and the small per-read tables and nbad come back.
+ * press_hip_verify_workspace_bytes: the device scratch the device-resident press_hip_verify_batch and
+ * press_hip_depress_crc_batch keep for a batch of this shape, exact as press_hip_workspace_bytes is and never below it:
+ * plus the samples (total_samples * 2 + 64 bytes), the tile table and 4 bytes per read.  0 for a method id out of range.
+ */
+#define PRESS_HIP_VERIFIED 0xFFFFFFFFu
+uint32_t press_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+int press_hip_signal_crc32(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			   uint64_t total_samples, uint32_t *crc, int device_resident);
+int press_hip_depress_crc_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+				uint32_t nreads, const uint64_t *off, const uint32_t *n, uint64_t total_samples,
+				uint32_t *crc, uint32_t *out_n, int device_resident);
+int press_hip_verify_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+			   uint32_t nreads, const int16_t *sig, const uint64_t *off, const uint32_t *n,
+			   uint64_t total_samples, uint32_t *first_bad, uint32_t *out_n, uint32_t *nbad,
+			   int device_resident);
+uint64_t press_hip_verify_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads);
+
+/*
  * PRESS_HIP_ZSTD_SVB_ZD, _ZSTD_SVB12_ZD and _ZSTD_HASGAM_ZDQ in the calls above (SURVEY.md 8f-3,
  * replaces the ZSTD_compress / ZSTD_decompress calls of press.c:1860-1910, 2020-2070, 8549-8589 for batches):
  *   press    writes one standard zstd frame (RFC 8878) per read whose content is the buffer
