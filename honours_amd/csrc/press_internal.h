@@ -210,7 +210,7 @@ struct ZsRead {               // per read
 	uint32_t pad[2];
 };
 // ZsRead on the decode side: nd = content size of the frame, mode 0 ok / 2 malformed / 3 left to libzstd,
-// pad[0] = its first block with sequences + 1 (0: none)
+// pad[0] = its first block with sequences + 1 (0: none), knz = 1: the frame's Content_Checksum in pad[1] is yet to be verified
 struct ZsCopy {               // content bytes [dst, dst + n) of ztmp: a copy of n bytes at src of the arena, or its byte n times
 	uint64_t src, dst;
 	uint32_t n, fill;

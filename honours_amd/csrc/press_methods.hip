@@ -563,6 +563,7 @@ static int zs_host_frames(const DecodeArgs &a, const ZsBufs &z, hipStream_t s, b
 		HIPCHK(hipMemcpy(z.ztmp + zoff[r], buf.data(), got, hipMemcpyHostToDevice));
 		rd[r].mode = 0;
 		rd[r].nd = (uint32_t) got;
+		rd[r].knz = 0; // (a Content_Checksum: libzstd has verified it)
 	}
 	HIPCHK(hipMemcpy(z.rd, rd.data(), (size_t) nr * sizeof(ZsRead), hipMemcpyHostToDevice));
 	return 0;

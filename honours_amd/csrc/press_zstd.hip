@@ -977,6 +977,16 @@ struct DevSink {
 		if ((threadIdx.x & 63) == 0)
 			z.dxblk[cur_xblk - 1].tail = tail;
 	}
+	// the content is whole only behind k_zs_exec: k_zs_finish checks the sum (noted in the read's record at once: nothing
+	// more stays alive through the walk)
+	__device__ int64_t checksum(uint64_t, uint32_t low32)
+	{
+		if ((threadIdx.x & 63) == 0) {
+			z.rd[read].pad[1] = low32;
+			z.rd[read].knz = 1;
+		}
+		return 0;
+	}
 	__device__ void close_unit()
 	{
 		if (unit != 0xFFFFFFFFu && (threadIdx.x & 63) == 0) {
@@ -1107,6 +1117,8 @@ __global__ __launch_bounds__(256, LEAN ? ZSWALK_LEAN_WAVES : ZSWALK_WAVES) void 
 #endif
 	const uint32_t cap_n = a.nsamp[r];
 	const uint64_t cap = zs_content_max(cap_n, z.kdiv); // what zs_slot() leaves room for
+	if ((threadIdx.x & 63) == 0)
+		z.rd[r].knz = 0; // (DevSink::checksum sets it)
 	DevSink sink{ z, a.in_off[r], z.zoff[r], r, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, false, 0, 0 };
 	sink.lit_abs = z.lit_base + z.zoff[r];
 	sink.nreads = a.nreads;
@@ -1130,14 +1142,13 @@ __global__ __launch_bounds__(256, LEAN ? ZSWALK_LEAN_WAVES : ZSWALK_WAVES) void 
 #endif
 	if (threadIdx.x & 63)
 		return;
-	ZsRead rd;
-	rd.nk = rd.knz = rd.dbase = rd.plen = 0;
+	ZsRead &rd = z.rd[r]; // (knz, pad[1]: a Content_Checksum that k_zs_finish is to verify - DevSink::checksum)
+	rd.nk = rd.dbase = rd.plen = 0;
 	rd.pad[0] = L >= 0 ? sink.first_xblk : 0;
-	rd.pad[1] = 0;
 	rd.nd = L >= 0 ? (uint32_t) L : 0;
-	rd.mode = L >= 0 ? 0 : L == zs::W_HOST ? 3 : L == zs::W_SEQ ? 4 : 2;
-	z.rd[r] = rd;
-	if (rd.mode == 3)
+	const uint32_t mode = L >= 0 ? 0 : L == zs::W_HOST ? 3 : L == zs::W_SEQ ? 4 : 2;
+	rd.mode = mode;
+	if (mode == 3)
 		atomicAdd(&z.dctl->nhost, 1u);
 }
 
@@ -1837,10 +1848,13 @@ __global__ __launch_bounds__(256) void k_zs_finish(DecodeArgs a, ZsBufs z)
 	const uint32_t cap_n = a.nsamp[r];
 	uint32_t n = cap_n ? cap_n : 1;
 	uint64_t len = 0; // too short for any read: the svb-zd decode reports the failure
+	// a frame with a Content_Checksum (never the reference's: ZSTD_compress writes none) whose content the device made:
+	// XXH64 is a chain, so this lane goes through the content alone
+	const bool ok = rd.mode == 0 && (!rd.knz || (uint32_t) zs::xxh64(z.ztmp + z.zoff[r], rd.nd) == rd.pad[1]);
 	if (!z.kdiv) { // ex-zd carries its own sample count; n[r] is the room
 		n = cap_n;
-		len = rd.mode == 0 ? rd.nd : 0;
-	} else if (rd.mode == 0 && rd.nd >= 4) {
+		len = ok ? rd.nd : 0;
+	} else if (ok && rd.nd >= 4) {
 		const uint8_t *S = z.ztmp + z.zoff[r];
 		const uint32_t cnt = (uint32_t) S[0] | ((uint32_t) S[1] << 8) | ((uint32_t) S[2] << 16) | ((uint32_t) S[3] << 24);
 		if (cnt <= cap_n) { // press.c:1901: the count in the stream is what gets decoded

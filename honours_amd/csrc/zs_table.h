@@ -16,6 +16,8 @@
 // read (press_zstd.hip), tests/ run it on the host against libzstd.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
+#include <utility>
 
 #if defined(__HIPCC__)
 #define ZS_FN __host__ __device__ inline
@@ -1000,9 +1002,15 @@ ZS_FN uint32_t seq_table(int which, uint32_t mode, const uint8_t *p, uint32_t av
 //                                     literals space, its content starts at dst
 //   sink.seq(i, ll, ml, off)          sequence i: ll literals, then ml bytes from `off` bytes back in the content
 //   sink.seq_end(tail)                the block's last `tail` literals follow its last match
+//   sink.checksum(n, low32) -> 0 / W_*  the frame says that XXH64 of its n content bytes ends in low32: a sink that has
+//                                     the content checks it here, the device's notes it for k_zs_finish.  Optional: a
+//                                     sink without this member leaves the sum unverified.
 // Returns the content size, or W_BAD (malformed) / W_HOST (valid zstd this reader leaves to
 // libzstd: dictionaries, 12-bit tables, several frames, more sequences than the sink takes).
 constexpr int64_t W_BAD = -1, W_HOST = -2, W_SEQ = -3;
+template <class S, class = void> struct sink_has_checksum : std::false_type {};
+template <class S>
+struct sink_has_checksum<S, std::void_t<decltype(std::declval<S &>().checksum(uint64_t(), uint32_t()))>> : std::true_type {};
 #if defined(HUF_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
 #define ZS_STAMP(sink, i) (sink).stamp(i) // diagnostic build: where a wave of k_zs_walk spends its time
 #else
@@ -1040,6 +1048,9 @@ template <class Sink, class Work> ZS_FN int64_t walk_frame(const uint8_t *fp, ui
 {
 	constexpr bool SEQS = sizeof(Work) > sizeof(ReadWorkLean);
 	FrameSrc<Sink> f{ fp, len, 0, false, sink, k };
+	// a skippable frame in front (RFC 8878 3.1.2: magic 0x184D2A5?) is valid zstd that the reference never writes: libzstd's
+	if (len >= 8 && (f[0] & 0xF0u) == 0x50 && f[1] == 0x2A && f[2] == 0x4D && f[3] == 0x18)
+		return W_HOST;
 	if (len < 6 || f[0] != 0x28 || f[1] != 0xB5 || f[2] != 0x2F || f[3] != 0xFD)
 		return W_BAD;
 	const uint32_t fhd = f[4];
@@ -1315,15 +1326,72 @@ template <class Sink, class Work> ZS_FN int64_t walk_frame(const uint8_t *fp, ui
 		if (last)
 			break;
 	}
-	if (checksum)
-		at += 4; // XXH64 of the content: not verified here
-	if (at > len)
-		return W_BAD;
+	uint32_t sum = 0; // the low four bytes of XXH64 of the content (RFC 8878 3.1.1: Content_Checksum)
+	if (checksum) {
+		if (at + 4 > len)
+			return W_BAD;
+		sum = (uint32_t) f[at] | ((uint32_t) f[at + 1] << 8) | ((uint32_t) f[at + 2] << 16) | ((uint32_t) f[at + 3] << 24);
+		at += 4;
+	}
 	if (at != len)
 		return W_HOST; // more frames behind this one
 	if (fcs_bytes && fcs != dst)
 		return W_BAD;
+	if constexpr (sink_has_checksum<Sink>::value) if (checksum) {
+		const int64_t e = sink.checksum(dst, sum);
+		if (e)
+			return e;
+	}
+	(void) sum;
 	return (int64_t) dst;
+}
+
+// XXH64 with seed 0 (the xxHash specification): what a frame's Content_Checksum is the low four bytes of.  Four
+// accumulators over stripes of 32 bytes, each a chain of its own - one lane's work.
+ZS_FN uint64_t xxh_rotl(uint64_t v, int r)
+{
+	return (v << r) | (v >> (64 - r));
+}
+ZS_FN uint64_t xxh_le(const uint8_t *p, int bytes) // (byte loads: the content starts anywhere)
+{
+	uint64_t v = 0;
+	for (int i = 0; i < bytes; i++)
+		v |= (uint64_t) p[i] << (8 * i);
+	return v;
+}
+ZS_FN uint64_t xxh64(const uint8_t *p, uint64_t len)
+{
+	constexpr uint64_t P1 = 11400714785074694791ull, P2 = 14029467366897019727ull, P3 = 1609587929392839161ull,
+			   P4 = 9650029242287828579ull, P5 = 2870177450012600261ull;
+	auto round = [](uint64_t acc, uint64_t in) { return xxh_rotl(acc + in * P2, 31) * P1; };
+	const uint8_t *const end = p + len;
+	uint64_t h;
+	if (len >= 32) {
+		uint64_t v[4] = { P1 + P2, P2, 0, 0 - P1 };
+		for (; end - p >= 32; p += 32)
+			for (int i = 0; i < 4; i++)
+				v[i] = round(v[i], xxh_le(p + 8 * i, 8));
+		h = xxh_rotl(v[0], 1) + xxh_rotl(v[1], 7) + xxh_rotl(v[2], 12) + xxh_rotl(v[3], 18);
+		for (int i = 0; i < 4; i++)
+			h = (h ^ round(0, v[i])) * P1 + P4;
+	} else {
+		h = P5;
+	}
+	h += len;
+	for (; end - p >= 8; p += 8)
+		h = xxh_rotl(h ^ round(0, xxh_le(p, 8)), 27) * P1 + P4;
+	if (end - p >= 4) {
+		h = xxh_rotl(h ^ (xxh_le(p, 4) * P1), 23) * P2 + P3;
+		p += 4;
+	}
+	for (; p < end; p++)
+		h = xxh_rotl(h ^ (*p * P5), 11) * P1;
+	h ^= h >> 33;
+	h *= P2;
+	h ^= h >> 29;
+	h *= P3;
+	h ^= h >> 32;
+	return h;
 }
 
 // one Huffman stream of a block: k bytes from the len bytes at s; dt[i] = byte | bits << 8

@@ -737,14 +737,15 @@ uint64_t press_hip_verify_workspace_bytes(int method, uint64_t total_samples, ui
  *            ZSTD_compress's own (the reference's streams, press.c:1462-1469) - Huffman literals,
  *            FSE-coded sequences with all four table modes, repeat offsets - one wave per frame walks
  *            the blocks, the literals are decoded in parallel, one wave per frame carries out its
- *            sequences.  Only frames with a dictionary, a 12-bit Huffman table, more sequences than the
- *            scratch takes, or several frames in one stream are decompressed by libzstd on the host
- *            inside the call.  NOTE: a zstd depress call waits on the host until the frames have been
+ *            sequences.  Only frames with a dictionary, a 12-bit Huffman table, more sequences, trees or
+ *            blocks than the batch's scratch takes, several frames in one stream or a skippable frame in
+ *            front or behind are decompressed by libzstd on the host inside the call.  NOTE: a zstd depress call waits on the host until the frames have been
  *            walked (the count of such frames comes back through page-locked memory behind an event), also
  *            when device_resident != 0 - the device meanwhile goes on with the rest of the batch, and the
  *            call does not wait for that; only a batch WITH such frames synchronises the stream.
- *            n[r] is the room in samples; the count in the stream decides (press.c:1901).  Content
- *            checksums are not verified.
+ *            n[r] is the room in samples; the count in the stream decides (press.c:1901).  A frame's
+ *            Content_Checksum (XXH64; ZSTD_compress writes none) is verified as libzstd does: on the
+ *            device, by one lane per such frame, and a read whose sum is wrong is refused.
  */
 /* frames the last zstd depress batch left to libzstd on the host (0 for this library's frames and for
  * ZSTD_compress's) */

@@ -3,10 +3,48 @@
 // for the host with AddressSanitizer + UBSan (GPU sanitizers are not available): whatever
 // the bytes are, the reader stays inside the frame and inside the output it was given.
 //   usage: zsframe_fuzz [iterations]     exit code 0 = no finding
+//          zsframe_fuzz 0 <directory>    only the frames in the files <name>_<room>.bin of that directory, each read
+//                                        with room for <room> content bytes (tests/test_zstd_reader_format.py: the
+//                                        damaged frames the device is given)
 #include "zsframe_model.cpp"
 #include <cstdio>
 #include <cstdlib>
+#include <dirent.h>
 #include <dlfcn.h>
+#include <string>
+
+static int frames_from(const char *dir)
+{
+	DIR *d = opendir(dir);
+	if (!d)
+		return fprintf(stderr, "no directory %s\n", dir), 8;
+	int decoded = 0, refused = 0, host = 0;
+	while (const dirent *e = readdir(d)) {
+		const std::string name = e->d_name;
+		const size_t us = name.rfind('_'), dot = name.rfind(".bin");
+		if (us == std::string::npos || dot == std::string::npos || dot < us)
+			continue;
+		const uint64_t cap = strtoull(name.c_str() + us + 1, nullptr, 10);
+		FILE *fp = fopen((std::string(dir) + "/" + name).c_str(), "rb");
+		if (!fp)
+			return fprintf(stderr, "cannot read %s\n", name.c_str()), 8;
+		std::vector<uint8_t> f; // exact-size heap copies: ASan sees any access one byte outside
+		uint8_t buf[65536];
+		for (size_t got; (got = fread(buf, 1, sizeof buf, fp)) > 0;)
+			f.insert(f.end(), buf, buf + got);
+		fclose(fp);
+		std::vector<uint8_t> exact(f), out(cap);
+		const int64_t r = zsm_decode(exact.data(), exact.size(), out.data(), cap);
+		if (r > (int64_t) cap)
+			return fprintf(stderr, "content larger than the room\n"), 4;
+		decoded += r >= 0;
+		refused += r == -1;
+		host += r == -2;
+	}
+	closedir(d);
+	printf("zsframe_fuzz: %d decoded, %d refused, %d left to libzstd - no finding\n", decoded, refused, host);
+	return 0;
+}
 
 static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
 static uint32_t rnd()
@@ -19,6 +57,8 @@ static uint32_t rnd()
 
 int main(int argc, char **argv)
 {
+	if (argc > 2)
+		return frames_from(argv[2]);
 	const int iters = argc > 1 ? atoi(argv[1]) : 20000;
 	int decoded = 0, refused = 0, host = 0;
 	for (int round = 0; round < 24; round++) {

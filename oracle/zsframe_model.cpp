@@ -254,6 +254,7 @@ struct HostSink {
 		memcpy(out + blk_out, lits + blk_lit, tail);
 		blk_out += tail;
 	}
+	int64_t checksum(uint64_t n, uint32_t low32) { return (uint32_t) zs::xxh64(out, n) == low32 ? 0 : zs::W_BAD; }
 	int64_t tree(const uint8_t *w, uint32_t t)
 	{
 		tl = t;

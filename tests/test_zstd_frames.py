@@ -229,7 +229,9 @@ def test_device_frames_small_slots():
 def test_model_reader_on_both_kinds_of_frames(model):
     """zs::walk_frame on the host (the code the device walks frames with): this library's frames decode, and
     so do libzstd's own at the reference's level 1 (press.h:275) and at levels 3 and 9 - sequences
-    included (FSE tables of all four modes, repeat offsets, overlapping matches)"""
+    included (FSE tables of all four modes, repeat offsets, overlapping matches).  The byte texts below reach the
+    device as reads, framed by ZSTD_compressStream2 with flushes and parameters, in tests/test_zstd_reader_format.py,
+    which also records which parts of the format its frames hold."""
     z = _zstd()
     oracle = _libs.oracle()
     m = ctypes.CDLL(MODEL_SO)
