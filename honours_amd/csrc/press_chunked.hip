@@ -2674,8 +2674,10 @@ __global__ __launch_bounds__(256) void k_pa_tiles(const uint32_t *nsamp, uint32_
 		tiles[first + j] = make_uint2(r, j);
 }
 
-// One workgroup per tile: [0, roundup8(out_n[r])) of the read, 8 samples per lane and step - a 16-byte load, two 16-byte
-// stores.  A refused read gets nothing.
+// One workgroup per tile: [0, out_n[r]) of the read, 8 samples per lane and step - a 16-byte load, two 16-byte stores;
+// the read's last, partial group float by float.  The decoder has written out_n[r] samples of the scratch and no more:
+// what lies behind them in the group is whatever an earlier call left there, and no float is made of it.  A refused
+// read gets nothing.
 __global__ __launch_bounds__(256) void k_pa_convert(const int16_t *sig, const uint64_t *off, const uint32_t *out_n,
 						     const float *cal, float *pa, const uint2 *tiles, const uint32_t *ntiles)
 {
@@ -2694,7 +2696,14 @@ __global__ __launch_bounds__(256) void k_pa_convert(const int16_t *sig, const ui
 	for (uint64_t i = first + threadIdx.x * 8; i < end; i += 256 * 8) {
 		const uint4 q = ld16_stream(sig + o + i);
 		const uint32_t v[4] = { q.x, q.y, q.z, q.w };
-		st_pa8(pa + o + i, v, c0, c1);
+		if (i + 8 <= on) {
+			st_pa8(pa + o + i, v, c0, c1);
+		} else {
+#pragma unroll
+			for (uint32_t k = 0; k < 8; k++)
+				if (i + k < on)
+					pa[o + i + k] = pa_of(v, k, c0, c1);
+		}
 	}
 }
 

@@ -231,6 +231,21 @@ extern "C" uint32_t press_hip_scratch_buffers(uint64_t *bytes)
 	return nb;
 }
 
+// Diagnostic: every scratch buffer but the static-Huffman table set to `byte`, in stream order behind the calls already
+// enqueued; the page-locked staging buffers behind a synchronisation (the host writes them).  No buffer grows, shrinks
+// or moves.
+extern "C" int press_hip_scratch_fill(int byte)
+{
+	API_ENTER;
+	const hipStream_t s = g.stream();
+	for (DevBuf *d = g_bufs; d; d = d->next)
+		if (d->p && d != &g.huff)
+			HIPCHK(hipMemsetAsync(d->p, byte & 0xFF, d->cap, s));
+	HIPCHK(hipStreamSynchronize(s));
+	staging_fill(byte & 0xFF);
+	return 0;
+}
+
 extern "C" void *press_hip_host_alloc(uint64_t bytes)
 {
 	API_LOCK;

@@ -148,6 +148,7 @@ private:
 	std::vector<uint64_t> doff, rel; // dense offsets of the streams; the slots relative to the first
 };
 void staging_release(); // the page-locked staging buffers
+void staging_fill(int byte); // ... set to one byte value (press_hip_scratch_fill); the stream must be idle
 
 // ---- zstd, loaded lazily (third party; the reference links -lzstd, press/Makefile:3) ----
 struct Zstd {

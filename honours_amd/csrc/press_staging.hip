@@ -60,6 +60,19 @@ void ph::staging_release()
 	stg.made = false;
 }
 
+// press_hip_scratch_fill: the caller has synchronised the stream, so no DMA has either buffer as its source or target
+void ph::staging_fill(int byte)
+{
+	if (!stg.made)
+		return;
+	for (int k = 0; k < 2; k++) {
+		if (stg.busy[k])
+			(void) hipEventSynchronize(stg.ev[k]);
+		stg.busy[k] = false;
+		memset(stg.buf[k], byte, STAGE_BYTES);
+	}
+}
+
 namespace {
 
 int staging_wait(int k)

@@ -88,7 +88,7 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_blow5_last_error", "press_hip_blow5_next_records", "press_hip_blow5_create",
      "press_hip_blow5_write", "press_hip_blow5_finish", "press_hip_blow5_write_batch", "press_hip_blow5_index",
      "press_hip_blow5_threads",
-     "press_hip_shutdown", "press_hip_scratch_buffers", "press_hip_host_alloc", "press_hip_host_free",
+     "press_hip_shutdown", "press_hip_scratch_buffers", "press_hip_scratch_fill", "press_hip_host_alloc", "press_hip_host_free",
      "press_hip_zstd_host_frames", "press_hip_symbol_counts", "press_hip_table_from_counts",
      "press_hip_write_table_file",
      "press_hip_crc32_combine", "press_hip_signal_crc32", "press_hip_depress_crc_batch", "press_hip_verify_batch",
@@ -696,6 +696,13 @@ def recode_packed(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len,
 def recode_fused(src, dst):
     """True where the press half's first pass comes out of the decode kernel (press_hip_recode_fused)"""
     return bool(load_library().press_hip_recode_fused(_mid(src), _mid(dst)))
+
+
+def scratch_fill(byte):
+    """test aid: set every scratch buffer of the library but the static-Huffman table, and its page-locked staging
+    buffers, to `byte` (press_hip_scratch_fill): a later call's result must not depend on it"""
+    if load_library().press_hip_scratch_fill(int(byte) & 0xFF):
+        raise PressError(last_error())
 
 
 def pass_a_launches():

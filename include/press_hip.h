@@ -428,10 +428,9 @@ int press_hip_depress_batch(int method, const uint8_t *in, const uint64_t *in_of
  *   in/in_off/in_len/off/n/total_samples/out_n   as in press_hip_depress_batch, with its checks, its room rules, its
  *            empty-read rules, PRESS_HIP_ENOTABLE and the zstd kinds' host wait; out_n is what that call gives
  *   pa       takes the place of sig: off[] counts floats.  Device resident it must be 16-byte aligned (PRESS_HIP_EARG),
- *            and floats are written to [off[r], off[r] + roundup8(n[r])) at most; what lies at or beyond out_n[r] in
- *            that range is unspecified - except that a read one of the four svb methods (svb12, svb12_zd, svb_zd,
- *            slow5_svb_zd) decodes is written as [off[r], off[r] + out_n[r]) and nothing else.  Nothing outside the
- *            rooms is written.  Host buffers receive exactly out_n[r] floats per read.  A refused read
+ *            and a decoded read is written as [off[r], off[r] + out_n[r]) and nothing else, whatever the method: no
+ *            float is ever made of a sample the call has not decoded.  Nothing outside the rooms is written.  Host
+ *            buffers receive exactly out_n[r] floats per read.  A refused read
  *            (out_n[r] = UINT32_MAX) leaves its neighbours' rooms alone; what its own room holds is unspecified, as
  *            with press_hip_depress_batch.
  *   cal      2 * nreads floats; a device pointer when device resident
@@ -440,7 +439,7 @@ int press_hip_depress_batch(int method, const uint8_t *in, const uint64_t *in_of
  * the floats are decoded into a device arena and the decoded ranges come back as press_hip_depress_batch's samples do.
  * press_hip_depress_pa_fused(method) == 1 (the four svb methods): the decode kernel converts the samples it holds in
  * registers and writes the floats itself - no int16 copy of the samples exists anywhere.  == 0: the method's decoder
- * runs unchanged into library scratch and a second kernel converts [0, roundup8(out_n[r])) of every decoded read.
+ * runs unchanged into library scratch and a second kernel converts [0, out_n[r]) of every decoded read.
  * press_hip_depress_pa_workspace_bytes: the device scratch the device-resident call keeps for a batch of this shape,
  * exact as press_hip_workspace_bytes is and never below it: for a fused method the same, for the others plus the
  * samples (total_samples * 2 + 64 bytes) and the converter's tile table.  0 for a method id out of range.
@@ -481,9 +480,9 @@ uint64_t press_hip_depress_pa_workspace_bytes(int method, uint64_t total_samples
  *   its out_n[r] decoded samples, and norm[] is written into `out`.
  *   in/in_off/in_len/off/n/total_samples/out_n   as in press_hip_depress_batch, with its checks, its room rules, its
  *            empty-read rules, PRESS_HIP_ENOTABLE and the zstd kinds' host wait
- *   out      off[] counts floats.  Device resident it must be 16-byte aligned (PRESS_HIP_EARG); floats are written to
- *            [off[r], off[r] + roundup8(n[r])) at most, what lies at or beyond out_n[r] in that range is unspecified,
- *            nothing outside the rooms is written and a refused read (out_n[r] = UINT32_MAX) gets no float at all.
+ *   out      off[] counts floats.  Device resident it must be 16-byte aligned (PRESS_HIP_EARG); a decoded read is
+ *            written as [off[r], off[r] + out_n[r]) and nothing else, nothing outside the rooms is written and a
+ *            refused read (out_n[r] = UINT32_MAX) gets no float at all.
  *            Host buffers receive exactly out_n[r] floats per read.
  *   stats    2 * nreads int32 as above ({0, 0} for an empty or refused read), or NULL
  * A bad method id or a NULL argument (stats of this call excepted) is PRESS_HIP_EARG before any device call;
@@ -781,6 +780,14 @@ void press_hip_shutdown(void);
 /* number of scratch buffers the library keeps; *bytes (may be NULL) = device bytes they hold now
  * (0 after press_hip_shutdown) */
 uint32_t press_hip_scratch_buffers(uint64_t *bytes);
+/* Diagnostic (tests; on no hot path): overwrite the library's scratch with `byte` (its low 8 bits), so that a later call
+ * shows whether any kernel reads a word that this call has not written.  One hipMemsetAsync over the whole capacity of
+ * every scratch buffer that holds memory, enqueued on the library's current stream, then - behind a synchronisation
+ * of that stream - a host memset of the two page-locked staging buffers.  Spared: the device copy of the
+ * static-Huffman table, the only scratch whose content is meant to outlive a call (it is written by the table calls
+ * and read by every shuffman_* batch).  Nothing is allocated, freed or resized: press_hip_scratch_buffers reports
+ * the same figures before and after.  PRESS_HIP_EHIP without a device. */
+int press_hip_scratch_fill(int byte);
 
 /* ======================================================================= (3) BLOW5 files (host) */
 

@@ -94,6 +94,27 @@ def test_scratch_registry_without_gpu():
     lib.press_hip_shutdown()  # harmless without a context
 
 
+def test_scratch_fill_without_gpu():
+    """the diagnostic fill needs the device like every entry point that touches scratch: PRESS_HIP_EHIP without one,
+    and the registry reports what it reported before"""
+    import ctypes
+
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    lib = press.load_library()
+    lib.press_hip_scratch_buffers.restype = ctypes.c_uint32
+    lib.press_hip_scratch_buffers.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+    before = ctypes.c_uint64(1)
+    nbuf = lib.press_hip_scratch_buffers(ctypes.byref(before))
+    assert lib.press_hip_scratch_fill(0xA5) == -3  # PRESS_HIP_EHIP
+    assert "HIP" in press.last_error() or "hip" in press.last_error()
+    with pytest.raises(press.PressError):
+        press.scratch_fill(0xA5)
+    after = ctypes.c_uint64(1)
+    assert lib.press_hip_scratch_buffers(ctypes.byref(after)) == nbuf and after.value == before.value == 0
+
+
 def test_workspace_bytes_without_gpu():
     """press_hip_workspace_bytes is the scratch plan summed (host arithmetic, no device): for every buffer the larger
     of what press and depress reserve, plus the device table for the Huffman methods.  It never shrinks when the batch

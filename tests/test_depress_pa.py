@@ -9,9 +9,8 @@ device call.  GPU: the read battery of _layouts.py through all 19 methods on sca
 samples, agreement with the two-call route, refused reads, the host path (pageable and page-locked), the scratch a
 fused method keeps, and a BLOW5 file end to end.
 
-Tail of a room, the choice the header states: a read the four svb methods decode is written as [off, off + out_n) and
-nothing else - the canary survives at [off + n, off + roundup8(n)); for the other methods those up to 7 floats are
-unspecified.
+Tail of a room, as the header states it: a decoded read is written as [off, off + out_n) and nothing else, whatever the
+method - the canary survives at [off + n, off + roundup8(n)).
 """
 import ctypes
 import json
@@ -198,8 +197,8 @@ class Case:
 
     def check(self, bits, out_n, device):
         """bits: the float arena as uint32.  out_n as the oracle's verdicts, every decoded read bit for bit, the canary
-        everywhere outside [off, off + roundup8(room)) (device) or [off, off + out_n) (host); the svb methods: and
-        behind the read's last float"""
+        everywhere outside [off, off + roundup8(room)) (device) or [off, off + out_n) (host), and behind the read's
+        last float"""
         m = self.m
         for k, (verdict, want) in enumerate(self.expect):
             tag = (m, k, int(self.rooms[k]))
@@ -214,7 +213,7 @@ class Case:
             exp = pa_bits(want, self.cal[k, 0], self.cal[k, 1])
             bad = np.nonzero(got != exp)[0]
             assert bad.size == 0, tag + ("first mismatch at", int(bad[0]), hex(int(got[bad[0]])), hex(int(exp[bad[0]])))
-            if device and m in L.SVB_KINDS:
+            if device:
                 assert (bits[o + len(want):o + L.roundup8(len(want))] == CANARY).all(), tag + ("tail of the room written",)
         if device:
             spans = [L.roundup8(r) for r in self.rooms]
