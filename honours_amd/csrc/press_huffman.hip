@@ -956,13 +956,13 @@ __device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *p, uint32_t 
 	return lo;
 }
 
-// the deltas of the 8 samples at i0 (16 bits each, two per register) with the exceptions
-// [e_first, e_first + e_cnt) merged in; samples outside [Ia, Ib) are left zero.  lowat(l) = delta of one-byte
-// value number l.
-template <typename LOWAT>
-__device__ __forceinline__ void gather8(LOWAT lowat, const uint32_t *pos, const uint32_t *val, uint32_t zd0,
-					uint32_t i0, uint32_t Ia, uint32_t Ib, uint32_t e_first, uint32_t e_cnt,
-					uint32_t v[4])
+// the deltas of the 8 samples at i0 (16 bits each, two per register) with the wave's e_cnt exceptions merged in;
+// samples outside [Ia, Ib) are left zero.  lowat(l) = delta of one-byte value number l; e_first = the read's
+// exceptions in front of the wave's; below(key) = the wave's exceptions with a position < key, posat(k) / valat(k) =
+// position / value of its exception number k < e_cnt.
+template <typename LOWAT, typename BELOW, typename POSAT, typename VALAT>
+__device__ __forceinline__ void gather8(LOWAT lowat, BELOW below, POSAT posat, VALAT valat, uint32_t zd0, uint32_t i0,
+					uint32_t Ia, uint32_t Ib, uint32_t e_first, uint32_t e_cnt, uint32_t v[4])
 {
 	v[0] = v[1] = v[2] = v[3] = 0;
 	const uint32_t lo = i0 > Ia ? i0 : Ia;
@@ -970,10 +970,9 @@ __device__ __forceinline__ void gather8(LOWAT lowat, const uint32_t *pos, const 
 	if (lo >= hi)
 		return;
 	const uint32_t uf = lo ? lo - 1 : 0;
-	const uint32_t e_end = e_first + e_cnt;
-	uint32_t e = e_first + lower_bound_u32(pos + e_first, e_cnt, uf);
-	uint32_t l = uf - e; // number of the next one-byte value
-	uint32_t nextpos = e < e_end ? pos[e] : 0xFFFFFFFFu;
+	uint32_t k = below(uf);
+	uint32_t l = uf - e_first - k; // number of the next one-byte value
+	uint32_t nextpos = k < e_cnt ? posat(k) : 0xFFFFFFFFu;
 #pragma unroll
 	for (int h = 0; h < 8; h++) {
 		const uint32_t i = i0 + h;
@@ -982,9 +981,9 @@ __device__ __forceinline__ void gather8(LOWAT lowat, const uint32_t *pos, const 
 			if (i == 0) {
 				dl = unzz16(zd0);
 			} else if (i - 1 == nextpos) {
-				dl = unzz16(val[e] & 0xFFFFu);
-				e++;
-				nextpos = e < e_end ? pos[e] : 0xFFFFFFFFu;
+				dl = unzz16(valat(k) & 0xFFFFu);
+				k++;
+				nextpos = k < e_cnt ? posat(k) : 0xFFFFFFFFu;
 			} else {
 				dl = lowat(l) & 0xFFFFu;
 				l++;
@@ -1027,17 +1026,47 @@ struct EmitPlan { // where a wave's samples lie and what they start from (wave-u
 
 // The deltas of the wave's values [L0, L1) are in the LDS staging buffer (src[l - L0]): write the samples they and
 // their exceptions make, 16 samples per lane and round (1024 per round; 8 per lane cost twice the wave scans and rounds).
-__device__ __forceinline__ void emit_samples16(const uint8_t *src, const EmitRead &R, const EmitPlan &P, uint32_t lane)
+//
+// Two copies, chosen per unit (wave-uniform).  !BIG, at most 64 exceptions: their positions are in the lanes' registers
+// (P.pe, 0xFFFFFFFF behind the last) and their values are loaded the same way, one per lane, IN FRONT of the round loop
+// and only where the unit has any; both go into the wave's own list exl[0 .. 63] / exl[64 .. 127] in LDS, which the rare
+// gather rounds search and read.  So the loop holds no vector-memory load, and no round waits for the stores of the
+// round before it: with a global load in the loop - even in a path that is not taken - the compiler puts
+// s_waitcnt vmcnt(0) into the plain path of every round, and on gfx950 stores count in vmcnt.
+// BIG, more than 64: positions and values are searched and read in global memory where needed, with those waits.
+template <bool BIG>
+__device__ __forceinline__ void emit_samples16(const uint8_t *src, uint32_t *exl_, const EmitRead &R, const EmitPlan &P,
+					       uint32_t lane)
 {
+	typedef __attribute__((address_space(3))) uint32_t *lds_u32p;
 	const uint32_t L0 = P.L0, L1 = P.L1, Ea = P.Ea, ecnt = P.ecnt, Ia = P.Ia, Ib = P.Ib, pe = P.pe;
 	uint32_t base = P.base;
+	const lds_u32p exl = (lds_u32p) exl_;
+	if (!BIG) { // (without exceptions too: the round with sample 0 is a gather round and searches the list)
+		uint32_t ve = 0;
+		if (ecnt != 0 && lane < ecnt)
+			ve = R.val[Ea + lane]; // (waited for here)
+		exl[lane] = pe;
+		exl[64 + lane] = ve;
+		wave_lds_sync();
+	}
 	auto ex_below = [&](uint32_t key) -> uint32_t { // exceptions of the wave with pos < key
-		if (ecnt == 0)
-			return 0u;
-		if (ecnt <= 64)
-			return (uint32_t) __popcll(__ballot(pe < key));
-		return uniform(lower_bound_u32(R.pos + Ea, ecnt, key));
+		if (BIG)
+			return uniform(lower_bound_u32(R.pos + Ea, ecnt, key));
+		return (uint32_t) __popcll(__ballot(pe < key));
 	};
+	// a lane's own search of the list (gather rounds only)
+	auto below = [&](uint32_t key) -> uint32_t {
+		if (BIG)
+			return lower_bound_u32(R.pos + Ea, ecnt, key);
+		uint32_t k = 0; // the list is sorted and 64 long: six steps
+#pragma unroll
+		for (uint32_t st = 32; st; st >>= 1)
+			k += exl[k + st - 1] < key ? st : 0u;
+		return k + (exl[k] < key ? 1u : 0u);
+	};
+	auto posat = [&](uint32_t k) -> uint32_t { return BIG ? R.pos[Ea + k] : exl[k]; };
+	auto valat = [&](uint32_t k) -> uint32_t { return BIG ? R.val[Ea + k] : exl[64 + k]; };
 	const bool shift = uniform(R.q) != 0;
 	const u16x2 qq = { (unsigned short) R.q, (unsigned short) R.q };
 	const uint32_t *s32 = reinterpret_cast<const uint32_t *>(src);
@@ -1072,12 +1101,8 @@ __device__ __forceinline__ void emit_samples16(const uint8_t *src, const EmitRea
 			expand8s(db, v + 4);
 		} else {
 			auto lowat = [&](uint32_t l) -> uint32_t { return (l >= L0 && l < L1) ? (uint32_t) (int32_t) (int8_t) src[l - L0] : 0u; };
-			gather8(lowat, R.pos, R.val, R.zd0, i0, Ia, Ib, Ea, ecnt, v);
-			gather8(lowat, R.pos, R.val, R.zd0, i0 + 8, Ia, Ib, Ea, ecnt, v + 4);
-			// (this rare path loads exception positions / values it may not use: with such a load possibly pending at
-			// the loop's back edge the compiler put a full vector-memory wait into the PLAIN path of every round - a
-			// wait for the previous round's sample stores.  Nothing of this path is pending behind this line.)
-			__builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
+			gather8(lowat, below, posat, valat, R.zd0, i0, Ia, Ib, Ea, ecnt, v);
+			gather8(lowat, below, posat, valat, R.zd0, i0 + 8, Ia, Ib, Ea, ecnt, v + 4);
 		}
 		const uint32_t ta = lane_prefix8(v) & 0xFFFFu;
 		const uint32_t tb = lane_prefix8(v + 4) & 0xFFFFu;
@@ -1158,6 +1183,7 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 		uint32_t img[EW][NCOL * 64];
 		uint32_t pad_row[2 * 64];
 		alignas(16) EmitStg stg_all;
+		uint32_t exl[EW][128]; // a wave's exceptions, at most 64: positions, values (emit_samples16)
 	};
 	__shared__ __attribute__((aligned(16))) Lds lds;
 	auto &lut = lds.lut;
@@ -1195,6 +1221,7 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 	}
 	uint32_t *col = img[wv] + lane;
 	uint8_t *stg = stg_all.s[wv];
+	uint32_t *exl = lds.exl[wv];
 	__syncthreads(); // the tables; from here on every wave is on its own: columns and staging are private, and
 	                 // what the other waves of its tile hold in front of it comes with the unit's plan
 	// persistent workgroups: the tables are loaded once.
@@ -1369,7 +1396,12 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 #if defined(EMIT_ABL) && EMIT_ABL == 2
 					if (a.nreads == 0x7FFFFFFFu)
 #endif
-					emit_samples16(stg, R, P, lane);
+					{
+						if (U.ecnt <= 64)
+							emit_samples16<false>(stg, exl, R, P, lane);
+						else
+							emit_samples16<true>(stg, exl, R, P, lane);
+					}
 					HSTAMP(5); // samples
 				}
 			} else {
