@@ -581,6 +581,17 @@ extern "C" int press_hip_signal_stats_timed(const int16_t *sig, const uint64_t *
 // which is fine in sequence - except for a fused pair (recode_fused), where the svb decode kernel writes the press half's
 // chunk descriptors while it reads its own: that press has a table, a first-chunk list and a control block to itself.
 
+// press_hip_recode_degraded_*, a pair that is not fused: D_bits in place over the out_n[r] samples the decode half has left
+// (the zstd kinds' host fallback lies inside launch_depress: it is behind us), before the press half reads them.  A fused
+// pair's decode kernel degrades the samples it holds (launch_recode_fused).
+static void recode_degrade(const RecodePlan &rp, const DecodeArgs &da, hipStream_t s)
+{
+	if (!rp.bits)
+		return;
+	launch_pa_tiles(da, (uint2 *) g.pa_tile.p, (uint32_t *) g.pa_ctl.p, s);
+	launch_degrade(da, da.sig, rp.bits, (const uint2 *) g.pa_tile.p, (const uint32_t *) g.pa_ctl.p, s);
+}
+
 static int launch_recode(const RecodePlan &rp, DecodeArgs &da, BatchArgs &pa, hipStream_t s)
 {
 	int rc;
@@ -592,11 +603,12 @@ static int launch_recode(const RecodePlan &rp, DecodeArgs &da, BatchArgs &pa, hi
 		pa.chunks = (ChunkDesc *) g.pchunks.p;
 		pa.first_chunk = (uint32_t *) g.pfirst.p;
 		pa.ctl = (ChunkCtl *) g.pctl.p;
-		launch_recode_fused(da, pa, sm.key2, sm.slow5, dm.exfmt, dm.ent, s);
+		launch_recode_fused(da, pa, sm.key2, sm.slow5, dm.exfmt, dm.ent, s, rp.bits);
 	} else {
 		if ((rc = launch_depress(rp.d, da, s)))
 			return rc;
 		launch_recode_counts(da.out_n, (uint32_t *) g.rn.p, da.nreads, s);
+		recode_degrade(rp, da, s);
 		if (rp.keep_heads)
 			launch_recode_refused(da.out_n, pa, (uint8_t *) g.rkeep.p, true, s);
 		if ((rc = launch_press(rp.p, pa, s)))
@@ -639,20 +651,29 @@ static int recode_fetch_decoded(Staged &st, const StreamsIn &host, bool last)
 	return 0;
 }
 
-extern "C" int press_hip_recode_batch(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
-				      const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
-				      uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
-				      int16_t *sig, uint32_t *out_n, int device_resident)
+static int bits_ok(uint32_t bits)
+{
+	return bits > 8 ? set_error(PRESS_HIP_EARG, "bits = %u: 0 .. 8 low bits can be dropped", bits) : 0;
+}
+
+// press_hip_recode_batch (bits == 0) and press_hip_recode_degraded_batch
+static int recode_batch(int src_method, int dst_method, uint32_t bits, const uint8_t *in, const uint64_t *in_off,
+			const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+			uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+			int16_t *sig, uint32_t *out_n, int device_resident)
 {
 	API_LOCK;
-	int rc = args_ok(src_method, dst_method, nreads && (!in || !in_off || !in_len || !n || !off || !out || !out_off || !out_len || !out_n),
+	int rc = bits_ok(bits);
+	if (rc)
+		return rc;
+	rc = args_ok(src_method, dst_method, nreads && (!in || !in_off || !in_len || !n || !off || !out || !out_off || !out_len || !out_n),
 			 nreads, device_resident ? sig : nullptr, "sig");
 	if (rc || (rc = device_ready(src_method, dst_method)))
 		return rc;
 	if (nreads == 0)
 		return 0;
 	hipStream_t s = g.stream();
-	const RecodePlan rp = make_recode_plan(src_method, dst_method, total_samples, nreads, sig != nullptr);
+	const RecodePlan rp = make_recode_plan(src_method, dst_method, total_samples, nreads, sig != nullptr, bits);
 	const StreamsIn host = { in, in_off, in_len, off, n, out_n, sig };
 	const SlotsOut slots = { out, out_off, out_len };
 	SlotsOut so = slots;
@@ -668,6 +689,24 @@ extern "C" int press_hip_recode_batch(int src_method, int dst_method, const uint
 	if ((rc = launch_recode(rp, da, pa, s)) || device_resident || (rc = recode_fetch_decoded(st, host, false)))
 		return rc;
 	return st.fetch_streams(slots);
+}
+
+extern "C" int press_hip_recode_batch(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
+				      const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+				      uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+				      int16_t *sig, uint32_t *out_n, int device_resident)
+{
+	return recode_batch(src_method, dst_method, 0, in, in_off, in_len, n, off, nreads, total_samples, out, out_off, out_len, sig, out_n,
+			    device_resident);
+}
+
+extern "C" int press_hip_recode_degraded_batch(int src_method, int dst_method, uint32_t bits, const uint8_t *in, const uint64_t *in_off,
+					       const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+					       uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+					       int16_t *sig, uint32_t *out_n, int device_resident)
+{
+	return recode_batch(src_method, dst_method, bits, in, in_off, in_len, n, off, nreads, total_samples, out, out_off, out_len, sig,
+			    out_n, device_resident);
 }
 
 // ------------------------------------------------------------------ packed recode: streams in, a library-made arena out
@@ -690,12 +729,13 @@ static int launch_recode_packed(const RecodePlan &rp, DecodeArgs &da, BatchArgs 
 		pa.chunks = (ChunkDesc *) g.pchunks.p;
 		pa.first_chunk = (uint32_t *) g.pfirst.p;
 		pa.ctl = (ChunkCtl *) g.pctl.p;
-		launch_recode_fused_packed(da, pa, sm.key2, sm.slow5, dm.exfmt, dm.ent, pk, phases, s);
+		launch_recode_fused_packed(da, pa, sm.key2, sm.slow5, dm.exfmt, dm.ent, pk, phases, s, rp.bits);
 	} else {
 		if (phases & PACK_SIZE) {
 			if ((rc = launch_depress(rp.d, da, s)))
 				return rc;
 			launch_recode_counts(da.out_n, (uint32_t *) g.rn.p, da.nreads, s);
+			recode_degrade(rp, da, s);
 			PackArgs sz = pk;
 			sz.layout = nullptr; // (the scan comes behind the refused reads' correction)
 			if ((rc = launch_press_packed(rp.p, pa, sz, PACK_SIZE, s)))
@@ -712,19 +752,22 @@ static int launch_recode_packed(const RecodePlan &rp, DecodeArgs &da, BatchArgs 
 	return launch_status();
 }
 
-extern "C" int press_hip_recode_sizes(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
-				      const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
-				      uint64_t total_samples, uint64_t *need, int16_t *sig, uint32_t *out_n, int device_resident)
+static int recode_sizes(int src_method, int dst_method, uint32_t bits, const uint8_t *in, const uint64_t *in_off,
+			const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+			uint64_t total_samples, uint64_t *need, int16_t *sig, uint32_t *out_n, int device_resident)
 {
 	API_LOCK;
-	int rc = args_ok(src_method, dst_method, nreads && (!in || !in_off || !in_len || !n || !off || !need || !out_n), nreads,
+	int rc = bits_ok(bits);
+	if (rc)
+		return rc;
+	rc = args_ok(src_method, dst_method, nreads && (!in || !in_off || !in_len || !n || !off || !need || !out_n), nreads,
 			 device_resident ? sig : nullptr, "sig");
 	if (rc || (rc = device_ready(src_method, dst_method)))
 		return rc;
 	if (nreads == 0)
 		return 0;
 	hipStream_t s = g.stream();
-	const RecodePlan rp = make_recode_packed_plan(src_method, dst_method, total_samples, nreads, sig != nullptr);
+	const RecodePlan rp = make_recode_packed_plan(src_method, dst_method, total_samples, nreads, sig != nullptr, bits);
 	const StreamsIn host = { in, in_off, in_len, off, n, out_n, sig };
 	Staged st(nreads, s);
 	DecodeArgs da;
@@ -739,13 +782,31 @@ extern "C" int press_hip_recode_sizes(int src_method, int dst_method, const uint
 	return recode_fetch_decoded(st, host, true);
 }
 
-extern "C" int press_hip_recode_packed(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
-				       const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
-				       uint64_t total_samples, uint8_t *out, uint64_t out_cap, uint32_t align, uint64_t *out_off,
-				       uint64_t *out_len, int16_t *sig, uint32_t *out_n, int device_resident)
+extern "C" int press_hip_recode_sizes(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
+				      const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+				      uint64_t total_samples, uint64_t *need, int16_t *sig, uint32_t *out_n, int device_resident)
+{
+	return recode_sizes(src_method, dst_method, 0, in, in_off, in_len, n, off, nreads, total_samples, need, sig, out_n, device_resident);
+}
+
+extern "C" int press_hip_recode_degraded_sizes(int src_method, int dst_method, uint32_t bits, const uint8_t *in, const uint64_t *in_off,
+					       const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+					       uint64_t total_samples, uint64_t *need, int16_t *sig, uint32_t *out_n, int device_resident)
+{
+	return recode_sizes(src_method, dst_method, bits, in, in_off, in_len, n, off, nreads, total_samples, need, sig, out_n,
+			    device_resident);
+}
+
+static int recode_packed(int src_method, int dst_method, uint32_t bits, const uint8_t *in, const uint64_t *in_off,
+			 const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+			 uint64_t total_samples, uint8_t *out, uint64_t out_cap, uint32_t align, uint64_t *out_off,
+			 uint64_t *out_len, int16_t *sig, uint32_t *out_n, int device_resident)
 {
 	API_LOCK;
-	int rc = args_ok(src_method, dst_method,
+	int rc = bits_ok(bits);
+	if (rc)
+		return rc;
+	rc = args_ok(src_method, dst_method,
 			 !out_off || (nreads && (!in || !in_off || !in_len || !n || !off || !out_len || !out_n || (!out && out_cap))), nreads,
 			 device_resident ? sig : nullptr, "sig");
 	if (rc || (rc = align_ok(align)) || (rc = device_ready(src_method, dst_method)))
@@ -753,7 +814,7 @@ extern "C" int press_hip_recode_packed(int src_method, int dst_method, const uin
 	if (nreads == 0)
 		return packed_empty(out_off, device_resident);
 	hipStream_t s = g.stream();
-	const RecodePlan rp = make_recode_packed_plan(src_method, dst_method, total_samples, nreads, sig != nullptr);
+	const RecodePlan rp = make_recode_packed_plan(src_method, dst_method, total_samples, nreads, sig != nullptr, bits);
 	const StreamsIn host = { in, in_off, in_len, off, n, out_n, sig };
 	Staged st(nreads, s);
 	DecodeArgs da;
@@ -776,6 +837,66 @@ extern "C" int press_hip_recode_packed(int src_method, int dst_method, const uin
 	if ((rc = packed_tail(st, out, out_cap, out_off, out_len, pa, pk, [&] { return launch_recode_packed(rp, da, pa, pk, PACK_WRITE, s); })))
 		return rc;
 	return recode_fetch_decoded(st, host, true);
+}
+
+extern "C" int press_hip_recode_packed(int src_method, int dst_method, const uint8_t *in, const uint64_t *in_off,
+				       const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+				       uint64_t total_samples, uint8_t *out, uint64_t out_cap, uint32_t align, uint64_t *out_off,
+				       uint64_t *out_len, int16_t *sig, uint32_t *out_n, int device_resident)
+{
+	return recode_packed(src_method, dst_method, 0, in, in_off, in_len, n, off, nreads, total_samples, out, out_cap, align, out_off,
+			     out_len, sig, out_n, device_resident);
+}
+
+extern "C" int press_hip_recode_degraded_packed(int src_method, int dst_method, uint32_t bits, const uint8_t *in, const uint64_t *in_off,
+						const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+						uint64_t total_samples, uint8_t *out, uint64_t out_cap, uint32_t align, uint64_t *out_off,
+						uint64_t *out_len, int16_t *sig, uint32_t *out_n, int device_resident)
+{
+	return recode_packed(src_method, dst_method, bits, in, in_off, in_len, n, off, nreads, total_samples, out, out_cap, align, out_off,
+			     out_len, sig, out_n, device_resident);
+}
+
+// ------------------------------------------------------------------ degrade: D_b of samples that are already there
+//
+// press_hip_signal_stats' layout, staging and tile table; the kernel of press_degrade.hip.  Host pointers: the samples are
+// staged, degraded in place there, and exactly n[r] samples per read come back into `out`.
+
+extern "C" int press_hip_degrade_batch(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				       uint64_t total_samples, uint32_t bits, int16_t *out, int device_resident)
+{
+	API_LOCK;
+	int rc = bits_ok(bits);
+	if (rc || (rc = args_ok(NONE, NONE, nreads && (!sig || !off || !n || !out), nreads, device_resident ? sig : nullptr, "sig")) ||
+	    (rc = args_ok(NONE, NONE, false, nreads, device_resident ? out : nullptr, "out")) || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	DecodeArgs a{};
+	a.nreads = nreads;
+	a.max_chunks = (uint32_t) (total_samples / CHUNK + nreads + 1); // (as ScratchPlan::max_chunks)
+	if (g.pa_tile.reserve((size_t) a.max_chunks * sizeof(uint2)) || g.pa_ctl.reserve(64))
+		return PRESS_HIP_EHIP;
+	SamplesIn in = { sig, off, n };
+	int16_t *dst = out;
+	Staged st(nreads, s);
+	if (!device_resident) {
+		if (g.outn.reserve((size_t) nreads * 4))
+			return PRESS_HIP_EHIP;
+		if ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in)))
+			return rc;
+		dst = (int16_t *) g.sig.p;
+		HIPCHK(hipMemcpyAsync(g.outn.p, g.nsamp.p, (size_t) nreads * 4, hipMemcpyDeviceToDevice, s)); // (fetch_elems' counts)
+	}
+	bind_io(a, in);
+	launch_pa_tiles(a, (uint2 *) g.pa_tile.p, (uint32_t *) g.pa_ctl.p, s);
+	if (bits || dst != in.sig) // (D_0 is the identity: out of place the reads' samples as they are, in place nothing)
+		launch_degrade(a, dst, bits, (const uint2 *) g.pa_tile.p, (const uint32_t *) g.pa_ctl.p, s);
+	if ((rc = launch_status()) || device_resident)
+		return rc;
+	std::vector<uint32_t> got(nreads);
+	return st.fetch_elems(out, g.sig.p, sizeof(int16_t), StreamsIn{ nullptr, nullptr, nullptr, off, n, got.data(), out });
 }
 
 // ------------------------------------------------------------------ verify: the digest of samples, of decoded streams; decode and compare
@@ -842,13 +963,17 @@ extern "C" int press_hip_depress_crc_batch(int method, const uint8_t *in, const 
 	return 0;
 }
 
-extern "C" int press_hip_verify_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
-				      uint32_t nreads, const int16_t *sig, const uint64_t *off, const uint32_t *n,
-				      uint64_t total_samples, uint32_t *first_bad, uint32_t *out_n, uint32_t *nbad,
-				      int device_resident)
+// press_hip_verify_batch (bits == 0) and press_hip_verify_degraded_batch
+static int verify_batch(int method, uint32_t bits, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+			uint32_t nreads, const int16_t *sig, const uint64_t *off, const uint32_t *n,
+			uint64_t total_samples, uint32_t *first_bad, uint32_t *out_n, uint32_t *nbad,
+			int device_resident)
 {
 	API_LOCK;
-	int rc = args_ok(method, NONE, !nbad || (nreads && (!in || !in_off || !in_len || !sig || !off || !n || !first_bad || !out_n)), nreads,
+	int rc = bits_ok(bits);
+	if (rc)
+		return rc;
+	rc = args_ok(method, NONE, !nbad || (nreads && (!in || !in_off || !in_len || !sig || !off || !n || !first_bad || !out_n)), nreads,
 			 device_resident ? sig : nullptr, "sig");
 	if (rc || (rc = device_ready(method, NONE)))
 		return rc;
@@ -877,11 +1002,27 @@ extern "C" int press_hip_verify_batch(int method, const uint8_t *in, const uint6
 	}
 	io.sig = (int16_t *) plan.ptr(&Ctx::rsig); // the decode goes to the library's samples
 	bind_io(a, io);
-	if ((rc = launch_verify(plan, a, want.sig, fb, nb, s)) || device_resident)
+	if ((rc = launch_verify(plan, a, want.sig, fb, nb, s, bits)) || device_resident)
 		return rc;
 	HIPCHK(hipMemcpyAsync(first_bad, fb, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipMemcpyAsync(nbad, nb, 4, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	return 0;
+}
+
+extern "C" int press_hip_verify_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+				      uint32_t nreads, const int16_t *sig, const uint64_t *off, const uint32_t *n,
+				      uint64_t total_samples, uint32_t *first_bad, uint32_t *out_n, uint32_t *nbad,
+				      int device_resident)
+{
+	return verify_batch(method, 0, in, in_off, in_len, nreads, sig, off, n, total_samples, first_bad, out_n, nbad, device_resident);
+}
+
+extern "C" int press_hip_verify_degraded_batch(int method, uint32_t bits, const uint8_t *in, const uint64_t *in_off,
+					       const uint64_t *in_len, uint32_t nreads, const int16_t *sig, const uint64_t *off,
+					       const uint32_t *n, uint64_t total_samples, uint32_t *first_bad, uint32_t *out_n,
+					       uint32_t *nbad, int device_resident)
+{
+	return verify_batch(method, bits, in, in_off, in_len, nreads, sig, off, n, total_samples, first_bad, out_n, nbad, device_resident);
 }

@@ -893,12 +893,22 @@ __device__ __forceinline__ void wave_lds_sync()
 // picoamperes with the read's two calibration floats (f.cal, loaded once per workgroup) and writes them to f.pa as two
 // 16-byte stores; the ragged tail writes its floats one by one and none at or beyond n.  a.sig is not used: no int16
 // copy of the samples is made.
+//
+// DEG (press_hip_recode_degraded_*, with FUSE): the samples are rounded to multiples of 2^b (D_b, degrade_pair: two
+// packed 16-bit operations a pair) behind the inverse scan and in front of the store and of the counts, so the stream
+// keeps what the press half will read and pass A's results describe the DEGRADED read.  The zig-zag deltas of the
+// degraded samples are no longer the stream's: the lane takes them again from its eight degraded samples and the degraded
+// value in front of them - the base b16 the scan has just added, which IS the sample in front of the lane (0 in front of
+// a read's first) - and a plain sub-tile, whose stream bytes hold no exception, may well hold one afterwards (a step of
+// 127 becomes one of up to 127 + 2^b): under DEG the plain sub-tiles count as the others do.  A compile-time variant:
+// the instantiations without DEG are what they were.
 __device__ __forceinline__ uint32_t exc_mask(const uint4 &z, uint32_t i0);
 __device__ __forceinline__ uint32_t low_mask(const uint4 &z, uint32_t i0, uint32_t n);
-template <bool KEY2, bool ZD, bool S5 = false, int FUSE = 0, typename OUT = int16_t>
+template <bool KEY2, bool ZD, bool S5 = false, int FUSE = 0, typename OUT = int16_t, bool DEG = false>
 __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a, FuseArgs f)
 {
 	static_assert(!FUSE || ZD, "the fused counts are those of the zig-zag delta methods");
+	static_assert(!DEG || FUSE, "D_b is applied where the samples go on to a press in the same call");
 	constexpr bool PA = sizeof(OUT) == sizeof(float);
 	static_assert(!PA || !FUSE, "one second consumer at a time");
 #ifdef DEC_STAMPS
@@ -1102,6 +1112,7 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a, FuseAr
 		if ((plain >> k) & 1u) { // uniform; plain sub-tiles hold only complete lanes
 			uint32_t v[4];
 			expand8(dat[k], v);
+			uint32_t front = 0; // DEG: the sample in front of the lane's eight
 			if (ZD) {
 #pragma unroll
 				for (int q = 0; q < 4; q++)
@@ -1112,6 +1123,16 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a, FuseAr
 #pragma unroll
 				for (int q = 0; q < 4; q++)
 					v[q] = pk_add16(v[q], b2);
+				if (DEG)
+					front = b16;
+			}
+			uint4 z = make_uint4(0, 0, 0, 0);
+			if constexpr (DEG) { // D_b of the samples, and the zig-zag deltas of what is left
+				const uint32_t fd = degrade_pair(front, f.deg_h2, f.deg_m2) << 16;
+#pragma unroll
+				for (int q = 0; q < 4; q++)
+					v[q] = degrade_pair(v[q], f.deg_h2, f.deg_m2);
+				z = make_uint4(zd_pair(v[0], fd), zd_pair(v[1], v[0]), zd_pair(v[2], v[1]), zd_pair(v[3], v[2]));
 			}
 			if (i0 < n) {
 				if constexpr (PA)
@@ -1119,7 +1140,35 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a, FuseAr
 				else
 					st16_stream(out + i0, make_uint4(v[0], v[1], v[2], v[3]));
 			}
-			if (FUSE && i0 < n) { // one-byte values only: no exception; their code lengths straight from the stream's bytes
+			if constexpr (DEG) { // the counts of a sub-tile that is not plain (below): the degraded values may hold exceptions
+				const uint32_t nv = i0 + 8 <= n ? 8u : (i0 < n ? n - i0 : 0u);
+				if (k == 0)
+					f_s0 = v[0];
+#pragma unroll
+				for (int h = 0; h < 4; h++)
+					f_ored |= nv >= (uint32_t) (2 * h + 2) ? v[h] : nv == (uint32_t) (2 * h + 1) ? (v[h] & 0xFFFFu) : 0u;
+				if (nv < 8) { // (a plain sub-tile holds complete lanes; zeros at or beyond n all the same)
+					const uint32_t zz[4] = { z.x, z.y, z.z, z.w };
+					uint32_t zc[4];
+#pragma unroll
+					for (uint32_t h = 0; h < 4; h++)
+						zc[h] = nv >= 2 * h + 2 ? zz[h] : nv == 2 * h + 1 ? (zz[h] & 0xFFFFu) : 0u;
+					z = make_uint4(zc[0], zc[1], zc[2], zc[3]);
+				}
+				const uint32_t em = exc_mask(z, i0);
+				if (__ballot(em != 0)) {
+					f_kmask |= 1u << k;
+					const uint32_t inc = wave_incl_scan_dpp(__popc(em));
+					f_etot += (uint32_t) __builtin_amdgcn_readlane((int) inc, 63);
+				}
+				if (FUSE == 2) {
+					const uint32_t zz[4] = { z.x, z.y, z.z, z.w };
+					const uint32_t lowm = low_mask(z, i0, n);
+#pragma unroll
+					for (int h = 0; h < 8; h++)
+						f_bits += s_len[((lowm >> h) & 1u) ? ((zz[h >> 1] >> (16 * (h & 1))) & 0xFFu) : 256u];
+				}
+			} else if (FUSE && i0 < n) { // one-byte values only: no exception; their code lengths straight from the stream's bytes
 				f_ored |= v[0] | v[1] | v[2] | v[3];
 				if (k == 0)
 					f_s0 = v[0];
@@ -1155,6 +1204,13 @@ __global__ __launch_bounds__(CWG) void k_svb_decode_chunked(DecodeArgs a, FuseAr
 #pragma unroll
 			for (int q = 0; q < 4; q++)
 				v[q] = pk_add16(v[q], b2);
+			if constexpr (DEG) { // D_b, and zd again from the degraded samples (those at or beyond n repeat the last: zeros)
+				const uint32_t fd = degrade_pair(b16, f.deg_h2, f.deg_m2) << 16;
+#pragma unroll
+				for (int q = 0; q < 4; q++)
+					v[q] = degrade_pair(v[q], f.deg_h2, f.deg_m2);
+				z = make_uint4(zd_pair(v[0], fd), zd_pair(v[1], v[0]), zd_pair(v[2], v[1]), zd_pair(v[3], v[2]));
+			}
 			if (FUSE) {
 				const uint32_t nv = i0 + 8 <= n ? 8u : (i0 < n ? n - i0 : 0u);
 				if (k == 0)
@@ -2430,7 +2486,7 @@ void launch_ex_encode_packed(const BatchArgs &a, int fmt, int ent, const PackArg
 // runs, k_svb_keyprefix gives them.  d.sig == p.sig, d.off == p.off; the two sides have a chunk table, a first-chunk list
 // and a control block each.
 template <bool KEY2, bool S5>
-static void run_recode(const DecodeArgs &d, const BatchArgs &p, int fmt, int ent, hipStream_t s)
+static void run_recode(const DecodeArgs &d, const BatchArgs &p, int fmt, int ent, uint32_t bits, hipStream_t s)
 {
 	(void) hipMemsetAsync(d.ctl, 0, sizeof(ChunkCtl), s);
 	hipLaunchKernelGGL((k_chunk_prep<true, KEY2>), dim3((d.nreads + 255) / 256), dim3(256), 0, s, d.off,
@@ -2441,9 +2497,13 @@ static void run_recode(const DecodeArgs &d, const BatchArgs &p, int fmt, int ent
 	hipLaunchKernelGGL((k_svb_keyprefix<KEY2, S5>), dim3((d.nreads + 3) / 4), dim3(256), 0, s, d);
 	launch_recode_counts(d.out_n, const_cast<uint32_t *>(p.nsamp), d.nreads, s);
 	ex_encode_prep(p, s);
-	const FuseArgs f = { p.chunks, p.first_chunk, p.cbits, p.meta, p.huff, nullptr, nullptr };
+	const FuseArgs f = { p.chunks, p.first_chunk, p.cbits, p.meta, p.huff, nullptr, nullptr, degrade_h2(bits), degrade_m2(bits) };
 	ktime_begin(1, s);
-	if (ent == 1)
+	if (bits && ent == 1)
+		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 2, int16_t, true>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
+	else if (bits)
+		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 1, int16_t, true>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
+	else if (ent == 1)
 		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 2>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
 	else
 		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 1>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
@@ -2451,16 +2511,16 @@ static void run_recode(const DecodeArgs &d, const BatchArgs &p, int fmt, int ent
 	ex_encode_tail(p, fmt, ent, s);
 }
 
-void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent, hipStream_t s)
+void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent, hipStream_t s, uint32_t bits)
 {
 	if (!d.nreads || !d.max_chunks)
 		return;
 	if (slow5)
-		run_recode<true, true>(d, p, fmt, ent, s);
+		run_recode<true, true>(d, p, fmt, ent, bits, s);
 	else if (key2bit)
-		run_recode<true, false>(d, p, fmt, ent, s);
+		run_recode<true, false>(d, p, fmt, ent, bits, s);
 	else
-		run_recode<false, false>(d, p, fmt, ent, s);
+		run_recode<false, false>(d, p, fmt, ent, bits, s);
 }
 
 // Packed recode, fused: run_recode with the press half cut where launch_ex_encode_packed cuts it.  PACK_SIZE: the slot
@@ -2468,7 +2528,7 @@ void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, 
 // their size, the scan lays the arena out and the PRESS half's chunk table (p.chunks / p.first_chunk) learns the bases.
 // PACK_WRITE: the section and the encoder as they are.  Pass A stays skipped.
 template <bool KEY2, bool S5>
-static void run_recode_packed(const DecodeArgs &d, const BatchArgs &p, int fmt, int ent, const PackArgs &pk, hipStream_t s)
+static void run_recode_packed(const DecodeArgs &d, const BatchArgs &p, int fmt, int ent, const PackArgs &pk, uint32_t bits, hipStream_t s)
 {
 	(void) hipMemsetAsync(d.ctl, 0, sizeof(ChunkCtl), s);
 	hipLaunchKernelGGL((k_chunk_prep<true, KEY2>), dim3((d.nreads + 255) / 256), dim3(256), 0, s, d.off,
@@ -2480,9 +2540,13 @@ static void run_recode_packed(const DecodeArgs &d, const BatchArgs &p, int fmt, 
 	launch_recode_counts(d.out_n, const_cast<uint32_t *>(p.nsamp), d.nreads, s);
 	(void) hipMemsetAsync(pk.slot, 0, ((size_t) p.nreads + 1) * 8, s);
 	ex_encode_prep(p, s);
-	const FuseArgs f = { p.chunks, p.first_chunk, p.cbits, p.meta, p.huff, nullptr, nullptr };
+	const FuseArgs f = { p.chunks, p.first_chunk, p.cbits, p.meta, p.huff, nullptr, nullptr, degrade_h2(bits), degrade_m2(bits) };
 	ktime_begin(1, s);
-	if (ent == 1)
+	if (bits && ent == 1)
+		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 2, int16_t, true>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
+	else if (bits)
+		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 1, int16_t, true>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
+	else if (ent == 1)
 		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 2>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
 	else
 		hipLaunchKernelGGL((k_svb_decode_chunked<KEY2, true, S5, 1>), dim3(d.max_chunks), dim3(CWG), 0, s, d, f);
@@ -2495,17 +2559,17 @@ static void run_recode_packed(const DecodeArgs &d, const BatchArgs &p, int fmt, 
 }
 
 void launch_recode_fused_packed(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent,
-				const PackArgs &pk, int phases, hipStream_t s)
+				const PackArgs &pk, int phases, hipStream_t s, uint32_t bits)
 {
 	if (!d.nreads || !d.max_chunks)
 		return;
 	if (phases & PACK_SIZE) {
 		if (slow5)
-			run_recode_packed<true, true>(d, p, fmt, ent, pk, s);
+			run_recode_packed<true, true>(d, p, fmt, ent, pk, bits, s);
 		else if (key2bit)
-			run_recode_packed<true, false>(d, p, fmt, ent, pk, s);
+			run_recode_packed<true, false>(d, p, fmt, ent, pk, bits, s);
 		else
-			run_recode_packed<false, false>(d, p, fmt, ent, pk, s);
+			run_recode_packed<false, false>(d, p, fmt, ent, pk, bits, s);
 	}
 	if (phases & PACK_WRITE)
 		ex_encode_streams(p, fmt, ent, s);

@@ -249,14 +249,16 @@ ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool 
 struct RecodePlan {
 	ScratchPlan d, p, all;
 	bool fused;      // pass A's results come from the svb decode kernel (recode_fused)
+	uint32_t bits;   // press_hip_recode_degraded_*: D_bits (0: none) - fused: in the decode kernel; else between the
+	                 // halves, over the tile table in `all`
 	bool keep_heads; // dst writes a stream for an empty read: a refused read's slot head is kept aside
 };
 bool recode_fused(int src, int dst);
-RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples);
+RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples, uint32_t bits = 0);
 
 // press_hip_recode_sizes / press_hip_recode_packed: the recode plan and the two per-read tables of PackArgs (the slot heads
 // of keep_heads stay in the plan and unused: a refused read of the packed form has no slot)
-RecodePlan make_recode_packed_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples);
+RecodePlan make_recode_packed_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples, uint32_t bits = 0);
 
 // press_hip_depress_pa_batch: the decode plan of the method; unless the method is fused (depress_pa_fused) the samples and
 // the converter's tile table; host pointers: the staged calibration and the float arena
@@ -304,7 +306,9 @@ int launch_depress_chunks(const ScratchPlan &p, const DecodeArgs &a, const Chunk
 // launch_verify: a.sig the samples' scratch; sig: the samples the streams are meant to hold, at a.off[]
 int launch_signal_crc(const ScratchPlan &p, const DecodeArgs &a, uint32_t *crc, hipStream_t s);
 int launch_depress_crc(const ScratchPlan &p, const DecodeArgs &a, uint32_t *crc, hipStream_t s);
-int launch_verify(const ScratchPlan &p, const DecodeArgs &a, const int16_t *sig, uint32_t *first_bad, uint32_t *nbad, hipStream_t s);
+// bits > 0: against D_bits of sig (press_hip_verify_degraded_batch)
+int launch_verify(const ScratchPlan &p, const DecodeArgs &a, const int16_t *sig, uint32_t *first_bad, uint32_t *nbad, hipStream_t s,
+		  uint32_t bits = 0);
 bool scale_rule_ok(const press_hip_scale_rule *rule); // ranks and floats as include/press_hip.h asks
 uint64_t chunk_rows_of(uint32_t c, uint32_t T, uint32_t S); // rows of a read of c samples in press_hip_chunk_plan, S = T - overlap
 // phases: PACK_SIZE | PACK_WRITE (press_internal.h); a.out_off must be pk.slot

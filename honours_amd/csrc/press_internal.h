@@ -327,12 +327,16 @@ struct FuseArgs {
 	// k_svb_decode_chunked<.., float> (press_hip_depress_pa_batch): the float arena at the caller's off[], two floats per read
 	float *pa;
 	const float *cal;
+	// k_svb_decode_chunked<.., DEG> (press_hip_recode_degraded_*): degrade_pair's two constants
+	uint32_t deg_h2, deg_m2;
 };
 constexpr uint32_t RECODE_KEEP = 64; // bytes of a refused read's slot kept aside (an empty read's stream is 4 / 16 bytes)
-void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent, hipStream_t s);
+// bits > 0: the decode kernel applies D_bits to the samples it holds, and pass A's results are those of the degraded read
+void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent, hipStream_t s,
+			 uint32_t bits = 0);
 // the packed form (press_hip_recode_sizes / press_hip_recode_packed): phases as launch_ex_encode_packed, p.out_off == pk.slot
 void launch_recode_fused_packed(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent,
-				 const PackArgs &pk, int phases, hipStream_t s);
+				 const PackArgs &pk, int phases, hipStream_t s, uint32_t bits = 0);
 void launch_recode_counts(const uint32_t *out_n, uint32_t *n, uint32_t nreads, hipStream_t s);
 void launch_recode_refused(const uint32_t *out_n, const BatchArgs &p, uint8_t *keep, bool save, hipStream_t s);
 
@@ -380,8 +384,12 @@ void launch_chunk_rows(const DecodeArgs &a, const float *cal, const uint64_t *ro
 void launch_crc(const DecodeArgs &a, const uint2 *tiles, const uint32_t *ntiles, uint32_t *raw, uint32_t *crc, hipStream_t s);
 // first_bad[r] of the samples at a.sig + a.off[r] against those at sig + a.off[r] (include/press_hip.h,
 // press_hip_verify_batch); *nbad = the reads that are not verified
+// bits > 0 (press_hip_verify_degraded_batch): against D_bits of those samples, taken in registers
 void launch_verify_cmp(const DecodeArgs &a, const int16_t *sig, const uint2 *tiles, const uint32_t *ntiles, uint32_t *first_bad,
-		       uint32_t *nbad, hipStream_t s);
+		       uint32_t *nbad, hipStream_t s, uint32_t bits = 0);
+// press_degrade.hip, over the same table: out[a.off[r] + i] = D_bits(a.sig[a.off[r] + i]) for i < a.out_n[r], bits in
+// 0 .. 8 (0: a copy); out == a.sig is fine
+void launch_degrade(const DecodeArgs &a, int16_t *out, uint32_t bits, const uint2 *tiles, const uint32_t *ntiles, hipStream_t s);
 void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip

@@ -213,12 +213,15 @@ bool recode_fused(int src, int dst)
 	return METHODS[src].family == FAM_SVB && METHODS[src].zd && METHODS[dst].family == FAM_EX;
 }
 
-RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples)
+// bits > 0 (press_hip_recode_degraded_*): a fused pair's decode kernel degrades the samples it holds and the plan is that
+// of bits == 0; every other pair runs the degrade kernel between its halves, over a tile table of the rooms
+RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples, uint32_t bits)
 {
 	RecodePlan r{};
 	r.d = make_plan(src, total_samples, nreads, true);
 	r.p = make_plan(dst, total_samples, nreads, false);
 	r.fused = recode_fused(src, dst);
+	r.bits = bits;
 	const Method &m = METHODS[dst];
 	r.keep_heads = (m.family == FAM_SVB && m.slow5) || (m.family == FAM_ZSTD && m.kdiv);
 	r.all = r.d;
@@ -232,12 +235,14 @@ RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t n
 	if (r.fused)
 		r.all.need(&Ctx::pchunks, (size_t) r.p.max_chunks * sizeof(ChunkDesc)).need(&Ctx::pfirst, nr * 4)
 			.need(&Ctx::pctl, 2 * sizeof(ChunkCtl));
+	if (bits && !r.fused)
+		r.all.need(&Ctx::pa_tile, (size_t) r.d.max_chunks * sizeof(uint2)).need(&Ctx::pa_ctl, 64);
 	return r;
 }
 
-RecodePlan make_recode_packed_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples)
+RecodePlan make_recode_packed_plan(int src, int dst, uint64_t total_samples, uint32_t nreads, bool keep_samples, uint32_t bits)
 {
-	RecodePlan r = make_recode_plan(src, dst, total_samples, nreads, keep_samples);
+	RecodePlan r = make_recode_plan(src, dst, total_samples, nreads, keep_samples, bits);
 	const size_t nr = (size_t) nreads + 1;
 	r.all.need(&Ctx::pneed, nr * 8).need(&Ctx::pslot, nr * 8);
 	return r;
@@ -319,6 +324,28 @@ extern "C" uint64_t press_hip_packed_workspace_bytes(int method, uint64_t total_
 	if (!method_ok(method))
 		return 0;
 	return plan_bytes(make_packed_plan(method, total_samples, nreads).merge(make_plan(method, total_samples, nreads, true)), is_shuff(method));
+}
+
+// the degraded recode calls: bits > 0 adds the degrade kernel's tile table to the undegraded figure of a pair that is not
+// fused; bits == 0, and a fused pair, nothing
+extern "C" uint64_t press_hip_recode_degraded_workspace_bytes(int src_method, int dst_method, uint32_t bits, uint64_t total_samples,
+							      uint32_t nreads, int keep_samples)
+{
+	API_LOCK;
+	if (!method_ok(src_method) || !method_ok(dst_method) || bits > 8)
+		return 0;
+	return plan_bytes(make_recode_plan(src_method, dst_method, total_samples, nreads, keep_samples != 0, bits).all,
+			  is_shuff(src_method) || is_shuff(dst_method));
+}
+
+extern "C" uint64_t press_hip_recode_degraded_packed_workspace_bytes(int src_method, int dst_method, uint32_t bits, uint64_t total_samples,
+								     uint32_t nreads, int keep_samples)
+{
+	API_LOCK;
+	if (!method_ok(src_method) || !method_ok(dst_method) || bits > 8)
+		return 0;
+	return plan_bytes(make_recode_packed_plan(src_method, dst_method, total_samples, nreads, keep_samples != 0, bits).all,
+			  is_shuff(src_method) || is_shuff(dst_method));
 }
 
 // as press_hip_recode_workspace_bytes, and the two tables of the packed plan
@@ -635,7 +662,8 @@ int ph::launch_depress_crc(const ScratchPlan &p, const DecodeArgs &a, uint32_t *
 	return rc ? rc : launch_signal_crc(p, a, crc, s);
 }
 
-int ph::launch_verify(const ScratchPlan &p, const DecodeArgs &a, const int16_t *sig, uint32_t *first_bad, uint32_t *nbad, hipStream_t s)
+int ph::launch_verify(const ScratchPlan &p, const DecodeArgs &a, const int16_t *sig, uint32_t *first_bad, uint32_t *nbad, hipStream_t s,
+		      uint32_t bits)
 {
 	const int rc = launch_depress(p, a, s);
 	if (rc)
@@ -643,7 +671,7 @@ int ph::launch_verify(const ScratchPlan &p, const DecodeArgs &a, const int16_t *
 	uint2 *tiles = (uint2 *) p.ptr(&Ctx::pa_tile);
 	uint32_t *ntiles = (uint32_t *) p.ptr(&Ctx::pa_ctl);
 	launch_pa_tiles(a, tiles, ntiles, s);
-	launch_verify_cmp(a, sig, tiles, ntiles, first_bad, nbad, s);
+	launch_verify_cmp(a, sig, tiles, ntiles, first_bad, nbad, s, bits);
 	return launch_status();
 }
 

@@ -234,9 +234,13 @@ __global__ __launch_bounds__(256) void k_crc_finish(const uint32_t *out_n, uint3
 
 // One workgroup per tile: the decoded samples against the caller's over [0, min(out_n[r], nsamp[r])); the smallest index
 // that differs goes into first_bad[r] (preset to VF_NONE) with one atomicMin per wave.  Loads of either side stay inside
-// [off[r], off[r] + roundup8(that minimum)); sig is only read.
+// [off[r], off[r] + roundup8(that minimum)); sig is only read.  DEG (press_hip_verify_degraded_batch): the caller's
+// samples are the originals of a degraded archive, and the decoded ones are compared with D_b of them, taken in registers
+// (degrade_pair; h2, m2: its constants) - no degraded copy of the originals exists.
+template <bool DEG>
 __global__ __launch_bounds__(256) void k_verify_cmp(const int16_t *dec, const int16_t *sig, const uint64_t *off, const uint32_t *nsamp,
-						     const uint32_t *out_n, const uint2 *tiles, const uint32_t *ntiles, uint32_t *first_bad)
+						     const uint32_t *out_n, const uint2 *tiles, const uint32_t *ntiles, uint32_t *first_bad,
+						     uint32_t h2, uint32_t m2)
 {
 	if (blockIdx.x >= uni(*ntiles))
 		return; // (the grid is an upper bound)
@@ -252,7 +256,10 @@ __global__ __launch_bounds__(256) void k_verify_cmp(const int16_t *dec, const in
 	const uint64_t o = uni64(off[r]);
 	uint32_t bad = VF_NONE;
 	for (uint64_t i = first + threadIdx.x * 8; i < end; i += STEP_SAMPLES) {
-		const uint4 a = ld16_stream(dec + o + i), b = ld16_stream(sig + o + i);
+		const uint4 a = ld16_stream(dec + o + i);
+		uint4 b = ld16_stream(sig + o + i);
+		if (DEG)
+			b = make_uint4(degrade_pair(b.x, h2, m2), degrade_pair(b.y, h2, m2), degrade_pair(b.z, h2, m2), degrade_pair(b.w, h2, m2));
 		const uint32_t x[4] = { a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w };
 		uint32_t m = 0; // bit e: sample e of the group differs
 #pragma unroll
@@ -305,14 +312,18 @@ void launch_crc(const DecodeArgs &a, const uint2 *tiles, const uint32_t *ntiles,
 }
 
 void launch_verify_cmp(const DecodeArgs &a, const int16_t *sig, const uint2 *tiles, const uint32_t *ntiles, uint32_t *first_bad,
-		       uint32_t *nbad, hipStream_t s)
+		       uint32_t *nbad, hipStream_t s, uint32_t bits)
 {
 	if (!a.nreads || !a.max_chunks)
 		return;
 	(void) hipMemsetAsync(first_bad, 0xFF, (size_t) a.nreads * 4, s);
 	(void) hipMemsetAsync(nbad, 0, 4, s);
-	hipLaunchKernelGGL(k_verify_cmp, dim3(a.max_chunks), dim3(256), 0, s, (const int16_t *) a.sig, sig, a.off, a.nsamp,
-			   (const uint32_t *) a.out_n, tiles, ntiles, first_bad);
+	if (bits)
+		hipLaunchKernelGGL(k_verify_cmp<true>, dim3(a.max_chunks), dim3(256), 0, s, (const int16_t *) a.sig, sig, a.off, a.nsamp,
+				   (const uint32_t *) a.out_n, tiles, ntiles, first_bad, degrade_h2(bits), degrade_m2(bits));
+	else
+		hipLaunchKernelGGL(k_verify_cmp<false>, dim3(a.max_chunks), dim3(256), 0, s, (const int16_t *) a.sig, sig, a.off, a.nsamp,
+				   (const uint32_t *) a.out_n, tiles, ntiles, first_bad, 0u, 0u);
 	hipLaunchKernelGGL(k_verify_finish, dim3((a.nreads + 255) / 256), dim3(256), 0, s, a.nsamp, (const uint32_t *) a.out_n, a.nreads,
 			   first_bad, nbad);
 }

@@ -46,4 +46,18 @@ __device__ __forceinline__ uint32_t zd_pair(uint32_t cur, uint32_t prevdw)
 	return __builtin_bit_cast(uint32_t, z);
 }
 
+// D_b (include/press_hip.h, press_hip_degrade_value) of the two samples packed in v, for b = 1 .. 8: round to the nearest
+// multiple of 2^b, ties up, saturating.  h2 = 2^(b-1) and m2 = ~(2^b - 1) in both halves (degrade_h2, degrade_m2).  The add
+// saturates (v_pk_add_i16 clamp), which is the definition's min: where s + 2^(b-1) passes 32767 the sum becomes 32767,
+// whose multiple below is 32768 - 2^b, the top bucket; where it does not, the 16-bit sum is the 32-bit one and its
+// multiple below cannot exceed that bucket.  Clearing the low bits is the arithmetic shift down and up again.
+__device__ __forceinline__ uint32_t degrade_pair(uint32_t v, uint32_t h2, uint32_t m2)
+{
+	const s16x2 s = __builtin_elementwise_add_sat(__builtin_bit_cast(s16x2, v), __builtin_bit_cast(s16x2, h2));
+	return __builtin_bit_cast(uint32_t, s) & m2;
+}
+// (b = 0: h2 = 0 and m2 = all ones, the identity)
+__host__ __device__ __forceinline__ uint32_t degrade_h2(uint32_t bits) { return bits ? 0x00010001u << (bits - 1) : 0u; }
+__host__ __device__ __forceinline__ uint32_t degrade_m2(uint32_t bits) { return ~(((1u << bits) - 1u) * 0x00010001u); }
+
 } // namespace ph

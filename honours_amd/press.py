@@ -92,7 +92,10 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_zstd_host_frames", "press_hip_symbol_counts", "press_hip_table_from_counts",
      "press_hip_write_table_file",
      "press_hip_crc32_combine", "press_hip_signal_crc32", "press_hip_depress_crc_batch", "press_hip_verify_batch",
-     "press_hip_verify_workspace_bytes"]))
+     "press_hip_verify_workspace_bytes",
+     "press_hip_degrade_value", "press_hip_degrade_batch", "press_hip_recode_degraded_batch",
+     "press_hip_recode_degraded_sizes", "press_hip_recode_degraded_packed", "press_hip_recode_degraded_workspace_bytes",
+     "press_hip_recode_degraded_packed_workspace_bytes", "press_hip_verify_degraded_batch"]))
 
 
 class PressError(RuntimeError):
@@ -218,6 +221,18 @@ def load_library(path=LIB_PATH):
                                                 ctypes.c_int]
         _lib.press_hip_verify_workspace_bytes.restype = ctypes.c_uint64
         _lib.press_hip_verify_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
+        _lib.press_hip_degrade_value.restype = ctypes.c_int16
+        _lib.press_hip_degrade_value.argtypes = [ctypes.c_int16, ctypes.c_uint32]
+        _lib.press_hip_degrade_batch.restype = ctypes.c_int
+        _lib.press_hip_degrade_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                 ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int]
+        # the degraded forms: the undegraded argument lists with `bits` behind the method ids
+        for name, at in (("recode_batch", 2), ("recode_sizes", 2), ("recode_packed", 2), ("verify_batch", 1),
+                         ("recode_workspace_bytes", 2), ("recode_packed_workspace_bytes", 2)):
+            plain = getattr(_lib, "press_hip_" + name)
+            deg = getattr(_lib, "press_hip_" + name.replace("recode_", "recode_degraded_").replace("verify_", "verify_degraded_"))
+            deg.restype = plain.restype
+            deg.argtypes = plain.argtypes[:at] + [ctypes.c_uint32] + plain.argtypes[at:]
         _lib.press_hip_debug_pass_a_launches.restype = ctypes.c_uint64
         _lib.press_hip_debug_pass_a_launches.argtypes = []
         libc = ctypes.CDLL(None)
@@ -639,23 +654,80 @@ def depress_chunks_batch(method, comp, in_off, in_len, rows, row_first, off, n, 
         raise PressError(last_error())
 
 
-def recode_batch(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, out_n, sig=None, total_samples=None):
+def degrade(samples, bits):
+    """D_bits of int16 samples (include/press_hip.h, press_hip_degrade_value), a numpy mirror: the nearest multiple of
+    2^bits, ties up, saturating at the largest multiple an int16 holds.  bits in 0 .. 8."""
+    bits = int(bits)
+    if not 0 <= bits <= 8:
+        raise PressError("degrade: bits = %d is not in 0 .. 8" % bits)
+    s = np.asarray(samples, dtype=np.int16)
+    if bits == 0:
+        return s.copy()
+    v = ((s.astype(np.int32) + (1 << (bits - 1))) >> bits) << bits
+    return np.minimum(v, 32768 - (1 << bits)).astype(np.int16)
+
+
+def degrade_value(s, bits):
+    """press_hip_degrade_value: the definition as the library's host arithmetic (no GPU)"""
+    return int(load_library().press_hip_degrade_value(int(s), int(bits)))
+
+
+def degrade_batch(sig, off, n, bits, out=None):
+    """Enqueue D_bits over a batch of reads (CUDA tensors as in press_batch); out: an int16 tensor laid out as sig, or
+    None: in place.  Only [off[r], off[r] + n[r]) of out is written."""
+    out = sig if out is None else out
+    rc = load_library().press_hip_degrade_batch(sig.data_ptr(), off.data_ptr(), n.data_ptr(), off.numel(), sig.numel(),
+                                                int(bits), out.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def degrade_batch_host(reads, bits):
+    """D_bits with host buffers: reads = list of int16 arrays -> list of int16 arrays"""
+    lib = load_library()
+    nreads = len(reads)
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    out = np.zeros(total + 64, dtype=np.int16)
+    if lib.press_hip_degrade_batch(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total, int(bits),
+                                   out.ctypes.data, 0):
+        raise PressError(last_error())
+    return [out[int(o): int(o) + int(k)].copy() for o, k in zip(off, ns)]
+
+
+def _degraded(lib, name, bits):
+    """press_hip_<name> for bits == 0 - the existing entry point, untouched - else its degraded form with `bits` bound
+    behind the `at` leading method ids"""
+    bits = int(bits)
+    if bits == 0:
+        return getattr(lib, "press_hip_" + name)
+    at = 1 if name.startswith("verify") else 2
+    fn = getattr(lib, "press_hip_" + name.replace("recode_", "recode_degraded_").replace("verify_", "verify_degraded_"))
+    return lambda *a: fn(*(a[:at] + (bits,) + a[at:]))
+
+
+def recode_batch(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, out_n, sig=None, total_samples=None,
+                 degrade_bits=0):
     """Enqueue the recoding of a batch of `src` streams into `dst` streams (CUDA tensors as in depress_batch and
     press_batch).  sig: the int16 tensor that also receives the decoded samples, or None - they then stay in library
-    scratch and total_samples (the extent of the layout off / n) must be given."""
+    scratch and total_samples (the extent of the layout off / n) must be given.  degrade_bits > 0: the streams hold
+    D_bits of the decoded samples, and sig receives those (press_hip_recode_degraded_batch)."""
     lib = load_library()
     nreads = off.numel()
     if sig is None and total_samples is None:
         raise PressError("recode_batch without sig needs total_samples")
     total = sig.numel() if total_samples is None else int(total_samples)
-    rc = lib.press_hip_recode_batch(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
+    rc = _degraded(lib, "recode_batch", degrade_bits)(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
                                     n.data_ptr(), off.data_ptr(), nreads, total, out.data_ptr(), out_off.data_ptr(),
                                     out_len.data_ptr(), None if sig is None else sig.data_ptr(), out_n.data_ptr(), 1)
     if rc:
         raise PressError(last_error())
 
 
-def recode_sizes(src, dst, comp, in_off, in_len, n, off, out_n, sig=None, total_samples=None):
+def recode_sizes(src, dst, comp, in_off, in_len, n, off, out_n, sig=None, total_samples=None, degrade_bits=0):
     """Enqueue the sizing of a recode (CUDA tensors as in recode_batch) -> int64 CUDA tensor of nreads entries: the
     bytes every read's `dst` stream takes (as press_sizes), -1 for a read either method refuses.  out_n and - if given -
     sig receive what the decode of `src` gives; no stream is written."""
@@ -667,7 +739,7 @@ def recode_sizes(src, dst, comp, in_off, in_len, n, off, out_n, sig=None, total_
         raise PressError("recode_sizes without sig needs total_samples")
     total = sig.numel() if total_samples is None else int(total_samples)
     need = torch.empty(nreads, dtype=torch.int64, device=comp.device)
-    rc = lib.press_hip_recode_sizes(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
+    rc = _degraded(lib, "recode_sizes", degrade_bits)(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
                                     n.data_ptr(), off.data_ptr(), nreads, total, need.data_ptr(),
                                     None if sig is None else sig.data_ptr(), out_n.data_ptr(), 1)
     if rc:
@@ -676,7 +748,7 @@ def recode_sizes(src, dst, comp, in_off, in_len, n, off, out_n, sig=None, total_
 
 
 def recode_packed(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, out_n, sig=None, total_samples=None,
-                  align=1):
+                  align=1, degrade_bits=0):
     """Enqueue the recoding of a batch into an arena the library lays out (press_hip_recode_packed).  CUDA tensors as
     in recode_batch, but out_off (int64, nreads+1) is WRITTEN, as by press_packed: out_off[-1] is what the batch needs,
     out.numel() the arena's capacity.  A read whose source stream is refused takes no byte."""
@@ -685,7 +757,7 @@ def recode_packed(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len,
     if sig is None and total_samples is None:
         raise PressError("recode_packed without sig needs total_samples")
     total = sig.numel() if total_samples is None else int(total_samples)
-    rc = lib.press_hip_recode_packed(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
+    rc = _degraded(lib, "recode_packed", degrade_bits)(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
                                      n.data_ptr(), off.data_ptr(), nreads, total, out.data_ptr(), out.numel(), int(align),
                                      out_off.data_ptr(), out_len.data_ptr(), None if sig is None else sig.data_ptr(),
                                      out_n.data_ptr(), 1)
@@ -710,7 +782,7 @@ def pass_a_launches():
     return int(load_library().press_hip_debug_pass_a_launches())
 
 
-def recode_batch_host(src, dst, streams, ns, caps=None, want_samples=False):
+def recode_batch_host(src, dst, streams, ns, caps=None, want_samples=False, degrade_bits=0):
     """Recode with host buffers: streams = list of bytes of method `src`, ns = sample counts / rooms ->
     list of bytes of method `dst` (None: the read failed); with want_samples -> (streams, list of int16 arrays)."""
     lib = load_library()
@@ -730,7 +802,7 @@ def recode_batch_host(src, dst, streams, ns, caps=None, want_samples=False):
     out_len = np.zeros(nreads, dtype=np.uint64)
     out_n = np.zeros(nreads, dtype=np.uint32)
     sig = np.zeros(total + 64, dtype=np.int16) if want_samples else None
-    rc = lib.press_hip_recode_batch(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
+    rc = _degraded(lib, "recode_batch", degrade_bits)(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
                                     ns.ctypes.data, off.ctypes.data, nreads, total, out.ctypes.data, out_off.ctypes.data,
                                     out_len.ctypes.data, sig.ctypes.data if want_samples else None, out_n.ctypes.data, 0)
     if rc:
@@ -741,7 +813,7 @@ def recode_batch_host(src, dst, streams, ns, caps=None, want_samples=False):
     return res, [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)]
 
 
-def recode_packed_host(src, dst, streams, ns, align=1, want_samples=False):
+def recode_packed_host(src, dst, streams, ns, align=1, want_samples=False, degrade_bits=0):
     """Packed recode with host buffers: streams = list of bytes of method `src`, ns = sample counts / rooms ->
     (list of bytes of method `dst` / None, arena bytes); with want_samples -> (streams, arena bytes, list of int16
     arrays).  No capacities: press_hip_recode_sizes gives the arena's size, so it is as large as the streams, not as a
@@ -757,7 +829,7 @@ def recode_packed_host(src, dst, streams, ns, align=1, want_samples=False):
     off, total = _layout(ns)
     need = np.zeros(nreads, dtype=np.uint64)
     out_n = np.zeros(nreads, dtype=np.uint32)
-    if lib.press_hip_recode_sizes(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
+    if _degraded(lib, "recode_sizes", degrade_bits)(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
                                   ns.ctypes.data, off.ctypes.data, nreads, total, need.ctypes.data, None,
                                   out_n.ctypes.data, 0):
         raise PressError(last_error())
@@ -767,7 +839,7 @@ def recode_packed_host(src, dst, streams, ns, align=1, want_samples=False):
     out_off = np.zeros(nreads + 1, dtype=np.uint64)
     out_len = np.zeros(nreads, dtype=np.uint64)
     sig = np.zeros(total + 64, dtype=np.int16) if want_samples else None
-    if lib.press_hip_recode_packed(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
+    if _degraded(lib, "recode_packed", degrade_bits)(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
                                    ns.ctypes.data, off.ctypes.data, nreads, total, out.ctypes.data, cap, int(align),
                                    out_off.ctypes.data, out_len.ctypes.data, sig.ctypes.data if want_samples else None,
                                    out_n.ctypes.data, 0):
@@ -1035,22 +1107,24 @@ def depress_crc_batch_host(method, streams, ns):
     return crc, out_n
 
 
-def verify_batch(method, comp, in_off, in_len, sig, off, n, first_bad, out_n, nbad):
+def verify_batch(method, comp, in_off, in_len, sig, off, n, first_bad, out_n, nbad, degrade_bits=0):
     """Enqueue decode-and-compare of a batch (CUDA tensors: the streams as in depress_batch; sig / off / n the samples
     they are meant to hold, laid out as press_batch takes them; first_bad, out_n: 32-bit, nreads entries; nbad: one
     32-bit word).  first_bad[r] = VERIFIED, or the first sample that differs (0: the stream is refused; min(out_n, n)
-    where only the counts differ); nbad = the reads that are not VERIFIED (press_hip_verify_batch)."""
+    where only the counts differ); nbad = the reads that are not VERIFIED (press_hip_verify_batch).  degrade_bits > 0:
+    sig holds the originals of a degraded archive and the comparison is with D_bits of them
+    (press_hip_verify_degraded_batch)."""
     nreads = off.numel()
     _u32_table(first_bad, nreads, "first_bad")
     _u32_table(nbad, 1, "nbad")
-    rc = load_library().press_hip_verify_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), nreads,
+    rc = _degraded(load_library(), "verify_batch", degrade_bits)(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), nreads,
                                                sig.data_ptr(), off.data_ptr(), n.data_ptr(), sig.numel(),
                                                first_bad.data_ptr(), out_n.data_ptr(), nbad.data_ptr(), 1)
     if rc:
         raise PressError(last_error())
 
 
-def verify_batch_host(method, streams, reads):
+def verify_batch_host(method, streams, reads, degrade_bits=0):
     """Decode and compare with host buffers: streams = list of bytes, reads = the int16 arrays they are meant to hold
     -> (first_bad uint32[nreads], out_n uint32[nreads], nbad)"""
     lib = load_library()
@@ -1066,7 +1140,7 @@ def verify_batch_host(method, streams, reads):
     first_bad = np.zeros(nreads, dtype=np.uint32)
     out_n = np.zeros(nreads, dtype=np.uint32)
     nbad = ctypes.c_uint32(0)
-    if lib.press_hip_verify_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads,
+    if _degraded(lib, "verify_batch", degrade_bits)(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads,
                                   sig.ctypes.data, off.ctypes.data, ns.ctypes.data, total, first_bad.ctypes.data,
                                   out_n.ctypes.data, ctypes.byref(nbad), 0):
         raise PressError(last_error())
@@ -1235,9 +1309,10 @@ def write_table(path, ln, bits, data_bytes):
         raise PressError(last_error())
 
 
-def _blow5_counts(path, counts, max_reads=4096, arena_bytes=1 << 28):
+def _blow5_counts(path, counts, max_reads=4096, arena_bytes=1 << 28, degrade_bits=0):
     """Counts of every read of a BLOW5 file, into the device tensor `counts`: the signal fields go to the device
-    as stored (svb-zd: decoded there by the slow5_svb_zd depress); the samples stay on the device."""
+    as stored (svb-zd: decoded there by the slow5_svb_zd depress); the samples stay on the device.  degrade_bits > 0:
+    the samples are degraded in place there before they are counted."""
     import torch
 
     dev = counts.device
@@ -1263,6 +1338,8 @@ def _blow5_counts(path, counts, max_reads=4096, arena_bytes=1 << 28):
                 d_in_len = torch.from_numpy(blen[:got].view(np.int64).copy()).to(dev)
                 d_out_n = torch.zeros(got, dtype=torch.int32, device=dev)
                 depress_batch("slow5_svb_zd", d_in, d_in_off, d_in_len, d_sig, d_off, d_n, d_out_n)
+                if degrade_bits:
+                    degrade_batch(d_sig, d_off, d_n, degrade_bits)
                 symbol_counts(d_sig, d_off, d_n, counts)
                 if not torch.equal(d_out_n, d_n):
                     raise PressError("a signal of %s does not decode" % path)
@@ -1271,6 +1348,8 @@ def _blow5_counts(path, counts, max_reads=4096, arena_bytes=1 << 28):
                 for k in range(got):
                     sig[int(off[k]):int(off[k]) + int(ns[k])] = arena[int(boff[k]):int(boff[k] + blen[k])].view(np.int16)
                 d_sig.copy_(torch.from_numpy(sig))
+                if degrade_bits:
+                    degrade_batch(d_sig, d_off, d_n, degrade_bits)
                 symbol_counts(d_sig, d_off, d_n, counts)
             else:
                 raise PressError("%s: signal method %d" % (path, rd.signal_method))
@@ -1278,19 +1357,23 @@ def _blow5_counts(path, counts, max_reads=4096, arena_bytes=1 << 28):
         rd.close()
 
 
-def train_table(src, path, max_bits=24):
+def train_table(src, path, max_bits=24, degrade_bits=0):
     """Fit a static-Huffman table to `src` (a list of int16 arrays, or the path of a BLOW5 file) and write it to
     `path` for use_table() / press_hip_load_table_file / the reference's read_code_table.  -> the counts
-    (numpy uint64[NBINS]; counts[256] = the exceptions, which the table does not code)."""
+    (numpy uint64[NBINS]; counts[256] = the exceptions, which the table does not code).  degrade_bits > 0: the table
+    is fitted to D_bits of the reads (degraded on the device, then counted) - the table for a degraded archive."""
+    degrade_bits = int(degrade_bits)
+    if not 0 <= degrade_bits <= 8:
+        raise PressError("train_table: degrade_bits = %d is not in 0 .. 8" % degrade_bits)
     if isinstance(src, (str, os.PathLike)):
         import torch
 
         use_torch_stream()
         counts = torch.zeros(NBINS, dtype=torch.int64, device="cuda")
-        _blow5_counts(os.fspath(src), counts)
+        _blow5_counts(os.fspath(src), counts, degrade_bits=degrade_bits)
         counts = counts.cpu().numpy().view(np.uint64)
     else:
-        counts = symbol_counts_host(src)
+        counts = symbol_counts_host(degrade_batch_host(src, degrade_bits) if degrade_bits else src)
     ln, bits = table_from_counts(counts, max_bits)
     write_table(path, ln, bits, int(counts[:256].sum()))
     return counts
@@ -1461,7 +1544,8 @@ def blow5_write_like(dst, like, fields, record_method=1, signal_method=1, index=
     return out_ids
 
 
-def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, passthrough=False, index=False, verify=False):
+def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, passthrough=False, index=False, verify=False,
+                    degrade_bits=0):
     """BLOW5 -> BLOW5 with the signal fields re-coded: codec(list of int16 arrays) -> list of svb-zd
     streams (default: the device, press_batch_host("slow5_svb_zd")); signal_method 0 writes the raw
     samples.  Signals of the source are decoded on the device when it stores them as svb-zd.
@@ -1472,7 +1556,16 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
     samples they were made of (verify_batch_host); a field that does not give them back raises PressError with the
     read's id and the first bad sample, and nothing more is written.  Nothing to check with passthrough or
     signal_method 0, which writes the samples themselves.
+    degrade_bits > 0: a lossy archive - the signals written decode to D_bits of the source's samples (degrade()); the
+    file is still plain BLOW5.  A source that stores svb-zd is decoded, degraded and pressed in one device call
+    (recode_batch_host) unless a codec is given; verify then compares the fields with D_bits of the source's samples
+    on the device (verify_batch_host(..., degrade_bits)).  Not with passthrough.
     Returns the number of reads written."""
+    degrade_bits = int(degrade_bits)
+    if not 0 <= degrade_bits <= 8:
+        raise PressError("blow5_transcode: degrade_bits = %d is not in 0 .. 8" % degrade_bits)
+    if passthrough and degrade_bits:
+        raise PressError("passthrough keeps the signal fields as they are: it cannot degrade them")
     lib = load_library()
     _blow5_writer_api(lib)
     rd = Blow5Reader(src)
@@ -1518,16 +1611,24 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
             if passthrough:
                 pass
             elif signal_method == 1:
-                out = (codec or (lambda reads: press_batch_host("slow5_svb_zd", reads)))(sigs)
+                if degrade_bits and codec is None and rd.signal_method == 1:
+                    out = recode_batch_host("slow5_svb_zd", "slow5_svb_zd", fields, [int(x) for x in ns[:got.value]],
+                                            degrade_bits=degrade_bits)
+                    if any(o is None for o in out):
+                        raise PressError("a signal of %s does not recode" % src)
+                else:
+                    out = (codec or (lambda reads: press_batch_host("slow5_svb_zd", reads)))(
+                        degrade_batch_host(sigs, degrade_bits) if degrade_bits else sigs)
                 if verify:
-                    first_bad, _, nbad = verify_batch_host("slow5_svb_zd", out, sigs)
+                    first_bad, _, nbad = verify_batch_host("slow5_svb_zd", out, sigs, degrade_bits=degrade_bits)
                     if nbad:
                         k = int(np.flatnonzero(first_bad != VERIFIED)[0])
                         idl = int(recs[k][0]) | (int(recs[k][1]) << 8)
                         raise PressError("read %s: the svb-zd field written for it does not decode to its samples (first bad sample %d)"
                                          % (recs[k][2:2 + idl].tobytes().split(b"\0")[0].decode(errors="replace"), int(first_bad[k])))
             else:
-                out = [np.ascontiguousarray(s, dtype=np.int16).tobytes() for s in sigs]
+                out = [np.ascontiguousarray(s, dtype=np.int16).tobytes()
+                       for s in (degrade_batch_host(sigs, degrade_bits) if degrade_bits else sigs)]
             _blow5_write_batch(lib, w, [r[:int(sp[k]) - 8] for k, r in enumerate(recs)],
                                [np.frombuffer(out[k], dtype=np.uint8) for k in range(got.value)],
                                [r[int(sp[k]) + int(sl[k]):] for k, r in enumerate(recs)])

@@ -722,6 +722,74 @@ int press_hip_verify_batch(int method, const uint8_t *in, const uint64_t *in_off
 uint64_t press_hip_verify_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads);
 
 /*
+ * Lossy archives: dropping the low b bits of every sample, on the device.
+ *
+ * The definition.  For bits = b in 0 .. 8 and a sample s (int16), computed in 32-bit integers:
+ *     D_0(s) = s
+ *     D_b(s) = min( ((s + 2^(b-1)) >> b) << b ,  32768 - 2^b )          (arithmetic shift)
+ * the nearest multiple of 2^b, ties towards +infinity, saturating at the largest multiple of 2^b an int16 holds - it
+ * never wraps; -32768 is a multiple of every 2^b and needs no clamp.  D_b is idempotent and monotone, and
+ * |D_b(s) - s| <= 2^(b-1), except in the saturated top bucket, where it is below 2^b.  This is believed to be the rounding
+ * of slow5tools' `degrade` apart from the saturation; that is from memory and NOT checked: no compatibility is claimed.
+ * bits > 8 is PRESS_HIP_EARG in every call below, before the method ids are looked at and before any device call.
+ *
+ * press_hip_degrade_value: the definition as host arithmetic, no GPU (bits > 8: s as it is).
+ *
+ * press_hip_degrade_batch: out[off[r] + i] = D_b(sig[off[r] + i]) for i < n[r].
+ *   sig / off / n / total_samples / device_resident   as press_hip_press_batch, with its checks (off[] multiples of 8
+ *            samples, a device sig 16-byte aligned, non-overlap on the host path).  Loads stay inside
+ *            [off[r], off[r] + roundup8(n[r])).
+ *   out      laid out as sig; device resident 16-byte aligned (PRESS_HIP_EARG).  out == sig (in place) is allowed.
+ *            Nothing outside [off[r], off[r] + n[r]) is written: a read's last group of fewer than 8 samples is stored
+ *            sample by sample.  Host buffers receive exactly n[r] samples per read.
+ *   device_resident != 0: the call only enqueues.  == 0: the samples are staged, the call is synchronous.
+ *
+ * press_hip_recode_degraded_batch / _sizes / _packed: press_hip_recode_batch / _sizes / _packed with `bits` behind
+ * dst_method.  Meaning: decode src, apply D_b, press with dst - the streams, out_len, need, out_off are byte for byte what
+ * press_hip_press_batch / _sizes / _packed (dst_method) give on D_b of the decoded samples.  sig, where the caller asks
+ * for samples, receives the DEGRADED samples: what the new streams decode to.  Refused source reads, out_n, the slot
+ * rules, the packed layout and align, the range coders' need and every check stay as in the undegraded calls.
+ * bits == 0 takes the undegraded calls' code path and gives their bytes.  bits > 0, two routes, chosen as
+ * press_hip_recode_fused chooses: where it is 1 the svb decode kernel applies D_b to the samples it holds in registers,
+ * behind its inverse scan and in front of its store and of the exception and code-bit counts it leaves for the press half,
+ * which therefore describe the degraded read - no further pass over the samples.  Every other pair decodes into the
+ * samples (the zstd kinds' host fallback included), press_hip_degrade_batch's kernel runs in place over out_n[r] samples
+ * of every decoded read, and the press half follows.
+ * press_hip_recode_degraded_sizes answers "how much smaller would this archive be without its b low bits" with no arena.
+ * press_hip_recode_degraded_workspace_bytes / _packed_workspace_bytes: press_hip_recode_workspace_bytes /
+ * _packed_workspace_bytes unchanged for bits == 0 and for a fused pair; for any other pair with bits > 0 that figure plus
+ * the degrade kernel's tile table ((total_samples / 32768 + nreads + 1) * 8 bytes and a 64-byte counter) - never below;
+ * 0 for a bad method id or bits.
+ *
+ * press_hip_verify_degraded_batch: press_hip_verify_batch with `bits` behind method.  sig holds the ORIGINAL samples; the
+ * decoded samples are compared with D_b of them, taken in registers inside the compare kernel - no degraded copy of the
+ * originals is made.  first_bad, nbad, out_n and PRESS_HIP_VERIFIED keep their meanings; bits == 0 is
+ * press_hip_verify_batch.  The workspace is press_hip_verify_workspace_bytes.
+ */
+int16_t press_hip_degrade_value(int16_t s, uint32_t bits);
+int press_hip_degrade_batch(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			    uint64_t total_samples, uint32_t bits, int16_t *out, int device_resident);
+int press_hip_recode_degraded_batch(int src_method, int dst_method, uint32_t bits, const uint8_t *in, const uint64_t *in_off,
+				    const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+				    uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+				    int16_t *sig, uint32_t *out_n, int device_resident);
+int press_hip_recode_degraded_sizes(int src_method, int dst_method, uint32_t bits, const uint8_t *in, const uint64_t *in_off,
+				    const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+				    uint64_t total_samples, uint64_t *need, int16_t *sig, uint32_t *out_n, int device_resident);
+int press_hip_recode_degraded_packed(int src_method, int dst_method, uint32_t bits, const uint8_t *in, const uint64_t *in_off,
+				     const uint64_t *in_len, const uint32_t *n, const uint64_t *off, uint32_t nreads,
+				     uint64_t total_samples, uint8_t *out, uint64_t out_cap, uint32_t align,
+				     uint64_t *out_off, uint64_t *out_len, int16_t *sig, uint32_t *out_n, int device_resident);
+uint64_t press_hip_recode_degraded_workspace_bytes(int src_method, int dst_method, uint32_t bits, uint64_t total_samples,
+						   uint32_t nreads, int keep_samples);
+uint64_t press_hip_recode_degraded_packed_workspace_bytes(int src_method, int dst_method, uint32_t bits, uint64_t total_samples,
+							  uint32_t nreads, int keep_samples);
+int press_hip_verify_degraded_batch(int method, uint32_t bits, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+				    uint32_t nreads, const int16_t *sig, const uint64_t *off, const uint32_t *n,
+				    uint64_t total_samples, uint32_t *first_bad, uint32_t *out_n, uint32_t *nbad,
+				    int device_resident);
+
+/*
  * PRESS_HIP_ZSTD_SVB_ZD, _ZSTD_SVB12_ZD and _ZSTD_HASGAM_ZDQ in the calls above (SURVEY.md 8f-3,
  * replaces the ZSTD_compress / ZSTD_decompress calls of press.c:1860-1910, 2020-2070, 8549-8589 for batches):
  *   press    writes one standard zstd frame (RFC 8878) per read whose content is the buffer
