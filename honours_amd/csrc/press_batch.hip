@@ -573,6 +573,84 @@ extern "C" int press_hip_signal_stats_timed(const int16_t *sig, const uint64_t *
 	return rc;
 }
 
+// ------------------------------------------------------------------ events of samples that are already there
+//
+// press_hip_signal_stats' layout and staging; the kernels of press_events.hip.  Two walks over the reads: the count with the
+// layout, then the records.  Host pointers: ev_first[nreads] comes back between them, the records' arena is reserved at
+// min(need, ev_cap) records and comes back in one transfer.
+
+static_assert(sizeof(press_hip_event) == 16 && sizeof(press_hip_event_params) == sizeof(EvParams), "the event structs");
+
+extern "C" int press_hip_event_params_preset(int rna, press_hip_event_params *prm)
+{
+	if (!prm)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	if (rna)
+		*prm = { 7, 14, 2.5f, 9.0f, 1.0f }; // events.c:50-54
+	else
+		*prm = { 3, 6, 1.4f, 9.0f, 0.2f }; // events.c:43-47
+	return 0;
+}
+
+extern "C" int press_hip_signal_events(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				       uint64_t total_samples, const float *cal, const press_hip_event_params *prm,
+				       press_hip_event *ev, uint64_t ev_cap, uint64_t *ev_first, uint32_t *ev_count, int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(NONE, NONE, !prm || !ev_first || (nreads && (!sig || !off || !n || !cal || !ev_count)) || (!ev && ev_cap), nreads,
+			 device_resident ? sig : nullptr, "sig");
+	if (rc)
+		return rc;
+	if (prm->w1 < 2 || prm->w1 > 64 || prm->w2 < 2 || prm->w2 > 64)
+		return set_error(PRESS_HIP_EARG, "window lengths %u, %u: 2 .. 64", prm->w1, prm->w2);
+	if ((rc = device_ready(NONE, NONE)))
+		return rc;
+	hipStream_t s = g.stream();
+	if (nreads == 0) { // (the layout of no reads: one zero)
+		if (device_resident)
+			HIPCHK(hipMemsetAsync(ev_first, 0, 8, s));
+		else
+			ev_first[0] = 0;
+		return 0;
+	}
+	const EvParams p = { prm->w1, prm->w2, prm->threshold1, prm->threshold2, prm->peak_height };
+	const ScratchPlan plan = make_events_plan(nreads, !device_resident);
+	if ((rc = plan.reserve()))
+		return rc;
+	void *state = plan.ptr(&Ctx::ev_state);
+	if (device_resident) {
+		launch_events_count(sig, off, n, nreads, cal, p, state, ev_cap, ev_first, ev_count, s);
+		if (ev_cap)
+			launch_events_write(sig, off, n, nreads, cal, p, state, ev, ev_cap, ev_first, s);
+		return launch_status();
+	}
+	SamplesIn in = { sig, off, n };
+	Staged st(nreads, s);
+	if ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in)))
+		return rc;
+	const float *dcal = (const float *) g.ev_cal.p;
+	uint64_t *dfirst = (uint64_t *) g.ev_first.p;
+	uint32_t *dcount = (uint32_t *) g.ev_cnt.p;
+	HIPCHK(hipMemcpyAsync(g.ev_cal.p, cal, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	launch_events_count(in.sig, in.off, in.n, nreads, dcal, p, state, ev_cap, dfirst, dcount, s);
+	if ((rc = launch_status()))
+		return rc;
+	HIPCHK(hipMemcpyAsync(ev_first, dfirst, ((size_t) nreads + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(ev_count, dcount, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	const uint64_t have = ev_first[nreads] < ev_cap ? ev_first[nreads] : ev_cap;
+	if (!have)
+		return 0;
+	if (g.ev_out.reserve(have * sizeof(press_hip_event)))
+		return PRESS_HIP_EHIP;
+	HIPCHK(hipMemsetAsync(g.ev_out.p, 0, have * sizeof(press_hip_event), s)); // (the room of a read that did not fit: zeros)
+	launch_events_write(in.sig, in.off, in.n, nreads, dcal, p, state, g.ev_out.p, ev_cap, dfirst, s);
+	if ((rc = launch_status()) || (rc = st.fetch_prefix(ev, g.ev_out.p, have * sizeof(press_hip_event))))
+		return rc;
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
 // ------------------------------------------------------------------ recode: streams in, streams out
 //
 // The two halves run one after the other on the stream, inside one call and one lock: the decode of `src` into the

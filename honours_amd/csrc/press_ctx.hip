@@ -217,6 +217,14 @@ extern "C" uint32_t press_hip_zstd_host_frames(void)
 	return g.zs_nhost;
 }
 
+extern "C" uint32_t press_hip_events_serial_reads(void)
+{
+	API_LOCK;
+	if (!g.ready || hipSetDevice(g.device) != hipSuccess)
+		return 0;
+	return events_serial_reads(g.stream());
+}
+
 extern "C" uint32_t press_hip_scratch_buffers(uint64_t *bytes)
 {
 	API_LOCK;

@@ -71,6 +71,7 @@ struct Ctx {
 	DevBuf st_rows, st_read, st_cal, st_stats; // median / MAD: the reads' count rows, the pick state, the normaliser's two floats; host path: stats
 	DevBuf ch_rows, ch_first; // chunk rows, host path: the row arena, the staged row_first
 	DevBuf vf_raw, vf_out; // verify / CRC-32: a word per read between the two kernels; host path: the staged crc or first_bad, and nbad
+	DevBuf ev_state, ev_cal, ev_first, ev_cnt, ev_out; // events: count and path per read; host path: the staged calibration, ev_first, ev_count, the records
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams
@@ -278,6 +279,10 @@ ScratchPlan make_chunks_plan(int method, uint64_t total_samples, uint32_t nreads
 // word per read; host pointers: the staged per-read result and nbad (vf_out: nreads words, then nbad).  method < 0
 // (press_hip_signal_crc32): no decode and no samples, the tile table and the words alone
 ScratchPlan make_verify_plan(int method, uint64_t total_samples, uint32_t nreads, bool host);
+
+// press_hip_signal_events: 8 bytes per read; host pointers: the staged calibration, ev_first and ev_count (the records'
+// arena is reserved by the call at min(need, ev_cap) once the need is known).  Nothing per sample: the sums stay in LDS
+ScratchPlan make_events_plan(uint32_t nreads, bool host);
 
 // press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
 ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);

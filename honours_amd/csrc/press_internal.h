@@ -390,6 +390,19 @@ void launch_verify_cmp(const DecodeArgs &a, const int16_t *sig, const uint2 *til
 // press_degrade.hip, over the same table: out[a.off[r] + i] = D_bits(a.sig[a.off[r] + i]) for i < a.out_n[r], bits in
 // 0 .. 8 (0: a copy); out == a.sig is fine
 void launch_degrade(const DecodeArgs &a, int16_t *out, uint32_t bits, const uint2 *tiles, const uint32_t *ntiles, hipStream_t s);
+// press_events.hip: the events of the n[r] samples at sig + off[r] as picoamperes of cal (include/press_hip.h,
+// press_hip_signal_events), a wave per read, in two walks: the count and the layout, then the records of the reads that
+// fit ev_cap.  state: events_state_bytes.  The kernels are timed as ring 1 of press_hip_kernel_times: count, scan, write
+struct EvParams { // press_hip_event_params
+	uint32_t w1, w2;
+	float thr1, thr2, height;
+};
+uint64_t events_state_bytes(uint32_t nreads);
+void launch_events_count(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const float *cal,
+			 const EvParams &p, void *state, uint64_t ev_cap, uint64_t *ev_first, uint32_t *ev_count, hipStream_t s);
+void launch_events_write(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const float *cal,
+			 const EvParams &p, void *state, void *ev, uint64_t ev_cap, const uint64_t *ev_first, hipStream_t s);
+uint32_t events_serial_reads(hipStream_t s); // synchronises s
 void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip

@@ -204,6 +204,16 @@ ScratchPlan make_verify_plan(int method, uint64_t total_samples, uint32_t nreads
 	return p;
 }
 
+// Events: the walk keeps its sums in LDS and registers, so the scratch does not depend on total_samples
+ScratchPlan make_events_plan(uint32_t nreads, bool host)
+{
+	ScratchPlan p{};
+	p.need(&Ctx::ev_state, events_state_bytes(nreads));
+	if (host)
+		p.need(&Ctx::ev_cal, (size_t) nreads * 8).need(&Ctx::ev_first, ((size_t) nreads + 1) * 8).need(&Ctx::ev_cnt, (size_t) nreads * 4);
+	return p;
+}
+
 // Fused pairs: BLOW5's and the reference's svb-zd streams into any exception-split method.  (svb12 has no deltas; the zstd
 // kinds and the svb destinations take the general path.)
 bool recode_fused(int src, int dst)
@@ -396,6 +406,13 @@ extern "C" uint64_t press_hip_verify_workspace_bytes(int method, uint64_t total_
 	if (!method_ok(method))
 		return 0;
 	return plan_bytes(make_verify_plan(method, total_samples, nreads, false).merge(make_plan(method, total_samples, nreads, false)), is_shuff(method));
+}
+
+// what the device-resident press_hip_signal_events keeps: 8 bytes per read, nothing per sample, no slices
+extern "C" uint64_t press_hip_signal_events_workspace_bytes(uint64_t total_samples, uint32_t nreads)
+{
+	(void) total_samples;
+	return plan_bytes(make_events_plan(nreads, false), false);
 }
 
 static bool rank_ok(uint32_t num, uint32_t den) { return den > 0 && num <= den; }

@@ -95,7 +95,9 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_verify_workspace_bytes",
      "press_hip_degrade_value", "press_hip_degrade_batch", "press_hip_recode_degraded_batch",
      "press_hip_recode_degraded_sizes", "press_hip_recode_degraded_packed", "press_hip_recode_degraded_workspace_bytes",
-     "press_hip_recode_degraded_packed_workspace_bytes", "press_hip_verify_degraded_batch"]))
+     "press_hip_recode_degraded_packed_workspace_bytes", "press_hip_verify_degraded_batch",
+     "press_hip_event_params_preset", "press_hip_signal_events", "press_hip_signal_events_workspace_bytes",
+     "press_hip_events_serial_reads"]))
 
 
 class PressError(RuntimeError):
@@ -143,6 +145,16 @@ def load_library(path=LIB_PATH):
         _lib.press_hip_signal_stats.restype = ctypes.c_int
         _lib.press_hip_signal_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_event_params_preset.restype = ctypes.c_int
+        _lib.press_hip_event_params_preset.argtypes = [ctypes.c_int, ctypes.c_void_p]
+        _lib.press_hip_signal_events.restype = ctypes.c_int
+        _lib.press_hip_signal_events.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_signal_events_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_signal_events_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+        _lib.press_hip_events_serial_reads.restype = ctypes.c_uint32
+        _lib.press_hip_events_serial_reads.argtypes = []
         _lib.press_hip_signal_stats_timed.restype = ctypes.c_int
         _lib.press_hip_signal_stats_timed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                       ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
@@ -1027,6 +1039,93 @@ def signal_stats_host(reads):
     if lib.press_hip_signal_stats(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, stats.ctypes.data, 0):
         raise PressError(last_error())
     return stats
+
+
+# ---------------------------------------------------------------------------- events: sigtk's segmentation
+
+class EventParams(ctypes.Structure):
+    """press_hip_event_params: the two window lengths (2 .. 64), their thresholds and the peak height"""
+    _fields_ = [("w1", ctypes.c_uint32), ("w2", ctypes.c_uint32), ("threshold1", ctypes.c_float),
+                ("threshold2", ctypes.c_float), ("peak_height", ctypes.c_float)]
+
+
+EVENT_DTYPE = np.dtype([("start", "<u4"), ("length", "<u4"), ("mean", "<f4"), ("stdv", "<f4")])  # press_hip_event
+EVENT_NOFIT = 0xFFFFFFFF  # ev_count of a read whose records did not fit ev_cap
+
+
+def event_params(rna=False):
+    """sigtk's detector parameters (press_hip_event_params_preset): DNA 3, 6, 1.4, 9.0, 0.2; RNA 7, 14, 2.5, 9.0, 1.0"""
+    p = EventParams()
+    if load_library().press_hip_event_params_preset(1 if rna else 0, ctypes.addressof(p)):
+        raise PressError(last_error())
+    return p
+
+
+def signal_events(sig, off, n, cal, prm, ev, ev_first, ev_count, ev_cap=None):
+    """Enqueue the event detection of a batch of samples (CUDA tensors as in signal_stats; cal float32 of 2 * nreads:
+    pa_cal; prm an EventParams; ev: 16-byte records as a 32-bit tensor of [cap, 4] - start, length, mean bits, stdv bits -
+    or None for a pure count; ev_first int64 of nreads + 1, WRITTEN; ev_count 32-bit of nreads): read r's events are
+    ev[ev_first[r]:ev_first[r + 1]] where they fit ev_cap (default: the rows of ev), else ev_count[r] = 0xFFFFFFFF
+    (press_hip_signal_events)."""
+    nreads = off.numel()
+    _u32_table(ev_count, nreads, "ev_count")
+    if ev_first.numel() < nreads + 1 or ev_first.element_size() != 8 or not ev_first.is_contiguous():
+        raise PressError("ev_first must be a contiguous 64-bit tensor of nreads + 1 entries")
+    if cal.numel() < 2 * nreads or cal.element_size() != 4 or not cal.is_contiguous():
+        raise PressError("cal must be a contiguous float32 tensor of 2 * nreads entries")
+    rows = 0
+    if ev is not None:
+        if ev.element_size() != 4 or not ev.is_contiguous() or ev.numel() % 4:
+            raise PressError("ev must be a contiguous 32-bit tensor of 4 words per record")
+        rows = ev.numel() // 4
+    cap = rows if ev_cap is None else int(ev_cap)
+    if cap > rows:
+        raise PressError("ev_cap is beyond ev")
+    if load_library().press_hip_signal_events(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(), cal.data_ptr(),
+                                              ctypes.addressof(prm), ev.data_ptr() if cap else None, cap,
+                                              ev_first.data_ptr(), ev_count.data_ptr(), 1):
+        raise PressError(last_error())
+
+
+def signal_events_host(reads, cal, prm=None, ev_cap=None):
+    """Events of a list of int16 arrays (host buffers, synchronous); cal (nreads, 2) float32 as pa_cal gives it, prm an
+    EventParams (default: the DNA preset), ev_cap a limit in records (default: what the batch needs, found with a pure
+    count) -> (ev, ev_first, ev_count): ev an EVENT_DTYPE array of min(need, ev_cap) records, ev_first uint64 of
+    nreads + 1, ev_count uint32 per read (0xFFFFFFFF: the read did not fit)."""
+    lib = load_library()
+    prm = event_params() if prm is None else prm
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    cal = np.ascontiguousarray(cal, dtype=np.float32).reshape(-1)
+    if cal.size != 2 * len(reads):
+        raise PressError("cal: two floats per read")
+    ev_first = np.zeros(len(reads) + 1, dtype=np.uint64)
+    ev_count = np.zeros(len(reads), dtype=np.uint32)
+
+    def call(ev, cap):
+        if lib.press_hip_signal_events(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, cal.ctypes.data,
+                                       ctypes.addressof(prm), ev.ctypes.data if cap else None, cap, ev_first.ctypes.data,
+                                       ev_count.ctypes.data, 0):
+            raise PressError(last_error())
+
+    if ev_cap is None:
+        call(None, 0)
+        ev_cap = int(ev_first[-1])
+    ev = np.zeros(int(ev_cap), dtype=EVENT_DTYPE)
+    call(ev, int(ev_cap))
+    return ev[:min(int(ev_first[-1]), int(ev_cap))], ev_first, ev_count
+
+
+def events_serial_reads():
+    """diagnostic: the reads whose sums took the serial path so far (press_hip_events_serial_reads)"""
+    return int(load_library().press_hip_events_serial_reads())
+
+
+def signal_events_workspace_bytes(total_samples, nreads):
+    return int(load_library().press_hip_signal_events_workspace_bytes(int(total_samples), int(nreads)))
 
 
 # ---------------------------------------------------------------------------- verifying: CRC-32 and compare-after-decode

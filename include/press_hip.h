@@ -722,6 +722,81 @@ int press_hip_verify_batch(int method, const uint8_t *in, const uint64_t *in_off
 uint64_t press_hip_verify_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads);
 
 /*
+ * Events: reads segmented on the device, bit for bit as sigtk's `event` subcommand segments them.
+ *
+ * The events of a read are detect_events (sigtk/src/events.c:506, scrappie's detector) applied to the read's picoampere
+ * floats, which are exactly press_hip_depress_pa_batch's:
+ *     x[i] = ((float) s[i] + cal[2r]) * cal[2r + 1]                  the add and the multiply rounded separately
+ * getevents (events.c:553) trims the read first and throws the result away, so the detection runs on the whole read; that
+ * step is not repeated here.  The definition, every operation rounded on its own in the precision named:
+ *   sums     S[0] = Q[0] = 0, S[i+1] = S[i] + (double) x[i], Q[i+1] = Q[i] + (double) (x[i] * x[i]) - the square rounded
+ *            to single precision first; sequential double-precision adds (events.c:293)
+ *   t-statistic of window w (events.c:315): 0 for i < w, for i > n - w, and everywhere when n < 2w; else with wf = (float) w
+ *            sum1 = S[i] - S[i-w], sumsq1 = Q[i] - Q[i-w] (double);  sum2 = (float) (S[i+w] - S[i]), sumsq2 likewise
+ *            mean1 = (float) (sum1 / (double) wf);  mean2 = sum2 / wf (single)
+ *            var = fmaxf((float) (((sumsq1 / (double) wf - (double) (mean1 * mean1)) + (double) (sumsq2 / wf))
+ *                                 - (double) (mean2 * mean2)), FLT_MIN)       products and sumsq2 / wf in single precision
+ *            t[i] = (float) (fabs((double) (mean2 - mean1)) / sqrt((double) (var / wf)))
+ *   peaks    short_long_peak_detector (events.c:371): two coupled state machines over t of w1 and of w2, stepped in that
+ *            order at every sample; the short one masks and resets the long one; differences are taken in single precision
+ *            before they are compared with peak_height
+ *   events   boundaries 0, peak[0], peak[1], ..., n (events.c:457, 475); per event, with len = (float) (end - start):
+ *            mean = (float) (S[end] - S[start]) / len
+ *            stdv = sqrtf(fmaxf((float) (Q[end] - Q[start]) / len - mean * mean, 0))
+ * The sums are exact, not close: a read whose sums cannot round in any order (every x a multiple of 2^q and
+ * n * max|x| < 2^(q + 53), likewise the squares - decided per read on the device) is summed by a wave scan, every other
+ * read by adds in the reference's order.  press_hip_events_serial_reads counts the latter.
+ *
+ * Where the reference does not answer, the library defines:
+ *   - the reference aborts (assert, events.c:242, in the discarded trimming) on every read shorter than 100 samples and
+ *     on every constant read; such reads get the events the definition above yields
+ *   - a read with no peak: the reference reads peaks[-1]; here it is one event [0, n) with the formulas above
+ *   - n = 0: no event
+ *   - cal is not validated: NaN and inf propagate, nothing faults and nothing outside the caller's rooms is written
+ *   - the peak positions strictly increase, so do the starts; records are in emission order
+ *   - reads of 2^31 samples and more, where the reference's int peak position wraps: the definition with exact integers
+ *
+ *   prm      press_hip_event_params_preset(rna, &prm): DNA 3, 6, 1.4, 9.0, 0.2; RNA 7, 14, 2.5, 9.0, 1.0
+ *            (events.c:43-54).  w1, w2 must lie in 2 .. 64, else PRESS_HIP_EARG before any device call.
+ *   sig / off / n / total_samples / device_resident   as press_hip_signal_stats, with its checks
+ *   cal      2 * nreads floats, press_hip_pa_cal's
+ *   ev / ev_cap / ev_first / ev_count   the layout of press_hip_press_packed.  ev_first (nreads + 1 entries) is WRITTEN:
+ *            ev_first[0] = 0, ev_first[r + 1] = ev_first[r] + the events of read r, whatever ev_cap is: ev_first[nreads]
+ *            always says what the batch needs.  Read r's records are ev[ev_first[r] .. ev_first[r + 1]) and
+ *            ev_count[r] their number iff ev_first[r + 1] <= ev_cap; otherwise ev_count[r] = UINT32_MAX and no record of
+ *            it is written.  Nothing at or beyond ev_cap is ever written.  ev == NULL with ev_cap == 0 is a pure count.
+ *            start and length are integers (the reference's length is (float) length, which is what the library uses
+ *            inside).
+ * device_resident != 0: every pointer but prm is a device pointer; the call only enqueues on the current stream and never
+ * waits on the host.  == 0: host pointers, synchronous: the samples are staged and counted, ev_first and ev_count come
+ * back - the call's one synchronisation besides the last -, the records' arena is reserved at min(ev_first[nreads],
+ * ev_cap) records and comes back in ONE transfer; the room of a read that did not fit arrives as zeros.
+ * A NULL argument (other than ev with ev_cap == 0) is PRESS_HIP_EARG before any device call; nreads == 0 is PRESS_HIP_OK
+ * (ev_first[0] = 0).
+ * One wave walks one read, twice (the count, then the records): the call's time is set by the longest read of the batch,
+ * as the range coders' is.
+ * press_hip_signal_events_workspace_bytes: the device scratch the device-resident call keeps: 8 bytes per read and 0
+ * bytes per sample - the sums never reach memory - so the batch is never cut into slices; exact as
+ * press_hip_workspace_bytes is, 0 for an empty batch.
+ * press_hip_events_serial_reads: a diagnostic, like press_hip_zstd_host_frames: the reads whose sums took the serial
+ * path, in all calls since the library was loaded (it waits for the current stream); 0 without a device.
+ */
+typedef struct {
+	uint32_t w1, w2;
+	float threshold1, threshold2, peak_height;
+} press_hip_event_params;
+typedef struct {
+	uint32_t start, length;
+	float mean, stdv;
+} press_hip_event; /* 16 bytes */
+int press_hip_event_params_preset(int rna, press_hip_event_params *prm);
+int press_hip_signal_events(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			    uint64_t total_samples, const float *cal, const press_hip_event_params *prm,
+			    press_hip_event *ev, uint64_t ev_cap, uint64_t *ev_first, uint32_t *ev_count, int device_resident);
+uint64_t press_hip_signal_events_workspace_bytes(uint64_t total_samples, uint32_t nreads);
+uint32_t press_hip_events_serial_reads(void);
+
+/*
  * Lossy archives: dropping the low b bits of every sample, on the device.
  *
  * The definition.  For bits = b in 0 .. 8 and a sample s (int16), computed in 32-bit integers:

@@ -1,0 +1,693 @@
+"""Event detection on the device (include/press_hip.h, "Events"): press_hip_signal_events against the
+definition, bit for bit in all four fields and in the layout arrays.
+
+The yardstick is `yard_events`, a numpy restatement of the definition with an explicit float32 / float64 per operation and
+the peak detector as a plain Python loop.  It is pinned to the reference: tests/golden/sigtk_events.json holds what
+sigtk's events.c, compiled as it is, gives for the three real reads and six reads of _layouts.battery() under both presets
+and two calibrations (tests/golden/make_events_golden.py), and the yardstick must reproduce every entry exactly.  The
+device is then compared with the yardstick on inputs the reference aborts on or was not run on.
+"""
+import ctypes
+import hashlib
+import json
+import os
+import struct
+import time
+
+import numpy as np
+import pytest
+
+import _layouts as L
+from honours_amd import press
+
+gpu = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+EARG = -2
+NOFIT = 0xFFFFFFFF
+FLT_MAX = float(np.finfo(np.float32).max)
+FLT_MIN = np.float32(np.finfo(np.float32).tiny)
+TILE = 64  # positions per step of the device's walk
+F32 = np.float32
+PRESETS = {"dna": (3, 6, 1.4, 9.0, 0.2), "rna": (7, 14, 2.5, 9.0, 1.0)}
+CUSTOM = (2, 64, 1.1, 4.0, 0.05)
+TINY_CAL = (-500.001, 1467.61 / 8192.0)  # offset, scale: the smallest non-zero |x| is 1.8e-4 and the squares' sums round
+
+
+# ------------------------------------------------------------------ the yardstick
+
+def cal32(offset, scale):
+    return F32(offset), F32(scale)
+
+
+def picoamperes(s, c0, c1):
+    with np.errstate(all="ignore"):
+        return ((np.asarray(s, dtype=np.int16).astype(F32) + F32(c0)) * F32(c1)).astype(F32)
+
+
+def yard_sums(x):
+    """S, Q of n + 1 doubles: sequential adds (np.add.accumulate adds in order); the square is rounded to float32 first"""
+    S = np.concatenate([[0.0], np.add.accumulate(x.astype(np.float64))])
+    Q = np.concatenate([[0.0], np.add.accumulate((x * x).astype(F32).astype(np.float64))])
+    return S, Q
+
+
+def yard_tstat(S, Q, n, w):
+    t = np.zeros(n, dtype=F32)
+    if n < 2 * w or w < 2:
+        return t
+    i = np.arange(w, n - w + 1)
+    wf = F32(w)
+    wd = np.float64(wf)
+    with np.errstate(all="ignore"):
+        sum1 = S[i] - S[i - w]
+        sumsq1 = Q[i] - Q[i - w]
+        sum2 = (S[i + w] - S[i]).astype(F32)
+        sumsq2 = (Q[i + w] - Q[i]).astype(F32)
+        mean1 = (sum1 / wd).astype(F32)
+        mean2 = (sum2 / wf).astype(F32)
+        cv = sumsq1 / wd
+        cv = cv - (mean1 * mean1).astype(F32).astype(np.float64)
+        cv = cv + (sumsq2 / wf).astype(F32).astype(np.float64)
+        cv = cv - (mean2 * mean2).astype(F32).astype(np.float64)
+        var = np.fmax(cv.astype(F32), FLT_MIN)  # fmaxf: a NaN gives the other operand
+        delta = (mean2 - mean1).astype(F32)
+        t[i] = (np.abs(delta.astype(np.float64)) / np.sqrt((var / wf).astype(F32).astype(np.float64))).astype(F32)
+    return t
+
+
+def _gt32(a, b, h):
+    """(float) (a - b) > h for float32 values held as Python floats: in double when that cannot differ, else in float32"""
+    d = a - b
+    if d != d:
+        return False
+    if abs(d - h) > 1e-6 * abs(h) or h == 0.0:
+        return d > h
+    with np.errstate(all="ignore"):
+        return bool(F32(a) - F32(b) > F32(h))
+
+
+def yard_peaks(t1, t2, prm):
+    """short_long_peak_detector, events.c:371-443, statement for statement"""
+    w = (int(prm[0]), int(prm[1]))
+    thr = (float(F32(prm[2])), float(F32(prm[3])))
+    h = float(F32(prm[4]))
+    sig = (t1.astype(np.float64).tolist(), t2.astype(np.float64).tolist())
+    masked, pos, val, valid = [0, 0], [-1, -1], [FLT_MAX, FLT_MAX], [False, False]
+    peaks = []
+    for i in range(len(sig[0])):
+        for k in (0, 1):
+            if masked[k] >= i:
+                continue
+            cur = sig[k][i]
+            if pos[k] == -1:
+                if cur < val[k]:
+                    val[k] = cur
+                elif _gt32(cur, val[k], h):
+                    val[k] = cur
+                    pos[k] = i
+            else:
+                if cur > val[k]:
+                    val[k] = cur
+                    pos[k] = i
+                if k == 0 and val[0] > thr[0]:
+                    masked[1] = pos[0] + w[0]
+                    pos[1] = -1
+                    val[1] = FLT_MAX
+                    valid[1] = False
+                if _gt32(val[k], cur, h) and val[k] > thr[k]:
+                    valid[k] = True
+                if valid[k] and (i - pos[k]) > w[k] // 2:
+                    peaks.append(pos[k])
+                    pos[k] = -1
+                    val[k] = cur
+                    valid[k] = False
+    return peaks
+
+
+def yard_events(s, c0, c1, prm):
+    """-> uint32 [k, 4]: start, length, mean bits, stdv bits.  No peak: one event [0, n); n = 0: none"""
+    n = len(s)
+    if n == 0:
+        return np.zeros((0, 4), dtype=np.uint32)
+    x = picoamperes(s, c0, c1)
+    with np.errstate(all="ignore"):
+        S, Q = yard_sums(x)
+        peaks = yard_peaks(yard_tstat(S, Q, n, int(prm[0])), yard_tstat(S, Q, n, int(prm[1])), prm)
+        b = np.array([0] + peaks + [n], dtype=np.int64)
+        start, end = b[:-1], b[1:]
+        length = (end - start).astype(F32)
+        mean = ((S[end] - S[start]).astype(F32) / length).astype(F32)
+        dq = (Q[end] - Q[start]).astype(F32)
+        var = ((dq / length).astype(F32) - (mean * mean).astype(F32)).astype(F32)
+        stdv = np.sqrt(np.fmax(var, F32(0))).astype(F32)
+    out = np.zeros((len(start), 4), dtype=np.uint32)
+    out[:, 0] = start
+    out[:, 1] = end - start
+    out[:, 2] = mean.view(np.uint32)
+    out[:, 3] = stdv.view(np.uint32)
+    return out
+
+
+def sums_cannot_round(v, n):
+    """the per-read test of the device: every non-zero v a multiple of 2^q and n * max|v| < 2^(q + 53), with the device's
+    bounds (|v| < 2^E from the largest exponent, n <= 2^L)"""
+    b = v.astype(F32).view(np.uint32) & 0x7FFFFFFF
+    b = b[b != 0]
+    if b.size == 0:
+        return True
+    e = (b >> 23).astype(np.int64)
+    if (e == 255).any():
+        return False
+    m = np.where(e > 0, (b & 0x7FFFFF) | 0x800000, b).astype(np.int64)
+    low = int((np.log2((m & -m).astype(np.float64)).astype(np.int64) + np.maximum(e, 1) - 150).min())
+    E = int(max(int(e.max()), 1)) - 126
+    Lg = 0 if n <= 1 else int(n - 1).bit_length()
+    return E + Lg <= low + 53
+
+
+def serial_expected(s, c0, c1):
+    x = picoamperes(s, c0, c1)
+    with np.errstate(all="ignore"):
+        return not (sums_cannot_round(x, len(s)) and sums_cannot_round((x * x).astype(F32), len(s)))
+
+
+# ------------------------------------------------------------------ inputs
+
+def fixture():
+    return json.load(open(os.path.join(GOLD, "sigtk_events.json")))
+
+
+_named = {}
+
+
+def named_reads():
+    if not _named:
+        flat = np.fromfile(os.path.join(GOLD, "three_reads.i16.bin"), dtype=np.int16)
+        o = 0
+        for r in json.load(open(os.path.join(GOLD, "three_reads.json")))["reads"]:
+            _named["three_reads/" + r["read_id"]] = flat[o:o + r["n"]].copy()
+            o += r["n"]
+        for name, s in L.battery():
+            _named["battery/" + name] = s
+    return _named
+
+
+_yard = {}
+
+
+def yard(key, s, c0, c1, prm):
+    """yard_events, once per (key, calibration, parameters): the reference of every test that needs it"""
+    k = (key, int(F32(c0).view(np.uint32)), int(F32(c1).view(np.uint32)), tuple(prm))
+    if k not in _yard:
+        _yard[k] = yard_events(s, c0, c1, prm)
+        _yard[k].setflags(write=False)
+    return _yard[k]
+
+
+def bits_f32(b):
+    return np.array([b], dtype=np.uint32).view(F32)[0]
+
+
+def _walk(rng, n, lo=-12, hi=13, base=480):
+    return (np.cumsum(rng.integers(lo, hi, size=n)) + base).astype(np.int64).astype(np.uint16).view(np.int16)
+
+
+def levels(rng, n, cuts, noise=3):
+    """a read of flat levels with a little noise and a level change at every position of `cuts`"""
+    lv = np.zeros(n, dtype=np.int64)
+    cur = 400
+    prev = 0
+    for k, c in enumerate(sorted(cuts) + [n]):
+        lv[prev:c] = cur
+        cur += 90 if k % 2 == 0 else -70
+        prev = c
+    return (lv + rng.integers(-noise, noise + 1, size=n)).astype(np.int16)
+
+
+CAL_A = cal32(6.0, 1467.61 / 8192.0)
+CAL_B = cal32(-243.0, 748.58 / 2048.0)
+
+
+# ------------------------------------------------------------------ without a GPU
+
+@pytest.fixture(scope="module")
+def cpu_lib():
+    from honours_amd import build
+    build.build()
+    return press.load_library()
+
+
+def test_yardstick_equals_the_reference():
+    """every entry of sigtk_events.json: the count, the digest of all records, the first and last eight in clear; and the
+    starts strictly increase"""
+    doc = fixture()
+    reads = named_reads()
+    assert len(doc["entries"]) == 36
+    for e in doc["entries"]:
+        s = reads[e["name"]]
+        assert len(s) == e["n"]
+        c0, c1 = bits_f32(e["cal_bits"][0]), bits_f32(e["cal_bits"][1])
+        ev = yard(e["name"], s, c0, c1, PRESETS[e["preset"]])
+        tag = (e["name"], e["cal_bits"], e["preset"])
+        assert len(ev) == e["count"], tag
+        assert ev[:8].tolist() == e["first"] and ev[-8:].tolist() == e["last"], tag
+        packed = b"".join(struct.pack("<IIII", *map(int, r)) for r in ev)
+        assert hashlib.sha256(packed).hexdigest() == e["sha256"], tag
+        assert (np.diff(ev[:, 0].astype(np.int64)) > 0).all() and ev[0, 0] == 0, tag
+        assert int(ev[:, 1].astype(np.int64).sum()) == e["n"], tag
+
+
+def test_fixture_calibrations():
+    doc = fixture()
+    want = {(int(CAL_A[0].view(np.uint32)), int(CAL_A[1].view(np.uint32))), (int(CAL_B[0].view(np.uint32)), int(CAL_B[1].view(np.uint32)))}
+    assert {tuple(e["cal_bits"]) for e in doc["entries"]} == want
+
+
+def tiny_read():
+    return _walk(np.random.default_rng(500001), 6000, -3, 4, 500)
+
+
+def test_rounding_condition_on_the_inputs():
+    """the sums of the three real reads cannot round under either calibration; those of the offset = -500.001 read can
+    (and those of some battery reads: samples next to -offset make squares far below the largest)"""
+    for name in {e["name"] for e in fixture()["entries"]}:
+        for c in (CAL_A, CAL_B):
+            assert name.startswith("battery/") or not serial_expected(named_reads()[name], *c), name
+    assert serial_expected(tiny_read(), *cal32(*TINY_CAL))
+    assert not any(serial_expected(s, *CAL_A) for s in ordinary_reads()[0])
+    x = picoamperes(tiny_read(), *cal32(*TINY_CAL))
+    assert 0 < np.abs(x[x != 0]).min() < 2.5e-4
+
+
+def test_presets(cpu_lib):
+    for rna, name in ((False, "dna"), (True, "rna")):
+        p = press.event_params(rna)
+        want = PRESETS[name]
+        assert (p.w1, p.w2) == want[:2]
+        assert [F32(p.threshold1), F32(p.threshold2), F32(p.peak_height)] == [F32(v) for v in want[2:]]
+    assert cpu_lib.press_hip_event_params_preset(0, None) == EARG
+    assert ctypes.sizeof(press.EventParams) == 20 and press.EVENT_DTYPE.itemsize == 16
+
+
+def test_symbols_and_header(cpu_lib):
+    header = open(os.path.join(os.path.dirname(GOLD), "..", "include", "press_hip.h")).read()
+    for s in ("press_hip_event_params_preset", "press_hip_signal_events", "press_hip_signal_events_workspace_bytes",
+              "press_hip_events_serial_reads"):
+        assert hasattr(cpu_lib, s) and s in press.HEADER_SYMBOLS and s + "(" in header, s
+
+
+def test_bad_arguments(cpu_lib):
+    """NULL arguments and window lengths outside 2 .. 64 are PRESS_HIP_EARG before any device call: the same with and
+    without a device"""
+    lib = cpu_lib
+    a = np.zeros(64, dtype=np.uint64)
+    p = a.ctypes.data
+    ok = press.event_params()
+    q = ctypes.addressof(ok)
+    for dr in (0, 1):
+        args = [p, p, p, 1, 8, p, q, p, 4, p, p]
+        for k in (0, 1, 2, 5, 6, 9, 10):
+            bad = list(args)
+            bad[k] = None
+            assert lib.press_hip_signal_events(*bad, dr) == EARG, (k, dr)
+            assert "NULL" in press.last_error()
+        assert lib.press_hip_signal_events(p, p, p, 1, 8, p, q, None, 4, p, p, dr) == EARG  # no records, but a capacity
+        for w1, w2 in ((1, 6), (0, 6), (65, 6), (3, 1), (3, 65), (3, 1 << 31)):
+            prm = press.EventParams(w1, w2, 1.4, 9.0, 0.2)
+            assert lib.press_hip_signal_events(*args[:6], ctypes.addressof(prm), *args[7:], dr) == EARG, (w1, w2, dr)
+            assert "window" in press.last_error()
+    assert lib.press_hip_signal_events(p + 2, p, p, 1, 8, p, q, p, 4, p, p, 1) == EARG and "aligned" in press.last_error()
+
+
+def test_workspace(cpu_lib):
+    """0 for an empty batch, monotone in both arguments, and nothing per sample: the sums never reach memory"""
+    ws = press.signal_events_workspace_bytes
+    assert ws(0, 0) == 0 and ws(1 << 30, 0) == 0
+    last = 0
+    for r in (1, 2, 64, 300, 8192, 100000):
+        for t in (0, 1000, 930_000_000, 1 << 40):
+            assert ws(t, r) == 8 * r
+        assert ws(1000, r) > last
+        last = ws(1000, r)
+
+
+# ------------------------------------------------------------------ GPU plumbing
+
+@pytest.fixture(scope="module")
+def lib():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    lb = press.load_library()
+    press.use_torch_stream()
+    yield lb
+    torch.cuda.synchronize()
+    press.use_torch_stream()
+    torch.cuda.empty_cache()
+
+
+def _t(a, dtype=None):
+    import torch
+    a = np.ascontiguousarray(a)
+    if dtype is not None:
+        a = a.view(dtype)
+    return torch.from_numpy(a.copy()).cuda()
+
+
+GUARD = 64
+CANARY32 = 0x5AC35AC3
+
+
+class Dev:
+    """a batch on the device in a scattered layout, and its output arrays between canaries"""
+
+    def __init__(self, reads, cals, seed=1):
+        import torch
+        rng = np.random.default_rng(seed)
+        self.reads = reads
+        self.nr = len(reads)
+        sig, off = L.scatter_reads(rng, reads)
+        self.sig, self.off = _t(sig), _t(off, np.int64)
+        self.n = _t(np.array([len(r) for r in reads], dtype=np.uint32), np.int32)
+        self.cal = _t(np.array(cals, dtype=F32).reshape(-1))
+        self.first = torch.full((self.nr + 1 + 2 * GUARD,), 0x5AC35AC35AC35AC3, dtype=torch.int64, device="cuda")
+        self.count = torch.full((self.nr + 2 * GUARD,), CANARY32, dtype=torch.int32, device="cuda")
+
+    def run(self, prm, cap=None, rows=None):
+        """cap None: a pure count first, then with exactly what the batch needs.  -> (ev [k, 4] uint32 of the rows below
+        the capacity, ev_first, ev_count); the canaries around all three are checked"""
+        import torch
+        p = press.EventParams(*prm)
+        f = self.first[GUARD:GUARD + self.nr + 1]
+        c = self.count[GUARD:GUARD + self.nr]
+        if cap is None:
+            press.signal_events(self.sig, self.off, self.n, self.cal, p, None, f, c)
+            cap = int(f[-1].item())
+        rows = cap if rows is None else rows
+        ev = torch.full((rows + 2 * GUARD, 4), CANARY32, dtype=torch.int32, device="cuda")
+        self.first.fill_(0x5AC35AC35AC35AC3)
+        self.count.fill_(CANARY32)
+        press.signal_events(self.sig, self.off, self.n, self.cal, p, ev[GUARD:GUARD + rows] if rows else None, f, c, ev_cap=cap)
+        torch.cuda.synchronize()
+        evh = ev.cpu().numpy().view(np.uint32)
+        fh = self.first.cpu().numpy().view(np.uint64)
+        ch = self.count.cpu().numpy().view(np.uint32)
+        assert (evh[:GUARD] == CANARY32).all() and (evh[GUARD + cap:] == CANARY32).all(), "a record outside [0, ev_cap)"
+        assert (fh[:GUARD] == 0x5AC35AC35AC35AC3).all() and (fh[GUARD + self.nr + 1:] == 0x5AC35AC35AC35AC3).all()
+        assert (ch[:GUARD] == CANARY32).all() and (ch[GUARD + self.nr:] == CANARY32).all()
+        return evh[GUARD:GUARD + cap], fh[GUARD:GUARD + self.nr + 1].copy(), ch[GUARD:GUARD + self.nr].copy()
+
+
+def one_nan(a):
+    """every NaN of the two float columns as one bit pattern (IEEE 754 leaves a NaN's sign and payload open)"""
+    a = a.copy()
+    f = a[:, 2:].view(F32)
+    a[:, 2:][np.isnan(f)] = 0x7FC00000
+    return a
+
+
+def check(got, want, cap=None, nan_equal=False):
+    """got = (ev, first, count) against the per-read records `want`: the layout, the counts, every field"""
+    ev, first, count = got
+    if nan_equal:
+        ev, want = one_nan(ev), [one_nan(w) for w in want]
+    k = np.array([len(w) for w in want], dtype=np.uint64)
+    assert first[0] == 0 and np.array_equal(first[1:], np.cumsum(k)), "ev_first"
+    cap = int(first[-1]) if cap is None else cap
+    for r, w in enumerate(want):
+        if int(first[r + 1]) <= cap:
+            assert count[r] == len(w), (r, count[r], len(w))
+            g = ev[int(first[r]):int(first[r + 1])]
+            if not np.array_equal(g, w):
+                bad = np.nonzero((g != w).any(axis=1))[0]
+                raise AssertionError("read %d (n = %d): %d of %d records differ, the first at %d: %s, expected %s"
+                                     % (r, int(w[:, 1].astype(np.int64).sum()), len(bad), len(w), bad[0], g[bad[0]], w[bad[0]]))
+        else:
+            assert count[r] == NOFIT, (r, count[r])
+
+
+def wants(keys, reads, cals, prm):
+    return [yard(k, s, c[0], c[1], prm) for k, s, c in zip(keys, reads, cals)]
+
+
+# ------------------------------------------------------------------ on the GPU
+
+def fixture_batch():
+    names = sorted({e["name"] for e in fixture()["entries"]})
+    reads = [named_reads()[k] for k in names]
+    return names, reads
+
+
+@gpu
+@pytest.mark.parametrize("preset", ["dna", "rna"])
+def test_fixture_reads(lib, preset):
+    """the reads of the fixture under both calibrations, scattered: what the reference gave (through the yardstick, which
+    test_yardstick_equals_the_reference pins to it).  The serial sums are taken by exactly the reads whose sums can
+    round, once per call that counts: by none of the real reads"""
+    names, reads = fixture_batch()
+    for cal in (CAL_A, CAL_B):
+        cals = [cal] * len(reads)
+        serial = [k for k, s in enumerate(reads) if serial_expected(s, *cal)]
+        assert not any(names[k].startswith("three_reads/") for k in serial)
+        before = press.events_serial_reads()
+        check(Dev(reads, cals, seed=3).run(PRESETS[preset]), wants(names, reads, cals, PRESETS[preset]))
+        assert press.events_serial_reads() == before + 2 * len(serial)  # (Dev.run: a pure count, then the call)
+
+
+@gpu
+def test_fixture_reads_custom_windows(lib):
+    """w1 = 2 and w2 = 64, the ends of the range, on the shorter fixture reads and a real one"""
+    names, reads = fixture_batch()
+    pick = [k for k, (nm, s) in enumerate(zip(names, reads)) if len(s) <= 20000]
+    pick.append(min((k for k in range(len(names)) if names[k].startswith("three_reads/")), key=lambda k: len(reads[k])))
+    names, reads = [names[k] for k in pick], [reads[k] for k in pick]
+    cals = [CAL_A if k % 2 else CAL_B for k in range(len(reads))]
+    check(Dev(reads, cals, seed=4).run(CUSTOM), wants(names, reads, cals, CUSTOM))
+
+
+LENGTHS = sorted({0, 1, 2, 3, 5, 6, 7, 11, 12, 13, 14, 27, 28, 29, 127, 128, 129, TILE - 1, TILE, TILE + 1, 2 * TILE - 1,
+                  2 * TILE, 2 * TILE + 1, 3 * TILE - 1, 3 * TILE, 3 * TILE + 1})
+
+
+@gpu
+@pytest.mark.parametrize("prm", [PRESETS["dna"], PRESETS["rna"], CUSTOM], ids=["dna", "rna", "custom"])
+def test_lengths_around_the_thresholds(lib, prm):
+    """n < 2w, n = 2w, one window either side, one sample either side of the walk's tile and of twice the tile"""
+    rng = np.random.default_rng(77)
+    reads, keys = [], []
+    for n in LENGTHS:
+        for v in range(2):
+            reads.append(levels(rng, n, [c for c in (n // 3, 2 * n // 3) if 0 < c < n]) if v else _walk(rng, n))
+            keys.append("len-%d-%d" % (n, v))
+    cals = [CAL_A if k % 3 else CAL_B for k in range(len(reads))]
+    got = Dev(reads, cals, seed=5).run(prm)
+    check(got, wants(keys, reads, cals, prm))
+    assert got[2][0] == 0 and got[2][2] == 1  # n = 0: no event; n = 1: one
+
+
+@gpu
+@pytest.mark.parametrize("prm", [PRESETS["dna"], PRESETS["rna"], CUSTOM], ids=["dna", "rna", "custom"])
+def test_stepped_reads(lib, prm):
+    """level changes at and next to the tile boundaries 64, 128, 192 and 256: the peak, its windows i - w and i + w and the
+    event boundary fall on both sides of them"""
+    rng = np.random.default_rng(78)
+    reads, keys = [], []
+    w2 = int(prm[1])
+    for d in range(-4, 5):
+        for shift in (0, w2, -w2):
+            cuts = sorted({c for c in (64 + d + shift, 128 + d, 192 + d - shift, 256 + d + shift, 300) if 0 < c < 330})
+            reads.append(levels(rng, 330, cuts, noise=2))
+            keys.append("step-%d-%d-%d" % (d, shift, w2))
+    cals = [CAL_A] * len(reads)
+    got = Dev(reads, cals, seed=6).run(prm)
+    want = wants(keys, reads, cals, prm)
+    check(got, want)
+    starts = np.concatenate([w[:, 0] for w in want])
+    assert len({int(s) for s in starts} & {63, 64, 65, 127, 128, 129}) >= 3, "the inputs put no boundary at a tile's edge"
+
+
+@gpu
+def test_constant_reads_and_reads_without_a_peak(lib):
+    """the one-event rule: [0, n) with the mean and the deviation of the whole read.  (A long constant read need not be
+    without a peak: where the sequential sums round, the two windows' means differ in the last place and the variance is
+    FLT_MIN, so the 1000-sample read has two events under the DNA preset.  The definition decides, not the name.)"""
+    rng = np.random.default_rng(79)
+    reads = [np.full(n, v, dtype=np.int16) for n, v in ((1, 7), (50, -1234), (150, 0), (1000, 500), (4000, -32768))]
+    reads += [_walk(rng, n) for n in (4, 5)] + [(np.arange(700) // 7 + 300).astype(np.int16)]
+    keys = ["flat-%d" % k for k in range(len(reads))]
+    cals = [CAL_A] * len(reads)
+    for prm in (PRESETS["dna"], PRESETS["rna"]):
+        want = wants(keys, reads, cals, prm)
+        single = [r for r in range(7) if len(want[r]) == 1]
+        assert len(single) >= 6 and {0, 1, 2, 5, 6} <= set(single)
+        got = Dev(reads, cals, seed=7).run(prm)
+        check(got, want)
+        for r in single:
+            assert got[0][int(got[1][r])].tolist()[:2] == [0, len(reads[r])]
+
+
+@gpu
+def test_ragged_short_reads(lib):
+    rng = np.random.default_rng(80)
+    ns = rng.integers(0, 400, size=300)
+    reads = [_walk(rng, int(n)) if k % 3 else levels(rng, int(n), [int(n) // 2] if n > 2 else []) for k, n in enumerate(ns)]
+    keys = ["ragged-%d" % k for k in range(300)]
+    cals = [CAL_A if k % 2 else CAL_B for k in range(300)]
+    check(Dev(reads, cals, seed=8).run(PRESETS["dna"]), wants(keys, reads, cals, PRESETS["dna"]))
+
+
+def ordinary_reads():
+    rng = np.random.default_rng(81)
+    return [_walk(rng, n) for n in (900, 64, 2500, 0, 129)], ["ord-%d" % k for k in range(5)]
+
+
+@gpu
+def test_serial_sums(lib):
+    """the offset = -500.001 read takes the serial sums - the counter rises by exactly one - and equals the definition;
+    inside a batch of ordinary reads it leaves their results as they are, and they do not count"""
+    prm = PRESETS["dna"]
+    tiny, tcal = tiny_read(), cal32(*TINY_CAL)
+    want_tiny = yard("tiny", tiny, tcal[0], tcal[1], prm)
+    assert len(want_tiny) > 100
+    d = Dev([tiny], [tcal], seed=9)
+    c0 = press.events_serial_reads()
+    got = d.run(prm, cap=len(want_tiny))
+    assert press.events_serial_reads() == c0 + 1
+    check(got, [want_tiny])
+    reads, keys = ordinary_reads()
+    cals = [CAL_A] * len(reads)
+    want = wants(keys, reads, cals, prm)
+    c0 = press.events_serial_reads()
+    alone = Dev(reads, cals, seed=10).run(prm, cap=sum(len(w) for w in want))
+    assert press.events_serial_reads() == c0
+    check(alone, want)
+    mixed_reads = reads[:2] + [tiny] + reads[2:]
+    mixed_cals = cals[:2] + [tcal] + cals[2:]
+    mixed_want = want[:2] + [want_tiny] + want[2:]
+    got = Dev(mixed_reads, mixed_cals, seed=11).run(prm, cap=sum(len(w) for w in mixed_want))
+    assert press.events_serial_reads() == c0 + 1
+    check(got, mixed_want)
+
+
+@gpu
+def test_nan_and_inf_calibrations(lib):
+    """cal is not validated: NaN and inf propagate as the definition says, and nothing is written outside the rooms"""
+    reads, keys = ordinary_reads()
+    reads, keys = reads[:3], keys[:3]
+    cals = [cal32(np.nan, 0.18), cal32(6.0, np.inf), cal32(3e38, 3e38)]
+    keys = [k + "-nonfinite" for k in keys]
+    check(Dev(reads, cals, seed=12).run(PRESETS["dna"]), wants(keys, reads, cals, PRESETS["dna"]), nan_equal=True)
+
+
+@gpu
+def test_capacity(lib):
+    """ev_cap at the total, one below it and 0: the same ev_first, UINT32_MAX on exactly the reads that do not fit, no
+    record at or beyond ev_cap (the canaries of Dev.run), the records below it as with room for all"""
+    reads, keys = ordinary_reads()
+    rng = np.random.default_rng(82)
+    reads, keys = reads + [_walk(rng, 300)], keys + ["cap-last"]
+    cals = [CAL_B] * len(reads)
+    prm = PRESETS["dna"]
+    want = wants(keys, reads, cals, prm)
+    total = sum(len(w) for w in want)
+    d = Dev(reads, cals, seed=13)
+    full = d.run(prm, cap=total)
+    check(full, want)
+    assert (full[2] != NOFIT).all()
+    for cap in (total - 1, len(want[0]) + len(want[1]), 0):
+        got = d.run(prm, cap=cap, rows=total)
+        assert np.array_equal(got[1], full[1])
+        check(got, want, cap=cap)
+        fits = full[1][1:] <= cap
+        assert np.array_equal(got[2] != NOFIT, fits) and not fits.all()
+    # a pure count: no records at all
+    got = d.run(prm, cap=0, rows=0)
+    assert np.array_equal(got[1], full[1])
+
+
+@gpu
+def test_repeatable_and_independent_of_scratch(lib):
+    import torch
+    reads, keys = ordinary_reads()
+    reads = reads + [tiny_read()]
+    cals = [CAL_A] * 5 + [cal32(*TINY_CAL)]
+    d = Dev(reads, cals, seed=14)
+    a = d.run(PRESETS["rna"])
+    b = d.run(PRESETS["rna"])
+    torch.cuda.synchronize()
+    press.scratch_fill(0xA5)
+    c = d.run(PRESETS["rna"])
+    for x in (b, c):
+        assert all(np.array_equal(p, q) for p, q in zip(a, x))
+    check(a, wants(keys + ["tiny"], reads, cals, PRESETS["rna"]))
+
+
+@gpu
+def test_host_form(lib):
+    """host pointers: the same records, layout and counts as device resident, with room for all, with less, and for an
+    empty batch"""
+    reads, keys = ordinary_reads()
+    reads, cals = reads + [tiny_read()], [CAL_A] * 5 + [cal32(*TINY_CAL)]
+    prm = PRESETS["dna"]
+    dev = Dev(reads, cals, seed=15).run(prm)
+    p = press.EventParams(*prm)
+    ev, first, count = press.signal_events_host(reads, np.array(cals, dtype=F32), p)
+    assert np.array_equal(ev.view(np.uint32).reshape(-1, 4), dev[0]) and np.array_equal(first, dev[1]) and np.array_equal(count, dev[2])
+    press.scratch_fill(0xA5)
+    cap = int(first[3]) + 1
+    ev2, first2, count2 = press.signal_events_host(reads, np.array(cals, dtype=F32), p, ev_cap=cap)
+    assert np.array_equal(first2, first) and len(ev2) == cap
+    fits = first[1:] <= cap
+    assert np.array_equal(count2 != NOFIT, fits) and np.array_equal(count2[fits], count[fits])
+    k = int(first[1:][fits].max())
+    assert np.array_equal(ev2[:k], ev[:k]) and not ev2[k:].view(np.uint32).any()  # the room of a read that did not fit: zeros
+    ev0, first0, count0 = press.signal_events_host([], np.zeros((0, 2), dtype=F32), p)
+    assert len(ev0) == 0 and first0.tolist() == [0] and len(count0) == 0
+
+
+@gpu
+def test_stream_contract(lib):
+    """device resident, on a side stream behind a delay: the call returns while the delay is pending - it only enqueues -
+    and its results are those of the same call made with nothing pending"""
+    import torch
+    reads, keys = ordinary_reads()
+    cals = [CAL_A] * len(reads)
+    prm = PRESETS["dna"]
+    want = wants(keys, reads, cals, prm)
+    total = sum(len(w) for w in want)
+    d = Dev(reads, cals, seed=16)
+    p = press.EventParams(*prm)
+    ev = torch.zeros((total, 4), dtype=torch.int32, device="cuda")
+    first = torch.zeros(len(reads) + 1, dtype=torch.int64, device="cuda")
+    count = torch.zeros(len(reads), dtype=torch.int32, device="cuda")
+    torch.cuda._sleep(100000)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    torch.cuda._sleep(20000000)
+    b.record()
+    b.synchronize()
+    hold_ms = 50.0
+    cycles = int(hold_ms * 20000000 / a.elapsed_time(b))
+    s = torch.cuda.Stream()
+    assert s.cuda_stream != 0 and lib.press_hip_set_stream(ctypes.c_void_p(s.cuda_stream)) == 0
+    try:
+        with torch.cuda.stream(s):
+            press.signal_events(d.sig, d.off, d.n, d.cal, p, ev, first, count)  # (scratch reserved: nothing left to allocate)
+        s.synchronize()
+        ev.zero_()
+        torch.cuda.synchronize()
+        e = torch.cuda.Event()
+        t0 = time.perf_counter()
+        with torch.cuda.stream(s):
+            torch.cuda._sleep(cycles)
+            e.record(s)
+            press.signal_events(d.sig, d.off, d.n, d.cal, p, ev, first, count)
+        t1 = time.perf_counter()
+        assert not e.query(), "a call that promises only to enqueue waited for the stream (or the delay ended early)"
+        s.synchronize()
+        assert e.query()
+        print("signal_events: %.3f ms of host time behind a delay of %g ms" % ((t1 - t0) * 1e3, hold_ms))
+        check((ev.cpu().numpy().view(np.uint32), first.cpu().numpy().view(np.uint64), count.cpu().numpy().view(np.uint32)), want)
+    finally:
+        torch.cuda.synchronize()
+        press.use_torch_stream()
