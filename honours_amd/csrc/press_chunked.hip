@@ -1455,13 +1455,19 @@ __global__ __launch_bounds__(256) void k_ex_redo_flag(BatchArgs a)
 // HUFF: also the number of Huffman code bits of every wave quarter (ChunkBits), which lets
 // k_huff_encode_chunked place its bits without any chain either.
 // Waves per SIMD the register allocator is asked to leave room for (measured: pass A is slower at 8 - a spill -,
-// the Huffman encoder 16 % faster - 38 instead of 76 registers; the svb and one-byte kernels are slower with any
-// hint: they stream, and the registers hold their loads in flight).
+// the Huffman encoder 16 % faster - 38 instead of 76 registers then, 62 now that it holds two groups of HENC_G
+// sub-tiles, still without a spill; the svb and one-byte kernels are slower with any hint: they stream, and the
+// registers hold their loads in flight).
 #ifndef SCAN_WAVES
 #define SCAN_WAVES 4
 #endif
 #ifndef HENC_WAVES
 #define HENC_WAVES 8
+#endif
+// Sub-tiles of the Huffman encoder behind one full vector-memory wait (a divisor of CK; two groups of them are held in
+// registers: 62 at 4, and 64 is what HENC_WAVES leaves) - see k_huff_encode_chunked
+#ifndef HENC_G
+#define HENC_G 4
 #endif
 template <bool REDO, bool HUFF = false>
 __global__ __launch_bounds__(CWG, SCAN_WAVES) void k_ex_scan_chunked(BatchArgs a)
@@ -1883,91 +1889,117 @@ __global__ __launch_bounds__(CWG, HENC_WAVES) void k_huff_encode_chunked(BatchAr
 	uint8_t *g = payload + (Bq >> 3); // byte of staging bit 0
 	uint32_t fill = nb;               // bits waiting at the front of the staging buffer
 	wave_lds_sync();
-	uint4 raw[2];
-	raw[0] = sub_load(in, n, ws + lane * 8);
-	raw[1] = sub_load(in, n, ws + SUB + lane * 8);
+	// HENC_G sub-tiles to a group.  Between a sample load and its use lie the copy-out loops with a number of stores
+	// the compiler cannot count, so what it puts in front of the samples' first use is s_waitcnt vmcnt(0) - a wait for
+	// everything, the stores' acknowledgements included (on gfx950 stores count in vmcnt, in order).  With a sub-tile
+	// per wait a wave had 1 KB behind every memory round trip and a prefetch overlapped nothing (3.5 TB/s of samples);
+	// now one wait per group covers HENC_G KB, and the other sub-tiles of the group, in front of which no load is
+	// issued, wait for no vector memory at all.
+	static_assert(CK % HENC_G == 0, "a quarter is a whole number of groups");
+	uint4 raw[HENC_G];
+#pragma unroll
+	for (int gi = 0; gi < HENC_G; gi++)
+		raw[gi] = sub_load(in, n, ws + gi * SUB + lane * 8);
 	// the sample in front of the sub-tile (behind the loads above: see k_ex_scan_chunked)
 	uint32_t carry = ws > 0 ? (uint32_t) (uint16_t) in[ws - 1] << 16 : 0u;
 #pragma unroll 1
-	for (int k = 0; k < CK; k++) {
-		const uint32_t sub0 = ws + k * SUB;
-		if (sub0 >= n)
+	for (int kg = 0; kg < CK; kg += HENC_G) {
+		if (ws + kg * SUB >= n)
 			break;
-		const uint32_t i0 = sub0 + lane * 8;
-		const uint4 nxt = k + 2 < CK ? sub_load(in, n, i0 + 2 * SUB) : make_uint4(0, 0, 0, 0);
-		const uint4 z = sub_zd(raw[0], n, i0, carry);
-		raw[0] = raw[1];
-		raw[1] = nxt;
-		const uint32_t zz[4] = { z.x, z.y, z.z, z.w };
-		uint32_t e[8];
-		uint32_t lb = 0;
-		if (sub0 != 0 && sub0 + SUB <= n && !__ballot(((z.x | z.y | z.z | z.w) & 0xFF00FF00u) != 0)) {
-			// a sub-tile of one-byte values only (nearly all are): no mask, no select per sample
+		uint4 cur[HENC_G];
+		// wait first: the empty asm takes the group's samples out of the load registers - they were asked for a group
+		// ago and have landed, what the wait pays for is the acknowledgement of the last sub-tile's stores -, then the
+		// next group's loads go out and have a whole group's work to arrive.  (The other order - issue the next
+		// group's loads, then use this one, as pass A does - makes the same wait cover the loads just issued:
+		// measured at this order's time or 20 us above it, never below)
 #pragma unroll
-			for (int h = 0; h < 8; h++) {
-				e[h] = enc[(zz[h >> 1] >> (16 * (h & 1))) & 0xFFu];
-				lb += e[h] >> 24;
-			}
-		} else {
-			const uint32_t lowm = low_mask(z, i0, n);
-#pragma unroll
-			for (int h = 0; h < 8; h++) {
-				e[h] = enc[((lowm >> h) & 1u) ? ((zz[h >> 1] >> (16 * (h & 1))) & 0xFFu) : 256u];
-				lb += e[h] >> 24;
-			}
+		for (int gi = 0; gi < HENC_G; gi++) {
+			typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+			u32x4 t = { raw[gi].x, raw[gi].y, raw[gi].z, raw[gi].w };
+			asm volatile("" : "+v"(t));
+			cur[gi] = make_uint4(t.x, t.y, t.z, t.w);
 		}
-		const uint32_t inc = wave_incl_scan_dpp(lb);
-		const uint32_t tot = (uint32_t) __builtin_amdgcn_readlane((int) inc, 63);
-		uint32_t pos = fill + inc - lb;
-		if (lb <= 64) {
-			// the lane's codes side by side in two registers (8 codes of the NA12878 table: 43 bits on
-			// average, more than 64 in one lane of 700), then at most three LDS atomics
-			uint64_t acc = 0;
-			uint32_t o = 0;
 #pragma unroll
-			for (int h = 0; h < 8; h++) {
-				acc |= (uint64_t) (e[h] & 0xFFFFFFu) << o;
-				o += e[h] >> 24;
-			}
-			const uint32_t sh = pos & 31u;
-			const uint64_t lo2 = acc << sh;
-			const uint32_t w2 = sh ? (uint32_t) (acc >> 32) >> (32u - sh) : 0u;
-			if ((uint32_t) lo2)
-				atomicOr(&stg[pos >> 5], (uint32_t) lo2);
-			if ((uint32_t) (lo2 >> 32))
-				atomicOr(&stg[(pos >> 5) + 1], (uint32_t) (lo2 >> 32));
-			if (w2)
-				atomicOr(&stg[(pos >> 5) + 2], w2);
-		} else {
+		for (int gi = 0; gi < HENC_G; gi++)
+			raw[gi] = kg + HENC_G < CK ? sub_load(in, n, ws + (kg + HENC_G + gi) * SUB + lane * 8) : make_uint4(0, 0, 0, 0);
 #pragma unroll
-			for (int h = 0; h < 8; h++) {
-				if (e[h]) {
-					const uint64_t wv = (uint64_t) (e[h] & 0xFFFFFFu) << (pos & 31u);
-					if ((uint32_t) wv)
-						atomicOr(&stg[pos >> 5], (uint32_t) wv);
-					if ((uint32_t) (wv >> 32))
-						atomicOr(&stg[(pos >> 5) + 1], (uint32_t) (wv >> 32));
-					pos += e[h] >> 24;
+		for (int gi = 0; gi < HENC_G; gi++) {
+			const uint32_t sub0 = ws + (kg + gi) * SUB;
+			if (sub0 >= n)
+				break;
+			const uint32_t i0 = sub0 + lane * 8;
+			const uint4 z = sub_zd(cur[gi], n, i0, carry);
+			const uint32_t zz[4] = { z.x, z.y, z.z, z.w };
+			uint32_t e[8];
+			uint32_t lb = 0;
+			if (sub0 != 0 && sub0 + SUB <= n && !__ballot(((z.x | z.y | z.z | z.w) & 0xFF00FF00u) != 0)) {
+				// a sub-tile of one-byte values only (nearly all are): no mask, no select per sample
+#pragma unroll
+				for (int h = 0; h < 8; h++) {
+					e[h] = enc[(zz[h >> 1] >> (16 * (h & 1))) & 0xFFu];
+					lb += e[h] >> 24;
+				}
+			} else {
+				const uint32_t lowm = low_mask(z, i0, n);
+#pragma unroll
+				for (int h = 0; h < 8; h++) {
+					e[h] = enc[((lowm >> h) & 1u) ? ((zz[h >> 1] >> (16 * (h & 1))) & 0xFFu) : 256u];
+					lb += e[h] >> 24;
 				}
 			}
+			const uint32_t inc = wave_incl_scan_dpp(lb);
+			const uint32_t tot = (uint32_t) __builtin_amdgcn_readlane((int) inc, 63);
+			uint32_t pos = fill + inc - lb;
+			if (lb <= 64) {
+				// the lane's codes side by side in two registers (8 codes of the NA12878 table: 43 bits on
+				// average, more than 64 in one lane of 700), then at most three LDS atomics
+				uint64_t acc = 0;
+				uint32_t o = 0;
+#pragma unroll
+				for (int h = 0; h < 8; h++) {
+					acc |= (uint64_t) (e[h] & 0xFFFFFFu) << o;
+					o += e[h] >> 24;
+				}
+				const uint32_t sh = pos & 31u;
+				const uint64_t lo2 = acc << sh;
+				const uint32_t w2 = sh ? (uint32_t) (acc >> 32) >> (32u - sh) : 0u;
+				if ((uint32_t) lo2)
+					atomicOr(&stg[pos >> 5], (uint32_t) lo2);
+				if ((uint32_t) (lo2 >> 32))
+					atomicOr(&stg[(pos >> 5) + 1], (uint32_t) (lo2 >> 32));
+				if (w2)
+					atomicOr(&stg[(pos >> 5) + 2], w2);
+			} else {
+#pragma unroll
+				for (int h = 0; h < 8; h++) {
+					if (e[h]) {
+						const uint64_t wv = (uint64_t) (e[h] & 0xFFFFFFu) << (pos & 31u);
+						if ((uint32_t) wv)
+							atomicOr(&stg[pos >> 5], (uint32_t) wv);
+						if ((uint32_t) (wv >> 32))
+							atomicOr(&stg[(pos >> 5) + 1], (uint32_t) (wv >> 32));
+						pos += e[h] >> 24;
+					}
+				}
+			}
+			wave_lds_sync();
+			// completed dwords out (unaligned 4-byte stores), the partial one to the front
+			const uint32_t total = fill + tot;
+			const uint32_t nfull = total >> 5;
+			for (uint32_t c = (uint32_t) lane; c < nfull; c += 64) {
+				const uint32_t v = stg[c];
+				stg[c] = 0;
+				__builtin_memcpy(g + 4ull * c, &v, 4);
+			}
+			if (nfull && lane == 0) {
+				const uint32_t tl = stg[nfull];
+				stg[nfull] = 0;
+				stg[0] = tl;
+			}
+			g += 4ull * nfull;
+			fill = total & 31u;
+			wave_lds_sync();
 		}
-		wave_lds_sync();
-		// completed dwords out (unaligned 4-byte stores), the partial one to the front
-		const uint32_t total = fill + tot;
-		const uint32_t nfull = total >> 5;
-		for (uint32_t c = (uint32_t) lane; c < nfull; c += 64) {
-			const uint32_t v = stg[c];
-			stg[c] = 0;
-			__builtin_memcpy(g + 4ull * c, &v, 4);
-		}
-		if (nfull && lane == 0) {
-			const uint32_t tl = stg[nfull];
-			stg[nfull] = 0;
-			stg[0] = tl;
-		}
-		g += 4ull * nfull;
-		fill = total & 31u;
-		wave_lds_sync();
 	}
 	// whole bytes that are left; a partial last byte belongs to whoever holds its last bit
 	if (lane == 0) {

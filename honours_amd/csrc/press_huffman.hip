@@ -1372,8 +1372,10 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 				land2(Un, Sn);
 			else
 				wave_lds_sync();
-			if (u_nn < nunits)
-				Unn = resolve(u_nn, tv_nn);
+			// (on every path, a missing unit's zero plan too - u_nn says whether it is used: a load that one path leaves
+			// unread counts as pending across the sample stores, and the loop's head would wait for those before it
+			// may write the register again)
+			Unn = resolve(u_nn, tv_nn);
 			HSTAMP(1); // the next units' loads land
 			if (fused) {
 				if (quota) {
@@ -1399,8 +1401,14 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 					{
 						if (U.ecnt <= 64)
 							emit_samples16<false>(stg, exl, R, P, lane);
-						else
+						else {
 							emit_samples16<true>(stg, exl, R, P, lane);
+							// the rare copy searches global memory in its rounds, and not every path reads what
+							// it has asked for: it waits for its own vector memory here - vmcnt(0) alone -, or
+							// the plain path of every later unit would (a register whose load may be pending
+							// makes whoever writes it next wait for everything, the sample stores included)
+							__builtin_amdgcn_s_waitcnt(0x0F70);
+						}
 					}
 					HSTAMP(5); // samples
 				}
