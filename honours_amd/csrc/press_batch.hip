@@ -651,6 +651,137 @@ extern "C" int press_hip_signal_events(const int16_t *sig, const uint64_t *off, 
 	return 0;
 }
 
+// ------------------------------------------------------------------ jnn segments and the adaptor of samples that are already there
+//
+// press_hip_signal_events' layout, staging and two walks; the kernels of press_segments.hip.
+
+static_assert(sizeof(press_hip_segment) == 8 && sizeof(press_hip_jnn_params) == sizeof(SegParams) &&
+		      sizeof(press_hip_jnn2_params) == sizeof(Seg2Params),
+	      "the segment structs");
+
+extern "C" int press_hip_jnn_params_preset(int which, press_hip_jnn_params *prm)
+{
+	if (!prm)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	switch (which) {
+	case 0: *prm = { 0.75f, 50, 50, 150, 0.25f, 5, 0.0f, 0.0f }; return 0;   // JNNV1_CDNA_PARAM, jnn.h:40-49
+	case 1: *prm = { 0.75f, 50, 50, 1000, 1.0f, 5, 0.0f, 0.0f }; return 0;   // JNNV1_DRNA_PARAM, jnn.h:29-38
+	case 2: *prm = { -1.0f, 50, 200, 250, 1.0f, 30, 0.0f, 0.0f }; return 0;  // JNNV1_POLYA, jnn.h:52-61
+	}
+	return set_error(PRESS_HIP_EARG, "preset %d: 0 cDNA, 1 dRNA, 2 poly-A", which);
+}
+
+extern "C" int press_hip_jnn2_params_preset(int which, press_hip_jnn2_params *prm)
+{
+	if (!prm)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	if (which != 0)
+		return set_error(PRESS_HIP_EARG, "preset %d: 0 the dRNA adaptor", which);
+	*prm = { 0.5f, 1500, 2000, 200000, 2000 }; // JNNV2_RNA_ADAPTOR, jnn.h:74-80
+	return 0;
+}
+
+extern "C" int press_hip_signal_segments(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+					 uint64_t total_samples, const float *cal, const press_hip_jnn_params *prm,
+					 press_hip_segment *seg, uint64_t seg_cap, uint64_t *seg_first, uint32_t *seg_count, float *thr,
+					 int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(NONE, NONE, !prm || !seg_first || (nreads && (!sig || !off || !n || !seg_count)) || (!seg && seg_cap), nreads,
+			 device_resident ? sig : nullptr, "sig");
+	if (rc)
+		return rc;
+	if (prm->window < 1 || prm->corrector < 0 || prm->error < 0 || prm->seg_dist < 0 || !std::isfinite(prm->stall_len))
+		return set_error(PRESS_HIP_EARG, "jnn parameters: window %d >= 1, corrector %d, error %d, seg_dist %d >= 0, a finite stall_len",
+				 prm->window, prm->corrector, prm->error, prm->seg_dist);
+	if ((rc = device_ready(NONE, NONE)))
+		return rc;
+	hipStream_t s = g.stream();
+	if (nreads == 0) { // (the layout of no reads: one zero)
+		if (device_resident)
+			HIPCHK(hipMemsetAsync(seg_first, 0, 8, s));
+		else
+			seg_first[0] = 0;
+		return 0;
+	}
+	const SegParams p = { prm->std_scale, prm->corrector, prm->seg_dist, prm->window, prm->stall_len, prm->error, prm->top, prm->bot };
+	const ScratchPlan plan = make_segments_plan(nreads, !device_resident, cal != nullptr);
+	if ((rc = plan.reserve()))
+		return rc;
+	void *state = plan.ptr(&Ctx::sg_state);
+	if (device_resident) {
+		launch_segments_count(sig, off, n, nreads, cal, p, state, seg_cap, seg_first, seg_count, thr, s);
+		if (seg_cap)
+			launch_segments_write(sig, off, n, nreads, cal, p, state, seg, seg_cap, seg_first, s);
+		return launch_status();
+	}
+	SamplesIn in = { sig, off, n };
+	Staged st(nreads, s);
+	if ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in)))
+		return rc;
+	const float *dcal = cal ? (const float *) g.sg_cal.p : nullptr;
+	uint64_t *dfirst = (uint64_t *) g.sg_first.p;
+	uint32_t *dcount = (uint32_t *) g.sg_cnt.p;
+	if (cal)
+		HIPCHK(hipMemcpyAsync(g.sg_cal.p, cal, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	launch_segments_count(in.sig, in.off, in.n, nreads, dcal, p, state, seg_cap, dfirst, dcount, thr ? (float *) g.sg_thr.p : nullptr, s);
+	if ((rc = launch_status()))
+		return rc;
+	HIPCHK(hipMemcpyAsync(seg_first, dfirst, ((size_t) nreads + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(seg_count, dcount, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	if (thr)
+		HIPCHK(hipMemcpyAsync(thr, g.sg_thr.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	const uint64_t have = seg_first[nreads] < seg_cap ? seg_first[nreads] : seg_cap;
+	if (!have)
+		return 0;
+	if (g.sg_out.reserve(have * sizeof(press_hip_segment)))
+		return PRESS_HIP_EHIP;
+	HIPCHK(hipMemsetAsync(g.sg_out.p, 0, have * sizeof(press_hip_segment), s)); // (the room of a read that did not fit: zeros)
+	launch_segments_write(in.sig, in.off, in.n, nreads, dcal, p, state, g.sg_out.p, seg_cap, dfirst, s);
+	if ((rc = launch_status()) || (rc = st.fetch_prefix(seg, g.sg_out.p, have * sizeof(press_hip_segment))))
+		return rc;
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
+extern "C" int press_hip_signal_adaptor(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+					uint64_t total_samples, const press_hip_jnn2_params *prm, int32_t *pair, float *thr,
+					int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(NONE, NONE, !prm || (nreads && (!sig || !off || !n || !pair)), nreads, device_resident ? sig : nullptr, "sig");
+	if (rc)
+		return rc;
+	if (prm->window < 1 || prm->window > 8192)
+		return set_error(PRESS_HIP_EARG, "window = %d: 1 .. 8192 (the window sums stay below 2^24)", prm->window);
+	if ((rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const Seg2Params p = { prm->std_scale, prm->seg_dist, prm->window, prm->hi_thresh, prm->lo_thresh };
+	const ScratchPlan plan = make_adaptor_plan(nreads, !device_resident);
+	if ((rc = plan.reserve()))
+		return rc;
+	if (device_resident) {
+		launch_adaptor(sig, off, n, nreads, p, pair, thr, s);
+		return launch_status();
+	}
+	SamplesIn in = { sig, off, n };
+	Staged st(nreads, s);
+	if ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in)))
+		return rc;
+	launch_adaptor(in.sig, in.off, in.n, nreads, p, (int32_t *) g.sg_out.p, thr ? (float *) g.sg_thr.p : nullptr, s);
+	if ((rc = launch_status()))
+		return rc;
+	HIPCHK(hipMemcpyAsync(pair, g.sg_out.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	if (thr)
+		HIPCHK(hipMemcpyAsync(thr, g.sg_thr.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
 // ------------------------------------------------------------------ recode: streams in, streams out
 //
 // The two halves run one after the other on the stream, inside one call and one lock: the decode of `src` into the

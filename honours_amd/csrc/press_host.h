@@ -72,6 +72,7 @@ struct Ctx {
 	DevBuf ch_rows, ch_first; // chunk rows, host path: the row arena, the staged row_first
 	DevBuf vf_raw, vf_out; // verify / CRC-32: a word per read between the two kernels; host path: the staged crc or first_bad, and nbad
 	DevBuf ev_state, ev_cal, ev_first, ev_cnt, ev_out; // events: count and path per read; host path: the staged calibration, ev_first, ev_count, the records
+	DevBuf sg_state, sg_cal, sg_first, sg_cnt, sg_thr, sg_out; // jnn segments: count and thresholds per read; host path: the staged calibration, seg_first, seg_count, thr, the records (the adaptor: the pairs)
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams
@@ -283,6 +284,12 @@ ScratchPlan make_verify_plan(int method, uint64_t total_samples, uint32_t nreads
 // press_hip_signal_events: 8 bytes per read; host pointers: the staged calibration, ev_first and ev_count (the records'
 // arena is reserved by the call at min(need, ev_cap) once the need is known).  Nothing per sample: the sums stay in LDS
 ScratchPlan make_events_plan(uint32_t nreads, bool host);
+
+// press_hip_signal_segments: 16 bytes per read; host pointers: the staged calibration (with_cal), seg_first, seg_count and
+// thr (the records' arena is reserved by the call, as the events').  Nothing per sample
+ScratchPlan make_segments_plan(uint32_t nreads, bool host, bool with_cal);
+// press_hip_signal_adaptor: no scratch of its own; host pointers: the pairs and thr
+ScratchPlan make_adaptor_plan(uint32_t nreads, bool host);
 
 // press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
 ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);

@@ -403,6 +403,28 @@ void launch_events_count(const int16_t *sig, const uint64_t *off, const uint32_t
 void launch_events_write(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const float *cal,
 			 const EvParams &p, void *state, void *ev, uint64_t ev_cap, const uint64_t *ev_first, hipStream_t s);
 uint32_t events_serial_reads(hipStream_t s); // synchronises s
+// press_segments.hip: sigtk's jnn segments of the n[r] samples at sig + off[r] (include/press_hip.h,
+// press_hip_signal_segments), a wave per read, in two walks as the events; cal NULL: the raw domain; thr NULL, or 2 * nreads.
+// state: segments_state_bytes.  launch_adaptor: jnnv2, one launch, no state.  Timed as ring 1 of press_hip_kernel_times
+struct SegParams { // press_hip_jnn_params
+	float std_scale;
+	int32_t corrector, seg_dist, window;
+	float stall_len;
+	int32_t error;
+	float top, bot;
+};
+struct Seg2Params { // press_hip_jnn2_params
+	float std_scale;
+	int32_t seg_dist, window, hi_thresh, lo_thresh;
+};
+uint64_t segments_state_bytes(uint32_t nreads);
+void launch_segments_count(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const float *cal,
+			   const SegParams &p, void *state, uint64_t seg_cap, uint64_t *seg_first, uint32_t *seg_count, float *thr,
+			   hipStream_t s);
+void launch_segments_write(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const float *cal,
+			   const SegParams &p, void *state, void *seg, uint64_t seg_cap, const uint64_t *seg_first, hipStream_t s);
+void launch_adaptor(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const Seg2Params &p, int32_t *pair,
+		    float *thr, hipStream_t s);
 void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip

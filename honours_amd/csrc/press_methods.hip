@@ -214,6 +214,27 @@ ScratchPlan make_events_plan(uint32_t nreads, bool host)
 	return p;
 }
 
+// Segments: sums and walk state stay in registers, so the scratch does not depend on total_samples either
+ScratchPlan make_segments_plan(uint32_t nreads, bool host, bool with_cal)
+{
+	ScratchPlan p{};
+	p.need(&Ctx::sg_state, segments_state_bytes(nreads));
+	if (host) {
+		p.need(&Ctx::sg_first, ((size_t) nreads + 1) * 8).need(&Ctx::sg_cnt, (size_t) nreads * 4).need(&Ctx::sg_thr, (size_t) nreads * 8);
+		if (with_cal)
+			p.need(&Ctx::sg_cal, (size_t) nreads * 8);
+	}
+	return p;
+}
+
+ScratchPlan make_adaptor_plan(uint32_t nreads, bool host)
+{
+	ScratchPlan p{};
+	if (host)
+		p.need(&Ctx::sg_out, (size_t) nreads * 8).need(&Ctx::sg_thr, (size_t) nreads * 8);
+	return p;
+}
+
 // Fused pairs: BLOW5's and the reference's svb-zd streams into any exception-split method.  (svb12 has no deltas; the zstd
 // kinds and the svb destinations take the general path.)
 bool recode_fused(int src, int dst)
@@ -413,6 +434,14 @@ extern "C" uint64_t press_hip_signal_events_workspace_bytes(uint64_t total_sampl
 {
 	(void) total_samples;
 	return plan_bytes(make_events_plan(nreads, false), false);
+}
+
+// what the device-resident press_hip_signal_segments keeps: 16 bytes per read, nothing per sample, no slices
+// (press_hip_signal_adaptor keeps nothing)
+extern "C" uint64_t press_hip_signal_segments_workspace_bytes(uint64_t total_samples, uint32_t nreads)
+{
+	(void) total_samples;
+	return plan_bytes(make_segments_plan(nreads, false, false), false);
 }
 
 static bool rank_ok(uint32_t num, uint32_t den) { return den > 0 && num <= den; }

@@ -1,0 +1,446 @@
+// press_segments.hip - sigtk's jnn segmenter (press_hip_signal_segments: jnn_core over jnn_raw / jnn_pa, sigtk/src/jnn.c:185-301)
+// and its jnnv2 adaptor finder (press_hip_signal_adaptor, jnn.c:98-178), bit for bit.  DESIGN.md 6.0.28 has the arguments;
+// in short:
+//
+//   k_segments<false>  ONE WAVE PER READ, three passes over the read in tiles of 64 samples, a lane each, four tiles in
+//                      flight.  Pass 1: S, the float sum of x in the reference's order - 64 dependent adds per tile on
+//                      values read lane by lane into a wave-uniform carry.  Pass 2: Q of (x - mn)^2 likewise.  (Both only
+//                      for std_scale > 0.)  Pass 3: the walk.  __ballot of x < top && x > bot is the tile as one
+//                      wave-uniform 64-bit mask, and jnn_core's state machine is stepped over it in scalar registers by
+//                      uniform branches; the stretches where nothing can happen are jumped with a find-first-set.  This
+//                      launch only counts; it leaves the count and the two thresholds per read (16 bytes).
+//   k_segments_scan    one wave: seg_first[] = the exclusive sums of the counts, seg_count[] with the reads that do not fit
+//   k_segments<true>   pass 3 again with the thresholds of the first launch, for the reads that fit, writing the records
+//   k_adaptor          one wave per read, the same three passes over t[j], the rolling mean of `window` samples; the
+//                      window sums are integers (below 2^24, so the reference's rolling float sum never rounds): the sum
+//                      at a tile's first position is carried, the others come from a wave scan of s[j + window] - s[j]
+//
+// A sum starting at +0 is never -0 (a + b = -0 only for a = b = -0), so the +0 that the lanes beyond n add changes nothing.
+
+#include "press_internal.h"
+#include "press_wave.h"
+
+#pragma clang fp contract(off) // every operation below rounds on its own, as the reference's does (x86-64, no FMA)
+
+namespace ph {
+
+constexpr uint32_t SEG_NOFIT = 0xFFFFFFFFu;
+constexpr uint32_t SEG_AHEAD = 4; // tiles whose loads are in flight while a group of as many is worked on
+
+struct SegRec { // press_hip_segment
+	uint32_t start, end;
+};
+struct SegState { // per read, between the launches (16 bytes)
+	uint32_t count, pad;
+	float bot, top;
+};
+
+__device__ __forceinline__ float seg_lane_f32(float v, uint32_t lane)
+{
+	return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int) lane));
+}
+
+// carry + v[0] + v[1] + ... + v[63], added in that order
+__device__ __forceinline__ float seg_chain(float carry, float v)
+{
+#pragma unroll
+	for (uint32_t j = 0; j < 64; j++)
+		carry = carry + seg_lane_f32(v, j);
+	return carry;
+}
+
+__device__ __forceinline__ int32_t seg_clamp(int16_t s) { return s > 1200 ? 1200 : s < 0 ? 0 : (int32_t) s; }
+
+// rm_outlier / rm_outlierf (jnn.c:60-94): a NaN is in neither branch and stays
+__device__ __forceinline__ float seg_x(int16_t s, bool raw, float c0, float c1)
+{
+	if (raw)
+		return (float) seg_clamp(s);
+	const float a = (float) s + c0;
+	const float p = a * c1;
+	return p > 1200.0f ? 1200.0f : p < 0.0f ? 0.0f : p;
+}
+
+// f(t, s): tile t of the read, s the lane's sample (0 beyond n); f returns false to stop
+template <class F>
+__device__ __forceinline__ void seg_tiles(const int16_t *in, uint32_t n, uint32_t lane, F &&f)
+{
+	const uint32_t ntile = (uint32_t) (((uint64_t) n + 63) / 64);
+	int16_t cur[SEG_AHEAD], nxt[SEG_AHEAD];
+	auto load = [&](uint32_t t0, int16_t *v) {
+#pragma unroll
+		for (uint32_t k = 0; k < SEG_AHEAD; k++) {
+			const uint64_t i = (uint64_t) (t0 + k) * 64 + lane;
+			v[k] = i < n ? in[i] : (int16_t) 0;
+		}
+	};
+	load(0, cur);
+	for (uint32_t t0 = 0; t0 < ntile; t0 += SEG_AHEAD) {
+		load(t0 + SEG_AHEAD, nxt);
+#pragma unroll
+		for (uint32_t k = 0; k < SEG_AHEAD; k++) {
+			if (t0 + k < ntile && !f(t0 + k, cur[k]))
+				return;
+			cur[k] = nxt[k];
+		}
+	}
+}
+
+struct SegWalk { // jnn_core's state (jnn.c:200-215) with exact integers, and the last record, which a merge may still change
+	bool prev;
+	uint32_t c, prev_err, start, count, last_start, last_end;
+	uint64_t w;
+	int64_t err;
+};
+
+// One block of 64 lanes per read.  WRITE: the records of a read that fits; else its count and its thresholds.
+template <bool WRITE>
+__global__ __launch_bounds__(64) void k_segments(const int16_t *sig, const uint64_t *off, const uint32_t *nsamp, const float *cal,
+						  SegParams p, SegState *state, float *thr, SegRec *seg, uint64_t seg_cap,
+						  const uint64_t *seg_first)
+{
+	const uint32_t r = blockIdx.x, lane = threadIdx.x;
+	const uint32_t n = uni(nsamp[r]);
+	const bool given = !(p.std_scale > 0.0f);
+	uint64_t first = 0, room = 0; // the read's records: seg[first .. first + room)
+	if (WRITE) {
+		first = uni64(seg_first[r]);
+		const uint64_t end = uni64(seg_first[r + 1]);
+		if (n == 0 || end > seg_cap || end <= first)
+			return;
+		room = end - first;
+	} else if (n == 0) { // no segment and no thresholds of its own
+		if (lane == 0) {
+			state[r] = { 0u, 0u, given ? p.bot : 0.0f, given ? p.top : 0.0f };
+			if (thr) {
+				thr[2 * (size_t) r] = given ? p.bot : 0.0f;
+				thr[2 * (size_t) r + 1] = given ? p.top : 0.0f;
+			}
+		}
+		return;
+	}
+	const int16_t *in = sig + uni64(off[r]);
+	const bool raw = cal == nullptr;
+	float c0 = 0.0f, c1 = 0.0f;
+	if (!raw) {
+		c0 = __int_as_float((int) uni((uint32_t) __float_as_int(cal[2 * (size_t) r])));
+		c1 = __int_as_float((int) uni((uint32_t) __float_as_int(cal[2 * (size_t) r + 1])));
+	}
+
+	float top = p.top, bot = p.bot;
+	if (WRITE) {
+		bot = __int_as_float((int) uni((uint32_t) __float_as_int(state[r].bot)));
+		top = __int_as_float((int) uni((uint32_t) __float_as_int(state[r].top)));
+	} else if (!given) { // meanf, stdvf (stat.h:17-44)
+		float S = 0.0f, Q = 0.0f;
+		seg_tiles(in, n, lane, [&](uint32_t t, int16_t s) {
+			const uint64_t i = (uint64_t) t * 64 + lane;
+			S = seg_chain(S, i < n ? seg_x(s, raw, c0, c1) : 0.0f);
+			return true;
+		});
+		const float nf = (float) n;
+		const float mn = S / nf;
+		seg_tiles(in, n, lane, [&](uint32_t t, int16_t s) {
+			const uint64_t i = (uint64_t) t * 64 + lane;
+			const float d = seg_x(s, raw, c0, c1) - mn;
+			const float q = d * d;
+			Q = seg_chain(Q, i < n ? q : 0.0f);
+			return true;
+		});
+		const float sd = sqrtf(Q / nf);
+		const float k = sd * p.std_scale;
+		top = mn + k;
+		bot = mn - k;
+	}
+
+	// ---- the walk (jnn.c:217-268)
+	const uint32_t window = (uint32_t) p.window;
+	const float stall = (float) p.window * p.stall_len;
+	SegWalk a = { false, 0u, 0u, 0u, 0u, 0u, 0u, (uint64_t) (uint32_t) p.corrector, 0 };
+	auto flush = [&]() { // the last record is final
+		if (WRITE && lane == 0 && (uint64_t) (a.count - 1) < room)
+			seg[first + (a.count - 1)] = { a.last_start, a.last_end };
+	};
+	auto grown = [&]() { // c and w have just been raised
+		if (a.c >= window && (uint64_t) a.c >= a.w && a.c % (uint32_t) a.w == 0)
+			a.err--;
+	};
+	seg_tiles(in, n, lane, [&](uint32_t t, int16_t s) {
+		const uint32_t base = t * 64;
+		const uint64_t i = (uint64_t) base + lane;
+		const float x = seg_x(s, raw, c0, c1);
+		const uint64_t mask = __ballot(i < n && x < top && x > bot);
+		const uint32_t here = n - base < 64 ? n - base : 64;
+		uint32_t pos = 0;
+		while (pos < here) {
+			uint64_t rest = mask >> pos;
+			if (!a.prev) { // an out-of-range sample changes nothing
+				if (!rest)
+					break;
+				pos += (uint32_t) __builtin_ctzll(rest);
+				rest = mask >> pos;
+			}
+			if (rest & 1) {
+				if (!a.prev) {
+					a.start = base + pos;
+					a.prev = true;
+				}
+				a.prev_err = 0;
+				if ((uint64_t) a.c < a.w) { // c and w rise together: c >= w at no sample of the run, err stays
+					const uint32_t k = ~rest ? (uint32_t) __builtin_ctzll(~rest) : 64u;
+					a.c += k;
+					a.w += k;
+					pos += k;
+				} else {
+					a.c++;
+					a.w++;
+					grown();
+					pos++;
+				}
+				continue;
+			}
+			// out of range behind an in-range sample
+			if (a.err < (int64_t) p.error) {
+				a.c++;
+				a.err++;
+				a.prev_err++;
+				grown();
+			} else {
+				if (a.c >= window || (a.count == 0 && (float) a.c >= stall)) {
+					const uint32_t end = base + pos - a.prev_err;
+					if (a.count && (int64_t) a.start - (int64_t) a.last_end < (int64_t) p.seg_dist) {
+						a.last_end = end;
+					} else {
+						if (a.count)
+							flush();
+						a.last_start = a.start;
+						a.last_end = end;
+						a.count++;
+					}
+				}
+				a.prev = false;
+				a.c = 0;
+				a.err = 0;
+				a.prev_err = 0;
+			}
+			pos++;
+		}
+		return true;
+	});
+	if (a.count)
+		flush();
+	if (!WRITE && lane == 0) {
+		state[r] = { a.count, 0u, bot, top };
+		if (thr) {
+			thr[2 * (size_t) r] = bot;
+			thr[2 * (size_t) r + 1] = top;
+		}
+	}
+}
+
+// One wave: seg_first[0] = 0, seg_first[r + 1] = seg_first[r] + count[r]; seg_count[r] = count[r] where the read fits
+__global__ __launch_bounds__(64) void k_segments_scan(const SegState *state, uint32_t nreads, uint64_t seg_cap, uint64_t *seg_first,
+						       uint32_t *seg_count)
+{
+	const uint32_t lane = threadIdx.x;
+	uint64_t before = 0;
+	if (lane == 0)
+		seg_first[0] = 0;
+	for (uint32_t r0 = 0; r0 < nreads; r0 += 64) {
+		const uint32_t r = r0 + lane;
+		const uint32_t c = r < nreads && r >= r0 ? state[r].count : 0u;
+		uint64_t inc = c;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const uint64_t o = __shfl_up(inc, d, 64);
+			if (lane >= (uint32_t) d)
+				inc += o;
+		}
+		if (r < nreads && r >= r0) {
+			seg_first[(size_t) r + 1] = before + inc;
+			seg_count[r] = before + inc <= seg_cap ? c : SEG_NOFIT;
+		}
+		before += __shfl(inc, 63, 64);
+		if (r0 + 64 < r0)
+			break;
+	}
+}
+
+// ------------------------------------------------------------------ jnnv2
+
+// f(t, tv, valid): tile t of the m = n - window rolling means, tv the lane's (valid: its position is below m); f returns
+// false to stop.  W: the integer sum of the window at the tile's first position
+template <class F>
+__device__ __forceinline__ void adaptor_tiles(const int16_t *in, uint32_t m, uint32_t window, uint32_t W, uint32_t lane, F &&f)
+{
+	const uint32_t ntile = (uint32_t) (((uint64_t) m + 63) / 64);
+	const float wf = (float) window;
+	int32_t cur[SEG_AHEAD], nxt[SEG_AHEAD]; // s[j + window] - s[j], clamped each; 0 beyond m
+	auto load = [&](uint32_t t0, int32_t *v) {
+#pragma unroll
+		for (uint32_t k = 0; k < SEG_AHEAD; k++) {
+			const uint64_t j = (uint64_t) (t0 + k) * 64 + lane;
+			v[k] = j < m ? seg_clamp(in[j + window]) - seg_clamp(in[j]) : 0;
+		}
+	};
+	load(0, cur);
+	for (uint32_t t0 = 0; t0 < ntile; t0 += SEG_AHEAD) {
+		load(t0 + SEG_AHEAD, nxt);
+#pragma unroll
+		for (uint32_t k = 0; k < SEG_AHEAD; k++) {
+			if (t0 + k < ntile) {
+				int32_t inc = cur[k];
+#pragma unroll
+				for (int d = 1; d < 64; d <<= 1) {
+					const int32_t o = __shfl_up(inc, d, 64);
+					if (lane >= (uint32_t) d)
+						inc += o;
+				}
+				const uint32_t Wj = W + (uint32_t) (inc - cur[k]); // 0 .. 1200 * window < 2^24: the float is exact
+				const uint64_t j = (uint64_t) (t0 + k) * 64 + lane;
+				if (!f(t0 + k, (float) Wj / wf, j < m))
+					return;
+				W += (uint32_t) __builtin_amdgcn_readlane(inc, 63);
+			}
+			cur[k] = nxt[k];
+		}
+	}
+}
+
+__global__ __launch_bounds__(64) void k_adaptor(const int16_t *sig, const uint64_t *off, const uint32_t *nsamp, Seg2Params p,
+						 int32_t *pair, float *thr)
+{
+	const uint32_t r = blockIdx.x, lane = threadIdx.x;
+	const uint32_t n = uni(nsamp[r]);
+	const uint32_t window = (uint32_t) p.window;
+	if (n <= window) { // (jnn.c:172)
+		if (lane == 0) {
+			pair[2 * (size_t) r] = pair[2 * (size_t) r + 1] = -1;
+			if (thr)
+				thr[2 * (size_t) r] = thr[2 * (size_t) r + 1] = 0.0f;
+		}
+		return;
+	}
+	const int16_t *in = sig + uni64(off[r]);
+	const uint32_t m = n - window;
+	uint32_t W0 = 0;
+	for (uint32_t i = lane; i < window; i += 64)
+		W0 += (uint32_t) seg_clamp(in[i]);
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1)
+		W0 += (uint32_t) __shfl_xor((int) W0, d, 64);
+	W0 = uni(W0);
+
+	float S = 0.0f, Q = 0.0f;
+	adaptor_tiles(in, m, window, W0, lane, [&](uint32_t, float tv, bool valid) {
+		S = seg_chain(S, valid ? tv : 0.0f);
+		return true;
+	});
+	const float mf = (float) m;
+	const float mn = S / mf;
+	adaptor_tiles(in, m, window, W0, lane, [&](uint32_t, float tv, bool valid) {
+		const float d = tv - mn;
+		const float q = d * d;
+		Q = seg_chain(Q, valid ? q : 0.0f);
+		return true;
+	});
+	const float sd = sqrtf(Q / mf);
+	const float bot = mn - sd * p.std_scale;
+
+	// ---- the walk (jnn.c:124-151) and the choice (jnn.c:152-166): the first record, once no merge can change it, with
+	// lo_thresh <= y - x <= hi_thresh
+	bool begin = false, has = false, found = false;
+	uint32_t start = 0, end = 0, lx = 0, ly = 0; // lx, ly: the last record
+	auto final_ok = [&]() {
+		const int64_t d = (int64_t) ly - (int64_t) lx;
+		return d <= (int64_t) p.hi_thresh && d >= (int64_t) p.lo_thresh;
+	};
+	adaptor_tiles(in, m, window, W0, lane, [&](uint32_t t, float tv, bool valid) {
+		const uint32_t base = t * 64;
+		const uint64_t lt = __ballot(valid && tv < bot), gt = __ballot(valid && tv > bot);
+		uint32_t pos = 0;
+		while (pos < 64) {
+			const uint64_t rl = lt >> pos, rg = gt >> pos;
+			if (!begin) { // nothing happens before the next value below bot
+				if (!rl)
+					break;
+				pos += (uint32_t) __builtin_ctzll(rl);
+				start = base + pos;
+				begin = true;
+				pos++;
+				continue;
+			}
+			// end is the last value below bot before the first one above it
+			const uint32_t g = rg ? (uint32_t) __builtin_ctzll(rg) : 64u;
+			const uint64_t below = g < 64 ? rl & ((1ull << g) - 1) : rl;
+			if (below)
+				end = base + pos + 63u - (uint32_t) __builtin_clzll(below);
+			if (!rg)
+				break;
+			if (has && (int64_t) start - (int64_t) ly < (int64_t) p.seg_dist) {
+				ly = end;
+			} else {
+				if (has && final_ok()) {
+					found = true;
+					return false;
+				}
+				lx = start;
+				ly = end;
+				has = true;
+			}
+			start = 0;
+			end = 0;
+			begin = false;
+			pos += g + 1;
+		}
+		return true;
+	});
+	if (!found && has && final_ok())
+		found = true;
+	if (lane == 0) {
+		const uint32_t shift = window / 2 - 1;
+		pair[2 * (size_t) r] = found ? (int32_t) (lx + shift) : 0;
+		pair[2 * (size_t) r + 1] = found ? (int32_t) (ly + shift) : 0;
+		if (thr) {
+			thr[2 * (size_t) r] = bot;
+			thr[2 * (size_t) r + 1] = mn;
+		}
+	}
+}
+
+uint64_t segments_state_bytes(uint32_t nreads) { return (uint64_t) nreads * sizeof(SegState); }
+
+// The counting walk and the layout: seg_first (nreads + 1), seg_count and thr (unless NULL) are written; state:
+// segments_state_bytes.  cal NULL: the raw domain
+void launch_segments_count(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const float *cal,
+			   const SegParams &p, void *state, uint64_t seg_cap, uint64_t *seg_first, uint32_t *seg_count, float *thr,
+			   hipStream_t s)
+{
+	ktime_begin(1, s);
+	hipLaunchKernelGGL((k_segments<false>), dim3(nreads), dim3(64), 0, s, sig, off, n, cal, p, (SegState *) state, thr,
+			   (SegRec *) nullptr, seg_cap, (const uint64_t *) nullptr);
+	ktime_end(1, s);
+	ktime_begin(1, s);
+	hipLaunchKernelGGL(k_segments_scan, dim3(1), dim3(64), 0, s, (const SegState *) state, nreads, seg_cap, seg_first, seg_count);
+	ktime_end(1, s);
+}
+
+// The writing walk behind launch_segments_count on the same stream: the records of the reads with seg_first[r + 1] <= seg_cap
+void launch_segments_write(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const float *cal,
+			   const SegParams &p, void *state, void *seg, uint64_t seg_cap, const uint64_t *seg_first, hipStream_t s)
+{
+	ktime_begin(1, s);
+	hipLaunchKernelGGL((k_segments<true>), dim3(nreads), dim3(64), 0, s, sig, off, n, cal, p, (SegState *) state, (float *) nullptr,
+			   (SegRec *) seg, seg_cap, seg_first);
+	ktime_end(1, s);
+}
+
+void launch_adaptor(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const Seg2Params &p, int32_t *pair,
+		    float *thr, hipStream_t s)
+{
+	ktime_begin(1, s);
+	hipLaunchKernelGGL(k_adaptor, dim3(nreads), dim3(64), 0, s, sig, off, n, p, pair, thr);
+	ktime_end(1, s);
+}
+
+} // namespace ph

@@ -97,7 +97,9 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_recode_degraded_sizes", "press_hip_recode_degraded_packed", "press_hip_recode_degraded_workspace_bytes",
      "press_hip_recode_degraded_packed_workspace_bytes", "press_hip_verify_degraded_batch",
      "press_hip_event_params_preset", "press_hip_signal_events", "press_hip_signal_events_workspace_bytes",
-     "press_hip_events_serial_reads"]))
+     "press_hip_events_serial_reads",
+     "press_hip_jnn_params_preset", "press_hip_jnn2_params_preset", "press_hip_signal_segments",
+     "press_hip_signal_segments_workspace_bytes", "press_hip_signal_adaptor"]))
 
 
 class PressError(RuntimeError):
@@ -155,6 +157,21 @@ def load_library(path=LIB_PATH):
         _lib.press_hip_signal_events_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
         _lib.press_hip_events_serial_reads.restype = ctypes.c_uint32
         _lib.press_hip_events_serial_reads.argtypes = []
+        _lib.press_hip_jnn_params_preset.restype = ctypes.c_int
+        _lib.press_hip_jnn_params_preset.argtypes = [ctypes.c_int, ctypes.c_void_p]
+        _lib.press_hip_jnn2_params_preset.restype = ctypes.c_int
+        _lib.press_hip_jnn2_params_preset.argtypes = [ctypes.c_int, ctypes.c_void_p]
+        _lib.press_hip_signal_segments.restype = ctypes.c_int
+        _lib.press_hip_signal_segments.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_int]
+        _lib.press_hip_signal_segments_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_signal_segments_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+        _lib.press_hip_signal_adaptor.restype = ctypes.c_int
+        _lib.press_hip_signal_adaptor.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_int]
         _lib.press_hip_signal_stats_timed.restype = ctypes.c_int
         _lib.press_hip_signal_stats_timed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                       ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
@@ -1126,6 +1143,151 @@ def events_serial_reads():
 
 def signal_events_workspace_bytes(total_samples, nreads):
     return int(load_library().press_hip_signal_events_workspace_bytes(int(total_samples), int(nreads)))
+
+
+# ---------------------------------------------------------------------------- segments: sigtk's jnn and jnnv2
+
+class JnnParams(ctypes.Structure):
+    """press_hip_jnn_params: jnn_param_t of sigtk (top and bot are used when std_scale is not > 0)"""
+    _fields_ = [("std_scale", ctypes.c_float), ("corrector", ctypes.c_int32), ("seg_dist", ctypes.c_int32),
+                ("window", ctypes.c_int32), ("stall_len", ctypes.c_float), ("error", ctypes.c_int32),
+                ("top", ctypes.c_float), ("bot", ctypes.c_float)]
+
+
+class Jnn2Params(ctypes.Structure):
+    """press_hip_jnn2_params: jnnv2_param_t of sigtk without the stall_len it never reads; window 1 .. 8192"""
+    _fields_ = [("std_scale", ctypes.c_float), ("seg_dist", ctypes.c_int32), ("window", ctypes.c_int32),
+                ("hi_thresh", ctypes.c_int32), ("lo_thresh", ctypes.c_int32)]
+
+
+SEGMENT_DTYPE = np.dtype([("start", "<u4"), ("end", "<u4")])  # press_hip_segment
+SEGMENT_NOFIT = 0xFFFFFFFF  # seg_count of a read whose records did not fit seg_cap
+JNN_KINDS = {"cdna": 0, "drna": 1, "polya": 2}
+
+
+def jnn_params(kind="cdna"):
+    """sigtk's segmenter parameters (press_hip_jnn_params_preset): "cdna", "drna" or "polya" (set top and bot yourself)"""
+    p = JnnParams()
+    if kind not in JNN_KINDS:
+        raise PressError("jnn_params: one of %s" % ", ".join(JNN_KINDS))
+    if load_library().press_hip_jnn_params_preset(JNN_KINDS[kind], ctypes.addressof(p)):
+        raise PressError(last_error())
+    return p
+
+
+def jnn2_params():
+    """sigtk's dRNA adaptor parameters (press_hip_jnn2_params_preset): 0.5, 1500, 2000, 200000, 2000"""
+    p = Jnn2Params()
+    if load_library().press_hip_jnn2_params_preset(0, ctypes.addressof(p)):
+        raise PressError(last_error())
+    return p
+
+
+def _f32_pairs(t, nreads, name):
+    if t.numel() < 2 * nreads or t.element_size() != 4 or not t.is_contiguous():
+        raise PressError("%s must be a contiguous 32-bit tensor of 2 * nreads entries" % name)
+
+
+def signal_segments(sig, off, n, cal, prm, seg, seg_first, seg_count, thr=None, seg_cap=None):
+    """Enqueue the jnn segmentation of a batch of samples (CUDA tensors as in signal_events; cal float32 of 2 * nreads or
+    None for the raw domain; prm a JnnParams; seg: 8-byte records as a 32-bit tensor of [cap, 2] - start, end - or None
+    for a pure count; seg_first int64 of nreads + 1, WRITTEN; seg_count 32-bit of nreads; thr None or float32 of
+    2 * nreads: bot, top per read): read r's segments are seg[seg_first[r]:seg_first[r + 1]] where they fit seg_cap
+    (default: the rows of seg), else seg_count[r] = 0xFFFFFFFF (press_hip_signal_segments)."""
+    nreads = off.numel()
+    _u32_table(seg_count, nreads, "seg_count")
+    if seg_first.numel() < nreads + 1 or seg_first.element_size() != 8 or not seg_first.is_contiguous():
+        raise PressError("seg_first must be a contiguous 64-bit tensor of nreads + 1 entries")
+    if cal is not None:
+        _f32_pairs(cal, nreads, "cal")
+    if thr is not None:
+        _f32_pairs(thr, nreads, "thr")
+    rows = 0
+    if seg is not None:
+        if seg.element_size() != 4 or not seg.is_contiguous() or seg.numel() % 2:
+            raise PressError("seg must be a contiguous 32-bit tensor of 2 words per record")
+        rows = seg.numel() // 2
+    cap = rows if seg_cap is None else int(seg_cap)
+    if cap > rows:
+        raise PressError("seg_cap is beyond seg")
+    if load_library().press_hip_signal_segments(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
+                                                cal.data_ptr() if cal is not None else None, ctypes.addressof(prm),
+                                                seg.data_ptr() if cap else None, cap, seg_first.data_ptr(),
+                                                seg_count.data_ptr(), thr.data_ptr() if thr is not None else None, 1):
+        raise PressError(last_error())
+
+
+def _host_batch(reads):
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    return sig, off, ns, total
+
+
+def signal_segments_host(reads, cal=None, prm=None, seg_cap=None, want_thr=True):
+    """Segments of a list of int16 arrays (host buffers, synchronous); cal None (raw domain) or (nreads, 2) float32, prm a
+    JnnParams (default: the cDNA preset), seg_cap a limit in records (default: what the batch needs, found with a pure
+    count) -> (seg, seg_first, seg_count, thr): seg a SEGMENT_DTYPE array of min(need, seg_cap) records, seg_first uint64
+    of nreads + 1, seg_count uint32 per read (0xFFFFFFFF: the read did not fit), thr float32 (nreads, 2): bot, top - or
+    None without want_thr."""
+    lib = load_library()
+    prm = jnn_params() if prm is None else prm
+    sig, off, ns, total = _host_batch(reads)
+    if cal is not None:
+        cal = np.ascontiguousarray(cal, dtype=np.float32).reshape(-1)
+        if cal.size != 2 * len(reads):
+            raise PressError("cal: two floats per read")
+    seg_first = np.zeros(len(reads) + 1, dtype=np.uint64)
+    seg_count = np.zeros(len(reads), dtype=np.uint32)
+    thr = np.zeros((len(reads), 2), dtype=np.float32) if want_thr else None
+
+    def call(seg, cap):
+        if lib.press_hip_signal_segments(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total,
+                                         cal.ctypes.data if cal is not None else None, ctypes.addressof(prm),
+                                         seg.ctypes.data if cap else None, cap, seg_first.ctypes.data, seg_count.ctypes.data,
+                                         thr.ctypes.data if want_thr else None, 0):
+            raise PressError(last_error())
+
+    if seg_cap is None:
+        call(None, 0)
+        seg_cap = int(seg_first[-1])
+    seg = np.zeros(int(seg_cap), dtype=SEGMENT_DTYPE)
+    call(seg, int(seg_cap))
+    return seg[:min(int(seg_first[-1]), int(seg_cap))], seg_first, seg_count, thr
+
+
+def signal_segments_workspace_bytes(total_samples, nreads):
+    return int(load_library().press_hip_signal_segments_workspace_bytes(int(total_samples), int(nreads)))
+
+
+def signal_adaptor(sig, off, n, prm, pair, thr=None):
+    """Enqueue sigtk's jnnv2 adaptor finder over a batch of samples (CUDA tensors as in signal_events; prm a Jnn2Params;
+    pair int32 of 2 * nreads, WRITTEN: the adaptor's start and end, (0, 0) for none, (-1, -1) for a read of at most
+    `window` samples; thr None or float32 of 2 * nreads: bot, mean) (press_hip_signal_adaptor)."""
+    nreads = off.numel()
+    _f32_pairs(pair, nreads, "pair")
+    if thr is not None:
+        _f32_pairs(thr, nreads, "thr")
+    if load_library().press_hip_signal_adaptor(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
+                                               ctypes.addressof(prm), pair.data_ptr(),
+                                               thr.data_ptr() if thr is not None else None, 1):
+        raise PressError(last_error())
+
+
+def signal_adaptor_host(reads, prm=None, want_thr=True):
+    """jnnv2 over a list of int16 arrays (host buffers, synchronous) -> (pair int32 (nreads, 2), thr float32 (nreads, 2):
+    bot, mean - or None without want_thr)"""
+    prm = jnn2_params() if prm is None else prm
+    sig, off, ns, total = _host_batch(reads)
+    pair = np.zeros((len(reads), 2), dtype=np.int32)
+    thr = np.zeros((len(reads), 2), dtype=np.float32) if want_thr else None
+    if load_library().press_hip_signal_adaptor(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total,
+                                               ctypes.addressof(prm), pair.ctypes.data,
+                                               thr.ctypes.data if want_thr else None, 0):
+        raise PressError(last_error())
+    return pair, thr
 
 
 # ---------------------------------------------------------------------------- verifying: CRC-32 and compare-after-decode

@@ -797,6 +797,91 @@ uint64_t press_hip_signal_events_workspace_bytes(uint64_t total_samples, uint32_
 uint32_t press_hip_events_serial_reads(void);
 
 /*
+ * Segments: the stall, homopolymer and poly-A stretches of a read and the end of a dRNA adaptor, found on the device bit
+ * for bit as sigtk's `jnn` segmenter and the `jnnv2` adaptor finder behind `prefix` find them (sigtk/src/jnn.c).
+ *
+ * press_hip_signal_segments is jnn_core (jnn.c:185) over jnn_raw / jnn_pa.  The definition, every operation rounded on
+ * its own in single precision, never fused:
+ *   signal   cal == NULL, the raw domain (jnn_raw): x[i] = (float) clamp(s[i], 0, 1200)
+ *            otherwise (jnn_pa on press_hip_depress_pa_batch's floats): p = ((float) s[i] + cal[2r]) * cal[2r + 1],
+ *            x[i] = p > 1200 ? 1200 : p < 0 ? 0 : p - a NaN stays a NaN and is never in range
+ *   thresholds   std_scale > 0:  mn = S / (float) n, S the sequential float sum of x from 0 (stat.h:17);
+ *            sd = sqrtf(Q / (float) n), Q the sequential float sum of (x[i] - mn) * (x[i] - mn), the difference and the
+ *            product each rounded (stat.h:36);  k = sd * std_scale, top = mn + k, bot = mn - k.
+ *            Otherwise (NaN included) top and bot are prm's.  The sums are added in the reference's order, nothing else.
+ *   walk     jnn.c:200-268 over in = x[i] < top && x[i] > bot, with exact integer counters: w starts at corrector and is
+ *            never reset; an in-range sample opens a stretch (start = i) unless one is open, c++, w++, and the run of
+ *            errors ends; an out-of-range sample of an open stretch is an error while err < error (c++, err++, run++);
+ *            after either, err-- if c >= window && c >= w && c % w == 0.  Any other out-of-range sample closes the
+ *            stretch: it is a segment if c >= window, or - only while no segment has been made -
+ *            (float) c >= (float) window * stall_len; its end is i - (the run of errors).  A segment whose
+ *            start - (the last record's end) < seg_dist is not a new record: it overwrites the last record's end.  A
+ *            stretch still open when the read ends is dropped.  n == 0: no segment.
+ *   thr      NULL, or 2 * nreads floats: bot, top of read r as the walk used them (prm's when std_scale is not > 0).  A
+ *            read of no samples has no thresholds of its own: prm's in that case, else 0, 0.  The segments alone do
+ *            not show the order of the sums; thr does.
+ *   prm      press_hip_jnn_params_preset(which, &prm): 0 cDNA 0.75, 50, 50, 150, 0.25, 5; 1 dRNA 0.75, 50, 50, 1000, 1.0,
+ *            5; 2 poly-A -1, 50, 200, 250, 1.0, 30 (jnn.h:29-61; top = bot = 0, for the caller to set).  window < 1,
+ *            corrector < 0, error < 0, seg_dist < 0 and a stall_len that is not finite are PRESS_HIP_EARG before any
+ *            device call.
+ *   sig / off / n / total_samples / device_resident   as press_hip_signal_events, with its checks, its host-pointer form
+ *            (counts, seg_first, seg_count and thr back, then the records in ONE transfer; the room of a read that did
+ *            not fit arrives as zeros) and its device-resident form, which only enqueues on the current stream
+ *   cal      NULL, or 2 * nreads floats, press_hip_pa_cal's; not validated: NaN and inf propagate, nothing faults
+ *   seg / seg_cap / seg_first / seg_count   the layout of press_hip_press_packed, as the events': seg_first (nreads + 1) is
+ *            always written in full and seg_first[nreads] is what the batch needs; seg_count[r] = UINT32_MAX for a read
+ *            that did not fit, of which nothing is written; nothing at or beyond seg_cap is ever written; seg == NULL
+ *            with seg_cap == 0 is a pure count (no writing walk runs).  Records are [start, end), in order.
+ * A NULL argument other than cal, thr and seg with seg_cap == 0 is PRESS_HIP_EARG; nreads == 0 is PRESS_HIP_OK
+ * (seg_first[0] = 0).
+ * Reads of 2^31 samples and more, where the reference's int counters wrap: the definition with exact integers (c and the
+ * positions in 32 bits without sign, w and err in 64).  (float) c is then the conversion of the exact count.
+ * press_hip_signal_segments_workspace_bytes: the device scratch the device-resident call keeps: 16 bytes per read (the
+ * count and the two thresholds) and 0 bytes per sample; exact, 0 for an empty batch.  The adaptor call keeps none.
+ *
+ * press_hip_signal_adaptor is jnnv2 (jnn.c:98), in the raw domain only, as in sigtk:
+ *   a read with n <= window gets the pair (-1, -1) (thr: 0, 0).  Otherwise, with m = n - window:
+ *   t[j] = (float) (the sum of clamp(s, 0, 1200) over [j, j + window)) / (float) window for j < m.  The reference keeps a
+ *            rolling float sum; it holds integers below 1200 * window, so it is exact while that is below 2^24: window
+ *            must lie in 1 .. 8192, else PRESS_HIP_EARG, and the sums are taken as integers
+ *   mn, sd   the sequential float formulas above over t[0 .. m);  bot = mn - sd * std_scale
+ *   walk     jnn.c:124-151: t < bot opens a dip (start = j) or, in an open one, sets end = j; t > bot closes an open dip
+ *            as (start, end) - end is 0 if no second value fell below -, merged into the last record (its end is
+ *            overwritten) if start - (its end) < seg_dist, else a new record; t == bot and NaN do nothing; a dip open
+ *            at the end is dropped
+ *   pair     2 * nreads: of the first record in order with lo_thresh <= end - start <= hi_thresh, AFTER all merging:
+ *            start + window / 2 - 1, end + window / 2 - 1 (integer division); (0, 0) if there is none.  Positions of
+ *            2^31 and more arrive modulo 2^32.
+ *   thr      NULL, or 2 * nreads floats: bot, mn
+ *   prm      press_hip_jnn2_params_preset(0, &prm): JNNV2_RNA_ADAPTOR 0.5, 1500, 2000, 200000, 2000 (jnn.h:74-80)
+ * One wave walks one read in both calls: their time is that of the batch's longest read.
+ */
+typedef struct {
+	float std_scale;
+	int32_t corrector, seg_dist, window;
+	float stall_len;
+	int32_t error;
+	float top, bot;
+} press_hip_jnn_params;
+typedef struct {
+	uint32_t start, end;
+} press_hip_segment; /* 8 bytes */
+typedef struct {
+	float std_scale;
+	int32_t seg_dist, window, hi_thresh, lo_thresh;
+} press_hip_jnn2_params;
+int press_hip_jnn_params_preset(int which, press_hip_jnn_params *prm);
+int press_hip_jnn2_params_preset(int which, press_hip_jnn2_params *prm);
+int press_hip_signal_segments(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			      uint64_t total_samples, const float *cal, const press_hip_jnn_params *prm,
+			      press_hip_segment *seg, uint64_t seg_cap, uint64_t *seg_first, uint32_t *seg_count, float *thr,
+			      int device_resident);
+uint64_t press_hip_signal_segments_workspace_bytes(uint64_t total_samples, uint32_t nreads);
+int press_hip_signal_adaptor(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			     uint64_t total_samples, const press_hip_jnn2_params *prm, int32_t *pair, float *thr,
+			     int device_resident);
+
+/*
  * Lossy archives: dropping the low b bits of every sample, on the device.
  *
  * The definition.  For bits = b in 0 .. 8 and a sample s (int16), computed in 32-bit integers:

@@ -1,0 +1,923 @@
+"""sigtk's jnn segmenter and jnnv2 adaptor finder on the device (include/press_hip.h, "Segments"):
+press_hip_signal_segments and press_hip_signal_adaptor against the definition, bit for bit in the records, the layout
+arrays, the pairs and - by bit pattern - the thresholds `thr`, which are what shows the order of the sums.
+
+The yardstick is a numpy restatement of the definition with one dtype per operation (np.cumsum(..., dtype=float32)[-1]
+is the sequential sum; np.sum is pairwise and is not) and the walks as plain Python loops.  It is pinned to the reference:
+tests/golden/sigtk_jnn.json holds what sigtk's jnn.c, compiled as it is, gives for the three real reads and every
+non-empty read of _layouts.battery() (tests/golden/make_jnn_golden.py), and the yardstick must reproduce every entry.
+"""
+import ctypes
+import hashlib
+import json
+import os
+import struct
+import time
+
+import numpy as np
+import pytest
+
+import _layouts as L
+from honours_amd import press
+
+gpu = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+EARG = -2
+NOFIT = 0xFFFFFFFF
+F32 = np.float32
+TILE = 64
+# std_scale, corrector, seg_dist, window, stall_len, error, top, bot (jnn.h:29-61)
+PRESETS = {"cdna": (0.75, 50, 50, 150, 0.25, 5, 0.0, 0.0), "drna": (0.75, 50, 50, 1000, 1.0, 5, 0.0, 0.0),
+           "polya": (-1.0, 50, 200, 250, 1.0, 30, 0.0, 0.0)}
+V2 = (0.5, 1500, 2000, 200000, 2000)  # std_scale, seg_dist, window, hi_thresh, lo_thresh (jnn.h:74-80)
+V2_SMALL = (0.5, 12, 16, 40, 8)
+# the placed and ragged masks: fixed thresholds, small parameters
+IN, OUT, BOT, TOP = 500, 100, 400.0, 600.0
+SMALL = [(-1.0, 0, 0, 4, 1.0, 1, TOP, BOT), (-1.0, 3, 6, 8, 0.5, 3, TOP, BOT), (-1.0, 1, 4, 2, 1.0, 2, TOP, BOT),
+         (-1.0, 2, 4, 5, 0.5, 1, TOP, BOT)]
+TINY_CAL = (-500.001, 1467.61 / 8192.0)
+
+
+# ------------------------------------------------------------------ the yardstick
+
+def bits(f):
+    return int(F32(f).view(np.uint32))
+
+
+def bits_f32(b):
+    return np.array([b], dtype=np.uint32).view(F32)[0]
+
+
+def yard_signal(s, cal):
+    s = np.asarray(s, dtype=np.int16)
+    if cal is None:
+        return np.clip(s.astype(np.int32), 0, 1200).astype(F32)
+    with np.errstate(all="ignore"):
+        p = ((s.astype(F32) + F32(cal[0])) * F32(cal[1])).astype(F32)
+        return np.where(p > F32(1200), F32(1200), np.where(p < F32(0), F32(0), p)).astype(F32)
+
+
+def seq_sum(v):
+    return np.cumsum(v, dtype=F32)[-1]
+
+
+def yard_mean_sd(x, total=seq_sum):
+    """meanf and stdvf (stat.h): every operation a float32 one"""
+    with np.errstate(all="ignore"):
+        nf = F32(len(x))
+        mn = F32(total(x) / nf)
+        d = (x - mn).astype(F32)
+        q = (d * d).astype(F32)
+        sd = F32(np.sqrt(F32(total(q) / nf)))
+    return mn, sd
+
+
+def yard_thresholds(x, prm, total=seq_sum):
+    """-> bot, top as the walk uses them"""
+    if not prm[0] > 0:
+        return F32(prm[7]), F32(prm[6])
+    if len(x) == 0:
+        return F32(0), F32(0)
+    mn, sd = yard_mean_sd(x, total)
+    with np.errstate(all="ignore"):
+        k = F32(sd * F32(prm[0]))
+        return F32(mn - k), F32(mn + k)
+
+
+def yard_walk(inr, prm, tally=None):
+    """jnn_core's loop (jnn.c:217-268), statement for statement, over the in-range flags"""
+    corrector, seg_dist, window, error = int(prm[1]), int(prm[2]), int(prm[3]), int(prm[5])
+    stall = float(F32(window) * F32(prm[4]))
+    prev, err, prev_err, c, w, start = False, 0, 0, 0, corrector, 0
+    segs = []
+    dec = stl = mrg = 0
+    for i, a in enumerate(inr):
+        if a:
+            if not prev:
+                start = i
+                prev = True
+            c += 1
+            w += 1
+            prev_err = 0
+            if c >= window and c >= w and not c % w:
+                err -= 1
+                dec += 1
+        elif prev:
+            if err < error:
+                c += 1
+                err += 1
+                prev_err += 1
+                if c >= window and c >= w and not c % w:
+                    err -= 1
+                    dec += 1
+            else:
+                if c >= window or (not segs and float(F32(c)) >= stall):
+                    stl += c < window
+                    end = i - prev_err
+                    if segs and start - segs[-1][1] < seg_dist:
+                        segs[-1][1] = end
+                        mrg += 1
+                    else:
+                        segs.append([start, end])
+                prev = False
+                c = err = prev_err = 0
+    if tally is not None:
+        tally["err--"] += dec
+        tally["stall"] += stl
+        tally["merge"] += mrg
+    return np.array(segs, dtype=np.uint32).reshape(-1, 2)
+
+
+def yard_segments(s, cal, prm, tally=None):
+    """-> (records uint32 [k, 2], (bot, top))"""
+    x = yard_signal(s, cal)
+    bot, top = yard_thresholds(x, prm)
+    with np.errstate(all="ignore"):
+        inr = ((x < top) & (x > bot)).tolist()
+    return yard_walk(inr, prm, tally), (bot, top)
+
+
+def yard_rolling(s, window):
+    c = np.clip(np.asarray(s, dtype=np.int64), 0, 1200)
+    P = np.concatenate([[0], np.cumsum(c)])
+    m = len(s) - window
+    W = P[window:window + m] - P[:m]
+    assert W.max() < 1 << 24
+    return (W.astype(F32) / F32(window)).astype(F32)
+
+
+def yard_adaptor(s, prm, info=None):
+    """jnnv2 (jnn.c:98-178) -> ((x, y), (bot, mean)); info: the records after merging, the merges"""
+    std_scale, seg_dist, window, hi, lo = prm
+    if len(s) <= window:
+        return (-1, -1), (F32(0), F32(0))
+    t = yard_rolling(s, window)
+    mn, sd = yard_mean_sd(t)
+    with np.errstate(all="ignore"):
+        bot = F32(mn - F32(sd * F32(std_scale)))
+        lt, gt = (t < bot).tolist(), (t > bot).tolist()
+    begin, start, end, segs, merges = False, 0, 0, [], 0
+    for j in range(len(lt)):
+        if lt[j] and not begin:
+            start = j
+            begin = True
+        elif lt[j]:
+            end = j
+        elif gt[j] and begin:
+            if segs and start - segs[-1][1] < seg_dist:
+                segs[-1][1] = end
+                merges += 1
+            else:
+                segs.append([start, end])
+            start = end = 0
+            begin = False
+    if info is not None:
+        info.update(segs=[tuple(v) for v in segs], merges=merges, open=begin)
+    for a, b in segs:
+        if lo <= b - a <= hi:
+            return (a + window // 2 - 1, b + window // 2 - 1), (bot, mn)
+    return (0, 0), (bot, mn)
+
+
+# ------------------------------------------------------------------ inputs
+
+def fixture():
+    return json.load(open(os.path.join(GOLD, "sigtk_jnn.json")))
+
+
+_named = {}
+
+
+def named_reads():
+    if not _named:
+        flat = np.fromfile(os.path.join(GOLD, "three_reads.i16.bin"), dtype=np.int16)
+        o = 0
+        for r in json.load(open(os.path.join(GOLD, "three_reads.json")))["reads"]:
+            _named["three_reads/" + r["read_id"]] = flat[o:o + r["n"]].copy()
+            o += r["n"]
+        for name, s in L.battery():
+            if len(s):
+                _named["battery/" + name] = s
+    return _named
+
+
+_yard = {}
+
+
+def yard(key, s, cal, prm):
+    """yard_segments once per (key, calibration, parameters): shared by the tests, never changed"""
+    k = (key, None if cal is None else (bits(cal[0]), bits(cal[1])), tuple(bits(v) if isinstance(v, float) else v for v in prm))
+    if k not in _yard:
+        rec, thr = yard_segments(s, cal, prm)
+        rec.setflags(write=False)
+        _yard[k] = (rec, thr)
+    return _yard[k]
+
+
+_yard2 = {}
+
+
+def yard2(key, s, prm):
+    k = (key, tuple(prm))
+    if k not in _yard2:
+        _yard2[k] = yard_adaptor(s, prm)
+    return _yard2[k]
+
+
+def entry_setup(e):
+    """-> (cal, prm) of a raw or pa fixture entry"""
+    if e["kind"] == "raw":
+        return None, PRESETS[e["preset"]]
+    p = list(PRESETS["polya"])
+    p[6], p[7] = float(bits_f32(e["top_bits"])), float(bits_f32(e["bot_bits"]))
+    return (bits_f32(e["cal_bits"][0]), bits_f32(e["cal_bits"][1])), tuple(p)
+
+
+def _walk(rng, n, lo=-12, hi=13, base=480):
+    return (np.cumsum(rng.integers(lo, hi, size=n)) + base).astype(np.int64).astype(np.uint16).view(np.int16)
+
+
+def mask_read(mask):
+    return np.where(np.asarray(mask, dtype=bool), IN, OUT).astype(np.int16)
+
+
+def run_mask(rng, n, one_max=24, zero_max=6):
+    """a random run-length mask of n flags"""
+    out = np.zeros(n, dtype=bool)
+    i, v = 0, bool(rng.integers(0, 2))
+    while i < n:
+        k = int(rng.integers(1, (one_max if v else zero_max) + 1))
+        out[i:i + k] = v
+        i += k
+        v = not v
+    return out
+
+
+def near_1200_read():
+    return np.random.default_rng(1200).integers(1100, 1260, size=40000).astype(np.int16)
+
+
+def tiny_read():
+    return _walk(np.random.default_rng(500001), 6000, -3, 4, 500)
+
+
+# ------------------------------------------------------------------ without a GPU
+
+@pytest.fixture(scope="module")
+def cpu_lib():
+    from honours_amd import build
+    build.build()
+    return press.load_library()
+
+
+def test_yardstick_equals_the_reference():
+    """every entry of sigtk_jnn.json: the count, the digest of all records, the first and last eight in clear; the pairs"""
+    doc = fixture()
+    reads = named_reads()
+    assert len(doc["entries"]) == 29 * 5 and len(reads) == 29
+    for e in doc["entries"]:
+        s = reads[e["name"]]
+        assert len(s) == e["n"]
+        if e["kind"] == "v2":
+            assert list(yard2(e["name"], s, V2)[0]) == e["pair"], e["name"]
+            continue
+        cal, prm = entry_setup(e)
+        rec = yard(e["name"], s, cal, prm)[0]
+        tag = (e["name"], e["kind"], e["preset"], e.get("cal_bits"))
+        assert len(rec) == e["count"], tag
+        assert rec[:8].tolist() == e["first"] and rec[-8:].tolist() == e["last"], tag
+        packed = b"".join(struct.pack("<II", *map(int, r)) for r in rec)
+        assert hashlib.sha256(packed).hexdigest() == e["sha256"], tag
+        assert (rec[:, 1] > rec[:, 0]).all() and (rec[1:, 0].astype(np.int64) > rec[:-1, 1]).all(), tag
+
+
+def test_fixture_conditions():
+    """what makes the fixture worth comparing with: enough segments, every kind of jnnv2 answer, and reads on which the
+    sequential sums are not the exactly rounded ones (what the thr comparison rests on)"""
+    doc = fixture()
+    ent = doc["entries"]
+    assert sum(e["kind"] == "raw" and e["count"] >= 4 for e in ent) >= 10
+    pairs = [tuple(e["pair"]) for e in ent if e["kind"] == "v2"]
+    assert sum(p[0] > 0 and p[1] > p[0] for p in pairs) >= 2 and pairs.count((0, 0)) >= 2 and pairs.count((-1, -1)) >= 2
+    assert sum(e["kind"] == "pa" and e["count"] >= 4 for e in ent) >= 6
+    cals = {tuple(e["cal_bits"]) for e in ent if e["kind"] == "pa"}
+    want = {(bits(c["offset"]), bits(F32(c["range"] / c["digitisation"]))) for c in doc["calibrations"]}
+    assert cals == want and len(want) == 2
+    for e in ent:  # the thresholds of the pa entries: the read's median picoampere value +- 15
+        if e["kind"] == "pa":
+            x = ((named_reads()[e["name"]].astype(F32) + bits_f32(e["cal_bits"][0])) * bits_f32(e["cal_bits"][1])).astype(F32)
+            med = F32(np.median(x))
+            assert e["top_bits"] == bits(med + F32(15)) and e["bot_bits"] == bits(med - F32(15))
+    differ = 0
+    for name, s in named_reads().items():
+        x = yard_signal(s, None)
+        mn, sd = yard_mean_sd(x)
+        xd = x.astype(np.float64)
+        mn1 = F32(xd.sum() / len(x))
+        sd1 = F32(np.sqrt(((xd - xd.mean()) ** 2).sum() / len(x)))
+        differ += bits(mn) != bits(mn1) or bits(sd) != bits(sd1)
+    assert differ >= 10, differ
+
+
+def test_presets(cpu_lib):
+    for kind, want in PRESETS.items():
+        p = press.jnn_params(kind)
+        assert (p.corrector, p.seg_dist, p.window, p.error) == (want[1], want[2], want[3], want[5])
+        assert [bits(p.std_scale), bits(p.stall_len), bits(p.top), bits(p.bot)] == [bits(want[0]), bits(want[4]), 0, 0]
+    q = press.jnn2_params()
+    assert (bits(q.std_scale), q.seg_dist, q.window, q.hi_thresh, q.lo_thresh) == (bits(0.5), 1500, 2000, 200000, 2000)
+    p = press.JnnParams()
+    assert cpu_lib.press_hip_jnn_params_preset(0, None) == EARG and cpu_lib.press_hip_jnn2_params_preset(0, None) == EARG
+    assert cpu_lib.press_hip_jnn_params_preset(3, ctypes.addressof(p)) == EARG
+    assert cpu_lib.press_hip_jnn_params_preset(-1, ctypes.addressof(p)) == EARG
+    assert cpu_lib.press_hip_jnn2_params_preset(1, ctypes.addressof(q)) == EARG
+    assert ctypes.sizeof(press.JnnParams) == 32 and ctypes.sizeof(press.Jnn2Params) == 20 and press.SEGMENT_DTYPE.itemsize == 8
+
+
+SYMBOLS = ("press_hip_jnn_params_preset", "press_hip_jnn2_params_preset", "press_hip_signal_segments",
+           "press_hip_signal_segments_workspace_bytes", "press_hip_signal_adaptor")
+
+
+def test_symbols_and_header(cpu_lib):
+    header = open(os.path.join(os.path.dirname(GOLD), "..", "include", "press_hip.h")).read()
+    for s in SYMBOLS:
+        assert hasattr(cpu_lib, s) and s in press.HEADER_SYMBOLS and s + "(" in header, s
+    for t in ("press_hip_jnn_params;", "press_hip_segment;", "press_hip_jnn2_params;"):
+        assert t in header
+
+
+def test_bad_arguments(cpu_lib):
+    """NULL arguments and parameters outside their ranges are PRESS_HIP_EARG before any device call: the same with and
+    without a device"""
+    lib = cpu_lib
+    a = np.zeros(64, dtype=np.uint64)
+    p = a.ctypes.data
+    ok = press.jnn_params("cdna")
+    q = ctypes.addressof(ok)
+    for dr in (0, 1):
+        # sig off n nreads total cal prm seg cap first count thr
+        args = [p, p, p, 1, 8, p, q, p, 4, p, p, p]
+        for k in (0, 1, 2, 6, 9, 10):
+            bad = list(args)
+            bad[k] = None
+            assert lib.press_hip_signal_segments(*bad, dr) == EARG, (k, dr)
+            assert "NULL" in press.last_error()
+        assert lib.press_hip_signal_segments(p, p, p, 1, 8, p, q, None, 4, p, p, p, dr) == EARG  # no records, but a capacity
+        for field, v in (("window", 0), ("window", -5), ("corrector", -1), ("error", -1), ("seg_dist", -1),
+                         ("stall_len", float("nan")), ("stall_len", float("inf")), ("stall_len", float("-inf"))):
+            prm = press.jnn_params("cdna")
+            setattr(prm, field, v)
+            assert lib.press_hip_signal_segments(*args[:6], ctypes.addressof(prm), *args[7:], dr) == EARG, (field, v, dr)
+            assert "jnn parameters" in press.last_error()
+        ok2 = press.jnn2_params()
+        q2 = ctypes.addressof(ok2)
+        args2 = [p, p, p, 1, 8, q2, p, p]
+        for k in (0, 1, 2, 5, 6):
+            bad = list(args2)
+            bad[k] = None
+            assert lib.press_hip_signal_adaptor(*bad, dr) == EARG, (k, dr)
+            assert "NULL" in press.last_error()
+        for w in (0, -1, 8193, 1 << 30):
+            prm = press.jnn2_params()
+            prm.window = w
+            assert lib.press_hip_signal_adaptor(*args2[:5], ctypes.addressof(prm), *args2[6:], dr) == EARG, (w, dr)
+            assert "window" in press.last_error()
+    assert lib.press_hip_signal_segments(p + 2, p, p, 1, 8, p, q, p, 4, p, p, p, 1) == EARG and "aligned" in press.last_error()
+    assert lib.press_hip_signal_adaptor(p + 2, p, p, 1, 8, q2, p, p, 1) == EARG and "aligned" in press.last_error()
+
+
+def test_workspace(cpu_lib):
+    """exact: the count and the two thresholds of every read, nothing per sample; 0 for an empty batch"""
+    ws = press.signal_segments_workspace_bytes
+    assert ws(0, 0) == 0 and ws(1 << 30, 0) == 0
+    for r in (1, 2, 64, 300, 8192, 100000):
+        for t in (0, 1000, 930_000_000, 1 << 40):
+            assert ws(t, r) == 16 * r
+
+
+def test_pairwise_sums_give_other_bits():
+    """the two reads of test_sums_that_round: a pairwise float sum (np.sum) gives other thresholds than the sequential one"""
+    for s, cal, prm in sum_cases():
+        x = yard_signal(s, cal)
+        seq = yard_thresholds(x, prm)
+        pw = yard_thresholds(x, prm, total=lambda v: np.sum(v, dtype=F32))
+        assert (bits(seq[0]), bits(seq[1])) != (bits(pw[0]), bits(pw[1]))
+    assert float(np.cumsum(yard_signal(near_1200_read(), None), dtype=np.float64)[-1]) > 2 ** 24
+
+
+def sum_cases():
+    return [(near_1200_read(), None, PRESETS["cdna"]), (tiny_read(), (F32(TINY_CAL[0]), F32(TINY_CAL[1])), PRESETS["cdna"])]
+
+
+# ------------------------------------------------------------------ GPU plumbing
+
+@pytest.fixture(scope="module")
+def lib():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    lb = press.load_library()
+    press.use_torch_stream()
+    yield lb
+    torch.cuda.synchronize()
+    press.use_torch_stream()
+    torch.cuda.empty_cache()
+
+
+def _t(a, dtype=None):
+    import torch
+    a = np.ascontiguousarray(a)
+    if dtype is not None:
+        a = a.view(dtype)
+    return torch.from_numpy(a.copy()).cuda()
+
+
+GUARD = 64
+CANARY32 = 0x5AC35AC3
+CANARY64 = 0x5AC35AC35AC35AC3
+
+
+class Dev:
+    """a batch on the device in a scattered layout, and its output arrays between canaries"""
+
+    def __init__(self, reads, cals=None, seed=1):
+        import torch
+        rng = np.random.default_rng(seed)
+        self.reads = reads
+        self.nr = len(reads)
+        sig, off = L.scatter_reads(rng, reads)
+        self.sig, self.off = _t(sig), _t(off, np.int64)
+        self.n = _t(np.array([len(r) for r in reads], dtype=np.uint32), np.int32)
+        self.cal = None if cals is None else _t(np.array(cals, dtype=F32).reshape(-1))
+        self.first = torch.full((self.nr + 1 + 2 * GUARD,), CANARY64, dtype=torch.int64, device="cuda")
+        self.count = torch.full((self.nr + 2 * GUARD,), CANARY32, dtype=torch.int32, device="cuda")
+        self.thr = torch.full((2 * self.nr + 2 * GUARD,), CANARY32, dtype=torch.int32, device="cuda")
+        self.pair = torch.full((2 * self.nr + 2 * GUARD,), CANARY32, dtype=torch.int32, device="cuda")
+
+    def _guards(self, t, k, canary, what):
+        h = t.cpu().numpy()
+        h = h.view(np.uint64 if h.itemsize == 8 else np.uint32)
+        assert (h[:GUARD] == canary).all() and (h[GUARD + k:] == canary).all(), what
+        return h[GUARD:GUARD + k].copy()
+
+    def run(self, prm, cap=None, rows=None, want_thr=True):
+        """cap None: a pure count first, then with exactly what the batch needs.  -> (seg [cap, 2] uint32, seg_first,
+        seg_count, thr bits [nr, 2] or None); the canaries around all four are checked"""
+        import torch
+        p = press.JnnParams(*prm)
+        f = self.first[GUARD:GUARD + self.nr + 1]
+        c = self.count[GUARD:GUARD + self.nr]
+        th = self.thr[GUARD:GUARD + 2 * self.nr].view(torch.float32) if want_thr else None
+        if cap is None:
+            press.signal_segments(self.sig, self.off, self.n, self.cal, p, None, f, c, th)
+            cap = int(f[-1].item())
+        rows = cap if rows is None else rows
+        seg = torch.full((rows + 2 * GUARD, 2), CANARY32, dtype=torch.int32, device="cuda")
+        self.first.fill_(CANARY64)
+        self.count.fill_(CANARY32)
+        self.thr.fill_(CANARY32)
+        press.signal_segments(self.sig, self.off, self.n, self.cal, p, seg[GUARD:GUARD + rows] if rows else None, f, c, th, seg_cap=cap)
+        torch.cuda.synchronize()
+        sh = seg.cpu().numpy().view(np.uint32)
+        assert (sh[:GUARD] == CANARY32).all() and (sh[GUARD + cap:] == CANARY32).all(), "a record outside [0, seg_cap)"
+        fh = self._guards(self.first, self.nr + 1, CANARY64, "seg_first")
+        ch = self._guards(self.count, self.nr, CANARY32, "seg_count")
+        tb = self._guards(self.thr, 2 * self.nr if want_thr else 0, CANARY32, "thr")
+        return sh[GUARD:GUARD + cap], fh, ch, tb.reshape(-1, 2) if want_thr else None
+
+    def adaptor(self, prm, want_thr=True):
+        """-> (pair int32 [nr, 2], thr bits [nr, 2] or None)"""
+        import torch
+        self.pair.fill_(CANARY32)
+        self.thr.fill_(CANARY32)
+        th = self.thr[GUARD:GUARD + 2 * self.nr].view(torch.float32) if want_thr else None
+        press.signal_adaptor(self.sig, self.off, self.n, press.Jnn2Params(*prm), self.pair[GUARD:GUARD + 2 * self.nr], th)
+        torch.cuda.synchronize()
+        ph = self._guards(self.pair, 2 * self.nr, CANARY32, "pair").view(np.int32).reshape(-1, 2)
+        tb = self._guards(self.thr, 2 * self.nr if want_thr else 0, CANARY32, "thr")
+        return ph, tb.reshape(-1, 2) if want_thr else None
+
+
+def one_nan(b):
+    """every NaN of an array of float bit patterns as one pattern (IEEE 754 leaves a NaN's sign and payload open)"""
+    b = np.array(b, dtype=np.uint32)
+    b[np.isnan(b.view(F32))] = 0x7FC00000
+    return b
+
+
+def thr_bits(want):
+    return np.array([[bits(w[1][0]), bits(w[1][1])] for w in want], dtype=np.uint32).reshape(-1, 2)
+
+
+def check(got, want, cap=None):
+    """got = (seg, first, count, thr) against the per-read (records, (bot, top)) `want`: layout, counts, records, thr bits"""
+    seg, first, count, thr = got
+    k = np.array([len(w[0]) for w in want], dtype=np.uint64)
+    assert first[0] == 0 and np.array_equal(first[1:], np.cumsum(k)), "seg_first"
+    cap = int(first[-1]) if cap is None else cap
+    for r, (w, _) in enumerate(want):
+        if int(first[r + 1]) <= cap:
+            assert count[r] == len(w), (r, count[r], len(w))
+            g = seg[int(first[r]):int(first[r + 1])]
+            if not np.array_equal(g, w):
+                bad = np.nonzero((g != w).any(axis=1))[0]
+                raise AssertionError("read %d: %d of %d records differ, the first at %d: %s, expected %s"
+                                     % (r, len(bad), len(w), bad[0], g[bad[0]], w[bad[0]]))
+        else:
+            assert count[r] == NOFIT, (r, count[r])
+    if thr is not None:
+        tw = thr_bits(want)
+        bad = np.nonzero((one_nan(thr) != one_nan(tw)).any(axis=1))[0]
+        assert not len(bad), "thr of read %d: %s, expected %s" % (bad[0], thr[bad[0]], tw[bad[0]])
+
+
+def wants(keys, reads, cals, prm):
+    return [yard(k, s, None if cals is None else cals[i], prm) for i, (k, s) in enumerate(zip(keys, reads))]
+
+
+def check_adaptor(got, keys, reads, prm):
+    pair, thr = got
+    want = [yard2(k, s, prm) for k, s in zip(keys, reads)]
+    wp = np.array([w[0] for w in want], dtype=np.int64).reshape(-1, 2)
+    bad = np.nonzero((pair != wp).any(axis=1))[0]
+    assert not len(bad), "pair of read %d (%s): %s, expected %s" % (bad[0], keys[bad[0]], pair[bad[0]], wp[bad[0]])
+    if thr is not None:
+        tw = thr_bits(want)
+        bad = np.nonzero((thr != tw).any(axis=1))[0]
+        assert not len(bad), "thr of read %d (%s): %s, expected %s" % (bad[0], keys[bad[0]], thr[bad[0]], tw[bad[0]])
+    return want
+
+
+# ------------------------------------------------------------------ on the GPU
+
+@gpu
+@pytest.mark.parametrize("want_thr", [True, False], ids=["thr", "nothr"])
+@pytest.mark.parametrize("preset", ["cdna", "drna"])
+def test_fixture_reads_raw(lib, preset, want_thr):
+    """the fixture's reads in the raw domain, scattered: what the reference gave (through the yardstick, which
+    test_yardstick_equals_the_reference pins to it), and the thresholds bit for bit"""
+    names = sorted(named_reads())
+    reads = [named_reads()[k] for k in names]
+    want = wants(names, reads, None, PRESETS[preset])
+    assert sum(len(w[0]) for w in want) > 50
+    check(Dev(reads, seed=3).run(PRESETS[preset], want_thr=want_thr), want)
+
+
+@gpu
+@pytest.mark.parametrize("want_thr", [True, False], ids=["thr", "nothr"])
+def test_fixture_reads_pa(lib, want_thr):
+    """jnn_pa under the poly-A preset, both calibrations: every read has thresholds of its own, so every entry is a call
+    of its own"""
+    pick = [e for e in fixture()["entries"] if e["kind"] == "pa"]
+    assert len(pick) == 58 and sum(e["count"] > 0 for e in pick) >= 12
+    for k, e in enumerate(pick):
+        cal, prm = entry_setup(e)
+        s = named_reads()[e["name"]]
+        want = [yard(e["name"], s, cal, prm)]
+        assert len(want[0][0]) == e["count"]
+        check(Dev([s], [cal], seed=40 + k).run(prm, want_thr=want_thr), want)
+
+
+@gpu
+@pytest.mark.parametrize("want_thr", [True, False], ids=["thr", "nothr"])
+def test_fixture_reads_adaptor(lib, want_thr):
+    names = sorted(named_reads())
+    reads = [named_reads()[k] for k in names]
+    want = check_adaptor(Dev(reads, seed=5).adaptor(V2, want_thr=want_thr), names, reads, V2)
+    got = {w[0] for w in want}
+    assert (0, 0) in got and (-1, -1) in got and sum(p[1] > p[0] > 0 for p in got) >= 2
+
+
+def length_reads(rng, lengths):
+    """per length a read that is all in range of [BOT, TOP], one with its tail out of range and one random walk"""
+    reads, keys = [], []
+    for n in lengths:
+        m = np.ones(n, dtype=bool)
+        reads.append(mask_read(m))
+        m2 = m.copy()
+        m2[max(n - 6, 0):] = False  # (more than `error` samples: the last of them closes, at c = n - 1 under the cDNA preset)
+        reads.append(mask_read(m2))
+        reads.append(_walk(rng, n))
+        keys += ["len-%d-%d" % (n, v) for v in range(3)]
+    return reads, keys
+
+
+@gpu
+@pytest.mark.parametrize("mode", ["fixed", "sums"])
+def test_lengths(lib, mode):
+    """0, 1, 2, one sample either side of the walk's tile and of twice the tile, and around window and window * stall_len
+    (cDNA: 150 and 37.5; the small set: 8 and 4): with fixed thresholds, where the closing sample decides, and with the
+    thresholds from the sums"""
+    rng = np.random.default_rng(77)
+    lengths = [0, 1, 2, 63, 64, 65, 127, 128, 129, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 36, 37, 38, 39, 40, 41, 149, 150, 151, 152, 153, 154]
+    reads, keys = length_reads(rng, lengths)
+    fixed = list(PRESETS["cdna"])
+    fixed[0], fixed[6], fixed[7] = -1.0, TOP, BOT
+    for prm in ((tuple(fixed), SMALL[1]) if mode == "fixed" else (PRESETS["cdna"], (0.75, 3, 6, 8, 0.5, 3, 0.0, 0.0))):
+        got = Dev(reads, seed=6).run(prm)
+        want = wants(keys, reads, None, prm)
+        check(got, want)
+        assert got[2][0] == 0 and got[2][3] == 0  # n = 0, n = 1: no segment
+        if mode == "fixed":
+            assert sum(len(w[0]) for w in want) >= 10
+            ns = {len(s) for s, w in zip(reads, want) if len(w[0])}
+            assert min(ns) in (39, 7) and (prm[3] != 150 or {151, 152} <= ns)  # the stall rule and the window rule begin where they should
+
+
+@gpu
+def test_adaptor_lengths(lib):
+    """n = window - 1, window (both -1, -1), window + 1 (one rolling mean), window + 64, and the tile's edges of the means"""
+    rng = np.random.default_rng(78)
+    for prm in (V2, V2_SMALL):
+        w = prm[2]
+        ns = [0, 1, w - 1, w, w + 1, w + 2, w + 63, w + 64, w + 65, w + 127, w + 128, w + 129, w + 300]
+        reads = [_walk(rng, n) for n in ns]
+        keys = ["alen-%d-%d" % (w, n) for n in ns]
+        want = check_adaptor(Dev(reads, seed=7).adaptor(prm), keys, reads, prm)
+        assert [x[0] for x in want[:4]] == [(-1, -1)] * 4 and want[4][0] != (-1, -1)
+
+
+def placed_masks(o, prm):
+    """the events of the walk placed at offset o of a read of 200 flags, for one parameter set"""
+    window, error = prm[3], prm[5]
+    n, run = 200, window + 6
+    out = {}
+    m = np.zeros(n, dtype=bool)
+    m[o:o + run] = True
+    out["first"] = m                                # a segment's first in-range sample at o
+    m = np.zeros(n, dtype=bool)
+    m[o - error - run:o - error] = True
+    out["close"] = m                                # ... its closing sample at o
+    m = np.zeros(n, dtype=bool)
+    m[o - 1 - run:o - 1] = True
+    out["errors"] = m                               # the error stretch begins at o - 1 and the closing sample reaches back
+    m = np.zeros(n, dtype=bool)
+    m[o - 2 - run:o - 2] = True
+    m[o - 1] = True                                 # (an error stretch, then in range again: the run of errors ends)
+    m[o + error + 1:o + error + 1 + run] = True
+    out["merge"] = m                                # two halves either side of o, close enough to merge where seg_dist allows
+    m = np.zeros(n, dtype=bool)
+    m[5:5 + run] = True
+    m[o:] = True
+    out["open"] = m[:o + run] if o + run < n else m  # a segment open at the read's end
+    return out
+
+
+@gpu
+def test_placed_masks(lib):
+    """with std_scale = -1 the in-range mask is the test's to choose: each event of the walk at every offset around the
+    first two tile edges; a read of all in-range and one of all out-of-range samples"""
+    offsets = list(range(60, 69)) + list(range(124, 133))
+    for k, prm in enumerate(SMALL):
+        reads, keys = [mask_read(np.ones(200, dtype=bool)), mask_read(np.zeros(200, dtype=bool))], ["all-in-%d" % k, "all-out-%d" % k]
+        for o in offsets:
+            for name, m in placed_masks(o, prm).items():
+                reads.append(mask_read(m))
+                keys.append("placed-%d-%s-%d" % (k, name, o))
+        tally = {"err--": 0, "stall": 0, "merge": 0}
+        for s in reads:
+            yard_segments(s, None, prm, tally)
+        want = wants(keys, reads, None, prm)
+        assert len(want[0][0]) == 0 and len(want[1][0]) == 0  # open at the end; nothing in range
+        starts = {int(w[0][j, 0]) for w in want for j in range(len(w[0]))}
+        ends = {int(w[0][j, 1]) for w in want for j in range(len(w[0]))}
+        assert set(offsets) <= starts and {o - 1 for o in offsets} <= ends and {o - prm[5] for o in offsets} <= ends
+        assert tally["merge"] >= (len(offsets) if k in (1, 3) else 0)  # (under the other two sets err-- keeps the stretch open)
+        check(Dev(reads, seed=20 + k).run(prm), want)
+
+
+@gpu
+def test_ragged_reads(lib):
+    """300 reads of random run-length masks under the four small parameter sets; the branches the inputs are meant to
+    reach are reached"""
+    rng = np.random.default_rng(80)
+    ns = rng.integers(1, 401, size=300)
+    reads = [mask_read(run_mask(rng, int(n), one_max=24 if k % 2 else 9, zero_max=6 if k % 3 else 2)) for k, n in enumerate(ns)]
+    keys = ["ragged-%d" % k for k in range(300)]
+    tally = {"err--": 0, "stall": 0, "merge": 0}
+    for k, prm in enumerate(SMALL):
+        for s in reads:
+            yard_segments(s, None, prm, tally)
+        check(Dev(reads, seed=30 + k).run(prm), wants(keys, reads, None, prm))
+    assert tally["err--"] >= 20 and tally["stall"] >= 20 and tally["merge"] >= 50, tally
+
+
+@gpu
+def test_sums_that_round(lib):
+    """a raw-domain read whose sum passes 2^24 and a picoampere read under offset = -500.001: thr bit for bit (a pairwise
+    sum gives other bits: test_pairwise_sums_give_other_bits)"""
+    for k, (s, cal, prm) in enumerate(sum_cases()):
+        want = [yard("sums-%d" % k, s, cal, prm)]
+        check(Dev([s], None if cal is None else [cal], seed=50 + k).run(prm), want)
+
+
+def dip_read(n, dips, base=600, low=100):
+    s = np.full(n, base, dtype=np.int16)
+    for a, d, *depth in dips:
+        s[a:a + d] = depth[0] if depth else low
+    return s
+
+
+def adaptor_walk_reads():
+    """reads for window 16, thresholds 8 and 40, seg_dist 12: single dips of every width (their width in the rolling
+    means grows by one with the width in the samples), shallow dips of about the window's width (down to one mean below
+    bot), pairs"""
+    reads, keys = [], []
+    for d in range(1, 64):
+        reads.append(dip_read(1500, [(700, d)]))
+        keys.append("dip-%d" % d)
+    for d in (15, 16):  # behind a wide dip that sets the deviation (and fails hi_thresh): how deep decides how wide
+        for low in range(100, 460, 4):
+            reads.append(dip_read(1500, [(200, 200), (900, d, low)]))
+            keys.append("shallow-%d-%d" % (d, low))
+    for gap in (18, 22, 26, 30, 40):
+        reads.append(dip_read(1500, [(600, 4), (600 + 4 + gap, 4)]))       # two short dips: together within the thresholds
+        keys.append("pair-short-%d" % gap)
+        reads.append(dip_read(1500, [(600, 24), (600 + 24 + gap, 24)]))    # two long ones: together beyond hi_thresh
+        keys.append("pair-long-%d" % gap)
+    reads.append(dip_read(1500, [(300, 60), (800, 14)]))                     # the first fails, a later one passes
+    keys.append("fail-then-pass")
+    reads.append(dip_read(1500, [(300, 14), (1480, 20)]))                    # a dip open at the end
+    keys.append("open-end")
+    reads.append(dip_read(1500, [(1480, 20)]))
+    keys.append("open-end-only")
+    return reads, keys
+
+
+@gpu
+def test_adaptor_walk(lib):
+    prm = V2_SMALL
+    lo, hi = prm[4], prm[3]
+    reads, keys = adaptor_walk_reads()
+    infos = []
+    for s in reads:
+        info = {}
+        yard_adaptor(s, prm, info)
+        infos.append(info)
+    widths = {b - a for i in infos for a, b in i["segs"]}
+    assert {lo - 1, lo, hi, hi + 1} <= widths, sorted(widths)
+    assert any(b == 0 and a > 0 for i in infos for a, b in i["segs"]), "no one-sample dip"
+    want = check_adaptor(Dev(reads, seed=60).adaptor(prm), keys, reads, prm)
+    by = dict(zip(keys, zip(want, infos)))
+    merged_ok = [k for k in keys if k.startswith("pair-short") and by[k][1]["merges"] and by[k][0][0] != (0, 0)]
+    merged_bad = [k for k in keys if k.startswith("pair-long") and by[k][1]["merges"] and by[k][0][0] == (0, 0)]
+    assert merged_ok and merged_bad, (merged_ok, merged_bad)
+    w, i = by["fail-then-pass"]
+    assert len(i["segs"]) == 2 and w[0][0] == i["segs"][1][0] + prm[2] // 2 - 1
+    assert by["open-end"][1]["open"] and by["open-end-only"][1]["open"] and by["open-end-only"][0][0] == (0, 0)
+
+
+def ordinary():
+    """a few reads with segments under SMALL[1] and under the cDNA preset"""
+    rng = np.random.default_rng(81)
+    reads = [mask_read(run_mask(rng, n)) for n in (900, 64, 2500, 0, 129)] + [named_reads()["battery/synth-0"][:20000]]
+    return reads, ["ord-%d" % k for k in range(len(reads))]
+
+
+@gpu
+def test_capacity(lib):
+    """seg_cap at the total, one below it and 0 between canaries, and seg == NULL: the same seg_first, UINT32_MAX on exactly
+    the reads that do not fit, no record at or beyond seg_cap (the canaries of Dev.run)"""
+    reads, keys = ordinary()
+    prm = SMALL[1]
+    want = wants(keys, reads, None, prm)
+    total = sum(len(w[0]) for w in want)
+    assert total > 20 and len(want[-1][0]) > 0
+    d = Dev(reads, seed=13)
+    full = d.run(prm, cap=total)
+    check(full, want)
+    assert (full[2] != NOFIT).all()
+    for cap in (total - 1, 0):
+        got = d.run(prm, cap=cap, rows=total)
+        assert np.array_equal(got[1], full[1])
+        check(got, want, cap=cap)
+        fits = full[1][1:] <= cap
+        assert np.array_equal(got[2] != NOFIT, fits) and not fits.all()
+    got = d.run(prm, cap=0, rows=0)  # a pure count: seg == NULL
+    assert np.array_equal(got[1], full[1]) and np.array_equal(got[3], full[3])
+
+
+@gpu
+def test_repeatable_and_independent_of_scratch(lib):
+    import torch
+    reads, keys = ordinary()
+    d = Dev(reads, seed=14)
+    prm = PRESETS["cdna"]
+    a, a2 = d.run(prm), d.adaptor(V2_SMALL)
+    b, b2 = d.run(prm), d.adaptor(V2_SMALL)
+    torch.cuda.synchronize()
+    press.scratch_fill(0xA5)
+    c, c2 = d.run(prm), d.adaptor(V2_SMALL)
+    for x in (b, c):
+        assert all(np.array_equal(p, q) for p, q in zip(a, x))
+    for x in (b2, c2):
+        assert all(np.array_equal(p, q) for p, q in zip(a2, x))
+    check(a, wants(keys, reads, None, prm))
+    check_adaptor(a2, keys, reads, V2_SMALL)
+
+
+@gpu
+def test_host_form(lib):
+    """host pointers: the same records, layout, counts and thresholds as device resident - raw and picoampere domain, with
+    room for all, with less, without thr, and for an empty batch; the adaptor likewise"""
+    reads, keys = ordinary()
+    cals = [(F32(6.0), F32(1467.61 / 8192.0))] * len(reads)
+    pa = list(PRESETS["polya"])
+    pa[3], pa[6], pa[7] = 20, 95.0, 85.0
+    for cal, prm in ((None, PRESETS["cdna"]), (cals, tuple(pa)), (None, SMALL[1])):
+        dev = Dev(reads, cal, seed=15).run(prm)
+        p = press.JnnParams(*prm)
+        hc = None if cal is None else np.array(cal, dtype=F32)
+        seg, first, count, thr = press.signal_segments_host(reads, hc, p)
+        assert np.array_equal(seg.view(np.uint32).reshape(-1, 2), dev[0]) and np.array_equal(first, dev[1])
+        assert np.array_equal(count, dev[2]) and np.array_equal(thr.view(np.uint32), dev[3])
+    assert len(seg) > 20
+    press.scratch_fill(0xA5)
+    cap = int(first[3]) + 1
+    seg2, first2, count2, thr2 = press.signal_segments_host(reads, None, p, seg_cap=cap, want_thr=False)
+    assert np.array_equal(first2, first) and len(seg2) == cap and thr2 is None
+    fits = first[1:] <= cap
+    assert np.array_equal(count2 != NOFIT, fits) and np.array_equal(count2[fits], count[fits]) and not fits.all()
+    k = int(first[1:][fits].max())
+    assert np.array_equal(seg2[:k], seg[:k]) and not seg2[k:].view(np.uint32).any()  # the room of a read that did not fit: zeros
+    seg0, first0, count0, thr0 = press.signal_segments_host([], None, p)
+    assert len(seg0) == 0 and first0.tolist() == [0] and len(count0) == 0
+    dev2 = Dev(reads, seed=16).adaptor(V2_SMALL)
+    pair, thr = press.signal_adaptor_host(reads, press.Jnn2Params(*V2_SMALL))
+    assert np.array_equal(pair, dev2[0]) and np.array_equal(thr.view(np.uint32), dev2[1])
+    pair0, _ = press.signal_adaptor_host([], press.Jnn2Params(*V2_SMALL))
+    assert pair0.shape == (0, 2)
+
+
+@gpu
+def test_stream_contract(lib):
+    """device resident, on a side stream behind a delay: both calls return while the delay is pending - they only enqueue -
+    and their results are those of the same calls made with nothing pending (as test_signal_events.py measures it)"""
+    import torch
+    reads, keys = ordinary()
+    prm = PRESETS["cdna"]
+    want = wants(keys, reads, None, prm)
+    total = sum(len(w[0]) for w in want)
+    d = Dev(reads, seed=17)
+    p, p2 = press.JnnParams(*prm), press.Jnn2Params(*V2_SMALL)
+    nr = len(reads)
+    seg = torch.zeros((total, 2), dtype=torch.int32, device="cuda")
+    first = torch.zeros(nr + 1, dtype=torch.int64, device="cuda")
+    count = torch.zeros(nr, dtype=torch.int32, device="cuda")
+    thr = torch.zeros(2 * nr, dtype=torch.float32, device="cuda")
+    pair = torch.zeros(2 * nr, dtype=torch.int32, device="cuda")
+    thr2 = torch.zeros(2 * nr, dtype=torch.float32, device="cuda")
+
+    def calls():
+        press.signal_segments(d.sig, d.off, d.n, None, p, seg, first, count, thr)
+        press.signal_adaptor(d.sig, d.off, d.n, p2, pair, thr2)
+
+    torch.cuda._sleep(100000)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    torch.cuda._sleep(20000000)
+    b.record()
+    b.synchronize()
+    hold_ms = 50.0
+    cycles = int(hold_ms * 20000000 / a.elapsed_time(b))
+    s = torch.cuda.Stream()
+    assert s.cuda_stream != 0 and lib.press_hip_set_stream(ctypes.c_void_p(s.cuda_stream)) == 0
+    try:
+        with torch.cuda.stream(s):
+            calls()  # (scratch reserved: nothing left to allocate)
+        s.synchronize()
+        seg.zero_()
+        pair.zero_()
+        torch.cuda.synchronize()
+        e = torch.cuda.Event()
+        t0 = time.perf_counter()
+        with torch.cuda.stream(s):
+            torch.cuda._sleep(cycles)
+            e.record(s)
+            calls()
+        t1 = time.perf_counter()
+        assert not e.query(), "a call that promises only to enqueue waited for the stream (or the delay ended early)"
+        assert (t1 - t0) * 1e3 < hold_ms / 2
+        s.synchronize()
+        assert e.query()
+        print("signal_segments + signal_adaptor: %.3f ms of host time behind a delay of %g ms" % ((t1 - t0) * 1e3, hold_ms))
+        check((seg.cpu().numpy().view(np.uint32), first.cpu().numpy().view(np.uint64), count.cpu().numpy().view(np.uint32),
+               thr.cpu().numpy().view(np.uint32).reshape(-1, 2)), want)
+        check_adaptor((pair.cpu().numpy().reshape(-1, 2), thr2.cpu().numpy().view(np.uint32).reshape(-1, 2)), keys, reads, V2_SMALL)
+    finally:
+        torch.cuda.synchronize()
+        press.use_torch_stream()
+
+
+@gpu
+def test_nan_and_inf_calibrations(lib):
+    """cal is not validated: NaN and inf go through the definition, nothing faults and nothing outside the rooms is
+    written (the canaries of Dev.run)"""
+    rng = np.random.default_rng(82)
+    reads = [_walk(rng, n) for n in (900, 64, 2500, 129)]
+    keys = ["nonfinite-%d" % k for k in range(4)]
+    cals = [(F32(np.nan), F32(0.18)), (F32(6.0), F32(np.inf)), (F32(3e38), F32(3e38)), (F32(-np.inf), F32(-1.0))]
+    pa = list(PRESETS["polya"])
+    pa[6], pa[7] = 2000.0, 1000.0
+    for prm in (PRESETS["cdna"], tuple(pa)):
+        check(Dev(reads, cals, seed=12).run(prm), wants(keys, reads, cals, prm))
