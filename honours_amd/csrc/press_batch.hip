@@ -1235,3 +1235,77 @@ extern "C" int press_hip_verify_degraded_batch(int method, uint32_t bits, const 
 {
 	return verify_batch(method, bits, in, in_off, in_len, nreads, sig, off, n, total_samples, first_bad, out_n, nbad, device_resident);
 }
+
+// ------------------------------------------------------------------ the stall methods (press_stall.hip)
+//
+// press_hip_press_batch / press_hip_depress_batch with a stall id in the place of the method: the same checks, the same
+// staging, one launch chain each (launch_stall_press / launch_stall_depress).
+
+static int stall_args_ok(int stall_method, bool null_arg, uint32_t nreads, const void *dev_arena)
+{
+	if (!stall_ok(stall_method))
+		return set_error(PRESS_HIP_EARG, "stall method %d: 0 rccm_svbbe21_zd, 1 dstall_fz_1500, 2 dstall_fz", stall_method);
+	return args_ok(NONE, NONE, null_arg, nreads, dev_arena, "sig");
+}
+
+extern "C" int press_hip_stall_press_batch(int stall_method, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+					   uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+					   uint32_t *stall, int device_resident)
+{
+	API_LOCK;
+	int rc = stall_args_ok(stall_method, nreads && (!sig || !off || !n || !out || !out_off || !out_len), nreads,
+			       device_resident ? sig : nullptr);
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const StallPlan plan = make_stall_plan(stall_method, total_samples, nreads, false, !device_resident);
+	if ((rc = plan.all.reserve()))
+		return rc;
+	BatchArgs a{};
+	a.nreads = nreads;
+	const SlotsOut host = { out, out_off, out_len };
+	SamplesIn in = { sig, off, n };
+	SlotsOut so = host;
+	Staged st(nreads, s);
+	if (!device_resident && ((rc = check_slots(out_off, nreads)) || (rc = st.layout(off, n, total_samples, "the sample range", true)) ||
+				 (rc = st.slots(host, so)) || (rc = st.samples(in, total_samples, in))))
+		return rc;
+	bind_io(a, in);
+	bind_io(a, so);
+	uint32_t *dstall = device_resident ? stall : stall ? (uint32_t *) g.sl_stall.p : nullptr;
+	if ((rc = launch_stall_press(stall_method, plan, a, dstall, s)) || device_resident)
+		return rc;
+	if (stall)
+		HIPCHK(hipMemcpyAsync(stall, dstall, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	return st.fetch_streams(host);
+}
+
+extern "C" int press_hip_stall_depress_batch(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t nreads,
+					     int16_t *sig, const uint64_t *off, const uint32_t *n, uint64_t total_samples,
+					     uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(NONE, NONE, nreads && (!in || !in_off || !in_len || !sig || !off || !n || !out_n), nreads,
+			 device_resident ? sig : nullptr, "sig");
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const StallPlan plan = make_stall_plan(PRESS_HIP_STALL_DSTALL_FZ, total_samples, nreads, true, !device_resident);
+	if ((rc = plan.all.reserve()))
+		return rc;
+	DecodeArgs a{};
+	a.nreads = nreads;
+	const StreamsIn host = { in, in_off, in_len, off, n, out_n, sig };
+	StreamsIn io = host;
+	Staged st(nreads, s);
+	if (!device_resident && (rc = st.streams(host, total_samples, true, g.arena, g.arena_off, io)))
+		return rc;
+	bind_io(a, io);
+	if ((rc = launch_stall_depress(plan, a, s)) || device_resident)
+		return rc;
+	return st.fetch_samples(host);
+}

@@ -95,6 +95,53 @@ void void_depress(int method, const uint8_t *in, uint64_t nbytes, int16_t *out, 
 	*nout = n;
 }
 
+void stall_press_(int sm, const int16_t *in, uint32_t n, uint8_t *out, uint64_t *nout)
+{
+	const uint64_t off[1] = { 0 };
+	const uint64_t ooff[2] = { 0, *nout };
+	uint64_t l = PRESS_HIP_FAILED;
+	int rc = n ? press_hip_stall_press_batch(sm, in, off, &n, 1, n, out, ooff, &l, nullptr, 0) : set_error(PRESS_HIP_EARG, "empty read");
+	if (!rc && l == PRESS_HIP_FAILED)
+		rc = set_error(-1, "the read is refused, or its stream does not fit %llu bytes", (unsigned long long) *nout);
+	if (rc) {
+		fprintf(stderr, "press_hip: %s\n", press_hip_last_error());
+		l = 0;
+	}
+	*nout = l;
+}
+
+void stall_depress_(const uint8_t *in, uint64_t nsamples, int16_t *out, uint32_t *nout)
+{
+	const uint64_t off[1] = { 0 };
+	const uint64_t ioff[1] = { 0 };
+	uint32_t n = (uint32_t) nsamples, got = UINT32_MAX;
+	// [exists] ([start u16][len u16][nstall u16][stall piece]) [nrest u32][rest piece]
+	uint64_t len = 5;
+	int rc = 0;
+	if (n == 0 || nsamples > UINT32_MAX || in[0] > 1) {
+		rc = set_error(-1, "malformed stream");
+	} else {
+		uint64_t pos = 1;
+		if (in[0]) {
+			uint16_t l1;
+			memcpy(&l1, in + 5, 2);
+			pos = 7 + (uint64_t) l1;
+		}
+		uint32_t l0;
+		memcpy(&l0, in + pos, 4);
+		len = pos + 4 + l0;
+		const uint64_t ilen[1] = { len };
+		rc = press_hip_stall_depress_batch(in, ioff, ilen, 1, out, off, &n, n, &got, 0);
+		if (!rc && got == UINT32_MAX)
+			rc = set_error(-1, "malformed stream");
+	}
+	if (rc) {
+		fprintf(stderr, "press_hip: %s\n", press_hip_last_error());
+		got = 0;
+	}
+	*nout = got;
+}
+
 // zstd level 1 (press.h:275) around a GPU-made inner stream (press.c:1865, 2025, 8554)
 int zstd_press_(int inner, bool prefix_n, const int16_t *in, uint32_t n, uint8_t *out, uint64_t *nout)
 {
@@ -328,5 +375,21 @@ void *press_hip_slow5_ptr_depress_svb_zd(const uint8_t *ptr, size_t count, size_
 	*n = (size_t) got * sizeof *out;
 	return out;
 }
+
+// ---- the stall methods (press.c:7716-8030).  Their depress takes the SAMPLE count in nin (press.c:7871) and no byte
+// count: the stream's length is what its own header says, as the reference reads it
+#define STALL_FAMILY(name, id)                                                                   \
+	uint64_t name##_bound_16(uint32_t nin) { return press_hip_stall_bound(id, nin); }        \
+	void name##_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout)      \
+	{                                                                                        \
+		stall_press_(id, in, nin, out, nout);                                            \
+	}                                                                                        \
+	void name##_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout)          \
+	{                                                                                        \
+		stall_depress_(in, nin, out, nout);                                              \
+	}
+STALL_FAMILY(rccm_svbbe21_zd, PRESS_HIP_STALL_RCCM_SVBBE21_ZD)
+STALL_FAMILY(dstall_fz_1500, PRESS_HIP_STALL_DSTALL_FZ_1500)
+STALL_FAMILY(dstall_fz, PRESS_HIP_STALL_DSTALL_FZ)
 
 } // extern "C"

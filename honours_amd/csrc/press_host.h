@@ -73,6 +73,7 @@ struct Ctx {
 	DevBuf vf_raw, vf_out; // verify / CRC-32: a word per read between the two kernels; host path: the staged crc or first_bad, and nbad
 	DevBuf ev_state, ev_cal, ev_first, ev_cnt, ev_out; // events: count and path per read; host path: the staged calibration, ev_first, ev_count, the records
 	DevBuf sg_state, sg_cal, sg_first, sg_cnt, sg_thr, sg_out; // jnn segments: count and thresholds per read; host path: the staged calibration, seg_first, seg_count, thr, the records (the adaptor: the pairs)
+	DevBuf sl_seg, sl_rd, sl_poff, sl_pn, sl_pooff, sl_polen, sl_poutn, sl_psig, sl_parena, sl_stall; // stall methods: first segments, plans, the piece table (StallBufs), the pieces' samples and streams; host path: (start, len) per read
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams
@@ -293,6 +294,21 @@ ScratchPlan make_adaptor_plan(uint32_t nreads, bool host);
 
 // press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
 ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);
+
+// press_hip_stall_press_batch / press_hip_stall_depress_batch: `inner` is rccm_vbbe21_zd's plan for the pieces as a batch
+// of npieces reads of piece_samples samples (its bind()s serve the inner launch), `all` what the call reserves: that, the
+// piece table, the pieces' samples and - press - their streams and the segmenter's state; host pointers: press's stall[]
+struct StallPlan {
+	ScratchPlan inner, all;
+	uint32_t npieces;
+	uint64_t piece_samples, arena_bytes;
+	StallBufs bufs() const; // the pointers of `all`, behind all.reserve()
+};
+inline bool stall_ok(int sm) { return sm >= 0 && sm < PRESS_HIP_NSTALL; }
+StallPlan make_stall_plan(int stall_method, uint64_t total_samples, uint32_t nreads, bool decode, bool host);
+// a.sig / off / nsamp: the caller's samples, a.out / out_off / out_len: its slots; stall: NULL or 2 * nreads words
+int launch_stall_press(int stall_method, const StallPlan &p, const BatchArgs &a, uint32_t *stall, hipStream_t s);
+int launch_stall_depress(const StallPlan &p, const DecodeArgs &a, hipStream_t s);
 
 int check_method(int method); // EARG / ENOTABLE
 int launch_status();          // EHIP if a kernel launch since the last call failed

@@ -425,6 +425,44 @@ void launch_segments_write(const int16_t *sig, const uint64_t *off, const uint32
 			   const SegParams &p, void *state, void *seg, uint64_t seg_cap, const uint64_t *seg_first, hipStream_t s);
 void launch_adaptor(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const Seg2Params &p, int32_t *pair,
 		    float *thr, hipStream_t s);
+// ... and segs[0] alone, in one launch (the stall methods): first[r] = { start, end }, start = STALL_NOSEG: no segment
+void launch_segments_first(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const SegParams &p, void *state,
+			   void *first, hipStream_t s);
+// press_stall.hip: the stall methods (include/press_hip.h, press_hip_stall_*).  A read becomes up to three PIECES - what
+// is left of it without the stall, the stall, and for dstall_fz the whole read - which the rccm_vbbe21_zd kernels press
+// and depress as the reads of a larger batch; piece k of read r is entry STALL_PIECES * r + k (depress: STALL_DPIECES)
+constexpr int PRESS_STALL_SVBBE21 = 0, PRESS_STALL_1500 = 1, PRESS_STALL_FZ = 2; // PRESS_HIP_STALL_* (press_hip.h)
+constexpr uint32_t STALL_NOSEG = 0xFFFFFFFFu;
+constexpr uint32_t STALL_PIECES = 3, STALL_DPIECES = 2;
+struct StallRead {            // per read: what the stream says (press: what the plan found)
+	uint32_t start, len;  // the stall [start, start + len) of the read, 0 and 0 without one
+	uint32_t exists;
+	uint32_t ok;          // press: the pieces fit the scratch; depress: the header passed every check
+};
+struct StallBufs {            // the scratch of one call (Ctx::sl_*), np pieces
+	uint2 *seg;           // [nreads] launch_segments_first
+	StallRead *rd;        // [nreads]
+	uint64_t *poff;       // [np + 1] piece p's samples start at psig[poff[p]] (multiples of 8)
+	uint32_t *pn;         // [np] its samples, 0: no such piece
+	uint64_t *pooff;      // [np + 1] press: its slot in parena; depress: its stream's offset in the caller's arena
+	uint64_t *polen;      // [np] its stream's bytes
+	uint32_t *poutn;      // [np] depress: the inner decoder's verdict
+	int16_t *psig;
+	uint8_t *parena;      // press
+	uint64_t sig_cap, arena_cap; // samples of psig, bytes of parena
+};
+uint64_t stall_piece_samples(int stall_method, uint64_t total_samples, uint32_t nreads, bool decode);
+uint64_t stall_arena_bytes(uint64_t piece_samples, uint32_t npieces);
+// press: segs[0] -> plan and piece table -> pieces' samples (behind it: the inner press of the pieces) -> the streams
+void launch_stall_plan(int stall_method, const uint32_t *n, uint32_t nreads, const StallBufs &b, hipStream_t s);
+void launch_stall_gather(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const StallBufs &b, hipStream_t s);
+void launch_stall_assemble(int stall_method, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint8_t *out, const uint64_t *out_off,
+			   uint64_t *out_len, uint32_t *stall, hipStream_t s);
+// depress: headers -> piece table (behind it: the inner depress of the pieces) -> the samples in place
+void launch_stall_parse(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, const uint32_t *n, uint32_t nreads,
+			const StallBufs &b, hipStream_t s);
+void launch_stall_scatter(int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint32_t *out_n,
+			  hipStream_t s);
 void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip

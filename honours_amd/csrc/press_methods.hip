@@ -151,6 +151,45 @@ ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads
 	return p;
 }
 
+// The stall methods: rccm_vbbe21_zd's plan over the pieces, and the piece table.  The pieces' streams are held at the
+// most a stream can take (stall_arena_bytes), so that a piece never fails for want of room: the caller's slot decides
+StallPlan make_stall_plan(int stall_method, uint64_t total_samples, uint32_t nreads, bool decode, bool host)
+{
+	StallPlan p{};
+	p.npieces = (decode ? STALL_DPIECES : STALL_PIECES) * nreads;
+	p.piece_samples = stall_piece_samples(stall_method, total_samples, nreads, decode);
+	p.arena_bytes = decode ? 0 : stall_arena_bytes(p.piece_samples, p.npieces);
+	p.inner = make_plan(PRESS_HIP_RCCM_VBBE21_ZD, p.piece_samples, p.npieces, decode);
+	p.all = p.inner;
+	const size_t np = (size_t) p.npieces + 1, nr = (size_t) nreads + 1;
+	p.all.need(&Ctx::sl_rd, nr * sizeof(StallRead)).need(&Ctx::sl_poff, np * 8).need(&Ctx::sl_pn, np * 4).need(&Ctx::sl_pooff, np * 8)
+		.need(&Ctx::sl_polen, np * 8).need(&Ctx::sl_psig, p.piece_samples * 2 + 64);
+	if (decode)
+		p.all.need(&Ctx::sl_poutn, np * 4);
+	else
+		p.all.need(&Ctx::sl_seg, nr * 8).need(&Ctx::sg_state, segments_state_bytes(nreads)).need(&Ctx::sl_parena, p.arena_bytes);
+	if (host && !decode)
+		p.all.need(&Ctx::sl_stall, nr * 8);
+	return p;
+}
+
+StallBufs StallPlan::bufs() const
+{
+	StallBufs b{};
+	b.seg = (uint2 *) all.ptr(&Ctx::sl_seg);
+	b.rd = (StallRead *) all.ptr(&Ctx::sl_rd);
+	b.poff = (uint64_t *) all.ptr(&Ctx::sl_poff);
+	b.pn = (uint32_t *) all.ptr(&Ctx::sl_pn);
+	b.pooff = (uint64_t *) all.ptr(&Ctx::sl_pooff);
+	b.polen = (uint64_t *) all.ptr(&Ctx::sl_polen);
+	b.poutn = (uint32_t *) all.ptr(&Ctx::sl_poutn);
+	b.psig = (int16_t *) all.ptr(&Ctx::sl_psig);
+	b.parena = (uint8_t *) all.ptr(&Ctx::sl_parena);
+	b.sig_cap = piece_samples;
+	b.arena_cap = arena_bytes;
+	return b;
+}
+
 // The svb family's decode kernel writes picoamperes itself; the zstd compositions over it take the general path (their
 // second stage is launched by press_zstd.hip with arguments of its own).
 bool depress_pa_fused(int method) { return method_ok(method) && METHODS[method].family == FAM_SVB; }
@@ -442,6 +481,64 @@ extern "C" uint64_t press_hip_signal_segments_workspace_bytes(uint64_t total_sam
 {
 	(void) total_samples;
 	return plan_bytes(make_segments_plan(nreads, false, false), false);
+}
+
+// The stall methods' bound is rccm_vbbe21_zd's (press.c:7723, 7893, 7981)
+extern "C" uint64_t press_hip_stall_bound(int stall_method, uint32_t n)
+{
+	return stall_ok(stall_method) ? press_hip_bound(PRESS_HIP_RCCM_VBBE21_ZD, n) : 0;
+}
+
+// the larger of what the device-resident press_hip_stall_press_batch and press_hip_stall_depress_batch ask of every buffer
+extern "C" uint64_t press_hip_stall_workspace_bytes(int stall_method, uint64_t total_samples, uint32_t nreads)
+{
+	if (!stall_ok(stall_method))
+		return 0;
+	ScratchPlan p = make_stall_plan(stall_method, total_samples, nreads, false, false).all;
+	return plan_bytes(p.merge(make_stall_plan(stall_method, total_samples, nreads, true, false).all), false);
+}
+
+// segs[0] of jnn_raw under JNNV1_CDNA_PARAM (press.c:7734), the plan, the pieces, rccm_vbbe21_zd over them, the streams
+int ph::launch_stall_press(int stall_method, const StallPlan &p, const BatchArgs &a, uint32_t *stall, hipStream_t s)
+{
+	const StallBufs b = p.bufs();
+	const SegParams cdna = { 0.75f, 50, 50, 150, 0.25f, 5, 0.0f, 0.0f }; // jnn.h:40-49 (press_hip_jnn_params_preset(0))
+	launch_segments_first(a.sig, a.off, a.nsamp, a.nreads, cdna, p.all.ptr(&Ctx::sg_state), b.seg, s);
+	launch_stall_plan(stall_method, a.nsamp, a.nreads, b, s);
+	launch_stall_gather(a.sig, a.off, a.nsamp, a.nreads, b, s);
+	BatchArgs in;
+	p.inner.bind(in);
+	in.nreads = p.npieces;
+	in.sig = b.psig;
+	in.off = b.poff;
+	in.nsamp = b.pn;
+	in.out = b.parena;
+	in.out_off = b.pooff;
+	in.out_len = b.polen;
+	const Method &m = METHODS[PRESS_HIP_RCCM_VBBE21_ZD];
+	launch_ex_encode_chunked(in, m.exfmt, m.ent, s);
+	launch_stall_assemble(stall_method, a.nsamp, a.nreads, b, a.out, a.out_off, a.out_len, stall, s);
+	return launch_status();
+}
+
+int ph::launch_stall_depress(const StallPlan &p, const DecodeArgs &a, hipStream_t s)
+{
+	const StallBufs b = p.bufs();
+	launch_stall_parse(a.in, a.in_off, a.in_len, a.nsamp, a.nreads, b, s);
+	DecodeArgs in;
+	p.inner.bind(in);
+	in.nreads = p.npieces;
+	in.in = a.in;
+	in.in_off = b.pooff;
+	in.in_len = b.polen;
+	in.sig = b.psig;
+	in.off = b.poff;
+	in.nsamp = b.pn;
+	in.out_n = b.poutn;
+	const Method &m = METHODS[PRESS_HIP_RCCM_VBBE21_ZD];
+	launch_ex_decode_chunked(in, m.exfmt, m.ent, s);
+	launch_stall_scatter(a.sig, a.off, a.nsamp, a.nreads, b, a.out_n, s);
+	return launch_status();
 }
 
 static bool rank_ok(uint32_t num, uint32_t den) { return den > 0 && num <= den; }

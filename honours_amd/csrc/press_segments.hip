@@ -25,6 +25,7 @@
 namespace ph {
 
 constexpr uint32_t SEG_NOFIT = 0xFFFFFFFFu;
+constexpr uint32_t SEG_NONE = 0xFFFFFFFFu; // launch_segments_first: start of a read without a segment (press_internal.h: STALL_NOSEG)
 constexpr uint32_t SEG_AHEAD = 4; // tiles whose loads are in flight while a group of as many is worked on
 
 struct SegRec { // press_hip_segment
@@ -94,7 +95,9 @@ struct SegWalk { // jnn_core's state (jnn.c:200-215) with exact integers, and th
 };
 
 // One block of 64 lanes per read.  WRITE: the records of a read that fits; else its count and its thresholds.
-template <bool WRITE>
+// FIRST (with !WRITE; the stall methods, press_stall.hip): one launch that keeps segs[0] alone - seg[r] is the read's
+// first record once no merge can change it, start = SEG_NONE for a read without one, and the walk stops there
+template <bool WRITE, bool FIRST = false>
 __global__ __launch_bounds__(64) void k_segments(const int16_t *sig, const uint64_t *off, const uint32_t *nsamp, const float *cal,
 						  SegParams p, SegState *state, float *thr, SegRec *seg, uint64_t seg_cap,
 						  const uint64_t *seg_first)
@@ -111,6 +114,8 @@ __global__ __launch_bounds__(64) void k_segments(const int16_t *sig, const uint6
 		room = end - first;
 	} else if (n == 0) { // no segment and no thresholds of its own
 		if (lane == 0) {
+			if (FIRST)
+				seg[r] = { SEG_NONE, 0u };
 			state[r] = { 0u, 0u, given ? p.bot : 0.0f, given ? p.top : 0.0f };
 			if (thr) {
 				thr[2 * (size_t) r] = given ? p.bot : 0.0f;
@@ -158,6 +163,8 @@ __global__ __launch_bounds__(64) void k_segments(const int16_t *sig, const uint6
 	const float stall = (float) p.window * p.stall_len;
 	SegWalk a = { false, 0u, 0u, 0u, 0u, 0u, 0u, (uint64_t) (uint32_t) p.corrector, 0 };
 	auto flush = [&]() { // the last record is final
+		if (FIRST && lane == 0 && a.count == 1)
+			seg[r] = { a.last_start, a.last_end };
 		if (WRITE && lane == 0 && (uint64_t) (a.count - 1) < room)
 			seg[first + (a.count - 1)] = { a.last_start, a.last_end };
 	};
@@ -225,10 +232,12 @@ __global__ __launch_bounds__(64) void k_segments(const int16_t *sig, const uint6
 			}
 			pos++;
 		}
-		return true;
+		return !(FIRST && a.count >= 2); // (the first record was flushed when the second began)
 	});
 	if (a.count)
 		flush();
+	if (FIRST && lane == 0 && a.count == 0)
+		seg[r] = { SEG_NONE, 0u };
 	if (!WRITE && lane == 0) {
 		state[r] = { a.count, 0u, bot, top };
 		if (thr) {
@@ -432,6 +441,16 @@ void launch_segments_write(const int16_t *sig, const uint64_t *off, const uint32
 	ktime_begin(1, s);
 	hipLaunchKernelGGL((k_segments<true>), dim3(nreads), dim3(64), 0, s, sig, off, n, cal, p, (SegState *) state, (float *) nullptr,
 			   (SegRec *) seg, seg_cap, seg_first);
+	ktime_end(1, s);
+}
+
+// The first record of every read in one launch (first: 8 bytes per read, start = 0xFFFFFFFF: none); state as above
+void launch_segments_first(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const SegParams &p, void *state,
+			   void *first, hipStream_t s)
+{
+	ktime_begin(1, s);
+	hipLaunchKernelGGL((k_segments<false, true>), dim3(nreads), dim3(64), 0, s, sig, off, n, (const float *) nullptr, p,
+			   (SegState *) state, (float *) nullptr, (SegRec *) first, (uint64_t) 0, (const uint64_t *) nullptr);
 	ktime_end(1, s);
 }
 

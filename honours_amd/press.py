@@ -26,6 +26,8 @@ METHODS = {
     "slow5_svb_zd": 15, "rc_vbe21_zd": 16, "rcc_vbe21_zd": 17, "rccm_vbbe21_zd": 18,
 }
 BATCH_METHODS = [m for m in METHODS if not m.startswith("zstd_")]
+# include/press_hip.h enum press_hip_stall_method: a family of its own (the generic batch calls do not take these ids)
+STALL_METHODS = {"rccm_svbbe21_zd": 0, "dstall_fz_1500": 1, "dstall_fz": 2}
 FAILED = (1 << 64) - 1
 
 # method -> (bound symbol, press symbol, depress symbol, calling convention)
@@ -99,7 +101,10 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_event_params_preset", "press_hip_signal_events", "press_hip_signal_events_workspace_bytes",
      "press_hip_events_serial_reads",
      "press_hip_jnn_params_preset", "press_hip_jnn2_params_preset", "press_hip_signal_segments",
-     "press_hip_signal_segments_workspace_bytes", "press_hip_signal_adaptor"]))
+     "press_hip_signal_segments_workspace_bytes", "press_hip_signal_adaptor",
+     "press_hip_stall_bound", "press_hip_stall_press_batch", "press_hip_stall_depress_batch",
+     "press_hip_stall_workspace_bytes"] +
+    [m + s for m in STALL_METHODS for s in ("_bound_16", "_press_16", "_depress_16")]))
 
 
 class PressError(RuntimeError):
@@ -172,6 +177,27 @@ def load_library(path=LIB_PATH):
         _lib.press_hip_signal_adaptor.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_int]
+        _lib.press_hip_stall_bound.restype = ctypes.c_uint64
+        _lib.press_hip_stall_bound.argtypes = [ctypes.c_int, ctypes.c_uint32]
+        _lib.press_hip_stall_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_stall_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
+        _lib.press_hip_stall_press_batch.restype = ctypes.c_int
+        _lib.press_hip_stall_press_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_stall_depress_batch.restype = ctypes.c_int
+        _lib.press_hip_stall_depress_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                       ctypes.c_void_p, ctypes.c_int]
+        for m in STALL_METHODS:
+            getattr(_lib, m + "_bound_16").restype = ctypes.c_uint64
+            getattr(_lib, m + "_bound_16").argtypes = [ctypes.c_uint32]
+            getattr(_lib, m + "_press_16").restype = None
+            getattr(_lib, m + "_press_16").argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                       ctypes.POINTER(ctypes.c_uint64)]
+            getattr(_lib, m + "_depress_16").restype = None
+            getattr(_lib, m + "_depress_16").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                         ctypes.POINTER(ctypes.c_uint32)]
         _lib.press_hip_signal_stats_timed.restype = ctypes.c_int
         _lib.press_hip_signal_stats_timed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                       ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
@@ -1291,6 +1317,119 @@ def signal_adaptor_host(reads, prm=None, want_thr=True):
 
 
 # ---------------------------------------------------------------------------- verifying: CRC-32 and compare-after-decode
+
+# ---------------------------------------------------------------------------- the stall methods
+
+def _sid(method):
+    return STALL_METHODS[method] if isinstance(method, str) else int(method)
+
+
+def stall_bound(method, n):
+    """X_bound_16(n) of a stall method: rccm_vbbe21_zd's for all three"""
+    return int(load_library().press_hip_stall_bound(_sid(method), int(n)))
+
+
+def stall_workspace_bytes(method, total_samples, nreads):
+    return int(load_library().press_hip_stall_workspace_bytes(_sid(method), int(total_samples), int(nreads)))
+
+
+def stall_press(method, sig, cap=None):
+    """X_press_16 of a stall method through the per-read symbol -> (ret, bytes); ret -1: the library reports *nout = 0"""
+    lib = load_library()
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    cap = stall_bound(method, sig.size) + 1024 if cap is None else int(cap)
+    out = np.zeros(cap + 64, dtype=np.uint8)
+    out[cap:] = 0xA5
+    nout = ctypes.c_uint64(cap)
+    name = [k for k, v in STALL_METHODS.items() if v == _sid(method)][0]
+    getattr(lib, name + "_press_16")(sig.ctypes.data, sig.size, out.ctypes.data, ctypes.byref(nout))
+    if not np.all(out[cap:] == 0xA5):
+        raise PressError("%s_press_16 wrote past its capacity" % name)
+    return (0, out[:nout.value].tobytes()) if nout.value else (-1, b"")
+
+
+def stall_depress(method, comp, n):
+    """X_depress_16 of a stall method through the per-read symbol: n is the read's SAMPLE count, which the reference
+    passes in the place of the byte count (press.c:7871) -> (ret, int16 array)"""
+    lib = load_library()
+    buf = np.frombuffer(bytes(comp) + b"\0" * 64, dtype=np.uint8).copy()
+    out = np.zeros(n + 64, dtype=np.int16)
+    out[n:] = 0x5A5A
+    nout = ctypes.c_uint32(n)
+    name = [k for k, v in STALL_METHODS.items() if v == _sid(method)][0]
+    getattr(lib, name + "_depress_16")(buf.ctypes.data, n, out.ctypes.data, ctypes.byref(nout))
+    if not np.all(out[n:] == 0x5A5A):
+        raise PressError("%s_depress_16 wrote past the sample capacity" % name)
+    return (0, out[:nout.value].copy()) if nout.value else (-1, out[:0].copy())
+
+
+def stall_press_batch(method, sig, off, n, out, out_off, out_len, stall=None):
+    """Enqueue the compression of a batch under a stall method.  CUDA tensors as in press_batch; stall: None, or int32
+    of 2 * nreads: (stall_start, stall_len) as written into every stream, (0, 0) without a stall"""
+    lib = load_library()
+    nreads = off.numel()
+    rc = lib.press_hip_stall_press_batch(_sid(method), sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
+                                         out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(),
+                                         None if stall is None else stall.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def stall_depress_batch(comp, in_off, in_len, sig, off, n, out_n):
+    """Enqueue the decompression of a batch of stall-method streams (one decoder reads all three).  CUDA tensors as in
+    depress_batch; n: the reads' exact sample counts"""
+    lib = load_library()
+    nreads = off.numel()
+    rc = lib.press_hip_stall_depress_batch(comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), nreads, sig.data_ptr(),
+                                           off.data_ptr(), n.data_ptr(), sig.numel(), out_n.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def stall_press_batch_host(method, reads, caps=None, want_stall=False):
+    """Host buffers: reads = list of int16 arrays -> list of bytes / None (want_stall: and uint32 [nreads, 2])"""
+    lib = load_library()
+    nreads = len(reads)
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    if caps is None:
+        caps = [stall_bound(method, int(x)) + 1024 if x else 32 for x in ns]
+    out_off = np.zeros(nreads + 1, dtype=np.uint64)
+    out_off[1:] = np.cumsum((np.asarray(caps, dtype=np.uint64) + 15) // 16 * 16)
+    out = np.zeros(int(out_off[-1]) + 64, dtype=np.uint8)
+    out_len = np.zeros(nreads, dtype=np.uint64)
+    stall = np.zeros((nreads, 2), dtype=np.uint32)
+    rc = lib.press_hip_stall_press_batch(_sid(method), sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total,
+                                         out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
+                                         stall.ctypes.data if want_stall else None, 0)
+    if rc:
+        raise PressError(last_error())
+    streams = [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
+    return (streams, stall) if want_stall else streams
+
+
+def stall_depress_batch_host(streams, ns):
+    """Host buffers: streams = list of bytes, ns = the reads' sample counts -> list of int16 arrays / None"""
+    lib = load_library()
+    nreads = len(streams)
+    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+    in_off = np.zeros(nreads, dtype=np.uint64)
+    if nreads > 1:
+        in_off[1:] = np.cumsum(in_len)[:-1]
+    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
+    ns = np.asarray(ns, dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    out_n = np.zeros(nreads, dtype=np.uint32)
+    rc = lib.press_hip_stall_depress_batch(comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads, sig.ctypes.data,
+                                           off.ctypes.data, ns.ctypes.data, total, out_n.ctypes.data, 0)
+    if rc:
+        raise PressError(last_error())
+    return [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)]
+
 
 VERIFIED = 0xFFFFFFFF  # PRESS_HIP_VERIFIED: first_bad of a read that decodes to the samples it is meant to hold
 

@@ -1017,6 +1017,76 @@ uint32_t press_hip_scratch_buffers(uint64_t *bytes);
  * the same figures before and after.  PRESS_HIP_EHIP without a device. */
 int press_hip_scratch_fill(int byte);
 
+/* ======================================================================= (2s) the stall methods */
+
+/*
+ * rccm_svbbe21_zd, dstall_fz_1500 and dstall_fz (press.c:7716-8148): the read is cut at a stall - the first segment
+ * (x, y) that sigtk's jnn_raw finds under JNNV1_CDNA_PARAM - and the stall and the rest are coded apart.  A family of
+ * its own with ids of its own; enum press_hip_method, PRESS_HIP_NMETHODS and the generic batch calls do not know them.
+ *
+ *   stream   [exists u8]  exists: [stall_start u16][stall_len u16][nstall u16][stall piece]  always: [nrest u32][rest piece]
+ *   rest     rccm_vbbe21_zd of the read without the samples [stall_start, stall_start + stall_len)
+ *   stall    rccm_vbbe21_submin of those samples as uint16: [min u16][vbbe21 section of x - min][one-byte values, rcms]
+ *   where    stall_start = (uint16_t) x, stall_len = (uint16_t) (y - x + 1) - the reference's truncations, kept; with the
+ *            threshold T: stall_len < T: no stall; else stall_start += 20 (in 16 bits), stall_len -= 40
+ *   T        rccm_svbbe21_zd 140, dstall_fz_1500 1500; dstall_fz makes the T = 140 stream and keeps it only where it is
+ *            strictly shorter than the read's bare rccm_vbbe21_zd stream (press.c:8006), else [0][u32][that stream]
+ * One decoder reads all three.  As in the svb family its nin carries the SAMPLE count, not the bytes (press.c:7871).
+ *
+ * Where the reference defines nothing, this library does:
+ *   1. No segment from jnn (n = 0 and every read the segmenter yields nothing for): no stall.  (The reference compares
+ *      an uninitialised stall_len with T there, press.c:7737, 7763.)
+ *   2. A stall piece of more than 65535 bytes - the reference truncates the count to 16 bits and writes a stream that does
+ *      not decode: rccm_svbbe21_zd and dstall_fz_1500 refuse the read (PRESS_HIP_FAILED), dstall_fz takes the form
+ *      without a stall.
+ *   3. A stream the decoder cannot trust is refused for that read before a byte of a piece is touched: exists neither 0
+ *      nor 1, stall_start + stall_len > n, a piece length that runs past in_len, an inner stream its own decoder
+ *      refuses.  The batch call marks it as every decoder of this library does, out_n[r] = UINT32_MAX; the per-read
+ *      symbols give *nout = 0.
+ * An empty read is refused, as rccm_vbbe21_zd refuses it.
+ */
+enum press_hip_stall_method {
+	PRESS_HIP_STALL_RCCM_SVBBE21_ZD = 0,
+	PRESS_HIP_STALL_DSTALL_FZ_1500  = 1,
+	PRESS_HIP_STALL_DSTALL_FZ       = 2,
+	PRESS_HIP_NSTALL                = 3
+};
+
+/* the reference's per-read symbols (press.h), synchronous; *nout of press: the capacity in, the length out (0: refused).
+ * depress: nin = the read's SAMPLE count; the bytes read are those the stream's own header announces. */
+uint64_t rccm_svbbe21_zd_bound_16(uint32_t nin);
+void rccm_svbbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rccm_svbbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t dstall_fz_1500_bound_16(uint32_t nin);
+void dstall_fz_1500_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void dstall_fz_1500_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t dstall_fz_bound_16(uint32_t nin);
+void dstall_fz_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void dstall_fz_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+
+/* the reference's X_bound_16: rccm_vbbe21_zd_bound_16(n) for all three; 0 for an id out of range */
+uint64_t press_hip_stall_bound(int stall_method, uint32_t n);
+
+/*
+ * The batch calls: arguments, layout rules and the meaning of device_resident as in press_hip_press_batch /
+ * press_hip_depress_batch (device resident: the call only enqueues on the current stream).
+ *   stall   NULL, or 2 * nreads words: (stall_start, stall_len) as written into read r's stream, (0, 0) where the stream
+ *           has no stall or the read failed
+ *   out_len the stream's bytes; PRESS_HIP_FAILED for a read that does not fit its slot (nothing outside a slot is
+ *           written, and nothing inside the slot of a read that fails), is empty, or is refused by rule 2
+ * depress: n[r] is the read's exact sample count (the range coder's streams do not carry it); out_n[r] = n[r], or
+ * UINT32_MAX for a refused read, whose room is not written.
+ */
+int press_hip_stall_press_batch(int stall_method, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len, uint32_t *stall,
+				int device_resident);
+int press_hip_stall_depress_batch(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t nreads, int16_t *sig,
+				  const uint64_t *off, const uint32_t *n, uint64_t total_samples, uint32_t *out_n, int device_resident);
+/* device scratch the two device-resident calls keep for a batch of this shape (the larger of the two per buffer): the
+ * inner method's, the pieces' samples (dstall_fz: up to twice the batch) and, for press, 6 bytes per piece sample of
+ * streams - the most a stream can take, so that only the caller's slot decides whether a read fits.  0 for a bad id. */
+uint64_t press_hip_stall_workspace_bytes(int stall_method, uint64_t total_samples, uint32_t nreads);
+
 /* ======================================================================= (3) BLOW5 files (host) */
 
 /*
