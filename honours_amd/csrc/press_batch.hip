@@ -109,7 +109,7 @@ extern "C" int press_hip_press_batch(int method, const int16_t *sig, const uint6
 	SamplesIn in = { sig, off, n };
 	SlotsOut so = host;
 	Staged st(nreads, s);
-	// host pointers: stage, run, copy back, synchronise
+	// host pointers: stage, run, copy back, synchronise (the slots' table goes up before the samples: samples_in in two steps)
 	if (!device_resident && ((rc = check_slots(out_off, nreads)) || (rc = st.layout(off, n, total_samples, "the sample range", true)) ||
 				 (rc = st.slots(host, so)) || (rc = st.samples(in, total_samples, in))))
 		return rc;
@@ -175,15 +175,13 @@ extern "C" int press_hip_press_sizes(int method, const int16_t *sig, const uint6
 	const PackArgs pk = { device_resident ? need : (uint64_t *) g.pneed.p, nullptr, (uint64_t *) g.pslot.p, 0, 1 };
 	SamplesIn in = { sig, off, n };
 	Staged st(nreads, s);
-	if (!device_resident && ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in))))
+	if (!device_resident && (rc = st.samples_in(in, total_samples, in)))
 		return rc;
 	bind_io(a, in);
 	bind_io(a, SlotsOut{ nullptr, pk.slot, pk.need }); // (need: an empty read's verdict of k_chunk_prep; the size kernel has the last word)
 	if ((rc = launch_press_packed(plan, a, pk, PACK_SIZE, s)) || device_resident)
 		return rc;
-	HIPCHK(hipMemcpyAsync(need, pk.need, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	return 0;
+	return st.fetch_tables({ { need, pk.need, (size_t) nreads * 8 } });
 }
 
 extern "C" int press_hip_press_packed(int method, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
@@ -215,7 +213,7 @@ extern "C" int press_hip_press_packed(int method, const int16_t *sig, const uint
 			return PRESS_HIP_EHIP;
 		pk.layout = (uint64_t *) g.arena_off.p;
 		so = { nullptr, pk.slot, (uint64_t *) g.lens.p };
-		if ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in)))
+		if ((rc = st.samples_in(in, total_samples, in)))
 			return rc;
 	}
 	bind_io(a, in);
@@ -242,7 +240,7 @@ extern "C" int press_hip_symbol_counts(const int16_t *sig, const uint64_t *off, 
 	if (nreads == 0)
 		return 0;
 	hipStream_t s = g.stream();
-	const uint32_t mc = (uint32_t) (total_samples / CHUNK + nreads + 1); // (as ScratchPlan::max_chunks)
+	const uint32_t mc = make_tiles_plan(total_samples, nreads).max_chunks; // (the buffers are its own, below)
 	int cus = 0;
 	HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g.device));
 	const uint32_t grid = (uint32_t) std::max(cus, 1) * TRAIN_WG_PER_CU;
@@ -271,9 +269,7 @@ extern "C" int press_hip_symbol_counts(const int16_t *sig, const uint64_t *off, 
 	launch_symbol_counts(in.sig, in.off, in.n, nreads, sum, g.chunks.p, nchunks, mc, (uint32_t) std::min<uint64_t>(grid, nch), s);
 	if ((rc = launch_status()) || device_resident)
 		return rc;
-	HIPCHK(hipMemcpyAsync(counts, sum, 257 * 8, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	return 0;
+	return st.fetch_tables({ { counts, sum, 257 * 8 } });
 }
 
 // ------------------------------------------------------------------ depress: samples, picoamperes, normalised floats, chunk rows
@@ -456,19 +452,17 @@ static int stats_begin(const SamplesIn &host, uint64_t total_samples, bool devic
 		       size_t result_bytes, Staged &st, DecodeArgs &a)
 {
 	int rc;
-	a = DecodeArgs{};
+	ScratchPlan plan = make_tiles_plan(total_samples, st.nreads);
+	plan.need(&Ctx::st_rows, rows_bytes).need(&Ctx::st_read, state_bytes);
+	if (!device_resident)
+		plan.need(&Ctx::st_stats, result_bytes);
+	if ((rc = plan.reserve()))
+		return rc;
+	plan.bind(a);
 	a.nreads = st.nreads;
-	a.max_chunks = (uint32_t) (total_samples / CHUNK + st.nreads + 1); // (as ScratchPlan::max_chunks)
-	if (g.pa_tile.reserve((size_t) a.max_chunks * sizeof(uint2)) || g.pa_ctl.reserve(64) || g.st_rows.reserve(rows_bytes) ||
-	    g.st_read.reserve(state_bytes))
-		return PRESS_HIP_EHIP;
 	SamplesIn in = host;
-	if (!device_resident) {
-		if (g.st_stats.reserve(result_bytes))
-			return PRESS_HIP_EHIP;
-		if ((rc = st.layout(host.off, host.n, total_samples, "the sample range", true)) || (rc = st.samples(host, total_samples, in)))
-			return rc;
-	}
+	if (!device_resident && (rc = st.samples_in(host, total_samples, in)))
+		return rc;
 	bind_io(a, in);
 	launch_pa_tiles(a, (uint2 *) g.pa_tile.p, (uint32_t *) g.pa_ctl.p, st.s);
 	return 0;
@@ -478,14 +472,6 @@ static void stats_launch(const DecodeArgs &a, int32_t *stats, hipEvent_t *ev, hi
 {
 	launch_signal_stats(a, (const uint2 *) g.pa_tile.p, (const uint32_t *) g.pa_ctl.p, g.st_read.p, (uint32_t *) g.st_rows.p, stats,
 			    nullptr, ev, s);
-}
-
-// the tail of their host-pointer form: the result back, synchronise
-static int stats_end(void *dst, size_t bytes, hipStream_t s)
-{
-	HIPCHK(hipMemcpyAsync(dst, g.st_stats.p, bytes, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	return 0;
 }
 
 extern "C" int press_hip_signal_stats(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
@@ -506,7 +492,7 @@ extern "C" int press_hip_signal_stats(const int16_t *sig, const uint64_t *off, c
 	stats_launch(a, device_resident ? stats : (int32_t *) g.st_stats.p, nullptr, s);
 	if ((rc = launch_status()) || device_resident)
 		return rc;
-	return stats_end(stats, (size_t) nreads * 8, s);
+	return st.fetch_tables({ { stats, g.st_stats.p, (size_t) nreads * 8 } });
 }
 
 // Quantiles of a batch: press_hip_signal_stats' layout and staging, nq ranks in four launches (press_quant.hip)
@@ -538,7 +524,7 @@ extern "C" int press_hip_signal_quantiles(const int16_t *sig, const uint64_t *of
 				rank_den, nq, device_resident ? q : (int32_t *) g.st_stats.p, nullptr, nullptr, s);
 	if ((rc = launch_status()) || device_resident)
 		return rc;
-	return stats_end(q, (size_t) nreads * nq * 4, s);
+	return st.fetch_tables({ { q, g.st_stats.p, (size_t) nreads * nq * 4 } });
 }
 
 // Profiling aid: the device-resident press_hip_signal_stats with an event behind every kernel; synchronous.
@@ -573,11 +559,77 @@ extern "C" int press_hip_signal_stats_timed(const int16_t *sig, const uint64_t *
 	return rc;
 }
 
+// ------------------------------------------------------------------ records of samples that are already there: two walks
+//
+// What press_hip_signal_events and press_hip_signal_segments share behind their checks.  Two walks over the reads: `count`
+// with the layout (first, count, and thr where the call has one), then `write` with the records of the reads that fit.
+// Host pointers: press_hip_signal_stats' staging; first[nreads] comes back between the walks, the records' arena is
+// reserved at min(need, cap) records and comes back in one transfer.
+
+struct RecordsOut { // the caller's results, or what is staged for them
+	void *rec;
+	uint64_t cap;
+	size_t rec_bytes;
+	uint64_t *first;
+	uint32_t *count;
+	float *thr; // NULL: not asked for, or a call without thresholds
+};
+struct RecordsStage { // the DevBufs of the host-pointer form: the calibration, first, count, the records; thr (NULL: a call without)
+	DevBuf &cal, &first, &cnt, &out;
+	DevBuf *thr;
+};
+
+template <class Count, class Write>
+static int two_walks(const SamplesIn &host, uint32_t nreads, uint64_t total_samples, const float *cal, const RecordsOut &out,
+		     const ScratchPlan &plan, const RecordsStage &b, int device_resident, Count count, Write write)
+{
+	int rc;
+	hipStream_t s = g.stream();
+	if (nreads == 0) { // (the layout of no reads: one zero)
+		if (device_resident)
+			HIPCHK(hipMemsetAsync(out.first, 0, 8, s));
+		else
+			out.first[0] = 0;
+		return 0;
+	}
+	if ((rc = plan.reserve()))
+		return rc;
+	if (device_resident) {
+		count(host, cal, out, s);
+		if (out.cap)
+			write(host, cal, out, s);
+		return launch_status();
+	}
+	SamplesIn in;
+	Staged st(nreads, s);
+	if ((rc = st.samples_in(host, total_samples, in)))
+		return rc;
+	const float *dcal = cal ? (const float *) b.cal.p : nullptr; // (NULL: the raw domain of the segments)
+	RecordsOut d = { nullptr, out.cap, out.rec_bytes, (uint64_t *) b.first.p, (uint32_t *) b.cnt.p, out.thr ? (float *) b.thr->p : nullptr };
+	if (cal)
+		HIPCHK(hipMemcpyAsync(b.cal.p, cal, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	count(in, dcal, d, s);
+	if ((rc = launch_status()) || (rc = st.fetch_tables({ { out.first, d.first, ((size_t) nreads + 1) * 8 },
+							       { out.count, d.count, (size_t) nreads * 4 },
+							       { out.thr, d.thr, (size_t) nreads * 8 } })))
+		return rc;
+	const uint64_t have = out.first[nreads] < out.cap ? out.first[nreads] : out.cap;
+	if (!have)
+		return 0;
+	if (b.out.reserve(have * out.rec_bytes))
+		return PRESS_HIP_EHIP;
+	HIPCHK(hipMemsetAsync(b.out.p, 0, have * out.rec_bytes, s)); // (the room of a read that did not fit: zeros)
+	d.rec = b.out.p;
+	write(in, dcal, d, s);
+	if ((rc = launch_status()) || (rc = st.fetch_prefix(out.rec, b.out.p, have * out.rec_bytes)))
+		return rc;
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
 // ------------------------------------------------------------------ events of samples that are already there
 //
-// press_hip_signal_stats' layout and staging; the kernels of press_events.hip.  Two walks over the reads: the count with the
-// layout, then the records.  Host pointers: ev_first[nreads] comes back between them, the records' arena is reserved at
-// min(need, ev_cap) records and comes back in one transfer.
+// two_walks over the kernels of press_events.hip.
 
 static_assert(sizeof(press_hip_event) == 16 && sizeof(press_hip_event_params) == sizeof(EvParams), "the event structs");
 
@@ -605,55 +657,22 @@ extern "C" int press_hip_signal_events(const int16_t *sig, const uint64_t *off, 
 		return set_error(PRESS_HIP_EARG, "window lengths %u, %u: 2 .. 64", prm->w1, prm->w2);
 	if ((rc = device_ready(NONE, NONE)))
 		return rc;
-	hipStream_t s = g.stream();
-	if (nreads == 0) { // (the layout of no reads: one zero)
-		if (device_resident)
-			HIPCHK(hipMemsetAsync(ev_first, 0, 8, s));
-		else
-			ev_first[0] = 0;
-		return 0;
-	}
 	const EvParams p = { prm->w1, prm->w2, prm->threshold1, prm->threshold2, prm->peak_height };
 	const ScratchPlan plan = make_events_plan(nreads, !device_resident);
-	if ((rc = plan.reserve()))
-		return rc;
-	void *state = plan.ptr(&Ctx::ev_state);
-	if (device_resident) {
-		launch_events_count(sig, off, n, nreads, cal, p, state, ev_cap, ev_first, ev_count, s);
-		if (ev_cap)
-			launch_events_write(sig, off, n, nreads, cal, p, state, ev, ev_cap, ev_first, s);
-		return launch_status();
-	}
-	SamplesIn in = { sig, off, n };
-	Staged st(nreads, s);
-	if ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in)))
-		return rc;
-	const float *dcal = (const float *) g.ev_cal.p;
-	uint64_t *dfirst = (uint64_t *) g.ev_first.p;
-	uint32_t *dcount = (uint32_t *) g.ev_cnt.p;
-	HIPCHK(hipMemcpyAsync(g.ev_cal.p, cal, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
-	launch_events_count(in.sig, in.off, in.n, nreads, dcal, p, state, ev_cap, dfirst, dcount, s);
-	if ((rc = launch_status()))
-		return rc;
-	HIPCHK(hipMemcpyAsync(ev_first, dfirst, ((size_t) nreads + 1) * 8, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipMemcpyAsync(ev_count, dcount, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	const uint64_t have = ev_first[nreads] < ev_cap ? ev_first[nreads] : ev_cap;
-	if (!have)
-		return 0;
-	if (g.ev_out.reserve(have * sizeof(press_hip_event)))
-		return PRESS_HIP_EHIP;
-	HIPCHK(hipMemsetAsync(g.ev_out.p, 0, have * sizeof(press_hip_event), s)); // (the room of a read that did not fit: zeros)
-	launch_events_write(in.sig, in.off, in.n, nreads, dcal, p, state, g.ev_out.p, ev_cap, dfirst, s);
-	if ((rc = launch_status()) || (rc = st.fetch_prefix(ev, g.ev_out.p, have * sizeof(press_hip_event))))
-		return rc;
-	HIPCHK(hipStreamSynchronize(s));
-	return 0;
+	return two_walks(
+		{ sig, off, n }, nreads, total_samples, cal, { ev, ev_cap, sizeof(press_hip_event), ev_first, ev_count, nullptr }, plan,
+		{ g.ev_cal, g.ev_first, g.ev_cnt, g.ev_out, nullptr }, device_resident,
+		[&](const SamplesIn &in, const float *c, const RecordsOut &o, hipStream_t s) {
+			launch_events_count(in.sig, in.off, in.n, nreads, c, p, plan.ptr(&Ctx::ev_state), o.cap, o.first, o.count, s);
+		},
+		[&](const SamplesIn &in, const float *c, const RecordsOut &o, hipStream_t s) {
+			launch_events_write(in.sig, in.off, in.n, nreads, c, p, plan.ptr(&Ctx::ev_state), o.rec, o.cap, o.first, s);
+		});
 }
 
 // ------------------------------------------------------------------ jnn segments and the adaptor of samples that are already there
 //
-// press_hip_signal_events' layout, staging and two walks; the kernels of press_segments.hip.
+// two_walks over the kernels of press_segments.hip (thr, and a NULL cal for the raw domain); the adaptor is one launch.
 
 static_assert(sizeof(press_hip_segment) == 8 && sizeof(press_hip_jnn_params) == sizeof(SegParams) &&
 		      sizeof(press_hip_jnn2_params) == sizeof(Seg2Params),
@@ -696,53 +715,17 @@ extern "C" int press_hip_signal_segments(const int16_t *sig, const uint64_t *off
 				 prm->window, prm->corrector, prm->error, prm->seg_dist);
 	if ((rc = device_ready(NONE, NONE)))
 		return rc;
-	hipStream_t s = g.stream();
-	if (nreads == 0) { // (the layout of no reads: one zero)
-		if (device_resident)
-			HIPCHK(hipMemsetAsync(seg_first, 0, 8, s));
-		else
-			seg_first[0] = 0;
-		return 0;
-	}
 	const SegParams p = { prm->std_scale, prm->corrector, prm->seg_dist, prm->window, prm->stall_len, prm->error, prm->top, prm->bot };
 	const ScratchPlan plan = make_segments_plan(nreads, !device_resident, cal != nullptr);
-	if ((rc = plan.reserve()))
-		return rc;
-	void *state = plan.ptr(&Ctx::sg_state);
-	if (device_resident) {
-		launch_segments_count(sig, off, n, nreads, cal, p, state, seg_cap, seg_first, seg_count, thr, s);
-		if (seg_cap)
-			launch_segments_write(sig, off, n, nreads, cal, p, state, seg, seg_cap, seg_first, s);
-		return launch_status();
-	}
-	SamplesIn in = { sig, off, n };
-	Staged st(nreads, s);
-	if ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in)))
-		return rc;
-	const float *dcal = cal ? (const float *) g.sg_cal.p : nullptr;
-	uint64_t *dfirst = (uint64_t *) g.sg_first.p;
-	uint32_t *dcount = (uint32_t *) g.sg_cnt.p;
-	if (cal)
-		HIPCHK(hipMemcpyAsync(g.sg_cal.p, cal, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
-	launch_segments_count(in.sig, in.off, in.n, nreads, dcal, p, state, seg_cap, dfirst, dcount, thr ? (float *) g.sg_thr.p : nullptr, s);
-	if ((rc = launch_status()))
-		return rc;
-	HIPCHK(hipMemcpyAsync(seg_first, dfirst, ((size_t) nreads + 1) * 8, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipMemcpyAsync(seg_count, dcount, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
-	if (thr)
-		HIPCHK(hipMemcpyAsync(thr, g.sg_thr.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	const uint64_t have = seg_first[nreads] < seg_cap ? seg_first[nreads] : seg_cap;
-	if (!have)
-		return 0;
-	if (g.sg_out.reserve(have * sizeof(press_hip_segment)))
-		return PRESS_HIP_EHIP;
-	HIPCHK(hipMemsetAsync(g.sg_out.p, 0, have * sizeof(press_hip_segment), s)); // (the room of a read that did not fit: zeros)
-	launch_segments_write(in.sig, in.off, in.n, nreads, dcal, p, state, g.sg_out.p, seg_cap, dfirst, s);
-	if ((rc = launch_status()) || (rc = st.fetch_prefix(seg, g.sg_out.p, have * sizeof(press_hip_segment))))
-		return rc;
-	HIPCHK(hipStreamSynchronize(s));
-	return 0;
+	return two_walks(
+		{ sig, off, n }, nreads, total_samples, cal, { seg, seg_cap, sizeof(press_hip_segment), seg_first, seg_count, thr }, plan,
+		{ g.sg_cal, g.sg_first, g.sg_cnt, g.sg_out, &g.sg_thr }, device_resident,
+		[&](const SamplesIn &in, const float *c, const RecordsOut &o, hipStream_t s) {
+			launch_segments_count(in.sig, in.off, in.n, nreads, c, p, plan.ptr(&Ctx::sg_state), o.cap, o.first, o.count, o.thr, s);
+		},
+		[&](const SamplesIn &in, const float *c, const RecordsOut &o, hipStream_t s) {
+			launch_segments_write(in.sig, in.off, in.n, nreads, c, p, plan.ptr(&Ctx::sg_state), o.rec, o.cap, o.first, s);
+		});
 }
 
 extern "C" int press_hip_signal_adaptor(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
@@ -770,16 +753,12 @@ extern "C" int press_hip_signal_adaptor(const int16_t *sig, const uint64_t *off,
 	}
 	SamplesIn in = { sig, off, n };
 	Staged st(nreads, s);
-	if ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in)))
+	if ((rc = st.samples_in(in, total_samples, in)))
 		return rc;
 	launch_adaptor(in.sig, in.off, in.n, nreads, p, (int32_t *) g.sg_out.p, thr ? (float *) g.sg_thr.p : nullptr, s);
 	if ((rc = launch_status()))
 		return rc;
-	HIPCHK(hipMemcpyAsync(pair, g.sg_out.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
-	if (thr)
-		HIPCHK(hipMemcpyAsync(thr, g.sg_thr.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	return 0;
+	return st.fetch_tables({ { pair, g.sg_out.p, (size_t) nreads * 8 }, { thr, g.sg_thr.p, (size_t) nreads * 8 } });
 }
 
 // ------------------------------------------------------------------ recode: streams in, streams out
@@ -1082,18 +1061,19 @@ extern "C" int press_hip_degrade_batch(const int16_t *sig, const uint64_t *off, 
 	if (nreads == 0)
 		return 0;
 	hipStream_t s = g.stream();
-	DecodeArgs a{};
+	ScratchPlan plan = make_tiles_plan(total_samples, nreads);
+	if (!device_resident)
+		plan.need(&Ctx::outn, (size_t) nreads * 4);
+	if ((rc = plan.reserve()))
+		return rc;
+	DecodeArgs a;
+	plan.bind(a);
 	a.nreads = nreads;
-	a.max_chunks = (uint32_t) (total_samples / CHUNK + nreads + 1); // (as ScratchPlan::max_chunks)
-	if (g.pa_tile.reserve((size_t) a.max_chunks * sizeof(uint2)) || g.pa_ctl.reserve(64))
-		return PRESS_HIP_EHIP;
 	SamplesIn in = { sig, off, n };
 	int16_t *dst = out;
 	Staged st(nreads, s);
 	if (!device_resident) {
-		if (g.outn.reserve((size_t) nreads * 4))
-			return PRESS_HIP_EHIP;
-		if ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in)))
+		if ((rc = st.samples_in(in, total_samples, in)))
 			return rc;
 		dst = (int16_t *) g.sig.p;
 		HIPCHK(hipMemcpyAsync(g.outn.p, g.nsamp.p, (size_t) nreads * 4, hipMemcpyDeviceToDevice, s)); // (fetch_elems' counts)
@@ -1131,14 +1111,12 @@ extern "C" int press_hip_signal_crc32(const int16_t *sig, const uint64_t *off, c
 	a.nreads = nreads;
 	SamplesIn in = { sig, off, n };
 	Staged st(nreads, s);
-	if (!device_resident && ((rc = st.layout(off, n, total_samples, "the sample range", true)) || (rc = st.samples(in, total_samples, in))))
+	if (!device_resident && (rc = st.samples_in(in, total_samples, in)))
 		return rc;
 	bind_io(a, in);
 	if ((rc = launch_signal_crc(plan, a, device_resident ? crc : (uint32_t *) g.vf_out.p, s)) || device_resident)
 		return rc;
-	HIPCHK(hipMemcpyAsync(crc, g.vf_out.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	return 0;
+	return st.fetch_tables({ { crc, g.vf_out.p, (size_t) nreads * 4 } });
 }
 
 extern "C" int press_hip_depress_crc_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
@@ -1166,10 +1144,7 @@ extern "C" int press_hip_depress_crc_batch(int method, const uint8_t *in, const 
 	bind_io(a, io);
 	if ((rc = launch_depress_crc(plan, a, device_resident ? crc : (uint32_t *) g.vf_out.p, s)) || device_resident)
 		return rc;
-	HIPCHK(hipMemcpyAsync(crc, g.vf_out.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	return 0;
+	return st.fetch_tables({ { crc, g.vf_out.p, (size_t) nreads * 4 }, { out_n, g.outn.p, (size_t) nreads * 4 } });
 }
 
 // press_hip_verify_batch (bits == 0) and press_hip_verify_degraded_batch
@@ -1213,11 +1188,7 @@ static int verify_batch(int method, uint32_t bits, const uint8_t *in, const uint
 	bind_io(a, io);
 	if ((rc = launch_verify(plan, a, want.sig, fb, nb, s, bits)) || device_resident)
 		return rc;
-	HIPCHK(hipMemcpyAsync(first_bad, fb, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipMemcpyAsync(nbad, nb, 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	return 0;
+	return st.fetch_tables({ { first_bad, fb, (size_t) nreads * 4 }, { nbad, nb, 4 }, { out_n, g.outn.p, (size_t) nreads * 4 } });
 }
 
 extern "C" int press_hip_verify_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,

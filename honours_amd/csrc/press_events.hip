@@ -9,7 +9,8 @@
 //                     machine on values read with v_readlane.  The doubles never reach memory: a detector keeps S and Q of
 //                     its pending peak, and an event is made of the sums at its two boundaries when the peak is emitted.
 //                     This launch only counts.
-//   k_events_scan     one wave: ev_first[] = the exclusive sums of the counts, ev_count[] with the reads that do not fit
+//   k_records_scan    one wave: ev_first[] = the exclusive sums of the counts, ev_count[] with the reads that do not fit
+//                     (the segments' layout too: launch_records_scan)
 //   k_events<true>    the same walk again, for the reads that fit, writing the records at ev_first[r]
 //
 // The sums.  The reference adds sequentially (events.c:299-302).  Before the walk the wave looks at the whole read once:
@@ -23,6 +24,7 @@
 // scheme: the carry is +0 or not zero, so carry + (a tile's -0) is +0 as the sequential sum is.
 
 #include <float.h>
+#include <stddef.h>
 
 #include "press_internal.h"
 #include "press_wave.h"
@@ -32,30 +34,18 @@
 namespace ph {
 
 constexpr uint32_t EV_RING = 256; // S, Q of positions [64 (t - 2), 64 (t + 1)] while tile t - 1 is worked on
-constexpr uint32_t EV_NOFIT = 0xFFFFFFFFu;
+constexpr uint32_t REC_NOFIT = 0xFFFFFFFFu; // count[r] of a read whose records do not fit (either record call)
 
 struct EvRec { // press_hip_event
 	uint32_t start, length;
 	float mean, stdv;
 };
-struct EvState { // per read, between the launches (8 bytes)
+struct EvState { // per read, between the launches (8 bytes); the count comes first: k_records_scan reads it there
 	uint32_t count, serial;
 };
+static_assert(offsetof(EvState, count) == 0, "k_records_scan: the count is the first word of a state record");
 
 __device__ uint32_t g_ev_serial; // reads whose sums took the serial path, since the library was loaded
-
-__device__ __forceinline__ double lane_f64(double v, uint32_t lane) // v of `lane` (wave-uniform), to every lane
-{
-	const uint64_t b = (uint64_t) __double_as_longlong(v);
-	const uint32_t lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) b, (int) lane);
-	const uint32_t hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (b >> 32), (int) lane);
-	return __longlong_as_double((long long) (((uint64_t) hi << 32) | lo));
-}
-
-__device__ __forceinline__ float lane_f32(float v, uint32_t lane)
-{
-	return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int) lane));
-}
 
 __device__ __forceinline__ double wave_incl_f64(double v, uint32_t lane)
 {
@@ -319,32 +309,34 @@ __global__ __launch_bounds__(64) void k_events(const int16_t *sig, const uint64_
 	}
 }
 
-// One wave: ev_first[0] = 0, ev_first[r + 1] = ev_first[r] + count[r]; ev_count[r] = count[r] where the read fits
-__global__ __launch_bounds__(64) void k_events_scan(const EvState *state, uint32_t nreads, uint64_t ev_cap, uint64_t *ev_first,
-						     uint32_t *ev_count)
+// One wave, the layout of either record call (launch_records_scan, press_internal.h): first[0] = 0, first[r + 1] =
+// first[r] + count of read r; count[r] = that count where the read fits below cap.  The count is the first word of a
+// state record of `stride` bytes (EvState, SegState)
+__global__ __launch_bounds__(64) void k_records_scan(const uint8_t *state, uint32_t stride, uint32_t nreads, uint64_t cap, uint64_t *first,
+						      uint32_t *count)
 {
 	const uint32_t lane = threadIdx.x;
 	uint64_t before = 0;
 	if (lane == 0)
-		ev_first[0] = 0;
+		first[0] = 0;
 	for (uint32_t r0 = 0; r0 < nreads; r0 += 64) {
 		const uint32_t r = r0 + lane;
-		const uint32_t c = r < nreads && r >= r0 ? state[r].count : 0u;
-		uint64_t inc = c;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint64_t o = __shfl_up(inc, d, 64);
-			if (lane >= (uint32_t) d)
-				inc += o;
-		}
+		const uint32_t c = r < nreads && r >= r0 ? *reinterpret_cast<const uint32_t *>(state + (size_t) r * stride) : 0u;
+		const uint64_t inc = wave_incl_scan64(c, lane);
 		if (r < nreads && r >= r0) {
-			ev_first[(size_t) r + 1] = before + inc;
-			ev_count[r] = before + inc <= ev_cap ? c : EV_NOFIT;
+			first[(size_t) r + 1] = before + inc;
+			count[r] = before + inc <= cap ? c : REC_NOFIT;
 		}
 		before += __shfl(inc, 63, 64);
 		if (r0 + 64 < r0)
 			break;
 	}
+}
+
+void launch_records_scan(const void *state, uint32_t state_stride, uint32_t nreads, uint64_t cap, uint64_t *first, uint32_t *count,
+			 hipStream_t s)
+{
+	hipLaunchKernelGGL(k_records_scan, dim3(1), dim3(64), 0, s, (const uint8_t *) state, state_stride, nreads, cap, first, count);
 }
 
 uint64_t events_state_bytes(uint32_t nreads) { return (uint64_t) nreads * sizeof(EvState); }
@@ -358,7 +350,7 @@ void launch_events_count(const int16_t *sig, const uint64_t *off, const uint32_t
 			   (EvState *) state, (EvRec *) nullptr, ev_cap, (const uint64_t *) nullptr);
 	ktime_end(1, s);
 	ktime_begin(1, s);
-	hipLaunchKernelGGL(k_events_scan, dim3(1), dim3(64), 0, s, (const EvState *) state, nreads, ev_cap, ev_first, ev_count);
+	launch_records_scan(state, sizeof(EvState), nreads, ev_cap, ev_first, ev_count, s);
 	ktime_end(1, s);
 }
 

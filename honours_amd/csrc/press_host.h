@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 
@@ -137,11 +138,19 @@ struct Staged {
 	// in the refusal (NULL: reads may overlap)
 	int layout(const uint64_t *off, const uint32_t *n, uint64_t total_samples, const char *what, bool with_sig);
 	int samples(const SamplesIn &h, uint64_t total_samples, SamplesIn &d); // behind layout(): the samples -> d
+	// the two in one, for reads that must not overlap ("the sample range"): the head of a call over samples that are there
+	int samples_in(const SamplesIn &h, uint64_t total_samples, SamplesIn &d);
 	int slots(const SlotsOut &h, SlotsOut &d);                              // an arena for the slots (checked: check_slots) -> d
 	// layout() of the rooms, then the streams dense in `arena`, their table in `offs` -> d; d.sig: g.sig with sig_room,
 	// else h.sig as it is
 	int streams(const StreamsIn &h, uint64_t total_samples, bool sig_room, DevBuf &arena, DevBuf &offs, StreamsIn &d);
 	// the tails; all but fetch_prefix end with the stream synchronised
+	struct Table { // a per-read result table on its way back; dst NULL: the caller did not ask for it
+		void *dst;
+		const void *dev;
+		size_t bytes;
+	};
+	int fetch_tables(std::initializer_list<Table> tables);                     // each table in turn
 	int fetch_streams(const SlotsOut &h);                                      // out_len, the streams of slots()' arena
 	int fetch_elems(void *dst, const void *dev, size_t es, const StreamsIn &h); // out_n, the decoded elements of `dev`
 	int fetch_samples(const StreamsIn &h);                                     // ... the samples of g.sig into h.sig
@@ -243,6 +252,8 @@ struct ScratchPlan {
 	ZsBufs zs() const;                 // z with its pointers
 };
 ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool decode);
+// The calls that decode nothing and walk samples by launch_pa_tiles' table: make_plan's max_chunks, and the table
+ScratchPlan make_tiles_plan(uint64_t total_samples, uint32_t nreads);
 
 // press_hip_recode_batch: src's streams -> samples -> dst's streams in one call.  d and p are the plans the two batch calls
 // would make (their bind()s and counts serve the two halves); `all` is what the call reserves: every buffer at the larger

@@ -403,6 +403,11 @@ void launch_events_count(const int16_t *sig, const uint64_t *off, const uint32_t
 void launch_events_write(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const float *cal,
 			 const EvParams &p, void *state, void *ev, uint64_t ev_cap, const uint64_t *ev_first, hipStream_t s);
 uint32_t events_serial_reads(hipStream_t s); // synchronises s
+// ... and the layout between the two walks of either record call, one wave: first[0] = 0, first[r + 1] = first[r] + the
+// count of read r, count[r] = that count where first[r + 1] <= cap, else 0xFFFFFFFF.  state: nreads records of
+// state_stride bytes, the count in the first 32-bit word of each
+void launch_records_scan(const void *state, uint32_t state_stride, uint32_t nreads, uint64_t cap, uint64_t *first, uint32_t *count,
+			 hipStream_t s);
 // press_segments.hip: sigtk's jnn segments of the n[r] samples at sig + off[r] (include/press_hip.h,
 // press_hip_signal_segments), a wave per read, in two walks as the events; cal NULL: the raw domain; thr NULL, or 2 * nreads.
 // state: segments_state_bytes.  launch_adaptor: jnnv2, one launch, no state.  Timed as ring 1 of press_hip_kernel_times

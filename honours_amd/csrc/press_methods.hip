@@ -71,6 +71,17 @@ void *ScratchPlan::ptr(DevBuf Ctx::*buf) const
 	return nullptr;
 }
 
+// Chunks (and tiles of the sample walkers) a batch can have: CHUNK samples each, and a partial one per read
+static inline uint32_t plan_max_chunks(uint64_t total_samples, uint32_t nreads) { return (uint32_t) (total_samples / CHUNK + nreads + 1); }
+
+ScratchPlan make_tiles_plan(uint64_t total_samples, uint32_t nreads)
+{
+	ScratchPlan p{};
+	p.max_chunks = plan_max_chunks(total_samples, nreads);
+	p.need(&Ctx::pa_tile, (size_t) p.max_chunks * sizeof(uint2)).need(&Ctx::pa_ctl, 64);
+	return p;
+}
+
 ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool decode)
 {
 	ScratchPlan p{};
@@ -78,7 +89,7 @@ ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool 
 	const bool zs = p.m->family == FAM_ZSTD;
 	const Method &k = zs ? METHODS[p.m->inner] : *p.m; // the method whose kernels make / read the samples
 	const size_t nr = (size_t) nreads + 1;
-	p.max_chunks = (uint32_t) (total_samples / CHUNK + nreads + 1);
+	p.max_chunks = plan_max_chunks(total_samples, nreads);
 	const size_t mc = p.max_chunks;
 	p.need(&Ctx::meta, nr * sizeof(ReadMeta));
 	if (zs) {
@@ -230,14 +241,13 @@ ScratchPlan make_chunks_plan(int method, uint64_t total_samples, uint32_t nreads
 // Verify and CRC-32: the general picoampere plan (decode, samples, tile table) for every method, and a word per read
 ScratchPlan make_verify_plan(int method, uint64_t total_samples, uint32_t nreads, bool host)
 {
-	ScratchPlan p{};
-	if (method >= 0) {
+	const ScratchPlan tiles = make_tiles_plan(total_samples, nreads);
+	ScratchPlan p = tiles;
+	if (method >= 0) { // (the same max_chunks)
 		p = make_plan(method, total_samples, nreads, true);
-		p.need(&Ctx::rsig, total_samples * 2 + 64);
-	} else {
-		p.max_chunks = (uint32_t) (total_samples / CHUNK + nreads + 1); // (as make_plan)
+		p.need(&Ctx::rsig, total_samples * 2 + 64).merge(tiles);
 	}
-	p.need(&Ctx::pa_tile, (size_t) p.max_chunks * sizeof(uint2)).need(&Ctx::pa_ctl, 64).need(&Ctx::vf_raw, (size_t) nreads * 4 + 4);
+	p.need(&Ctx::vf_raw, (size_t) nreads * 4 + 4);
 	if (host)
 		p.need(&Ctx::vf_out, (size_t) nreads * 4 + 4);
 	return p;

@@ -9,13 +9,16 @@
 //                      wave-uniform 64-bit mask, and jnn_core's state machine is stepped over it in scalar registers by
 //                      uniform branches; the stretches where nothing can happen are jumped with a find-first-set.  This
 //                      launch only counts; it leaves the count and the two thresholds per read (16 bytes).
-//   k_segments_scan    one wave: seg_first[] = the exclusive sums of the counts, seg_count[] with the reads that do not fit
+//   k_records_scan     (press_events.hip) one wave: seg_first[] = the exclusive sums of the counts, seg_count[] with the
+//                      reads that do not fit
 //   k_segments<true>   pass 3 again with the thresholds of the first launch, for the reads that fit, writing the records
 //   k_adaptor          one wave per read, the same three passes over t[j], the rolling mean of `window` samples; the
 //                      window sums are integers (below 2^24, so the reference's rolling float sum never rounds): the sum
 //                      at a tile's first position is carried, the others come from a wave scan of s[j + window] - s[j]
 //
 // A sum starting at +0 is never -0 (a + b = -0 only for a = b = -0), so the +0 that the lanes beyond n add changes nothing.
+
+#include <stddef.h>
 
 #include "press_internal.h"
 #include "press_wave.h"
@@ -24,29 +27,24 @@
 
 namespace ph {
 
-constexpr uint32_t SEG_NOFIT = 0xFFFFFFFFu;
 constexpr uint32_t SEG_NONE = 0xFFFFFFFFu; // launch_segments_first: start of a read without a segment (press_internal.h: STALL_NOSEG)
 constexpr uint32_t SEG_AHEAD = 4; // tiles whose loads are in flight while a group of as many is worked on
 
 struct SegRec { // press_hip_segment
 	uint32_t start, end;
 };
-struct SegState { // per read, between the launches (16 bytes)
+struct SegState { // per read, between the launches (16 bytes); the count comes first: launch_records_scan reads it there
 	uint32_t count, pad;
 	float bot, top;
 };
-
-__device__ __forceinline__ float seg_lane_f32(float v, uint32_t lane)
-{
-	return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int) lane));
-}
+static_assert(offsetof(SegState, count) == 0, "k_records_scan: the count is the first word of a state record");
 
 // carry + v[0] + v[1] + ... + v[63], added in that order
 __device__ __forceinline__ float seg_chain(float carry, float v)
 {
 #pragma unroll
 	for (uint32_t j = 0; j < 64; j++)
-		carry = carry + seg_lane_f32(v, j);
+		carry = carry + lane_f32(v, j);
 	return carry;
 }
 
@@ -247,34 +245,6 @@ __global__ __launch_bounds__(64) void k_segments(const int16_t *sig, const uint6
 	}
 }
 
-// One wave: seg_first[0] = 0, seg_first[r + 1] = seg_first[r] + count[r]; seg_count[r] = count[r] where the read fits
-__global__ __launch_bounds__(64) void k_segments_scan(const SegState *state, uint32_t nreads, uint64_t seg_cap, uint64_t *seg_first,
-						       uint32_t *seg_count)
-{
-	const uint32_t lane = threadIdx.x;
-	uint64_t before = 0;
-	if (lane == 0)
-		seg_first[0] = 0;
-	for (uint32_t r0 = 0; r0 < nreads; r0 += 64) {
-		const uint32_t r = r0 + lane;
-		const uint32_t c = r < nreads && r >= r0 ? state[r].count : 0u;
-		uint64_t inc = c;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint64_t o = __shfl_up(inc, d, 64);
-			if (lane >= (uint32_t) d)
-				inc += o;
-		}
-		if (r < nreads && r >= r0) {
-			seg_first[(size_t) r + 1] = before + inc;
-			seg_count[r] = before + inc <= seg_cap ? c : SEG_NOFIT;
-		}
-		before += __shfl(inc, 63, 64);
-		if (r0 + 64 < r0)
-			break;
-	}
-}
-
 // ------------------------------------------------------------------ jnnv2
 
 // f(t, tv, valid): tile t of the m = n - window rolling means, tv the lane's (valid: its position is below m); f returns
@@ -430,7 +400,7 @@ void launch_segments_count(const int16_t *sig, const uint64_t *off, const uint32
 			   (SegRec *) nullptr, seg_cap, (const uint64_t *) nullptr);
 	ktime_end(1, s);
 	ktime_begin(1, s);
-	hipLaunchKernelGGL(k_segments_scan, dim3(1), dim3(64), 0, s, (const SegState *) state, nreads, seg_cap, seg_first, seg_count);
+	launch_records_scan(state, sizeof(SegState), nreads, seg_cap, seg_first, seg_count, s);
 	ktime_end(1, s);
 }
 

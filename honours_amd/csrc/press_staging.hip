@@ -312,6 +312,12 @@ int Staged::samples(const SamplesIn &h, uint64_t total_samples, SamplesIn &d)
 	return rc;
 }
 
+int Staged::samples_in(const SamplesIn &h, uint64_t total_samples, SamplesIn &d)
+{
+	const int rc = layout(h.off, h.n, total_samples, "the sample range", true);
+	return rc ? rc : samples(h, total_samples, d);
+}
+
 int Staged::slots(const SlotsOut &h, SlotsOut &d)
 {
 	const uint64_t a0 = h.out_off[0], a1 = h.out_off[nreads];
@@ -355,6 +361,16 @@ int Staged::streams(const StreamsIn &h, uint64_t total_samples, bool sig_room, D
 	}
 	d = { (const uint8_t *) arena.p,      (const uint64_t *) offs.p, (const uint64_t *) g.lens2.p, (const uint64_t *) g.off.p,
 	      (const uint32_t *) g.nsamp.p,  (uint32_t *) g.outn.p,     sig_room ? (int16_t *) g.sig.p : h.sig };
+	return 0;
+}
+
+// The tail of a host-pointer call whose results are per-read tables and nothing else
+int Staged::fetch_tables(std::initializer_list<Table> tables)
+{
+	for (const Table &t : tables)
+		if (t.dst)
+			HIPCHK(hipMemcpyAsync(t.dst, t.dev, t.bytes, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
 	return 0;
 }
 

@@ -47,17 +47,6 @@ __device__ __forceinline__ uint64_t up8(uint64_t n) { return (n + 7) & ~7ull; }
 // 32-bit position deltas, 16-bit values) + a byte per other sample + what the coder adds to a stream it stores raw
 __device__ __forceinline__ uint64_t piece_cap(uint64_t np) { return np ? (6 * np + 64 + 15) & ~15ull : 0ull; }
 
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v, uint32_t lane)
-{
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint64_t o = __shfl_up(v, d, 64);
-		if (lane >= (uint32_t) d)
-			v += o;
-	}
-	return v;
-}
-
 // dst[0, nb) = src[0, nb) by the lanes of a wave: the bytes in front of dst's first 16-byte boundary, 16-byte stores
 // fed by loads at whatever address the source has, the last bytes
 __device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *src, uint64_t nb, uint32_t lane)

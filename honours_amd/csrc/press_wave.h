@@ -1,4 +1,5 @@
-// press_wave.h - wave-level helpers of the chunked kernels (press_chunked.hip, press_train.hip).
+// press_wave.h - wave-level helpers shared by the kernel files.  Only moves of bits and integer arithmetic: the units that
+// compile with fp contract(off) include this header, and a float operation here would escape their pragma.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,6 +35,31 @@ __device__ __forceinline__ uint32_t prev_lane(uint32_t v, uint32_t lane0)
 {
 	// DPP wave_shr:1 - lane l reads lane l-1; lane 0 keeps `old`
 	return (uint32_t) __builtin_amdgcn_update_dpp((int) lane0, (int) v, 0x138, 0xf, 0xf, false);
+}
+
+// v of `lane` (wave-uniform), to every lane
+__device__ __forceinline__ float lane_f32(float v, uint32_t lane)
+{
+	return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int) lane));
+}
+__device__ __forceinline__ double lane_f64(double v, uint32_t lane)
+{
+	const uint64_t b = (uint64_t) __double_as_longlong(v);
+	const uint32_t lo = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) b, (int) lane);
+	const uint32_t hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (b >> 32), (int) lane);
+	return __longlong_as_double((long long) (((uint64_t) hi << 32) | lo));
+}
+
+// inclusive sum over the lanes of a wave
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v, uint32_t lane)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint64_t o = __shfl_up(v, d, 64);
+		if (lane >= (uint32_t) d)
+			v += o;
+	}
+	return v;
 }
 
 // zig-zag delta of the two samples packed in `cur`, given the dword holding the two

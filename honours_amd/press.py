@@ -647,11 +647,7 @@ def signal_quantiles(sig, off, n, ranks, q):
 def signal_quantiles_host(reads, ranks):
     """quantiles of a list of int16 arrays (host buffers, synchronous) -> (nreads, len(ranks)) int32"""
     lib = load_library()
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
+    sig, off, ns, total = _host_batch(reads)
     num, den = _ranks(ranks)
     q = np.zeros((len(reads), num.size), dtype=np.int32)
     if lib.press_hip_signal_quantiles(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, num.ctypes.data,
@@ -696,8 +692,8 @@ def depress_chunks_batch(method, comp, in_off, in_len, rows, row_first, off, n, 
     dt = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}.get(rows.dtype)
     if dt is None or rows.dim() != 2 or not rows.is_contiguous():
         raise PressError("rows must be a contiguous [nrows, T] tensor of float32, float16 or bfloat16")
-    if q is not None and (q.numel() < 2 * nreads or q.element_size() != 4 or not q.is_contiguous()):
-        raise PressError("q must be a contiguous 32-bit tensor of 2 * nreads entries")
+    if q is not None:
+        _f32_pairs(q, nreads, "q")
     if row_first.numel() < nreads + 1 or row_first.element_size() != 8:
         raise PressError("row_first must be a 64-bit tensor of nreads + 1 entries")
     rc = load_library().press_hip_depress_chunks_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
@@ -741,11 +737,7 @@ def degrade_batch_host(reads, bits):
     """D_bits with host buffers: reads = list of int16 arrays -> list of int16 arrays"""
     lib = load_library()
     nreads = len(reads)
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
+    sig, off, ns, total = _host_batch(reads)
     out = np.zeros(total + 64, dtype=np.int16)
     if lib.press_hip_degrade_batch(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total, int(bits),
                                    out.ctypes.data, 0):
@@ -916,15 +908,22 @@ def _layout(ns):
     return off, int(pad.sum())
 
 
+def _host_batch(reads, alloc=np.zeros):
+    """a list of int16 arrays laid out by _layout in one arena from alloc(count, dtype), which returns zeros
+    -> (sig, off, ns uint32, total)"""
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = alloc(total + 64, np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    return sig, off, ns, total
+
+
 def press_batch_host(method, reads, caps=None):
     """Batch call with host buffers: reads = list of int16 arrays -> list of bytes / None."""
     lib = load_library()
     nreads = len(reads)
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
+    sig, off, ns, total = _host_batch(reads)
     if caps is None:
         caps = [int(lib.press_hip_bound(_mid(method), int(x))) + 1024 for x in ns]
     out_off = np.zeros(nreads + 1, dtype=np.uint64)
@@ -948,11 +947,7 @@ def press_packed_host(method, reads, align=1):
     exceeds it."""
     lib = load_library()
     nreads = len(reads)
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
+    sig, off, ns, total = _host_batch(reads)
     need = np.zeros(nreads, dtype=np.uint64)
     if lib.press_hip_press_sizes(_mid(method), sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total,
                                  need.ctypes.data, 0):
@@ -1073,11 +1068,7 @@ def depress_chunks_batch_host(method, streams, ns, T, overlap, dtype="float16", 
 def signal_stats_host(reads):
     """{median, MAD} of a list of int16 arrays (host buffers, synchronous) -> (nreads, 2) int32"""
     lib = load_library()
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
+    sig, off, ns, total = _host_batch(reads)
     stats = np.zeros((len(reads), 2), dtype=np.int32)
     if lib.press_hip_signal_stats(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, stats.ctypes.data, 0):
         raise PressError(last_error())
@@ -1104,6 +1095,41 @@ def event_params(rna=False):
     return p
 
 
+def _i64_first(t, nreads, name):
+    if t.numel() < nreads + 1 or t.element_size() != 8 or not t.is_contiguous():
+        raise PressError("%s must be a contiguous 64-bit tensor of nreads + 1 entries" % name)
+
+
+def _f32_pairs(t, nreads, name, kind="32-bit"):
+    if t.numel() < 2 * nreads or t.element_size() != 4 or not t.is_contiguous():
+        raise PressError("%s must be a contiguous %s tensor of 2 * nreads entries" % (name, kind))
+
+
+def _record_cap(rec, words, cap, name):
+    """rec: None or a contiguous 32-bit tensor of `words` words per record; cap: None (the rows of rec) or a limit within
+    them -> the cap to call with"""
+    rows = 0
+    if rec is not None:
+        if rec.element_size() != 4 or not rec.is_contiguous() or rec.numel() % words:
+            raise PressError("%s must be a contiguous 32-bit tensor of %d words per record" % (name, words))
+        rows = rec.numel() // words
+    cap = rows if cap is None else int(cap)
+    if cap > rows:
+        raise PressError("%s_cap is beyond %s" % (name, name))
+    return cap
+
+
+def _count_then_records(call, first, cap, dtype):
+    """The host forms of the record calls: call(rec, cap) fills `first`; cap None: what the batch needs, found with a pure
+    count; then the records -> the min(need, cap) of them that were written"""
+    if cap is None:
+        call(None, 0)
+        cap = int(first[-1])
+    rec = np.zeros(int(cap), dtype=dtype)
+    call(rec, int(cap))
+    return rec[:min(int(first[-1]), int(cap))]
+
+
 def signal_events(sig, off, n, cal, prm, ev, ev_first, ev_count, ev_cap=None):
     """Enqueue the event detection of a batch of samples (CUDA tensors as in signal_stats; cal float32 of 2 * nreads:
     pa_cal; prm an EventParams; ev: 16-byte records as a 32-bit tensor of [cap, 4] - start, length, mean bits, stdv bits -
@@ -1112,18 +1138,9 @@ def signal_events(sig, off, n, cal, prm, ev, ev_first, ev_count, ev_cap=None):
     (press_hip_signal_events)."""
     nreads = off.numel()
     _u32_table(ev_count, nreads, "ev_count")
-    if ev_first.numel() < nreads + 1 or ev_first.element_size() != 8 or not ev_first.is_contiguous():
-        raise PressError("ev_first must be a contiguous 64-bit tensor of nreads + 1 entries")
-    if cal.numel() < 2 * nreads or cal.element_size() != 4 or not cal.is_contiguous():
-        raise PressError("cal must be a contiguous float32 tensor of 2 * nreads entries")
-    rows = 0
-    if ev is not None:
-        if ev.element_size() != 4 or not ev.is_contiguous() or ev.numel() % 4:
-            raise PressError("ev must be a contiguous 32-bit tensor of 4 words per record")
-        rows = ev.numel() // 4
-    cap = rows if ev_cap is None else int(ev_cap)
-    if cap > rows:
-        raise PressError("ev_cap is beyond ev")
+    _i64_first(ev_first, nreads, "ev_first")
+    _f32_pairs(cal, nreads, "cal", "float32")
+    cap = _record_cap(ev, 4, ev_cap, "ev")
     if load_library().press_hip_signal_events(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(), cal.data_ptr(),
                                               ctypes.addressof(prm), ev.data_ptr() if cap else None, cap,
                                               ev_first.data_ptr(), ev_count.data_ptr(), 1):
@@ -1137,11 +1154,7 @@ def signal_events_host(reads, cal, prm=None, ev_cap=None):
     nreads + 1, ev_count uint32 per read (0xFFFFFFFF: the read did not fit)."""
     lib = load_library()
     prm = event_params() if prm is None else prm
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
+    sig, off, ns, total = _host_batch(reads)
     cal = np.ascontiguousarray(cal, dtype=np.float32).reshape(-1)
     if cal.size != 2 * len(reads):
         raise PressError("cal: two floats per read")
@@ -1154,12 +1167,7 @@ def signal_events_host(reads, cal, prm=None, ev_cap=None):
                                        ev_count.ctypes.data, 0):
             raise PressError(last_error())
 
-    if ev_cap is None:
-        call(None, 0)
-        ev_cap = int(ev_first[-1])
-    ev = np.zeros(int(ev_cap), dtype=EVENT_DTYPE)
-    call(ev, int(ev_cap))
-    return ev[:min(int(ev_first[-1]), int(ev_cap))], ev_first, ev_count
+    return _count_then_records(call, ev_first, ev_cap, EVENT_DTYPE), ev_first, ev_count
 
 
 def events_serial_reads():
@@ -1209,11 +1217,6 @@ def jnn2_params():
     return p
 
 
-def _f32_pairs(t, nreads, name):
-    if t.numel() < 2 * nreads or t.element_size() != 4 or not t.is_contiguous():
-        raise PressError("%s must be a contiguous 32-bit tensor of 2 * nreads entries" % name)
-
-
 def signal_segments(sig, off, n, cal, prm, seg, seg_first, seg_count, thr=None, seg_cap=None):
     """Enqueue the jnn segmentation of a batch of samples (CUDA tensors as in signal_events; cal float32 of 2 * nreads or
     None for the raw domain; prm a JnnParams; seg: 8-byte records as a 32-bit tensor of [cap, 2] - start, end - or None
@@ -1222,34 +1225,17 @@ def signal_segments(sig, off, n, cal, prm, seg, seg_first, seg_count, thr=None, 
     (default: the rows of seg), else seg_count[r] = 0xFFFFFFFF (press_hip_signal_segments)."""
     nreads = off.numel()
     _u32_table(seg_count, nreads, "seg_count")
-    if seg_first.numel() < nreads + 1 or seg_first.element_size() != 8 or not seg_first.is_contiguous():
-        raise PressError("seg_first must be a contiguous 64-bit tensor of nreads + 1 entries")
+    _i64_first(seg_first, nreads, "seg_first")
     if cal is not None:
         _f32_pairs(cal, nreads, "cal")
     if thr is not None:
         _f32_pairs(thr, nreads, "thr")
-    rows = 0
-    if seg is not None:
-        if seg.element_size() != 4 or not seg.is_contiguous() or seg.numel() % 2:
-            raise PressError("seg must be a contiguous 32-bit tensor of 2 words per record")
-        rows = seg.numel() // 2
-    cap = rows if seg_cap is None else int(seg_cap)
-    if cap > rows:
-        raise PressError("seg_cap is beyond seg")
+    cap = _record_cap(seg, 2, seg_cap, "seg")
     if load_library().press_hip_signal_segments(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
                                                 cal.data_ptr() if cal is not None else None, ctypes.addressof(prm),
                                                 seg.data_ptr() if cap else None, cap, seg_first.data_ptr(),
                                                 seg_count.data_ptr(), thr.data_ptr() if thr is not None else None, 1):
         raise PressError(last_error())
-
-
-def _host_batch(reads):
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
-    return sig, off, ns, total
 
 
 def signal_segments_host(reads, cal=None, prm=None, seg_cap=None, want_thr=True):
@@ -1276,12 +1262,7 @@ def signal_segments_host(reads, cal=None, prm=None, seg_cap=None, want_thr=True)
                                          thr.ctypes.data if want_thr else None, 0):
             raise PressError(last_error())
 
-    if seg_cap is None:
-        call(None, 0)
-        seg_cap = int(seg_first[-1])
-    seg = np.zeros(int(seg_cap), dtype=SEGMENT_DTYPE)
-    call(seg, int(seg_cap))
-    return seg[:min(int(seg_first[-1]), int(seg_cap))], seg_first, seg_count, thr
+    return _count_then_records(call, seg_first, seg_cap, SEGMENT_DTYPE), seg_first, seg_count, thr
 
 
 def signal_segments_workspace_bytes(total_samples, nreads):
@@ -1390,11 +1371,7 @@ def stall_press_batch_host(method, reads, caps=None, want_stall=False):
     """Host buffers: reads = list of int16 arrays -> list of bytes / None (want_stall: and uint32 [nreads, 2])"""
     lib = load_library()
     nreads = len(reads)
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
+    sig, off, ns, total = _host_batch(reads)
     if caps is None:
         caps = [stall_bound(method, int(x)) + 1024 if x else 32 for x in ns]
     out_off = np.zeros(nreads + 1, dtype=np.uint64)
@@ -1458,11 +1435,7 @@ def signal_crc32(sig, off, n, crc):
 def signal_crc32_host(reads):
     """CRC-32 of a list of int16 arrays (host buffers, synchronous) -> uint32[nreads]"""
     lib = load_library()
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
+    sig, off, ns, total = _host_batch(reads)
     crc = np.zeros(len(reads), dtype=np.uint32)
     if lib.press_hip_signal_crc32(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, crc.ctypes.data, 0):
         raise PressError(last_error())
@@ -1532,11 +1505,7 @@ def verify_batch_host(method, streams, reads, degrade_bits=0):
     if len(reads) != nreads:
         raise PressError("verify_batch_host: one stream per read")
     comp, in_off, in_len = _streams_arena(streams)
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
+    sig, off, ns, total = _host_batch(reads)
     first_bad = np.zeros(nreads, dtype=np.uint32)
     out_n = np.zeros(nreads, dtype=np.uint32)
     nbad = ctypes.c_uint32(0)
@@ -1559,12 +1528,12 @@ class HostBatch:
         self.lib, self.mid, self.nreads = lib, _mid(method), len(reads)
         self.pinned = pinned
         self._held = []
-        self.ns = np.array([len(r) for r in reads], dtype=np.uint32)
-        self.off, self.total = _layout(self.ns)
-        self.sig = self._alloc(self.total + 64, np.int16)
-        self.sig[:] = 0
-        for r, o in zip(reads, self.off):
-            self.sig[int(o): int(o) + len(r)] = r
+        def zeroed(count, dtype):  # (page-locked memory comes as it is)
+            a = self._alloc(count, dtype)
+            a[:] = 0
+            return a
+
+        self.sig, self.off, self.ns, self.total = _host_batch(reads, zeroed)
         caps = [int(lib.press_hip_bound(self.mid, int(x))) + 1024 for x in self.ns]
         self.out_off = np.zeros(self.nreads + 1, dtype=np.uint64)
         self.out_off[1:] = np.cumsum((np.asarray(caps, dtype=np.uint64) + 15) // 16 * 16)
@@ -1671,11 +1640,7 @@ def symbol_counts_host(reads, counts=None):
     `counts` when it is given."""
     lib = load_library()
     _train_api(lib)
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = np.zeros(total + 64, dtype=np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
+    sig, off, ns, total = _host_batch(reads)
     out = np.zeros(NBINS, dtype=np.uint64) if counts is None else np.ascontiguousarray(counts, dtype=np.uint64).copy()
     rc = lib.press_hip_symbol_counts(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total,
                                      out.ctypes.data, 0)

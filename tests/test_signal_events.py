@@ -604,6 +604,51 @@ def test_capacity(lib):
     assert np.array_equal(got[1], full[1])
 
 
+def many_reads():
+    """130 short walks at mixed lengths: more reads than the layout kernel has lanes, so its second round carries a sum"""
+    rng = np.random.default_rng(83)
+    ns = (300, 190, 257, 64, 311, 0, 129)
+    return [_walk(rng, ns[k % len(ns)]) for k in range(130)], ["many-%d" % k for k in range(130)]
+
+
+@gpu
+@pytest.mark.parametrize("nreads", [63, 64, 65, 130])
+def test_capacity_beyond_one_round_of_the_layout(lib, nreads):
+    """test_capacity around the 64 reads the layout kernel takes per round: ev_cap at the total, where exactly the first
+    round fits, one above that, one below the total and 0 - the same ev_first, UINT32_MAX on exactly the reads that do not
+    fit, the records below ev_cap, the canaries beyond it; for 130 reads the host form at a cap inside the second round"""
+    reads, keys = many_reads()
+    reads, keys = reads[:nreads], keys[:nreads]
+    cals = [CAL_B] * nreads
+    prm = PRESETS["dna"]
+    want = wants(keys, reads, cals, prm)
+    k = np.array([len(w) for w in want])
+    assert len(set(k.tolist())) > 1 and k[:64].any() and (nreads <= 64 or k[64:].any()), k
+    total = int(k.sum())
+    d = Dev(reads, cals, seed=17)
+    full = d.run(prm, cap=total)
+    check(full, want)
+    assert (full[2] != NOFIT).all() and int(full[1][nreads]) == total
+    caps = [total - 1, 0]
+    if nreads > 64:
+        caps += [int(full[1][64]), int(full[1][64]) + 1]
+    got = {}
+    for cap in caps:
+        got[cap] = d.run(prm, cap=cap, rows=total)
+        assert np.array_equal(got[cap][1], full[1])
+        check(got[cap], want, cap=cap)
+        fits = full[1][1:] <= cap
+        assert np.array_equal(got[cap][2] != NOFIT, fits) and not fits.all()
+    if nreads == 130:
+        cap = int(full[1][64]) + 1
+        ev, first, count = press.signal_events_host(reads, np.array(cals, dtype=F32), press.EventParams(*prm), ev_cap=cap)
+        assert np.array_equal(first, full[1]) and np.array_equal(count, got[cap][2]) and len(ev) == cap
+        fits = full[1][1:] <= cap
+        top = int(full[1][1:][fits].max())
+        ev = ev.view(np.uint32).reshape(-1, 4)
+        assert np.array_equal(ev[:top], full[0][:top]) and not ev[top:].any()  # the room of a read that did not fit: zeros
+
+
 @gpu
 def test_repeatable_and_independent_of_scratch(lib):
     import torch
