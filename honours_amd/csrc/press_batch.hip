@@ -761,6 +761,111 @@ extern "C" int press_hip_signal_adaptor(const int16_t *sig, const uint64_t *off,
 	return st.fetch_tables({ { pair, g.sg_out.p, (size_t) nreads * 8 }, { thr, g.sg_thr.p, (size_t) nreads * 8 } });
 }
 
+// ------------------------------------------------------------------ range statistics and sigtk's prefix of samples that are already there
+//
+// The kernels of press_ranges.hip: one launch for the statistics; the adaptor, the poly-A walk and (with stat) the
+// statistics of the two stretches for the prefix.
+
+static_assert(sizeof(press_hip_range_stat) == 12 && sizeof(press_hip_prefix) == 16, "the range and prefix structs");
+
+extern "C" int press_hip_signal_range_stats(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+					    uint64_t total_samples, const float *cal, const uint32_t *range,
+					    press_hip_range_stat *out, int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(NONE, NONE, nreads && (!sig || !off || !n || !out), nreads, device_resident ? sig : nullptr, "sig");
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_range_stats_plan(nreads, !device_resident, cal != nullptr, range != nullptr);
+	if ((rc = plan.reserve()))
+		return rc;
+	if (device_resident) {
+		launch_range_stats(sig, off, n, nreads, 0, cal, range, out, s);
+		return launch_status();
+	}
+	SamplesIn in = { sig, off, n };
+	Staged st(nreads, s);
+	if ((rc = st.samples_in(in, total_samples, in)))
+		return rc;
+	if (cal)
+		HIPCHK(hipMemcpyAsync(g.sg_cal.p, cal, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	if (range)
+		HIPCHK(hipMemcpyAsync(g.px_range.p, range, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	launch_range_stats(in.sig, in.off, in.n, nreads, 0, cal ? (const float *) g.sg_cal.p : nullptr,
+			   range ? (const uint32_t *) g.px_range.p : nullptr, g.px_stat.p, s);
+	if ((rc = launch_status()))
+		return rc;
+	return st.fetch_tables({ { out, g.px_stat.p, (size_t) nreads * 12 } });
+}
+
+extern "C" int press_hip_prefix_params_preset(int which, press_hip_prefix_params *prm)
+{
+	if (!prm)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	if (which != 0)
+		return set_error(PRESS_HIP_EARG, "preset %d: 0 the dRNA prefix", which);
+	prm->adaptor = { 0.5f, 1500, 2000, 200000, 2000 };         // JNNV2_RNA_ADAPTOR, jnn.h:74-80
+	prm->polya = { -1.0f, 50, 200, 250, 1.0f, 30, 0.0f, 0.0f }; // JNNV1_POLYA, jnn.h:52-61
+	prm->rna = 1;
+	prm->shift = 30.0f; // m_a+30+20, m_a+30-20 (cfunc.c:191)
+	prm->half = 20.0f;
+	return 0;
+}
+
+extern "C" int press_hip_signal_prefix(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				       uint64_t total_samples, const float *cal, const press_hip_prefix_params *prm,
+				       press_hip_prefix *out, press_hip_range_stat *stat, float *thr, int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(NONE, NONE, !prm || (nreads && (!sig || !off || !n || !cal || !out)), nreads, device_resident ? sig : nullptr, "sig");
+	if (rc)
+		return rc;
+	const press_hip_jnn_params &pa = prm->polya;
+	if (pa.window < 1 || pa.corrector < 0 || pa.error < 0 || pa.seg_dist < 0 || !std::isfinite(pa.stall_len))
+		return set_error(PRESS_HIP_EARG, "jnn parameters: window %d >= 1, corrector %d, error %d, seg_dist %d >= 0, a finite stall_len",
+				 pa.window, pa.corrector, pa.error, pa.seg_dist);
+	if (prm->adaptor.window < 1 || prm->adaptor.window > 8192)
+		return set_error(PRESS_HIP_EARG, "window = %d: 1 .. 8192 (the window sums stay below 2^24)", prm->adaptor.window);
+	if (stat && nreads > 0x7FFFFFFFu)
+		return set_error(PRESS_HIP_EARG, "nreads = %u with stat: at most 2^31 - 1 (two ranges per read)", nreads);
+	if ((rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const Seg2Params p2 = { prm->adaptor.std_scale, prm->adaptor.seg_dist, prm->adaptor.window, prm->adaptor.hi_thresh, prm->adaptor.lo_thresh };
+	const SegParams p = { pa.std_scale, pa.corrector, pa.seg_dist, pa.window, pa.stall_len, pa.error, pa.top, pa.bot };
+	const ScratchPlan plan = make_prefix_plan(nreads, !device_resident);
+	if ((rc = plan.reserve()))
+		return rc;
+	int32_t *pair = (int32_t *) g.px_pair.p;
+	uint32_t *range = (uint32_t *) g.px_range.p;
+	auto launch = [&](const SamplesIn &in, const float *c, void *o, void *st, float *t) {
+		launch_adaptor(in.sig, in.off, in.n, nreads, p2, pair, nullptr, s);
+		launch_prefix(in.sig, in.off, in.n, nreads, c, p, prm->rna, prm->shift, prm->half, pair, o, t, range, s);
+		if (st)
+			launch_range_stats(in.sig, in.off, in.n, 2 * nreads, 1, c, range, st, s);
+	};
+	if (device_resident) {
+		launch({ sig, off, n }, cal, out, stat, thr);
+		return launch_status();
+	}
+	SamplesIn in = { sig, off, n };
+	Staged st(nreads, s);
+	if ((rc = st.samples_in(in, total_samples, in)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(g.sg_cal.p, cal, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	launch(in, (const float *) g.sg_cal.p, g.px_out.p, stat ? g.px_stat.p : nullptr, thr ? (float *) g.sg_thr.p : nullptr);
+	if ((rc = launch_status()))
+		return rc;
+	return st.fetch_tables({ { out, g.px_out.p, (size_t) nreads * 16 },
+				 { stat, g.px_stat.p, (size_t) nreads * 24 },
+				 { thr, g.sg_thr.p, (size_t) nreads * 8 } });
+}
+
 // ------------------------------------------------------------------ recode: streams in, streams out
 //
 // The two halves run one after the other on the stream, inside one call and one lock: the decode of `src` into the

@@ -74,6 +74,7 @@ struct Ctx {
 	DevBuf vf_raw, vf_out; // verify / CRC-32: a word per read between the two kernels; host path: the staged crc or first_bad, and nbad
 	DevBuf ev_state, ev_cal, ev_first, ev_cnt, ev_out; // events: count and path per read; host path: the staged calibration, ev_first, ev_count, the records
 	DevBuf sg_state, sg_cal, sg_first, sg_cnt, sg_thr, sg_out; // jnn segments: count and thresholds per read; host path: the staged calibration, seg_first, seg_count, thr, the records (the adaptor: the pairs)
+	DevBuf px_pair, px_range, px_out, px_stat; // range statistics and prefix: the adaptor's pairs, the ranges (host path: the caller's); host path: the prefix records, the statistics (the calibration and thr: sg_cal, sg_thr)
 	DevBuf sl_seg, sl_rd, sl_poff, sl_pn, sl_pooff, sl_polen, sl_poutn, sl_psig, sl_parena, sl_stall; // stall methods: first segments, plans, the piece table (StallBufs), the pieces' samples and streams; host path: (start, len) per read
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
@@ -302,6 +303,12 @@ ScratchPlan make_events_plan(uint32_t nreads, bool host);
 ScratchPlan make_segments_plan(uint32_t nreads, bool host, bool with_cal);
 // press_hip_signal_adaptor: no scratch of its own; host pointers: the pairs and thr
 ScratchPlan make_adaptor_plan(uint32_t nreads, bool host);
+// press_hip_signal_range_stats: no scratch of its own; host pointers: the staged calibration (with_cal) and ranges
+// (with_range), the statistics
+ScratchPlan make_range_stats_plan(uint32_t nreads, bool host, bool with_cal, bool with_range);
+// press_hip_signal_prefix: 24 bytes per read, the adaptor's pairs and the two ranges; host pointers: the staged calibration,
+// the records, thr and the statistics
+ScratchPlan make_prefix_plan(uint32_t nreads, bool host);
 
 // press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
 ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);

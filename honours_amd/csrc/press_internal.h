@@ -433,6 +433,14 @@ void launch_adaptor(const int16_t *sig, const uint64_t *off, const uint32_t *n, 
 // ... and segs[0] alone, in one launch (the stall methods): first[r] = { start, end }, start = STALL_NOSEG: no segment
 void launch_segments_first(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const SegParams &p, void *state,
 			   void *first, hipStream_t s);
+// press_ranges.hip: mean, deviation and median (12 bytes) of range i of read i >> shift, a wave per range (include/press_hip.h,
+// press_hip_signal_range_stats); range NULL (whole reads), or 2 * nranges words; cal NULL: the raw domain.  launch_prefix,
+// behind launch_adaptor on the same stream (press_hip_signal_prefix): out 16 bytes per read, thr NULL or 2 * nreads, and
+// range: 4 words per read, the adaptor's range and the poly-A's for launch_range_stats with shift 1.  Timed as ring 1
+void launch_range_stats(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nranges, uint32_t shift, const float *cal,
+			const uint32_t *range, void *out, hipStream_t s);
+void launch_prefix(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const float *cal, const SegParams &polya,
+		   int32_t rna, float shift, float half, const int32_t *pair, void *out, float *thr, uint32_t *range, hipStream_t s);
 // press_stall.hip: the stall methods (include/press_hip.h, press_hip_stall_*).  A read becomes up to three PIECES - what
 // is left of it without the stall, the stall, and for dstall_fz the whole read - which the rccm_vbbe21_zd kernels press
 // and depress as the reads of a larger batch; piece k of read r is entry STALL_PIECES * r + k (depress: STALL_DPIECES)

@@ -284,6 +284,29 @@ ScratchPlan make_adaptor_plan(uint32_t nreads, bool host)
 	return p;
 }
 
+ScratchPlan make_range_stats_plan(uint32_t nreads, bool host, bool with_cal, bool with_range)
+{
+	ScratchPlan p{};
+	if (host) {
+		p.need(&Ctx::px_stat, (size_t) nreads * 12);
+		if (with_cal)
+			p.need(&Ctx::sg_cal, (size_t) nreads * 8);
+		if (with_range)
+			p.need(&Ctx::px_range, (size_t) nreads * 8);
+	}
+	return p;
+}
+
+ScratchPlan make_prefix_plan(uint32_t nreads, bool host)
+{
+	ScratchPlan p{};
+	p.need(&Ctx::px_pair, (size_t) nreads * 8).need(&Ctx::px_range, (size_t) nreads * 16);
+	if (host)
+		p.need(&Ctx::sg_cal, (size_t) nreads * 8).need(&Ctx::px_out, (size_t) nreads * 16).need(&Ctx::sg_thr, (size_t) nreads * 8)
+			.need(&Ctx::px_stat, (size_t) nreads * 24);
+	return p;
+}
+
 // Fused pairs: BLOW5's and the reference's svb-zd streams into any exception-split method.  (svb12 has no deltas; the zstd
 // kinds and the svb destinations take the general path.)
 bool recode_fused(int src, int dst)
@@ -491,6 +514,13 @@ extern "C" uint64_t press_hip_signal_segments_workspace_bytes(uint64_t total_sam
 {
 	(void) total_samples;
 	return plan_bytes(make_segments_plan(nreads, false, false), false);
+}
+
+// what the device-resident press_hip_signal_prefix keeps: 24 bytes per read (the adaptor's pairs, the two ranges), nothing
+// per sample (press_hip_signal_range_stats keeps nothing)
+extern "C" uint64_t press_hip_signal_prefix_workspace_bytes(uint32_t nreads)
+{
+	return plan_bytes(make_prefix_plan(nreads, false), false);
 }
 
 // The stall methods' bound is rccm_vbbe21_zd's (press.c:7723, 7893, 7981)

@@ -102,6 +102,8 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_events_serial_reads",
      "press_hip_jnn_params_preset", "press_hip_jnn2_params_preset", "press_hip_signal_segments",
      "press_hip_signal_segments_workspace_bytes", "press_hip_signal_adaptor",
+     "press_hip_signal_range_stats", "press_hip_prefix_params_preset", "press_hip_signal_prefix",
+     "press_hip_signal_prefix_workspace_bytes",
      "press_hip_stall_bound", "press_hip_stall_press_batch", "press_hip_stall_depress_batch",
      "press_hip_stall_workspace_bytes"] +
     [m + s for m in STALL_METHODS for s in ("_bound_16", "_press_16", "_depress_16")]))
@@ -177,6 +179,18 @@ def load_library(path=LIB_PATH):
         _lib.press_hip_signal_adaptor.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_int]
+        _lib.press_hip_signal_range_stats.restype = ctypes.c_int
+        _lib.press_hip_signal_range_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_int]
+        _lib.press_hip_prefix_params_preset.restype = ctypes.c_int
+        _lib.press_hip_prefix_params_preset.argtypes = [ctypes.c_int, ctypes.c_void_p]
+        _lib.press_hip_signal_prefix.restype = ctypes.c_int
+        _lib.press_hip_signal_prefix.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_signal_prefix_workspace_bytes.restype = ctypes.c_uint64
+        _lib.press_hip_signal_prefix_workspace_bytes.argtypes = [ctypes.c_uint32]
         _lib.press_hip_stall_bound.restype = ctypes.c_uint64
         _lib.press_hip_stall_bound.argtypes = [ctypes.c_int, ctypes.c_uint32]
         _lib.press_hip_stall_workspace_bytes.restype = ctypes.c_uint64
@@ -1295,6 +1309,128 @@ def signal_adaptor_host(reads, prm=None, want_thr=True):
                                                thr.ctypes.data if want_thr else None, 0):
         raise PressError(last_error())
     return pair, thr
+
+
+# ---------------------------------------------------------------------------- range statistics and sigtk's stat and prefix
+
+class PrefixParams(ctypes.Structure):
+    """press_hip_prefix_params: the adaptor finder's and the poly-A walk's parameters, rna, and the thresholds
+    m_a + shift +- half"""
+    _fields_ = [("adaptor", Jnn2Params), ("polya", JnnParams), ("rna", ctypes.c_int32), ("shift", ctypes.c_float),
+                ("half", ctypes.c_float)]
+
+
+RANGE_STAT_DTYPE = np.dtype([("mean", "<f4"), ("stdv", "<f4"), ("median", "<f4")])  # press_hip_range_stat
+PREFIX_DTYPE = np.dtype([("adapt_start", "<i4"), ("adapt_end", "<i4"), ("polya_start", "<i4"), ("polya_end", "<i4")])  # press_hip_prefix
+
+
+def prefix_params():
+    """sigtk prefix's parameters (press_hip_prefix_params_preset): JNNV2_RNA_ADAPTOR, JNNV1_POLYA, rna 1, 30, 20"""
+    p = PrefixParams()
+    if load_library().press_hip_prefix_params_preset(0, ctypes.addressof(p)):
+        raise PressError(last_error())
+    return p
+
+
+def _f32_rows(t, rows, words, name):
+    if t.numel() < rows * words or t.element_size() != 4 or not t.is_contiguous():
+        raise PressError("%s must be a contiguous 32-bit tensor of %d words per record" % (name, words))
+
+
+def range_stats(sig, off, n, cal, rng, out):
+    """Enqueue the mean, deviation and median of a sample range of every read (CUDA tensors as in signal_segments; cal
+    float32 of 2 * nreads or None for the raw domain; rng None for whole reads, or 32-bit of 2 * nreads: a, b in samples from
+    the read's start, clamped, at any offset; out float32 of [nreads, 3], WRITTEN: mean, stdv, median)
+    (press_hip_signal_range_stats)."""
+    nreads = off.numel()
+    if cal is not None:
+        _f32_pairs(cal, nreads, "cal")
+    if rng is not None:
+        _f32_pairs(rng, nreads, "range")
+    _f32_rows(out, nreads, 3, "out")
+    if load_library().press_hip_signal_range_stats(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
+                                                   cal.data_ptr() if cal is not None else None,
+                                                   rng.data_ptr() if rng is not None else None, out.data_ptr(), 1):
+        raise PressError(last_error())
+
+
+def _host_cal(cal, nreads):
+    cal = np.ascontiguousarray(cal, dtype=np.float32).reshape(-1)
+    if cal.size != 2 * nreads:
+        raise PressError("cal: two floats per read")
+    return cal
+
+
+def range_stats_host(reads, cal=None, rng=None):
+    """Range statistics of a list of int16 arrays (host buffers, synchronous); cal None (raw domain) or (nreads, 2) float32,
+    rng None (whole reads) or (nreads, 2) unsigned: a, b -> a RANGE_STAT_DTYPE array of nreads records"""
+    sig, off, ns, total = _host_batch(reads)
+    if cal is not None:
+        cal = _host_cal(cal, len(reads))
+    if rng is not None:
+        rng = np.ascontiguousarray(rng, dtype=np.uint32).reshape(-1)
+        if rng.size != 2 * len(reads):
+            raise PressError("rng: two positions per read")
+    out = np.zeros(len(reads), dtype=RANGE_STAT_DTYPE)
+    if load_library().press_hip_signal_range_stats(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total,
+                                                   cal.ctypes.data if cal is not None else None,
+                                                   rng.ctypes.data if rng is not None else None, out.ctypes.data, 0):
+        raise PressError(last_error())
+    return out
+
+
+def signal_prefix(sig, off, n, cal, prm, out, stat=None, thr=None):
+    """Enqueue sigtk's prefix over a batch of samples (CUDA tensors as in signal_segments; cal float32 of 2 * nreads,
+    required; prm a PrefixParams; out int32 of [nreads, 4], WRITTEN: adapt_start, adapt_end, polya_start, polya_end; stat
+    None or float32 of [2 * nreads, 3]: mean, stdv, median of the adaptor, then of the poly-A tail, in picoamperes; thr None
+    or float32 of 2 * nreads: bot, top of the poly-A walk) (press_hip_signal_prefix)."""
+    nreads = off.numel()
+    _f32_pairs(cal, nreads, "cal")
+    _f32_rows(out, nreads, 4, "out")
+    if stat is not None:
+        _f32_rows(stat, 2 * nreads, 3, "stat")
+    if thr is not None:
+        _f32_pairs(thr, nreads, "thr")
+    if load_library().press_hip_signal_prefix(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(), cal.data_ptr(),
+                                              ctypes.addressof(prm), out.data_ptr(),
+                                              stat.data_ptr() if stat is not None else None,
+                                              thr.data_ptr() if thr is not None else None, 1):
+        raise PressError(last_error())
+
+
+def signal_prefix_host(reads, cal, prm=None, want_stat=True, want_thr=True):
+    """sigtk's prefix over a list of int16 arrays (host buffers, synchronous); cal (nreads, 2) float32; prm a PrefixParams
+    (default: the preset) -> (out PREFIX_DTYPE of nreads, stat RANGE_STAT_DTYPE (nreads, 2): adaptor, poly-A - or None
+    without want_stat, thr float32 (nreads, 2): bot, top - or None without want_thr)"""
+    prm = prefix_params() if prm is None else prm
+    sig, off, ns, total = _host_batch(reads)
+    cal = _host_cal(cal, len(reads))
+    out = np.zeros(len(reads), dtype=PREFIX_DTYPE)
+    stat = np.zeros((len(reads), 2), dtype=RANGE_STAT_DTYPE) if want_stat else None
+    thr = np.zeros((len(reads), 2), dtype=np.float32) if want_thr else None
+    if load_library().press_hip_signal_prefix(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, cal.ctypes.data,
+                                              ctypes.addressof(prm), out.ctypes.data, stat.ctypes.data if want_stat else None,
+                                              thr.ctypes.data if want_thr else None, 0):
+        raise PressError(last_error())
+    return out, stat, thr
+
+
+def signal_prefix_workspace_bytes(nreads):
+    return int(load_library().press_hip_signal_prefix_workspace_bytes(int(nreads)))
+
+
+def signal_stat_table(sig, off, n, cal):
+    """sigtk stat's six columns per read as a float32 CUDA tensor of [nreads, 6]: raw_mean, pa_mean, raw_std, pa_std,
+    raw_median, pa_median (CUDA tensors as in range_stats; cal float32 of 2 * nreads).  Two range_stats calls over whole
+    reads; only enqueues."""
+    import torch
+
+    nreads = off.numel()
+    raw = torch.empty((nreads, 3), dtype=torch.float32, device=sig.device)
+    pa = torch.empty((nreads, 3), dtype=torch.float32, device=sig.device)
+    range_stats(sig, off, n, None, None, raw)
+    range_stats(sig, off, n, cal, None, pa)
+    return torch.stack((raw, pa), dim=2).reshape(nreads, 6)
 
 
 # ---------------------------------------------------------------------------- verifying: CRC-32 and compare-after-decode

@@ -882,6 +882,82 @@ int press_hip_signal_adaptor(const int16_t *sig, const uint64_t *off, const uint
 			     int device_resident);
 
 /*
+ * Range statistics and the prefix of a dRNA read: sigtk's `stat` and `prefix` subcommands on the device, bit for bit
+ * (sigtk/src/cfunc.c:126-234, stat.h:17-73, misc.c:15-32).
+ *
+ * press_hip_signal_range_stats: the mean, the deviation and the median of the samples [a, b) of every read, L = b - a of
+ * them.  Every operation is rounded on its own in single precision, never fused:
+ *   x[i]     cal == NULL, the raw domain (meani16 / stdvi16): (float) s[i], no clamp.  Otherwise picoamperes as
+ *            signal_in_picoamps has them: ((float) s[i] + cal[2r]) * cal[2r + 1], no clamp (this is NOT the segmenter's
+ *            rm_outlierf)
+ *   mean     S / (float) L, S the float sum of x from the range's first sample on, added in that order
+ *   stdv     sqrtf(Q / (float) L), Q the float sum in that order of (x[i] - mean) * (x[i] - mean), the difference and the
+ *            product each rounded
+ *   median   the L / 2-th smallest (0-based) of x, the reference's ks_ksmall(L, copy, L / 2), found as a selection among
+ *            the 16-bit keys s + 32768, never among floats: in the raw domain (float) of the selected sample; with cal
+ *            and cal[2r + 1] < 0, x of the L / 2-th LARGEST sample, else x of the L / 2-th smallest.  x is monotone in s
+ *            for every finite calibration, so this is medianf's value there; for a NaN calibration this formula is the
+ *            definition
+ *   L == 0   mean and stdv are NaN (what 0 / 0 gives), median is 0; the reference has no value there
+ *   range    NULL: the whole read, [0, n[r]).  Otherwise 2 * nreads words a, b in samples from the read's start: b is
+ *            clamped to n[r] and a to b.  NO alignment is asked of off[r] + a, and loads stay inside
+ *            [off[r] + a, off[r] + b)
+ *   cal      NULL, or 2 * nreads floats, press_hip_pa_cal's; not validated: NaN and inf propagate, nothing faults
+ *   sig / off / n / total_samples / device_resident   as press_hip_signal_segments, with its checks and its two forms:
+ *            host pointers go through the staging layer and the call is synchronous; device resident, the call only
+ *            enqueues on the current stream and never waits
+ *   out      nreads records
+ * A NULL argument other than cal and range is PRESS_HIP_EARG before any device call; nreads == 0 is PRESS_HIP_OK.
+ * sigtk's `stat` is this call on whole reads, once with cal == NULL and once with it.
+ * One wave takes one range, in two passes over its samples (the sum and the keys' high bytes, the squares and the low
+ * bytes); the counting is on integers in LDS, so the result is the same from run to run, and nothing is kept per sample.
+ * The call's time is that of its longest range, as the segments' and the events' is that of the longest read.
+ *
+ * press_hip_signal_prefix is prefix_func (cfunc.c:169-234): where the adaptor ends and where the poly-A tail lies.
+ *   adapt_start, adapt_end   press_hip_signal_adaptor's pair under prm->adaptor, unchanged: (-1, -1) for n <= window,
+ *            (0, 0) if none was found
+ *   only if adapt_end > 0 and prm->rna:  m_a = the range mean above (picoamperes) of [adapt_start, adapt_end),
+ *            t = m_a + shift, top = t + half, bot = t - half: three float operations, as C evaluates m_a+30+20.  The
+ *            poly-A pair is the FIRST record of press_hip_signal_segments' definition (jnn_pa: clamped picoamperes) over
+ *            the suffix [adapt_end, n) under prm->polya with these thresholds whatever its std_scale says, reported as
+ *            positions in the read: start + adapt_end, end + adapt_end
+ *   in every other case (no adaptor, rna == 0, no segment, a NaN m_a)   polya_start = polya_end = -1
+ *   stat     NULL, or 2 * nreads records, the adaptor's then the poly-A's: the range statistics (picoamperes) of
+ *            [adapt_start, adapt_end) and [polya_start, polya_end); a stretch that is absent is an empty range (NaN, NaN,
+ *            0).  (A start below 0, which only an adaptor window of 1 can give, is beyond every end: an empty range.)
+ *   thr      NULL, or 2 * nreads floats: bot, top as the walk used them (NaN for a NaN m_a); 0, 0 where no walk ran
+ *   cal      required
+ *   prm      press_hip_prefix_params_preset(0, &prm): JNNV2_RNA_ADAPTOR, JNNV1_POLYA, rna 1, shift 30, half 20.  The
+ *            parameter checks of press_hip_signal_adaptor (on adaptor) and press_hip_signal_segments (on polya) apply,
+ *            before any device call; with stat, nreads is at most 2^31 - 1
+ * A NULL argument other than stat and thr is PRESS_HIP_EARG; nreads == 0 is PRESS_HIP_OK.  The two forms are those above.
+ * Three launches: the adaptor kernel; a wave per read that adds m_a and walks the suffix for its first record; with stat,
+ * the range kernel over 2 * nreads ranges.  The call's time is that of the batch's longest read.
+ * press_hip_signal_prefix_workspace_bytes: the device scratch the device-resident call keeps, 24 bytes per read (the
+ * adaptor's pairs, the two ranges) and 0 per sample; exact, 0 for an empty batch.  The range call keeps none.
+ */
+typedef struct {
+	float mean, stdv, median;
+} press_hip_range_stat; /* 12 bytes */
+typedef struct {
+	press_hip_jnn2_params adaptor;
+	press_hip_jnn_params polya;
+	int32_t rna;
+	float shift, half;
+} press_hip_prefix_params;
+typedef struct {
+	int32_t adapt_start, adapt_end, polya_start, polya_end;
+} press_hip_prefix; /* 16 bytes */
+int press_hip_signal_range_stats(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				 uint64_t total_samples, const float *cal, const uint32_t *range,
+				 press_hip_range_stat *out, int device_resident);
+int press_hip_prefix_params_preset(int which, press_hip_prefix_params *prm);
+int press_hip_signal_prefix(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			    uint64_t total_samples, const float *cal, const press_hip_prefix_params *prm,
+			    press_hip_prefix *out, press_hip_range_stat *stat, float *thr, int device_resident);
+uint64_t press_hip_signal_prefix_workspace_bytes(uint32_t nreads);
+
+/*
  * Lossy archives: dropping the low b bits of every sample, on the device.
  *
  * The definition.  For bits = b in 0 .. 8 and a sample s (int16), computed in 32-bit integers:
