@@ -272,6 +272,66 @@ extern "C" int press_hip_symbol_counts(const int16_t *sig, const uint64_t *off, 
 	return st.fetch_tables({ { counts, sum, 257 * 8 } });
 }
 
+// ------------------------------------------------------------------ dataset analysis: tallies and moments
+
+extern "C" int press_hip_signal_tally(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				      uint64_t total_samples, uint64_t *raw, uint64_t *delta, uint64_t *trans,
+				      press_hip_moments *mom, int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(NONE, NONE, nreads && (!sig || !off || !n), nreads, device_resident ? sig : nullptr, "sig");
+	if (rc)
+		return rc;
+	if (!device_resident && nreads && (rc = check_layout(off, n, nreads, total_samples)))
+		return rc;
+	if (nreads == 0 || (!raw && !delta && !trans && !mom))
+		return 0;
+	if ((rc = device_ready(NONE, NONE)))
+		return rc;
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_tally_plan(total_samples, nreads, !device_resident);
+	uint32_t mc = plan.max_chunks;
+	if (!device_resident) { // the host form knows the number of chunks: reads that overlap may need more than the plan's
+		uint64_t nch = 0;
+		for (uint32_t r = 0; r < nreads; r++)
+			nch += n[r] / CHUNK + (n[r] % CHUNK != 0);
+		if (nch > 0xFFFFFFFFull)
+			return set_error(PRESS_HIP_EARG, "%llu chunks of samples: at most 2^32 - 1", (unsigned long long) nch);
+		mc = std::max(mc, (uint32_t) nch);
+	}
+	if ((rc = plan.reserve()) || g.tl_chunks.reserve(tally_scratch_bytes(mc)))
+		return rc ? rc : PRESS_HIP_EHIP;
+	int cus = 0;
+	HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g.device));
+	const uint32_t ncu = (uint32_t) std::max(cus, 1);
+	uint32_t *nchunks = (uint32_t *) g.tl_ctl.p;
+	if (device_resident) {
+		launch_signal_tally(sig, off, n, nreads, raw, delta, trans, mom, g.tl_chunks.p, nchunks, mc, ncu, s);
+		return launch_status();
+	}
+	// host pointers: stage the samples and the caller's tables, run, copy the tables and the moments back, synchronise
+	uint64_t *const d_raw = (uint64_t *) g.tl_tab.p, *const d_delta = d_raw + PRESS_HIP_TALLY_BINS, *const d_trans = d_delta + PRESS_HIP_TALLY_BINS;
+	const size_t bins = (size_t) PRESS_HIP_TALLY_BINS * 8, cells = (size_t) PRESS_HIP_TALLY_SYMS * PRESS_HIP_TALLY_SYMS * 8;
+	SamplesIn in = { sig, off, n };
+	Staged st(nreads, s);
+	if ((rc = st.layout(off, n, total_samples, nullptr, true)))
+		return rc;
+	if (raw)
+		HIPCHK(hipMemcpyAsync(d_raw, raw, bins, hipMemcpyHostToDevice, s));
+	if (delta)
+		HIPCHK(hipMemcpyAsync(d_delta, delta, bins, hipMemcpyHostToDevice, s));
+	if (trans)
+		HIPCHK(hipMemcpyAsync(d_trans, trans, cells, hipMemcpyHostToDevice, s));
+	if ((rc = st.samples(in, total_samples, in)))
+		return rc;
+	launch_signal_tally(in.sig, in.off, in.n, nreads, raw ? d_raw : nullptr, delta ? d_delta : nullptr, trans ? d_trans : nullptr,
+			    mom ? g.tl_mom.p : nullptr, g.tl_chunks.p, nchunks, mc, ncu, s);
+	if ((rc = launch_status()))
+		return rc;
+	return st.fetch_tables({ { raw, d_raw, bins }, { delta, d_delta, bins }, { trans, d_trans, cells },
+				 { mom, g.tl_mom.p, (size_t) nreads * sizeof(press_hip_moments) } });
+}
+
 // ------------------------------------------------------------------ depress: samples, picoamperes, normalised floats, chunk rows
 
 extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint64_t *in_off,

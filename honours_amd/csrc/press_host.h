@@ -76,6 +76,7 @@ struct Ctx {
 	DevBuf sg_state, sg_cal, sg_first, sg_cnt, sg_thr, sg_out; // jnn segments: count and thresholds per read; host path: the staged calibration, seg_first, seg_count, thr, the records (the adaptor: the pairs)
 	DevBuf px_pair, px_range, px_out, px_stat; // range statistics and prefix: the adaptor's pairs, the ranges (host path: the caller's); host path: the prefix records, the statistics (the calibration and thr: sg_cal, sg_thr)
 	DevBuf sl_seg, sl_rd, sl_poff, sl_pn, sl_pooff, sl_polen, sl_poutn, sl_psig, sl_parena, sl_stall; // stall methods: first segments, plans, the piece table (StallBufs), the pieces' samples and streams; host path: (start, len) per read
+	DevBuf tl_chunks, tl_ctl, tl_tab, tl_mom; // dataset tallies: the chunk list and its count; host path: the three tables in a row, the moments
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams
@@ -309,6 +310,9 @@ ScratchPlan make_range_stats_plan(uint32_t nreads, bool host, bool with_cal, boo
 // press_hip_signal_prefix: 24 bytes per read, the adaptor's pairs and the two ranges; host pointers: the staged calibration,
 // the records, thr and the statistics
 ScratchPlan make_prefix_plan(uint32_t nreads, bool host);
+
+// press_hip_signal_tally: the chunk list (max_chunks entries of 8 bytes) and its count; host pointers: the tables, the moments
+ScratchPlan make_tally_plan(uint64_t total_samples, uint32_t nreads, bool host);
 
 // press_hip_press_sizes / press_hip_press_packed: the press plan of the method and the two per-read tables of PackArgs
 ScratchPlan make_packed_plan(int method, uint64_t total_samples, uint32_t nreads);

@@ -493,6 +493,13 @@ uint64_t train_scratch_bytes(uint32_t max_chunks);
 void launch_symbol_counts(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, uint64_t *counts,
 			  void *chunks, uint32_t *nchunks, uint32_t max_chunks, uint32_t grid, hipStream_t s);
 
+// dataset analysis (press_tally.hip): adds into raw[65536], delta[65536], trans[257 * 257] and sets mom[nreads]; any of the four may
+// be NULL.  chunks takes tally_scratch_bytes(max_chunks), nchunks is one device word (zeroed here), cus is the device's
+// number of compute units: the launch sizes its persistent grid from it
+uint64_t tally_scratch_bytes(uint32_t max_chunks);
+void launch_signal_tally(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, uint64_t *raw, uint64_t *delta,
+			 uint64_t *trans, void *mom, void *chunks, uint32_t *nchunks, uint32_t max_chunks, uint32_t cus, hipStream_t s);
+
 // sets press_hip_last_error() (press_ctx.hip) and returns code
 int set_error(int code, const char *fmt, ...);
 

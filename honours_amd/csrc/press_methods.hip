@@ -307,6 +307,19 @@ ScratchPlan make_prefix_plan(uint32_t nreads, bool host)
 	return p;
 }
 
+// Tallies: 8 bytes per chunk of the work list, nothing per sample
+ScratchPlan make_tally_plan(uint64_t total_samples, uint32_t nreads, bool host)
+{
+	ScratchPlan p{};
+	if (nreads == 0)
+		return p;
+	p.max_chunks = plan_max_chunks(total_samples, nreads);
+	p.need(&Ctx::tl_chunks, tally_scratch_bytes(p.max_chunks)).need(&Ctx::tl_ctl, 64);
+	if (host)
+		p.need(&Ctx::tl_tab, (size_t) PRESS_HIP_TALLY_WORDS * 8).need(&Ctx::tl_mom, (size_t) nreads * sizeof(press_hip_moments));
+	return p;
+}
+
 // Fused pairs: BLOW5's and the reference's svb-zd streams into any exception-split method.  (svb12 has no deltas; the zstd
 // kinds and the svb destinations take the general path.)
 bool recode_fused(int src, int dst)
@@ -521,6 +534,12 @@ extern "C" uint64_t press_hip_signal_segments_workspace_bytes(uint64_t total_sam
 extern "C" uint64_t press_hip_signal_prefix_workspace_bytes(uint32_t nreads)
 {
 	return plan_bytes(make_prefix_plan(nreads, false), false);
+}
+
+// what the device-resident press_hip_signal_tally keeps: the chunk list and its count
+extern "C" uint64_t press_hip_signal_tally_workspace_bytes(uint64_t total_samples, uint32_t nreads)
+{
+	return plan_bytes(make_tally_plan(total_samples, nreads, false), false);
 }
 
 // The stall methods' bound is rccm_vbbe21_zd's (press.c:7723, 7893, 7981)

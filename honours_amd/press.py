@@ -104,6 +104,7 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_signal_segments_workspace_bytes", "press_hip_signal_adaptor",
      "press_hip_signal_range_stats", "press_hip_prefix_params_preset", "press_hip_signal_prefix",
      "press_hip_signal_prefix_workspace_bytes",
+     "press_hip_signal_tally", "press_hip_signal_tally_workspace_bytes",
      "press_hip_stall_bound", "press_hip_stall_press_batch", "press_hip_stall_depress_batch",
      "press_hip_stall_workspace_bytes"] +
     [m + s for m in STALL_METHODS for s in ("_bound_16", "_press_16", "_depress_16")]))
@@ -1878,6 +1879,294 @@ def train_table(src, path, max_bits=24, degrade_bits=0):
     ln, bits = table_from_counts(counts, max_bits)
     write_table(path, ln, bits, int(counts[:256].sum()))
     return counts
+
+
+# ---------------------------------------------------------------------------- dataset analysis: tallies and moments
+
+TALLY_BINS = 65536   # counters of raw and of delta, indexed by zz(v) = (v << 1) ^ (v >> 15) as uint16
+TALLY_SYMS = NBINS   # trans is TALLY_SYMS x TALLY_SYMS: the 256 one-byte symbols, then the exceptions as one class
+# include/press_hip.h press_hip_moments
+MOMENTS_DTYPE = np.dtype([("sum", "<i8"), ("sumsq", "<u8"), ("min", "<i4"), ("max", "<i4"), ("n", "<u4"), ("nex", "<u4")])
+TALLY_OUTPUTS = ("raw", "delta", "trans", "mom")
+
+
+def _tally_api(lib):
+    lib.press_hip_signal_tally.restype = ctypes.c_int
+    lib.press_hip_signal_tally.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    lib.press_hip_signal_tally_workspace_bytes.restype = ctypes.c_uint64
+    lib.press_hip_signal_tally_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+
+
+def signal_tally_workspace_bytes(total_samples, nreads):
+    lib = load_library()
+    _tally_api(lib)
+    return int(lib.press_hip_signal_tally_workspace_bytes(int(total_samples), int(nreads)))
+
+
+def signal_tally(sig, off, n, raw=None, delta=None, trans=None, mom=None):
+    """Enqueue press_hip_signal_tally on the device (CUDA tensors: sig int16, off int64 read starts in multiples of 8
+    samples, n int32 sample counts).  raw and delta (64-bit, TALLY_BINS entries) and trans (64-bit, TALLY_SYMS squared)
+    are ADDED to; mom (32 bytes per read: a contiguous tensor of nreads * 4 64-bit or nreads * 8 32-bit words, read with
+    MOMENTS_DTYPE) is set.  Any may be None."""
+    lib = load_library()
+    _tally_api(lib)
+    nreads = off.numel()
+    for name, t, words in (("raw", raw, TALLY_BINS), ("delta", delta, TALLY_BINS), ("trans", trans, TALLY_SYMS * TALLY_SYMS)):
+        if t is not None and (t.numel() != words or t.element_size() != 8 or not t.is_contiguous()):
+            raise PressError("%s must be a contiguous 64-bit tensor of %d entries" % (name, words))
+    if mom is not None and (mom.numel() * mom.element_size() != 32 * nreads or not mom.is_contiguous()):
+        raise PressError("mom must be a contiguous tensor of 32 bytes per read")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    rc = lib.press_hip_signal_tally(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(), ptr(raw), ptr(delta),
+                                    ptr(trans), ptr(mom), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def signal_tally_host(reads, want=TALLY_OUTPUTS, into=None):
+    """Tallies of a list of int16 arrays (host buffers, synchronous) -> dict with the members of `want`: raw, delta
+    (numpy uint64[TALLY_BINS]), trans (uint64[TALLY_SYMS, TALLY_SYMS]), mom (MOMENTS_DTYPE[nreads]).  into: a dict of
+    tables the counts are added to (copies are returned)."""
+    lib = load_library()
+    _tally_api(lib)
+    sig, off, ns, total = _host_batch(reads)
+    shapes = {"raw": (TALLY_BINS,), "delta": (TALLY_BINS,), "trans": (TALLY_SYMS, TALLY_SYMS)}
+    out = {}
+    for k in want:
+        if k == "mom":
+            out[k] = np.zeros(len(reads), dtype=MOMENTS_DTYPE)
+        elif into is not None and k in into:
+            out[k] = np.ascontiguousarray(into[k], dtype=np.uint64).reshape(shapes[k]).copy()
+        else:
+            out[k] = np.zeros(shapes[k], dtype=np.uint64)
+    ptr = lambda k: out[k].ctypes.data if k in out else None
+    rc = lib.press_hip_signal_tally(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, ptr("raw"),
+                                    ptr("delta"), ptr("trans"), ptr("mom"), 0)
+    if rc:
+        raise PressError(last_error())
+    return out
+
+
+def tally_value(index):
+    """the int16 value of a counter index of raw / delta: the inverse of zz"""
+    index = np.asarray(index, dtype=np.int64)
+    return (index >> 1) ^ -(index & 1)
+
+
+def tally_table(counts):
+    """raw or delta counters -> (values ascending, counts) with the zero rows dropped: the rows printtally prints"""
+    c = np.asarray(counts, dtype=np.uint64).reshape(-1)
+    values = tally_value(np.arange(c.size))
+    order = np.argsort(values, kind="stable")
+    values, c = values[order], c[order]
+    keep = c != 0
+    return values[keep], c[keep]
+
+
+def tally_text(counts):
+    """the text viz/freq_slow5 and viz/freq_delta_slow5 print for these counters (tally.c printtally)"""
+    v, c = tally_table(counts)
+    return "signal\tfreq\n" + "".join("%d\t%d\n" % (int(a), int(b)) for a, b in zip(v, c))
+
+
+def _entropy_bits(counts, total):
+    """- sum p log2 p of integer counts with sum `total`, term by term (no cancellation: a peaked table keeps its digits);
+    for p above one half, log2 p = log1p(-(total - c) / total) / ln 2"""
+    import math
+
+    def term(c):
+        if 2 * c > total:
+            return -(c / total) * math.log1p(-((total - c) / total)) / math.log(2.0)
+        return -(c / total) * (math.log2(c) - math.log2(total))
+    return math.fsum(term(c) for c in counts if c) if total else 0.0
+
+
+def tally_summary(counts):
+    """The eleven numbers of viz/freq_analyse.R over a raw or delta table -> dict of n, min, q1, mean, median, q3, max, mode,
+    var (population), std, entropy (bits per value).  Integers and fractions, rounded once to float; a quantile is the
+    first value in ascending order whose cumulative count reaches n * q; the mode is the smallest value among ties.  An
+    empty table: n = 0 and None for the rest."""
+    from fractions import Fraction
+    v, c = tally_table(counts)
+    v, c = [int(x) for x in v], [int(x) for x in c]
+    n = sum(c)
+    if n == 0:
+        return dict(n=0, min=None, q1=None, mean=None, median=None, q3=None, max=None, mode=None, var=None, std=None, entropy=None)
+
+    def quantile(num, den):
+        cum = 0
+        for val, cnt in zip(v, c):
+            cum += cnt
+            if cum * den >= n * num:
+                return val
+        return v[-1]
+
+    s1 = sum(a * b for a, b in zip(v, c))
+    s2 = sum(a * a * b for a, b in zip(v, c))
+    var = Fraction(n * s2 - s1 * s1, n * n)
+    top = max(c)
+    return dict(n=n, min=v[0], q1=quantile(1, 4), mean=float(Fraction(s1, n)), median=quantile(1, 2), q3=quantile(3, 4),
+                max=v[-1], mode=v[c.index(top)], var=float(var), std=_sqrt_fraction(var), entropy=_entropy_bits(c, n))
+
+
+def _sqrt_fraction(q):
+    """sqrt of a non-negative Fraction p / q as a float: isqrt(p q 4^64) / (q 2^64), an integer root of at least 64 bits
+    (relative error below 2^-63), rounded once"""
+    import math
+    from fractions import Fraction
+    if q <= 0:
+        return 0.0
+    return float(Fraction(math.isqrt((q.numerator * q.denominator) << 128), q.denominator << 64))
+
+
+def transition_entropy(trans):
+    """(H0, H1) in bits of a transition table: H0 the order-0 entropy of the symbol the transitions arrive at (column
+    sums), H1 = H(sym[i] | sym[i-1]) = H(pairs) - H(row sums).  (0, 0) for an empty table."""
+    t = np.asarray(trans, dtype=np.uint64).reshape(TALLY_SYMS, TALLY_SYMS)
+    cells = [int(x) for x in t.reshape(-1) if x]
+    n = sum(cells)
+    if n == 0:
+        return 0.0, 0.0
+    rows = [int(x) for x in t.sum(axis=1, dtype=object)]
+    cols = [int(x) for x in t.sum(axis=0, dtype=object)]
+    return _entropy_bits(cols, n), max(0.0, _entropy_bits(cells, n) - _entropy_bits(rows, n))
+
+
+def moments_stats(mom, dor=None):
+    """Per read, from the exact integers of MOMENTS_DTYPE records -> dict of float64 arrays mean, var (population) and sd
+    (NaN for an empty read): var = (n * sumsq - sum^2) / n^2 as a rational, rounded once.  dor: [nreads, 3] digitisation,
+    offset, range -> also min_pa, max_pa, mean_pa = (x + offset) * (range / dig), var_pa = var * (range / dig)^2 and sd_pa
+    (viz/stats.c)."""
+    import math
+    from fractions import Fraction
+    mom = np.asarray(mom, dtype=MOMENTS_DTYPE).reshape(-1)
+    out = {k: np.full(mom.size, np.nan) for k in ("mean", "var", "sd")}
+    for r, m in enumerate(mom):
+        n, s1, s2 = int(m["n"]), int(m["sum"]), int(m["sumsq"])
+        if n == 0:
+            continue
+        var = Fraction(n * s2 - s1 * s1, n * n)
+        out["mean"][r] = float(Fraction(s1, n))
+        out["var"][r] = float(var)
+        out["sd"][r] = _sqrt_fraction(var)
+    if dor is not None:
+        dor = np.asarray(dor, dtype=np.float64).reshape(-1, 3)
+        with np.errstate(all="ignore"):
+            scale = dor[:, 2] / dor[:, 0]
+            out["min_pa"] = (mom["min"] + dor[:, 1]) * scale
+            out["max_pa"] = (mom["max"] + dor[:, 1]) * scale
+            out["mean_pa"] = (out["mean"] + dor[:, 1]) * scale
+            out["var_pa"] = out["var"] * scale ** 2
+            out["sd_pa"] = np.sqrt(out["var_pa"])
+    return out
+
+
+def _report_batches(src, max_reads, arena_bytes, dev):
+    """the reads of a BLOW5 file or of a list of int16 arrays as device batches -> (d_sig, d_off, d_n, ids, dor rows)"""
+    import torch
+
+    if not isinstance(src, (str, os.PathLike)):
+        for k0 in range(0, len(src), max_reads):
+            part = src[k0:k0 + max_reads]
+            sig, off, ns, _ = _host_batch(part)
+            yield (torch.from_numpy(sig).to(dev), torch.from_numpy(off.view(np.int64)).to(dev),
+                   torch.from_numpy(ns.view(np.int32)).to(dev), ["read-%08d" % (k0 + k) for k in range(len(part))], None)
+        return
+    lib = load_library()
+    path = os.fspath(src)
+    rd = Blow5Reader(path)
+    lib.press_hip_blow5_next_pa.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.POINTER(ctypes.c_uint32)]
+    try:
+        arena = np.empty(arena_bytes, dtype=np.uint8)
+        boff = np.zeros(max_reads, dtype=np.uint64)
+        blen = np.zeros(max_reads, dtype=np.uint64)
+        bns = np.zeros(max_reads, dtype=np.uint32)
+        dor = np.zeros((max_reads, 3), dtype=np.float64)
+        idbuf = ctypes.create_string_buffer(max_reads * rd.ID_LEN)
+        got = ctypes.c_uint32()
+        while True:
+            if lib.press_hip_blow5_next_pa(rd._h, max_reads, arena.ctypes.data, arena.size, boff.ctypes.data, blen.ctypes.data,
+                                           bns.ctypes.data, idbuf, dor.ctypes.data, ctypes.byref(got)):
+                raise PressError(lib.press_hip_blow5_last_error().decode())
+            g = got.value
+            if g == 0:
+                break
+            ids = [idbuf.raw[k * rd.ID_LEN:(k + 1) * rd.ID_LEN].split(b"\0")[0].decode() for k in range(g)]
+            ns = bns[:g].copy()
+            off, total = _layout(ns)
+            d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+            d_n = torch.from_numpy(ns.view(np.int32)).to(dev)
+            if rd.signal_method == 1:  # svb-zd fields: decoded on the device, the samples stay there
+                end = int(boff[g - 1] + blen[g - 1])
+                d_sig = torch.zeros(total + 64, dtype=torch.int16, device=dev)
+                d_in = torch.from_numpy(arena[:end + 64].copy()).to(dev)
+                d_in_off = torch.from_numpy(boff[:g].view(np.int64).copy()).to(dev)
+                d_in_len = torch.from_numpy(blen[:g].view(np.int64).copy()).to(dev)
+                d_out_n = torch.zeros(g, dtype=torch.int32, device=dev)
+                depress_batch("slow5_svb_zd", d_in, d_in_off, d_in_len, d_sig, d_off, d_n, d_out_n)
+                if not torch.equal(d_out_n, d_n):
+                    raise PressError("a signal of %s does not decode" % path)
+            elif rd.signal_method == 0:  # int16 samples as stored
+                sig = np.zeros(total + 64, dtype=np.int16)
+                for k in range(g):
+                    sig[int(off[k]):int(off[k]) + int(ns[k])] = arena[int(boff[k]):int(boff[k] + blen[k])].view(np.int16)
+                d_sig = torch.from_numpy(sig).to(dev)
+            else:
+                raise PressError("%s: signal method %d" % (path, rd.signal_method))
+            yield d_sig, d_off, d_n, ids, dor[:g].copy()
+    finally:
+        rd.close()
+
+
+def dataset_report(src, max_reads=4096, arena_bytes=1 << 28):
+    """What the data looks like, tallied on the device: src is the path of a BLOW5 file or a list of int16 arrays.  The
+    reads go through in batches (svb-zd signal fields are decoded on the device), one press_hip_signal_tally per batch
+    with all four outputs; only the tables and the moments come back.  -> dict:
+      raw, delta, trans      the tables (numpy uint64)
+      raw_summary, delta_summary, symbol_summary   tally_summary of raw, of delta, and of the symbol stream (trans' column
+                             sums as a table over 0 .. 256)
+      h0, h1                 transition_entropy(trans)
+      bits                   {"raw", "delta", "symbols", "symbols_order1"}: entropy in bits per sample
+      ratio                  16 / bits for each of them (inf where the entropy is 0)
+      mom, ids, dor, stats   the per-read moments, the read ids, [nreads, 3] digitisation / offset / range (None for a list
+                             of arrays) and moments_stats(mom, dor)
+      reads, samples         counts"""
+    import torch
+
+    use_torch_stream()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    raw = torch.zeros(TALLY_BINS, dtype=torch.int64, device=dev)
+    delta = torch.zeros(TALLY_BINS, dtype=torch.int64, device=dev)
+    trans = torch.zeros(TALLY_SYMS * TALLY_SYMS, dtype=torch.int64, device=dev)
+    moms, ids, dors = [], [], []
+    for d_sig, d_off, d_n, batch_ids, dor in _report_batches(src, max_reads, arena_bytes, dev):
+        mom = torch.zeros(4 * d_off.numel(), dtype=torch.int64, device=dev)
+        signal_tally(d_sig, d_off, d_n, raw, delta, trans, mom)
+        moms.append(mom.cpu().numpy().view(MOMENTS_DTYPE))
+        ids += batch_ids
+        dors.append(dor)
+    rep = {"raw": raw.cpu().numpy().view(np.uint64), "delta": delta.cpu().numpy().view(np.uint64),
+           "trans": trans.cpu().numpy().view(np.uint64).reshape(TALLY_SYMS, TALLY_SYMS)}
+    rep["mom"] = np.concatenate(moms) if moms else np.zeros(0, dtype=MOMENTS_DTYPE)
+    rep["ids"] = ids
+    rep["dor"] = np.concatenate(dors) if dors and dors[0] is not None else None
+    rep["stats"] = moments_stats(rep["mom"], rep["dor"])
+    rep["reads"] = len(ids)
+    rep["samples"] = int(rep["mom"]["n"].astype(np.uint64).sum())
+    rep["raw_summary"] = tally_summary(rep["raw"])
+    rep["delta_summary"] = tally_summary(rep["delta"])
+    cols = rep["trans"].sum(axis=0)
+    sym = np.zeros(TALLY_BINS, dtype=np.uint64)  # symbol k as the value k: counter index zz(k) = 2 k
+    sym[2 * np.arange(TALLY_SYMS)] = cols
+    rep["symbol_summary"] = tally_summary(sym)
+    rep["h0"], rep["h1"] = transition_entropy(rep["trans"])
+    rep["bits"] = {"raw": rep["raw_summary"]["entropy"] or 0.0, "delta": rep["delta_summary"]["entropy"] or 0.0,
+                   "symbols": rep["h0"], "symbols_order1": rep["h1"]}
+    rep["ratio"] = {k: (16.0 / b if b > 0 else float("inf")) for k, b in rep["bits"].items()}
+    return rep
 
 
 # ---------------------------------------------------------------------------- BLOW5 input (host side)

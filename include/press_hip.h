@@ -958,6 +958,46 @@ int press_hip_signal_prefix(const int16_t *sig, const uint64_t *off, const uint3
 uint64_t press_hip_signal_prefix_workspace_bytes(uint32_t nreads);
 
 /*
+ * Dataset analysis: value, delta and transition tallies and per-read moments - what the reference's
+ * viz/freq_slow5, viz/freq_delta_slow5, viz/get_exceptions and press/stats.c compute on the host, in ONE pass over a batch.
+ *
+ * For read r with c = n[r] samples s[0 .. c):
+ *     zz(v)  = (uint16_t) ((v << 1) ^ (v >> 15))  for an int16 v: the index of viz/tally.h, trans.c's zig-zag
+ *     d[i]   = (int16_t) (s[i] - s[i-1])          for i in [1, c), wrapped to 16 bits
+ *     sym[i] = min(zz(d[i]), 256)                 what the shuffman_* and range-coder methods code; 256: the exceptions
+ *   raw      NULL, or 65536 counters:    raw[zz(s[i])] += 1                       for i in [0, c)
+ *   delta    NULL, or 65536 counters:    delta[zz(d[i])] += 1                     for i in [1, c); delta[0 .. 255] is what
+ *            press_hip_symbol_counts adds to its counts[0 .. 255], the sum of delta[256 ..] what it adds to counts[256]
+ *   trans    NULL, or 257 * 257 counters: trans[257 * sym[i-1] + sym[i]] += 1     for i in [2, c)
+ *   mom      NULL, or nreads records:  sum and sumsq of the samples, min and max (32767 and -32768 for an empty read, as
+ *            init_stats leaves them), n = c, and nex = the number of i in [1, c) with d[i] outside [-128, 127]
+ *            (zz(d[i]) > 255).  Exact integers; sumsq cannot wrap (2^32 samples of at most 2^30)
+ * The three tables are ADDED to, as press_hip_symbol_counts adds: a caller accumulates over batches and zeroes them itself.
+ * mom is SET.  Nothing else is written.  All outputs NULL, or nreads == 0, is PRESS_HIP_OK after the checks.
+ *   sig / off / n / total_samples / device_resident   as press_hip_symbol_counts, with its checks: off[] multiples of 8;
+ *            reads may overlap or repeat and are then counted twice.  Device resident: every pointer is a device pointer
+ *            and the call only enqueues on the current stream; the work list has room for total_samples / 32768 + nreads + 1
+ *            chunks of 32768 samples, so a batch whose reads overlap passes the sum of n[] where that is larger.
+ *            Host pointers: synchronous, through the staging layer; the call adds to the caller's host tables.
+ * Every sum is one of integers: the same on every run.
+ * press_hip_signal_tally_workspace_bytes: the device scratch the device-resident call keeps, 8 bytes per chunk and 64;
+ * exact, 0 for an empty batch.
+ */
+#define PRESS_HIP_TALLY_BINS 65536                   /* counters of raw and of delta */
+#define PRESS_HIP_TALLY_SYMS 257                     /* trans is PRESS_HIP_TALLY_SYMS squared counters */
+#define PRESS_HIP_TALLY_WORDS (2 * 65536 + 257 * 257) /* the three tables together */
+typedef struct {
+	int64_t sum;
+	uint64_t sumsq;
+	int32_t min, max;
+	uint32_t n, nex;
+} press_hip_moments; /* 32 bytes */
+int press_hip_signal_tally(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			   uint64_t total_samples, uint64_t *raw, uint64_t *delta, uint64_t *trans,
+			   press_hip_moments *mom, int device_resident);
+uint64_t press_hip_signal_tally_workspace_bytes(uint64_t total_samples, uint32_t nreads);
+
+/*
  * Lossy archives: dropping the low b bits of every sample, on the device.
  *
  * The definition.  For bits = b in 0 .. 8 and a sample s (int16), computed in 32-bit integers:
