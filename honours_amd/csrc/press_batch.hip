@@ -1445,3 +1445,94 @@ extern "C" int press_hip_stall_depress_batch(const uint8_t *in, const uint64_t *
 		return rc;
 	return st.fetch_samples(host);
 }
+
+// ------------------------------------------------------------------ the range-coder family: every coder on every layout
+//
+// press_hip_press_batch / press_hip_depress_batch with a (coder, layout) pair in the place of the method: the same checks,
+// the same staging, the same launch through the pair's row (rcf_method); press adds k_rcf_raw where the caller asks.
+
+static int rcf_args_ok(int coder, int layout, bool null_arg, uint32_t nreads, const void *dev_arena)
+{
+	if (!rcf_ok(coder, layout))
+		return set_error(PRESS_HIP_EARG, "range-coder family: coder %d (0 rc, 1 rcc, 2 rccm, 3 rccdf), layout %d (0 vbe21, 1 vbbe21, 2 vbsbe21, 3 vbsse21)",
+				 coder, layout);
+	return args_ok(NONE, NONE, null_arg, nreads, dev_arena, "sig");
+}
+
+extern "C" uint64_t press_hip_rcf_bound(int coder, int layout, uint32_t n)
+{
+	return rcf_ok(coder, layout) ? bound_vbzd(n) : 0; // press.c:5422 ... 7613: vb1e2_zd_bound_16 for all sixteen
+}
+
+extern "C" int press_hip_rcf_press_batch(int coder, int layout, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+					 uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len, uint8_t *raw,
+					 int device_resident)
+{
+	API_LOCK;
+	int rc = rcf_args_ok(coder, layout, nreads && (!sig || !off || !n || !out || !out_off || !out_len), nreads,
+			     device_resident ? sig : nullptr);
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	ScratchPlan plan = make_plan(rcf_method(coder, layout), total_samples, nreads, false);
+	if (raw && !device_resident)
+		plan.need(&Ctx::vf_raw, nreads);
+	if ((rc = plan.reserve()))
+		return rc;
+	BatchArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	const SlotsOut host = { out, out_off, out_len };
+	SamplesIn in = { sig, off, n };
+	SlotsOut so = host;
+	Staged st(nreads, s);
+	if (!device_resident && ((rc = check_slots(out_off, nreads)) || (rc = st.layout(off, n, total_samples, "the sample range", true)) ||
+				 (rc = st.slots(host, so)) || (rc = st.samples(in, total_samples, in))))
+		return rc;
+	bind_io(a, in);
+	bind_io(a, so);
+	uint8_t *draw = device_resident ? raw : raw ? (uint8_t *) g.vf_raw.p : nullptr;
+	if ((rc = launch_press(plan, a, s)))
+		return rc;
+	if (draw) {
+		launch_rcf_raw(a, draw, s);
+		if ((rc = launch_status()))
+			return rc;
+	}
+	if (device_resident)
+		return 0;
+	if (raw)
+		HIPCHK(hipMemcpyAsync(raw, draw, nreads, hipMemcpyDeviceToHost, s));
+	return st.fetch_streams(host);
+}
+
+extern "C" int press_hip_rcf_depress_batch(int coder, int layout, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+					   uint32_t nreads, int16_t *sig, const uint64_t *off, const uint32_t *n, uint64_t total_samples,
+					   uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	int rc = rcf_args_ok(coder, layout, nreads && (!in || !in_off || !in_len || !sig || !off || !n || !out_n), nreads,
+			     device_resident ? sig : nullptr);
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_plan(rcf_method(coder, layout), total_samples, nreads, true);
+	if ((rc = plan.reserve()))
+		return rc;
+	DecodeArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	const StreamsIn host = { in, in_off, in_len, off, n, out_n, sig };
+	StreamsIn io = host;
+	Staged st(nreads, s);
+	if (!device_resident && (rc = st.streams(host, total_samples, true, g.arena, g.arena_off, io)))
+		return rc;
+	bind_io(a, io);
+	if ((rc = launch_depress(plan, a, s)) || device_resident)
+		return rc;
+	return st.fetch_samples(host);
+}

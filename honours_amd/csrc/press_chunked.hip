@@ -2674,8 +2674,10 @@ static void ex_encode_streams(const BatchArgs &a, int fmt, int ent, hipStream_t 
 			launch_rcs_encode(a, s);
 		else if (ent == 3)
 			launch_rcc_encode(a, s);
-		else
+		else if (ent == 4)
 			launch_rcm_encode(a, s);
+		else
+			launch_cdf_encode(a, s);
 		ktime_end(0, s);
 		return;
 	}

@@ -142,6 +142,39 @@ void stall_depress_(const uint8_t *in, uint64_t nsamples, int16_t *out, uint32_t
 	*nout = got;
 }
 
+// the range-coder family: one read through press_hip_rcf_press_batch / press_hip_rcf_depress_batch
+void rcf_press_(int coder, int layout, const int16_t *in, uint32_t n, uint8_t *out, uint64_t *nout)
+{
+	const uint64_t off[1] = { 0 };
+	const uint64_t ooff[2] = { 0, *nout };
+	uint64_t l = PRESS_HIP_FAILED;
+	int rc = n ? press_hip_rcf_press_batch(coder, layout, in, off, &n, 1, n, out, ooff, &l, nullptr, 0) : set_error(PRESS_HIP_EARG, "empty read");
+	if (!rc && l == PRESS_HIP_FAILED)
+		rc = set_error(-1, "stream does not fit %llu bytes", (unsigned long long) *nout);
+	if (rc) {
+		fprintf(stderr, "press_hip: %s\n", press_hip_last_error());
+		l = 0;
+	}
+	*nout = l;
+}
+
+void rcf_depress_(int coder, int layout, const uint8_t *in, uint64_t nbytes, int16_t *out, uint32_t *nout)
+{
+	const uint64_t off[1] = { 0 };
+	const uint64_t ioff[1] = { 0 };
+	const uint64_t ilen[1] = { nbytes };
+	uint32_t cap = *nout, got = UINT32_MAX;
+	int rc = cap ? press_hip_rcf_depress_batch(coder, layout, in, ioff, ilen, 1, out, off, &cap, cap, &got, 0)
+		     : set_error(PRESS_HIP_EARG, "no room for samples");
+	if (!rc && got == UINT32_MAX)
+		rc = set_error(-1, "malformed stream");
+	if (rc) {
+		fprintf(stderr, "press_hip: %s\n", press_hip_last_error());
+		got = 0;
+	}
+	*nout = got;
+}
+
 // zstd level 1 (press.h:275) around a GPU-made inner stream (press.c:1865, 2025, 8554)
 int zstd_press_(int inner, bool prefix_n, const int16_t *in, uint32_t n, uint8_t *out, uint64_t *nout)
 {
@@ -391,5 +424,30 @@ void *press_hip_slow5_ptr_depress_svb_zd(const uint8_t *ptr, size_t count, size_
 STALL_FAMILY(rccm_svbbe21_zd, PRESS_HIP_STALL_RCCM_SVBBE21_ZD)
 STALL_FAMILY(dstall_fz_1500, PRESS_HIP_STALL_DSTALL_FZ_1500)
 STALL_FAMILY(dstall_fz, PRESS_HIP_STALL_DSTALL_FZ)
+
+// ---- the thirteen pairs of the range-coder family that are not public methods (press.h:752-899), VB_FAMILY's shape
+#define RCF_FAMILY(name, coder, layout)                                                          \
+	uint64_t name##_zd_bound_16(uint32_t nin) { return press_hip_rcf_bound(coder, layout, nin); } \
+	void name##_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout)   \
+	{                                                                                        \
+		rcf_press_(coder, layout, in, nin, out, nout);                                   \
+	}                                                                                        \
+	void name##_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout)       \
+	{                                                                                        \
+		rcf_depress_(coder, layout, in, nin, out, nout);                                 \
+	}
+RCF_FAMILY(rc_vbbe21, PRESS_HIP_RCF_RC, PRESS_HIP_RCF_VBBE21)
+RCF_FAMILY(rc_vbsbe21, PRESS_HIP_RCF_RC, PRESS_HIP_RCF_VBSBE21)
+RCF_FAMILY(rc_vbsse21, PRESS_HIP_RCF_RC, PRESS_HIP_RCF_VBSSE21)
+RCF_FAMILY(rcc_vbbe21, PRESS_HIP_RCF_RCC, PRESS_HIP_RCF_VBBE21)
+RCF_FAMILY(rcc_vbsbe21, PRESS_HIP_RCF_RCC, PRESS_HIP_RCF_VBSBE21)
+RCF_FAMILY(rcc_vbsse21, PRESS_HIP_RCF_RCC, PRESS_HIP_RCF_VBSSE21)
+RCF_FAMILY(rccm_vbe21, PRESS_HIP_RCF_RCCM, PRESS_HIP_RCF_VBE21)
+RCF_FAMILY(rccm_vbsbe21, PRESS_HIP_RCF_RCCM, PRESS_HIP_RCF_VBSBE21)
+RCF_FAMILY(rccm_vbsse21, PRESS_HIP_RCF_RCCM, PRESS_HIP_RCF_VBSSE21)
+RCF_FAMILY(rccdf_vbe21, PRESS_HIP_RCF_RCCDF, PRESS_HIP_RCF_VBE21)
+RCF_FAMILY(rccdf_vbbe21, PRESS_HIP_RCF_RCCDF, PRESS_HIP_RCF_VBBE21)
+RCF_FAMILY(rccdf_vbsbe21, PRESS_HIP_RCF_RCCDF, PRESS_HIP_RCF_VBSBE21)
+RCF_FAMILY(rccdf_vbsse21, PRESS_HIP_RCF_RCCDF, PRESS_HIP_RCF_VBSSE21)
 
 } // extern "C"

@@ -224,6 +224,31 @@ inline bool method_ok(int m) { return m >= 0 && m < PRESS_HIP_NMETHODS; }
 inline bool is_shuff(const Method &m) { return m.family == FAM_EX && m.ent == 1; }
 inline bool is_rc(const Method &m) { return m.family == FAM_EX && m.ent >= 2; }
 
+// ---- the range-coder family (press_hip_rcf_*): every coder on every layout.  Rows of its own behind the public ids,
+// where method_ok does not reach them; the three pairs that are public methods go through the public rows.
+constexpr int RCF_PRIVATE = PRESS_HIP_NMETHODS; // private id = RCF_PRIVATE + 4 * coder + layout
+#define M_RCF(coder, ent)                                                                                    \
+	M_EX(RCF_PRIVATE + 4 * coder + 0, EXF_VBE21, ent), M_EX(RCF_PRIVATE + 4 * coder + 1, EXF_VBBE21, ent), \
+		M_EX(RCF_PRIVATE + 4 * coder + 2, EXF_VBSBE21, ent), M_EX(RCF_PRIVATE + 4 * coder + 3, EXF_VBSSE21, ent)
+constexpr Method RCF_METHODS[PRESS_HIP_NRCF_CODERS * PRESS_HIP_NRCF_LAYOUTS] = {
+	M_RCF(PRESS_HIP_RCF_RC, 2), M_RCF(PRESS_HIP_RCF_RCC, 3), M_RCF(PRESS_HIP_RCF_RCCM, 4), M_RCF(PRESS_HIP_RCF_RCCDF, 5),
+};
+static_assert((int) EXF_VBE21 == (int) PRESS_HIP_RCF_VBE21 && (int) EXF_VBBE21 == (int) PRESS_HIP_RCF_VBBE21 &&
+		      (int) EXF_VBSBE21 == (int) PRESS_HIP_RCF_VBSBE21 && (int) EXF_VBSSE21 == (int) PRESS_HIP_RCF_VBSSE21,
+	      "the family's layout ids are the exception formats");
+inline bool rcf_ok(int coder, int layout)
+{
+	return coder >= 0 && coder < PRESS_HIP_NRCF_CODERS && layout >= 0 && layout < PRESS_HIP_NRCF_LAYOUTS;
+}
+inline const Method &rcf_method(int coder, int layout)
+{
+	const Method &m = RCF_METHODS[4 * coder + layout];
+	for (const Method &pub : METHODS)
+		if (pub.family == FAM_EX && pub.exfmt == m.exfmt && pub.ent == m.ent)
+			return pub;
+	return m;
+}
+
 // ---- bounds: the reference's formulas ----
 inline uint32_t svb16_keylen(uint32_t n) { return (n >> 3) + (((n & 7) + 7) >> 3); }
 inline uint64_t bound_svb32(uint32_t n) { return (uint64_t) (n + 3) / 4 + (uint64_t) n * 4 + 16; }    // streamvbyte.h:35
@@ -254,6 +279,7 @@ struct ScratchPlan {
 	ZsBufs zs() const;                 // z with its pointers
 };
 ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool decode);
+ScratchPlan make_plan(const Method &method, uint64_t total_samples, uint32_t nreads, bool decode); // ... or a row of RCF_METHODS
 // The calls that decode nothing and walk samples by launch_pa_tiles' table: make_plan's max_chunks, and the table
 ScratchPlan make_tiles_plan(uint64_t total_samples, uint32_t nreads);
 

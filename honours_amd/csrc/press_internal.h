@@ -476,7 +476,7 @@ void launch_stall_parse(const uint8_t *in, const uint64_t *in_off, const uint64_
 			const StallBufs &b, hipStream_t s);
 void launch_stall_scatter(int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint32_t *out_n,
 			  hipStream_t s);
-void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing
+void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing, 5 nibble-CDF coder
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip
 void launch_huff_decode(const DecodeArgs &a, uint32_t minlen, hipStream_t s);      // press_huffman.hip
@@ -487,6 +487,10 @@ void launch_rcc_encode(const BatchArgs &a, hipStream_t s);  // order 1 (rcc_vbe2
 void launch_rcc_decode(const DecodeArgs &a, hipStream_t s);
 void launch_rcm_encode(const BatchArgs &a, hipStream_t s);  // order 1-0 context mixing (rccm_vbbe21_zd)
 void launch_rcm_decode(const DecodeArgs &a, hipStream_t s);
+void launch_cdf_encode(const BatchArgs &a, hipStream_t s);  // ent 5: the adaptive nibble-CDF coder (rccdf_*_zd), press_cdf.hip
+void launch_cdf_decode(const DecodeArgs &a, hipStream_t s);
+// behind the encode of a range-coder method (ent >= 2): raw[r] = 1 where the coder gave up and stored the one-byte values
+void launch_rcf_raw(const BatchArgs &a, uint8_t *raw, hipStream_t s);
 // symbol counts of a batch for fitting a Huffman table (press_train.hip): adds into counts[257]; chunks takes
 // train_scratch_bytes(max_chunks), nchunks is one device word (zeroed here)
 uint64_t train_scratch_bytes(uint32_t max_chunks);

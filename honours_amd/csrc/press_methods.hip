@@ -84,8 +84,14 @@ ScratchPlan make_tiles_plan(uint64_t total_samples, uint32_t nreads)
 
 ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool decode)
 {
+	return make_plan(METHODS[method], total_samples, nreads, decode);
+}
+
+// (a row of METHODS, or a private one of RCF_METHODS)
+ScratchPlan make_plan(const Method &method, uint64_t total_samples, uint32_t nreads, bool decode)
+{
 	ScratchPlan p{};
-	p.m = &METHODS[method];
+	p.m = &method;
 	const bool zs = p.m->family == FAM_ZSTD;
 	const Method &k = zs ? METHODS[p.m->inner] : *p.m; // the method whose kernels make / read the samples
 	const size_t nr = (size_t) nreads + 1;

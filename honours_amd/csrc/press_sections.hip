@@ -628,6 +628,8 @@ void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s)
 			launch_rcc_decode(a, s);
 		else if (ent == 4)
 			launch_rcm_decode(a, s);
+		else if (ent == 5)
+			launch_cdf_decode(a, s);
 		else
 			launch_huff_decode(a, a.huf_minlen, s);
 		ktime_end(1, s);

@@ -28,6 +28,10 @@ METHODS = {
 BATCH_METHODS = [m for m in METHODS if not m.startswith("zstd_")]
 # include/press_hip.h enum press_hip_stall_method: a family of its own (the generic batch calls do not take these ids)
 STALL_METHODS = {"rccm_svbbe21_zd": 0, "dstall_fz_1500": 1, "dstall_fz": 2}
+# include/press_hip.h enum press_hip_rcf_coder / press_hip_rcf_layout: the range-coder family, every coder on every
+# layout (ids of its own again; "rccdf" on "vbe21" is the reference's rccdf_vbe21_zd)
+RCF_CODERS = {"rc": 0, "rcc": 1, "rccm": 2, "rccdf": 3}
+RCF_LAYOUTS = {"vbe21": 0, "vbbe21": 1, "vbsbe21": 2, "vbsse21": 3}
 FAILED = (1 << 64) - 1
 
 # method -> (bound symbol, press symbol, depress symbol, calling convention)
@@ -106,8 +110,10 @@ HEADER_SYMBOLS = sorted(set(
      "press_hip_signal_prefix_workspace_bytes",
      "press_hip_signal_tally", "press_hip_signal_tally_workspace_bytes",
      "press_hip_stall_bound", "press_hip_stall_press_batch", "press_hip_stall_depress_batch",
-     "press_hip_stall_workspace_bytes"] +
-    [m + s for m in STALL_METHODS for s in ("_bound_16", "_press_16", "_depress_16")]))
+     "press_hip_stall_workspace_bytes",
+     "press_hip_rcf_bound", "press_hip_rcf_press_batch", "press_hip_rcf_depress_batch"] +
+    [m + s for m in STALL_METHODS for s in ("_bound_16", "_press_16", "_depress_16")] +
+    ["%s_%s_zd%s" % (c, l, s) for c in RCF_CODERS for l in RCF_LAYOUTS for s in ("_bound_16", "_press_16", "_depress_16")]))
 
 
 class PressError(RuntimeError):
@@ -204,7 +210,17 @@ def load_library(path=LIB_PATH):
         _lib.press_hip_stall_depress_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                                        ctypes.c_void_p, ctypes.c_int]
-        for m in STALL_METHODS:
+        _lib.press_hip_rcf_bound.restype = ctypes.c_uint64
+        _lib.press_hip_rcf_bound.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32]
+        _lib.press_hip_rcf_press_batch.restype = ctypes.c_int
+        _lib.press_hip_rcf_press_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        _lib.press_hip_rcf_depress_batch.restype = ctypes.c_int
+        _lib.press_hip_rcf_depress_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
+        for m in list(STALL_METHODS) + ["%s_%s_zd" % (c, l) for c in RCF_CODERS for l in RCF_LAYOUTS]:
             getattr(_lib, m + "_bound_16").restype = ctypes.c_uint64
             getattr(_lib, m + "_bound_16").argtypes = [ctypes.c_uint32]
             getattr(_lib, m + "_press_16").restype = None
@@ -1540,6 +1556,119 @@ def stall_depress_batch_host(streams, ns):
     out_n = np.zeros(nreads, dtype=np.uint32)
     rc = lib.press_hip_stall_depress_batch(comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads, sig.ctypes.data,
                                            off.ctypes.data, ns.ctypes.data, total, out_n.ctypes.data, 0)
+    if rc:
+        raise PressError(last_error())
+    return [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)]
+
+
+# ---- the range-coder family: every coder on every layout (press_hip_rcf_*)
+
+
+def _rcf_ids(coder, layout):
+    return (RCF_CODERS[coder] if isinstance(coder, str) else int(coder),
+            RCF_LAYOUTS[layout] if isinstance(layout, str) else int(layout))
+
+
+def rcf_name(coder, layout):
+    """the reference's name of a pair: rcf_name("rccdf", "vbe21") == "rccdf_vbe21_zd" """
+    c, l = _rcf_ids(coder, layout)
+    return "%s_%s_zd" % ([k for k, v in RCF_CODERS.items() if v == c][0], [k for k, v in RCF_LAYOUTS.items() if v == l][0])
+
+
+def rcf_bound(coder, layout, n):
+    """X_bound_16(n) of a pair: the plain layouts' for all sixteen; 0 for an id out of range"""
+    c, l = _rcf_ids(coder, layout)
+    return int(load_library().press_hip_rcf_bound(c, l, int(n)))
+
+
+def rcf_press(coder, layout, sig, cap=None):
+    """X_press_16 of a pair through the per-read symbol -> (ret, bytes); ret -1: the library reports *nout = 0"""
+    lib = load_library()
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    cap = rcf_bound(coder, layout, sig.size) + 1024 if cap is None else int(cap)
+    out = np.zeros(cap + 64, dtype=np.uint8)
+    out[cap:] = 0xA5
+    nout = ctypes.c_uint64(cap)
+    name = rcf_name(coder, layout)
+    getattr(lib, name + "_press_16")(sig.ctypes.data, sig.size, out.ctypes.data, ctypes.byref(nout))
+    if not np.all(out[cap:] == 0xA5):
+        raise PressError("%s_press_16 wrote past its capacity" % name)
+    return (0, out[:nout.value].tobytes()) if nout.value else (-1, b"")
+
+
+def rcf_depress(coder, layout, comp, n):
+    """X_depress_16 of a pair through the per-read symbol; n: the read's exact sample count -> (ret, int16 array)"""
+    lib = load_library()
+    buf = np.frombuffer(bytes(comp) + b"\0" * 64, dtype=np.uint8).copy()
+    out = np.zeros(n + 64, dtype=np.int16)
+    out[n:] = 0x5A5A
+    nout = ctypes.c_uint32(n)
+    name = rcf_name(coder, layout)
+    getattr(lib, name + "_depress_16")(buf.ctypes.data, len(comp), out.ctypes.data, ctypes.byref(nout))
+    if not np.all(out[n:] == 0x5A5A):
+        raise PressError("%s_depress_16 wrote past the sample capacity" % name)
+    return (0, out[:nout.value].copy()) if nout.value else (-1, out[:0].copy())
+
+
+def rcf_press_batch(coder, layout, sig, off, n, out, out_off, out_len, raw=None):
+    """Enqueue the compression of a batch under a pair of the family.  CUDA tensors as in press_batch; raw: None, or
+    uint8 of nreads: 1 where the coder gave up and the payload is the read's one-byte values as they are"""
+    c, l = _rcf_ids(coder, layout)
+    nreads = off.numel()
+    rc = load_library().press_hip_rcf_press_batch(c, l, sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
+                                                  out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(),
+                                                  None if raw is None else raw.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def rcf_depress_batch(coder, layout, comp, in_off, in_len, sig, off, n, out_n):
+    """Enqueue the decompression of a batch of streams of a pair.  CUDA tensors as in depress_batch; n: the reads' exact
+    sample counts"""
+    c, l = _rcf_ids(coder, layout)
+    nreads = off.numel()
+    rc = load_library().press_hip_rcf_depress_batch(c, l, comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), nreads,
+                                                    sig.data_ptr(), off.data_ptr(), n.data_ptr(), sig.numel(), out_n.data_ptr(), 1)
+    if rc:
+        raise PressError(last_error())
+
+
+def rcf_press_batch_host(coder, layout, reads, caps=None, want_raw=False):
+    """Host buffers: reads = list of int16 arrays -> list of bytes / None (want_raw: and uint8 [nreads])"""
+    c, l = _rcf_ids(coder, layout)
+    nreads = len(reads)
+    sig, off, ns, total = _host_batch(reads)
+    if caps is None:
+        caps = [rcf_bound(c, l, int(x)) + 1024 if x else 32 for x in ns]
+    out_off = np.zeros(nreads + 1, dtype=np.uint64)
+    out_off[1:] = np.cumsum((np.asarray(caps, dtype=np.uint64) + 15) // 16 * 16)
+    out = np.zeros(int(out_off[-1]) + 64, dtype=np.uint8)
+    out_len = np.zeros(nreads, dtype=np.uint64)
+    raw = np.zeros(nreads, dtype=np.uint8)
+    rc = load_library().press_hip_rcf_press_batch(c, l, sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total,
+                                                  out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
+                                                  raw.ctypes.data if want_raw else None, 0)
+    if rc:
+        raise PressError(last_error())
+    streams = [None if int(k) == FAILED else out[int(o): int(o) + int(k)].tobytes() for o, k in zip(out_off[:-1], out_len)]
+    return (streams, raw) if want_raw else streams
+
+
+def rcf_depress_batch_host(coder, layout, streams, ns):
+    """Host buffers: streams = list of bytes, ns = the reads' exact sample counts -> list of int16 arrays / None"""
+    c, l = _rcf_ids(coder, layout)
+    nreads = len(streams)
+    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+    in_off = np.zeros(nreads, dtype=np.uint64)
+    if nreads > 1:
+        in_off[1:] = np.cumsum(in_len)[:-1]
+    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
+    ns = np.asarray(ns, dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    out_n = np.zeros(nreads, dtype=np.uint32)
+    rc = load_library().press_hip_rcf_depress_batch(c, l, comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads,
+                                                    sig.ctypes.data, off.ctypes.data, ns.ctypes.data, total, out_n.ctypes.data, 0)
     if rc:
         raise PressError(last_error())
     return [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)]

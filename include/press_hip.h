@@ -1203,6 +1203,108 @@ int press_hip_stall_depress_batch(const uint8_t *in, const uint64_t *in_off, con
  * streams - the most a stream can take, so that only the caller's slot decides whether a read fits.  0 for a bad id. */
 uint64_t press_hip_stall_workspace_bytes(int stall_method, uint64_t total_samples, uint32_t nreads);
 
+/* ======================================================================= (2t) the range-coder family */
+
+/*
+ * The reference pairs each of its four range coders with each of its four exception layouts (press.h:712-899): sixteen
+ * methods {rc, rcc, rccm, rccdf}_{vbe21, vbbe21, vbsbe21, vbsse21}_zd.  A stream is the layout's header and exception
+ * section as the plain method L_zd writes them, then the read's one-byte values through the coder.  Three of the pairs are
+ * public methods (rc_vbe21_zd, rcc_vbe21_zd, rccm_vbbe21_zd: the same kernels, the same bytes); the family reaches all
+ * sixteen, with ids of its own: enum press_hip_method, PRESS_HIP_NMETHODS and the generic batch calls do not know them.
+ *
+ *   rc      TurboRC's order-0 binary coder (rcsenc), rcc its order-1 coder (rccsenc), rccm its order 1-0 context mixing
+ *           (rcmsenc) - as in the three public methods
+ *   rccdf   TurboRC's adaptive nibble-CDF coder (rccdfenc / rccdfdec): two 16-ary decisions per byte, 17 tables of 16
+ *           cumulative frequencies, each moving towards the coded symbol by 1/128.  The stream depends on how rccdf.c was
+ *           compiled: with __AVX2__ it uses a 32-bit range, 14-bit frequencies and 16-bit output.  This library writes
+ *           and reads the variant WITHOUT __AVX2__ - 64-bit range, 15-bit frequencies, 32-bit little-endian words -
+ *           because TurboRC's own makefile leaves AVX2 off; a reference built with -mavx2 or -march=native on such a host
+ *           makes other bytes.
+ *
+ * Raw-stored payloads.  Every one of the four coders gives up once its output reaches nlow * 255 / 256 - 8 bytes (nlow:
+ * the read's one-byte values) and stores the nlow bytes verbatim; every read of at most nine one-byte values ends so.
+ * Nothing in the stream says that this happened, and the decoder - the reference's and this library's - decodes such a
+ * payload like any other: the read does NOT come back.  press reports it instead:
+ *   raw     NULL, or nreads bytes: raw[r] = 1 where the payload of read r has nlow bytes and equals the one-byte values
+ *           byte for byte (the coder gave up), else 0 (also for a read that failed).  A caller who needs the read back
+ *           stores such a read with another method.
+ * Slots: a stream needs at most its section plus nlow + 32 bytes; press_hip_rcf_bound, the reference's X_bound_16
+ * (that of the plain layouts for all sixteen; 0 for an id out of range), covers it on signal data.
+ * A stream that ends early is decoded with zeros behind its end; nothing outside a read's stream is read.
+ *
+ * The batch calls: arguments, layout rules and the meaning of device_resident as in press_hip_press_batch /
+ * press_hip_depress_batch (device resident: the call only enqueues on the current stream; raw is then a device pointer).
+ * depress: n[r] is the read's exact sample count (the streams do not carry it).  A bad coder or layout id or a NULL
+ * argument (raw excepted) is PRESS_HIP_EARG before any device call; nreads == 0 is PRESS_HIP_OK.
+ *
+ * The family's ids are accepted by these calls alone: the recode, picoampere, normalise, chunk-row, verify, CRC, sizes
+ * and packed calls do not learn them.  Not built: rccm_svb_zd, rccm_svb12_zd, the range-coder methods without zd, jumps.
+ */
+enum press_hip_rcf_coder {
+	PRESS_HIP_RCF_RC      = 0,
+	PRESS_HIP_RCF_RCC     = 1,
+	PRESS_HIP_RCF_RCCM    = 2,
+	PRESS_HIP_RCF_RCCDF   = 3,
+	PRESS_HIP_NRCF_CODERS = 4
+};
+enum press_hip_rcf_layout {
+	PRESS_HIP_RCF_VBE21    = 0,
+	PRESS_HIP_RCF_VBBE21   = 1,
+	PRESS_HIP_RCF_VBSBE21  = 2,
+	PRESS_HIP_RCF_VBSSE21  = 3,
+	PRESS_HIP_NRCF_LAYOUTS = 4
+};
+uint64_t press_hip_rcf_bound(int coder, int layout, uint32_t n);
+int press_hip_rcf_press_batch(int coder, int layout, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			      uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len, uint8_t *raw,
+			      int device_resident);
+int press_hip_rcf_depress_batch(int coder, int layout, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+				uint32_t nreads, int16_t *sig, const uint64_t *off, const uint32_t *n, uint64_t total_samples,
+				uint32_t *out_n, int device_resident);
+
+/* the reference's per-read symbols of the thirteen pairs that are not public methods (press.h:752-899), synchronous, as
+ * rc_vbe21_zd_press_16 and its kin above: *nout of press the capacity in, the length out (0: refused); *nout of depress
+ * the exact sample count in */
+uint64_t rc_vbbe21_zd_bound_16(uint32_t nin);
+void rc_vbbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rc_vbbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rc_vbsbe21_zd_bound_16(uint32_t nin);
+void rc_vbsbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rc_vbsbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rc_vbsse21_zd_bound_16(uint32_t nin);
+void rc_vbsse21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rc_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rcc_vbbe21_zd_bound_16(uint32_t nin);
+void rcc_vbbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rcc_vbbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rcc_vbsbe21_zd_bound_16(uint32_t nin);
+void rcc_vbsbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rcc_vbsbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rcc_vbsse21_zd_bound_16(uint32_t nin);
+void rcc_vbsse21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rcc_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rccm_vbe21_zd_bound_16(uint32_t nin);
+void rccm_vbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rccm_vbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rccm_vbsbe21_zd_bound_16(uint32_t nin);
+void rccm_vbsbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rccm_vbsbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rccm_vbsse21_zd_bound_16(uint32_t nin);
+void rccm_vbsse21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rccm_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rccdf_vbe21_zd_bound_16(uint32_t nin);
+void rccdf_vbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rccdf_vbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rccdf_vbbe21_zd_bound_16(uint32_t nin);
+void rccdf_vbbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rccdf_vbbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rccdf_vbsbe21_zd_bound_16(uint32_t nin);
+void rccdf_vbsbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rccdf_vbsbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rccdf_vbsse21_zd_bound_16(uint32_t nin);
+void rccdf_vbsse21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rccdf_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+
 /* ======================================================================= (3) BLOW5 files (host) */
 
 /*
