@@ -4,19 +4,20 @@
 // started at a wrong bit position falls back onto true code boundaries after a few codes.
 // The payload of every read is cut into SUBSEQUENCES of OWN bits (256 for the NA12878 table,
 // whose shortest code has 4 bits), one lane each; a TILE = 256 subsequences (8 KiB) is the unit the records are
-// kept by, a quarter of it (64 subsequences) what a wave takes at a time.  In the two heavy kernels the waves of a
+// kept by, a quarter of it (64 subsequences) what a wave of k_huf_emit takes at a time.  In the two heavy kernels the waves of a
 // workgroup share the tables and nothing else - no barrier, no wave waits for another:
 //
 //   k_huf_sync   where do codes start?  Lengths (and the sample deltas the symbols stand for - no symbols): one
 //                LDS look-up takes every whole code that fits in 12 bits, and its entry is the increment of ONE
-//                accumulator (position, codes, delta sum).  Lane i first runs through the last RU = OWN/2 bits of
-//                its OWN subsequence: where that run crosses into the next subsequence is lane i + 1's guess of its
-//                first code's start (right in ~97 % of the cases; handed over by a lane shuffle); then through its
-//                own subsequence from its guess.  Leaves a record per subsequence {start, codes, sum of their
-//                deltas}, where it ended, per wave of a tile the totals, and ONE 64-bit word per unit: the lanes
-//                whose guess is not where the left neighbour ended (~3 %) and the unit's first lane (no guess: it
-//                starts at bit 0).  Nothing is repaired here.
-//                The lane's bits live in a private LDS column (dword j of lane l at j*64 + l: any mix of per-lane
+//                accumulator (position, codes, delta sum).  Lane i takes two subsequences in a row, A and B (a wave
+//                half a tile).  It first runs through the last RU = OWN/2 bits of B: where that run crosses into
+//                the next subsequence is lane i + 1's guess of its A's first code's start (right in ~97 % of the
+//                cases; handed over by a lane shuffle); then through A from its guess and through B from where A
+//                ended - one run-up for two subsequences.  Leaves a record per subsequence {start, codes, sum of
+//                their deltas}, where it ended, per 64 subsequences the totals and ONE 64-bit word: the
+//                subsequences whose start is not where the one in front ended (~3 % of the A's) and the wave's first
+//                (no guess: it starts at bit 0).  Nothing is repaired here.
+//                The bits a lane scans live in a private LDS column (dword j of lane l at j*64 + l: any mix of per-lane
 //                positions is bank-conflict free).  The lean loops are divergent while-loops (a lane that is through
 //                leaves); while 12 bits are left in front of the limit nothing can step over it, so the body is one
 //                look-up fed from a register window over the column (the dword behind the window is fetched while
@@ -26,11 +27,12 @@
 //                was right is dropped; the others are decoded again from where the subsequence in front ended; the
 //                wave totals take the difference (one 64-bit atomic); if the subsequence's own end moved, its right
 //                neighbour goes on the next round's list.  Four launches; an ordinary table is through after two
-//                (1 150 000 -> 30 000 -> 900 -> 20 entries).
+//                (on bench.py's batch 450 000 -> 600 -> 3 -> 0 entries).
 //   k_huf_serial what is listed after that (a code whose lengths share a factor never synchronises): one wave
 //                per such read walks it serially from the first unsettled subsequence - slow, enough for ANY
 //                table and stream; the rounds before it are only faster.
-//   k_huf_chain  one workgroup per read: what the read delivers, whether k_huf_emit can write its samples, and per
+//   k_huf_chain  one workgroup per read: what the read delivers (a read whose codes end in bits that are no code is
+//                refused), whether k_huf_emit can write its samples, and per
 //                unit of k_huf_emit a plan (HufUnit, 32 bytes): where its payload lies, the codes in front of it (scan of
 //                the wave totals) and what it delivers, its slice of the exceptions and the sample value in front of it.
 //   k_huf_emit   lane i decodes its subsequence once more from its true start, now with the two-symbol
@@ -216,6 +218,59 @@ __device__ __forceinline__ void col_load(uint32_t *col, const uint8_t *src, int3
 	}
 }
 
+// NP dwords of a payload [0, nby) from byte offset rb0 (a multiple of 4, not negative) into registers (k_huf_sync's
+// lanes hold two subsequences in a row and write them to the column in turn).  Bytes behind the payload read as zero.
+// The last bytes of a payload: every dword is loaded whole from an address clamped into the payload and shifted
+// into place - unconditional loads, all in flight together, and no more registers than the lanes inside need (a
+// byte at a time as in col_load, 4 NP loads and their conditions did not fit 64 registers).
+template <int NP>
+__device__ __forceinline__ void pay_load(uint32_t (&r)[NP], const uint8_t *src, int32_t rb0, int32_t nby)
+{
+	if (rb0 + 4 * NP <= nby) {
+		const uint8_t *q = src + rb0;
+		uint4 t[NP / 4 ? NP / 4 : 1];
+		uint32_t x[NP % 4 ? NP % 4 : 1];
+#pragma unroll
+		for (int j = 0; j < NP / 4; j++)
+			t[j] = ld16_pay(q + 16 * j);
+#pragma unroll
+		for (int j = 0; j < NP % 4; j++)
+			x[j] = ld4_pay(q + 4 * (NP / 4 * 4 + j));
+		// (every branch writes r[] in the same order: the array stays in registers)
+#pragma unroll
+		for (int j = 0; j < NP / 4; j++) {
+			r[4 * j + 0] = t[j].x;
+			r[4 * j + 1] = t[j].y;
+			r[4 * j + 2] = t[j].z;
+			r[4 * j + 3] = t[j].w;
+		}
+#pragma unroll
+		for (int j = 0; j < NP % 4; j++)
+			r[NP / 4 * 4 + j] = x[j];
+	} else if (nby >= 4) {
+		uint32_t d[NP];
+#pragma unroll
+		for (int j = 0; j < NP; j++) {
+			const int32_t p = rb0 + 4 * j;
+			d[j] = ld4_pay(src + (p < nby - 4 ? p : nby - 4));
+		}
+#pragma unroll
+		for (int j = 0; j < NP; j++) {
+			const int32_t over = rb0 + 4 * j - (nby - 4); // bytes the dword was moved down by
+			r[j] = over <= 0 ? d[j] : (over < 4 ? d[j] >> (8 * over) : 0u);
+		}
+	} else {
+		// a payload of one to three bytes (or none)
+		uint32_t x = 0;
+		if (rb0 == 0)
+			for (int32_t i = 0; i < nby; i++)
+				x |= (uint32_t) src[i] << (8 * i);
+#pragma unroll
+		for (int j = 0; j < NP; j++)
+			r[j] = j ? 0u : x;
+	}
+}
+
 // the delta a one-byte value stands for (zig-zag undone)
 __device__ __forceinline__ int32_t unzz8(uint32_t z) { return (int32_t) (z >> 1) ^ -(int32_t) (z & 1u); }
 
@@ -361,7 +416,7 @@ __device__ __forceinline__ void wave_lds_sync()
 
 // ------------------------------------------------------------------ first pass
 
-// Sixteen waves share the tables and nothing else: a wave takes a quarter of a tile (64 subsequences) per ticket and
+// Sixteen waves share the tables and nothing else: a wave takes half a tile (128 subsequences) per ticket and
 // never meets the workgroup's other waves at a barrier, so that the waves of a CU are in different phases - loads,
 // run-up, own pass, records - at any time (with the four barriers per round of the tile-per-256-threads version the
 // sixteen waves of a workgroup waited for the round's loads together: 0.82 ms for 0.62 ms of instruction issue).
@@ -384,7 +439,7 @@ __device__ __forceinline__ uint32_t pack_rec(uint32_t f, uint32_t c, uint32_t d)
 }
 
 constexpr uint32_t LIST_NONE = 0xFFFFFFFFu; // an unused list slot
-constexpr uint32_t SYNC_UC = 16;            // quarter tiles a workgroup takes from the global counter at a time
+constexpr uint32_t SYNC_UC = 16;            // tickets (half tiles) a workgroup takes from the global counter at a time
 
 // append the lanes with `yes` to the list whose counter is *cnt (one atomic per wave)
 __device__ __forceinline__ void list_push(uint32_t *list, uint32_t *cnt, uint32_t cap, bool yes, uint32_t value, uint32_t lane)
@@ -418,20 +473,47 @@ __device__ __forceinline__ void load_len_tables(const HuffDev *hd, LenTabs *t, u
 }
 
 
-// All tiles, first pass.  Persistent workgroups (the tables are loaded once); a wave's unit of work is a quarter of
-// a tile: every lane runs up through the half subsequence in front of its own - where that crosses into its
-// subsequence is its guess of the first code's start - and then through its own.  Lanes whose guess is not where the
-// left neighbour ended go on the list of k_huf_fix, and so does every unit's first lane, unchecked: where the
-// subsequence in front of it ended another wave knows (k_huf_fix drops the entry if the guess was right).  Nothing
-// is repaired here.  Units are drawn from a ticket (as in k_huf_emit); which lanes are to be looked at again leaves the
+// a wave's image takes another subsequence out of its lanes' registers
+template <int NDW, int S>
+__device__ __forceinline__ void col_put(uint32_t *col, const uint32_t *r)
+{
+	wave_lds_sync(); // (the image is free: the scans over what it held are through)
+#pragma unroll
+	for (int j = 0; j < NDW; j++)
+		col[j * S] = r[j];
+	wave_lds_sync();
+}
+
+// bit i of x -> bit 2 i
+__device__ __forceinline__ unsigned long long spread32(uint32_t x)
+{
+	unsigned long long v = x;
+	v = (v | v << 16) & 0x0000FFFF0000FFFFull;
+	v = (v | v << 8) & 0x00FF00FF00FF00FFull;
+	v = (v | v << 4) & 0x0F0F0F0F0F0F0F0Full;
+	v = (v | v << 2) & 0x3333333333333333ull;
+	v = (v | v << 1) & 0x5555555555555555ull;
+	return v;
+}
+
+// All tiles, first pass.  Persistent workgroups (the tables are loaded once); a wave's unit of work is half a tile,
+// and a lane takes two subsequences in a row, A and B: it runs up through the last half of B - where that crosses into
+// the right neighbour's A is that lane's guess of its first code's start - then through A from its own guess and
+// through B from where A ended.  One run-up for two subsequences, and B's start is no guess.  Subsequences whose start
+// is not where the subsequence in front ended go on the list of k_huf_fix (an A whose guess failed; a B only where A's
+// pass ran into bits that are no code), and so does every pair's first A, unchecked: where the subsequence in front
+// of it ended another wave knows (k_huf_fix drops the entry if the guess was right).  Nothing is repaired here.
+// Pairs of units are drawn from a ticket (as in k_huf_emit); which subsequences are to be looked at again leaves the
 // kernel as one 64-bit word per unit (DecodeArgs::hbits), from which k_huf_list makes k_huf_fix's list.
 template <int RU, bool TRIE>
 __global__ __launch_bounds__(WGS, 2 * HUF_SYNC_PER_CU * 2) void k_huf_sync(DecodeArgs a)
 {
 	constexpr int OWN = HufGeo<RU>::OWN, NDW = HufGeo<RU>::NDW;
+	constexpr int W = OWN / 32, NP = 2 * W + 1;        // dwords of a subsequence; of a lane's two and the reach behind them
 	constexpr int RUNUP = OWN * HUF_RUNUP_EIGHTHS / 8; // bits of the run-up (the last RUNUP bits of the subsequence in front)
 	constexpr int S = SYNC_S;
-	// the tables, then a wave's image: row j = dword j of [the subsequence in front, lane 0 .. lane 63]; two rows behind
+	constexpr uint32_t UP = HT / 128; // pairs of units a tile has
+	// the tables, then a wave's image: row j = dword j of the subsequence the lanes are scanning (A or B); two rows behind
 	// the last (len_scan reads the row behind a position's, and a code may reach 23 bits past the subsequence).  One
 	// struct: len_scan also reads the row IN FRONT of a position's (the biased position) - for row 0 that is the
 	// image in front, for the first image the tables: anything, as long as it is the workgroup's LDS
@@ -445,7 +527,7 @@ __global__ __launch_bounds__(WGS, 2 * HUF_SYNC_PER_CU * 2) void k_huf_sync(Decod
 	auto &imgs = lds.imgs;
 
 	const uint32_t n = min(uniform(a.ctl->nchunks), a.max_htiles);
-	const uint32_t nunits = n * (HT / 64);
+	const uint32_t nunits = n * UP; // (pairs of units)
 	const uint32_t lane = threadIdx.x & 63;
 	if (threadIdx.x == 0)
 		s_ticket = 0;
@@ -479,59 +561,79 @@ __global__ __launch_bounds__(WGS, 2 * HUF_SYNC_PER_CU * 2) void k_huf_sync(Decod
 		if (u >= nunits)
 			break;
 		HSTAMP(0); // ticket
-		const uint32_t k = u / (HT / 64);
-		const uint32_t tid = (u % (HT / 64)) * 64 + lane; // the lane's subsequence of the tile
+		const uint32_t k = u / UP;
+		const uint32_t tid = (u % UP) * 128 + 2 * lane; // A, the first of the lane's two subsequences of the tile; B = tid + 1
 		const HufTile *dp = a.htiles + k;
 		const uint32_t nbits_t = uniform(dp->nbits);
 		const uint32_t t = uniform(dp->t_last) & 0x7FFFFFFFu;
 		const uint8_t *src = a.in + dp->src;
 		const int32_t nby = (int32_t) ((nbits_t + 7) >> 3); // (nbits_t < 2^32: below 2^29 bytes)
-		const bool exact = t == 0 && tid < 64; // the unit's first lane starts the read's payload: its start is known
+		const bool exact = t == 0 && u % UP == 0; // the pair's first lane starts the read's payload: A's start is known
 
-		wave_lds_sync(); // (the image is free: the last unit's scans are through)
-		col_load<NDW, S>(col, src, (int32_t) tid * (OWN / 8), 0, nby);
-		wave_lds_sync();
+		// A's dwords, B's (the first of them A's reach) and B's reach: one batch of loads.  The image holds one
+		// subsequence at a time; the other waits in registers
+		uint32_t pay[NP];
+		pay_load<NP>(pay, src, (int32_t) tid * (OWN / 8), nby);
+		col_put<NDW, S>(col, pay + W);
 		HSTAMP(1); // descriptor + payload loads
-		// payload end in the coordinates of the own column
-		const uint32_t nb = clamp_nb((int64_t) nbits_t - (int64_t) tid * OWN);
+		// payload end in the coordinates of A's and B's column
+		const uint32_t nbA = clamp_nb((int64_t) nbits_t - (int64_t) tid * OWN);
+		const uint32_t nbB = clamp_nb((int64_t) nbits_t - (int64_t) (tid + 1) * OWN);
 
-		// ---- every lane runs through the END of its own subsequence: where that run crosses into the next
-		// subsequence is the right neighbour's guess of its first code's start.  (No lane reads another's column, and
-		// no bits in front of the unit are loaded: the unit's first lane has no guess - it starts at bit 0 and is
-		// listed unchecked as before; k_huf_fix decodes it again unless bit 0 happened to be right.  A second payload
-		// load for that one lane - a second memory round trip per unit - cost more than those repairs.)
-		uint32_t f, c0, c, dz, dv;
+		// ---- every lane runs through the END of its B: where that run crosses into the next subsequence is the right
+		// neighbour's guess of its A's first code's start.  (No lane reads another's column, and no bits in front of
+		// the pair are loaded: the pair's first lane has no guess - its A starts at bit 0 and is listed unchecked;
+		// k_huf_fix decodes it again unless bit 0 happened to be right.  A second payload load for that one lane - a
+		// second memory round trip per ticket - cost more than those repairs.)
+		uint32_t fA, c0, cA, cB, dz, dA, dB;
 		{
-			const uint32_t g = len_scan<TRIE, S>(col, &lds.tabs, a.huff, (uint32_t) (OWN - RUNUP), OWN, nb, c0, dz);
+			const uint32_t g = len_scan<TRIE, S>(col, &lds.tabs, a.huff, (uint32_t) (OWN - RUNUP), OWN, nbB, c0, dz);
 			const uint32_t gl = (uint32_t) __shfl_up((int) g, 1, 64); // the left neighbour's run
-			f = gl == HEND ? HEND : gl - OWN;
-			if (gl == HEND && nb > 0)
-				f = 0; // the run ended in the payload's last bits or in a bit pattern that is no code: any guess will do
+			fA = gl == HEND ? HEND : gl - OWN;
+			if (gl == HEND && nbA > 0)
+				fA = 0; // the run ended in the payload's last bits or in a bit pattern that is no code: any guess will do
 			if (lane == 0)
-				f = nb > 0 ? 0u : HEND;
+				fA = nbA > 0 ? 0u : HEND;
 		}
 		HSTAMP(2); // run-up
-		const uint32_t e = len_scan<TRIE, S>(col, &lds.tabs, a.huff, f, OWN, nb, c, dv);
-		HSTAMP(3); // own pass
-		const uint32_t e8 = e == HEND ? R_END : e - OWN;
-		const uint32_t cw = wave_scan(c), dw = wave_scan(dv);
-		// ---- whose guess is not where the neighbour ended
-		const uint32_t f8 = f == HEND ? R_END : f;
-		const uint32_t pe8 = (uint32_t) __shfl_up((int) e8, 1, 64);
-		const bool broken = lane ? f8 != pe8 : !exact;
-		const unsigned long long bm = __ballot(broken);
-		a.hrec[(uint64_t) k * HT + tid] = pack_rec(f, c, dv);
-		a.hend[(uint64_t) k * HT + tid] = (uint8_t) e8;
-		// per unit: the wave's totals (k_huf_fix adds what its repairs change) and the lanes to be looked at again, one
-		// 64-bit word from which k_huf_list makes the dense list of k_huf_fix's first round.  (A list written here -
-		// slots taken 128 at a time per wave, a few scattered stores per unit - cost this kernel 80 us of its 600.
-		// Both stores by lane 63: a store by lane 0 at the end of the loop body was merged by the compiler with the
-		// ticket code of lane 0 at its top, across the wave-uniform read of the ticket - the loop never ended.)
-		if (lane == 63) {
-			a.hwave[u] = make_uint2(cw, dw & 0xFFFFu);
-			a.hbits[u] = bm;
+		col_put<NDW, S>(col, pay);
+		// (two scans with their own accumulators: 128 four-bit codes are more than the one-register accumulator counts)
+		const uint32_t eA = len_scan<TRIE, S>(col, &lds.tabs, a.huff, fA, OWN, nbA, cA, dA);
+		HSTAMP(3); // own pass A
+		// B starts where A ended - unless A's pass ended in bits that are no code (or in a payload's last bits) while B
+		// has payload bits: then any guess will do, and B is listed
+		uint32_t fB = eA == HEND ? HEND : eA - OWN;
+		if (eA == HEND && nbB > 0)
+			fB = 0;
+		col_put<NDW, S>(col, pay + W);
+		const uint32_t eB = len_scan<TRIE, S>(col, &lds.tabs, a.huff, fB, OWN, nbB, cB, dB);
+		HSTAMP(4); // own pass B
+		const uint32_t eA8 = eA == HEND ? R_END : eA - OWN, eB8 = eB == HEND ? R_END : eB - OWN;
+		const uint32_t cw = wave_scan(cA + cB), dw = wave_scan(dA + dB);
+		// ---- whose start is not where the subsequence in front ended
+		const uint32_t fA8 = fA == HEND ? R_END : fA, fB8 = fB == HEND ? R_END : fB;
+		const uint32_t pe8 = (uint32_t) __shfl_up((int) eB8, 1, 64);
+		const unsigned long long bmA = __ballot(lane ? fA8 != pe8 : !exact), bmB = __ballot(fB8 != eA8);
+		// (tid is even: a lane's two records are one 8-byte store, its two ends one 2-byte store)
+		const uint64_t ri = (uint64_t) k * HT + tid;
+		*reinterpret_cast<uint2 *>(a.hrec + ri) = make_uint2(pack_rec(fA, cA, dA), pack_rec(fB, cB, dB));
+		*reinterpret_cast<uint16_t *>(a.hend + ri) = (uint16_t) (eA8 | (eB8 << 8));
+		// per unit (64 subsequences: lanes 0 .. 31 are the pair's first, lanes 32 .. 63 its second): the totals (k_huf_fix
+		// adds what its repairs change) and the subsequences to be looked at again, one 64-bit word (bit 2 l: lane l's A,
+		// bit 2 l + 1: its B) from which k_huf_list makes the dense list of k_huf_fix's first round.  (A list written
+		// here - slots taken 128 at a time per wave, a few scattered stores per unit - cost this kernel 80 us of its 600.
+		// Both stores by lanes 31 and 63, each its unit's: a store by lane 0 at the end of the loop body was merged by
+		// the compiler with the ticket code of lane 0 at its top, across the wave-uniform read of the ticket - the loop
+		// never ended.)
+		const uint32_t cw31 = (uint32_t) __shfl((int) cw, 31, 64), dw31 = (uint32_t) __shfl((int) dw, 31, 64);
+		if ((lane & 31u) == 31u) {
+			const bool hi = lane == 63;
+			const uint32_t uu = 2 * u + (hi ? 1u : 0u);
+			a.hwave[uu] = make_uint2(hi ? cw - cw31 : cw, (hi ? dw - dw31 : dw) & 0xFFFFu);
+			a.hbits[uu] = hi ? spread32((uint32_t) (bmA >> 32)) | spread32((uint32_t) (bmB >> 32)) << 1
+					 : spread32((uint32_t) bmA) | spread32((uint32_t) bmB) << 1;
 		}
-		HSTAMP(4); // records, list
+		HSTAMP(5); // records, list
 	}
 	HSTAMP_FLUSH(0);
 }
@@ -598,6 +700,10 @@ __global__ __launch_bounds__(FIX_WG) void k_huf_fix(DecodeArgs a, int round, int
 	const uint32_t *in_cnt = round ? &a.ctl->lists[round - 1] : &a.ctl->ticket2;
 	uint32_t *out_cnt = &a.ctl->lists[round]; // (zero since the control block was cleared)
 	const uint32_t n = min(uniform(*in_cnt), a.hlist_cap);
+#ifdef HUF_STAMPS
+	if (blockIdx.x == 0 && threadIdx.x == 0)
+		g_hstamp[16 + (round & 7)] = n; // (the length of this round's list of the last call: tools/hufstamps.py)
+#endif
 	if ((uint32_t) FIX_WG * blockIdx.x >= n)
 		return;
 	const uint32_t lane = threadIdx.x & 63;
@@ -606,7 +712,7 @@ __global__ __launch_bounds__(FIX_WG) void k_huf_fix(DecodeArgs a, int round, int
 	uint32_t *col = imgs[threadIdx.x >> 6] + lane;
 	for (uint32_t i0 = FIX_WG * blockIdx.x + (threadIdx.x & ~63u); i0 < n; i0 += (uint32_t) FIX_WG * gridDim.x) {
 		uint32_t ent = i0 + lane < n ? in_list[i0 + lane] : LIST_NONE;
-		// (k_huf_sync lists the first lane of every quarter tile unchecked: most of them started where the
+		// (k_huf_sync lists the first lane of every half tile unchecked: most of them started where the
 		// subsequence in front ended - nothing to do)
 		if (ent != LIST_NONE && (a.hrec[ent] & 0xFFu) == a.hend[ent - 1])
 			ent = LIST_NONE;
@@ -731,6 +837,7 @@ __global__ __launch_bounds__(HT) void k_huf_chain(DecodeArgs a)
 	constexpr uint32_t UPT = HT / 64;                 // units per tile
 	__shared__ uint32_t s_w[HT / 64], s_wd[HT / 64];
 	__shared__ unsigned long long s_cum;
+	__shared__ uint32_t s_stop, s_refuse;
 
 	const uint32_t r = blockIdx.x;
 	const uint32_t tid = threadIdx.x;
@@ -740,8 +847,11 @@ __global__ __launch_bounds__(HT) void k_huf_chain(DecodeArgs a)
 	const uint32_t nu = nt * UPT;
 	const uint2 *hw = a.hwave + (uint64_t) k0 * UPT;
 	// all codes of the read: the unit plans below need what it delivers
-	if (tid == 0)
+	if (tid == 0) {
 		s_cum = 0;
+		s_stop = 0xFFFFFFFFu;
+		s_refuse = 0;
+	}
 	__syncthreads();
 	{
 		uint64_t c = 0;
@@ -781,10 +891,49 @@ __global__ __launch_bounds__(HT) void k_huf_chain(DecodeArgs a)
 	__syncthreads(); // (s_cum; and the exceptions' prefixes are read by other threads below)
 	const uint64_t cumall = s_cum;
 	const uint32_t nlow = cumall < want ? (uint32_t) cumall : want; // what huffman_decode_memory delivered
+	// Fewer codes than the header announces: did they run out with the payload - the read stands with what it has - or
+	// in bits that are no code, where the reference's walk leaves its tree (the oracle refuses the read)?  The scans end
+	// a subsequence the same way in both cases (HEND), so the first subsequence without an end is walked once more,
+	// from its first code on bit by bit through the trie: a walk that leaves the tree inside the payload refuses the
+	// read (ReadMeta::status; k_chunk_prep_meta makes that its out_n).  Rare - a stream cut short or damaged - and
+	// one thread's work of at most a subsequence and a code.
+	if (cumall < want) { // (the same for every thread of the workgroup)
+		constexpr uint32_t OWN = HufGeo<RU>::OWN;
+		const uint64_t nbits0 = a.htiles[k0].nbits;
+		const uint64_t nsub64 = (nbits0 + OWN - 1) / OWN;
+		const uint32_t nsub = nsub64 < (uint64_t) nt * HT ? (uint32_t) nsub64 : nt * HT;
+		const uint8_t *he = a.hend + (uint64_t) k0 * HT;
+		for (uint32_t i = tid; i < nsub; i += HT)
+			if (he[i] == R_END) {
+				atomicMin(&s_stop, i);
+				break;
+			}
+		__syncthreads();
+		if (tid == 0 && s_stop != 0xFFFFFFFFu) {
+			const uint32_t f = a.hrec[(uint64_t) k0 * HT + s_stop] & 0xFFu;
+			if (f != R_END) {
+				const HuffDev *hd = a.huff;
+				const uint8_t *pay = a.in + a.htiles[k0].src;
+				uint64_t p = (uint64_t) s_stop * OWN + f;
+				int node = 0;
+				for (uint32_t i = 0; i < OWN + 64 && p < nbits0; i++, p++) {
+					node = hd->child[node][(pay[p >> 3] >> (p & 7)) & 1u];
+					if (node < 0) {
+						s_refuse = 1;
+						break;
+					}
+					if (hd->leaf[node] >= 0)
+						node = 0;
+				}
+			}
+		}
+		__syncthreads();
+	}
+	const bool refused = s_refuse != 0;
 	// k_huf_emit writes the samples itself if the lists interleave into exactly 1 + nlow + nex samples:
 	// every exception sits among (or right behind) the delivered values.  (k_chunk_prep_meta refuses a read that is not
 	// fused for the complement of this condition: the two lines go together.)
-	const bool fused = nlow >= 1 && (nex == 0 || pos[nex - 1] < nlow + nex);
+	const bool fused = !refused && nlow >= 1 && (nex == 0 || pos[nex - 1] < nlow + nex);
 	const uint32_t zd0 = uniform(a.meta[r].zd0) & 0xFFFFu, q = uniform(a.meta[r].q);
 	// the tiles of a read are consecutive payload pieces (k_huff_tiles): unit u's payload starts u * UB bytes behind the
 	// first tile's
@@ -856,6 +1005,8 @@ __global__ __launch_bounds__(HT) void k_huf_chain(DecodeArgs a)
 	static_assert(HUF_U_QUOTA >= 64u * 255u, "a unit's quota");
 	if (tid == 0) {
 		a.meta[r].nlow = nlow;
+		if (refused)
+			a.meta[r].status = 1;
 		if (fused)
 			a.hread[2 * r + 1] = nt | HUF_FUSED;
 	}
