@@ -13,328 +13,13 @@ import os
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("PRESS_HIP_LIB", os.path.join(_HERE, "libpress_hip.so"))  # override: diagnostic builds
-TABLE_PATH = os.path.join(_HERE, "data", "NA12878_zd.huffman")
+from .abi import (HEADER_SYMBOLS, LIB_PATH, METHODS, RCF_CODERS, RCF_LAYOUTS, STALL_METHODS, _SYMS,  # noqa: F401
+                  PressError, load_library)
+from . import abi
 
-# include/press_hip.h enum press_hip_method
-METHODS = {
-    "svb12": 0, "svb12_zd": 1, "svb_zd": 2, "zstd_svb_zd": 3, "zstd_svb12_zd": 4,
-    "vbe21_zd": 5, "vbbe21_zd": 6, "vbsbe21_zd": 7, "vbsse21_zd": 8,
-    "shuffman_vbe21_zd": 9, "shuffman_vbbe21_zd": 10, "shuffman_vbsbe21_zd": 11,
-    "shuffman_vbsse21_zd": 12, "hasgam_vbsse21_zdq": 13, "zstd_hasgam_vbsse21_zdq": 14,
-    "slow5_svb_zd": 15, "rc_vbe21_zd": 16, "rcc_vbe21_zd": 17, "rccm_vbbe21_zd": 18,
-}
+TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "NA12878_zd.huffman")
 BATCH_METHODS = [m for m in METHODS if not m.startswith("zstd_")]
-# include/press_hip.h enum press_hip_stall_method: a family of its own (the generic batch calls do not take these ids)
-STALL_METHODS = {"rccm_svbbe21_zd": 0, "dstall_fz_1500": 1, "dstall_fz": 2}
-# include/press_hip.h enum press_hip_rcf_coder / press_hip_rcf_layout: the range-coder family, every coder on every
-# layout (ids of its own again; "rccdf" on "vbe21" is the reference's rccdf_vbe21_zd)
-RCF_CODERS = {"rc": 0, "rcc": 1, "rccm": 2, "rccdf": 3}
-RCF_LAYOUTS = {"vbe21": 0, "vbbe21": 1, "vbsbe21": 2, "vbsse21": 3}
 FAILED = (1 << 64) - 1
-
-# method -> (bound symbol, press symbol, depress symbol, calling convention)
-#   "svb"    void press(in, n, out, &nout64);  void depress(in, nsamples, out, &nout64)
-#   "svb_nz" as svb, depress without nout (svb12_depress)
-#   "vb"     void press(in, n32, out, &nout64); void depress(in, nbytes, out, &nout32)
-#   "int"    int press(...) ; int depress(in, nbytes, out, &nout32)
-#   "shuff"  int press(se, ...); int depress(root, ...)
-_SYMS = {
-    "svb12": ("svb12_bound", "svb12_press", "svb12_depress", "svb_nz"),
-    "svb12_zd": ("svb12_zd_bound", "svb12_zd_press", "svb12_zd_depress", "svb"),
-    "svb_zd": ("svb_zd_bound_16", "svb_zd_press_16", "svb_zd_depress_16", "svb"),
-    "zstd_svb_zd": ("zstd_svb_zd_bound_16", "zstd_svb_zd_press_16", "zstd_svb_zd_depress_16", "int"),
-    "zstd_svb12_zd": ("zstd_svb12_zd_bound", "zstd_svb12_zd_press", "zstd_svb12_zd_depress", "int"),
-    "vbe21_zd": ("vbe21_zd_bound_16", "vbe21_zd_press_16", "vbe21_zd_depress_16", "vb"),
-    "vbbe21_zd": ("vbbe21_zd_bound_16", "vbbe21_zd_press_16", "vbbe21_zd_depress_16", "vb"),
-    "vbsbe21_zd": ("vbsbe21_zd_bound_16", "vbsbe21_zd_press_16", "vbsbe21_zd_depress_16", "vb"),
-    "vbsse21_zd": ("vbsse21_zd_bound_16", "vbsse21_zd_press_16", "vbsse21_zd_depress_16", "vb"),
-    "shuffman_vbe21_zd": ("shuffman_vbe21_zd_bound_16", "shuffman_vbe21_zd_press_16",
-                          "shuffman_vbe21_zd_depress_16", "shuff"),
-    "shuffman_vbbe21_zd": ("shuffman_vbbe21_zd_bound_16", "shuffman_vbbe21_zd_press_16",
-                           "shuffman_vbbe21_zd_depress_16", "shuff"),
-    "shuffman_vbsbe21_zd": ("shuffman_vbsbe21_zd_bound_16", "shuffman_vbsbe21_zd_press_16",
-                            "shuffman_vbsbe21_zd_depress_16", "shuff"),
-    "shuffman_vbsse21_zd": ("shuffman_vbsse21_zd_bound_16", "shuffman_vbsse21_zd_press_16",
-                            "shuffman_vbsse21_zd_depress_16", "shuff"),
-    "hasgam_vbsse21_zdq": ("hasgam_vbsse21_zdq_bound_16", "hasgam_vbsse21_zdq_press_16",
-                           "hasgam_vbsse21_zdq_depress_16", "int"),
-    "zstd_hasgam_vbsse21_zdq": ("zstd_hasgam_vbsse21_zdq_bound_16", "zstd_hasgam_vbsse21_zdq_press_16",
-                                "zstd_hasgam_vbsse21_zdq_depress_16", "int"),
-    # BLOW5's signal codec (slow5lib svb-zd)
-    "slow5_svb_zd": ("slow5_svb_zd_bound", "slow5_svb_zd_press", "slow5_svb_zd_depress", "int"),
-    # vbe21 + order-0 range coder (one read per lane on the device)
-    "rc_vbe21_zd": ("rc_vbe21_zd_bound_16", "rc_vbe21_zd_press_16", "rc_vbe21_zd_depress_16", "vb"),
-    # ... order 1 (one read per workgroup)
-    "rcc_vbe21_zd": ("rcc_vbe21_zd_bound_16", "rcc_vbe21_zd_press_16", "rcc_vbe21_zd_depress_16", "vb"),
-    "rccm_vbbe21_zd": ("rccm_vbbe21_zd_bound_16", "rccm_vbbe21_zd_press_16", "rccm_vbbe21_zd_depress_16", "vb"),
-}
-
-# every symbol include/press_hip.h declares (checked by tests/test_abi_symbols.py)
-HEADER_SYMBOLS = sorted(set(
-    [s for t in _SYMS.values() for s in t[:3]] +
-    ["read_code_table", "build_symbol_encoder", "free_encoder", "free_huffman_tree",
-     "press_hip_last_error", "press_hip_set_device", "press_hip_set_stream", "press_hip_reset_stream",
-     "press_hip_get_stream",
-     "press_hip_synchronize", "press_hip_load_table_file", "press_hip_set_table", "press_hip_bound",
-     "press_hip_press_batch", "press_hip_depress_batch", "press_hip_workspace_bytes",
-     "press_hip_pa_cal", "press_hip_depress_pa_batch", "press_hip_depress_pa_fused",
-     "press_hip_depress_pa_workspace_bytes", "press_hip_blow5_next_pa",
-     "press_hip_signal_stats", "press_hip_norm_cal", "press_hip_depress_norm_batch",
-     "press_hip_depress_norm_workspace_bytes", "press_hip_signal_stats_timed",
-     "press_hip_signal_quantiles", "press_hip_scale_cal", "press_hip_chunk_plan", "press_hip_depress_chunks_batch",
-     "press_hip_depress_chunks_workspace_bytes",
-     "press_hip_recode_batch", "press_hip_recode_workspace_bytes", "press_hip_recode_fused",
-     "press_hip_recode_sizes", "press_hip_recode_packed", "press_hip_recode_packed_workspace_bytes",
-     "press_hip_press_sizes", "press_hip_press_packed", "press_hip_packed_exact", "press_hip_packed_workspace_bytes",
-     "press_hip_kernel_timing", "press_hip_kernel_times",
-     "press_hip_slow5_ptr_compress_svb_zd", "press_hip_slow5_ptr_depress_svb_zd",
-     "press_hip_blow5_open", "press_hip_blow5_close", "press_hip_blow5_methods", "press_hip_blow5_next",
-     "press_hip_blow5_last_error", "press_hip_blow5_next_records", "press_hip_blow5_create",
-     "press_hip_blow5_write", "press_hip_blow5_finish", "press_hip_blow5_write_batch", "press_hip_blow5_index",
-     "press_hip_blow5_threads",
-     "press_hip_shutdown", "press_hip_scratch_buffers", "press_hip_scratch_fill", "press_hip_host_alloc", "press_hip_host_free",
-     "press_hip_zstd_host_frames", "press_hip_symbol_counts", "press_hip_table_from_counts",
-     "press_hip_write_table_file",
-     "press_hip_crc32_combine", "press_hip_signal_crc32", "press_hip_depress_crc_batch", "press_hip_verify_batch",
-     "press_hip_verify_workspace_bytes",
-     "press_hip_degrade_value", "press_hip_degrade_batch", "press_hip_recode_degraded_batch",
-     "press_hip_recode_degraded_sizes", "press_hip_recode_degraded_packed", "press_hip_recode_degraded_workspace_bytes",
-     "press_hip_recode_degraded_packed_workspace_bytes", "press_hip_verify_degraded_batch",
-     "press_hip_event_params_preset", "press_hip_signal_events", "press_hip_signal_events_workspace_bytes",
-     "press_hip_events_serial_reads",
-     "press_hip_jnn_params_preset", "press_hip_jnn2_params_preset", "press_hip_signal_segments",
-     "press_hip_signal_segments_workspace_bytes", "press_hip_signal_adaptor",
-     "press_hip_signal_range_stats", "press_hip_prefix_params_preset", "press_hip_signal_prefix",
-     "press_hip_signal_prefix_workspace_bytes",
-     "press_hip_signal_tally", "press_hip_signal_tally_workspace_bytes",
-     "press_hip_stall_bound", "press_hip_stall_press_batch", "press_hip_stall_depress_batch",
-     "press_hip_stall_workspace_bytes",
-     "press_hip_rcf_bound", "press_hip_rcf_press_batch", "press_hip_rcf_depress_batch"] +
-    [m + s for m in STALL_METHODS for s in ("_bound_16", "_press_16", "_depress_16")] +
-    ["%s_%s_zd%s" % (c, l, s) for c in RCF_CODERS for l in RCF_LAYOUTS for s in ("_bound_16", "_press_16", "_depress_16")]))
-
-
-class PressError(RuntimeError):
-    pass
-
-
-_lib = None
-
-
-def load_library(path=LIB_PATH):
-    """dlopen libpress_hip.so (no GPU needed for that) - raises if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(path):
-            raise PressError("%s is not built: run `python -m honours_amd.build` "
-                             "(there is no CPU fallback)" % path)
-        _lib = ctypes.CDLL(path)
-        _lib.press_hip_last_error.restype = ctypes.c_char_p
-        _lib.press_hip_bound.restype = ctypes.c_uint64
-        _lib.press_hip_bound.argtypes = [ctypes.c_int, ctypes.c_uint32]
-        _lib.press_hip_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
-        _lib.press_hip_get_stream.restype = ctypes.c_void_p
-        _lib.press_hip_set_stream.argtypes = [ctypes.c_void_p]
-        _lib.press_hip_load_table_file.argtypes = [ctypes.c_char_p]
-        _lib.press_hip_press_batch.restype = ctypes.c_int
-        _lib.press_hip_press_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_depress_batch.restype = ctypes.c_int
-        _lib.press_hip_depress_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                                 ctypes.c_int]
-        _lib.press_hip_pa_cal.restype = ctypes.c_int
-        _lib.press_hip_pa_cal.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
-        _lib.press_hip_depress_pa_batch.restype = ctypes.c_int
-        _lib.press_hip_depress_pa_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                    ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                    ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_depress_pa_fused.restype = ctypes.c_int
-        _lib.press_hip_depress_pa_fused.argtypes = [ctypes.c_int]
-        _lib.press_hip_depress_pa_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_depress_pa_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
-        _lib.press_hip_signal_stats.restype = ctypes.c_int
-        _lib.press_hip_signal_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_event_params_preset.restype = ctypes.c_int
-        _lib.press_hip_event_params_preset.argtypes = [ctypes.c_int, ctypes.c_void_p]
-        _lib.press_hip_signal_events.restype = ctypes.c_int
-        _lib.press_hip_signal_events.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_signal_events_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_signal_events_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
-        _lib.press_hip_events_serial_reads.restype = ctypes.c_uint32
-        _lib.press_hip_events_serial_reads.argtypes = []
-        _lib.press_hip_jnn_params_preset.restype = ctypes.c_int
-        _lib.press_hip_jnn_params_preset.argtypes = [ctypes.c_int, ctypes.c_void_p]
-        _lib.press_hip_jnn2_params_preset.restype = ctypes.c_int
-        _lib.press_hip_jnn2_params_preset.argtypes = [ctypes.c_int, ctypes.c_void_p]
-        _lib.press_hip_signal_segments.restype = ctypes.c_int
-        _lib.press_hip_signal_segments.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_int]
-        _lib.press_hip_signal_segments_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_signal_segments_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
-        _lib.press_hip_signal_adaptor.restype = ctypes.c_int
-        _lib.press_hip_signal_adaptor.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_int]
-        _lib.press_hip_signal_range_stats.restype = ctypes.c_int
-        _lib.press_hip_signal_range_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                      ctypes.c_int]
-        _lib.press_hip_prefix_params_preset.restype = ctypes.c_int
-        _lib.press_hip_prefix_params_preset.argtypes = [ctypes.c_int, ctypes.c_void_p]
-        _lib.press_hip_signal_prefix.restype = ctypes.c_int
-        _lib.press_hip_signal_prefix.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_signal_prefix_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_signal_prefix_workspace_bytes.argtypes = [ctypes.c_uint32]
-        _lib.press_hip_stall_bound.restype = ctypes.c_uint64
-        _lib.press_hip_stall_bound.argtypes = [ctypes.c_int, ctypes.c_uint32]
-        _lib.press_hip_stall_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_stall_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
-        _lib.press_hip_stall_press_batch.restype = ctypes.c_int
-        _lib.press_hip_stall_press_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_stall_depress_batch.restype = ctypes.c_int
-        _lib.press_hip_stall_depress_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-                                                       ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_rcf_bound.restype = ctypes.c_uint64
-        _lib.press_hip_rcf_bound.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32]
-        _lib.press_hip_rcf_press_batch.restype = ctypes.c_int
-        _lib.press_hip_rcf_press_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_rcf_depress_batch.restype = ctypes.c_int
-        _lib.press_hip_rcf_depress_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
-        for m in list(STALL_METHODS) + ["%s_%s_zd" % (c, l) for c in RCF_CODERS for l in RCF_LAYOUTS]:
-            getattr(_lib, m + "_bound_16").restype = ctypes.c_uint64
-            getattr(_lib, m + "_bound_16").argtypes = [ctypes.c_uint32]
-            getattr(_lib, m + "_press_16").restype = None
-            getattr(_lib, m + "_press_16").argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                                                       ctypes.POINTER(ctypes.c_uint64)]
-            getattr(_lib, m + "_depress_16").restype = None
-            getattr(_lib, m + "_depress_16").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                                         ctypes.POINTER(ctypes.c_uint32)]
-        _lib.press_hip_signal_stats_timed.restype = ctypes.c_int
-        _lib.press_hip_signal_stats_timed.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-        _lib.press_hip_norm_cal.restype = ctypes.c_int
-        _lib.press_hip_norm_cal.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
-        _lib.press_hip_depress_norm_batch.restype = ctypes.c_int
-        _lib.press_hip_depress_norm_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_depress_norm_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_depress_norm_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
-        _lib.press_hip_signal_quantiles.restype = ctypes.c_int
-        _lib.press_hip_signal_quantiles.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                    ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                    ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_scale_cal.restype = ctypes.c_int
-        _lib.press_hip_scale_cal.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-        _lib.press_hip_chunk_plan.restype = ctypes.c_int
-        _lib.press_hip_chunk_plan.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        _lib.press_hip_depress_chunks_batch.restype = ctypes.c_int
-        _lib.press_hip_depress_chunks_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
-                                                        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_depress_chunks_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_depress_chunks_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
-                                                                  ctypes.c_uint32, ctypes.c_uint32]
-        _lib.press_hip_recode_batch.restype = ctypes.c_int
-        _lib.press_hip_recode_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_recode_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_recode_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32,
-                                                          ctypes.c_int]
-        _lib.press_hip_recode_fused.restype = ctypes.c_int
-        _lib.press_hip_recode_fused.argtypes = [ctypes.c_int, ctypes.c_int]
-        _lib.press_hip_press_sizes.restype = ctypes.c_int
-        _lib.press_hip_press_sizes.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_press_packed.restype = ctypes.c_int
-        _lib.press_hip_press_packed.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                                                ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_packed_exact.restype = ctypes.c_int
-        _lib.press_hip_packed_exact.argtypes = [ctypes.c_int]
-        _lib.press_hip_packed_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_packed_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
-        _lib.press_hip_recode_sizes.restype = ctypes.c_int
-        _lib.press_hip_recode_sizes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_recode_packed.restype = ctypes.c_int
-        _lib.press_hip_recode_packed.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
-                                                 ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_recode_packed_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_recode_packed_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
-                                                                 ctypes.c_uint32, ctypes.c_int]
-        _lib.press_hip_crc32_combine.restype = ctypes.c_uint32
-        _lib.press_hip_crc32_combine.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64]
-        _lib.press_hip_signal_crc32.restype = ctypes.c_int
-        _lib.press_hip_signal_crc32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_depress_crc_batch.restype = ctypes.c_int
-        _lib.press_hip_depress_crc_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        _lib.press_hip_verify_batch.restype = ctypes.c_int
-        _lib.press_hip_verify_batch.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_int]
-        _lib.press_hip_verify_workspace_bytes.restype = ctypes.c_uint64
-        _lib.press_hip_verify_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32]
-        _lib.press_hip_degrade_value.restype = ctypes.c_int16
-        _lib.press_hip_degrade_value.argtypes = [ctypes.c_int16, ctypes.c_uint32]
-        _lib.press_hip_degrade_batch.restype = ctypes.c_int
-        _lib.press_hip_degrade_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                                 ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int]
-        # the degraded forms: the undegraded argument lists with `bits` behind the method ids
-        for name, at in (("recode_batch", 2), ("recode_sizes", 2), ("recode_packed", 2), ("verify_batch", 1),
-                         ("recode_workspace_bytes", 2), ("recode_packed_workspace_bytes", 2)):
-            plain = getattr(_lib, "press_hip_" + name)
-            deg = getattr(_lib, "press_hip_" + name.replace("recode_", "recode_degraded_").replace("verify_", "verify_degraded_"))
-            deg.restype = plain.restype
-            deg.argtypes = plain.argtypes[:at] + [ctypes.c_uint32] + plain.argtypes[at:]
-        _lib.press_hip_debug_pass_a_launches.restype = ctypes.c_uint64
-        _lib.press_hip_debug_pass_a_launches.argtypes = []
-        libc = ctypes.CDLL(None)
-        libc.fopen.restype = ctypes.c_void_p
-        libc.fopen.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-        libc.fclose.argtypes = [ctypes.c_void_p]
-        libc.malloc.restype = ctypes.c_void_p
-        libc.malloc.argtypes = [ctypes.c_size_t]
-        _lib._libc = libc
-        _lib.read_code_table.restype = ctypes.c_bool
-        _lib.read_code_table.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
-                                         ctypes.POINTER(ctypes.c_uint)]
-        _lib.build_symbol_encoder.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        _lib.free_encoder.argtypes = [ctypes.c_void_p]
-        _lib.free_huffman_tree.argtypes = [ctypes.c_void_p]
-    return _lib
 
 
 def open_libzstd():
@@ -342,25 +27,33 @@ def open_libzstd():
     already holds comes first: a second copy of another version frees the first one's allocations and glibc aborts
     ("free(): invalid pointer" - round 2's rocprofv3 run); an absolute path only last, bound
     to itself (RTLD_DEEPBIND)."""
-    import os
     tries = [("libzstd.so.1", os.RTLD_NOW | os.RTLD_NOLOAD), ("libzstd.so.1", os.RTLD_NOW), ("libzstd.so", os.RTLD_NOW),
              ("/opt/conda/lib/libzstd.so.1", os.RTLD_NOW | os.RTLD_DEEPBIND)]
     for name, mode in tries:
         try:
-            z = ctypes.CDLL(name, mode=mode)
+            return abi.declare(ctypes.CDLL(name, mode=mode), abi.ZSTD)
         except OSError:
             continue
-        z.ZSTD_decompress.restype = ctypes.c_size_t
-        z.ZSTD_decompress.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
-        z.ZSTD_compress.restype = ctypes.c_size_t
-        z.ZSTD_compress.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        z.ZSTD_isError.argtypes = [ctypes.c_size_t]
-        return z
     return None
 
 
 def last_error():
     return load_library().press_hip_last_error().decode()
+
+
+def _call(name, *args):
+    """the library's `name`, which returns a status: raises what the library reports unless it is 0"""
+    if getattr(load_library(), name)(*args):
+        raise PressError(last_error())
+
+
+def _ptr(x):
+    """the address of a torch tensor, a numpy array or a ctypes structure; None for None"""
+    if x is None:
+        return None
+    if isinstance(x, np.ndarray):
+        return x.ctypes.data
+    return ctypes.addressof(x) if isinstance(x, ctypes.Structure) else x.data_ptr()
 
 
 def _mid(method):
@@ -417,86 +110,122 @@ def use_table(path=TABLE_PATH):
     load_table(path)
 
 
+def _press_16(name, sig, cap, table=None):
+    """the per-read symbol `name` (table: the encoder a shuffman_* symbol takes first) on one read, with a canary behind
+    the capacity -> (ret, bytes); ret as the reference returns it (void symbols: 0, or -1 when the library reports
+    *nout = 0)"""
+    sig = np.ascontiguousarray(sig, dtype=np.int16)
+    out = np.zeros(cap + 64, dtype=np.uint8)
+    out[cap:] = 0xA5  # canary: nothing may be written past the capacity
+    nout = ctypes.c_uint64(cap)
+    ret = getattr(load_library(), name)(*(() if table is None else (table,)), sig.ctypes.data, sig.size, out.ctypes.data,
+                                        ctypes.byref(nout))
+    if not np.all(out[cap:] == 0xA5):
+        raise PressError("%s wrote past its capacity" % name)
+    if ret is None:
+        ret = 0 if nout.value else -1
+    return ret, (out[: nout.value].tobytes() if ret == 0 else b"")
+
+
+def _depress_16(name, comp, nin, n, kind="vb", table=None):
+    """the per-read symbol `name` of calling convention `kind` (table: the tree a shuffman_* symbol takes first) on one
+    stream, nin what it is given as the input's size, with a canary behind the n samples -> (ret, int16 array)"""
+    buf = np.frombuffer(bytes(comp) + b"\0" * 64, dtype=np.uint8).copy()
+    out = np.zeros(n + 64, dtype=np.int16)
+    out[n:] = 0x5A5A
+    nout = (ctypes.c_uint64 if kind == "svb" else ctypes.c_uint32)(n)
+    args = (() if table is None else (table,)) + (buf.ctypes.data, nin, out.ctypes.data)
+    ret = getattr(load_library(), name)(*args, *(() if kind == "svb_nz" else (ctypes.byref(nout),)))
+    if not np.all(out[n:] == 0x5A5A):
+        raise PressError("%s wrote past the sample capacity" % name)
+    if ret is None:
+        ret = -1 if kind == "vb" and nout.value == 0 else 0
+    return ret, out[:nout.value].copy()
+
+
 def bound(method, n):
     """X_bound(n): what press/test.c mallocs for the compressed read."""
-    lib = load_library()
-    name = _SYMS[method][0]
-    fn = getattr(lib, name)
-    fn.restype = ctypes.c_uint64
-    fn.argtypes = [ctypes.c_uint64 if _SYMS[method][3] in ("svb", "svb_nz") else ctypes.c_uint32]
-    return int(fn(n))
+    return int(getattr(load_library(), _SYMS[method][0])(n))
 
 
 def press(method, sig, cap=None):
     """X_press through the drop-in symbol. -> (ret, bytes); ret as the reference returns it
     (void methods: 0, or -1 when the library reports *nout = 0)."""
-    lib = load_library()
     _, pname, _, kind = _SYMS[method]
-    sig = np.ascontiguousarray(sig, dtype=np.int16)
-    n = sig.size
-    cap = bound(method, n) + 1024 if cap is None else int(cap)
-    out = np.zeros(cap + 64, dtype=np.uint8)
-    out[cap:] = 0xA5  # canary: nothing may be written past the capacity
-    nout = ctypes.c_uint64(cap)
-    fn = getattr(lib, pname)
-    if kind in ("svb", "svb_nz", "vb"):
-        fn.restype = None
-        nt = ctypes.c_uint32 if (kind == "vb" or method == "svb12") else ctypes.c_uint64
-        fn.argtypes = [ctypes.c_void_p, nt, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
-        fn(sig.ctypes.data, n, out.ctypes.data, ctypes.byref(nout))
-        ret = 0 if nout.value else -1
-    elif kind == "int":
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
-        ret = fn(sig.ctypes.data, n, out.ctypes.data, ctypes.byref(nout))
-    else:
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-                       ctypes.POINTER(ctypes.c_uint64)]
-        ret = fn(default_table().se, sig.ctypes.data, n, out.ctypes.data, ctypes.byref(nout))
-    if not np.all(out[cap:] == 0xA5):
-        raise PressError("%s wrote past its capacity" % pname)
-    return ret, (out[: nout.value].tobytes() if ret == 0 else b"")
+    cap = bound(method, np.size(sig)) + 1024 if cap is None else int(cap)
+    return _press_16(pname, sig, cap, default_table().se if kind == "shuff" else None)
 
 
 def depress(method, comp, n):
     """X_depress through the drop-in symbol. -> (ret, int16 array)"""
-    lib = load_library()
     _, _, dname, kind = _SYMS[method]
-    buf = np.frombuffer(bytes(comp) + b"\0" * 64, dtype=np.uint8).copy()
-    out = np.zeros(n + 64, dtype=np.int16)
-    out[n:] = 0x5A5A
-    fn = getattr(lib, dname)
-    ret = 0
-    if kind == "svb_nz":
-        fn.restype = None
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
-        fn(buf.ctypes.data, n, out.ctypes.data)
-        got = n
-    elif kind == "svb":
-        fn.restype = None
-        nout = ctypes.c_uint64(n)
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
-        fn(buf.ctypes.data, n, out.ctypes.data, ctypes.byref(nout))
-        got = nout.value
-    else:
-        nout = ctypes.c_uint32(n)
-        if kind == "shuff":
-            fn.restype = ctypes.c_int
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                           ctypes.POINTER(ctypes.c_uint32)]
-            ret = fn(default_table().root, buf.ctypes.data, len(comp), out.ctypes.data, ctypes.byref(nout))
-        else:
-            fn.restype = None if kind == "vb" else ctypes.c_int
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
-            r = fn(buf.ctypes.data, len(comp), out.ctypes.data, ctypes.byref(nout))
-            ret = 0 if kind == "vb" else r
-        got = nout.value
-        if kind == "vb" and got == 0:
-            ret = -1
-    if not np.all(out[n:] == 0x5A5A):
-        raise PressError("%s wrote past the sample capacity" % dname)
-    return ret, out[:got].copy()
+    return _depress_16(dname, comp, n if kind in ("svb", "svb_nz") else len(comp), n, kind,
+                       default_table().root if kind == "shuff" else None)
+
+
+# ---------------------------------------------------------------------------- host buffers of the batch calls
+
+def _layout(ns):
+    """read starts padded to multiples of 8 samples -> (off uint64[nreads], total)"""
+    ns = np.asarray(ns, dtype=np.int64)
+    pad = (ns + 7) // 8 * 8
+    off = np.zeros(ns.size, dtype=np.uint64)
+    if ns.size > 1:
+        off[1:] = np.cumsum(pad)[:-1]
+    return off, int(pad.sum())
+
+
+def _host_batch(reads, alloc=np.zeros):
+    """a list of int16 arrays laid out by _layout in one arena from alloc(count, dtype), which returns zeros
+    -> (sig, off, ns uint32, total)"""
+    ns = np.array([len(r) for r in reads], dtype=np.uint32)
+    off, total = _layout(ns)
+    sig = alloc(total + 64, np.int16)
+    for r, o in zip(reads, off):
+        sig[int(o): int(o) + len(r)] = r
+    return sig, off, ns, total
+
+
+def _streams_arena(streams):
+    """a list of bytes end to end in one arena with 64 zero bytes behind -> (comp uint8, in_off uint64, in_len uint64)"""
+    nreads = len(streams)
+    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+    in_off = np.zeros(nreads, dtype=np.uint64)
+    if nreads > 1:
+        in_off[1:] = np.cumsum(in_len)[:-1]
+    return np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy(), in_off, in_len
+
+
+def _decode_batch(streams, ns):
+    """what every host decode form lays out: the streams' arena and the layout of the samples they decode to
+    -> (comp, in_off, in_len, ns uint32, off, total)"""
+    ns = np.asarray(ns, dtype=np.uint32)
+    return _streams_arena(streams) + (ns,) + _layout(ns)
+
+
+def _slots(caps):
+    """output slots of `caps` bytes, each rounded up to 16 -> out_off uint64[nreads + 1]"""
+    out_off = np.zeros(len(caps) + 1, dtype=np.uint64)
+    out_off[1:] = np.cumsum((np.asarray(caps, dtype=np.uint64) + 15) // 16 * 16)
+    return out_off
+
+
+def _streams_of(out, out_off, out_len):
+    """the streams a press call left in `out` -> list of bytes (None: the read failed)"""
+    return [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
+
+
+def _reads_of(buf, off, out_n):
+    """the reads a decode call left in `buf` -> list of array copies (None: the read failed)"""
+    return [None if int(k) == 0xFFFFFFFF else buf[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)]
+
+
+def _cal_pairs(cal, nreads, who):
+    """calibrations, (nreads, 2) or flat -> float32[2 * nreads]"""
+    cal = np.ascontiguousarray(cal, dtype=np.float32).reshape(-1)
+    if cal.size != 2 * nreads:
+        raise PressError("%s: two calibration floats per read" % who)
+    return cal
 
 
 # ---------------------------------------------------------------------------- batch API (torch CUDA tensors)
@@ -505,31 +234,20 @@ def use_torch_stream():
     """Make the batch calls enqueue on torch's current CUDA stream."""
     import torch
 
-    lib = load_library()
-    rc = lib.press_hip_set_device(torch.cuda.current_device())
-    if rc:
-        raise PressError(last_error())
-    rc = lib.press_hip_set_stream(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_set_device", torch.cuda.current_device())
+    _call("press_hip_set_stream", torch.cuda.current_stream().cuda_stream)
 
 
 def load_table(path=TABLE_PATH):
-    lib = load_library()
-    if lib.press_hip_load_table_file(path.encode()):
-        raise PressError(last_error())
+    _call("press_hip_load_table_file", path.encode())
 
 
 def press_batch(method, sig, off, n, out, out_off, out_len):
     """Enqueue the compression of a batch.  All arguments are CUDA tensors: sig int16,
     off int64 (nreads read starts, multiples of 8), n int32 (nreads sample counts),
     out uint8, out_off int64 (nreads+1 slot bounds), out_len int64 (nreads; -1 = failed)."""
-    lib = load_library()
-    nreads = off.numel()
-    rc = lib.press_hip_press_batch(_mid(method), sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads,
-                                   sig.numel(), out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_press_batch", _mid(method), _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(), _ptr(out),
+          _ptr(out_off), _ptr(out_len), 1)
 
 
 def press_sizes(method, sig, off, n):
@@ -538,13 +256,8 @@ def press_sizes(method, sig, off, n):
     Nothing is compressed."""
     import torch
 
-    lib = load_library()
-    nreads = off.numel()
-    need = torch.empty(nreads, dtype=torch.int64, device=sig.device)
-    rc = lib.press_hip_press_sizes(_mid(method), sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
-                                   need.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    need = torch.empty(off.numel(), dtype=torch.int64, device=sig.device)
+    _call("press_hip_press_sizes", _mid(method), _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(), _ptr(need), 1)
     return need
 
 
@@ -553,12 +266,8 @@ def press_packed(method, sig, off, n, out, out_off, out_len, align=1):
     as in press_batch, but out_off (int64, nreads+1) is WRITTEN: read r's stream is out[out_off[r] ..
     out_off[r] + out_len[r]), out_off[-1] is what the batch needs; out.numel() is the arena's capacity - a read
     that does not fit it gets out_len = -1 and is not written."""
-    lib = load_library()
-    nreads = off.numel()
-    rc = lib.press_hip_press_packed(_mid(method), sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
-                                    out.data_ptr(), out.numel(), int(align), out_off.data_ptr(), out_len.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_press_packed", _mid(method), _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(), _ptr(out),
+          out.numel(), int(align), _ptr(out_off), _ptr(out_len), 1)
 
 
 def packed_exact(method):
@@ -568,13 +277,8 @@ def packed_exact(method):
 
 def depress_batch(method, comp, in_off, in_len, sig, off, n, out_n):
     """Enqueue the decompression of a batch (CUDA tensors; out_n int32, -1 = failed)."""
-    lib = load_library()
-    nreads = off.numel()
-    rc = lib.press_hip_depress_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
-                                     nreads, sig.data_ptr(), off.data_ptr(), n.data_ptr(), sig.numel(),
-                                     out_n.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_depress_batch", _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), off.numel(), _ptr(sig),
+          _ptr(off), _ptr(n), sig.numel(), _ptr(out_n), 1)
 
 
 def pa_cal(dor):
@@ -582,21 +286,15 @@ def pa_cal(dor):
     {offset, range / digitisation} for depress_pa_batch (press_hip_pa_cal: host arithmetic, no GPU)"""
     dor = np.ascontiguousarray(dor, dtype=np.float64).reshape(-1, 3)
     cal = np.zeros((dor.shape[0], 2), dtype=np.float32)
-    if load_library().press_hip_pa_cal(dor.ctypes.data, dor.shape[0], cal.ctypes.data):
-        raise PressError(last_error())
+    _call("press_hip_pa_cal", _ptr(dor), dor.shape[0], _ptr(cal))
     return cal
 
 
 def depress_pa_batch(method, comp, in_off, in_len, pa, off, n, cal, out_n):
     """Enqueue the decompression of a batch straight to picoamperes (CUDA tensors as in depress_batch; pa float32 in
     the place of sig, cal float32 of 2 * nreads: pa_cal): pa[off[r] + i] = ((float) s[i] + cal[2r]) * cal[2r + 1]."""
-    lib = load_library()
-    nreads = off.numel()
-    rc = lib.press_hip_depress_pa_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), nreads,
-                                        pa.data_ptr(), off.data_ptr(), n.data_ptr(), pa.numel(), cal.data_ptr(),
-                                        out_n.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_depress_pa_batch", _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), off.numel(), _ptr(pa),
+          _ptr(off), _ptr(n), pa.numel(), _ptr(cal), _ptr(out_n), 1)
 
 
 def depress_pa_fused(method):
@@ -608,12 +306,8 @@ def signal_stats(sig, off, n, stats):
     """Enqueue the per-read median and MAD of a batch of samples (CUDA tensors: sig int16, off int64 read starts in
     multiples of 8 samples, n int32 sample counts, stats int32 of 2 * nreads): stats[2r] = the n[r] // 2-th smallest
     sample, stats[2r + 1] = the n[r] // 2-th smallest |sample - median| (press_hip_signal_stats)."""
-    nreads = off.numel()
-    if stats.numel() < 2 * nreads or stats.element_size() != 4 or not stats.is_contiguous():
-        raise PressError("stats must be a contiguous 32-bit tensor of 2 * nreads entries")
-    if load_library().press_hip_signal_stats(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
-                                             stats.data_ptr(), 1):
-        raise PressError(last_error())
+    _f32_pairs(stats, off.numel(), "stats")
+    _call("press_hip_signal_stats", _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(), _ptr(stats), 1)
 
 
 def norm_cal(stats):
@@ -621,8 +315,7 @@ def norm_cal(stats):
     calibration with which depress_pa_batch writes the normalised signal (press_hip_norm_cal: host arithmetic, no GPU)"""
     stats = np.ascontiguousarray(stats, dtype=np.int32).reshape(-1, 2)
     cal = np.zeros((stats.shape[0], 2), dtype=np.float32)
-    if load_library().press_hip_norm_cal(stats.ctypes.data, stats.shape[0], cal.ctypes.data):
-        raise PressError(last_error())
+    _call("press_hip_norm_cal", _ptr(stats), stats.shape[0], _ptr(cal))
     return cal
 
 
@@ -630,14 +323,10 @@ def depress_norm_batch(method, comp, in_off, in_len, out, off, n, out_n, stats=N
     """Enqueue the decompression of a batch straight to the normalised signal (CUDA tensors as in depress_pa_batch, out
     float32 in the place of pa): out[off[r] + i] = (s[i] - median) / (1.4826 * MAD) in signal_stats' and norm_cal's
     arithmetic over the read's decoded samples.  stats: int32 of 2 * nreads that receives {median, MAD}, or None."""
-    nreads = off.numel()
-    if stats is not None and (stats.numel() < 2 * nreads or stats.element_size() != 4 or not stats.is_contiguous()):
-        raise PressError("stats must be a contiguous 32-bit tensor of 2 * nreads entries")
-    rc = load_library().press_hip_depress_norm_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
-                                                     nreads, out.data_ptr(), off.data_ptr(), n.data_ptr(), out.numel(),
-                                                     None if stats is None else stats.data_ptr(), out_n.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    if stats is not None:
+        _f32_pairs(stats, off.numel(), "stats")
+    _call("press_hip_depress_norm_batch", _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), off.numel(), _ptr(out),
+          _ptr(off), _ptr(n), out.numel(), _ptr(stats), _ptr(out_n), 1)
 
 
 class ScaleRule(ctypes.Structure):
@@ -659,7 +348,7 @@ def _ranks(ranks):
 def _rule_ptr(rule):
     if rule is not None and not isinstance(rule, ScaleRule):
         raise PressError("rule must be a press.ScaleRule or None")
-    return None if rule is None else ctypes.addressof(rule)
+    return _ptr(rule)
 
 
 def signal_quantiles(sig, off, n, ranks, q):
@@ -670,20 +359,17 @@ def signal_quantiles(sig, off, n, ranks, q):
     num, den = _ranks(ranks)
     if q.numel() < num.size * nreads or q.element_size() != 4 or not q.is_contiguous():
         raise PressError("q must be a contiguous 32-bit tensor of len(ranks) * nreads entries")
-    if load_library().press_hip_signal_quantiles(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
-                                                 num.ctypes.data, den.ctypes.data, num.size, q.data_ptr(), 1):
-        raise PressError(last_error())
+    _call("press_hip_signal_quantiles", _ptr(sig), _ptr(off), _ptr(n), nreads, sig.numel(), _ptr(num), _ptr(den), num.size,
+          _ptr(q), 1)
 
 
 def signal_quantiles_host(reads, ranks):
     """quantiles of a list of int16 arrays (host buffers, synchronous) -> (nreads, len(ranks)) int32"""
-    lib = load_library()
     sig, off, ns, total = _host_batch(reads)
     num, den = _ranks(ranks)
     q = np.zeros((len(reads), num.size), dtype=np.int32)
-    if lib.press_hip_signal_quantiles(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, num.ctypes.data,
-                                      den.ctypes.data, num.size, q.ctypes.data, 0):
-        raise PressError(last_error())
+    _call("press_hip_signal_quantiles", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, _ptr(num), _ptr(den), num.size,
+          _ptr(q), 0)
     return q
 
 
@@ -692,24 +378,19 @@ def scale_cal(q, rule):
     which depress_pa_batch writes the scaled signal (press_hip_scale_cal: host arithmetic, no GPU)"""
     q = np.ascontiguousarray(q, dtype=np.int32).reshape(-1, 2)
     cal = np.zeros((q.shape[0], 2), dtype=np.float32)
-    if load_library().press_hip_scale_cal(q.ctypes.data, q.shape[0], _rule_ptr(rule), cal.ctypes.data):
-        raise PressError(last_error())
+    _call("press_hip_scale_cal", _ptr(q), q.shape[0], _rule_ptr(rule), _ptr(cal))
     return cal
 
 
 def chunk_plan(ns, T, overlap):
     """the rows of reads of ns samples cut into rows of T that overlap by `overlap` (press_hip_chunk_plan: host
     arithmetic, no GPU) -> (row_first uint64[nreads + 1], row_read uint32[rows], row_start uint32[rows])"""
-    lib = load_library()
     ns = np.ascontiguousarray(ns, dtype=np.uint32)
     row_first = np.zeros(ns.size + 1, dtype=np.uint64)
-    if lib.press_hip_chunk_plan(ns.ctypes.data, ns.size, int(T), int(overlap), row_first.ctypes.data, None, None):
-        raise PressError(last_error())
+    _call("press_hip_chunk_plan", _ptr(ns), ns.size, int(T), int(overlap), _ptr(row_first), None, None)
     row_read = np.zeros(int(row_first[-1]), dtype=np.uint32)
     row_start = np.zeros(int(row_first[-1]), dtype=np.uint32)
-    if lib.press_hip_chunk_plan(ns.ctypes.data, ns.size, int(T), int(overlap), row_first.ctypes.data, row_read.ctypes.data,
-                                row_start.ctypes.data):
-        raise PressError(last_error())
+    _call("press_hip_chunk_plan", _ptr(ns), ns.size, int(T), int(overlap), _ptr(row_first), _ptr(row_read), _ptr(row_start))
     return row_first, row_read, row_start
 
 
@@ -727,13 +408,9 @@ def depress_chunks_batch(method, comp, in_off, in_len, rows, row_first, off, n, 
         _f32_pairs(q, nreads, "q")
     if row_first.numel() < nreads + 1 or row_first.element_size() != 8:
         raise PressError("row_first must be a 64-bit tensor of nreads + 1 entries")
-    rc = load_library().press_hip_depress_chunks_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
-                                                       nreads, rows.data_ptr(), rows.shape[0], dt, rows.shape[1], int(overlap),
-                                                       row_first.data_ptr(), off.data_ptr(), n.data_ptr(), int(total_samples),
-                                                       _rule_ptr(rule), None if q is None else q.data_ptr(),
-                                                       out_n.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_depress_chunks_batch", _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), nreads, _ptr(rows),
+          rows.shape[0], dt, rows.shape[1], int(overlap), _ptr(row_first), _ptr(off), _ptr(n), int(total_samples),
+          _rule_ptr(rule), _ptr(q), _ptr(out_n), 1)
 
 
 def degrade(samples, bits):
@@ -758,33 +435,30 @@ def degrade_batch(sig, off, n, bits, out=None):
     """Enqueue D_bits over a batch of reads (CUDA tensors as in press_batch); out: an int16 tensor laid out as sig, or
     None: in place.  Only [off[r], off[r] + n[r]) of out is written."""
     out = sig if out is None else out
-    rc = load_library().press_hip_degrade_batch(sig.data_ptr(), off.data_ptr(), n.data_ptr(), off.numel(), sig.numel(),
-                                                int(bits), out.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_degrade_batch", _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(), int(bits), _ptr(out), 1)
 
 
 def degrade_batch_host(reads, bits):
     """D_bits with host buffers: reads = list of int16 arrays -> list of int16 arrays"""
-    lib = load_library()
-    nreads = len(reads)
     sig, off, ns, total = _host_batch(reads)
     out = np.zeros(total + 64, dtype=np.int16)
-    if lib.press_hip_degrade_batch(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total, int(bits),
-                                   out.ctypes.data, 0):
-        raise PressError(last_error())
-    return [out[int(o): int(o) + int(k)].copy() for o, k in zip(off, ns)]
+    _call("press_hip_degrade_batch", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, int(bits), _ptr(out), 0)
+    return _reads_of(out, off, ns)
 
 
-def _degraded(lib, name, bits):
-    """press_hip_<name> for bits == 0 - the existing entry point, untouched - else its degraded form with `bits` bound
-    behind the `at` leading method ids"""
-    bits = int(bits)
-    if bits == 0:
-        return getattr(lib, "press_hip_" + name)
-    at = 1 if name.startswith("verify") else 2
-    fn = getattr(lib, "press_hip_" + name.replace("recode_", "recode_degraded_").replace("verify_", "verify_degraded_"))
-    return lambda *a: fn(*(a[:at] + (bits,) + a[at:]))
+def _call_degraded(name, bits, *args):
+    """_call of press_hip_<name> for bits == 0 - the existing entry point, untouched - else of its degraded form with
+    `bits` behind the leading method ids"""
+    if int(bits) == 0:
+        return _call("press_hip_" + name, *args)
+    deg, at = abi.DEGRADED[name]
+    _call("press_hip_" + deg, *args[:at], int(bits), *args[at:])
+
+
+def _recode_total(who, sig, total_samples):
+    if sig is None and total_samples is None:
+        raise PressError("%s without sig needs total_samples" % who)
+    return sig.numel() if total_samples is None else int(total_samples)
 
 
 def recode_batch(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, out_n, sig=None, total_samples=None,
@@ -793,16 +467,9 @@ def recode_batch(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len, 
     press_batch).  sig: the int16 tensor that also receives the decoded samples, or None - they then stay in library
     scratch and total_samples (the extent of the layout off / n) must be given.  degrade_bits > 0: the streams hold
     D_bits of the decoded samples, and sig receives those (press_hip_recode_degraded_batch)."""
-    lib = load_library()
-    nreads = off.numel()
-    if sig is None and total_samples is None:
-        raise PressError("recode_batch without sig needs total_samples")
-    total = sig.numel() if total_samples is None else int(total_samples)
-    rc = _degraded(lib, "recode_batch", degrade_bits)(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
-                                    n.data_ptr(), off.data_ptr(), nreads, total, out.data_ptr(), out_off.data_ptr(),
-                                    out_len.data_ptr(), None if sig is None else sig.data_ptr(), out_n.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    total = _recode_total("recode_batch", sig, total_samples)
+    _call_degraded("recode_batch", degrade_bits, _mid(src), _mid(dst), _ptr(comp), _ptr(in_off), _ptr(in_len), _ptr(n),
+                   _ptr(off), off.numel(), total, _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(sig), _ptr(out_n), 1)
 
 
 def recode_sizes(src, dst, comp, in_off, in_len, n, off, out_n, sig=None, total_samples=None, degrade_bits=0):
@@ -811,17 +478,10 @@ def recode_sizes(src, dst, comp, in_off, in_len, n, off, out_n, sig=None, total_
     sig receive what the decode of `src` gives; no stream is written."""
     import torch
 
-    lib = load_library()
-    nreads = off.numel()
-    if sig is None and total_samples is None:
-        raise PressError("recode_sizes without sig needs total_samples")
-    total = sig.numel() if total_samples is None else int(total_samples)
-    need = torch.empty(nreads, dtype=torch.int64, device=comp.device)
-    rc = _degraded(lib, "recode_sizes", degrade_bits)(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
-                                    n.data_ptr(), off.data_ptr(), nreads, total, need.data_ptr(),
-                                    None if sig is None else sig.data_ptr(), out_n.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    total = _recode_total("recode_sizes", sig, total_samples)
+    need = torch.empty(off.numel(), dtype=torch.int64, device=comp.device)
+    _call_degraded("recode_sizes", degrade_bits, _mid(src), _mid(dst), _ptr(comp), _ptr(in_off), _ptr(in_len), _ptr(n),
+                   _ptr(off), off.numel(), total, _ptr(need), _ptr(sig), _ptr(out_n), 1)
     return need
 
 
@@ -830,17 +490,10 @@ def recode_packed(src, dst, comp, in_off, in_len, n, off, out, out_off, out_len,
     """Enqueue the recoding of a batch into an arena the library lays out (press_hip_recode_packed).  CUDA tensors as
     in recode_batch, but out_off (int64, nreads+1) is WRITTEN, as by press_packed: out_off[-1] is what the batch needs,
     out.numel() the arena's capacity.  A read whose source stream is refused takes no byte."""
-    lib = load_library()
-    nreads = off.numel()
-    if sig is None and total_samples is None:
-        raise PressError("recode_packed without sig needs total_samples")
-    total = sig.numel() if total_samples is None else int(total_samples)
-    rc = _degraded(lib, "recode_packed", degrade_bits)(_mid(src), _mid(dst), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
-                                     n.data_ptr(), off.data_ptr(), nreads, total, out.data_ptr(), out.numel(), int(align),
-                                     out_off.data_ptr(), out_len.data_ptr(), None if sig is None else sig.data_ptr(),
-                                     out_n.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    total = _recode_total("recode_packed", sig, total_samples)
+    _call_degraded("recode_packed", degrade_bits, _mid(src), _mid(dst), _ptr(comp), _ptr(in_off), _ptr(in_len), _ptr(n),
+                   _ptr(off), off.numel(), total, _ptr(out), out.numel(), int(align), _ptr(out_off), _ptr(out_len),
+                   _ptr(sig), _ptr(out_n), 1)
 
 
 def recode_fused(src, dst):
@@ -851,8 +504,7 @@ def recode_fused(src, dst):
 def scratch_fill(byte):
     """test aid: set every scratch buffer of the library but the static-Huffman table, and its page-locked staging
     buffers, to `byte` (press_hip_scratch_fill): a later call's result must not depend on it"""
-    if load_library().press_hip_scratch_fill(int(byte) & 0xFF):
-        raise PressError(last_error())
+    _call("press_hip_scratch_fill", int(byte) & 0xFF)
 
 
 def pass_a_launches():
@@ -860,35 +512,29 @@ def pass_a_launches():
     return int(load_library().press_hip_debug_pass_a_launches())
 
 
+def _packed_arena(need, align):
+    """what the streams of `need` bytes (FAILED: none) take, each rounded up to `align` -> (cap, a uint8 arena of cap + 64)"""
+    step = np.where(need == np.uint64(FAILED), np.uint64(0), need)
+    cap = int(((step + np.uint64(align - 1)) // np.uint64(align) * np.uint64(align)).sum())
+    return cap, np.zeros(cap + 64, dtype=np.uint8)  # (+ 64: what a later depress_batch may read behind the last stream)
+
+
 def recode_batch_host(src, dst, streams, ns, caps=None, want_samples=False, degrade_bits=0):
     """Recode with host buffers: streams = list of bytes of method `src`, ns = sample counts / rooms ->
     list of bytes of method `dst` (None: the read failed); with want_samples -> (streams, list of int16 arrays)."""
-    lib = load_library()
     nreads = len(streams)
-    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
-    in_off = np.zeros(nreads, dtype=np.uint64)
-    if nreads > 1:
-        in_off[1:] = np.cumsum(in_len)[:-1]
-    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
-    ns = np.asarray(ns, dtype=np.uint32)
-    off, total = _layout(ns)
+    comp, in_off, in_len, ns, off, total = _decode_batch(streams, ns)
     if caps is None:
-        caps = [int(lib.press_hip_bound(_mid(dst), int(x))) + 1024 if x else 64 for x in ns]
-    out_off = np.zeros(nreads + 1, dtype=np.uint64)
-    out_off[1:] = np.cumsum((np.asarray(caps, dtype=np.uint64) + 15) // 16 * 16)
+        caps = [int(load_library().press_hip_bound(_mid(dst), int(x))) + 1024 if x else 64 for x in ns]
+    out_off = _slots(caps)
     out = np.zeros(int(out_off[-1]) + 64, dtype=np.uint8)
     out_len = np.zeros(nreads, dtype=np.uint64)
     out_n = np.zeros(nreads, dtype=np.uint32)
     sig = np.zeros(total + 64, dtype=np.int16) if want_samples else None
-    rc = _degraded(lib, "recode_batch", degrade_bits)(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
-                                    ns.ctypes.data, off.ctypes.data, nreads, total, out.ctypes.data, out_off.ctypes.data,
-                                    out_len.ctypes.data, sig.ctypes.data if want_samples else None, out_n.ctypes.data, 0)
-    if rc:
-        raise PressError(last_error())
-    res = [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
-    if not want_samples:
-        return res
-    return res, [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)]
+    _call_degraded("recode_batch", degrade_bits, _mid(src), _mid(dst), _ptr(comp), _ptr(in_off), _ptr(in_len), _ptr(ns),
+                   _ptr(off), nreads, total, _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(sig), _ptr(out_n), 0)
+    res = _streams_of(out, out_off, out_len)
+    return (res, _reads_of(sig, off, out_n)) if want_samples else res
 
 
 def recode_packed_host(src, dst, streams, ns, align=1, want_samples=False, degrade_bits=0):
@@ -896,77 +542,35 @@ def recode_packed_host(src, dst, streams, ns, align=1, want_samples=False, degra
     (list of bytes of method `dst` / None, arena bytes); with want_samples -> (streams, arena bytes, list of int16
     arrays).  No capacities: press_hip_recode_sizes gives the arena's size, so it is as large as the streams, not as a
     bound.  As with press_packed_host the convenience costs the front of the chain twice (here the decode too)."""
-    lib = load_library()
     nreads = len(streams)
-    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
-    in_off = np.zeros(nreads, dtype=np.uint64)
-    if nreads > 1:
-        in_off[1:] = np.cumsum(in_len)[:-1]
-    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
-    ns = np.asarray(ns, dtype=np.uint32)
-    off, total = _layout(ns)
+    comp, in_off, in_len, ns, off, total = _decode_batch(streams, ns)
     need = np.zeros(nreads, dtype=np.uint64)
     out_n = np.zeros(nreads, dtype=np.uint32)
-    if _degraded(lib, "recode_sizes", degrade_bits)(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
-                                  ns.ctypes.data, off.ctypes.data, nreads, total, need.ctypes.data, None,
-                                  out_n.ctypes.data, 0):
-        raise PressError(last_error())
-    step = np.where(need == np.uint64(FAILED), np.uint64(0), need)
-    cap = int(((step + np.uint64(align - 1)) // np.uint64(align) * np.uint64(align)).sum())
-    out = np.zeros(cap + 64, dtype=np.uint8)  # (+ 64: what a later depress_batch may read behind the last stream)
+    _call_degraded("recode_sizes", degrade_bits, _mid(src), _mid(dst), _ptr(comp), _ptr(in_off), _ptr(in_len), _ptr(ns),
+                   _ptr(off), nreads, total, _ptr(need), None, _ptr(out_n), 0)
+    cap, out = _packed_arena(need, align)
     out_off = np.zeros(nreads + 1, dtype=np.uint64)
     out_len = np.zeros(nreads, dtype=np.uint64)
     sig = np.zeros(total + 64, dtype=np.int16) if want_samples else None
-    if _degraded(lib, "recode_packed", degrade_bits)(_mid(src), _mid(dst), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
-                                   ns.ctypes.data, off.ctypes.data, nreads, total, out.ctypes.data, cap, int(align),
-                                   out_off.ctypes.data, out_len.ctypes.data, sig.ctypes.data if want_samples else None,
-                                   out_n.ctypes.data, 0):
-        raise PressError(last_error())
-    res = [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
-    if not want_samples:
-        return res, int(out_off[-1])
-    return res, int(out_off[-1]), [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy()
-                                   for o, k in zip(off, out_n)]
-
-
-def _layout(ns):
-    """read starts padded to multiples of 8 samples -> (off uint64[nreads], total)"""
-    ns = np.asarray(ns, dtype=np.int64)
-    pad = (ns + 7) // 8 * 8
-    off = np.zeros(ns.size, dtype=np.uint64)
-    if ns.size > 1:
-        off[1:] = np.cumsum(pad)[:-1]
-    return off, int(pad.sum())
-
-
-def _host_batch(reads, alloc=np.zeros):
-    """a list of int16 arrays laid out by _layout in one arena from alloc(count, dtype), which returns zeros
-    -> (sig, off, ns uint32, total)"""
-    ns = np.array([len(r) for r in reads], dtype=np.uint32)
-    off, total = _layout(ns)
-    sig = alloc(total + 64, np.int16)
-    for r, o in zip(reads, off):
-        sig[int(o): int(o) + len(r)] = r
-    return sig, off, ns, total
+    _call_degraded("recode_packed", degrade_bits, _mid(src), _mid(dst), _ptr(comp), _ptr(in_off), _ptr(in_len), _ptr(ns),
+                   _ptr(off), nreads, total, _ptr(out), cap, int(align), _ptr(out_off), _ptr(out_len), _ptr(sig),
+                   _ptr(out_n), 0)
+    res = _streams_of(out, out_off, out_len)
+    return (res, int(out_off[-1]), _reads_of(sig, off, out_n)) if want_samples else (res, int(out_off[-1]))
 
 
 def press_batch_host(method, reads, caps=None):
     """Batch call with host buffers: reads = list of int16 arrays -> list of bytes / None."""
-    lib = load_library()
     nreads = len(reads)
     sig, off, ns, total = _host_batch(reads)
     if caps is None:
-        caps = [int(lib.press_hip_bound(_mid(method), int(x))) + 1024 for x in ns]
-    out_off = np.zeros(nreads + 1, dtype=np.uint64)
-    out_off[1:] = np.cumsum((np.asarray(caps, dtype=np.uint64) + 15) // 16 * 16)
+        caps = [int(load_library().press_hip_bound(_mid(method), int(x))) + 1024 for x in ns]
+    out_off = _slots(caps)
     out = np.zeros(int(out_off[-1]) + 64, dtype=np.uint8)
     out_len = np.zeros(nreads, dtype=np.uint64)
-    rc = lib.press_hip_press_batch(_mid(method), sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads,
-                                   total, out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, 0)
-    if rc:
-        raise PressError(last_error())
-    return [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes()
-            for o, l in zip(out_off[:-1], out_len)]
+    _call("press_hip_press_batch", _mid(method), _ptr(sig), _ptr(off), _ptr(ns), nreads, total, _ptr(out), _ptr(out_off),
+          _ptr(out_len), 0)
+    return _streams_of(out, out_off, out_len)
 
 
 def press_packed_host(method, reads, align=1):
@@ -976,94 +580,50 @@ def press_packed_host(method, reads, align=1):
     the chain (the svb counting pass, pass A, the zstd inner encode) runs in the sizes call and again in the packed call.
     A caller who minds calls press_hip_press_packed once with a guessed out_cap and again only where out_off[nreads]
     exceeds it."""
-    lib = load_library()
     nreads = len(reads)
     sig, off, ns, total = _host_batch(reads)
     need = np.zeros(nreads, dtype=np.uint64)
-    if lib.press_hip_press_sizes(_mid(method), sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total,
-                                 need.ctypes.data, 0):
-        raise PressError(last_error())
-    step = np.where(need == np.uint64(FAILED), np.uint64(0), need)
-    cap = int(((step + np.uint64(align - 1)) // np.uint64(align) * np.uint64(align)).sum())
-    out = np.zeros(cap + 64, dtype=np.uint8)  # (+ 64: what a later depress_batch may read behind the last stream)
+    _call("press_hip_press_sizes", _mid(method), _ptr(sig), _ptr(off), _ptr(ns), nreads, total, _ptr(need), 0)
+    cap, out = _packed_arena(need, align)
     out_off = np.zeros(nreads + 1, dtype=np.uint64)
     out_len = np.zeros(nreads, dtype=np.uint64)
-    if lib.press_hip_press_packed(_mid(method), sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total,
-                                  out.ctypes.data, cap, int(align), out_off.ctypes.data, out_len.ctypes.data, 0):
-        raise PressError(last_error())
-    return [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes()
-            for o, l in zip(out_off[:-1], out_len)], int(out_off[-1])
+    _call("press_hip_press_packed", _mid(method), _ptr(sig), _ptr(off), _ptr(ns), nreads, total, _ptr(out), cap, int(align),
+          _ptr(out_off), _ptr(out_len), 0)
+    return _streams_of(out, out_off, out_len), int(out_off[-1])
 
 
 def depress_batch_host(method, streams, ns):
     """Batch decode with host buffers: streams = list of bytes, ns = sample counts / capacities."""
-    lib = load_library()
-    nreads = len(streams)
-    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
-    in_off = np.zeros(nreads, dtype=np.uint64)
-    if nreads > 1:
-        in_off[1:] = np.cumsum(in_len)[:-1]
-    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
-    ns = np.asarray(ns, dtype=np.uint32)
-    off, total = _layout(ns)
+    comp, in_off, in_len, ns, off, total = _decode_batch(streams, ns)
     sig = np.zeros(total + 64, dtype=np.int16)
-    out_n = np.zeros(nreads, dtype=np.uint32)
-    rc = lib.press_hip_depress_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
-                                     nreads, sig.ctypes.data, off.ctypes.data, ns.ctypes.data, total,
-                                     out_n.ctypes.data, 0)
-    if rc:
-        raise PressError(last_error())
-    return [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy()
-            for o, k in zip(off, out_n)]
+    out_n = np.zeros(len(streams), dtype=np.uint32)
+    _call("press_hip_depress_batch", _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), len(streams), _ptr(sig),
+          _ptr(off), _ptr(ns), total, _ptr(out_n), 0)
+    return _reads_of(sig, off, out_n)
 
 
 def depress_pa_batch_host(method, streams, ns, cals):
     """Batch decode to picoamperes with host buffers: streams = list of bytes, ns = sample counts / capacities,
     cals = (nreads, 2) float32 (pa_cal) -> list of float32 arrays (None: the read failed)."""
-    lib = load_library()
-    nreads = len(streams)
-    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
-    in_off = np.zeros(nreads, dtype=np.uint64)
-    if nreads > 1:
-        in_off[1:] = np.cumsum(in_len)[:-1]
-    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
-    ns = np.asarray(ns, dtype=np.uint32)
-    cal = np.ascontiguousarray(cals, dtype=np.float32).reshape(-1)
-    if cal.size != 2 * nreads:
-        raise PressError("depress_pa_batch_host: two calibration floats per read")
-    off, total = _layout(ns)
+    comp, in_off, in_len, ns, off, total = _decode_batch(streams, ns)
+    cal = _cal_pairs(cals, len(streams), "depress_pa_batch_host")
     pa = np.zeros(total + 64, dtype=np.float32)
-    out_n = np.zeros(nreads, dtype=np.uint32)
-    rc = lib.press_hip_depress_pa_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
-                                        nreads, pa.ctypes.data, off.ctypes.data, ns.ctypes.data, total,
-                                        cal.ctypes.data, out_n.ctypes.data, 0)
-    if rc:
-        raise PressError(last_error())
-    return [None if int(k) == 0xFFFFFFFF else pa[int(o): int(o) + int(k)].copy()
-            for o, k in zip(off, out_n)]
+    out_n = np.zeros(len(streams), dtype=np.uint32)
+    _call("press_hip_depress_pa_batch", _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), len(streams), _ptr(pa),
+          _ptr(off), _ptr(ns), total, _ptr(cal), _ptr(out_n), 0)
+    return _reads_of(pa, off, out_n)
 
 
 def depress_norm_batch_host(method, streams, ns):
     """Batch decode to the normalised signal with host buffers: streams = list of bytes, ns = sample counts /
     capacities -> (list of float32 arrays (None: the read failed), (nreads, 2) int32 {median, MAD})."""
-    lib = load_library()
-    nreads = len(streams)
-    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
-    in_off = np.zeros(nreads, dtype=np.uint64)
-    if nreads > 1:
-        in_off[1:] = np.cumsum(in_len)[:-1]
-    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
-    ns = np.asarray(ns, dtype=np.uint32)
-    off, total = _layout(ns)
+    comp, in_off, in_len, ns, off, total = _decode_batch(streams, ns)
     out = np.zeros(total + 64, dtype=np.float32)
-    out_n = np.zeros(nreads, dtype=np.uint32)
-    stats = np.zeros((nreads, 2), dtype=np.int32)
-    rc = lib.press_hip_depress_norm_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
-                                          nreads, out.ctypes.data, off.ctypes.data, ns.ctypes.data, total,
-                                          stats.ctypes.data, out_n.ctypes.data, 0)
-    if rc:
-        raise PressError(last_error())
-    return ([None if int(k) == 0xFFFFFFFF else out[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)], stats)
+    out_n = np.zeros(len(streams), dtype=np.uint32)
+    stats = np.zeros((len(streams), 2), dtype=np.int32)
+    _call("press_hip_depress_norm_batch", _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), len(streams), _ptr(out),
+          _ptr(off), _ptr(ns), total, _ptr(stats), _ptr(out_n), 0)
+    return _reads_of(out, off, out_n), stats
 
 
 def depress_chunks_batch_host(method, streams, ns, T, overlap, dtype="float16", rule=None):
@@ -1072,38 +632,29 @@ def depress_chunks_batch_host(method, streams, ns, T, overlap, dtype="float16", 
     float32 / float16, or of uint16 bit patterns for "bfloat16"; q (nreads, 2) int32 {q_lo, q_hi} (rule: a ScaleRule) or
     {median, MAD} (None); row_read / row_start: per row the read and the sample it starts at (chunk_plan); out_n uint32
     per read, the decoded count or 0xFFFFFFFF for a read that failed - its rows are zeros and its q {0, 0}."""
-    lib = load_library()
     nreads = len(streams)
     if dtype not in CHUNK_DTYPES:
         raise PressError("dtype: one of %s" % ", ".join(CHUNK_DTYPES))
-    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
-    in_off = np.zeros(nreads, dtype=np.uint64)
-    if nreads > 1:
-        in_off[1:] = np.cumsum(in_len)[:-1]
-    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
-    ns = np.asarray(ns, dtype=np.uint32)
-    off, total = _layout(ns)
+    comp, in_off, in_len, ns, off, total = _decode_batch(streams, ns)
     row_first, row_read, row_start = chunk_plan(ns, T, overlap)
     rows = np.zeros((int(row_first[-1]), int(T)), dtype={"float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}[dtype])
     out_n = np.zeros(nreads, dtype=np.uint32)
     q = np.zeros((nreads, 2), dtype=np.int32)
-    rc = lib.press_hip_depress_chunks_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads,
-                                            rows.ctypes.data, rows.shape[0], CHUNK_DTYPES[dtype], int(T), int(overlap),
-                                            row_first.ctypes.data, off.ctypes.data, ns.ctypes.data, total, _rule_ptr(rule),
-                                            q.ctypes.data, out_n.ctypes.data, 0)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_depress_chunks_batch", _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), nreads, _ptr(rows),
+          rows.shape[0], CHUNK_DTYPES[dtype], int(T), int(overlap), _ptr(row_first), _ptr(off), _ptr(ns), total,
+          _rule_ptr(rule), _ptr(q), _ptr(out_n), 0)
     return rows, q, row_read, row_start, out_n
 
 
 def signal_stats_host(reads):
     """{median, MAD} of a list of int16 arrays (host buffers, synchronous) -> (nreads, 2) int32"""
-    lib = load_library()
     sig, off, ns, total = _host_batch(reads)
     stats = np.zeros((len(reads), 2), dtype=np.int32)
-    if lib.press_hip_signal_stats(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, stats.ctypes.data, 0):
-        raise PressError(last_error())
+    _call("press_hip_signal_stats", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, _ptr(stats), 0)
     return stats
+
+
+
 
 
 # ---------------------------------------------------------------------------- events: sigtk's segmentation
@@ -1118,12 +669,15 @@ EVENT_DTYPE = np.dtype([("start", "<u4"), ("length", "<u4"), ("mean", "<f4"), ("
 EVENT_NOFIT = 0xFFFFFFFF  # ev_count of a read whose records did not fit ev_cap
 
 
+def _preset(family, which, prm):
+    """press_hip_<family>_params_preset(which) into the structure prm -> prm"""
+    _call("press_hip_%s_params_preset" % family, which, _ptr(prm))
+    return prm
+
+
 def event_params(rna=False):
     """sigtk's detector parameters (press_hip_event_params_preset): DNA 3, 6, 1.4, 9.0, 0.2; RNA 7, 14, 2.5, 9.0, 1.0"""
-    p = EventParams()
-    if load_library().press_hip_event_params_preset(1 if rna else 0, ctypes.addressof(p)):
-        raise PressError(last_error())
-    return p
+    return _preset("event", 1 if rna else 0, EventParams())
 
 
 def _i64_first(t, nreads, name):
@@ -1172,10 +726,8 @@ def signal_events(sig, off, n, cal, prm, ev, ev_first, ev_count, ev_cap=None):
     _i64_first(ev_first, nreads, "ev_first")
     _f32_pairs(cal, nreads, "cal", "float32")
     cap = _record_cap(ev, 4, ev_cap, "ev")
-    if load_library().press_hip_signal_events(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(), cal.data_ptr(),
-                                              ctypes.addressof(prm), ev.data_ptr() if cap else None, cap,
-                                              ev_first.data_ptr(), ev_count.data_ptr(), 1):
-        raise PressError(last_error())
+    _call("press_hip_signal_events", _ptr(sig), _ptr(off), _ptr(n), nreads, sig.numel(), _ptr(cal), _ptr(prm),
+          _ptr(ev) if cap else None, cap, _ptr(ev_first), _ptr(ev_count), 1)
 
 
 def signal_events_host(reads, cal, prm=None, ev_cap=None):
@@ -1183,20 +735,15 @@ def signal_events_host(reads, cal, prm=None, ev_cap=None):
     EventParams (default: the DNA preset), ev_cap a limit in records (default: what the batch needs, found with a pure
     count) -> (ev, ev_first, ev_count): ev an EVENT_DTYPE array of min(need, ev_cap) records, ev_first uint64 of
     nreads + 1, ev_count uint32 per read (0xFFFFFFFF: the read did not fit)."""
-    lib = load_library()
     prm = event_params() if prm is None else prm
     sig, off, ns, total = _host_batch(reads)
-    cal = np.ascontiguousarray(cal, dtype=np.float32).reshape(-1)
-    if cal.size != 2 * len(reads):
-        raise PressError("cal: two floats per read")
+    cal = _cal_pairs(cal, len(reads), "cal")
     ev_first = np.zeros(len(reads) + 1, dtype=np.uint64)
     ev_count = np.zeros(len(reads), dtype=np.uint32)
 
     def call(ev, cap):
-        if lib.press_hip_signal_events(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, cal.ctypes.data,
-                                       ctypes.addressof(prm), ev.ctypes.data if cap else None, cap, ev_first.ctypes.data,
-                                       ev_count.ctypes.data, 0):
-            raise PressError(last_error())
+        _call("press_hip_signal_events", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, _ptr(cal), _ptr(prm),
+              _ptr(ev) if cap else None, cap, _ptr(ev_first), _ptr(ev_count), 0)
 
     return _count_then_records(call, ev_first, ev_cap, EVENT_DTYPE), ev_first, ev_count
 
@@ -1232,20 +779,14 @@ JNN_KINDS = {"cdna": 0, "drna": 1, "polya": 2}
 
 def jnn_params(kind="cdna"):
     """sigtk's segmenter parameters (press_hip_jnn_params_preset): "cdna", "drna" or "polya" (set top and bot yourself)"""
-    p = JnnParams()
     if kind not in JNN_KINDS:
         raise PressError("jnn_params: one of %s" % ", ".join(JNN_KINDS))
-    if load_library().press_hip_jnn_params_preset(JNN_KINDS[kind], ctypes.addressof(p)):
-        raise PressError(last_error())
-    return p
+    return _preset("jnn", JNN_KINDS[kind], JnnParams())
 
 
 def jnn2_params():
     """sigtk's dRNA adaptor parameters (press_hip_jnn2_params_preset): 0.5, 1500, 2000, 200000, 2000"""
-    p = Jnn2Params()
-    if load_library().press_hip_jnn2_params_preset(0, ctypes.addressof(p)):
-        raise PressError(last_error())
-    return p
+    return _preset("jnn2", 0, Jnn2Params())
 
 
 def signal_segments(sig, off, n, cal, prm, seg, seg_first, seg_count, thr=None, seg_cap=None):
@@ -1262,11 +803,8 @@ def signal_segments(sig, off, n, cal, prm, seg, seg_first, seg_count, thr=None, 
     if thr is not None:
         _f32_pairs(thr, nreads, "thr")
     cap = _record_cap(seg, 2, seg_cap, "seg")
-    if load_library().press_hip_signal_segments(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
-                                                cal.data_ptr() if cal is not None else None, ctypes.addressof(prm),
-                                                seg.data_ptr() if cap else None, cap, seg_first.data_ptr(),
-                                                seg_count.data_ptr(), thr.data_ptr() if thr is not None else None, 1):
-        raise PressError(last_error())
+    _call("press_hip_signal_segments", _ptr(sig), _ptr(off), _ptr(n), nreads, sig.numel(), _ptr(cal), _ptr(prm),
+          _ptr(seg) if cap else None, cap, _ptr(seg_first), _ptr(seg_count), _ptr(thr), 1)
 
 
 def signal_segments_host(reads, cal=None, prm=None, seg_cap=None, want_thr=True):
@@ -1275,23 +813,17 @@ def signal_segments_host(reads, cal=None, prm=None, seg_cap=None, want_thr=True)
     count) -> (seg, seg_first, seg_count, thr): seg a SEGMENT_DTYPE array of min(need, seg_cap) records, seg_first uint64
     of nreads + 1, seg_count uint32 per read (0xFFFFFFFF: the read did not fit), thr float32 (nreads, 2): bot, top - or
     None without want_thr."""
-    lib = load_library()
     prm = jnn_params() if prm is None else prm
     sig, off, ns, total = _host_batch(reads)
     if cal is not None:
-        cal = np.ascontiguousarray(cal, dtype=np.float32).reshape(-1)
-        if cal.size != 2 * len(reads):
-            raise PressError("cal: two floats per read")
+        cal = _cal_pairs(cal, len(reads), "cal")
     seg_first = np.zeros(len(reads) + 1, dtype=np.uint64)
     seg_count = np.zeros(len(reads), dtype=np.uint32)
     thr = np.zeros((len(reads), 2), dtype=np.float32) if want_thr else None
 
     def call(seg, cap):
-        if lib.press_hip_signal_segments(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total,
-                                         cal.ctypes.data if cal is not None else None, ctypes.addressof(prm),
-                                         seg.ctypes.data if cap else None, cap, seg_first.ctypes.data, seg_count.ctypes.data,
-                                         thr.ctypes.data if want_thr else None, 0):
-            raise PressError(last_error())
+        _call("press_hip_signal_segments", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, _ptr(cal), _ptr(prm),
+              _ptr(seg) if cap else None, cap, _ptr(seg_first), _ptr(seg_count), _ptr(thr), 0)
 
     return _count_then_records(call, seg_first, seg_cap, SEGMENT_DTYPE), seg_first, seg_count, thr
 
@@ -1308,10 +840,7 @@ def signal_adaptor(sig, off, n, prm, pair, thr=None):
     _f32_pairs(pair, nreads, "pair")
     if thr is not None:
         _f32_pairs(thr, nreads, "thr")
-    if load_library().press_hip_signal_adaptor(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
-                                               ctypes.addressof(prm), pair.data_ptr(),
-                                               thr.data_ptr() if thr is not None else None, 1):
-        raise PressError(last_error())
+    _call("press_hip_signal_adaptor", _ptr(sig), _ptr(off), _ptr(n), nreads, sig.numel(), _ptr(prm), _ptr(pair), _ptr(thr), 1)
 
 
 def signal_adaptor_host(reads, prm=None, want_thr=True):
@@ -1321,10 +850,7 @@ def signal_adaptor_host(reads, prm=None, want_thr=True):
     sig, off, ns, total = _host_batch(reads)
     pair = np.zeros((len(reads), 2), dtype=np.int32)
     thr = np.zeros((len(reads), 2), dtype=np.float32) if want_thr else None
-    if load_library().press_hip_signal_adaptor(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total,
-                                               ctypes.addressof(prm), pair.ctypes.data,
-                                               thr.ctypes.data if want_thr else None, 0):
-        raise PressError(last_error())
+    _call("press_hip_signal_adaptor", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, _ptr(prm), _ptr(pair), _ptr(thr), 0)
     return pair, thr
 
 
@@ -1343,10 +869,7 @@ PREFIX_DTYPE = np.dtype([("adapt_start", "<i4"), ("adapt_end", "<i4"), ("polya_s
 
 def prefix_params():
     """sigtk prefix's parameters (press_hip_prefix_params_preset): JNNV2_RNA_ADAPTOR, JNNV1_POLYA, rna 1, 30, 20"""
-    p = PrefixParams()
-    if load_library().press_hip_prefix_params_preset(0, ctypes.addressof(p)):
-        raise PressError(last_error())
-    return p
+    return _preset("prefix", 0, PrefixParams())
 
 
 def _f32_rows(t, rows, words, name):
@@ -1365,17 +888,7 @@ def range_stats(sig, off, n, cal, rng, out):
     if rng is not None:
         _f32_pairs(rng, nreads, "range")
     _f32_rows(out, nreads, 3, "out")
-    if load_library().press_hip_signal_range_stats(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
-                                                   cal.data_ptr() if cal is not None else None,
-                                                   rng.data_ptr() if rng is not None else None, out.data_ptr(), 1):
-        raise PressError(last_error())
-
-
-def _host_cal(cal, nreads):
-    cal = np.ascontiguousarray(cal, dtype=np.float32).reshape(-1)
-    if cal.size != 2 * nreads:
-        raise PressError("cal: two floats per read")
-    return cal
+    _call("press_hip_signal_range_stats", _ptr(sig), _ptr(off), _ptr(n), nreads, sig.numel(), _ptr(cal), _ptr(rng), _ptr(out), 1)
 
 
 def range_stats_host(reads, cal=None, rng=None):
@@ -1383,16 +896,13 @@ def range_stats_host(reads, cal=None, rng=None):
     rng None (whole reads) or (nreads, 2) unsigned: a, b -> a RANGE_STAT_DTYPE array of nreads records"""
     sig, off, ns, total = _host_batch(reads)
     if cal is not None:
-        cal = _host_cal(cal, len(reads))
+        cal = _cal_pairs(cal, len(reads), "cal")
     if rng is not None:
         rng = np.ascontiguousarray(rng, dtype=np.uint32).reshape(-1)
         if rng.size != 2 * len(reads):
             raise PressError("rng: two positions per read")
     out = np.zeros(len(reads), dtype=RANGE_STAT_DTYPE)
-    if load_library().press_hip_signal_range_stats(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total,
-                                                   cal.ctypes.data if cal is not None else None,
-                                                   rng.ctypes.data if rng is not None else None, out.ctypes.data, 0):
-        raise PressError(last_error())
+    _call("press_hip_signal_range_stats", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, _ptr(cal), _ptr(rng), _ptr(out), 0)
     return out
 
 
@@ -1408,11 +918,8 @@ def signal_prefix(sig, off, n, cal, prm, out, stat=None, thr=None):
         _f32_rows(stat, 2 * nreads, 3, "stat")
     if thr is not None:
         _f32_pairs(thr, nreads, "thr")
-    if load_library().press_hip_signal_prefix(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(), cal.data_ptr(),
-                                              ctypes.addressof(prm), out.data_ptr(),
-                                              stat.data_ptr() if stat is not None else None,
-                                              thr.data_ptr() if thr is not None else None, 1):
-        raise PressError(last_error())
+    _call("press_hip_signal_prefix", _ptr(sig), _ptr(off), _ptr(n), nreads, sig.numel(), _ptr(cal), _ptr(prm), _ptr(out),
+          _ptr(stat), _ptr(thr), 1)
 
 
 def signal_prefix_host(reads, cal, prm=None, want_stat=True, want_thr=True):
@@ -1421,14 +928,12 @@ def signal_prefix_host(reads, cal, prm=None, want_stat=True, want_thr=True):
     without want_stat, thr float32 (nreads, 2): bot, top - or None without want_thr)"""
     prm = prefix_params() if prm is None else prm
     sig, off, ns, total = _host_batch(reads)
-    cal = _host_cal(cal, len(reads))
+    cal = _cal_pairs(cal, len(reads), "cal")
     out = np.zeros(len(reads), dtype=PREFIX_DTYPE)
     stat = np.zeros((len(reads), 2), dtype=RANGE_STAT_DTYPE) if want_stat else None
     thr = np.zeros((len(reads), 2), dtype=np.float32) if want_thr else None
-    if load_library().press_hip_signal_prefix(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, cal.ctypes.data,
-                                              ctypes.addressof(prm), out.ctypes.data, stat.ctypes.data if want_stat else None,
-                                              thr.ctypes.data if want_thr else None, 0):
-        raise PressError(last_error())
+    _call("press_hip_signal_prefix", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, _ptr(cal), _ptr(prm), _ptr(out),
+          _ptr(stat), _ptr(thr), 0)
     return out, stat, thr
 
 
@@ -1467,98 +972,60 @@ def stall_workspace_bytes(method, total_samples, nreads):
     return int(load_library().press_hip_stall_workspace_bytes(_sid(method), int(total_samples), int(nreads)))
 
 
+def _stall_name(method):
+    return [k for k, v in STALL_METHODS.items() if v == _sid(method)][0]
+
+
 def stall_press(method, sig, cap=None):
     """X_press_16 of a stall method through the per-read symbol -> (ret, bytes); ret -1: the library reports *nout = 0"""
-    lib = load_library()
-    sig = np.ascontiguousarray(sig, dtype=np.int16)
-    cap = stall_bound(method, sig.size) + 1024 if cap is None else int(cap)
-    out = np.zeros(cap + 64, dtype=np.uint8)
-    out[cap:] = 0xA5
-    nout = ctypes.c_uint64(cap)
-    name = [k for k, v in STALL_METHODS.items() if v == _sid(method)][0]
-    getattr(lib, name + "_press_16")(sig.ctypes.data, sig.size, out.ctypes.data, ctypes.byref(nout))
-    if not np.all(out[cap:] == 0xA5):
-        raise PressError("%s_press_16 wrote past its capacity" % name)
-    return (0, out[:nout.value].tobytes()) if nout.value else (-1, b"")
+    cap = stall_bound(method, np.size(sig)) + 1024 if cap is None else int(cap)
+    return _press_16(_stall_name(method) + "_press_16", sig, cap)
 
 
 def stall_depress(method, comp, n):
     """X_depress_16 of a stall method through the per-read symbol: n is the read's SAMPLE count, which the reference
     passes in the place of the byte count (press.c:7871) -> (ret, int16 array)"""
-    lib = load_library()
-    buf = np.frombuffer(bytes(comp) + b"\0" * 64, dtype=np.uint8).copy()
-    out = np.zeros(n + 64, dtype=np.int16)
-    out[n:] = 0x5A5A
-    nout = ctypes.c_uint32(n)
-    name = [k for k, v in STALL_METHODS.items() if v == _sid(method)][0]
-    getattr(lib, name + "_depress_16")(buf.ctypes.data, n, out.ctypes.data, ctypes.byref(nout))
-    if not np.all(out[n:] == 0x5A5A):
-        raise PressError("%s_depress_16 wrote past the sample capacity" % name)
-    return (0, out[:nout.value].copy()) if nout.value else (-1, out[:0].copy())
+    return _depress_16(_stall_name(method) + "_depress_16", comp, n, n)
 
 
 def stall_press_batch(method, sig, off, n, out, out_off, out_len, stall=None):
     """Enqueue the compression of a batch under a stall method.  CUDA tensors as in press_batch; stall: None, or int32
     of 2 * nreads: (stall_start, stall_len) as written into every stream, (0, 0) without a stall"""
-    lib = load_library()
-    nreads = off.numel()
-    rc = lib.press_hip_stall_press_batch(_sid(method), sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
-                                         out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(),
-                                         None if stall is None else stall.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_stall_press_batch", _sid(method), _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(), _ptr(out),
+          _ptr(out_off), _ptr(out_len), _ptr(stall), 1)
 
 
 def stall_depress_batch(comp, in_off, in_len, sig, off, n, out_n):
     """Enqueue the decompression of a batch of stall-method streams (one decoder reads all three).  CUDA tensors as in
     depress_batch; n: the reads' exact sample counts"""
-    lib = load_library()
-    nreads = off.numel()
-    rc = lib.press_hip_stall_depress_batch(comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), nreads, sig.data_ptr(),
-                                           off.data_ptr(), n.data_ptr(), sig.numel(), out_n.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_stall_depress_batch", _ptr(comp), _ptr(in_off), _ptr(in_len), off.numel(), _ptr(sig), _ptr(off),
+          _ptr(n), sig.numel(), _ptr(out_n), 1)
 
 
 def stall_press_batch_host(method, reads, caps=None, want_stall=False):
     """Host buffers: reads = list of int16 arrays -> list of bytes / None (want_stall: and uint32 [nreads, 2])"""
-    lib = load_library()
     nreads = len(reads)
     sig, off, ns, total = _host_batch(reads)
     if caps is None:
         caps = [stall_bound(method, int(x)) + 1024 if x else 32 for x in ns]
-    out_off = np.zeros(nreads + 1, dtype=np.uint64)
-    out_off[1:] = np.cumsum((np.asarray(caps, dtype=np.uint64) + 15) // 16 * 16)
+    out_off = _slots(caps)
     out = np.zeros(int(out_off[-1]) + 64, dtype=np.uint8)
     out_len = np.zeros(nreads, dtype=np.uint64)
     stall = np.zeros((nreads, 2), dtype=np.uint32)
-    rc = lib.press_hip_stall_press_batch(_sid(method), sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total,
-                                         out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
-                                         stall.ctypes.data if want_stall else None, 0)
-    if rc:
-        raise PressError(last_error())
-    streams = [None if int(l) == FAILED else out[int(o): int(o) + int(l)].tobytes() for o, l in zip(out_off[:-1], out_len)]
+    _call("press_hip_stall_press_batch", _sid(method), _ptr(sig), _ptr(off), _ptr(ns), nreads, total, _ptr(out),
+          _ptr(out_off), _ptr(out_len), _ptr(stall) if want_stall else None, 0)
+    streams = _streams_of(out, out_off, out_len)
     return (streams, stall) if want_stall else streams
 
 
 def stall_depress_batch_host(streams, ns):
     """Host buffers: streams = list of bytes, ns = the reads' sample counts -> list of int16 arrays / None"""
-    lib = load_library()
-    nreads = len(streams)
-    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
-    in_off = np.zeros(nreads, dtype=np.uint64)
-    if nreads > 1:
-        in_off[1:] = np.cumsum(in_len)[:-1]
-    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
-    ns = np.asarray(ns, dtype=np.uint32)
-    off, total = _layout(ns)
+    comp, in_off, in_len, ns, off, total = _decode_batch(streams, ns)
     sig = np.zeros(total + 64, dtype=np.int16)
-    out_n = np.zeros(nreads, dtype=np.uint32)
-    rc = lib.press_hip_stall_depress_batch(comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads, sig.ctypes.data,
-                                           off.ctypes.data, ns.ctypes.data, total, out_n.ctypes.data, 0)
-    if rc:
-        raise PressError(last_error())
-    return [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)]
+    out_n = np.zeros(len(streams), dtype=np.uint32)
+    _call("press_hip_stall_depress_batch", _ptr(comp), _ptr(in_off), _ptr(in_len), len(streams), _ptr(sig), _ptr(off),
+          _ptr(ns), total, _ptr(out_n), 0)
+    return _reads_of(sig, off, out_n)
 
 
 # ---- the range-coder family: every coder on every layout (press_hip_rcf_*)
@@ -1583,54 +1050,27 @@ def rcf_bound(coder, layout, n):
 
 def rcf_press(coder, layout, sig, cap=None):
     """X_press_16 of a pair through the per-read symbol -> (ret, bytes); ret -1: the library reports *nout = 0"""
-    lib = load_library()
-    sig = np.ascontiguousarray(sig, dtype=np.int16)
-    cap = rcf_bound(coder, layout, sig.size) + 1024 if cap is None else int(cap)
-    out = np.zeros(cap + 64, dtype=np.uint8)
-    out[cap:] = 0xA5
-    nout = ctypes.c_uint64(cap)
-    name = rcf_name(coder, layout)
-    getattr(lib, name + "_press_16")(sig.ctypes.data, sig.size, out.ctypes.data, ctypes.byref(nout))
-    if not np.all(out[cap:] == 0xA5):
-        raise PressError("%s_press_16 wrote past its capacity" % name)
-    return (0, out[:nout.value].tobytes()) if nout.value else (-1, b"")
+    cap = rcf_bound(coder, layout, np.size(sig)) + 1024 if cap is None else int(cap)
+    return _press_16(rcf_name(coder, layout) + "_press_16", sig, cap)
 
 
 def rcf_depress(coder, layout, comp, n):
     """X_depress_16 of a pair through the per-read symbol; n: the read's exact sample count -> (ret, int16 array)"""
-    lib = load_library()
-    buf = np.frombuffer(bytes(comp) + b"\0" * 64, dtype=np.uint8).copy()
-    out = np.zeros(n + 64, dtype=np.int16)
-    out[n:] = 0x5A5A
-    nout = ctypes.c_uint32(n)
-    name = rcf_name(coder, layout)
-    getattr(lib, name + "_depress_16")(buf.ctypes.data, len(comp), out.ctypes.data, ctypes.byref(nout))
-    if not np.all(out[n:] == 0x5A5A):
-        raise PressError("%s_depress_16 wrote past the sample capacity" % name)
-    return (0, out[:nout.value].copy()) if nout.value else (-1, out[:0].copy())
+    return _depress_16(rcf_name(coder, layout) + "_depress_16", comp, len(comp), n)
 
 
 def rcf_press_batch(coder, layout, sig, off, n, out, out_off, out_len, raw=None):
     """Enqueue the compression of a batch under a pair of the family.  CUDA tensors as in press_batch; raw: None, or
     uint8 of nreads: 1 where the coder gave up and the payload is the read's one-byte values as they are"""
-    c, l = _rcf_ids(coder, layout)
-    nreads = off.numel()
-    rc = load_library().press_hip_rcf_press_batch(c, l, sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
-                                                  out.data_ptr(), out_off.data_ptr(), out_len.data_ptr(),
-                                                  None if raw is None else raw.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_rcf_press_batch", *_rcf_ids(coder, layout), _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(),
+          _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(raw), 1)
 
 
 def rcf_depress_batch(coder, layout, comp, in_off, in_len, sig, off, n, out_n):
     """Enqueue the decompression of a batch of streams of a pair.  CUDA tensors as in depress_batch; n: the reads' exact
     sample counts"""
-    c, l = _rcf_ids(coder, layout)
-    nreads = off.numel()
-    rc = load_library().press_hip_rcf_depress_batch(c, l, comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), nreads,
-                                                    sig.data_ptr(), off.data_ptr(), n.data_ptr(), sig.numel(), out_n.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_rcf_depress_batch", *_rcf_ids(coder, layout), _ptr(comp), _ptr(in_off), _ptr(in_len), off.numel(),
+          _ptr(sig), _ptr(off), _ptr(n), sig.numel(), _ptr(out_n), 1)
 
 
 def rcf_press_batch_host(coder, layout, reads, caps=None, want_raw=False):
@@ -1640,38 +1080,27 @@ def rcf_press_batch_host(coder, layout, reads, caps=None, want_raw=False):
     sig, off, ns, total = _host_batch(reads)
     if caps is None:
         caps = [rcf_bound(c, l, int(x)) + 1024 if x else 32 for x in ns]
-    out_off = np.zeros(nreads + 1, dtype=np.uint64)
-    out_off[1:] = np.cumsum((np.asarray(caps, dtype=np.uint64) + 15) // 16 * 16)
+    out_off = _slots(caps)
     out = np.zeros(int(out_off[-1]) + 64, dtype=np.uint8)
     out_len = np.zeros(nreads, dtype=np.uint64)
     raw = np.zeros(nreads, dtype=np.uint8)
-    rc = load_library().press_hip_rcf_press_batch(c, l, sig.ctypes.data, off.ctypes.data, ns.ctypes.data, nreads, total,
-                                                  out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data,
-                                                  raw.ctypes.data if want_raw else None, 0)
-    if rc:
-        raise PressError(last_error())
-    streams = [None if int(k) == FAILED else out[int(o): int(o) + int(k)].tobytes() for o, k in zip(out_off[:-1], out_len)]
+    _call("press_hip_rcf_press_batch", c, l, _ptr(sig), _ptr(off), _ptr(ns), nreads, total, _ptr(out), _ptr(out_off),
+          _ptr(out_len), _ptr(raw) if want_raw else None, 0)
+    streams = _streams_of(out, out_off, out_len)
     return (streams, raw) if want_raw else streams
 
 
 def rcf_depress_batch_host(coder, layout, streams, ns):
     """Host buffers: streams = list of bytes, ns = the reads' exact sample counts -> list of int16 arrays / None"""
-    c, l = _rcf_ids(coder, layout)
-    nreads = len(streams)
-    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
-    in_off = np.zeros(nreads, dtype=np.uint64)
-    if nreads > 1:
-        in_off[1:] = np.cumsum(in_len)[:-1]
-    comp = np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy()
-    ns = np.asarray(ns, dtype=np.uint32)
-    off, total = _layout(ns)
+    comp, in_off, in_len, ns, off, total = _decode_batch(streams, ns)
     sig = np.zeros(total + 64, dtype=np.int16)
-    out_n = np.zeros(nreads, dtype=np.uint32)
-    rc = load_library().press_hip_rcf_depress_batch(c, l, comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads,
-                                                    sig.ctypes.data, off.ctypes.data, ns.ctypes.data, total, out_n.ctypes.data, 0)
-    if rc:
-        raise PressError(last_error())
-    return [None if int(k) == 0xFFFFFFFF else sig[int(o): int(o) + int(k)].copy() for o, k in zip(off, out_n)]
+    out_n = np.zeros(len(streams), dtype=np.uint32)
+    _call("press_hip_rcf_depress_batch", *_rcf_ids(coder, layout), _ptr(comp), _ptr(in_off), _ptr(in_len), len(streams),
+          _ptr(sig), _ptr(off), _ptr(ns), total, _ptr(out_n), 0)
+    return _reads_of(sig, off, out_n)
+
+
+
 
 
 VERIFIED = 0xFFFFFFFF  # PRESS_HIP_VERIFIED: first_bad of a read that decodes to the samples it is meant to hold
@@ -1691,20 +1120,15 @@ def _u32_table(t, nreads, name):
 def signal_crc32(sig, off, n, crc):
     """Enqueue the per-read CRC-32 of a batch of samples (CUDA tensors as in signal_stats; crc: 32-bit, nreads entries):
     crc[r] = zlib.crc32 of the n[r] int16 samples at sig[off[r]:] as bytes (press_hip_signal_crc32)."""
-    nreads = off.numel()
-    _u32_table(crc, nreads, "crc")
-    if load_library().press_hip_signal_crc32(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(),
-                                             crc.data_ptr(), 1):
-        raise PressError(last_error())
+    _u32_table(crc, off.numel(), "crc")
+    _call("press_hip_signal_crc32", _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(), _ptr(crc), 1)
 
 
 def signal_crc32_host(reads):
     """CRC-32 of a list of int16 arrays (host buffers, synchronous) -> uint32[nreads]"""
-    lib = load_library()
     sig, off, ns, total = _host_batch(reads)
     crc = np.zeros(len(reads), dtype=np.uint32)
-    if lib.press_hip_signal_crc32(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, crc.ctypes.data, 0):
-        raise PressError(last_error())
+    _call("press_hip_signal_crc32", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, _ptr(crc), 0)
     return crc
 
 
@@ -1712,37 +1136,19 @@ def depress_crc_batch(method, comp, in_off, in_len, off, n, total_samples, crc, 
     """Enqueue the decompression of a batch into library scratch and the CRC-32 of what was decoded (CUDA tensors as in
     depress_batch; off / n / total_samples lay out the library's sample scratch; crc: 32-bit, nreads entries, 0 for a
     refused read).  No sample reaches the caller (press_hip_depress_crc_batch)."""
-    nreads = off.numel()
-    _u32_table(crc, nreads, "crc")
-    rc = load_library().press_hip_depress_crc_batch(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(),
-                                                    nreads, off.data_ptr(), n.data_ptr(), int(total_samples),
-                                                    crc.data_ptr(), out_n.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
-
-
-def _streams_arena(streams):
-    nreads = len(streams)
-    in_len = np.array([len(s) for s in streams], dtype=np.uint64)
-    in_off = np.zeros(nreads, dtype=np.uint64)
-    if nreads > 1:
-        in_off[1:] = np.cumsum(in_len)[:-1]
-    return np.frombuffer(b"".join(streams) + b"\0" * 64, dtype=np.uint8).copy(), in_off, in_len
+    _u32_table(crc, off.numel(), "crc")
+    _call("press_hip_depress_crc_batch", _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), off.numel(), _ptr(off),
+          _ptr(n), int(total_samples), _ptr(crc), _ptr(out_n), 1)
 
 
 def depress_crc_batch_host(method, streams, ns):
     """Decode and digest with host buffers: streams = list of bytes, ns = sample counts / rooms ->
     (crc uint32[nreads], out_n uint32[nreads]; 0 and 0xFFFFFFFF for a refused read)"""
-    lib = load_library()
-    nreads = len(streams)
-    comp, in_off, in_len = _streams_arena(streams)
-    ns = np.asarray(ns, dtype=np.uint32)
-    off, total = _layout(ns)
-    crc = np.zeros(nreads, dtype=np.uint32)
-    out_n = np.zeros(nreads, dtype=np.uint32)
-    if lib.press_hip_depress_crc_batch(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads,
-                                       off.ctypes.data, ns.ctypes.data, total, crc.ctypes.data, out_n.ctypes.data, 0):
-        raise PressError(last_error())
+    comp, in_off, in_len, ns, off, total = _decode_batch(streams, ns)
+    crc = np.zeros(len(streams), dtype=np.uint32)
+    out_n = np.zeros(len(streams), dtype=np.uint32)
+    _call("press_hip_depress_crc_batch", _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), len(streams), _ptr(off),
+          _ptr(ns), total, _ptr(crc), _ptr(out_n), 0)
     return crc, out_n
 
 
@@ -1753,20 +1159,15 @@ def verify_batch(method, comp, in_off, in_len, sig, off, n, first_bad, out_n, nb
     where only the counts differ); nbad = the reads that are not VERIFIED (press_hip_verify_batch).  degrade_bits > 0:
     sig holds the originals of a degraded archive and the comparison is with D_bits of them
     (press_hip_verify_degraded_batch)."""
-    nreads = off.numel()
-    _u32_table(first_bad, nreads, "first_bad")
+    _u32_table(first_bad, off.numel(), "first_bad")
     _u32_table(nbad, 1, "nbad")
-    rc = _degraded(load_library(), "verify_batch", degrade_bits)(_mid(method), comp.data_ptr(), in_off.data_ptr(), in_len.data_ptr(), nreads,
-                                               sig.data_ptr(), off.data_ptr(), n.data_ptr(), sig.numel(),
-                                               first_bad.data_ptr(), out_n.data_ptr(), nbad.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call_degraded("verify_batch", degrade_bits, _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), off.numel(),
+                   _ptr(sig), _ptr(off), _ptr(n), sig.numel(), _ptr(first_bad), _ptr(out_n), _ptr(nbad), 1)
 
 
 def verify_batch_host(method, streams, reads, degrade_bits=0):
     """Decode and compare with host buffers: streams = list of bytes, reads = the int16 arrays they are meant to hold
     -> (first_bad uint32[nreads], out_n uint32[nreads], nbad)"""
-    lib = load_library()
     nreads = len(streams)
     if len(reads) != nreads:
         raise PressError("verify_batch_host: one stream per read")
@@ -1775,10 +1176,8 @@ def verify_batch_host(method, streams, reads, degrade_bits=0):
     first_bad = np.zeros(nreads, dtype=np.uint32)
     out_n = np.zeros(nreads, dtype=np.uint32)
     nbad = ctypes.c_uint32(0)
-    if _degraded(lib, "verify_batch", degrade_bits)(_mid(method), comp.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, nreads,
-                                  sig.ctypes.data, off.ctypes.data, ns.ctypes.data, total, first_bad.ctypes.data,
-                                  out_n.ctypes.data, ctypes.byref(nbad), 0):
-        raise PressError(last_error())
+    _call_degraded("verify_batch", degrade_bits, _mid(method), _ptr(comp), _ptr(in_off), _ptr(in_len), nreads, _ptr(sig),
+                   _ptr(off), _ptr(ns), total, _ptr(first_bad), _ptr(out_n), ctypes.byref(nbad), 0)
     return first_bad, out_n, int(nbad.value)
 
 
@@ -1800,47 +1199,38 @@ class HostBatch:
             return a
 
         self.sig, self.off, self.ns, self.total = _host_batch(reads, zeroed)
-        caps = [int(lib.press_hip_bound(self.mid, int(x))) + 1024 for x in self.ns]
-        self.out_off = np.zeros(self.nreads + 1, dtype=np.uint64)
-        self.out_off[1:] = np.cumsum((np.asarray(caps, dtype=np.uint64) + 15) // 16 * 16)
+        self.out_off = _slots([int(lib.press_hip_bound(self.mid, int(x))) + 1024 for x in self.ns])
         self.out = self._alloc(int(self.out_off[-1]) + 64, np.uint8)
         self.out_len = np.zeros(self.nreads, dtype=np.uint64)
         self.back = self._alloc(self.total + 64, np.int16)
         self.out_n = np.zeros(self.nreads, dtype=np.uint32)
+        # the arguments of the two calls, resolved once: press() and depress() are one call into the library each
+        self._in_off = np.ascontiguousarray(self.out_off[:-1])
+        self._press = (self.mid, _ptr(self.sig), _ptr(self.off), _ptr(self.ns), self.nreads, self.total, _ptr(self.out),
+                       _ptr(self.out_off), _ptr(self.out_len), 0)
+        self._depress = (self.mid, _ptr(self.out), _ptr(self._in_off), _ptr(self.out_len), self.nreads, _ptr(self.back),
+                         _ptr(self.off), _ptr(self.ns), self.total, _ptr(self.out_n), 0)
 
     def _alloc(self, count, dtype):
         nbytes = int(count) * np.dtype(dtype).itemsize
         if not self.pinned:
             return np.zeros(count, dtype=dtype)
-        self.lib.press_hip_host_alloc.restype = ctypes.c_void_p
-        self.lib.press_hip_host_alloc.argtypes = [ctypes.c_uint64]
         p = self.lib.press_hip_host_alloc(nbytes)
-        if not p:
+        if not p:  # (returns the pointer, not a status: not a case for _call)
             raise PressError(last_error())
         self._held.append(p)
         buf = (ctypes.c_uint8 * nbytes).from_address(p)
         return np.frombuffer(buf, dtype=dtype)
 
     def press(self):
-        rc = self.lib.press_hip_press_batch(self.mid, self.sig.ctypes.data, self.off.ctypes.data,
-                                            self.ns.ctypes.data, self.nreads, self.total, self.out.ctypes.data,
-                                            self.out_off.ctypes.data, self.out_len.ctypes.data, 0)
-        if rc:
-            raise PressError(last_error())
+        _call("press_hip_press_batch", *self._press)
 
     def streams(self):
-        return [None if int(l) == FAILED else self.out[int(o): int(o) + int(l)].tobytes()
-                for o, l in zip(self.out_off[:-1], self.out_len)]
+        return _streams_of(self.out, self.out_off, self.out_len)
 
     def depress(self):
         """decode the streams press() left in the slots of `out` into `back`"""
-        in_off = np.ascontiguousarray(self.out_off[:-1])
-        rc = self.lib.press_hip_depress_batch(self.mid, self.out.ctypes.data, in_off.ctypes.data,
-                                              self.out_len.ctypes.data, self.nreads, self.back.ctypes.data,
-                                              self.off.ctypes.data, self.ns.ctypes.data, self.total,
-                                              self.out_n.ctypes.data, 0)
-        if rc:
-            raise PressError(last_error())
+        _call("press_hip_depress_batch", *self._depress)
 
     def lossless(self):
         return bool(np.array_equal(self.out_n, self.ns)) and all(
@@ -1849,26 +1239,23 @@ class HostBatch:
 
     def close(self):
         self.sig = self.out = self.back = None
-        if self._held:
-            self.lib.press_hip_host_free.argtypes = [ctypes.c_void_p]
-            for p in self._held:
-                self.lib.press_hip_host_free(p)
-            self._held = []
+        for p in self._held:
+            self.lib.press_hip_host_free(p)
+        self._held = []
+
+
+
 
 
 def kernel_timing(enable=True):
     """(re)start / stop the HIP-event timing of the dominant kernel of each batch call"""
-    lib = load_library()
-    if lib.press_hip_kernel_timing(1 if enable else 0):
-        raise PressError(last_error())
+    _call("press_hip_kernel_timing", 1 if enable else 0)
 
 
 def kernel_times(which):
     """elapsed ms of the dominant kernel of every press (which=0) / depress (1) call so far"""
-    lib = load_library()
     buf = (ctypes.c_float * 128)()
-    lib.press_hip_kernel_times.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
-    n = lib.press_hip_kernel_times(which, buf, 128)
+    n = load_library().press_hip_kernel_times(which, buf, 128)
     return [buf[i] for i in range(n)]
 
 
@@ -1877,67 +1264,59 @@ def kernel_times(which):
 NBINS = 257  # the 256 one-byte zd values the shuffman_* methods code, then the exceptions
 
 
+def _rows(lib, *names):
+    """(re)apply the table's rows of `names` to a library handle"""
+    return abi.declare(lib, {n: abi.PROTOS[n] for n in names})
+
+
 def _train_api(lib):
-    lib.press_hip_symbol_counts.restype = ctypes.c_int
-    lib.press_hip_symbol_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-                                            ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
-    lib.press_hip_table_from_counts.restype = ctypes.c_int
-    lib.press_hip_table_from_counts.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-    lib.press_hip_write_table_file.restype = ctypes.c_int
-    lib.press_hip_write_table_file.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+    """load_library() has declared these; kept because tests/test_table_training.py calls it before the raw functions"""
+    _rows(lib, "press_hip_symbol_counts", "press_hip_table_from_counts", "press_hip_write_table_file")
+
+
+def _tally_api(lib):
+    """as _train_api, for tests/test_signal_tally.py"""
+    _rows(lib, "press_hip_signal_tally", "press_hip_signal_tally_workspace_bytes")
 
 
 def symbol_counts(sig, off, n, counts):
     """Enqueue the counting of a batch on the device, ADDING into counts (CUDA tensors: sig int16, off int64
     read starts in multiples of 8 samples, n int32 sample counts, counts int64 of NBINS entries holding
     uint64 values)."""
-    lib = load_library()
-    _train_api(lib)
     if counts.numel() != NBINS or counts.element_size() != 8 or not counts.is_contiguous():
         raise PressError("counts must be a contiguous 64-bit tensor of %d entries" % NBINS)
-    rc = lib.press_hip_symbol_counts(sig.data_ptr(), off.data_ptr(), n.data_ptr(), off.numel(), sig.numel(),
-                                     counts.data_ptr(), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_symbol_counts", _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(), _ptr(counts), 1)
 
 
 def symbol_counts_host(reads, counts=None):
     """Counts of a list of int16 arrays (host buffers, synchronous) -> numpy uint64[NBINS]; added to
     `counts` when it is given."""
-    lib = load_library()
-    _train_api(lib)
     sig, off, ns, total = _host_batch(reads)
     out = np.zeros(NBINS, dtype=np.uint64) if counts is None else np.ascontiguousarray(counts, dtype=np.uint64).copy()
-    rc = lib.press_hip_symbol_counts(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total,
-                                     out.ctypes.data, 0)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_symbol_counts", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, _ptr(out), 0)
     return out
 
 
 def table_from_counts(counts, max_bits=24):
     """The reference's Huffman construction over counts[0..255] (a longer counts array: the rest is ignored),
     limited to max_bits -> (len uint32[256], bits uint64[256]); bit k of bits[s] is the k-th emitted bit."""
-    lib = load_library()
-    _train_api(lib)
     c = np.ascontiguousarray(np.asarray(counts, dtype=np.uint64)[:256])
     if c.size != 256:
         raise PressError("table_from_counts needs 256 counts")
     ln = np.zeros(256, dtype=np.uint32)
     bits = np.zeros(256, dtype=np.uint64)
-    if lib.press_hip_table_from_counts(c.ctypes.data, int(max_bits), ln.ctypes.data, bits.ctypes.data):
-        raise PressError(last_error())
+    _call("press_hip_table_from_counts", _ptr(c), int(max_bits), _ptr(ln), _ptr(bits))
     return ln, bits
 
 
 def write_table(path, ln, bits, data_bytes):
     """The table file (the format of NA12878_zd.huffman) that use_table() / press_hip_load_table_file read."""
-    lib = load_library()
-    _train_api(lib)
     ln = np.ascontiguousarray(ln, dtype=np.uint32)
     bits = np.ascontiguousarray(bits, dtype=np.uint64)
-    if lib.press_hip_write_table_file(path.encode(), ln.ctypes.data, bits.ctypes.data, int(data_bytes) & 0xFFFFFFFF):
-        raise PressError(last_error())
+    _call("press_hip_write_table_file", path.encode(), _ptr(ln), _ptr(bits), int(data_bytes) & 0xFFFFFFFF)
+
+
+
 
 
 def _blow5_counts(path, counts, max_reads=4096, arena_bytes=1 << 28, degrade_bits=0):
@@ -2019,18 +1398,8 @@ MOMENTS_DTYPE = np.dtype([("sum", "<i8"), ("sumsq", "<u8"), ("min", "<i4"), ("ma
 TALLY_OUTPUTS = ("raw", "delta", "trans", "mom")
 
 
-def _tally_api(lib):
-    lib.press_hip_signal_tally.restype = ctypes.c_int
-    lib.press_hip_signal_tally.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-    lib.press_hip_signal_tally_workspace_bytes.restype = ctypes.c_uint64
-    lib.press_hip_signal_tally_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
-
-
 def signal_tally_workspace_bytes(total_samples, nreads):
-    lib = load_library()
-    _tally_api(lib)
-    return int(lib.press_hip_signal_tally_workspace_bytes(int(total_samples), int(nreads)))
+    return int(load_library().press_hip_signal_tally_workspace_bytes(int(total_samples), int(nreads)))
 
 
 def signal_tally(sig, off, n, raw=None, delta=None, trans=None, mom=None):
@@ -2038,27 +1407,20 @@ def signal_tally(sig, off, n, raw=None, delta=None, trans=None, mom=None):
     samples, n int32 sample counts).  raw and delta (64-bit, TALLY_BINS entries) and trans (64-bit, TALLY_SYMS squared)
     are ADDED to; mom (32 bytes per read: a contiguous tensor of nreads * 4 64-bit or nreads * 8 32-bit words, read with
     MOMENTS_DTYPE) is set.  Any may be None."""
-    lib = load_library()
-    _tally_api(lib)
     nreads = off.numel()
     for name, t, words in (("raw", raw, TALLY_BINS), ("delta", delta, TALLY_BINS), ("trans", trans, TALLY_SYMS * TALLY_SYMS)):
         if t is not None and (t.numel() != words or t.element_size() != 8 or not t.is_contiguous()):
             raise PressError("%s must be a contiguous 64-bit tensor of %d entries" % (name, words))
     if mom is not None and (mom.numel() * mom.element_size() != 32 * nreads or not mom.is_contiguous()):
         raise PressError("mom must be a contiguous tensor of 32 bytes per read")
-    ptr = lambda t: None if t is None else t.data_ptr()
-    rc = lib.press_hip_signal_tally(sig.data_ptr(), off.data_ptr(), n.data_ptr(), nreads, sig.numel(), ptr(raw), ptr(delta),
-                                    ptr(trans), ptr(mom), 1)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_signal_tally", _ptr(sig), _ptr(off), _ptr(n), nreads, sig.numel(), _ptr(raw), _ptr(delta), _ptr(trans),
+          _ptr(mom), 1)
 
 
 def signal_tally_host(reads, want=TALLY_OUTPUTS, into=None):
     """Tallies of a list of int16 arrays (host buffers, synchronous) -> dict with the members of `want`: raw, delta
     (numpy uint64[TALLY_BINS]), trans (uint64[TALLY_SYMS, TALLY_SYMS]), mom (MOMENTS_DTYPE[nreads]).  into: a dict of
     tables the counts are added to (copies are returned)."""
-    lib = load_library()
-    _tally_api(lib)
     sig, off, ns, total = _host_batch(reads)
     shapes = {"raw": (TALLY_BINS,), "delta": (TALLY_BINS,), "trans": (TALLY_SYMS, TALLY_SYMS)}
     out = {}
@@ -2069,12 +1431,12 @@ def signal_tally_host(reads, want=TALLY_OUTPUTS, into=None):
             out[k] = np.ascontiguousarray(into[k], dtype=np.uint64).reshape(shapes[k]).copy()
         else:
             out[k] = np.zeros(shapes[k], dtype=np.uint64)
-    ptr = lambda k: out[k].ctypes.data if k in out else None
-    rc = lib.press_hip_signal_tally(sig.ctypes.data, off.ctypes.data, ns.ctypes.data, len(reads), total, ptr("raw"),
-                                    ptr("delta"), ptr("trans"), ptr("mom"), 0)
-    if rc:
-        raise PressError(last_error())
+    _call("press_hip_signal_tally", _ptr(sig), _ptr(off), _ptr(ns), len(reads), total, _ptr(out.get("raw")),
+          _ptr(out.get("delta")), _ptr(out.get("trans")), _ptr(out.get("mom")), 0)
     return out
+
+
+
 
 
 def tally_value(index):
@@ -2202,12 +1564,8 @@ def _report_batches(src, max_reads, arena_bytes, dev):
             yield (torch.from_numpy(sig).to(dev), torch.from_numpy(off.view(np.int64)).to(dev),
                    torch.from_numpy(ns.view(np.int32)).to(dev), ["read-%08d" % (k0 + k) for k in range(len(part))], None)
         return
-    lib = load_library()
     path = os.fspath(src)
     rd = Blow5Reader(path)
-    lib.press_hip_blow5_next_pa.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.POINTER(ctypes.c_uint32)]
     try:
         arena = np.empty(arena_bytes, dtype=np.uint8)
         boff = np.zeros(max_reads, dtype=np.uint64)
@@ -2217,9 +1575,8 @@ def _report_batches(src, max_reads, arena_bytes, dev):
         idbuf = ctypes.create_string_buffer(max_reads * rd.ID_LEN)
         got = ctypes.c_uint32()
         while True:
-            if lib.press_hip_blow5_next_pa(rd._h, max_reads, arena.ctypes.data, arena.size, boff.ctypes.data, blen.ctypes.data,
-                                           bns.ctypes.data, idbuf, dor.ctypes.data, ctypes.byref(got)):
-                raise PressError(lib.press_hip_blow5_last_error().decode())
+            _blow5_call("press_hip_blow5_next_pa", rd._h, max_reads, _ptr(arena), arena.size, _ptr(boff), _ptr(blen), _ptr(bns),
+                        idbuf, _ptr(dor), ctypes.byref(got))
             g = got.value
             if g == 0:
                 break
@@ -2300,6 +1657,13 @@ def dataset_report(src, max_reads=4096, arena_bytes=1 << 28):
 
 # ---------------------------------------------------------------------------- BLOW5 input (host side)
 
+def _blow5_call(name, *args):
+    """as _call, for the press_hip_blow5_* functions: they report through press_hip_blow5_last_error"""
+    lib = load_library()
+    if getattr(lib, name)(*args):
+        raise PressError(lib.press_hip_blow5_last_error().decode())
+
+
 class Blow5Reader:
     """press_hip_blow5_*: iterate over a BLOW5 file's signal fields as stored (svb-zd streams for
     signal method 1) - what depress_batch_host("slow5_svb_zd", ...) / the device batch API decode."""
@@ -2307,33 +1671,22 @@ class Blow5Reader:
     ID_LEN = 64
 
     def __init__(self, path):
-        lib = load_library()
-        lib.press_hip_blow5_last_error.restype = ctypes.c_char_p
-        lib.press_hip_blow5_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
-        lib.press_hip_blow5_close.argtypes = [ctypes.c_void_p]
-        lib.press_hip_blow5_methods.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-        lib.press_hip_blow5_next.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.POINTER(ctypes.c_uint32)]
         self._h = ctypes.c_void_p()
-        if lib.press_hip_blow5_open(path.encode(), ctypes.byref(self._h)):
-            raise PressError(lib.press_hip_blow5_last_error().decode())
+        _blow5_call("press_hip_blow5_open", path.encode(), ctypes.byref(self._h))
         rm, sm = ctypes.c_int(), ctypes.c_int()
-        lib.press_hip_blow5_methods(self._h, ctypes.byref(rm), ctypes.byref(sm))
+        load_library().press_hip_blow5_methods(self._h, ctypes.byref(rm), ctypes.byref(sm))
         self.record_method, self.signal_method = rm.value, sm.value
 
     def next_batch(self, max_reads=4096, arena_bytes=1 << 28):
         """-> list of (read_id, n_samples, signal field bytes); empty at the end of the file"""
-        lib = load_library()
         arena = np.empty(arena_bytes, dtype=np.uint8)
         off = np.zeros(max_reads, dtype=np.uint64)
         ln = np.zeros(max_reads, dtype=np.uint64)
         ns = np.zeros(max_reads, dtype=np.uint32)
         ids = ctypes.create_string_buffer(max_reads * self.ID_LEN)
         got = ctypes.c_uint32()
-        if lib.press_hip_blow5_next(self._h, max_reads, arena.ctypes.data, arena_bytes, off.ctypes.data,
-                                    ln.ctypes.data, ns.ctypes.data, ids, ctypes.byref(got)):
-            raise PressError(lib.press_hip_blow5_last_error().decode())
+        _blow5_call("press_hip_blow5_next", self._h, max_reads, _ptr(arena), arena_bytes, _ptr(off), _ptr(ln), _ptr(ns), ids,
+                    ctypes.byref(got))
         out = []
         for k in range(got.value):
             rid = ids.raw[k * self.ID_LEN:(k + 1) * self.ID_LEN].split(b"\0")[0].decode()
@@ -2343,10 +1696,6 @@ class Blow5Reader:
     def next_batch_pa(self, max_reads=4096, arena_bytes=1 << 28):
         """-> list of (read_id, n_samples, signal field bytes, (digitisation, offset, range)); empty at the end of the
         file.  The three doubles as the record stores them: pa_cal makes depress_pa_batch's calibration of them."""
-        lib = load_library()
-        lib.press_hip_blow5_next_pa.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
         arena = np.empty(arena_bytes, dtype=np.uint8)
         off = np.zeros(max_reads, dtype=np.uint64)
         ln = np.zeros(max_reads, dtype=np.uint64)
@@ -2354,9 +1703,8 @@ class Blow5Reader:
         dor = np.zeros((max_reads, 3), dtype=np.float64)
         ids = ctypes.create_string_buffer(max_reads * self.ID_LEN)
         got = ctypes.c_uint32()
-        if lib.press_hip_blow5_next_pa(self._h, max_reads, arena.ctypes.data, arena_bytes, off.ctypes.data,
-                                       ln.ctypes.data, ns.ctypes.data, ids, dor.ctypes.data, ctypes.byref(got)):
-            raise PressError(lib.press_hip_blow5_last_error().decode())
+        _blow5_call("press_hip_blow5_next_pa", self._h, max_reads, _ptr(arena), arena_bytes, _ptr(off), _ptr(ln), _ptr(ns), ids,
+                    _ptr(dor), ctypes.byref(got))
         out = []
         for k in range(got.value):
             rid = ids.raw[k * self.ID_LEN:(k + 1) * self.ID_LEN].split(b"\0")[0].decode()
@@ -2366,20 +1714,15 @@ class Blow5Reader:
 
     def set_threads(self, n):
         """host threads that inflate records (0: as many as the host offers, at most 32)"""
-        lib = load_library()
-        lib.press_hip_blow5_threads.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        if lib.press_hip_blow5_threads(self._h, int(n)):
-            raise PressError(lib.press_hip_blow5_last_error().decode())
+        _blow5_call("press_hip_blow5_threads", self._h, int(n))
 
     def next_arena(self, arena, off, ln, ns, max_reads):
         """the raw call: signal fields into the caller's arena (numpy uint8; page-locked memory from
         press.host_alloc for a fast copy to the device), offsets / lengths / sample counts into off / ln / ns
         (numpy uint64, uint64, uint32 of >= max_reads).  -> reads delivered (0 at the end of the file)"""
-        lib = load_library()
         got = ctypes.c_uint32()
-        if lib.press_hip_blow5_next(self._h, max_reads, arena.ctypes.data, arena.size, off.ctypes.data,
-                                    ln.ctypes.data, ns.ctypes.data, None, ctypes.byref(got)):
-            raise PressError(lib.press_hip_blow5_last_error().decode())
+        _blow5_call("press_hip_blow5_next", self._h, max_reads, _ptr(arena), arena.size, _ptr(off), _ptr(ln), _ptr(ns), None,
+                    ctypes.byref(got))
         return got.value
 
     def close(self):
@@ -2388,18 +1731,7 @@ class Blow5Reader:
             self._h = ctypes.c_void_p()
 
 
-def _blow5_writer_api(lib):
-    lib.press_hip_blow5_last_error.restype = ctypes.c_char_p
-    lib.press_hip_blow5_create.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                           ctypes.POINTER(ctypes.c_void_p)]
-    lib.press_hip_blow5_write.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                          ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
-    lib.press_hip_blow5_write_batch.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6
-    lib.press_hip_blow5_index.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.press_hip_blow5_finish.argtypes = [ctypes.c_void_p]
-
-
-def _blow5_write_batch(lib, w, pres, sigs, posts):
+def _blow5_write_batch(w, pres, sigs, posts):
     """press_hip_blow5_write_batch over lists of numpy uint8 arrays (posts may hold empty arrays)"""
     n = len(pres)
     PT = ctypes.c_void_p * n
@@ -2410,8 +1742,7 @@ def _blow5_write_batch(lib, w, pres, sigs, posts):
         pre_p[k], pre_l[k] = pres[k].ctypes.data, pres[k].size
         sig_p[k], sig_l[k] = (sigs[k].ctypes.data if sigs[k].size else None), sigs[k].size
         post_p[k], post_l[k] = (posts[k].ctypes.data if posts[k].size else None), posts[k].size
-    if lib.press_hip_blow5_write_batch(w, n, pre_p, pre_l, sig_p, sig_l, post_p, post_l):
-        raise PressError(lib.press_hip_blow5_last_error().decode())
+    _blow5_call("press_hip_blow5_write_batch", w, n, pre_p, pre_l, sig_p, sig_l, post_p, post_l)
 
 
 def blow5_write_like(dst, like, fields, record_method=1, signal_method=1, index=False, ids=None):
@@ -2420,17 +1751,14 @@ def blow5_write_like(dst, like, fields, record_method=1, signal_method=1, index=
     fields of `like`'s first record and a read id of its own (ids, default "read-%08d" padded to the template's
     length).  For benchmarks and tests: a file of any size with realistic framing.  -> the read ids"""
     lib = load_library()
-    _blow5_writer_api(lib)
     rd = Blow5Reader(like)
-    lib.press_hip_blow5_next_records.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64] + \
-        [ctypes.c_void_p] * 5 + [ctypes.POINTER(ctypes.c_uint32)]
     cap = 1 << 26
     arena = np.empty(cap, dtype=np.uint8)
     ro, rl, sp, sl = (np.zeros(1, dtype=np.uint64) for _ in range(4))
     ns = np.zeros(1, dtype=np.uint32)
     got = ctypes.c_uint32()
-    if lib.press_hip_blow5_next_records(rd._h, 1, arena.ctypes.data, cap, ro.ctypes.data, rl.ctypes.data, sp.ctypes.data,
-                                        sl.ctypes.data, ns.ctypes.data, ctypes.byref(got)) or got.value != 1:
+    if lib.press_hip_blow5_next_records(rd._h, 1, _ptr(arena), cap, _ptr(ro), _ptr(rl), _ptr(sp), _ptr(sl), _ptr(ns),
+                                        ctypes.byref(got)) or got.value != 1:
         rd.close()
         raise PressError("no template record in " + like)
     rec = arena[int(ro[0]):int(ro[0]) + int(rl[0])].copy()
@@ -2438,10 +1766,10 @@ def blow5_write_like(dst, like, fields, record_method=1, signal_method=1, index=
     fixed = rec[2 + idl:int(sp[0]) - 8].copy()          # read group, digitisation ... sampling rate
     post = rec[int(sp[0]) + int(sl[0]):].copy()         # auxiliary fields
     w = ctypes.c_void_p()
-    if lib.press_hip_blow5_create(dst.encode(), rd._h, record_method, signal_method, ctypes.byref(w)):
+    try:
+        _blow5_call("press_hip_blow5_create", dst.encode(), rd._h, record_method, signal_method, ctypes.byref(w))
+    finally:
         rd.close()
-        raise PressError(lib.press_hip_blow5_last_error().decode())
-    rd.close()
     out_ids = []
     try:
         if index:
@@ -2456,10 +1784,9 @@ def blow5_write_like(dst, like, fields, record_method=1, signal_method=1, index=
                 f = fields[k]
                 sigs.append(f if isinstance(f, np.ndarray) else np.frombuffer(f, dtype=np.uint8))
                 posts.append(post)
-            _blow5_write_batch(lib, w, pres, sigs, posts)
+            _blow5_write_batch(w, pres, sigs, posts)
     finally:
-        if lib.press_hip_blow5_finish(w):
-            raise PressError(lib.press_hip_blow5_last_error().decode())
+        _blow5_call("press_hip_blow5_finish", w)
     return out_ids
 
 
@@ -2486,19 +1813,13 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
     if passthrough and degrade_bits:
         raise PressError("passthrough keeps the signal fields as they are: it cannot degrade them")
     lib = load_library()
-    _blow5_writer_api(lib)
     rd = Blow5Reader(src)
-    lib.press_hip_blow5_next_records.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64] + \
-        [ctypes.c_void_p] * 5 + [ctypes.POINTER(ctypes.c_uint32)]
-    lib.press_hip_blow5_create.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                           ctypes.POINTER(ctypes.c_void_p)]
-    lib.press_hip_blow5_write.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                          ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
-    lib.press_hip_blow5_finish.argtypes = [ctypes.c_void_p]
     w = ctypes.c_void_p()
-    if lib.press_hip_blow5_create(dst.encode(), rd._h, record_method, signal_method, ctypes.byref(w)):
+    try:
+        _blow5_call("press_hip_blow5_create", dst.encode(), rd._h, record_method, signal_method, ctypes.byref(w))
+    except PressError:
         rd.close()
-        raise PressError(lib.press_hip_blow5_last_error().decode())
+        raise
     total = 0
     try:
         if index:
@@ -2509,9 +1830,8 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
         ns = np.zeros(maxr, dtype=np.uint32)
         got = ctypes.c_uint32()
         while True:
-            if lib.press_hip_blow5_next_records(rd._h, maxr, arena.ctypes.data, cap, ro.ctypes.data, rl.ctypes.data,
-                                                sp.ctypes.data, sl.ctypes.data, ns.ctypes.data, ctypes.byref(got)):
-                raise PressError(lib.press_hip_blow5_last_error().decode())
+            _blow5_call("press_hip_blow5_next_records", rd._h, maxr, _ptr(arena), cap, _ptr(ro), _ptr(rl), _ptr(sp), _ptr(sl),
+                        _ptr(ns), ctypes.byref(got))
             if got.value == 0:
                 break
             recs = [arena[int(ro[k]):int(ro[k]) + int(rl[k])] for k in range(got.value)]
@@ -2548,12 +1868,11 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
             else:
                 out = [np.ascontiguousarray(s, dtype=np.int16).tobytes()
                        for s in (degrade_batch_host(sigs, degrade_bits) if degrade_bits else sigs)]
-            _blow5_write_batch(lib, w, [r[:int(sp[k]) - 8] for k, r in enumerate(recs)],
+            _blow5_write_batch(w, [r[:int(sp[k]) - 8] for k, r in enumerate(recs)],
                                [np.frombuffer(out[k], dtype=np.uint8) for k in range(got.value)],
                                [r[int(sp[k]) + int(sl[k]):] for k, r in enumerate(recs)])
             total += got.value
     finally:
         rd.close()
-        if lib.press_hip_blow5_finish(w):
-            raise PressError(lib.press_hip_blow5_last_error().decode())
+        _blow5_call("press_hip_blow5_finish", w)
     return total

@@ -33,6 +33,53 @@ def test_header_symbols_exported(lib):
     assert set(press.HEADER_SYMBOLS) == decl
 
 
+def _declared_prototypes():
+    """name -> (return type, [parameter declarations]) of every function include/press_hip.h declares, as C text"""
+    src = open(os.path.join(ROOT, "include", "press_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)  # (a return type is not to reach back into a #define)
+    decl = re.findall(r"((?:\b[A-Za-z_][A-Za-z0-9_]*\b[\s*]+)+)\b([a-z_][a-z0-9_]*)\s*\(([^;{]*)\)\s*;", src)
+    out = {}
+    for ret, name, params in decl:
+        ret = re.sub(r"\s*\*\s*", " *", " ".join(ret.split())).strip()
+        ret = re.sub(r"^(?:extern|static|inline)\s+", "", ret)
+        params = " ".join(params.split())
+        out[name] = (ret, [] if params in ("", "void") else [p.strip() for p in params.split(",")])
+    return out
+
+
+def _c_class(text, is_return):
+    """the ctypes class a C parameter declaration or return type must be bound as"""
+    import ctypes
+
+    if "*" in text or "[" in text:
+        return ctypes.c_char_p if re.match(r"const char \*[a-z_]*$", text) else ctypes.c_void_p
+    scalar = {"int": ctypes.c_int, "int16_t": ctypes.c_int16, "uint32_t": ctypes.c_uint32, "unsigned int": ctypes.c_uint32,
+              "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t}
+    if is_return:
+        scalar.update({"void": None, "bool": ctypes.c_bool})
+        return scalar[text]
+    return scalar[text.rsplit(" ", 1)[0]]  # (every parameter of the header is named)
+
+
+def test_prototypes_match_header():
+    """the table honours_amd/abi.py binds the library with says what the header says: for every declared function the
+    same number of parameters, each of the ctypes class of its C type (a pointer or array: c_void_p, `const char *`:
+    c_char_p), and the same return type.  A wrong arity, or a uint64_t bound as c_uint32, fails here and not at the first
+    large value."""
+    from honours_amd import abi
+
+    decl = _declared_prototypes()
+    assert set(decl) == _declared_symbols() and len(decl) >= 200
+    assert set(abi.PROTOS) == set(decl) and press.HEADER_SYMBOLS == sorted(decl)
+    for name, (ret, params) in sorted(decl.items()):
+        restype, argtypes = abi.PROTOS[name]
+        assert len(argtypes) == len(params), (name, len(argtypes), params)
+        for k, (got, text) in enumerate(zip(argtypes, params)):
+            assert got is _c_class(text, False), (name, k, text, got)
+        assert restype is _c_class(ret, True), (name, ret, restype)
+
+
 def test_bounds_match_oracle(lib, oracle):
     """X_bound is host arithmetic: same values as the oracle"""
     for m in press.METHODS:

@@ -39,17 +39,9 @@ class Lib:
 
     def __init__(self, path, torch, table):
         self.l = l = ctypes.CDLL(path)
-        l.press_hip_last_error.restype = ctypes.c_char_p
-        l.press_hip_set_stream.argtypes = [ctypes.c_void_p]
-        l.press_hip_load_table_file.argtypes = [ctypes.c_char_p]
-        l.press_hip_bound.restype = ctypes.c_uint64
-        l.press_hip_bound.argtypes = [ctypes.c_int, ctypes.c_uint32]
-        V, U32, U64, I = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
-        l.press_hip_press_batch.argtypes = [I, V, V, V, U32, U64, V, V, V, I]
-        l.press_hip_depress_batch.argtypes = [I, V, V, V, U32, V, V, V, U64, V, I]
-        if hasattr(l, "press_hip_press_packed"):
-            l.press_hip_press_packed.argtypes = [I, V, V, V, U32, U64, V, U64, U32, V, V, I]
-            l.press_hip_press_sizes.argtypes = [I, V, V, V, U32, U64, V, I]
+        from honours_amd import abi
+
+        abi.declare(l, optional=True)  # (an older build lacks some of the table's symbols)
         self.ok(l.press_hip_set_device(torch.cuda.current_device()))
         self.ok(l.press_hip_set_stream(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
         self.ok(l.press_hip_load_table_file(table.encode()))
