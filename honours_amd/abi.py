@@ -144,6 +144,11 @@ PROTOS = {
     "press_hip_rcf_bound": (Q, [I, I, U]),
     "press_hip_rcf_press_batch": (I, [I, I] + SIG + [P, P, P, P, I]),
     "press_hip_rcf_depress_batch": (I, [I, I] + IN + [P, P, P, Q, P, I]),
+    "press_hip_rice_bound": (Q, [I, U]),
+    "press_hip_rice_press_batch": (I, [I] + SIG + [P, P, P, P, I]),
+    "press_hip_rice_press_sizes": (I, [I] + SIG + [P, P, I]),
+    "press_hip_rice_depress_batch": (I, [I] + IN + [P, P, P, Q, P, I]),
+    "press_hip_rice_repairs": (I, [P]),
     "press_hip_blow5_open": (I, [S, P]),
     "press_hip_blow5_close": (None, [P]),
     "press_hip_blow5_methods": (I, [P, P, P]),
@@ -173,8 +178,8 @@ _PER_READ = {
 }
 for _syms in _SYMS.values():
     PROTOS.update(zip(_syms[:3], _PER_READ[_syms[3]]))
-# the stall methods and the sixteen coder_layout_zd pairs are called as "vb"
-for _m in list(STALL_METHODS) + ["%s_%s_zd" % (c, l) for c in RCF_CODERS for l in RCF_LAYOUTS]:
+# the stall methods, the sixteen coder_layout_zd pairs and the four rice_layout_zd methods are called as "vb"
+for _m in list(STALL_METHODS) + ["%s_%s_zd" % (c, l) for c in list(RCF_CODERS) + ["rice"] for l in RCF_LAYOUTS]:
     PROTOS.update(zip((_m + "_bound_16", _m + "_press_16", _m + "_depress_16"), _PER_READ["vb"]))
 
 # the degraded forms: plain name -> (degraded name, the leading method ids `bits` goes behind)

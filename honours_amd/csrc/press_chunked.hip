@@ -2513,6 +2513,21 @@ void launch_ex_encode_packed(const BatchArgs &a, int fmt, int ent, const PackArg
 		ex_encode_streams(a, fmt, ent, s);
 }
 
+// press_hip_rice_press_sizes: the chain up to the exception lists as the packed press runs it (k_chunk_prep leaves status 0,
+// so k_low_encode_chunked writes every read's one-byte values to a.low_tmp without a section in front), k_ex_sizes for
+// header and section, then the Rice count and pick.  Nothing of the caller's but need[] is written.
+void launch_ex_rice_sizes(const BatchArgs &a, int fmt, uint64_t *need, hipStream_t s)
+{
+	if (!a.nreads || !a.max_chunks)
+		return;
+	ex_encode_prep(a, s);
+	ex_pass_a(a, 6, s);
+	ex_encode_lists(a, fmt, s);
+	launch_ex_sizes(a, fmt, 6, need, s);
+	hipLaunchKernelGGL(k_low_encode_chunked<false>, dim3(a.max_chunks), dim3(CWG), 0, s, a);
+	launch_rice_encode(a, need, s);
+}
+
 // Recode, fused (press_hip_recode_batch): the svb decode of `d` leaves pass A's results in the chunk table of the press
 // `p`, whose sample counts p.nsamp are the decoder's verdicts (0 for a read it refuses) - known before the main kernel
 // runs, k_svb_keyprefix gives them.  d.sig == p.sig, d.off == p.off; the two sides have a chunk table, a first-chunk list
@@ -2676,8 +2691,10 @@ static void ex_encode_streams(const BatchArgs &a, int fmt, int ent, hipStream_t 
 			launch_rcc_encode(a, s);
 		else if (ent == 4)
 			launch_rcm_encode(a, s);
-		else
+		else if (ent == 5)
 			launch_cdf_encode(a, s);
+		else
+			launch_rice_encode(a, nullptr, s);
 		ktime_end(0, s);
 		return;
 	}

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "press_host.h"
+#include "press_rice_walk.h"
 
 using namespace ph;
 
@@ -166,6 +167,46 @@ void rcf_depress_(int coder, int layout, const uint8_t *in, uint64_t nbytes, int
 	uint32_t cap = *nout, got = UINT32_MAX;
 	int rc = cap ? press_hip_rcf_depress_batch(coder, layout, in, ioff, ilen, 1, out, off, &cap, cap, &got, 0)
 		     : set_error(PRESS_HIP_EARG, "no room for samples");
+	if (!rc && got == UINT32_MAX)
+		rc = set_error(-1, "malformed stream");
+	if (rc) {
+		fprintf(stderr, "press_hip: %s\n", press_hip_last_error());
+		got = 0;
+	}
+	*nout = got;
+}
+
+// the Rice family: one read through press_hip_rice_press_batch / press_hip_rice_depress_batch
+void rice_press_(int layout, const int16_t *in, uint32_t n, uint8_t *out, uint64_t *nout)
+{
+	const uint64_t off[1] = { 0 };
+	const uint64_t ooff[2] = { 0, *nout };
+	uint64_t l = PRESS_HIP_FAILED;
+	int rc = n ? press_hip_rice_press_batch(layout, in, off, &n, 1, n, out, ooff, &l, nullptr, 0) : set_error(PRESS_HIP_EARG, "empty read");
+	if (!rc && l == PRESS_HIP_FAILED)
+		rc = set_error(-1, "stream does not fit %llu bytes", (unsigned long long) *nout);
+	if (rc) {
+		fprintf(stderr, "press_hip: %s\n", press_hip_last_error());
+		l = 0;
+	}
+	*nout = l;
+}
+
+// nsamples: the read's SAMPLE count, as the reference's symbols take it (press.c:5050); the stream's length is found by
+// reading it (press_rice_walk.h)
+void rice_depress_(int layout, const uint8_t *in, uint64_t nsamples, int16_t *out, uint32_t *nout)
+{
+	const uint64_t off[1] = { 0 };
+	const uint64_t ioff[1] = { 0 };
+	uint64_t ilen[1] = { 0 };
+	uint32_t n = (uint32_t) nsamples, got = UINT32_MAX;
+	int rc;
+	if (n == 0 || nsamples > *nout)
+		rc = set_error(PRESS_HIP_EARG, "no room for samples");
+	else if (!rice_stream_len(layout, in, n, ilen))
+		rc = set_error(-1, "malformed stream");
+	else
+		rc = press_hip_rice_depress_batch(layout, in, ioff, ilen, 1, out, off, &n, n, &got, 0);
 	if (!rc && got == UINT32_MAX)
 		rc = set_error(-1, "malformed stream");
 	if (rc) {
@@ -449,5 +490,21 @@ RCF_FAMILY(rccdf_vbe21, PRESS_HIP_RCF_RCCDF, PRESS_HIP_RCF_VBE21)
 RCF_FAMILY(rccdf_vbbe21, PRESS_HIP_RCF_RCCDF, PRESS_HIP_RCF_VBBE21)
 RCF_FAMILY(rccdf_vbsbe21, PRESS_HIP_RCF_RCCDF, PRESS_HIP_RCF_VBSBE21)
 RCF_FAMILY(rccdf_vbsse21, PRESS_HIP_RCF_RCCDF, PRESS_HIP_RCF_VBSSE21)
+
+// ---- the four methods of the Rice family (press.h:673-701); depress: nin is the sample count
+#define RICE_FAMILY(name, layout)                                                                \
+	uint64_t name##_zd_bound_16(uint32_t nin) { return press_hip_rice_bound(layout, nin); }  \
+	void name##_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout)   \
+	{                                                                                        \
+		rice_press_(layout, in, nin, out, nout);                                         \
+	}                                                                                        \
+	void name##_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout)       \
+	{                                                                                        \
+		rice_depress_(layout, in, nin, out, nout);                                       \
+	}
+RICE_FAMILY(rice_vbe21, PRESS_HIP_RCF_VBE21)
+RICE_FAMILY(rice_vbbe21, PRESS_HIP_RCF_VBBE21)
+RICE_FAMILY(rice_vbsbe21, PRESS_HIP_RCF_VBSBE21)
+RICE_FAMILY(rice_vbsse21, PRESS_HIP_RCF_VBSSE21)
 
 } // extern "C"

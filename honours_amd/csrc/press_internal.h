@@ -129,6 +129,33 @@ struct ChunkCtl {                           // device control block; every word 
 	uint32_t pad5[31];
 };
 
+// The Rice methods (press_rice.hip).  Press: a read's one-byte values in units of RICE_UNIT, a wave each; unit i of a read is
+// entry RICE_UPC * first_chunk + i of the unit tables.  Depress: the payload in subsequences of RICE_SUB bits, a lane each,
+// RICE_DT of them a tile.
+constexpr uint32_t RICE_UNIT = 1024;
+constexpr uint32_t RICE_UPC = CHUNK / RICE_UNIT;
+constexpr uint32_t RICE_COPY = 1280; // payload bytes per unit index in k_rice_copy: more than RICE_UNIT values at nine bits take
+constexpr uint32_t RICE_SUB = 256;
+constexpr uint32_t RICE_DT = 256;
+constexpr uint32_t RICE_CTL_WORDS = 16; // DecodeArgs::ri_ctl: tiles; subsequences decoded again by fix round 1, 2; values of the walk
+struct RiceRead {             // press, per read (k_rice_pick)
+	uint64_t nbits;       // payload bits
+	uint64_t paylen;      // ... and bytes
+	uint32_t k;
+	uint32_t ok;          // 0: refused (k_ex_section), or the slot is too small
+	uint32_t nlow, nunits;
+};
+struct RiceDRead {            // depress, per read (k_rice_dplan)
+	uint64_t paylen;      // payload bytes
+	uint64_t wpos, widx;  // where the serial walk starts: bit, value
+	uint32_t k;
+	uint32_t nsubs;       // subsequences decoded in parallel
+	uint32_t tile0;       // first tile
+	uint32_t nlow;
+	uint32_t hmin;        // first subsequence that is not settled (nsubs: none)
+	uint32_t ok;          // k_ex_parse accepted the read
+};
+
 // Arguments common to every batch kernel.
 struct BatchArgs {
 	const int16_t *sig;       // samples of all reads
@@ -154,6 +181,13 @@ struct BatchArgs {
 	                          // encoder has them in registers (zeroed by the caller; NULL for the other methods)
 	uint32_t *zkcnt;          // ... and [max_chunks] at a read's FIRST chunk: the read's key bytes that are not zero (with zhist;
 	                          // their positions and values are listed in ex_pos / ex_val of the read, in order)
+	// the Rice methods (press_rice.hip; NULL for the other methods)
+	uint32_t *ri_sum;         // [max_chunks * RICE_UPC][8] per unit: the sums of x >> k
+	uint64_t *ri_start;       // [max_chunks * RICE_UPC] per unit: its first bit of the read's payload
+	RiceRead *ri_rd;          // [nreads]
+	uint8_t *ri_pay;          // the staged payloads: read r's at 2 * off[r], ri_pay_bytes in all
+	uint64_t ri_pay_bytes;
+	uint8_t *ri_k;            // [nreads] the caller's k[], or NULL
 };
 
 struct HufTile {             // one tile of a read's Huffman payload (press_huffman.hip), 32 bytes
@@ -198,6 +232,13 @@ struct DecodeArgs {
 	uint32_t max_htiles;
 	uint32_t hlist_cap;
 	uint32_t huf_minlen;      // shortest code of the table (selects the subsequence size on the host)
+	// the Rice methods (press_rice.hip; NULL for the other methods)
+	RiceDRead *ri_drd;        // [nreads]
+	uint2 *ri_tile;           // [ri_max_tiles] { read, tile of the read }
+	uint32_t *ri_rec;         // [ri_max_tiles * RICE_DT][3] per subsequence: start, end, codes
+	uint64_t *ri_tbase;       // [2 * ri_max_tiles] per tile: the read's codes in front of it; behind them: the tiles' own counts
+	uint32_t *ri_ctl;         // [RICE_CTL_WORDS]
+	uint32_t ri_max_tiles;
 };
 
 // zstd frames on the device (press_zstd.hip, zs_table.h): scratch of one batch
@@ -476,7 +517,7 @@ void launch_stall_parse(const uint8_t *in, const uint64_t *in_off, const uint64_
 			const StallBufs &b, hipStream_t s);
 void launch_stall_scatter(int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint32_t *out_n,
 			  hipStream_t s);
-void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing, 5 nibble-CDF coder
+void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing, 5 nibble-CDF coder, 6 Golomb-Rice
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip
 void launch_huff_decode(const DecodeArgs &a, uint32_t minlen, hipStream_t s);      // press_huffman.hip
@@ -489,6 +530,11 @@ void launch_rcm_encode(const BatchArgs &a, hipStream_t s);  // order 1-0 context
 void launch_rcm_decode(const DecodeArgs &a, hipStream_t s);
 void launch_cdf_encode(const BatchArgs &a, hipStream_t s);  // ent 5: the adaptive nibble-CDF coder (rccdf_*_zd), press_cdf.hip
 void launch_cdf_decode(const DecodeArgs &a, hipStream_t s);
+// ent 6: Golomb-Rice (rice_*_zd), press_rice.hip.  need != NULL: k_rice_count and k_rice_pick alone, need[r] += the payload's bytes
+void launch_rice_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);
+void launch_rice_decode(const DecodeArgs &a, hipStream_t s);
+// press_hip_rice_press_sizes: the press chain of ent 6 as far as the sizes; a.out_off: nreads + 1 zeros, a.out_len == need
+void launch_ex_rice_sizes(const BatchArgs &a, int fmt, uint64_t *need, hipStream_t s); // press_chunked.hip
 // behind the encode of a range-coder method (ent >= 2): raw[r] = 1 where the coder gave up and stored the one-byte values
 void launch_rcf_raw(const BatchArgs &a, uint8_t *raw, hipStream_t s);
 // symbol counts of a batch for fitting a Huffman table (press_train.hip): adds into counts[257]; chunks takes

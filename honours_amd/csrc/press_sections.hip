@@ -220,12 +220,13 @@ __global__ __launch_bounds__(64) void k_ex_section(BatchArgs a, int fmt, int huf
 	}
 	const uint64_t nlow = (uint64_t) (n - 1) - nex;
 	// one-byte stream: raw, or at least the 4-byte count of the Huffman stream
-	// (huff: 0 plain, 1 / 2 static Huffman (v1 / chunked pass B), 3 range coder: its stream is sized by k_rcs_encode)
-	const uint64_t need = hdr + seclen + (huff == 3 ? 0 : huff ? 4 : nlow);
+	// (huff: 0 plain, 1 / 2 static Huffman (v1 / chunked pass B), 3 range coder: its stream is sized by k_rcs_encode,
+	// 4 Golomb-Rice: sized by k_rice_pick, and the splice holds for a section of any length)
+	const uint64_t need = hdr + seclen + (huff >= 3 ? 0 : huff ? 4 : nlow);
 	if (need > cap)
 		return;
 	// press.c:4520,4636,4752: the b/sb/ss Huffman variants keep the section length in a uint16_t
-	if (huff && fmt != EXF_VBE21 && seclen > 65535) // (the entropy-coded b/sb/ss forms keep this length in a uint16_t: press.c:4520, 6917)
+	if (huff && huff != 4 && fmt != EXF_VBE21 && seclen > 65535) // (the entropy-coded b/sb/ss forms keep this length in a uint16_t: press.c:4520, 6917)
 		return;
 	// ex_zd.c:411: the reference works in a 2n+1024-byte buffer
 	if (fmt == EXF_EXZD && need > 2ull * n + 1024)
@@ -295,6 +296,7 @@ __global__ __launch_bounds__(64) void k_ex_section(BatchArgs a, int fmt, int huf
 //   plain          hdr + seclen + nlow
 //   static Huffman hdr + seclen + 4 + the read's code bits (ChunkBits of its last chunk, k_ex_prefix) in whole bytes
 //   range coders   hdr + seclen + nlow + RC_PACK_SLACK: the smallest slot certain to hold the coded stream
+//   Golomb-Rice    hdr + seclen: k_rice_pick adds the payload's exact length
 // One wave per read, after k_ex_list.
 __global__ __launch_bounds__(64) void k_ex_sizes(BatchArgs a, int fmt, int huff, uint64_t *need)
 {
@@ -326,8 +328,10 @@ __global__ __launch_bounds__(64) void k_ex_sizes(BatchArgs a, int fmt, int huff,
 			size = hdr + seclen + 4 + (bits + 7) / 8;
 		} else if (huff == 3) {
 			size += RC_PACK_SLACK;
+		} else if (huff == 4) {
+			size = hdr + seclen; // k_rice_pick adds the payload
 		}
-		if (huff && fmt != EXF_VBE21 && seclen > 65535) // the uint16_t section length (press.c:4520, 6917)
+		if (huff && huff != 4 && fmt != EXF_VBE21 && seclen > 65535) // the uint16_t section length (press.c:4520, 6917)
 			size = FAIL64;
 		if (fmt == EXF_EXZD && hdr + seclen + nlow > 2ull * n + 1024) // ex_zd.c:411
 			size = FAIL64;
@@ -603,14 +607,14 @@ __global__ __launch_bounds__(64) void k_ex_parse_fill_vbe21(DecodeArgs a)
 
 void launch_ex_section(const BatchArgs &a, int fmt, int ent, hipStream_t s)
 {
-	hipLaunchKernelGGL(k_ex_section, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent >= 2 ? 3 : 0);
+	hipLaunchKernelGGL(k_ex_section, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent == 6 ? 4 : ent >= 2 ? 3 : 0);
 	if (fmt == EXF_VBE21)
 		hipLaunchKernelGGL(k_ex_fill_vbe21, dim3(a.nreads), dim3(64), 0, s, a);
 }
 
 void launch_ex_sizes(const BatchArgs &a, int fmt, int ent, uint64_t *need, hipStream_t s)
 {
-	hipLaunchKernelGGL(k_ex_sizes, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent >= 2 ? 3 : 0, need);
+	hipLaunchKernelGGL(k_ex_sizes, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent == 6 ? 4 : ent >= 2 ? 3 : 0, need);
 }
 
 // k_ex_parse and, for the Huffman variants, the stream decode into a.low (timed as the
@@ -630,6 +634,8 @@ void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s)
 			launch_rcm_decode(a, s);
 		else if (ent == 5)
 			launch_cdf_decode(a, s);
+		else if (ent == 6)
+			launch_rice_decode(a, s);
 		else
 			launch_huff_decode(a, a.huf_minlen, s);
 		ktime_end(1, s);

@@ -1100,7 +1100,17 @@ def rcf_depress_batch_host(coder, layout, streams, ns):
     return _reads_of(sig, off, out_n)
 
 
+# ---- the Rice family (press_hip_rice_*) has a module of its own, honours_amd/rice.py; its wrappers are reachable here too
 
+
+def __getattr__(name):
+    """press.rice_name, press.rice_press_batch ...: the functions of honours_amd.rice (PEP 562; the module is imported on
+    first use, it imports this one)"""
+    if name.startswith("rice_"):
+        from . import rice
+        if hasattr(rice, name):
+            return getattr(rice, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 VERIFIED = 0xFFFFFFFF  # PRESS_HIP_VERIFIED: first_bad of a read that decodes to the samples it is meant to hold

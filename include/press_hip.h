@@ -1238,7 +1238,8 @@ uint64_t press_hip_stall_workspace_bytes(int stall_method, uint64_t total_sample
  * argument (raw excepted) is PRESS_HIP_EARG before any device call; nreads == 0 is PRESS_HIP_OK.
  *
  * The family's ids are accepted by these calls alone: the recode, picoampere, normalise, chunk-row, verify, CRC, sizes
- * and packed calls do not learn them.  Not built: rccm_svb_zd, rccm_svb12_zd, the range-coder methods without zd, jumps.
+ * and packed calls do not learn them, and neither do the calls of the Rice family (2u), which takes the layout ids
+ * alone.  Not built: rccm_svb_zd, rccm_svb12_zd, the range-coder methods without zd, jumps.
  */
 enum press_hip_rcf_coder {
 	PRESS_HIP_RCF_RC      = 0,
@@ -1304,6 +1305,84 @@ void rccdf_vbsbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32
 uint64_t rccdf_vbsse21_zd_bound_16(uint32_t nin);
 void rccdf_vbsse21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
 void rccdf_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+
+/* ======================================================================= (2u) the Rice family */
+
+/*
+ * The reference's table-free entropy stage: rice_{vbe21, vbbe21, vbsbe21, vbsse21}_zd (press.h:664-701, press.c:4854-5390),
+ * Golomb-Rice coding of the read's one-byte values behind the layout's header and exception section.  No table, no
+ * adaptive state: a code's length is a function of the value and of one parameter k per read, so press is a count, a scan
+ * and a bit scatter and depress a self-synchronising prefix code, both parallel within a read.  A family with ids of its
+ * own like (2t): the layout ids are enum press_hip_rcf_layout; enum press_hip_method, PRESS_HIP_NMETHODS and the generic
+ * batch calls, the recode, picoampere, normalise, chunk-row, verify, CRC and packed calls do not know these methods.
+ *
+ * The stream.  With P(L) the plain stream of L_zd, nex its exception count, nlow = n - 1 - nex and
+ * sec(L) = P(L)[: len - nlow], the stream of rice_L_zd is sec(L) + rice(low), low being the read's nlow one-byte values
+ * (the same under all four layouts).  rice(low), press.c:4860-4924:
+ *   bit order  bit i of the payload is bit i % 8, counted from the least significant, of byte i / 8 (the opposite of the
+ *              Huffman stream)
+ *   k          bits 0, 1, 2 hold k >> 2 & 1, k >> 1 & 1, k & 1
+ *   a value x  x >> k one-bits, a zero bit, the low k bits of x from the most significant down
+ *   choice     k is the smallest of 0 .. 7 that minimises the sum of (x >> k) + 1 + k over the values, taken in 64 bits
+ *              (the reference compares with '<': ties go to the lower k); without a value, k = 0
+ *   length     nbits = 3 + that sum, (nbits - 1) / 8 + 1 bytes: never fewer than one
+ *
+ * Where the reference leaves a hole, this library defines:
+ *   1. padding    The reference builds the payload in an uninitialised block and touches only bits below nbits: the bits
+ *                 behind nbits in the last byte are whatever the heap held.  This library writes zeros there; "equal to
+ *                 the reference" means equal after clearing those bits of the reference's last byte.
+ *   2. decoder    (press.c:4927-4978) the unary run is counted modulo 256 (q is a uint8_t), however long it is; the value
+ *                 is (uint8_t) ((q << k) | rem).  The reference reads on behind the stream's end; this library reads
+ *                 nothing outside [in_off, in_off + in_len), and bits behind the end are zero (the rule of (2t): a stream
+ *                 that ends early is decoded with zeros behind its end).  A stream shorter than its own section is
+ *                 refused: out_n[r] = 0.
+ *   3. sections   For vbbe21, vbsbe21 and vbsse21 the reference keeps the section length in a uint16_t (press.c:5087 and
+ *                 its siblings) and mis-splices a section of 65536 bytes or more.  This library's stream is the splice
+ *                 above for any section length; it equals the reference's wherever the section is shorter than that.
+ *   4. tiny reads rice_bound(nlow) = nlow * 1.5 is smaller than the payload for nlow == 0 and for some reads with
+ *                 nlow == 1: the reference writes a byte past a block.  This library's stream is what the rules above
+ *                 give; for n = 1: the 2-byte first sample, the empty section (nex = 0), one payload byte 0x00.
+ *   5. bounds     press_hip_rice_bound is the reference's X_bound_16 (vb1e2_zd_bound_16 for all four; 0 for a bad id).
+ *                 The exact size is known before a byte is written (press_hip_rice_press_sizes).  A read whose slot is
+ *                 too small fails as in press_hip_press_batch (out_len[r] = PRESS_HIP_FAILED); the other reads are
+ *                 untouched.
+ *
+ *   k        NULL, or nreads bytes: the parameter read r was coded with (0 for a read that was refused); a device pointer
+ *            when device_resident
+ *   need[r]  press_hip_rice_press_sizes: the exact stream length of read r, section plus payload (PRESS_HIP_FAILED for an
+ *            empty read); no arena, nothing else is written
+ * Everything else - argument and layout rules, PRESS_HIP_EARG for a bad layout id or a NULL argument (k excepted) before
+ * any device call, nreads == 0, the host-pointer form, "device resident: the call only enqueues on the current stream",
+ * depress: n[r] is the read's exact sample count - is as for press_hip_rcf_press_batch / press_hip_rcf_depress_batch.
+ * Depress runs a fixed number of launches: subsequences whose guessed start is wrong are repaired in two rounds, what is
+ * still unsettled is decoded by a serial walk per read (slow, right for any stream).  press_hip_rice_repairs: the
+ * subsequences the two rounds decoded again and the values the walk decoded in the last depress call (it synchronises).
+ */
+uint64_t press_hip_rice_bound(int layout, uint32_t n);
+int press_hip_rice_press_batch(int layout, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			       uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len, uint8_t *k,
+			       int device_resident);
+int press_hip_rice_press_sizes(int layout, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+			       uint64_t total_samples, uint64_t *need, uint8_t *k, int device_resident);
+int press_hip_rice_depress_batch(int layout, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t nreads,
+				 int16_t *sig, const uint64_t *off, const uint32_t *n, uint64_t total_samples, uint32_t *out_n,
+				 int device_resident);
+int press_hip_rice_repairs(uint32_t *counts);
+
+/* the reference's per-read symbols (press.h:673-701), synchronous, as the range-coder symbols above: *nout of press the
+ * capacity in, the length out (0: refused); depress takes the SAMPLE count as nin (press.c:5050), *nout the capacity in */
+uint64_t rice_vbe21_zd_bound_16(uint32_t nin);
+void rice_vbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rice_vbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rice_vbbe21_zd_bound_16(uint32_t nin);
+void rice_vbbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rice_vbbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rice_vbsbe21_zd_bound_16(uint32_t nin);
+void rice_vbsbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rice_vbsbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t rice_vbsse21_zd_bound_16(uint32_t nin);
+void rice_vbsse21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+void rice_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
 
 /* ======================================================================= (3) BLOW5 files (host) */
 

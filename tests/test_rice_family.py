@@ -1,0 +1,486 @@
+"""The Rice family (include/press_hip.h section 2u, press_hip_rice_*): Golomb-Rice coding of the one-byte values on the four
+exception layouts, rice_{vbe21, vbbe21, vbsbe21, vbsse21}_zd.
+
+Without a GPU: the yardstick of tests/_rice.py against what the REAL reference made of the fixture's reads
+(tests/golden/ref_rice.json); what the fixture holds; header, symbols and Python mirror; the bound; bad arguments; the
+wrappers without a GPU.  On the GPU: the device's streams byte for byte against the yardstick, and back again; forged
+payloads against the yardstick's decoder.
+"""
+import inspect
+import os
+
+import numpy as np
+import pytest
+
+import _layouts as L
+import _rcf
+import _rice as R
+from honours_amd import press
+
+gpu = pytest.mark.gpu
+EARG = -2
+FAILED64 = (1 << 64) - 1
+FAILED32 = (1 << 32) - 1
+HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "press_hip.h")
+GUARD = 48
+FILL8, FILL16 = 0xA5, 0x5A5A
+CANARY = 0x5AC35AC3
+
+_cache = {}
+
+
+def reads_by_name():
+    if "reads" not in _cache:
+        _cache["reads"] = dict(R.named_reads())
+    return _cache["reads"]
+
+
+def expected(layout, s):
+    """the yardstick's (stream, k, nbits), computed once per (layout, read)"""
+    key = (layout, np.asarray(s).tobytes())
+    if key not in _cache:
+        _cache[key] = R.expected(layout, s)
+    return _cache[key]
+
+
+# ------------------------------------------------------------------ without a GPU
+
+@pytest.fixture(scope="module")
+def cpu_lib():
+    from honours_amd import build
+    build.build()
+    return press.load_library()
+
+
+def test_yardstick_equals_the_reference():
+    """encode() behind the plain layouts' sections reproduces every stream of the fixture - hash, length and k - and decode()
+    reads every payload back; the fixture's reads are the reads of _rice.named_reads()"""
+    ent = {e["name"]: e for e in R.fixture()["entries"]}
+    assert list(ent) == list(reads_by_name())
+    for name, s in reads_by_name().items():
+        e = ent[name]
+        assert e["n"] == len(s) and e["samples_sha256"] == R.sha(s.tobytes()), name
+        for layout in R.LAYOUTS:
+            f = e["methods"][R.name(layout)]
+            stream, k, nbits = expected(layout, s)
+            assert (len(stream), k, nbits % 8, R.sha(stream)) == (f["len"], f["k"], f["nbits_mod8"], f["sha256"]), (name, layout)
+            assert ("stream" in f) == (len(s) < 64) and (len(s) >= 64 or bytes.fromhex(f["stream"]) == stream), (name, layout)
+            assert stream == R.clear_padding(stream, nbits)
+            assert np.array_equal(R.decoded(layout, stream, R.head_len(layout, s), len(s)), s), (name, layout)
+
+
+def test_fixture_conditions():
+    """every case with n >= 3 has the reference's own round trip recorded as good; the lengths the issue quotes; every k"""
+    ent = {e["name"]: e for e in R.fixture()["entries"]}
+    ks = set()
+    for name, e in ent.items():
+        for m, f in e["methods"].items():
+            assert e["n"] < 3 or f["roundtrip"] is True, (name, m)
+            ks.add(f["k"])
+    assert ks == set(range(8))
+    real = [e for n, e in ent.items() if n.startswith("three_reads/")]
+    assert [e["n"] for e in real] == [7329, 155185, 95350]
+    assert [e["methods"]["rice_vbe21_zd"]["len"] for e in real] == [4821, 106327, 67467]
+    assert [e["methods"]["rice_vbe21_zd"]["k"] for e in real] == [3, 3, 4]
+    # n = 1: the 2-byte first sample (417 in zig-zag: 834), the empty section, one payload byte 0x00
+    one = ent["single-1"]["methods"]
+    assert all(f["stream"] == "4203" + "00" * 5 and f["k"] == 0 for f in one.values())
+
+
+def test_yardstick_decoder_rules():
+    """definition 2: the run counts modulo 256, the value is cut to a byte, bits behind the end are zero"""
+    assert R.decode(b"", 3) == bytes(3)
+    assert R.decode(bytes([0x02]) + bytes(16), 5) == bytes(5)                 # k = 2, zeros
+    assert R.decode(b"\xff" * 40, 3) == bytes([((40 * 8 - 3) % 256) << 7 & 255, 0, 0])  # k = 7: one run to the end
+    # k = 0, a run of 300 ones: 300 mod 256 = 44
+    bits = np.zeros(3 + 301, dtype=np.uint8)
+    bits[3:303] = 1
+    assert R.decode(np.packbits(bits, bitorder="little").tobytes(), 2) == bytes([44, 0])
+    for U, k in R.EVERY_K:
+        low = R.uniform_low(U)
+        payload, kk, nbits = R.encode(low)
+        assert kk == k and R.decode(payload, len(low)) == low
+    assert R.pick_k(bytes([255]) * 100)[0] == 7 and R.pick_k(bytes([1]) * 1000)[0] == 0 and R.pick_k(b"") == (0, 0)
+
+
+SYMBOLS = ["press_hip_rice_bound", "press_hip_rice_press_batch", "press_hip_rice_press_sizes", "press_hip_rice_depress_batch",
+           "press_hip_rice_repairs"] + [R.name(l) + s for l in R.LAYOUTS for s in ("_bound_16", "_press_16", "_depress_16")]
+WRAPPERS = ["rice_name", "rice_bound", "rice_press", "rice_depress", "rice_press_batch", "rice_press_batch_host",
+            "rice_press_sizes", "rice_press_sizes_host", "rice_depress_batch", "rice_depress_batch_host", "rice_repairs"]
+
+
+def test_symbols_header_and_mirror(cpu_lib):
+    from honours_amd import build, rice
+    header = open(HEADER).read()
+    for s in SYMBOLS:
+        assert hasattr(cpu_lib, s) and s in press.HEADER_SYMBOLS and s + "(" in header, s
+    flat = " ".join(header.split())
+    assert len(press.METHODS) == 19 and "PRESS_HIP_NMETHODS = 19" in flat  # a family of its own
+    for words in ("(2u) the Rice family", "1. padding", "2. decoder", "3. sections", "4. tiny reads", "5. bounds",
+                  "neither do the calls of the Rice family"):
+        assert words in header, words
+    assert "press_rice.hip" in build.SOURCES
+    public = sorted(n for n, f in vars(rice).items() if not n.startswith("_") and inspect.isfunction(f) and f.__module__ == rice.__name__)
+    assert public == sorted(WRAPPERS)
+    for w in WRAPPERS:
+        assert getattr(press, w) is getattr(rice, w)
+    assert press.rice_name("vbe21") == "rice_vbe21_zd" and press.rice_name(3) == "rice_vbsse21_zd"
+    with pytest.raises(AttributeError):
+        press.rice_nothing
+
+
+def test_bound_is_the_plain_layouts(cpu_lib, oracle):
+    for l in R.LAYOUTS:
+        for n in (1, 2, 7, 8, 9, 1000, 7329, 155185, 5724000):
+            b = oracle.bound(l + "_zd", n)
+            assert press.rice_bound(l, n) == press.rcf_bound("rc", l, n) == b
+            assert cpu_lib.press_hip_rice_bound(press.RCF_LAYOUTS[l], n) == b and getattr(cpu_lib, R.name(l) + "_bound_16")(n) == b
+    for bad in (-1, 4, 1000):
+        assert cpu_lib.press_hip_rice_bound(bad, 100) == 0
+
+
+def test_bad_arguments(cpu_lib):
+    """a bad layout id and NULL arguments (k excepted) are PRESS_HIP_EARG before any device call"""
+    lib = cpu_lib
+    a = np.zeros(64, dtype=np.uint64)
+    p = a.ctypes.data
+    for form in (0, 1):
+        for bad in (-1, 4, 1000):
+            assert lib.press_hip_rice_press_batch(bad, p, p, p, 1, 8, p, p, p, None, form) == EARG
+            assert "layout" in press.last_error()
+            assert lib.press_hip_rice_press_sizes(bad, p, p, p, 1, 8, p, None, form) == EARG
+            assert lib.press_hip_rice_depress_batch(bad, p, p, p, 1, p, p, p, 8, p, form) == EARG
+            assert lib.press_hip_rice_press_batch(bad, p, p, p, 0, 0, p, p, p, None, form) == EARG  # (an empty batch too)
+        for k in range(6):
+            args = [p] * 6
+            args[k] = None
+            assert lib.press_hip_rice_press_batch(0, args[0], args[1], args[2], 1, 8, args[3], args[4], args[5], None, form) == EARG
+        for k in range(4):
+            args = [p] * 4
+            args[k] = None
+            assert lib.press_hip_rice_press_sizes(1, args[0], args[1], args[2], 1, 8, args[3], None, form) == EARG
+        for k in range(7):
+            args = [p] * 7
+            args[k] = None
+            assert lib.press_hip_rice_depress_batch(2, args[0], args[1], args[2], 1, args[3], args[4], args[5], 8, args[6], form) == EARG
+    assert lib.press_hip_rice_press_batch(0, p + 2, p, p, 1, 8, p, p, p, None, 1) == EARG  # a device arena off 16 bytes
+    assert lib.press_hip_rice_repairs(None) == EARG
+
+
+def test_wrappers_without_gpu(cpu_lib):
+    """every wrapper of the family on a machine without a GPU: the pure ones answer, the others raise what the library
+    reports (or, the per-read symbols, return the reference's failure) - none falls back to anything"""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("this machine has a GPU")
+    reads = [_rcf.signal(5, 9), _rcf.signal(6, 40)]
+    streams = [expected("vbe21", s)[0] for s in reads]
+    for l in R.LAYOUTS:
+        assert press.rice_press(l, reads[0]) == (-1, b"")
+        ret, back = press.rice_depress(l, streams[0], 9)
+        assert ret == -1 and back.size == 0 and back.dtype == np.int16
+        for call in (lambda: press.rice_press_batch_host(l, reads), lambda: press.rice_press_batch_host(l, reads, want_k=True),
+                     lambda: press.rice_press_sizes_host(l, reads), lambda: press.rice_press_sizes_host(l, reads, want_k=True),
+                     lambda: press.rice_depress_batch_host(l, streams, [9, 40])):
+            with pytest.raises(press.PressError):
+                call()
+    z = lambda n, dt: torch.zeros(n, dtype=dt)  # noqa: E731
+    sig, off, n = z(64, torch.int16), z(2, torch.int64), z(2, torch.int32)
+    out, out_off, out_len, k = z(256, torch.uint8), z(3, torch.int64), z(2, torch.int64), z(2, torch.uint8)
+    for call in (lambda: press.rice_press_batch("vbe21", sig, off, n, out, out_off, out_len),
+                 lambda: press.rice_press_batch(1, sig, off, n, out, out_off, out_len, k=k),
+                 lambda: press.rice_press_sizes("vbsbe21", sig, off, n, out_len, k=k),
+                 lambda: press.rice_depress_batch("vbsse21", out, off, out_len, sig, off, n, n),
+                 press.rice_repairs):
+        with pytest.raises(press.PressError):
+            call()
+
+
+# ------------------------------------------------------------------ GPU plumbing
+
+@pytest.fixture(scope="module")
+def lib():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    lb = press.load_library()
+    press.use_torch_stream()
+    yield lb
+    torch.cuda.synchronize()
+    press.use_torch_stream()
+    torch.cuda.empty_cache()
+
+
+def _t(a, dtype=None):
+    import torch
+    a = np.ascontiguousarray(a)
+    if dtype is not None:
+        a = a.view(dtype)
+    return torch.from_numpy(a.copy()).cuda()
+
+
+def slot_for(n):
+    return 8 * n + 4096 if n else 32
+
+
+class PressRun:
+    """A batch in a scattered layout, the slots back to back from an odd offset; canaries in front of and behind out_len,
+    need and k, and every byte of the arena outside the streams and the slots of failed reads must keep its fill"""
+
+    def __init__(self, reads, caps=None, seed=1):
+        import torch
+        rng = np.random.default_rng(seed)
+        self.reads, self.nr = reads, len(reads)
+        sig, off = L.scatter_reads(rng, reads)
+        caps = [slot_for(len(r)) for r in reads] if caps is None else caps
+        self.out_off = L.slots(rng, np.asarray(caps, dtype=np.uint64))
+        self.sig, self.off = _t(sig), _t(off.astype(np.uint64), np.int64)
+        self.n = _t(np.array([len(r) for r in reads], dtype=np.uint32), np.int32)
+        self.d_out_off = _t(self.out_off, np.int64)
+        self.out = torch.full((int(self.out_off[-1]) + 64,), FILL8, dtype=torch.uint8, device="cuda")
+        self.out_len = torch.full((self.nr + 2 * GUARD,), CANARY, dtype=torch.int64, device="cuda")
+        self.k = torch.full((self.nr + 2 * GUARD,), FILL8, dtype=torch.uint8, device="cuda")
+
+    def _tables(self, want_k):
+        import torch
+        torch.cuda.synchronize()
+        ol = self.out_len.cpu().numpy().view(np.uint64)
+        kk = self.k.cpu().numpy()
+        assert (ol[:GUARD] == CANARY).all() and (ol[GUARD + self.nr:] == CANARY).all(), "out_len / need"
+        assert (kk[:GUARD] == FILL8).all() and (kk[GUARD + (self.nr if want_k else 0):] == FILL8).all(), "k"
+        self.out_len.fill_(CANARY)
+        self.k.fill_(FILL8)
+        return ol[GUARD:GUARD + self.nr].copy(), kk[GUARD:GUARD + self.nr].copy()
+
+    def run(self, layout, want_k=True):
+        """-> (streams (None: failed), k uint8 [nr])"""
+        press.rice_press_batch(layout, self.sig, self.off, self.n, self.out, self.d_out_off, self.out_len[GUARD:GUARD + self.nr],
+                               self.k[GUARD:GUARD + self.nr] if want_k else None)
+        ol, kk = self._tables(want_k)
+        out = self.out.cpu().numpy()
+        written = np.zeros(len(out), dtype=bool)
+        streams = []
+        for r in range(self.nr):
+            o, cap = int(self.out_off[r]), int(self.out_off[r + 1] - self.out_off[r])
+            if ol[r] == FAILED64:
+                streams.append(None)
+                written[o:o + cap] = True  # (a read that fails may leave its own slot in any state, as the generic calls do)
+            else:
+                assert ol[r] <= cap
+                written[o:o + int(ol[r])] = True
+                streams.append(out[o:o + int(ol[r])].tobytes())
+        assert (out[~written] == FILL8).all(), "a byte outside the streams was written"
+        self.out.fill_(FILL8)
+        return streams, kk
+
+    def sizes(self, layout, want_k=True):
+        """-> (need uint64 [nr], k); the arena keeps its fill"""
+        press.rice_press_sizes(layout, self.sig, self.off, self.n, self.out_len[GUARD:GUARD + self.nr],
+                               self.k[GUARD:GUARD + self.nr] if want_k else None)
+        need, kk = self._tables(want_k)
+        assert bool((self.out == FILL8).all())
+        return need, kk
+
+
+class DepressRun:
+    def __init__(self, streams, ns, seed=2):
+        import torch
+        rng = np.random.default_rng(seed)
+        self.ns = [int(n) for n in ns]
+        self.nr = len(streams)
+        arena, in_off, in_len = L.scatter_streams(rng, streams)
+        self.off, self.total = L.scatter_rooms(rng, self.ns, min_gap=8)
+        self.arena, self.in_off, self.in_len = _t(arena), _t(in_off, np.int64), _t(in_len, np.int64)
+        self.d_off, self.n = _t(self.off, np.int64), _t(np.array(self.ns, dtype=np.uint32), np.int32)
+        self.sig = torch.full((self.total,), FILL16, dtype=torch.int16, device="cuda")
+        self.out_n = torch.full((self.nr + 2 * GUARD,), CANARY, dtype=torch.int32, device="cuda")
+
+    def run(self, layout):
+        """-> samples per read (None: refused); nothing outside the rooms of the decoded reads is written"""
+        import torch
+        press.rice_depress_batch(layout, self.arena, self.in_off, self.in_len, self.sig, self.d_off, self.n,
+                                 self.out_n[GUARD:GUARD + self.nr])
+        torch.cuda.synchronize()
+        sig = self.sig.cpu().numpy()
+        on = self.out_n.cpu().numpy().view(np.uint32)
+        assert (on[:GUARD] == CANARY).all() and (on[GUARD + self.nr:] == CANARY).all(), "out_n"
+        on = on[GUARD:GUARD + self.nr]
+        got, spans = [], []
+        for r in range(self.nr):
+            o = int(self.off[r])
+            if on[r] == FAILED32:
+                got.append(None)
+                spans.append(0)
+            else:
+                assert on[r] == self.ns[r]
+                got.append(sig[o:o + self.ns[r]].copy())
+                spans.append(self.ns[r])
+        assert (sig[L.outside_rooms(self.total, self.off, spans)] == FILL16).all(), "a sample outside the decoded reads was written"
+        self.sig.fill_(FILL16)
+        self.out_n.fill_(CANARY)
+        return got
+
+
+def check_batch(layout, reads, seed, caps=None):
+    """press: streams and k equal to the yardstick's; depress: the device reads them back"""
+    run = PressRun(reads, caps=caps, seed=seed)
+    streams, k = run.run(layout)
+    for r, s in enumerate(reads):
+        want, wk, _ = expected(layout, s)
+        assert k[r] == wk, (layout, r, len(s))
+        assert streams[r] == want, (layout, r, len(s))
+    got = DepressRun(streams, [len(s) for s in reads], seed=seed + 1).run(layout)
+    for r, g in enumerate(got):
+        assert g is not None and np.array_equal(g, reads[r]), (layout, r, len(reads[r]))
+    return run, streams, k
+
+
+# ------------------------------------------------------------------ on the GPU
+
+@gpu
+@pytest.mark.parametrize("layout", R.LAYOUTS)
+def test_real_reads(lib, layout):
+    """1: the three real reads in one batch"""
+    reads = [s for _, s in _rcf.real_reads()]
+    _, streams, k = check_batch(layout, reads, seed=11)
+    assert list(k) == [3, 3, 4]
+    if layout == "vbe21":
+        assert [len(s) for s in streams] == [4821, 106327, 67467]
+    ent = {e["name"]: e for e in R.fixture()["entries"]}
+    for (name, _), st in zip(_rcf.real_reads(), streams):
+        assert R.sha(st) == ent[name]["methods"][R.name(layout)]["sha256"]
+
+
+@gpu
+@pytest.mark.parametrize("layout", R.LAYOUTS)
+def test_every_k(lib, layout):
+    """2: uniform values of [0, U) make every k of 0 .. 6 win, 100 values of 255 k = 7, and 1000 values of 1 tie between
+    k = 0 and k = 1: the lower wins"""
+    lows = [R.uniform_low(U) for U, _ in R.EVERY_K] + [bytes([255]) * 100, bytes([1]) * 1000]
+    want = [k for _, k in R.EVERY_K] + [7, 0]
+    assert [R.pick_k(low)[0] for low in lows] == want  # the yardstick first
+    costs = [int((np.frombuffer(bytes([1]) * 1000, dtype=np.uint8).astype(np.int64) >> k).sum()) + 1000 * (1 + k) for k in (0, 1)]
+    assert costs[0] == costs[1]
+    _, _, k = check_batch(layout, [_rcf.from_low(low) for low in lows], seed=21)
+    assert list(k) == want
+
+
+@gpu
+@pytest.mark.parametrize("layout", R.LAYOUTS)
+def test_long_runs(lib, layout):
+    """3: k = 0 and two runs of 255 ones, one at the end of a writer's unit, both across a reader's subsequence boundary"""
+    low = R.long_runs_low()
+    payload, k, nbits = R.encode(low)
+    bits = np.unpackbits(np.frombuffer(payload, dtype=np.uint8), bitorder="little")
+    assert k == 0 and bits[1026:1026 + 255].all() and not bits[1281] and bits[2258:2258 + 255].all() and not bits[2513]
+    assert 1026 // 256 != (1026 + 254) // 256 and 2258 // 256 != (2258 + 254) // 256
+    check_batch(layout, [_rcf.from_low(low), _rcf.from_low(low[::-1]), _rcf.from_low(bytes([255]) * 40 + low)], seed=31)
+
+
+def seam_reads():
+    if "seams" not in _cache:
+        _cache["seams"] = [_rcf.signal(400 + j, n, exr=0.01 if j % 3 == 0 else 0.0) for j in range(6, 18)
+                           for n in (2 ** j - 1, 2 ** j, 2 ** j + 1, 2 ** j + 2)]
+    return _cache["seams"]
+
+
+@gpu
+@pytest.mark.parametrize("layout", R.LAYOUTS)
+def test_seams(lib, layout):
+    """4: reads of 2^j - 1 .. 2^j + 2 samples, j = 6 .. 17, in one batch; the slots start at every residue modulo 8"""
+    reads = seam_reads()
+    caps = [len(expected(layout, s)[0]) + 1 + r % 5 for r, s in enumerate(reads)]
+    run, _, _ = check_batch(layout, reads, seed=41, caps=caps)
+    assert set(int(o) % 8 for o in run.out_off[:-1]) == set(range(8))
+
+
+@gpu
+@pytest.mark.parametrize("layout", R.LAYOUTS)
+def test_tiny_and_dense(lib, layout):
+    """5: n = 1, 2, 3, 9, 10, a constant read and a read with 14 % exceptions"""
+    reads = [_rcf.signal(100 + n, n) for n in (1, 2, 3, 9, 10)] + [np.full(3000, 417, dtype=np.int16),
+                                                                    _rcf.signal(7, 2000, exr=0.14, spread=127)]
+    _, streams, k = check_batch(layout, reads, seed=51)
+    assert len(streams[0]) == 7 and streams[0][2:] == bytes(5) and k[0] == 0
+
+
+@gpu
+@pytest.mark.parametrize("layout", R.LAYOUTS)
+def test_slots(lib, layout):
+    """6: a slot one byte short fails that read alone; press_hip_rice_press_sizes gives exactly the out_len of a press
+    with room, and k"""
+    reads = [_rcf.signal(61, 700), _rcf.signal(62, 12), _rcf.signal(63, 2000, exr=0.14, spread=127), _rcf.signal(64, 40000, exr=0.02),
+             _rcf.signal(65, 1)]
+    exp = [expected(layout, s)[0] for s in reads]
+    exact = PressRun(reads, caps=[len(e) for e in exp], seed=61)
+    streams, k = exact.run(layout)
+    assert streams == exp
+    need, k2 = exact.sizes(layout)
+    assert list(need) == [len(e) for e in exp] and np.array_equal(k, k2)
+    assert list(exact.sizes(layout, want_k=False)[0]) == [len(e) for e in exp]
+    for short in range(len(reads)):
+        got = PressRun(reads, caps=[len(e) - (r == short) for r, e in enumerate(exp)], seed=62 + short).run(layout, want_k=False)[0]
+        assert got == [None if r == short else e for r, e in enumerate(exp)], short
+    assert PressRun(reads[:4], caps=[0, 4, 5, 7], seed=69).run(layout)[0] == [None] * 4
+
+
+@gpu
+def test_forged_payloads(lib):
+    """7: payloads no press makes, behind the sections of valid streams: the decoder is total, gives what the yardstick's
+    decoder gives and writes nothing outside the rooms; the valid neighbours come back"""
+    layout = "vbe21"
+    s0, s1, s2 = _rcf.from_low(bytes(4097)), _rcf.from_low(bytes(300)), _rcf.signal(71, 5000, exr=0.01)
+    full = expected(layout, s2)[0]
+    h0, h1, h2 = (R.head_len(layout, s) for s in (s0, s1, s2))
+    never = expected(layout, s0)[0][:h0] + bytes([0x02]) + bytes(1600)  # k = 2, every code 3 bits: never synchronises
+    ones = expected(layout, s1)[0][:h1] + b"\xff" * 64                  # k = 7, one run to the end
+    cut = full[:h2 + (len(full) - h2) // 2]
+    short = expected(layout, s0)[0][:h0] + bytes([0x02])                # ... and a payload of one byte
+    long_run = expected(layout, s1)[0][:h1] + bytes([0x07]) + b"\xff" * 999 + bytes(8)  # k = 0, a run of 7997 ones, zeros
+    streams = [never, full, ones, full, cut, full, short, long_run]
+    ns = [len(s0), len(s2), len(s1), len(s2), len(s2), len(s2), len(s0), len(s1)]
+    heads = [h0, h2, h1, h2, h2, h2, h0, h1]
+    got = DepressRun(streams, ns, seed=71).run(layout)
+    for r, g in enumerate(got):
+        want = R.decoded(layout, streams[r], heads[r], ns[r])
+        assert g is not None and np.array_equal(g, want), r
+    assert np.array_equal(got[0], np.zeros(4098, dtype=np.int16)) and np.array_equal(got[1], s2)
+    assert press.rice_repairs()[2] > 0  # the walk had work
+    # a stream shorter than its own section is refused
+    assert DepressRun([full[:5], full], [len(s2), len(s2)], seed=72).run(layout)[0] is None
+
+
+@gpu
+def test_forms(lib):
+    """8: host form = device form; the twelve per-read symbols; the same bytes whatever the scratch held"""
+    import torch
+    reads = [s for _, s in _rcf.named_reads()[3:]] + [_rcf.real_reads()[0][1]]
+    caps = [slot_for(len(r)) for r in reads]
+    short = _rcf.real_reads()[0][1]
+    for layout in R.LAYOUTS:
+        dev, dk = PressRun(reads, seed=81).run(layout)
+        streams, k = press.rice_press_batch_host(layout, reads, caps=caps, want_k=True)
+        assert streams == dev and np.array_equal(k, dk) and press.rice_press_batch_host(layout, reads, caps=caps) == streams
+        need, k2 = press.rice_press_sizes_host(layout, reads, want_k=True)
+        assert list(need) == [len(s) for s in streams] and np.array_equal(k2, k)
+        back = press.rice_depress_batch_host(layout, streams, [len(r) for r in reads])
+        for r, g in enumerate(back):
+            assert np.array_equal(g, reads[r]), (layout, r)
+        assert press.rice_bound(layout, len(short)) == getattr(lib, R.name(layout) + "_bound_16")(len(short))
+        ret, one = press.rice_press(layout, short)
+        assert ret == 0 and one == expected(layout, short)[0]
+        ret, b = press.rice_depress(layout, one, len(short))
+        assert ret == 0 and np.array_equal(b, short)
+    assert press.rice_press_batch_host("vbe21", []) == [] and press.rice_depress_batch_host("vbe21", [], []) == []
+    p = PressRun(reads, seed=82)
+    first = p.run("vbbe21")
+    d = DepressRun(first[0], [len(r) for r in reads], seed=83)
+    for fill in (0x00, 0xFF, 0xA5):
+        torch.cuda.synchronize()
+        press.scratch_fill(fill)
+        again = p.run("vbbe21")
+        assert again[0] == first[0] and np.array_equal(again[1], first[1]), fill
+        press.scratch_fill(fill)
+        assert np.array_equal(p.sizes("vbbe21")[0], [len(s) for s in first[0]]), fill
+        press.scratch_fill(fill)
+        for r, g in enumerate(d.run("vbbe21")):
+            assert np.array_equal(g, reads[r]), (fill, r)
