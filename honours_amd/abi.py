@@ -149,6 +149,11 @@ PROTOS = {
     "press_hip_rice_press_sizes": (I, [I] + SIG + [P, P, I]),
     "press_hip_rice_depress_batch": (I, [I] + IN + [P, P, P, Q, P, I]),
     "press_hip_rice_repairs": (I, [P]),
+    "press_hip_huffman_bound": (Q, [I, U]),
+    "press_hip_huffman_press_batch": (I, [I] + SIG + [P, P, P, P, I]),
+    "press_hip_huffman_press_sizes": (I, [I] + SIG + [P, P, I]),
+    "press_hip_huffman_depress_batch": (I, [I] + IN + [P, P, P, Q, P, I]),
+    "press_hip_huffman_repairs": (I, [P]),
     "press_hip_blow5_open": (I, [S, P]),
     "press_hip_blow5_close": (None, [P]),
     "press_hip_blow5_methods": (I, [P, P, P]),
@@ -181,6 +186,9 @@ for _syms in _SYMS.values():
 # the stall methods, the sixteen coder_layout_zd pairs and the four rice_layout_zd methods are called as "vb"
 for _m in list(STALL_METHODS) + ["%s_%s_zd" % (c, l) for c in list(RCF_CODERS) + ["rice"] for l in RCF_LAYOUTS]:
     PROTOS.update(zip((_m + "_bound_16", _m + "_press_16", _m + "_depress_16"), _PER_READ["vb"]))
+# ... and the four huffman_layout_zd methods as "int"
+for _m in ["huffman_%s_zd" % l for l in RCF_LAYOUTS]:
+    PROTOS.update(zip((_m + "_bound_16", _m + "_press_16", _m + "_depress_16"), _PER_READ["int"]))
 
 # the degraded forms: plain name -> (degraded name, the leading method ids `bits` goes behind)
 DEGRADED = {"recode_batch": ("recode_degraded_batch", 2), "recode_sizes": ("recode_degraded_sizes", 2),

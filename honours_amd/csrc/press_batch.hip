@@ -1674,3 +1674,129 @@ extern "C" int press_hip_rice_repairs(uint32_t counts[3])
 	counts[0] = w[1], counts[1] = w[2], counts[2] = w[3];
 	return 0;
 }
+
+// ------------------------------------------------------------------ the per-read Huffman family: a code per read on every layout
+//
+// As the Rice family (rows of DHUF_METHODS); press reports the longest code of every read where the caller asks, and
+// press_hip_huffman_press_sizes runs the chain as far as the sizes.
+
+static int dhuf_args_ok(int layout, bool null_arg, uint32_t nreads, const void *dev_arena)
+{
+	if (!rice_ok(layout))
+		return set_error(PRESS_HIP_EARG, "per-read Huffman family: layout %d (0 vbe21, 1 vbbe21, 2 vbsbe21, 3 vbsse21)", layout);
+	return args_ok(NONE, NONE, null_arg, nreads, dev_arena, "sig");
+}
+
+extern "C" uint64_t press_hip_huffman_bound(int layout, uint32_t n)
+{
+	return rice_ok(layout) ? bound_vbzd(n) : 0; // press.c:3965, 4061, 4177, 4293: vb1e2_zd_bound_16 for all four
+}
+
+extern "C" int press_hip_huffman_press_batch(int layout, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+					     uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
+					     uint8_t *maxlen, int device_resident)
+{
+	API_LOCK;
+	int rc = dhuf_args_ok(layout, nreads && (!sig || !off || !n || !out || !out_off || !out_len), nreads,
+			      device_resident ? sig : nullptr);
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	ScratchPlan plan = make_plan(DHUF_METHODS[layout], total_samples, nreads, false);
+	if (maxlen && !device_resident)
+		plan.need(&Ctx::ri_k, nreads);
+	if ((rc = plan.reserve()))
+		return rc;
+	BatchArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	const SlotsOut host = { out, out_off, out_len };
+	SamplesIn in = { sig, off, n };
+	SlotsOut so = host;
+	Staged st(nreads, s);
+	if (!device_resident && ((rc = check_slots(out_off, nreads)) || (rc = st.layout(off, n, total_samples, "the sample range", true)) ||
+				 (rc = st.slots(host, so)) || (rc = st.samples(in, total_samples, in))))
+		return rc;
+	bind_io(a, in);
+	bind_io(a, so);
+	a.ri_k = device_resident ? maxlen : maxlen ? (uint8_t *) g.ri_k.p : nullptr;
+	if ((rc = launch_press(plan, a, s)) || device_resident)
+		return rc;
+	if (maxlen)
+		HIPCHK(hipMemcpyAsync(maxlen, a.ri_k, nreads, hipMemcpyDeviceToHost, s));
+	return st.fetch_streams(host);
+}
+
+extern "C" int press_hip_huffman_press_sizes(int layout, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+					     uint64_t total_samples, uint64_t *need, uint8_t *maxlen, int device_resident)
+{
+	API_LOCK;
+	int rc = dhuf_args_ok(layout, nreads && (!sig || !off || !n || !need), nreads, device_resident ? sig : nullptr);
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const size_t nr = (size_t) nreads + 1;
+	ScratchPlan plan = make_plan(DHUF_METHODS[layout], total_samples, nreads, false);
+	plan.need(&Ctx::pslot, nr * 8); // the slot table the chain is run against: all zeros
+	if (!device_resident)
+		plan.need(&Ctx::pneed, nr * 8).need(&Ctx::ri_k, nreads);
+	if ((rc = plan.reserve()))
+		return rc;
+	BatchArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	SamplesIn in = { sig, off, n };
+	Staged st(nreads, s);
+	if (!device_resident && (rc = st.samples_in(in, total_samples, in)))
+		return rc;
+	bind_io(a, in);
+	uint64_t *dneed = device_resident ? need : (uint64_t *) g.pneed.p;
+	HIPCHK(hipMemsetAsync(g.pslot.p, 0, nr * 8, s));
+	a.out_off = (const uint64_t *) g.pslot.p;
+	a.out_len = dneed;
+	a.ri_k = device_resident ? maxlen : maxlen ? (uint8_t *) g.ri_k.p : nullptr;
+	launch_ex_dhuf_sizes(a, DHUF_METHODS[layout].exfmt, dneed, s);
+	if ((rc = launch_status()) || device_resident)
+		return rc;
+	return st.fetch_tables({ { need, dneed, (size_t) nreads * 8 }, { maxlen, a.ri_k, nreads } });
+}
+
+extern "C" int press_hip_huffman_depress_batch(int layout, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+					       uint32_t nreads, int16_t *sig, const uint64_t *off, const uint32_t *n,
+					       uint64_t total_samples, uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	int rc = dhuf_args_ok(layout, nreads && (!in || !in_off || !in_len || !sig || !off || !n || !out_n), nreads,
+			      device_resident ? sig : nullptr);
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const ScratchPlan plan = make_plan(DHUF_METHODS[layout], total_samples, nreads, true);
+	if ((rc = plan.reserve()))
+		return rc;
+	DecodeArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	const StreamsIn host = { in, in_off, in_len, off, n, out_n, sig };
+	StreamsIn io = host;
+	Staged st(nreads, s);
+	if (!device_resident && (rc = st.streams(host, total_samples, true, g.arena, g.arena_off, io)))
+		return rc;
+	bind_io(a, io);
+	if ((rc = launch_depress(plan, a, s)) || device_resident)
+		return rc;
+	return st.fetch_samples(host);
+}
+
+// what the repair rounds and the serial walk of the last press_hip_huffman_depress_batch had to touch (the counters are
+// the Rice family's: the last depress call of either family)
+extern "C" int press_hip_huffman_repairs(uint32_t counts[3])
+{
+	return press_hip_rice_repairs(counts);
+}

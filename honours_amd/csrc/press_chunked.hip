@@ -2528,6 +2528,19 @@ void launch_ex_rice_sizes(const BatchArgs &a, int fmt, uint64_t *need, hipStream
 	launch_rice_encode(a, need, s);
 }
 
+// press_hip_huffman_press_sizes: the same chain with the per-read Huffman stage at its end (hist and tree)
+void launch_ex_dhuf_sizes(const BatchArgs &a, int fmt, uint64_t *need, hipStream_t s)
+{
+	if (!a.nreads || !a.max_chunks)
+		return;
+	ex_encode_prep(a, s);
+	ex_pass_a(a, 7, s);
+	ex_encode_lists(a, fmt, s);
+	launch_ex_sizes(a, fmt, 7, need, s);
+	hipLaunchKernelGGL(k_low_encode_chunked<false>, dim3(a.max_chunks), dim3(CWG), 0, s, a);
+	launch_dhuf_encode(a, need, s);
+}
+
 // Recode, fused (press_hip_recode_batch): the svb decode of `d` leaves pass A's results in the chunk table of the press
 // `p`, whose sample counts p.nsamp are the decoder's verdicts (0 for a read it refuses) - known before the main kernel
 // runs, k_svb_keyprefix gives them.  d.sig == p.sig, d.off == p.off; the two sides have a chunk table, a first-chunk list
@@ -2693,8 +2706,10 @@ static void ex_encode_streams(const BatchArgs &a, int fmt, int ent, hipStream_t 
 			launch_rcm_encode(a, s);
 		else if (ent == 5)
 			launch_cdf_encode(a, s);
-		else
+		else if (ent == 6)
 			launch_rice_encode(a, nullptr, s);
+		else
+			launch_dhuf_encode(a, nullptr, s);
 		ktime_end(0, s);
 		return;
 	}

@@ -6,6 +6,7 @@
 
 #include "press_host.h"
 #include "press_rice_walk.h"
+#include "press_dhuf_walk.h"
 
 using namespace ph;
 
@@ -214,6 +215,53 @@ void rice_depress_(int layout, const uint8_t *in, uint64_t nsamples, int16_t *ou
 		got = 0;
 	}
 	*nout = got;
+}
+
+// the per-read Huffman family: one read through press_hip_huffman_press_batch / press_hip_huffman_depress_batch
+int dhuf_press_(int layout, const int16_t *in, uint32_t n, uint8_t *out, uint64_t *nout)
+{
+	const uint64_t off[1] = { 0 };
+	const uint64_t ooff[2] = { 0, *nout };
+	uint64_t l = PRESS_HIP_FAILED;
+	int rc = n ? press_hip_huffman_press_batch(layout, in, off, &n, 1, n, out, ooff, &l, nullptr, 0) : set_error(PRESS_HIP_EARG, "empty read");
+	if (!rc && l == PRESS_HIP_FAILED)
+		rc = set_error(-1, "stream does not fit %llu bytes", (unsigned long long) *nout);
+	if (rc) {
+		fprintf(stderr, "press_hip: %s\n", press_hip_last_error());
+		*nout = 0;
+		return -1;
+	}
+	*nout = l;
+	return 0;
+}
+
+// nbytes: the stream's length, *nout the capacity in samples (press.c:4011); the sample count the batch call wants is
+// read from the stream (press_dhuf_walk.h), and a stream that says more than the capacity is refused
+int dhuf_depress_(int layout, const uint8_t *in, uint64_t nbytes, int16_t *out, uint32_t *nout)
+{
+	const uint64_t off[1] = { 0 };
+	const uint64_t ioff[1] = { 0 };
+	const uint64_t ilen[1] = { nbytes };
+	uint64_t ns = 0;
+	uint32_t n = 0, got = UINT32_MAX;
+	int rc;
+	if (!dhuf_stream_samples(layout, in, nbytes, &ns))
+		rc = set_error(-1, "malformed stream");
+	else if (ns > *nout)
+		rc = set_error(PRESS_HIP_EARG, "no room for samples");
+	else {
+		n = (uint32_t) ns;
+		rc = press_hip_huffman_depress_batch(layout, in, ioff, ilen, 1, out, off, &n, n, &got, 0);
+	}
+	if (!rc && got == UINT32_MAX)
+		rc = set_error(-1, "malformed stream");
+	if (rc) {
+		fprintf(stderr, "press_hip: %s\n", press_hip_last_error());
+		*nout = 0;
+		return -1;
+	}
+	*nout = got;
+	return 0;
 }
 
 // zstd level 1 (press.h:275) around a GPU-made inner stream (press.c:1865, 2025, 8554)
@@ -506,5 +554,21 @@ RICE_FAMILY(rice_vbe21, PRESS_HIP_RCF_VBE21)
 RICE_FAMILY(rice_vbbe21, PRESS_HIP_RCF_VBBE21)
 RICE_FAMILY(rice_vbsbe21, PRESS_HIP_RCF_VBSBE21)
 RICE_FAMILY(rice_vbsse21, PRESS_HIP_RCF_VBSSE21)
+
+// ---- the four methods of the per-read Huffman family (press.h:602-631): int results, depress: nin is the stream's length
+#define DHUF_FAMILY(name, layout)                                                                  \
+	uint64_t name##_zd_bound_16(uint32_t nin) { return press_hip_huffman_bound(layout, nin); } \
+	int name##_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout)      \
+	{                                                                                          \
+		return dhuf_press_(layout, in, nin, out, nout);                                    \
+	}                                                                                          \
+	int name##_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout)          \
+	{                                                                                          \
+		return dhuf_depress_(layout, in, nin, out, nout);                                  \
+	}
+DHUF_FAMILY(huffman_vbe21, PRESS_HIP_RCF_VBE21)
+DHUF_FAMILY(huffman_vbbe21, PRESS_HIP_RCF_VBBE21)
+DHUF_FAMILY(huffman_vbsbe21, PRESS_HIP_RCF_VBSBE21)
+DHUF_FAMILY(huffman_vbsse21, PRESS_HIP_RCF_VBSSE21)
 
 } // extern "C"

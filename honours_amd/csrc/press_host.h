@@ -77,6 +77,7 @@ struct Ctx {
 	DevBuf px_pair, px_range, px_out, px_stat; // range statistics and prefix: the adaptor's pairs, the ranges (host path: the caller's); host path: the prefix records, the statistics (the calibration and thr: sg_cal, sg_thr)
 	DevBuf sl_seg, sl_rd, sl_poff, sl_pn, sl_pooff, sl_polen, sl_poutn, sl_psig, sl_parena, sl_stall; // stall methods: first segments, plans, the piece table (StallBufs), the pieces' samples and streams; host path: (start, len) per read
 	DevBuf ri_sum, ri_start, ri_rd, ri_pay, ri_drd, ri_tile, ri_rec, ri_tbase, ri_ctl, ri_k; // Rice methods: the units' sums and first bits, the reads' records, the staged payloads; depress: reads, tiles, subsequence records, tile bases, counters; host path: k[]
+	DevBuf dh_tab; // per-read Huffman methods: codes and counts (press), decode tables (depress); the other buffers are the Rice methods'
 	DevBuf tl_chunks, tl_ctl, tl_tab, tl_mom; // dataset tallies: the chunk list and its count; host path: the three tables in a row, the moments
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
@@ -184,7 +185,7 @@ struct Method {
 	int id;
 	Family family;
 	bool key2, zd, slow5; // FAM_SVB: 2-bit keys (svb32), zig-zag delta, BLOW5's framing
-	int exfmt, ent;       // FAM_EX: ExFmt; entropy stage 0 plain, 1 static Huffman, 2 / 3 / 4 / 5 range coder, 6 Golomb-Rice
+	int exfmt, ent;       // FAM_EX: ExFmt; entropy stage 0 plain, 1 static Huffman, 2 / 3 / 4 / 5 range coder, 6 Golomb-Rice, 7 a Huffman code per read
 	int inner;            // FAM_ZSTD: the method whose streams the frames hold ...
 	uint32_t kdiv;        // ... and its samples per key byte (ZsBufs::kdiv)
 };
@@ -259,6 +260,14 @@ constexpr Method RICE_METHODS[PRESS_HIP_NRCF_LAYOUTS] = {
 inline bool is_rice(const Method &m) { return m.family == FAM_EX && m.ent == 6; }
 inline bool rice_ok(int layout) { return layout >= 0 && layout < PRESS_HIP_NRCF_LAYOUTS; }
 
+// ---- the per-read Huffman family (press_hip_huffman_*): a Huffman code from each read's own one-byte values, on every layout
+constexpr int DHUF_PRIVATE = RICE_PRIVATE + PRESS_HIP_NRCF_LAYOUTS; // private id = DHUF_PRIVATE + layout
+constexpr Method DHUF_METHODS[PRESS_HIP_NRCF_LAYOUTS] = {
+	M_EX(DHUF_PRIVATE + 0, EXF_VBE21, 7), M_EX(DHUF_PRIVATE + 1, EXF_VBBE21, 7), M_EX(DHUF_PRIVATE + 2, EXF_VBSBE21, 7),
+	M_EX(DHUF_PRIVATE + 3, EXF_VBSSE21, 7),
+};
+inline bool is_dhuf(const Method &m) { return m.family == FAM_EX && m.ent == 7; }
+
 // ---- bounds: the reference's formulas ----
 inline uint32_t svb16_keylen(uint32_t n) { return (n >> 3) + (((n & 7) + 7) >> 3); }
 inline uint64_t bound_svb32(uint32_t n) { return (uint64_t) (n + 3) / 4 + (uint64_t) n * 4 + 16; }    // streamvbyte.h:35
@@ -291,7 +300,7 @@ struct ScratchPlan {
 	ZsBufs zs() const;                 // z with its pointers
 };
 ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool decode);
-ScratchPlan make_plan(const Method &method, uint64_t total_samples, uint32_t nreads, bool decode); // ... or a row of RCF_METHODS / RICE_METHODS
+ScratchPlan make_plan(const Method &method, uint64_t total_samples, uint32_t nreads, bool decode); // ... or a row of RCF_METHODS / RICE_METHODS / DHUF_METHODS
 // The calls that decode nothing and walk samples by launch_pa_tiles' table: make_plan's max_chunks, and the table
 ScratchPlan make_tiles_plan(uint64_t total_samples, uint32_t nreads);
 

@@ -156,6 +156,31 @@ struct RiceDRead {            // depress, per read (k_rice_dplan)
 	uint32_t ok;          // k_ex_parse accepted the read
 };
 
+// The per-read Huffman methods (press_dhuf.hip).  Units, subsequences and tiles are the Rice methods', and so are their
+// buffers (BatchArgs::ri_*, DecodeArgs::ri_*); ri_rd holds DhRead records.  dh_tab is the family's own: per read
+// DH_PRESS_TAB bytes for press (256 x { code | len << 56 }, then the 256 counts), a DhTab for depress.
+constexpr uint32_t DH_UNIT = RICE_UNIT;
+constexpr uint32_t DH_W = 11;                        // bits of the decoder's direct look-up
+constexpr uint32_t DH_PRESS_TAB = 256 * 8 + 256 * 4;
+struct DhRead {               // press, per read (k_dh_tree)
+	uint64_t nbits;       // payload bits
+	uint64_t paylen;      // ... and bytes
+	uint32_t tablen;      // bytes of the table in front of the payload
+	uint32_t maxlen;      // the longest code
+	uint32_t ok;          // 0: refused (k_ex_section), or the slot is too small
+	uint32_t nlow, nunits, nsym;
+};
+struct DhTab {                // depress, per read (k_dh_table)
+	uint64_t lcode[256];  // the codes, first bit on top, ascending
+	uint16_t ent[256];    // ... their symbol | len << 8
+	uint16_t direct[1u << DH_W]; // by the next DH_W bits: symbol | len << 8, 0: no code, 0xFFFF: a longer code, in lcode
+	uint32_t nent;
+	uint32_t tablen;      // bytes of the table in front of the payload
+	uint32_t mode;        // 0: decode the payload, 1: nothing to decode (no value, or one symbol without a bit), 2: refused
+	uint32_t pad;
+};
+static_assert(sizeof(DhRead) % 8 == 0 && sizeof(DhTab) % 8 == 0, "arrays of them keep their uint64_t aligned");
+
 // Arguments common to every batch kernel.
 struct BatchArgs {
 	const int16_t *sig;       // samples of all reads
@@ -187,7 +212,8 @@ struct BatchArgs {
 	RiceRead *ri_rd;          // [nreads]
 	uint8_t *ri_pay;          // the staged payloads: read r's at 2 * off[r], ri_pay_bytes in all
 	uint64_t ri_pay_bytes;
-	uint8_t *ri_k;            // [nreads] the caller's k[], or NULL
+	uint8_t *ri_k;            // [nreads] the caller's k[] (per-read Huffman: maxlen[]), or NULL
+	uint8_t *dh_tab;          // the per-read Huffman methods (press_dhuf.hip): [nreads][DH_PRESS_TAB] codes and counts
 };
 
 struct HufTile {             // one tile of a read's Huffman payload (press_huffman.hip), 32 bytes
@@ -239,6 +265,7 @@ struct DecodeArgs {
 	uint64_t *ri_tbase;       // [2 * ri_max_tiles] per tile: the read's codes in front of it; behind them: the tiles' own counts
 	uint32_t *ri_ctl;         // [RICE_CTL_WORDS]
 	uint32_t ri_max_tiles;
+	uint8_t *dh_tab;          // the per-read Huffman methods (press_dhuf.hip): [nreads] DhTab
 };
 
 // zstd frames on the device (press_zstd.hip, zs_table.h): scratch of one batch
@@ -517,7 +544,7 @@ void launch_stall_parse(const uint8_t *in, const uint64_t *in_off, const uint64_
 			const StallBufs &b, hipStream_t s);
 void launch_stall_scatter(int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint32_t *out_n,
 			  hipStream_t s);
-void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing, 5 nibble-CDF coder, 6 Golomb-Rice
+void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing, 5 nibble-CDF coder, 6 Golomb-Rice, 7 a Huffman code per read
 void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
 void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip
 void launch_huff_decode(const DecodeArgs &a, uint32_t minlen, hipStream_t s);      // press_huffman.hip
@@ -535,6 +562,12 @@ void launch_rice_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);
 void launch_rice_decode(const DecodeArgs &a, hipStream_t s);
 // press_hip_rice_press_sizes: the press chain of ent 6 as far as the sizes; a.out_off: nreads + 1 zeros, a.out_len == need
 void launch_ex_rice_sizes(const BatchArgs &a, int fmt, uint64_t *need, hipStream_t s); // press_chunked.hip
+// ent 7: a Huffman code per read (huffman_*_zd), press_dhuf.hip.  need != NULL: k_dh_hist and k_dh_tree alone, need[r] += the
+// bytes of table and payload
+void launch_dhuf_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);
+void launch_dhuf_decode(const DecodeArgs &a, hipStream_t s);
+// press_hip_huffman_press_sizes: launch_ex_rice_sizes with ent 7
+void launch_ex_dhuf_sizes(const BatchArgs &a, int fmt, uint64_t *need, hipStream_t s); // press_chunked.hip
 // behind the encode of a range-coder method (ent >= 2): raw[r] = 1 where the coder gave up and stored the one-byte values
 void launch_rcf_raw(const BatchArgs &a, uint8_t *raw, hipStream_t s);
 // symbol counts of a batch for fitting a Huffman table (press_train.hip): adds into counts[257]; chunks takes

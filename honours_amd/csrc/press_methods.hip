@@ -138,20 +138,22 @@ ScratchPlan make_plan(const Method &method, uint64_t total_samples, uint32_t nre
 		p.need(&Ctx::cbits, mc * sizeof(ChunkBits));
 	if (is_rc(k))
 		p.need(&Ctx::low, total_samples + 64); // the one-byte values between the two stages
-	if (is_rice(k) && !decode) {
+	if ((is_rice(k) || is_dhuf(k)) && !decode) {
 		// press_rice.hip: 32 units per chunk; a staged payload never takes more than nine bits a value, the reads' stagings
 		// start at twice their sample offsets
 		p.ri_pay_bytes = 2 * total_samples + 64;
 		p.need(&Ctx::ri_sum, mc * RICE_UPC * 32).need(&Ctx::ri_start, mc * RICE_UPC * 8).need(&Ctx::ri_rd, nr * sizeof(RiceRead))
 			.need(&Ctx::ri_pay, p.ri_pay_bytes);
 	}
-	if (is_rice(k) && decode) {
+	if ((is_rice(k) || is_dhuf(k)) && decode) {
 		// tiles of RICE_DT subsequences of RICE_SUB bits: a read has at most ceil((9 nlow + 3) / RICE_SUB) subsequences
 		const uint64_t dt = total_samples * 9 / ((uint64_t) RICE_SUB * RICE_DT) + 2ull * nreads + 2;
 		const size_t mt = p.ri_max_tiles = dt > 0xFFFFFFull ? 0xFFFFFFu : (uint32_t) dt;
 		p.need(&Ctx::ri_drd, nr * sizeof(RiceDRead)).need(&Ctx::ri_tile, mt * sizeof(uint2)).need(&Ctx::ri_rec, mt * RICE_DT * 12)
 			.need(&Ctx::ri_tbase, mt * 16).need(&Ctx::ri_ctl, RICE_CTL_WORDS * 4);
 	}
+	if (is_dhuf(k)) // press_dhuf.hip: the Rice methods' buffers (ri_rd holds DhRead records), and the reads' tables
+		p.need(&Ctx::ri_rd, nr * sizeof(DhRead)).need(&Ctx::dh_tab, nr * (decode ? sizeof(DhTab) : (size_t) DH_PRESS_TAB));
 	if (decode && is_shuff(k)) {
 		// Huffman tiles of a batch (press_huffman.hip, k_huff_tiles): a read of n samples has at most
 		// n - 1 codes of at most maxlen bits, cut into tiles of HUF_HT subsequences
@@ -394,7 +396,7 @@ void ScratchPlan::bind(BatchArgs &a) const
 	memset(&a, 0, sizeof a);
 	B(meta), B(ex_pos), B(ex_val), B(chunks), B(gran), B(ctl), B(first_chunk), B(cbits);
 	BIND(a, low_tmp, low);
-	B(ri_sum), B(ri_start), B(ri_rd), B(ri_pay);
+	B(ri_sum), B(ri_start), B(ri_rd), B(ri_pay), B(dh_tab);
 	a.ri_pay_bytes = ri_pay_bytes;
 	a.huff = (const HuffDev *) g.huff.p; // (the table's, not the batch's: upload_table)
 	a.max_chunks = max_chunks;
@@ -410,7 +412,7 @@ void ScratchPlan::bind(DecodeArgs &a) const
 	a.max_htiles = max_htiles;
 	a.hlist_cap = hlist_cap;
 	a.huf_minlen = huf_minlen;
-	B(ri_drd), B(ri_tile), B(ri_rec), B(ri_tbase), B(ri_ctl);
+	B(ri_drd), B(ri_tile), B(ri_rec), B(ri_tbase), B(ri_ctl), B(dh_tab);
 	a.ri_max_tiles = ri_max_tiles;
 }
 

@@ -607,14 +607,14 @@ __global__ __launch_bounds__(64) void k_ex_parse_fill_vbe21(DecodeArgs a)
 
 void launch_ex_section(const BatchArgs &a, int fmt, int ent, hipStream_t s)
 {
-	hipLaunchKernelGGL(k_ex_section, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent == 6 ? 4 : ent >= 2 ? 3 : 0);
+	hipLaunchKernelGGL(k_ex_section, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent >= 6 ? 4 : ent >= 2 ? 3 : 0);
 	if (fmt == EXF_VBE21)
 		hipLaunchKernelGGL(k_ex_fill_vbe21, dim3(a.nreads), dim3(64), 0, s, a);
 }
 
 void launch_ex_sizes(const BatchArgs &a, int fmt, int ent, uint64_t *need, hipStream_t s)
 {
-	hipLaunchKernelGGL(k_ex_sizes, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent == 6 ? 4 : ent >= 2 ? 3 : 0, need);
+	hipLaunchKernelGGL(k_ex_sizes, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent >= 6 ? 4 : ent >= 2 ? 3 : 0, need);
 }
 
 // k_ex_parse and, for the Huffman variants, the stream decode into a.low (timed as the
@@ -636,6 +636,8 @@ void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s)
 			launch_cdf_decode(a, s);
 		else if (ent == 6)
 			launch_rice_decode(a, s);
+		else if (ent == 7)
+			launch_dhuf_decode(a, s);
 		else
 			launch_huff_decode(a, a.huf_minlen, s);
 		ktime_end(1, s);

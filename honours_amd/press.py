@@ -1100,16 +1100,18 @@ def rcf_depress_batch_host(coder, layout, streams, ns):
     return _reads_of(sig, off, out_n)
 
 
-# ---- the Rice family (press_hip_rice_*) has a module of its own, honours_amd/rice.py; its wrappers are reachable here too
+# ---- the Rice family (press_hip_rice_*) and the per-read Huffman family (press_hip_huffman_*) have modules of their own,
+# honours_amd/rice.py and honours_amd/huffman.py; their wrappers are reachable here too
 
 
 def __getattr__(name):
-    """press.rice_name, press.rice_press_batch ...: the functions of honours_amd.rice (PEP 562; the module is imported on
-    first use, it imports this one)"""
-    if name.startswith("rice_"):
-        from . import rice
-        if hasattr(rice, name):
-            return getattr(rice, name)
+    """press.rice_name, press.huffman_press_batch ...: the functions of honours_amd.rice and honours_amd.huffman
+    (PEP 562; a module is imported on first use, it imports this one)"""
+    if name.startswith("rice_") or name.startswith("huffman_"):
+        import importlib
+        mod = importlib.import_module("." + name.split("_")[0], __package__)
+        if hasattr(mod, name):
+            return getattr(mod, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

@@ -1384,6 +1384,87 @@ uint64_t rice_vbsse21_zd_bound_16(uint32_t nin);
 void rice_vbsse21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
 void rice_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
 
+/* ======================================================================= (2v) the per-read Huffman family */
+
+/*
+ * The reference's entropy stage that needs no fitted table and still reaches the static table's ratio:
+ * huffman_{vbe21, vbbe21, vbsbe21, vbsse21}_zd (press.h:602-631, press.c:3960-4407, huffman/huffman.c:984-1072).  A Huffman
+ * code is built from each read's own one-byte values and written in front of the payload.  No adaptive state: press is a
+ * histogram, a tree per read, a scan and a bit scatter, depress a self-synchronising prefix code, both parallel within a
+ * read.  A family with ids of its own like (2t) and (2u): the layout ids are enum press_hip_rcf_layout; enum
+ * press_hip_method, PRESS_HIP_NMETHODS and the generic batch calls, the recode, picoampere, normalise, chunk-row, verify,
+ * CRC and packed calls do not know these methods.
+ *
+ * The stream.  With P(L), nex, nlow and sec(L) as in (2u), the stream of huffman_L_zd is sec(L) + huffman(low):
+ *   counts   the symbols present are ordered ascending by count, ties by ascending symbol value
+ *   tree     until one node is left: the first two nodes of the list, m1 and m2, get a parent with count m1 + m2, m1 its
+ *            zero child and m2 its one child; the parent goes back in front of every remaining node whose count is not
+ *            smaller than its own (so in front of equal leaves and of equal parents made earlier)
+ *   codes    a symbol's code is its path from the root, zero or one per edge, first edge first
+ *   table    one byte (nsym - 1) & 255; nlow as a big-endian u32; per present symbol in ascending symbol order
+ *            { u8 symbol, u8 len, ceil(len / 8) code bytes }, code bit k in bit k % 8, from the least significant, of
+ *            code byte k / 8
+ *   payload  the codes of the values in order, first code bit first; payload bit i in bit i % 8, from the least
+ *            significant, of byte i / 8; the last byte zero padded
+ * With nlow < 2^32 no code is longer than about 46 bits (a code of depth d needs F(d + 2) values); 64 bits hold every code
+ * press can make, 32 do not (34 symbols with Fibonacci counts: 33 bits).
+ *
+ * Where the reference leaves a hole, this library defines:
+ *   1. one value   One distinct one-byte value (a constant stretch, n = 2): the reference aborts in press.  This library
+ *                  writes what the rules give: count byte 0x00, nlow, the one entry { symbol, 0 } without a code byte,
+ *                  no payload byte; its decoder gives nlow copies of the symbol.
+ *   2. no value    n = 1, or every value an exception: ff 00 00 00 00, as the reference writes it (its own depress
+ *                  fails on that stream).  The decoder reads a table whose count field is 0 as empty whatever the first
+ *                  byte says, and returns the read.
+ *   3. sections    For vbbe21, vbsbe21 and vbsse21 the reference keeps the section length in a uint16_t (press.c:4076);
+ *                  this library's stream is the splice above for any section length.
+ *   4. decoder     A table is valid when it has 1 to 256 entries, every length is in 1 .. 63 (or it is the single entry
+ *                  of length 0), the codes are prefix-free and the table ends inside the stream; a symbol may appear
+ *                  twice and the table may be incomplete.  A read is refused, as every decoder of this library marks it
+ *                  (out_n[r] = UINT32_MAX), when its table is invalid, when the table's count is not n[r] - 1 - nex,
+ *                  when bits inside the payload are no code, or when the payload ends before nlow values are out.  The
+ *                  other reads of the batch are untouched, and nothing outside [in_off, in_off + in_len) is read.
+ *   5. bounds      press_hip_huffman_bound is the reference's X_bound_16 (vb1e2_zd_bound_16 for all four; 0 for a bad
+ *                  id).  The exact size is known before a byte is written (press_hip_huffman_press_sizes).  A read whose
+ *                  slot is too small fails alone (out_len[r] = PRESS_HIP_FAILED).
+ *
+ *   maxlen   NULL, or nreads bytes: the longest code of read r's table (0 for cases 1 and 2 and for a refused read); a
+ *            device pointer when device_resident
+ *   need[r]  press_hip_huffman_press_sizes: the exact stream length of read r (PRESS_HIP_FAILED for an empty read); no
+ *            arena, nothing else is written
+ * Everything else - arguments, layouts, PRESS_HIP_EARG, the host-pointer form, "device resident: the call only enqueues
+ * on the current stream", depress: n[r] is the read's exact sample count - is as in (2u).  Depress runs a fixed number of
+ * launches, with four repair rounds and a serial walk per read for what they leave.  press_hip_huffman_repairs: the
+ * subsequences the first round decoded again, those the later rounds did, and the values the walk decoded in the last
+ * depress call of this family or of (2u), whose counters these are (it synchronises).
+ */
+uint64_t press_hip_huffman_bound(int layout, uint32_t n);
+int press_hip_huffman_press_batch(int layout, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				  uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len, uint8_t *maxlen,
+				  int device_resident);
+int press_hip_huffman_press_sizes(int layout, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				  uint64_t total_samples, uint64_t *need, uint8_t *maxlen, int device_resident);
+int press_hip_huffman_depress_batch(int layout, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t nreads,
+				    int16_t *sig, const uint64_t *off, const uint32_t *n, uint64_t total_samples, uint32_t *out_n,
+				    int device_resident);
+int press_hip_huffman_repairs(uint32_t *counts);
+
+/* the reference's per-read symbols (press.h:602-631), synchronous: 0, or -1 with *nout = 0.  *nout of press the capacity
+ * in, the length out; depress takes the stream's byte count as nin and the capacity in samples in *nout: the sample count
+ * is read from the stream (nex and the table's count), and a stream that says more than the capacity is refused */
+uint64_t huffman_vbe21_zd_bound_16(uint32_t nin);
+int huffman_vbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+int huffman_vbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t huffman_vbbe21_zd_bound_16(uint32_t nin);
+int huffman_vbbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+int huffman_vbbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t huffman_vbsbe21_zd_bound_16(uint32_t nin);
+int huffman_vbsbe21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+int huffman_vbsbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+uint64_t huffman_vbsse21_zd_bound_16(uint32_t nin);
+int huffman_vbsse21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
+int huffman_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+
 /* ======================================================================= (3) BLOW5 files (host) */
 
 /*

@@ -1,0 +1,598 @@
+"""The per-read Huffman family (include/press_hip.h section 2v, press_hip_huffman_*): a Huffman code from each read's own
+one-byte values on the four exception layouts, huffman_{vbe21, vbbe21, vbsbe21, vbsse21}_zd.
+
+Without a GPU: the yardstick of tests/_dhuf.py against what the REAL reference made of the fixture's reads
+(tests/golden/ref_huffman.json); what the fixture holds; header, symbols and Python mirror; the bound; bad arguments; the
+wrappers without a GPU.  On the GPU: the device's streams byte for byte against the yardstick and the fixture, and back
+again; forged tables and payloads against definition 4.
+"""
+import inspect
+import os
+
+import numpy as np
+import pytest
+
+import _dhuf as D
+import _layouts as L
+import _rcf
+from honours_amd import press
+
+gpu = pytest.mark.gpu
+EARG = -2
+FAILED64 = (1 << 64) - 1
+FAILED32 = (1 << 32) - 1
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+HEADER = os.path.join(ROOT, "include", "press_hip.h")
+GUARD = 48
+FILL8, FILL16 = 0xA5, 0x5A5A
+CANARY = 0x5AC35AC3
+SUB, TILE = 256, 256  # bits of a reader's subsequence, subsequences of a tile (press_internal.h)
+
+_cache = {}
+
+
+def reads_by_name():
+    if "reads" not in _cache:
+        _cache["reads"] = dict(D.named_reads())
+    return _cache["reads"]
+
+
+def fixture_entries():
+    if "ent" not in _cache:
+        _cache["ent"] = {e["name"]: e for e in D.fixture()["entries"]}
+    return _cache["ent"]
+
+
+def expected(layout, s):
+    """the yardstick's (stream, maxlen), computed once per (layout, read); table and payload once per read"""
+    s = np.ascontiguousarray(s, dtype=np.int16)
+    key = (layout, s.tobytes())
+    if key not in _cache:
+        tkey = ("tail", s.tobytes())
+        if tkey not in _cache:
+            _cache[tkey] = D.encode(D.low_of(s))
+        tail, maxlen = _cache[tkey]
+        _cache[key] = (_rcf.split(layout, s)[0] + tail, maxlen)
+    return _cache[key]
+
+
+# ------------------------------------------------------------------ without a GPU
+
+@pytest.fixture(scope="module")
+def cpu_lib():
+    from honours_amd import build
+    build.build()
+    return press.load_library()
+
+
+def test_yardstick_equals_the_reference():
+    """encode() behind the plain layouts' sections reproduces every stream of the fixture - hash, length and longest code -
+    and decode() reads every payload back (the one large read: its hash alone); the fixture's reads are the reads of
+    _dhuf.named_reads()"""
+    ent = fixture_entries()
+    assert list(ent) == list(reads_by_name())
+    for name, s in reads_by_name().items():
+        e = ent[name]
+        assert e["n"] == len(s) and e["samples_sha256"] == D.sha(s.tobytes()), name
+        for layout in D.LAYOUTS:
+            f = e["methods"][D.name(layout)]
+            stream, maxlen = expected(layout, s)
+            assert (len(stream), maxlen, D.sha(stream)) == (f["len"], f["maxlen"], f["sha256"]), (name, layout)
+            assert ("stream" in f) == (len(s) < 64) and (len(s) >= 64 or bytes.fromhex(f["stream"]) == stream), (name, layout)
+            if name != D.BIG:
+                assert np.array_equal(D.decoded(layout, stream, D.head_len(layout, s), len(s)), s), (name, layout)
+
+
+def test_fixture_conditions():
+    """the reference aborts exactly on the reads with one distinct one-byte value, whose streams are definition 1's; every
+    other read with a value comes back through the reference's own depress; the lengths the issue quotes; the code widths"""
+    ent = fixture_entries()
+    for name, e in ent.items():
+        low = D.low_of(reads_by_name()[name])
+        for m, f in e["methods"].items():
+            assert (f["reference"] == "aborts") == (len(set(low)) == 1), (name, m)
+            assert f["roundtrip"] is (len(set(low)) > 1), (name, m)
+    assert [n for n, e in ent.items() if e["methods"]["huffman_vbe21_zd"]["reference"] == "aborts"] == \
+        ["walk-2", "constant-3000", "all-255-x100", "all-1-x1000"]
+    real = [e for n, e in ent.items() if n.startswith("three_reads/")]
+    assert [e["methods"]["huffman_vbe21_zd"]["len"] for e in real] == [5262, 104701, 67121]
+    assert [e["methods"]["huffman_vbbe21_zd"]["len"] for e in real] == [5262, 104699, 67118]
+    assert ent["fib-24"]["n"] == 121393 and ent["fib-24"]["methods"]["huffman_vbe21_zd"]["maxlen"] == 23
+    assert ent[D.BIG]["n"] == 14930352 and ent[D.BIG]["methods"]["huffman_vbe21_zd"]["maxlen"] == 33
+    assert ent[D.BIG]["methods"]["huffman_vbe21_zd"]["len"] == 4886186
+    assert ent["two-symbols"]["methods"]["huffman_vbe21_zd"]["maxlen"] == 1
+    assert ent["never-sync"]["methods"]["huffman_vbe21_zd"]["maxlen"] == 3 and SUB % 3 != 0
+    # definition 2, n = 1: the 2-byte first sample (417 in zig-zag: 834), the empty section, ff 00 00 00 00
+    assert all(f["stream"] == "4203" + "00" * 4 + "ff00000000" for f in ent["single-1"]["methods"].values())
+    # definition 1, n = 2: count byte 0, nlow = 1, the entry { symbol, 0 }
+    s = reads_by_name()["walk-2"]
+    assert all(bytes.fromhex(f["stream"])[6:] == bytes([0, 0, 0, 0, 1, D.low_of(s)[0], 0]) for f in ent["walk-2"]["methods"].values())
+
+
+def test_yardstick_tree_and_decoder_rules():
+    """ties: a parent goes in front of equal leaves and of equal parents made earlier; definition 4 in the yardstick"""
+    counts = np.zeros(256, dtype=np.int64)
+    counts[[10, 20, 30, 40]] = 1
+    # (10, 20) -> P1 = 2 goes behind 30, 40 (smaller) ... list 30 40 P1; (30, 40) -> P2 = 2 in front of P1: P2 P1
+    assert D.build_code(counts) == {30: (2, 0b00), 40: (2, 0b10), 10: (2, 0b01), 20: (2, 0b11)}
+    counts[:] = 0
+    counts[[1, 2, 3]] = [1, 1, 2]
+    # (1, 2) -> P = 2 in front of the leaf 3 with the same count: P is the zero child of the root
+    assert D.build_code(counts) == {1: (2, 0b00), 2: (2, 0b10), 3: (1, 0b1)}
+    assert D.encode(b"") == (bytes([0xFF, 0, 0, 0, 0]), 0) and D.encode(bytes([7]) * 9) == (bytes([0, 0, 0, 0, 9, 7, 0]), 0)
+    assert D.decode(bytes([0x33, 0, 0, 0, 0]), 0) == b"" and D.decode(bytes([0, 0, 0, 0, 9, 7, 0]), 9) == bytes([7]) * 9
+    assert D.decode(bytes([0, 0, 0, 0, 9, 7, 0]), 8) is None
+    for low in (bytes([1, 2, 2, 3, 3, 3, 3]), D.never_sync_low(), D.fib_low(24)):
+        assert D.decode(D.encode(low)[0], len(low)) == low
+        assert D.decode(D.encode(low)[0][:-1], len(low)) is None
+
+
+SYMBOLS = ["press_hip_huffman_bound", "press_hip_huffman_press_batch", "press_hip_huffman_press_sizes",
+           "press_hip_huffman_depress_batch", "press_hip_huffman_repairs"] + \
+          [D.name(l) + s for l in D.LAYOUTS for s in ("_bound_16", "_press_16", "_depress_16")]
+WRAPPERS = ["huffman_name", "huffman_bound", "huffman_press", "huffman_depress", "huffman_press_batch", "huffman_press_batch_host",
+            "huffman_press_sizes", "huffman_press_sizes_host", "huffman_depress_batch", "huffman_depress_batch_host",
+            "huffman_repairs"]
+
+
+def test_symbols_header_and_mirror(cpu_lib):
+    from honours_amd import abi, build, huffman
+    header = open(HEADER).read()
+    for s in SYMBOLS:
+        assert hasattr(cpu_lib, s) and s in press.HEADER_SYMBOLS and s + "(" in header, s
+    flat = " ".join(header.split())
+    assert len(press.METHODS) == 19 and "PRESS_HIP_NMETHODS = 19" in flat  # a family of its own
+    for words in ("(2v) the per-read Huffman family", "1. one value", "2. no value", "3. sections", "4. decoder", "5. bounds"):
+        assert words in header, words
+    assert "press_dhuf.hip" in build.SOURCES and "press_dhuf_walk.h" in build.HEADERS
+    for l in D.LAYOUTS:  # the reference's signatures: int results
+        assert abi.PROTOS[D.name(l) + "_press_16"][0] is abi.PROTOS[D.name(l) + "_depress_16"][0] is abi.I
+    public = sorted(n for n, f in vars(huffman).items()
+                    if not n.startswith("_") and inspect.isfunction(f) and f.__module__ == huffman.__name__)
+    assert public == sorted(WRAPPERS)
+    for w in WRAPPERS:
+        assert getattr(press, w) is getattr(huffman, w)
+    assert press.huffman_name("vbe21") == "huffman_vbe21_zd" and press.huffman_name(3) == "huffman_vbsse21_zd"
+    with pytest.raises(AttributeError):
+        press.huffman_nothing
+
+
+def test_docs_state_the_sanitizer_run():
+    """DESIGN.md names the stand-alone sanitizer run of the host reader with its case count, and the tool exists"""
+    design = " ".join(open(os.path.join(ROOT, "DESIGN.md")).read().split())
+    assert "tools/dhuf_walk_check.cpp" in design and "2959 cases" in design
+    assert os.path.exists(os.path.join(ROOT, "tools", "dhuf_walk_check.cpp"))
+
+
+def test_bound_is_the_plain_layouts(cpu_lib, oracle):
+    for l in D.LAYOUTS:
+        for n in (1, 2, 7, 8, 9, 1000, 7329, 155185, 5724000):
+            b = oracle.bound(l + "_zd", n)
+            assert press.huffman_bound(l, n) == press.rice_bound(l, n) == b
+            assert cpu_lib.press_hip_huffman_bound(press.RCF_LAYOUTS[l], n) == b and getattr(cpu_lib, D.name(l) + "_bound_16")(n) == b
+    for bad in (-1, 4, 1000):
+        assert cpu_lib.press_hip_huffman_bound(bad, 100) == 0
+
+
+def test_bad_arguments(cpu_lib):
+    """a bad layout id and NULL arguments (maxlen excepted) are PRESS_HIP_EARG before any device call"""
+    lib = cpu_lib
+    a = np.zeros(64, dtype=np.uint64)
+    p = a.ctypes.data
+    for form in (0, 1):
+        for bad in (-1, 4, 1000):
+            assert lib.press_hip_huffman_press_batch(bad, p, p, p, 1, 8, p, p, p, None, form) == EARG
+            assert "layout" in press.last_error()
+            assert lib.press_hip_huffman_press_sizes(bad, p, p, p, 1, 8, p, None, form) == EARG
+            assert lib.press_hip_huffman_depress_batch(bad, p, p, p, 1, p, p, p, 8, p, form) == EARG
+            assert lib.press_hip_huffman_press_batch(bad, p, p, p, 0, 0, p, p, p, None, form) == EARG  # (an empty batch too)
+        for k in range(6):
+            args = [p] * 6
+            args[k] = None
+            assert lib.press_hip_huffman_press_batch(0, args[0], args[1], args[2], 1, 8, args[3], args[4], args[5], None, form) == EARG
+        for k in range(4):
+            args = [p] * 4
+            args[k] = None
+            assert lib.press_hip_huffman_press_sizes(1, args[0], args[1], args[2], 1, 8, args[3], None, form) == EARG
+        for k in range(7):
+            args = [p] * 7
+            args[k] = None
+            assert lib.press_hip_huffman_depress_batch(2, args[0], args[1], args[2], 1, args[3], args[4], args[5], 8, args[6], form) == EARG
+    assert lib.press_hip_huffman_press_batch(0, p + 2, p, p, 1, 8, p, p, p, None, 1) == EARG  # a device arena off 16 bytes
+    assert lib.press_hip_huffman_repairs(None) == EARG
+
+
+def test_wrappers_without_gpu(cpu_lib):
+    """every wrapper of the family on a machine without a GPU: the pure ones answer, the others raise what the library
+    reports (or, the per-read symbols, return the reference's failure) - no TypeError, and none falls back to anything"""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("this machine has a GPU")
+    reads = [_rcf.signal(5, 9), _rcf.signal(6, 40)]
+    streams = [expected("vbe21", s)[0] for s in reads]
+    for l in D.LAYOUTS:
+        assert press.huffman_press(l, reads[0]) == (-1, b"")
+        ret, back = press.huffman_depress(l, streams[0], 9)
+        assert ret == -1 and back.size == 0 and back.dtype == np.int16
+        for call in (lambda: press.huffman_press_batch_host(l, reads), lambda: press.huffman_press_batch_host(l, reads, want_maxlen=True),
+                     lambda: press.huffman_press_sizes_host(l, reads), lambda: press.huffman_press_sizes_host(l, reads, want_maxlen=True),
+                     lambda: press.huffman_depress_batch_host(l, streams, [9, 40])):
+            with pytest.raises(press.PressError) as err:
+                call()
+            assert "device" in str(err.value).lower()
+    z = lambda n, dt: torch.zeros(n, dtype=dt)  # noqa: E731
+    sig, off, n = z(64, torch.int16), z(2, torch.int64), z(2, torch.int32)
+    out, out_off, out_len, ml = z(256, torch.uint8), z(3, torch.int64), z(2, torch.int64), z(2, torch.uint8)
+    for call in (lambda: press.huffman_press_batch("vbe21", sig, off, n, out, out_off, out_len),
+                 lambda: press.huffman_press_batch(1, sig, off, n, out, out_off, out_len, maxlen=ml),
+                 lambda: press.huffman_press_sizes("vbsbe21", sig, off, n, out_len, maxlen=ml),
+                 lambda: press.huffman_depress_batch("vbsse21", out, off, out_len, sig, off, n, n),
+                 press.huffman_repairs):
+        with pytest.raises(press.PressError):
+            call()
+
+
+# ------------------------------------------------------------------ GPU plumbing
+
+@pytest.fixture(scope="module")
+def lib():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    lb = press.load_library()
+    press.use_torch_stream()
+    yield lb
+    torch.cuda.synchronize()
+    press.use_torch_stream()
+    torch.cuda.empty_cache()
+
+
+def _t(a, dtype=None):
+    import torch
+    a = np.ascontiguousarray(a)
+    if dtype is not None:
+        a = a.view(dtype)
+    return torch.from_numpy(a.copy()).cuda()
+
+
+def slot_for(n):
+    return 8 * n + 4096 if n else 32
+
+
+class PressRun:
+    """A batch in a scattered layout, the slots back to back from an odd offset; canaries in front of and behind out_len,
+    need and maxlen, and every byte of the arena outside the streams and the slots of failed reads must keep its fill"""
+
+    def __init__(self, reads, caps=None, seed=1):
+        import torch
+        rng = np.random.default_rng(seed)
+        self.reads, self.nr = reads, len(reads)
+        sig, off = L.scatter_reads(rng, reads)
+        caps = [slot_for(len(r)) for r in reads] if caps is None else caps
+        self.out_off = L.slots(rng, np.asarray(caps, dtype=np.uint64))
+        self.sig, self.off = _t(sig), _t(off.astype(np.uint64), np.int64)
+        self.n = _t(np.array([len(r) for r in reads], dtype=np.uint32), np.int32)
+        self.d_out_off = _t(self.out_off, np.int64)
+        self.out = torch.full((int(self.out_off[-1]) + 64,), FILL8, dtype=torch.uint8, device="cuda")
+        self.out_len = torch.full((self.nr + 2 * GUARD,), CANARY, dtype=torch.int64, device="cuda")
+        self.ml = torch.full((self.nr + 2 * GUARD,), FILL8, dtype=torch.uint8, device="cuda")
+
+    def _tables(self, want_ml):
+        import torch
+        torch.cuda.synchronize()
+        ol = self.out_len.cpu().numpy().view(np.uint64)
+        ml = self.ml.cpu().numpy()
+        assert (ol[:GUARD] == CANARY).all() and (ol[GUARD + self.nr:] == CANARY).all(), "out_len / need"
+        assert (ml[:GUARD] == FILL8).all() and (ml[GUARD + (self.nr if want_ml else 0):] == FILL8).all(), "maxlen"
+        self.out_len.fill_(CANARY)
+        self.ml.fill_(FILL8)
+        return ol[GUARD:GUARD + self.nr].copy(), ml[GUARD:GUARD + self.nr].copy()
+
+    def run(self, layout, want_ml=True):
+        """-> (streams (None: failed), maxlen uint8 [nr])"""
+        press.huffman_press_batch(layout, self.sig, self.off, self.n, self.out, self.d_out_off, self.out_len[GUARD:GUARD + self.nr],
+                                  self.ml[GUARD:GUARD + self.nr] if want_ml else None)
+        ol, ml = self._tables(want_ml)
+        out = self.out.cpu().numpy()
+        written = np.zeros(len(out), dtype=bool)
+        streams = []
+        for r in range(self.nr):
+            o, cap = int(self.out_off[r]), int(self.out_off[r + 1] - self.out_off[r])
+            if ol[r] == FAILED64:
+                streams.append(None)
+                written[o:o + cap] = True  # (a read that fails may leave its own slot in any state, as the generic calls do)
+            else:
+                assert ol[r] <= cap
+                written[o:o + int(ol[r])] = True
+                streams.append(out[o:o + int(ol[r])].tobytes())
+        assert (out[~written] == FILL8).all(), "a byte outside the streams was written"
+        self.out.fill_(FILL8)
+        return streams, ml
+
+    def sizes(self, layout, want_ml=True):
+        """-> (need uint64 [nr], maxlen); the arena keeps its fill"""
+        press.huffman_press_sizes(layout, self.sig, self.off, self.n, self.out_len[GUARD:GUARD + self.nr],
+                                  self.ml[GUARD:GUARD + self.nr] if want_ml else None)
+        need, ml = self._tables(want_ml)
+        assert bool((self.out == FILL8).all())
+        return need, ml
+
+
+class DepressRun:
+    def __init__(self, streams, ns, seed=2):
+        import torch
+        rng = np.random.default_rng(seed)
+        self.ns = [int(n) for n in ns]
+        self.nr = len(streams)
+        arena, in_off, in_len = L.scatter_streams(rng, streams)
+        self.off, self.total = L.scatter_rooms(rng, self.ns, min_gap=8)
+        self.arena, self.in_off, self.in_len = _t(arena), _t(in_off, np.int64), _t(in_len, np.int64)
+        self.d_off, self.n = _t(self.off, np.int64), _t(np.array(self.ns, dtype=np.uint32), np.int32)
+        self.sig = torch.full((self.total,), FILL16, dtype=torch.int16, device="cuda")
+        self.out_n = torch.full((self.nr + 2 * GUARD,), CANARY, dtype=torch.int32, device="cuda")
+
+    def run(self, layout):
+        """-> samples per read (None: refused); nothing outside the rooms of the decoded reads is written"""
+        import torch
+        press.huffman_depress_batch(layout, self.arena, self.in_off, self.in_len, self.sig, self.d_off, self.n,
+                                    self.out_n[GUARD:GUARD + self.nr])
+        torch.cuda.synchronize()
+        sig = self.sig.cpu().numpy()
+        on = self.out_n.cpu().numpy().view(np.uint32)
+        assert (on[:GUARD] == CANARY).all() and (on[GUARD + self.nr:] == CANARY).all(), "out_n"
+        on = on[GUARD:GUARD + self.nr]
+        got, spans = [], []
+        for r in range(self.nr):
+            o = int(self.off[r])
+            if on[r] == FAILED32:
+                got.append(None)
+                spans.append(0)
+            else:
+                assert on[r] == self.ns[r]
+                got.append(sig[o:o + self.ns[r]].copy())
+                spans.append(self.ns[r])
+        assert (sig[L.outside_rooms(self.total, self.off, spans)] == FILL16).all(), "a sample outside the decoded reads was written"
+        self.sig.fill_(FILL16)
+        self.out_n.fill_(CANARY)
+        return got
+
+
+def check_batch(layout, reads, seed, caps=None):
+    """press: streams and longest codes equal to the yardstick's, press_sizes the streams' lengths with no arena; depress:
+    the device reads them back"""
+    run = PressRun(reads, caps=caps, seed=seed)
+    streams, ml = run.run(layout)
+    for r, s in enumerate(reads):
+        want, wml = expected(layout, s)
+        assert ml[r] == wml, (layout, r, len(s))
+        assert streams[r] == want, (layout, r, len(s))
+    need, ml2 = run.sizes(layout)
+    assert list(need) == [len(s) for s in streams] and np.array_equal(ml, ml2)
+    got = DepressRun(streams, [len(s) for s in reads], seed=seed + 1).run(layout)
+    for r, g in enumerate(got):
+        assert g is not None and np.array_equal(g, reads[r]), (layout, r, len(reads[r]))
+    return run, streams, ml
+
+
+# ------------------------------------------------------------------ on the GPU
+
+@gpu
+@pytest.mark.parametrize("layout", D.LAYOUTS)
+def test_fixture_reads(lib, layout):
+    """1: every read of the fixture but the large one, alone and in one mixed batch: hash, length and longest code as the
+    fixture records them, press_sizes, and back"""
+    ent = fixture_entries()
+    names = [n for n in reads_by_name() if n != D.BIG]
+    for j, name in enumerate(names):
+        _, streams, ml = check_batch(layout, [reads_by_name()[name]], seed=100 + j)
+        f = ent[name]["methods"][D.name(layout)]
+        assert (len(streams[0]), int(ml[0]), D.sha(streams[0])) == (f["len"], f["maxlen"], f["sha256"]), name
+    _, streams, ml = check_batch(layout, [reads_by_name()[n] for n in names], seed=11)
+    for name, st, m in zip(names, streams, ml):
+        f = ent[name]["methods"][D.name(layout)]
+        assert (len(st), int(m), D.sha(st)) == (f["len"], f["maxlen"], f["sha256"]), name
+    if layout in ("vbe21", "vbbe21"):
+        want = [5262, 104701, 67121] if layout == "vbe21" else [5262, 104699, 67118]
+        assert [len(s) for s in streams[:3]] == want and (layout != "vbe21" or sum(want) == 177084)
+
+
+@gpu
+@pytest.mark.parametrize("layout", D.LAYOUTS)
+def test_large_read(lib, layout):
+    """2: 14 930 352 samples, 34 symbols with Fibonacci counts, a 33-bit code: the stream's hash and length as the reference
+    made them, press_sizes, and the samples back"""
+    s = reads_by_name()[D.BIG]
+    f = fixture_entries()[D.BIG]["methods"][D.name(layout)]
+    run = PressRun([s], seed=21)
+    streams, ml = run.run(layout)
+    assert (len(streams[0]), int(ml[0]), D.sha(streams[0])) == (f["len"], 33, f["sha256"])
+    assert list(run.sizes(layout)[0]) == [f["len"]]
+    got = DepressRun(streams, [len(s)], seed=22).run(layout)
+    assert got[0] is not None and np.array_equal(got[0], s)
+
+
+def with_edge_exceptions(seed, n):
+    """n samples whose first and whose last step are exceptions"""
+    d = np.random.default_rng(seed).integers(-12, 13, size=n)
+    d[1], d[n - 1] = 300, -300
+    return (np.cumsum(d) + 500).astype(np.int16)
+
+
+def seam_reads():
+    if "seams" not in _cache:
+        rng = np.random.default_rng(31)
+        out = [_rcf.from_low(rng.integers(0, 30, size=k).astype(np.uint8).tobytes()) for k in (1023, 1024, 1025, 2047, 2048, 2049)]
+        # 1-bit codes: a value a bit, so the counts are the reader's seams - a subsequence, a tile - and one either side
+        # (the values 1 and 2: a step down and a step up, so the walk stays inside 16 bits)
+        out += [_rcf.from_low(rng.integers(1, 3, size=k).astype(np.uint8).tobytes())
+                for k in (SUB - 1, SUB, SUB + 1, SUB * TILE - 1, SUB * TILE, SUB * TILE + 1, 2 * SUB * TILE + 1)]
+        # 2 .. 6 distinct symbols: tables of 11 .. 23 bytes, so the payload starts at every byte offset modulo 4
+        out += [_rcf.from_low(rng.integers(0, k, size=300 + k).astype(np.uint8).tobytes()) for k in range(2, 7)]
+        out += [with_edge_exceptions(32, 700), with_edge_exceptions(33, 3)]
+        _cache["seams"] = out
+    return _cache["seams"]
+
+
+@gpu
+@pytest.mark.parametrize("layout", D.LAYOUTS)
+def test_seams(lib, layout):
+    """3: the writer's unit (1024 values), the reader's subsequence and tile, tables of every length modulo 4, an exception
+    as the first and as the last value; slots with a few bytes to spare, at every residue modulo 8"""
+    reads = seam_reads()
+    caps = [len(expected(layout, s)[0]) + 1 + r % 5 for r, s in enumerate(reads)]
+    run, streams, _ = check_batch(layout, reads, seed=41, caps=caps)
+    assert set(int(o) % 8 for o in run.out_off[:-1]) == set(range(8))
+    # the tables of the reads with 2 .. 6 symbols end at every byte offset modulo 4
+    assert {D.parse_table(streams[r][D.head_len(layout, reads[r]):])[2] % 4 for r in range(13, 18)} == {0, 1, 2, 3}
+    for s in reads[-2:]:
+        assert len(D.low_of(s)) == len(s) - 1 - 2  # both edge steps are exceptions
+
+
+@gpu
+@pytest.mark.parametrize("layout", D.LAYOUTS)
+def test_holes(lib, layout):
+    """4: definitions 1 and 2, byte for byte: n = 1, n = 2, a constant read of 3000 samples; they come back"""
+    reads = [np.array([417], dtype=np.int16), np.array([417, 420], dtype=np.int16), np.full(3000, 417, dtype=np.int16)]
+    _, streams, ml = check_batch(layout, reads, seed=51)
+    assert list(ml) == [0, 0, 0]
+    assert streams[0] == bytes.fromhex("4203" + "00" * 4 + "ff00000000")
+    assert streams[1] == bytes.fromhex("4203" + "00" * 4 + "00" + "00000001" + "0600")
+    assert streams[2] == bytes.fromhex("4203" + "00" * 4 + "00" + "00000bb7" + "0000")
+    # a count field of 0 is an empty table whatever the first byte says
+    got = DepressRun([bytes.fromhex("4203" + "00" * 4 + "3300000000"), streams[2]], [1, 3000], seed=52).run(layout)
+    assert np.array_equal(got[0], reads[0]) and np.array_equal(got[1], reads[2])
+
+
+@gpu
+@pytest.mark.parametrize("layout", D.LAYOUTS)
+def test_slots(lib, layout):
+    """5: a slot one byte short fails that read alone, and the canaries around every slot stay"""
+    reads = [_rcf.signal(61, 700), _rcf.signal(62, 12), _rcf.signal(63, 2000, exr=0.14, spread=127), _rcf.signal(64, 40000, exr=0.02),
+             _rcf.signal(65, 1), np.full(50, 3, dtype=np.int16)]
+    exp = [expected(layout, s)[0] for s in reads]
+    exact = PressRun(reads, caps=[len(e) for e in exp], seed=61)
+    streams, ml = exact.run(layout)
+    assert streams == exp
+    assert list(exact.sizes(layout, want_ml=False)[0]) == [len(e) for e in exp]
+    for short in range(len(reads)):
+        got, ml = PressRun(reads, caps=[len(e) - (r == short) for r, e in enumerate(exp)], seed=62 + short).run(layout)
+        assert got == [None if r == short else e for r, e in enumerate(exp)], short
+        assert ml[short] == 0
+    assert PressRun(reads[:4], caps=[0, 4, 5, 7], seed=69).run(layout)[0] == [None] * 4
+
+
+def forge(entries, symbols, count=None, nent=None):
+    """table + payload of a hand-made table: entries [(symbol, len, bits)], the values' codes by their symbol"""
+    code = {s: (ln, b) for s, ln, b in entries}
+    out = bytearray([((len(entries) if nent is None else nent) - 1) & 255]) + int(len(symbols) if count is None else count).to_bytes(4, "big")
+    for s, ln, b in entries:
+        out += bytes([s, ln]) + int(b).to_bytes((ln + 7) // 8, "little")
+    bits = []
+    for s in symbols:
+        ln, b = code[s]
+        bits += [(b >> k) & 1 for k in range(ln)]
+    return bytes(out) + np.packbits(np.array(bits, dtype=np.uint8), bitorder="little").tobytes()
+
+
+@gpu
+def test_forged_streams(lib):
+    """6: definition 4.  Every forged stream stands next to an undamaged read that must come back"""
+    layout = "vbe21"
+    good = _rcf.signal(71, 5000, exr=0.01)
+    full = expected(layout, good)[0]
+    n = 301
+    head = expected(layout, _rcf.from_low(bytes(n - 1)))[0][:D.head_len(layout, _rcf.from_low(bytes(n - 1)))]
+    vals = [int(v) for v in np.random.default_rng(72).integers(0, 2, size=n - 1)]
+    two = [(0, 2, 0b00), (1, 2, 0b01)]  # the codes 00 and 10: 01 and 11 are no code
+    unary = [(i, i + 1, (1 << i) - 1) for i in range(63)]  # 1^i 0, up to 63 bits
+    uvals = [int(v) for v in np.random.default_rng(73).integers(0, 63, size=n - 1)]
+    incomplete = forge(two, vals)
+    broken = bytearray(incomplete)
+    broken[5 + 6 + 20] |= 0x02  # a second bit set: 01 or 11
+    forged = {
+        "duplicate code": forge([(0, 1, 0), (1, 1, 0)], vals),
+        "a code heads another": forge([(0, 1, 0), (1, 2, 0b00), (2, 1, 1)], vals),
+        "length 0 among several": forge([(0, 0, 0), (1, 1, 1)], vals),
+        "length 64": forge([(0, 64, 1 << 63), (1, 1, 0)], [1] * (n - 1)),
+        "table past the end": forge([(0, 1, 0), (1, 1, 1)], [], count=n - 1, nent=40),
+        "count field": forge([(0, 1, 0), (1, 1, 1)], vals, count=n - 2),
+        "no code": bytes(broken),
+        "one byte short": forge([(0, 1, 0), (1, 1, 1)], vals)[:-1],
+    }
+    valid = {"incomplete table": (incomplete, vals), "codes of 63 bits": (forge(unary, uvals), uvals),
+             "a symbol twice": (forge([(5, 1, 0), (5, 2, 0b01), (6, 2, 0b11)], [5] * (n - 1)), [5] * (n - 1))}
+    streams, ns = [], []
+    for tail in forged.values():
+        streams += [head + tail, full]
+        ns += [n, len(good)]
+    for tail, _ in valid.values():
+        streams += [head + tail, full]
+        ns += [n, len(good)]
+    for st, k in zip(streams[::2], ns[::2]):  # the yardstick first
+        want = D.decode(st[len(head):], k - 1)
+        assert (want is None) == (streams.index(st) < 2 * len(forged))
+    got = DepressRun(streams, ns, seed=74).run(layout)
+    for j, name in enumerate(forged):
+        assert got[2 * j] is None, name
+        assert np.array_equal(got[2 * j + 1], good), name
+    for j, (name, (tail, v)) in enumerate(valid.items()):
+        g = got[2 * (len(forged) + j)]
+        assert g is not None and np.array_equal(g, _rcf.from_low(bytes(v))), name
+        assert np.array_equal(got[2 * (len(forged) + j) + 1], good), name
+    # the per-read symbol refuses a stream that says more samples than the capacity, and reads one that fits
+    ret, back = press.huffman_depress(layout, full, len(good) - 1)
+    assert ret == -1 and back.size == 0
+    ret, back = press.huffman_depress(layout, full, len(good) + 5)
+    assert ret == 0 and np.array_equal(back, good)
+
+
+@gpu
+def test_walk_and_repairs(lib):
+    """7: eight symbols of three bits each never synchronise: the read belongs to the walk and decodes; the three real
+    reads need no walk"""
+    layout = "vbbe21"
+    never = reads_by_name()["never-sync"]
+    stream = expected(layout, never)[0]
+    got = DepressRun([stream], [len(never)], seed=81).run(layout)
+    assert np.array_equal(got[0], never)
+    assert press.huffman_repairs()[2] > 0  # the walk had work
+    real = [s for _, s in _rcf.real_reads()]
+    got = DepressRun([expected(layout, s)[0] for s in real], [len(s) for s in real], seed=82).run(layout)
+    assert all(np.array_equal(g, s) for g, s in zip(got, real))
+    assert press.huffman_repairs()[2] == 0
+
+
+@gpu
+def test_forms(lib):
+    """8: host form = device form; the twelve per-read symbols; the same bytes whatever the scratch held"""
+    import torch
+    reads = [s for _, s in _rcf.named_reads()[3:]] + [_rcf.real_reads()[0][1]]
+    caps = [slot_for(len(r)) for r in reads]
+    short = _rcf.real_reads()[0][1]
+    for layout in D.LAYOUTS:
+        dev, dml = PressRun(reads, seed=91).run(layout)
+        streams, ml = press.huffman_press_batch_host(layout, reads, caps=caps, want_maxlen=True)
+        assert streams == dev and np.array_equal(ml, dml) and press.huffman_press_batch_host(layout, reads, caps=caps) == streams
+        need, ml2 = press.huffman_press_sizes_host(layout, reads, want_maxlen=True)
+        assert list(need) == [len(s) for s in streams] and np.array_equal(ml2, ml)
+        back = press.huffman_depress_batch_host(layout, streams, [len(r) for r in reads])
+        for r, g in enumerate(back):
+            assert np.array_equal(g, reads[r]), (layout, r)
+        assert press.huffman_bound(layout, len(short)) == getattr(lib, D.name(layout) + "_bound_16")(len(short))
+        ret, one = press.huffman_press(layout, short)
+        assert ret == 0 and one == expected(layout, short)[0]
+        ret, b = press.huffman_depress(layout, one, len(short))
+        assert ret == 0 and np.array_equal(b, short)
+    assert press.huffman_press_batch_host("vbe21", []) == [] and press.huffman_depress_batch_host("vbe21", [], []) == []
+    p = PressRun(reads, seed=92)
+    first = p.run("vbbe21")
+    d = DepressRun(first[0], [len(r) for r in reads], seed=93)
+    for fill in (0x00, 0xFF, 0xA5):
+        torch.cuda.synchronize()
+        press.scratch_fill(fill)
+        again = p.run("vbbe21")
+        assert again[0] == first[0] and np.array_equal(again[1], first[1]), fill
+        press.scratch_fill(fill)
+        assert np.array_equal(p.sizes("vbbe21")[0], [len(s) for s in first[0]]), fill
+        press.scratch_fill(fill)
+        for r, g in enumerate(d.run("vbbe21")):
+            assert np.array_equal(g, reads[r]), (fill, r)
