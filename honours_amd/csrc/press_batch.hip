@@ -334,26 +334,22 @@ extern "C" int press_hip_signal_tally(const int16_t *sig, const uint64_t *off, c
 
 // ------------------------------------------------------------------ depress: samples, picoamperes, normalised floats, chunk rows
 
-extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint64_t *in_off,
-				       const uint64_t *in_len, uint32_t nreads, int16_t *sig,
-				       const uint64_t *off, const uint32_t *n, uint64_t total_samples,
-				       uint32_t *out_n, int device_resident)
+// The depress of a method's row, behind the caller's argument check.  ready: the method id the device must be ready for
+// (NONE: a row of a family with ids of its own)
+static int row_depress(const Method &m, int ready, const StreamsIn &host, uint32_t nreads, uint64_t total_samples, int device_resident)
 {
-	API_LOCK;
-	int rc = args_ok(method, NONE, nreads && (!in || !in_off || !in_len || !sig || !off || !n || !out_n), nreads,
-			 device_resident ? sig : nullptr, "sig");
-	if (rc || (rc = device_ready(method, NONE)))
+	int rc = device_ready(ready, NONE);
+	if (rc)
 		return rc;
 	if (nreads == 0)
 		return 0;
 	hipStream_t s = g.stream();
-	const ScratchPlan plan = make_plan(method, total_samples, nreads, true);
+	const ScratchPlan plan = make_plan(m, total_samples, nreads, true);
 	if ((rc = plan.reserve()))
 		return rc;
 	DecodeArgs a;
 	plan.bind(a);
 	a.nreads = nreads;
-	const StreamsIn host = { in, in_off, in_len, off, n, out_n, sig };
 	StreamsIn io = host;
 	Staged st(nreads, s);
 	if (!device_resident && (rc = st.streams(host, total_samples, true, g.arena, g.arena_off, io)))
@@ -362,6 +358,17 @@ extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint
 	if ((rc = launch_depress(plan, a, s)) || device_resident)
 		return rc;
 	return st.fetch_samples(host);
+}
+
+extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint64_t *in_off,
+				       const uint64_t *in_len, uint32_t nreads, int16_t *sig,
+				       const uint64_t *off, const uint32_t *n, uint64_t total_samples,
+				       uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	const int rc = args_ok(method, NONE, nreads && (!in || !in_off || !in_len || !sig || !off || !n || !out_n), nreads,
+			       device_resident ? sig : nullptr, "sig");
+	return rc ? rc : row_depress(METHODS[method], method, { in, in_off, in_len, off, n, out_n, sig }, nreads, total_samples, device_resident);
 }
 
 // Picoamperes: press_hip_depress_batch with the float arena `pa` in the place of sig.  A fused method's decode kernel
@@ -1513,40 +1520,108 @@ extern "C" int press_hip_rcf_depress_batch(int coder, int layout, const uint8_t 
 					   uint32_t *out_n, int device_resident)
 {
 	API_LOCK;
-	int rc = rcf_args_ok(coder, layout, nreads && (!in || !in_off || !in_len || !sig || !off || !n || !out_n), nreads,
-			     device_resident ? sig : nullptr);
+	const int rc = rcf_args_ok(coder, layout, nreads && (!in || !in_off || !in_len || !sig || !off || !n || !out_n), nreads,
+				   device_resident ? sig : nullptr);
+	return rc ? rc : row_depress(rcf_method(coder, layout), NONE, { in, in_off, in_len, off, n, out_n, sig }, nreads, total_samples, device_resident);
+}
+
+// ------------------------------------------------------------------ the Rice family and the per-read Huffman family
+//
+// As the range-coder family with the layout alone in the place of the pair: the rows of RICE_METHODS (Golomb-Rice on every
+// layout) or of DHUF_METHODS (a code per read on every layout).  Press reports a byte of every read where the caller asks -
+// the Rice parameter k, the longest code -, and the sizes call runs the chain as far as the sizes.  One function each for
+// press, sizes and depress: a family is its rows and its name in the error text.
+
+struct PrefixFamily {
+	const Method *rows;
+	const char *name;
+};
+static constexpr PrefixFamily RICE_FAMILY = { RICE_METHODS, "Rice" }, DHUF_FAMILY = { DHUF_METHODS, "per-read Huffman" };
+
+static int prefix_args_ok(const PrefixFamily &f, int layout, bool null_arg, uint32_t nreads, const void *dev_arena)
+{
+	if (!rice_ok(layout))
+		return set_error(PRESS_HIP_EARG, "%s family: layout %d (0 vbe21, 1 vbbe21, 2 vbsbe21, 3 vbsse21)", f.name, layout);
+	return args_ok(NONE, NONE, null_arg, nreads, dev_arena, "sig");
+}
+
+// byte: k[] or maxlen[]
+static int prefix_press(const PrefixFamily &f, int layout, SamplesIn in, const SlotsOut &host, uint32_t nreads, uint64_t total_samples,
+			uint8_t *byte, int device_resident)
+{
+	API_LOCK;
+	int rc = prefix_args_ok(f, layout, nreads && (!in.sig || !in.off || !in.n || !host.out || !host.out_off || !host.out_len), nreads,
+				device_resident ? in.sig : nullptr);
 	if (rc || (rc = device_ready(NONE, NONE)))
 		return rc;
 	if (nreads == 0)
 		return 0;
 	hipStream_t s = g.stream();
-	const ScratchPlan plan = make_plan(rcf_method(coder, layout), total_samples, nreads, true);
+	ScratchPlan plan = make_plan(f.rows[layout], total_samples, nreads, false);
+	if (byte && !device_resident)
+		plan.need(&Ctx::ri_k, nreads);
 	if ((rc = plan.reserve()))
 		return rc;
-	DecodeArgs a;
+	BatchArgs a;
 	plan.bind(a);
 	a.nreads = nreads;
-	const StreamsIn host = { in, in_off, in_len, off, n, out_n, sig };
-	StreamsIn io = host;
+	SlotsOut so = host;
 	Staged st(nreads, s);
-	if (!device_resident && (rc = st.streams(host, total_samples, true, g.arena, g.arena_off, io)))
+	if (!device_resident && ((rc = check_slots(host.out_off, nreads)) || (rc = st.layout(in.off, in.n, total_samples, "the sample range", true)) ||
+				 (rc = st.slots(host, so)) || (rc = st.samples(in, total_samples, in))))
 		return rc;
-	bind_io(a, io);
-	if ((rc = launch_depress(plan, a, s)) || device_resident)
+	bind_io(a, in);
+	bind_io(a, so);
+	a.ri_k = device_resident ? byte : byte ? (uint8_t *) g.ri_k.p : nullptr;
+	if ((rc = launch_press(plan, a, s)) || device_resident)
 		return rc;
-	return st.fetch_samples(host);
+	if (byte)
+		HIPCHK(hipMemcpyAsync(byte, a.ri_k, nreads, hipMemcpyDeviceToHost, s));
+	return st.fetch_streams(host);
 }
 
-// ------------------------------------------------------------------ the Rice family: Golomb-Rice on every layout
-//
-// As the range-coder family with the layout alone in the place of the pair (rows of RICE_METHODS); press reports the
-// parameter k of every read where the caller asks, and press_hip_rice_press_sizes runs the chain as far as the sizes.
-
-static int rice_args_ok(int layout, bool null_arg, uint32_t nreads, const void *dev_arena)
+static int prefix_sizes(const PrefixFamily &f, int layout, SamplesIn in, uint32_t nreads, uint64_t total_samples, uint64_t *need,
+			uint8_t *byte, int device_resident)
 {
-	if (!rice_ok(layout))
-		return set_error(PRESS_HIP_EARG, "Rice family: layout %d (0 vbe21, 1 vbbe21, 2 vbsbe21, 3 vbsse21)", layout);
-	return args_ok(NONE, NONE, null_arg, nreads, dev_arena, "sig");
+	API_LOCK;
+	int rc = prefix_args_ok(f, layout, nreads && (!in.sig || !in.off || !in.n || !need), nreads, device_resident ? in.sig : nullptr);
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	const size_t nr = (size_t) nreads + 1;
+	const Method &m = f.rows[layout];
+	ScratchPlan plan = make_plan(m, total_samples, nreads, false);
+	plan.need(&Ctx::pslot, nr * 8); // the slot table the chain is run against: all zeros
+	if (!device_resident)
+		plan.need(&Ctx::pneed, nr * 8).need(&Ctx::ri_k, nreads);
+	if ((rc = plan.reserve()))
+		return rc;
+	BatchArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	Staged st(nreads, s);
+	if (!device_resident && (rc = st.samples_in(in, total_samples, in)))
+		return rc;
+	bind_io(a, in);
+	uint64_t *dneed = device_resident ? need : (uint64_t *) g.pneed.p;
+	HIPCHK(hipMemsetAsync(g.pslot.p, 0, nr * 8, s));
+	a.out_off = (const uint64_t *) g.pslot.p;
+	a.out_len = dneed;
+	a.ri_k = device_resident ? byte : byte ? (uint8_t *) g.ri_k.p : nullptr;
+	launch_ex_prefix_sizes(a, m.exfmt, m.ent, dneed, s);
+	if ((rc = launch_status()) || device_resident)
+		return rc;
+	return st.fetch_tables({ { need, dneed, (size_t) nreads * 8 }, { byte, a.ri_k, nreads } });
+}
+
+static int prefix_depress(const PrefixFamily &f, int layout, const StreamsIn &host, uint32_t nreads, uint64_t total_samples, int device_resident)
+{
+	API_LOCK;
+	const int rc = prefix_args_ok(f, layout, nreads && (!host.in || !host.in_off || !host.in_len || !host.sig || !host.off || !host.n || !host.out_n),
+				      nreads, device_resident ? host.sig : nullptr);
+	return rc ? rc : row_depress(f.rows[layout], NONE, host, nreads, total_samples, device_resident);
 }
 
 extern "C" uint64_t press_hip_rice_bound(int layout, uint32_t n)
@@ -1558,102 +1633,20 @@ extern "C" int press_hip_rice_press_batch(int layout, const int16_t *sig, const 
 					  uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len, uint8_t *k,
 					  int device_resident)
 {
-	API_LOCK;
-	int rc = rice_args_ok(layout, nreads && (!sig || !off || !n || !out || !out_off || !out_len), nreads,
-			      device_resident ? sig : nullptr);
-	if (rc || (rc = device_ready(NONE, NONE)))
-		return rc;
-	if (nreads == 0)
-		return 0;
-	hipStream_t s = g.stream();
-	ScratchPlan plan = make_plan(RICE_METHODS[layout], total_samples, nreads, false);
-	if (k && !device_resident)
-		plan.need(&Ctx::ri_k, nreads);
-	if ((rc = plan.reserve()))
-		return rc;
-	BatchArgs a;
-	plan.bind(a);
-	a.nreads = nreads;
-	const SlotsOut host = { out, out_off, out_len };
-	SamplesIn in = { sig, off, n };
-	SlotsOut so = host;
-	Staged st(nreads, s);
-	if (!device_resident && ((rc = check_slots(out_off, nreads)) || (rc = st.layout(off, n, total_samples, "the sample range", true)) ||
-				 (rc = st.slots(host, so)) || (rc = st.samples(in, total_samples, in))))
-		return rc;
-	bind_io(a, in);
-	bind_io(a, so);
-	a.ri_k = device_resident ? k : k ? (uint8_t *) g.ri_k.p : nullptr;
-	if ((rc = launch_press(plan, a, s)) || device_resident)
-		return rc;
-	if (k)
-		HIPCHK(hipMemcpyAsync(k, a.ri_k, nreads, hipMemcpyDeviceToHost, s));
-	return st.fetch_streams(host);
+	return prefix_press(RICE_FAMILY, layout, { sig, off, n }, { out, out_off, out_len }, nreads, total_samples, k, device_resident);
 }
 
 extern "C" int press_hip_rice_press_sizes(int layout, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
 					  uint64_t total_samples, uint64_t *need, uint8_t *k, int device_resident)
 {
-	API_LOCK;
-	int rc = rice_args_ok(layout, nreads && (!sig || !off || !n || !need), nreads, device_resident ? sig : nullptr);
-	if (rc || (rc = device_ready(NONE, NONE)))
-		return rc;
-	if (nreads == 0)
-		return 0;
-	hipStream_t s = g.stream();
-	const size_t nr = (size_t) nreads + 1;
-	ScratchPlan plan = make_plan(RICE_METHODS[layout], total_samples, nreads, false);
-	plan.need(&Ctx::pslot, nr * 8); // the slot table the chain is run against: all zeros
-	if (!device_resident)
-		plan.need(&Ctx::pneed, nr * 8).need(&Ctx::ri_k, nreads);
-	if ((rc = plan.reserve()))
-		return rc;
-	BatchArgs a;
-	plan.bind(a);
-	a.nreads = nreads;
-	SamplesIn in = { sig, off, n };
-	Staged st(nreads, s);
-	if (!device_resident && (rc = st.samples_in(in, total_samples, in)))
-		return rc;
-	bind_io(a, in);
-	uint64_t *dneed = device_resident ? need : (uint64_t *) g.pneed.p;
-	HIPCHK(hipMemsetAsync(g.pslot.p, 0, nr * 8, s));
-	a.out_off = (const uint64_t *) g.pslot.p;
-	a.out_len = dneed;
-	a.ri_k = device_resident ? k : k ? (uint8_t *) g.ri_k.p : nullptr;
-	launch_ex_rice_sizes(a, RICE_METHODS[layout].exfmt, dneed, s);
-	if ((rc = launch_status()) || device_resident)
-		return rc;
-	return st.fetch_tables({ { need, dneed, (size_t) nreads * 8 }, { k, a.ri_k, nreads } });
+	return prefix_sizes(RICE_FAMILY, layout, { sig, off, n }, nreads, total_samples, need, k, device_resident);
 }
 
 extern "C" int press_hip_rice_depress_batch(int layout, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
 					    uint32_t nreads, int16_t *sig, const uint64_t *off, const uint32_t *n, uint64_t total_samples,
 					    uint32_t *out_n, int device_resident)
 {
-	API_LOCK;
-	int rc = rice_args_ok(layout, nreads && (!in || !in_off || !in_len || !sig || !off || !n || !out_n), nreads,
-			      device_resident ? sig : nullptr);
-	if (rc || (rc = device_ready(NONE, NONE)))
-		return rc;
-	if (nreads == 0)
-		return 0;
-	hipStream_t s = g.stream();
-	const ScratchPlan plan = make_plan(RICE_METHODS[layout], total_samples, nreads, true);
-	if ((rc = plan.reserve()))
-		return rc;
-	DecodeArgs a;
-	plan.bind(a);
-	a.nreads = nreads;
-	const StreamsIn host = { in, in_off, in_len, off, n, out_n, sig };
-	StreamsIn io = host;
-	Staged st(nreads, s);
-	if (!device_resident && (rc = st.streams(host, total_samples, true, g.arena, g.arena_off, io)))
-		return rc;
-	bind_io(a, io);
-	if ((rc = launch_depress(plan, a, s)) || device_resident)
-		return rc;
-	return st.fetch_samples(host);
+	return prefix_depress(RICE_FAMILY, layout, { in, in_off, in_len, off, n, out_n, sig }, nreads, total_samples, device_resident);
 }
 
 // what the repair rounds and the serial walk of the last press_hip_rice_depress_batch had to touch
@@ -1675,18 +1668,6 @@ extern "C" int press_hip_rice_repairs(uint32_t counts[3])
 	return 0;
 }
 
-// ------------------------------------------------------------------ the per-read Huffman family: a code per read on every layout
-//
-// As the Rice family (rows of DHUF_METHODS); press reports the longest code of every read where the caller asks, and
-// press_hip_huffman_press_sizes runs the chain as far as the sizes.
-
-static int dhuf_args_ok(int layout, bool null_arg, uint32_t nreads, const void *dev_arena)
-{
-	if (!rice_ok(layout))
-		return set_error(PRESS_HIP_EARG, "per-read Huffman family: layout %d (0 vbe21, 1 vbbe21, 2 vbsbe21, 3 vbsse21)", layout);
-	return args_ok(NONE, NONE, null_arg, nreads, dev_arena, "sig");
-}
-
 extern "C" uint64_t press_hip_huffman_bound(int layout, uint32_t n)
 {
 	return rice_ok(layout) ? bound_vbzd(n) : 0; // press.c:3965, 4061, 4177, 4293: vb1e2_zd_bound_16 for all four
@@ -1696,102 +1677,20 @@ extern "C" int press_hip_huffman_press_batch(int layout, const int16_t *sig, con
 					     uint64_t total_samples, uint8_t *out, const uint64_t *out_off, uint64_t *out_len,
 					     uint8_t *maxlen, int device_resident)
 {
-	API_LOCK;
-	int rc = dhuf_args_ok(layout, nreads && (!sig || !off || !n || !out || !out_off || !out_len), nreads,
-			      device_resident ? sig : nullptr);
-	if (rc || (rc = device_ready(NONE, NONE)))
-		return rc;
-	if (nreads == 0)
-		return 0;
-	hipStream_t s = g.stream();
-	ScratchPlan plan = make_plan(DHUF_METHODS[layout], total_samples, nreads, false);
-	if (maxlen && !device_resident)
-		plan.need(&Ctx::ri_k, nreads);
-	if ((rc = plan.reserve()))
-		return rc;
-	BatchArgs a;
-	plan.bind(a);
-	a.nreads = nreads;
-	const SlotsOut host = { out, out_off, out_len };
-	SamplesIn in = { sig, off, n };
-	SlotsOut so = host;
-	Staged st(nreads, s);
-	if (!device_resident && ((rc = check_slots(out_off, nreads)) || (rc = st.layout(off, n, total_samples, "the sample range", true)) ||
-				 (rc = st.slots(host, so)) || (rc = st.samples(in, total_samples, in))))
-		return rc;
-	bind_io(a, in);
-	bind_io(a, so);
-	a.ri_k = device_resident ? maxlen : maxlen ? (uint8_t *) g.ri_k.p : nullptr;
-	if ((rc = launch_press(plan, a, s)) || device_resident)
-		return rc;
-	if (maxlen)
-		HIPCHK(hipMemcpyAsync(maxlen, a.ri_k, nreads, hipMemcpyDeviceToHost, s));
-	return st.fetch_streams(host);
+	return prefix_press(DHUF_FAMILY, layout, { sig, off, n }, { out, out_off, out_len }, nreads, total_samples, maxlen, device_resident);
 }
 
 extern "C" int press_hip_huffman_press_sizes(int layout, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
 					     uint64_t total_samples, uint64_t *need, uint8_t *maxlen, int device_resident)
 {
-	API_LOCK;
-	int rc = dhuf_args_ok(layout, nreads && (!sig || !off || !n || !need), nreads, device_resident ? sig : nullptr);
-	if (rc || (rc = device_ready(NONE, NONE)))
-		return rc;
-	if (nreads == 0)
-		return 0;
-	hipStream_t s = g.stream();
-	const size_t nr = (size_t) nreads + 1;
-	ScratchPlan plan = make_plan(DHUF_METHODS[layout], total_samples, nreads, false);
-	plan.need(&Ctx::pslot, nr * 8); // the slot table the chain is run against: all zeros
-	if (!device_resident)
-		plan.need(&Ctx::pneed, nr * 8).need(&Ctx::ri_k, nreads);
-	if ((rc = plan.reserve()))
-		return rc;
-	BatchArgs a;
-	plan.bind(a);
-	a.nreads = nreads;
-	SamplesIn in = { sig, off, n };
-	Staged st(nreads, s);
-	if (!device_resident && (rc = st.samples_in(in, total_samples, in)))
-		return rc;
-	bind_io(a, in);
-	uint64_t *dneed = device_resident ? need : (uint64_t *) g.pneed.p;
-	HIPCHK(hipMemsetAsync(g.pslot.p, 0, nr * 8, s));
-	a.out_off = (const uint64_t *) g.pslot.p;
-	a.out_len = dneed;
-	a.ri_k = device_resident ? maxlen : maxlen ? (uint8_t *) g.ri_k.p : nullptr;
-	launch_ex_dhuf_sizes(a, DHUF_METHODS[layout].exfmt, dneed, s);
-	if ((rc = launch_status()) || device_resident)
-		return rc;
-	return st.fetch_tables({ { need, dneed, (size_t) nreads * 8 }, { maxlen, a.ri_k, nreads } });
+	return prefix_sizes(DHUF_FAMILY, layout, { sig, off, n }, nreads, total_samples, need, maxlen, device_resident);
 }
 
 extern "C" int press_hip_huffman_depress_batch(int layout, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
 					       uint32_t nreads, int16_t *sig, const uint64_t *off, const uint32_t *n,
 					       uint64_t total_samples, uint32_t *out_n, int device_resident)
 {
-	API_LOCK;
-	int rc = dhuf_args_ok(layout, nreads && (!in || !in_off || !in_len || !sig || !off || !n || !out_n), nreads,
-			      device_resident ? sig : nullptr);
-	if (rc || (rc = device_ready(NONE, NONE)))
-		return rc;
-	if (nreads == 0)
-		return 0;
-	hipStream_t s = g.stream();
-	const ScratchPlan plan = make_plan(DHUF_METHODS[layout], total_samples, nreads, true);
-	if ((rc = plan.reserve()))
-		return rc;
-	DecodeArgs a;
-	plan.bind(a);
-	a.nreads = nreads;
-	const StreamsIn host = { in, in_off, in_len, off, n, out_n, sig };
-	StreamsIn io = host;
-	Staged st(nreads, s);
-	if (!device_resident && (rc = st.streams(host, total_samples, true, g.arena, g.arena_off, io)))
-		return rc;
-	bind_io(a, io);
-	if ((rc = launch_depress(plan, a, s)) || device_resident)
-		return rc;
-	return st.fetch_samples(host);
+	return prefix_depress(DHUF_FAMILY, layout, { in, in_off, in_len, off, n, out_n, sig }, nreads, total_samples, device_resident);
 }
 
 // what the repair rounds and the serial walk of the last press_hip_huffman_depress_batch had to touch (the counters are

@@ -2513,32 +2513,23 @@ void launch_ex_encode_packed(const BatchArgs &a, int fmt, int ent, const PackArg
 		ex_encode_streams(a, fmt, ent, s);
 }
 
-// press_hip_rice_press_sizes: the chain up to the exception lists as the packed press runs it (k_chunk_prep leaves status 0,
-// so k_low_encode_chunked writes every read's one-byte values to a.low_tmp without a section in front), k_ex_sizes for
-// header and section, then the Rice count and pick.  Nothing of the caller's but need[] is written.
-void launch_ex_rice_sizes(const BatchArgs &a, int fmt, uint64_t *need, hipStream_t s)
+// press_hip_rice_press_sizes, press_hip_huffman_press_sizes (ent 6, 7): the chain up to the exception lists as the packed
+// press runs it (k_chunk_prep leaves status 0, so k_low_encode_chunked writes every read's one-byte values to a.low_tmp
+// without a section in front), k_ex_sizes for header and section, then the stage's own sizes: the Rice count and pick, or
+// the per-read Huffman hist and tree.  Nothing of the caller's but need[] is written.
+void launch_ex_prefix_sizes(const BatchArgs &a, int fmt, int ent, uint64_t *need, hipStream_t s)
 {
 	if (!a.nreads || !a.max_chunks)
 		return;
 	ex_encode_prep(a, s);
-	ex_pass_a(a, 6, s);
+	ex_pass_a(a, ent, s);
 	ex_encode_lists(a, fmt, s);
-	launch_ex_sizes(a, fmt, 6, need, s);
+	launch_ex_sizes(a, fmt, ent, need, s);
 	hipLaunchKernelGGL(k_low_encode_chunked<false>, dim3(a.max_chunks), dim3(CWG), 0, s, a);
-	launch_rice_encode(a, need, s);
-}
-
-// press_hip_huffman_press_sizes: the same chain with the per-read Huffman stage at its end (hist and tree)
-void launch_ex_dhuf_sizes(const BatchArgs &a, int fmt, uint64_t *need, hipStream_t s)
-{
-	if (!a.nreads || !a.max_chunks)
-		return;
-	ex_encode_prep(a, s);
-	ex_pass_a(a, 7, s);
-	ex_encode_lists(a, fmt, s);
-	launch_ex_sizes(a, fmt, 7, need, s);
-	hipLaunchKernelGGL(k_low_encode_chunked<false>, dim3(a.max_chunks), dim3(CWG), 0, s, a);
-	launch_dhuf_encode(a, need, s);
+	if (ent == 6)
+		launch_rice_encode(a, need, s);
+	else
+		launch_dhuf_encode(a, need, s);
 }
 
 // Recode, fused (press_hip_recode_batch): the svb decode of `d` leaves pass A's results in the chunk table of the press

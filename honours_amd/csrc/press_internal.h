@@ -129,26 +129,35 @@ struct ChunkCtl {                           // device control block; every word 
 	uint32_t pad5[31];
 };
 
-// The Rice methods (press_rice.hip).  Press: a read's one-byte values in units of RICE_UNIT, a wave each; unit i of a read is
-// entry RICE_UPC * first_chunk + i of the unit tables.  Depress: the payload in subsequences of RICE_SUB bits, a lane each,
-// RICE_DT of them a tile.
-constexpr uint32_t RICE_UNIT = 1024;
-constexpr uint32_t RICE_UPC = CHUNK / RICE_UNIT;
-constexpr uint32_t RICE_COPY = 1280; // payload bytes per unit index in k_rice_copy: more than RICE_UNIT values at nine bits take
-constexpr uint32_t RICE_SUB = 256;
-constexpr uint32_t RICE_DT = 256;
-constexpr uint32_t RICE_CTL_WORDS = 16; // DecodeArgs::ri_ctl: tiles; subsequences decoded again by fix round 1, 2; values of the walk
-struct RiceRead {             // press, per read (k_rice_pick)
+// The prefix-code engine (press_prefix.h) of the Rice methods (press_rice.hip) and the per-read Huffman methods
+// (press_dhuf.hip).  Press: a read's one-byte values in units of PFX_UNIT, a wave each; unit i of a read is entry
+// PFX_UPC * first_chunk + i of the unit tables.  Depress: the payload in subsequences of PFX_SUB bits, a lane each, PFX_DT
+// of them a tile.  Both families use the buffers BatchArgs::ri_* and DecodeArgs::ri_* and the two records below.
+constexpr uint32_t PFX_UNIT = 1024;
+constexpr uint32_t PFX_UPC = CHUNK / PFX_UNIT;
+constexpr uint32_t PFX_COPY = 1280; // payload bytes per unit index in prefix_copy: more than PFX_UNIT values at nine bits take
+constexpr uint32_t PFX_WIN = 256;   // dwords of a writer's LDS window
+constexpr uint32_t PFX_SUB = 256;
+constexpr uint32_t PFX_DT = 256;
+constexpr uint32_t PFX_CTL_WORDS = 16; // DecodeArgs::ri_ctl: tiles; subsequences decoded again by the first fix round, by the later ones; values of the walk
+constexpr uint64_t PFX_FAIL64 = ~0ull;
+constexpr uint32_t PFX_NONE = 0xFFFFFFFFu; // record: no start known (the subsequence was given up); tile table: an id that is not used
+constexpr uint32_t PFX_SAT = 0xFFFFFFFEu;  // record: no end
+struct PfxRead {              // press, per read (k_rice_pick / k_dh_tree)
 	uint64_t nbits;       // payload bits
 	uint64_t paylen;      // ... and bytes
-	uint32_t k;
 	uint32_t ok;          // 0: refused (k_ex_section), or the slot is too small
 	uint32_t nlow, nunits;
+	uint32_t k;           // Rice: the parameter
+	uint32_t tablen;      // per-read Huffman: bytes of the table in front of the payload
+	uint32_t maxlen;      // ... the longest code
+	uint32_t nsym;        // ... the symbols present
+	uint32_t pad;
 };
-struct RiceDRead {            // depress, per read (k_rice_dplan)
+struct PfxDRead {             // depress, per read (prefix_dplan)
 	uint64_t paylen;      // payload bytes
 	uint64_t wpos, widx;  // where the serial walk starts: bit, value
-	uint32_t k;
+	uint32_t k;           // Rice: the parameter (per-read Huffman: 0)
 	uint32_t nsubs;       // subsequences decoded in parallel
 	uint32_t tile0;       // first tile
 	uint32_t nlow;
@@ -156,20 +165,10 @@ struct RiceDRead {            // depress, per read (k_rice_dplan)
 	uint32_t ok;          // k_ex_parse accepted the read
 };
 
-// The per-read Huffman methods (press_dhuf.hip).  Units, subsequences and tiles are the Rice methods', and so are their
-// buffers (BatchArgs::ri_*, DecodeArgs::ri_*); ri_rd holds DhRead records.  dh_tab is the family's own: per read
-// DH_PRESS_TAB bytes for press (256 x { code | len << 56 }, then the 256 counts), a DhTab for depress.
-constexpr uint32_t DH_UNIT = RICE_UNIT;
+// The per-read Huffman methods' own (press_dhuf.hip): dh_tab, per read DH_PRESS_TAB bytes for press (256 x { code | len << 56 },
+// then the 256 counts), a DhTab for depress.
 constexpr uint32_t DH_W = 11;                        // bits of the decoder's direct look-up
 constexpr uint32_t DH_PRESS_TAB = 256 * 8 + 256 * 4;
-struct DhRead {               // press, per read (k_dh_tree)
-	uint64_t nbits;       // payload bits
-	uint64_t paylen;      // ... and bytes
-	uint32_t tablen;      // bytes of the table in front of the payload
-	uint32_t maxlen;      // the longest code
-	uint32_t ok;          // 0: refused (k_ex_section), or the slot is too small
-	uint32_t nlow, nunits, nsym;
-};
 struct DhTab {                // depress, per read (k_dh_table)
 	uint64_t lcode[256];  // the codes, first bit on top, ascending
 	uint16_t ent[256];    // ... their symbol | len << 8
@@ -179,7 +178,7 @@ struct DhTab {                // depress, per read (k_dh_table)
 	uint32_t mode;        // 0: decode the payload, 1: nothing to decode (no value, or one symbol without a bit), 2: refused
 	uint32_t pad;
 };
-static_assert(sizeof(DhRead) % 8 == 0 && sizeof(DhTab) % 8 == 0, "arrays of them keep their uint64_t aligned");
+static_assert(sizeof(PfxRead) % 8 == 0 && sizeof(PfxDRead) % 8 == 0 && sizeof(DhTab) % 8 == 0, "arrays of them keep their uint64_t aligned");
 
 // Arguments common to every batch kernel.
 struct BatchArgs {
@@ -206,10 +205,10 @@ struct BatchArgs {
 	                          // encoder has them in registers (zeroed by the caller; NULL for the other methods)
 	uint32_t *zkcnt;          // ... and [max_chunks] at a read's FIRST chunk: the read's key bytes that are not zero (with zhist;
 	                          // their positions and values are listed in ex_pos / ex_val of the read, in order)
-	// the Rice methods (press_rice.hip; NULL for the other methods)
-	uint32_t *ri_sum;         // [max_chunks * RICE_UPC][8] per unit: the sums of x >> k
-	uint64_t *ri_start;       // [max_chunks * RICE_UPC] per unit: its first bit of the read's payload
-	RiceRead *ri_rd;          // [nreads]
+	// the Rice and the per-read Huffman methods (press_prefix.h; NULL for the other methods)
+	uint32_t *ri_sum;         // [max_chunks * PFX_UPC][8] per unit: Rice: the sums of x >> k; per-read Huffman: its bits, in the first word
+	uint64_t *ri_start;       // [max_chunks * PFX_UPC] per unit: its first bit of the read's payload
+	PfxRead *ri_rd;           // [nreads]
 	uint8_t *ri_pay;          // the staged payloads: read r's at 2 * off[r], ri_pay_bytes in all
 	uint64_t ri_pay_bytes;
 	uint8_t *ri_k;            // [nreads] the caller's k[] (per-read Huffman: maxlen[]), or NULL
@@ -258,12 +257,12 @@ struct DecodeArgs {
 	uint32_t max_htiles;
 	uint32_t hlist_cap;
 	uint32_t huf_minlen;      // shortest code of the table (selects the subsequence size on the host)
-	// the Rice methods (press_rice.hip; NULL for the other methods)
-	RiceDRead *ri_drd;        // [nreads]
+	// the Rice and the per-read Huffman methods (press_prefix.h; NULL for the other methods)
+	PfxDRead *ri_drd;         // [nreads]
 	uint2 *ri_tile;           // [ri_max_tiles] { read, tile of the read }
-	uint32_t *ri_rec;         // [ri_max_tiles * RICE_DT][3] per subsequence: start, end, codes
+	uint32_t *ri_rec;         // [ri_max_tiles * PFX_DT][3] per subsequence: start, end, codes
 	uint64_t *ri_tbase;       // [2 * ri_max_tiles] per tile: the read's codes in front of it; behind them: the tiles' own counts
-	uint32_t *ri_ctl;         // [RICE_CTL_WORDS]
+	uint32_t *ri_ctl;         // [PFX_CTL_WORDS]; what the last depress of either family left
 	uint32_t ri_max_tiles;
 	uint8_t *dh_tab;          // the per-read Huffman methods (press_dhuf.hip): [nreads] DhTab
 };
@@ -560,14 +559,13 @@ void launch_cdf_decode(const DecodeArgs &a, hipStream_t s);
 // ent 6: Golomb-Rice (rice_*_zd), press_rice.hip.  need != NULL: k_rice_count and k_rice_pick alone, need[r] += the payload's bytes
 void launch_rice_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);
 void launch_rice_decode(const DecodeArgs &a, hipStream_t s);
-// press_hip_rice_press_sizes: the press chain of ent 6 as far as the sizes; a.out_off: nreads + 1 zeros, a.out_len == need
-void launch_ex_rice_sizes(const BatchArgs &a, int fmt, uint64_t *need, hipStream_t s); // press_chunked.hip
 // ent 7: a Huffman code per read (huffman_*_zd), press_dhuf.hip.  need != NULL: k_dh_hist and k_dh_tree alone, need[r] += the
 // bytes of table and payload
 void launch_dhuf_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);
 void launch_dhuf_decode(const DecodeArgs &a, hipStream_t s);
-// press_hip_huffman_press_sizes: launch_ex_rice_sizes with ent 7
-void launch_ex_dhuf_sizes(const BatchArgs &a, int fmt, uint64_t *need, hipStream_t s); // press_chunked.hip
+// press_hip_{rice, huffman}_press_sizes: the press chain of ent 6 or 7 as far as the sizes; a.out_off: nreads + 1 zeros,
+// a.out_len == need
+void launch_ex_prefix_sizes(const BatchArgs &a, int fmt, int ent, uint64_t *need, hipStream_t s); // press_chunked.hip
 // behind the encode of a range-coder method (ent >= 2): raw[r] = 1 where the coder gave up and stored the one-byte values
 void launch_rcf_raw(const BatchArgs &a, uint8_t *raw, hipStream_t s);
 // symbol counts of a batch for fitting a Huffman table (press_train.hip): adds into counts[257]; chunks takes

@@ -139,21 +139,21 @@ ScratchPlan make_plan(const Method &method, uint64_t total_samples, uint32_t nre
 	if (is_rc(k))
 		p.need(&Ctx::low, total_samples + 64); // the one-byte values between the two stages
 	if ((is_rice(k) || is_dhuf(k)) && !decode) {
-		// press_rice.hip: 32 units per chunk; a staged payload never takes more than nine bits a value, the reads' stagings
+		// press_prefix.h: 32 units per chunk; a staged payload never takes more than nine bits a value, the reads' stagings
 		// start at twice their sample offsets
 		p.ri_pay_bytes = 2 * total_samples + 64;
-		p.need(&Ctx::ri_sum, mc * RICE_UPC * 32).need(&Ctx::ri_start, mc * RICE_UPC * 8).need(&Ctx::ri_rd, nr * sizeof(RiceRead))
+		p.need(&Ctx::ri_sum, mc * PFX_UPC * 32).need(&Ctx::ri_start, mc * PFX_UPC * 8).need(&Ctx::ri_rd, nr * sizeof(PfxRead))
 			.need(&Ctx::ri_pay, p.ri_pay_bytes);
 	}
 	if ((is_rice(k) || is_dhuf(k)) && decode) {
-		// tiles of RICE_DT subsequences of RICE_SUB bits: a read has at most ceil((9 nlow + 3) / RICE_SUB) subsequences
-		const uint64_t dt = total_samples * 9 / ((uint64_t) RICE_SUB * RICE_DT) + 2ull * nreads + 2;
+		// tiles of PFX_DT subsequences of PFX_SUB bits: a read has at most ceil((9 nlow + 3) / PFX_SUB) subsequences
+		const uint64_t dt = total_samples * 9 / ((uint64_t) PFX_SUB * PFX_DT) + 2ull * nreads + 2;
 		const size_t mt = p.ri_max_tiles = dt > 0xFFFFFFull ? 0xFFFFFFu : (uint32_t) dt;
-		p.need(&Ctx::ri_drd, nr * sizeof(RiceDRead)).need(&Ctx::ri_tile, mt * sizeof(uint2)).need(&Ctx::ri_rec, mt * RICE_DT * 12)
-			.need(&Ctx::ri_tbase, mt * 16).need(&Ctx::ri_ctl, RICE_CTL_WORDS * 4);
+		p.need(&Ctx::ri_drd, nr * sizeof(PfxDRead)).need(&Ctx::ri_tile, mt * sizeof(uint2)).need(&Ctx::ri_rec, mt * PFX_DT * 12)
+			.need(&Ctx::ri_tbase, mt * 16).need(&Ctx::ri_ctl, PFX_CTL_WORDS * 4);
 	}
-	if (is_dhuf(k)) // press_dhuf.hip: the Rice methods' buffers (ri_rd holds DhRead records), and the reads' tables
-		p.need(&Ctx::ri_rd, nr * sizeof(DhRead)).need(&Ctx::dh_tab, nr * (decode ? sizeof(DhTab) : (size_t) DH_PRESS_TAB));
+	if (is_dhuf(k)) // press_dhuf.hip: beside the engine's buffers, the reads' tables
+		p.need(&Ctx::dh_tab, nr * (decode ? sizeof(DhTab) : (size_t) DH_PRESS_TAB));
 	if (decode && is_shuff(k)) {
 		// Huffman tiles of a batch (press_huffman.hip, k_huff_tiles): a read of n samples has at most
 		// n - 1 codes of at most maxlen bits, cut into tiles of HUF_HT subsequences

@@ -62,6 +62,36 @@ __device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v, uint32_t lane)
 	return v;
 }
 
+// ... of 32-bit values
+__device__ __forceinline__ uint32_t scan32(uint32_t v, uint32_t lane)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint32_t o = (uint32_t) __shfl_up((int) v, d, 64);
+		if (lane >= (uint32_t) d)
+			v += o;
+	}
+	return v;
+}
+
+// sum / maximum over the lanes of a wave, to every lane
+__device__ __forceinline__ uint64_t sum64(uint64_t v)
+{
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1)
+		v += __shfl_xor(v, d, 64);
+	return v;
+}
+__device__ __forceinline__ uint32_t max32(uint32_t v)
+{
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) {
+		const uint32_t o = (uint32_t) __shfl_xor((int) v, d, 64);
+		v = o > v ? o : v;
+	}
+	return v;
+}
+
 // zig-zag delta of the two samples packed in `cur`, given the dword holding the two
 // samples before them (trans.c:75,215 on packed 16-bit lanes)
 __device__ __forceinline__ uint32_t zd_pair(uint32_t cur, uint32_t prevdw)

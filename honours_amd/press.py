@@ -1101,7 +1101,79 @@ def rcf_depress_batch_host(coder, layout, streams, ns):
 
 
 # ---- the Rice family (press_hip_rice_*) and the per-read Huffman family (press_hip_huffman_*) have modules of their own,
-# honours_amd/rice.py and honours_amd/huffman.py; their wrappers are reachable here too
+# honours_amd/rice.py and honours_amd/huffman.py; their wrappers are reachable here too.  The two ABIs differ in the
+# symbols' prefix ("rice", "huffman") and in what the per-read byte means (k, the longest code): the wrappers' bodies are
+# these helpers.
+
+
+def _prefix_layout(layout):
+    return RCF_LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+
+
+def _prefix_name(prefix, layout):
+    l = _prefix_layout(layout)
+    return "%s_%s_zd" % (prefix, [k for k, v in RCF_LAYOUTS.items() if v == l][0])
+
+
+def _prefix_bound(prefix, layout, n):
+    return int(getattr(load_library(), "press_hip_%s_bound" % prefix)(_prefix_layout(layout), int(n)))
+
+
+def _prefix_press_batch(prefix, layout, sig, off, n, out, out_off, out_len, byte):
+    _call("press_hip_%s_press_batch" % prefix, _prefix_layout(layout), _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(),
+          _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(byte), 1)
+
+
+def _prefix_press_sizes(prefix, layout, sig, off, n, need, byte):
+    _call("press_hip_%s_press_sizes" % prefix, _prefix_layout(layout), _ptr(sig), _ptr(off), _ptr(n), off.numel(), sig.numel(),
+          _ptr(need), _ptr(byte), 1)
+
+
+def _prefix_depress_batch(prefix, layout, comp, in_off, in_len, sig, off, n, out_n):
+    _call("press_hip_%s_depress_batch" % prefix, _prefix_layout(layout), _ptr(comp), _ptr(in_off), _ptr(in_len), off.numel(),
+          _ptr(sig), _ptr(off), _ptr(n), sig.numel(), _ptr(out_n), 1)
+
+
+def _prefix_press_batch_host(prefix, slack, layout, reads, caps, want_byte):
+    """slack: what a default slot has beyond the bound"""
+    l = _prefix_layout(layout)
+    nreads = len(reads)
+    sig, off, ns, total = _host_batch(reads)
+    if caps is None:
+        caps = [_prefix_bound(prefix, l, int(x)) + slack if x else 32 for x in ns]
+    out_off = _slots(caps)
+    out = np.zeros(int(out_off[-1]) + 64, dtype=np.uint8)
+    out_len = np.zeros(nreads, dtype=np.uint64)
+    byte = np.zeros(nreads, dtype=np.uint8)
+    _call("press_hip_%s_press_batch" % prefix, l, _ptr(sig), _ptr(off), _ptr(ns), nreads, total, _ptr(out), _ptr(out_off),
+          _ptr(out_len), _ptr(byte) if want_byte else None, 0)
+    streams = _streams_of(out, out_off, out_len)
+    return (streams, byte) if want_byte else streams
+
+
+def _prefix_press_sizes_host(prefix, layout, reads, want_byte):
+    nreads = len(reads)
+    sig, off, ns, total = _host_batch(reads)
+    need = np.zeros(nreads, dtype=np.uint64)
+    byte = np.zeros(nreads, dtype=np.uint8)
+    _call("press_hip_%s_press_sizes" % prefix, _prefix_layout(layout), _ptr(sig), _ptr(off), _ptr(ns), nreads, total, _ptr(need),
+          _ptr(byte) if want_byte else None, 0)
+    return (need, byte) if want_byte else need
+
+
+def _prefix_depress_batch_host(prefix, layout, streams, ns):
+    comp, in_off, in_len, ns, off, total = _decode_batch(streams, ns)
+    sig = np.zeros(total + 64, dtype=np.int16)
+    out_n = np.zeros(len(streams), dtype=np.uint32)
+    _call("press_hip_%s_depress_batch" % prefix, _prefix_layout(layout), _ptr(comp), _ptr(in_off), _ptr(in_len), len(streams),
+          _ptr(sig), _ptr(off), _ptr(ns), total, _ptr(out_n), 0)
+    return _reads_of(sig, off, out_n)
+
+
+def _prefix_repairs(prefix):
+    c = np.zeros(3, dtype=np.uint32)
+    _call("press_hip_%s_repairs" % prefix, _ptr(c))
+    return tuple(int(x) for x in c)
 
 
 def __getattr__(name):

@@ -13,19 +13,14 @@ import numpy as np
 import pytest
 
 import _dhuf as D
-import _layouts as L
+import _prefix_runs as P
 import _rcf
 from honours_amd import press
 
 gpu = pytest.mark.gpu
 EARG = -2
-FAILED64 = (1 << 64) - 1
-FAILED32 = (1 << 32) - 1
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 HEADER = os.path.join(ROOT, "include", "press_hip.h")
-GUARD = 48
-FILL8, FILL16 = 0xA5, 0x5A5A
-CANARY = 0x5AC35AC3
 SUB, TILE = 256, 256  # bits of a reader's subsequence, subsequences of a tile (press_internal.h)
 
 _cache = {}
@@ -234,126 +229,32 @@ def test_wrappers_without_gpu(cpu_lib):
 
 # ------------------------------------------------------------------ GPU plumbing
 
+slot_for = P.slot_for
+FAMILY = P.Family(press.huffman_press_batch, press.huffman_press_sizes, press.huffman_depress_batch, "maxlen")
+RICE = P.Family(press.rice_press_batch, press.rice_press_sizes, press.rice_depress_batch, "k")
+
+
 @pytest.fixture(scope="module")
 def lib():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    lb = press.load_library()
-    press.use_torch_stream()
-    yield lb
-    torch.cuda.synchronize()
-    press.use_torch_stream()
-    torch.cuda.empty_cache()
+    yield from P.lib()
 
 
-def _t(a, dtype=None):
-    import torch
-    a = np.ascontiguousarray(a)
-    if dtype is not None:
-        a = a.view(dtype)
-    return torch.from_numpy(a.copy()).cuda()
-
-
-def slot_for(n):
-    return 8 * n + 4096 if n else 32
-
-
-class PressRun:
-    """A batch in a scattered layout, the slots back to back from an odd offset; canaries in front of and behind out_len,
-    need and maxlen, and every byte of the arena outside the streams and the slots of failed reads must keep its fill"""
+class PressRun(P.PressRun):
+    """tests/_prefix_runs.py, with the per-read Huffman wrappers; the per-read table is maxlen"""
 
     def __init__(self, reads, caps=None, seed=1):
-        import torch
-        rng = np.random.default_rng(seed)
-        self.reads, self.nr = reads, len(reads)
-        sig, off = L.scatter_reads(rng, reads)
-        caps = [slot_for(len(r)) for r in reads] if caps is None else caps
-        self.out_off = L.slots(rng, np.asarray(caps, dtype=np.uint64))
-        self.sig, self.off = _t(sig), _t(off.astype(np.uint64), np.int64)
-        self.n = _t(np.array([len(r) for r in reads], dtype=np.uint32), np.int32)
-        self.d_out_off = _t(self.out_off, np.int64)
-        self.out = torch.full((int(self.out_off[-1]) + 64,), FILL8, dtype=torch.uint8, device="cuda")
-        self.out_len = torch.full((self.nr + 2 * GUARD,), CANARY, dtype=torch.int64, device="cuda")
-        self.ml = torch.full((self.nr + 2 * GUARD,), FILL8, dtype=torch.uint8, device="cuda")
-
-    def _tables(self, want_ml):
-        import torch
-        torch.cuda.synchronize()
-        ol = self.out_len.cpu().numpy().view(np.uint64)
-        ml = self.ml.cpu().numpy()
-        assert (ol[:GUARD] == CANARY).all() and (ol[GUARD + self.nr:] == CANARY).all(), "out_len / need"
-        assert (ml[:GUARD] == FILL8).all() and (ml[GUARD + (self.nr if want_ml else 0):] == FILL8).all(), "maxlen"
-        self.out_len.fill_(CANARY)
-        self.ml.fill_(FILL8)
-        return ol[GUARD:GUARD + self.nr].copy(), ml[GUARD:GUARD + self.nr].copy()
+        super().__init__(FAMILY, reads, caps=caps, seed=seed)
 
     def run(self, layout, want_ml=True):
-        """-> (streams (None: failed), maxlen uint8 [nr])"""
-        press.huffman_press_batch(layout, self.sig, self.off, self.n, self.out, self.d_out_off, self.out_len[GUARD:GUARD + self.nr],
-                                  self.ml[GUARD:GUARD + self.nr] if want_ml else None)
-        ol, ml = self._tables(want_ml)
-        out = self.out.cpu().numpy()
-        written = np.zeros(len(out), dtype=bool)
-        streams = []
-        for r in range(self.nr):
-            o, cap = int(self.out_off[r]), int(self.out_off[r + 1] - self.out_off[r])
-            if ol[r] == FAILED64:
-                streams.append(None)
-                written[o:o + cap] = True  # (a read that fails may leave its own slot in any state, as the generic calls do)
-            else:
-                assert ol[r] <= cap
-                written[o:o + int(ol[r])] = True
-                streams.append(out[o:o + int(ol[r])].tobytes())
-        assert (out[~written] == FILL8).all(), "a byte outside the streams was written"
-        self.out.fill_(FILL8)
-        return streams, ml
+        return super().run(layout, want_ml)
 
     def sizes(self, layout, want_ml=True):
-        """-> (need uint64 [nr], maxlen); the arena keeps its fill"""
-        press.huffman_press_sizes(layout, self.sig, self.off, self.n, self.out_len[GUARD:GUARD + self.nr],
-                                  self.ml[GUARD:GUARD + self.nr] if want_ml else None)
-        need, ml = self._tables(want_ml)
-        assert bool((self.out == FILL8).all())
-        return need, ml
+        return super().sizes(layout, want_ml)
 
 
-class DepressRun:
+class DepressRun(P.DepressRun):
     def __init__(self, streams, ns, seed=2):
-        import torch
-        rng = np.random.default_rng(seed)
-        self.ns = [int(n) for n in ns]
-        self.nr = len(streams)
-        arena, in_off, in_len = L.scatter_streams(rng, streams)
-        self.off, self.total = L.scatter_rooms(rng, self.ns, min_gap=8)
-        self.arena, self.in_off, self.in_len = _t(arena), _t(in_off, np.int64), _t(in_len, np.int64)
-        self.d_off, self.n = _t(self.off, np.int64), _t(np.array(self.ns, dtype=np.uint32), np.int32)
-        self.sig = torch.full((self.total,), FILL16, dtype=torch.int16, device="cuda")
-        self.out_n = torch.full((self.nr + 2 * GUARD,), CANARY, dtype=torch.int32, device="cuda")
-
-    def run(self, layout):
-        """-> samples per read (None: refused); nothing outside the rooms of the decoded reads is written"""
-        import torch
-        press.huffman_depress_batch(layout, self.arena, self.in_off, self.in_len, self.sig, self.d_off, self.n,
-                                    self.out_n[GUARD:GUARD + self.nr])
-        torch.cuda.synchronize()
-        sig = self.sig.cpu().numpy()
-        on = self.out_n.cpu().numpy().view(np.uint32)
-        assert (on[:GUARD] == CANARY).all() and (on[GUARD + self.nr:] == CANARY).all(), "out_n"
-        on = on[GUARD:GUARD + self.nr]
-        got, spans = [], []
-        for r in range(self.nr):
-            o = int(self.off[r])
-            if on[r] == FAILED32:
-                got.append(None)
-                spans.append(0)
-            else:
-                assert on[r] == self.ns[r]
-                got.append(sig[o:o + self.ns[r]].copy())
-                spans.append(self.ns[r])
-        assert (sig[L.outside_rooms(self.total, self.off, spans)] == FILL16).all(), "a sample outside the decoded reads was written"
-        self.sig.fill_(FILL16)
-        self.out_n.fill_(CANARY)
-        return got
+        super().__init__(FAMILY, streams, ns, seed=seed)
 
 
 def check_batch(layout, reads, seed, caps=None):
@@ -596,3 +497,52 @@ def test_forms(lib):
         press.scratch_fill(fill)
         for r, g in enumerate(d.run("vbbe21")):
             assert np.array_equal(g, reads[r]), (fill, r)
+
+
+@gpu
+def test_families_alternate(lib):
+    """9: the Rice family and this one share the engine's scratch and its counters.  Depress Rice, Huffman, Rice, Huffman
+    in one process: every result is the yardstick's, and the repair counters read behind each call are those of that
+    call (the last depress of either family), as a first pair of runs gave them.  Then press the same reads Rice,
+    Huffman, Rice: streams and k / maxlen are the yardsticks' each time"""
+    import _rice as R
+    layout = "vbe21"
+    # the Rice streams `never`, `full` and `long_run` of test_rice_family.test_forged_payloads
+    s0, s1, s2 = _rcf.from_low(bytes(4097)), _rcf.from_low(bytes(300)), _rcf.signal(71, 5000, exr=0.01)
+    rice_reads = [s0, s2, s1]
+    rice_exp = [R.expected(layout, s) for s in rice_reads]
+    heads = [R.head_len(layout, s) for s in rice_reads]
+    rice_streams = [rice_exp[0][0][:heads[0]] + bytes([0x02]) + bytes(1600),                       # k = 2, every code 3 bits
+                    rice_exp[1][0],
+                    rice_exp[2][0][:heads[2]] + bytes([0x07]) + b"\xff" * 999 + bytes(8)]          # k = 0, a run of 7997 ones
+    rice_ns = [len(s) for s in rice_reads]
+    assert rice_ns == [4098, 5000, 301]
+    rice_want = [R.decoded(layout, st, h, n) for st, h, n in zip(rice_streams, heads, rice_ns)]
+    huff_reads = [reads_by_name()["never-sync"], min((s for _, s in _rcf.real_reads()), key=len)]
+    huff_streams = [expected(layout, s)[0] for s in huff_reads]
+
+    rice = P.DepressRun(RICE, rice_streams, rice_ns, seed=101)
+    huff = DepressRun(huff_streams, [len(s) for s in huff_reads], seed=102)
+
+    def rice_step():
+        for r, g in enumerate(rice.run(layout)):
+            assert g is not None and np.array_equal(g, rice_want[r]), r
+        return press.rice_repairs()
+
+    def huff_step():
+        for r, g in enumerate(huff.run(layout)):
+            assert g is not None and np.array_equal(g, huff_reads[r]), r
+        return press.huffman_repairs()
+
+    first = (rice_step(), huff_step())
+    assert first[0][2] > 0 and first[1][2] > 0  # both walks had work
+    for step, want in ((rice_step, first[0]), (huff_step, first[1]), (rice_step, first[0]), (huff_step, first[1])):
+        assert step() == want
+    assert press.rice_repairs() == press.huffman_repairs() == first[1]  # one set of counters: the last call's
+
+    reads = rice_reads + huff_reads
+    for fam, run in ((RICE, P.PressRun(RICE, reads, seed=103)), (FAMILY, PressRun(reads, seed=104)), (RICE, P.PressRun(RICE, reads, seed=105))):
+        streams, tab = run.run(layout)
+        for r, s in enumerate(reads):
+            want = R.expected(layout, s)[:2] if fam is RICE else expected(layout, s)
+            assert (streams[r], int(tab[r])) == (want[0], want[1]), (fam.table, r)
