@@ -323,7 +323,7 @@ static uint32_t cdf_blocks(uint32_t nreads)
 	return b < CDF_MAX_BLOCKS ? b : CDF_MAX_BLOCKS;
 }
 
-void launch_cdf_encode(const BatchArgs &a, hipStream_t s)
+void launch_cdf_encode(const BatchArgs &a, uint64_t *, hipStream_t s)
 {
 	(void) hipMemsetAsync(&a.ctl->ticket2, 0, 4, s);
 	hipLaunchKernelGGL(k_cdf_encode, dim3(cdf_blocks(a.nreads)), dim3(64), 0, s, a);

@@ -185,33 +185,34 @@ struct Method {
 	int id;
 	Family family;
 	bool key2, zd, slow5; // FAM_SVB: 2-bit keys (svb32), zig-zag delta, BLOW5's framing
-	int exfmt, ent;       // FAM_EX: ExFmt; entropy stage 0 plain, 1 static Huffman, 2 / 3 / 4 / 5 range coder, 6 Golomb-Rice, 7 a Huffman code per read
+	ExFmt exfmt;          // FAM_EX: the section's layout ...
+	ExEnt ent;            // ... and the entropy stage, a row of EX_STAGES
 	int inner;            // FAM_ZSTD: the method whose streams the frames hold ...
 	uint32_t kdiv;        // ... and its samples per key byte (ZsBufs::kdiv)
 };
-#define M_SVB(id, key2, zd, slow5) { id, FAM_SVB, key2, zd, slow5, 0, 0, 0, 0 }
+#define M_SVB(id, key2, zd, slow5) { id, FAM_SVB, key2, zd, slow5, EXF_VBE21, ENT_PLAIN, 0, 0 }
 #define M_EX(id, fmt, ent) { id, FAM_EX, false, false, false, fmt, ent, 0, 0 }
-#define M_ZSTD(id, inner, kdiv) { id, FAM_ZSTD, false, false, false, 0, 0, inner, kdiv }
+#define M_ZSTD(id, inner, kdiv) { id, FAM_ZSTD, false, false, false, EXF_VBE21, ENT_PLAIN, inner, kdiv }
 constexpr Method METHODS[] = {
 	M_SVB(PRESS_HIP_SVB12, false, false, false),
 	M_SVB(PRESS_HIP_SVB12_ZD, false, true, false),
 	M_SVB(PRESS_HIP_SVB_ZD, true, true, false),
 	M_ZSTD(PRESS_HIP_ZSTD_SVB_ZD, PRESS_HIP_SVB_ZD, 4),
 	M_ZSTD(PRESS_HIP_ZSTD_SVB12_ZD, PRESS_HIP_SVB12_ZD, 8),
-	M_EX(PRESS_HIP_VBE21_ZD, EXF_VBE21, 0),
-	M_EX(PRESS_HIP_VBBE21_ZD, EXF_VBBE21, 0),
-	M_EX(PRESS_HIP_VBSBE21_ZD, EXF_VBSBE21, 0),
-	M_EX(PRESS_HIP_VBSSE21_ZD, EXF_VBSSE21, 0),
-	M_EX(PRESS_HIP_SHUFF_VBE21_ZD, EXF_VBE21, 1),
-	M_EX(PRESS_HIP_SHUFF_VBBE21_ZD, EXF_VBBE21, 1),
-	M_EX(PRESS_HIP_SHUFF_VBSBE21_ZD, EXF_VBSBE21, 1),
-	M_EX(PRESS_HIP_SHUFF_VBSSE21_ZD, EXF_VBSSE21, 1),
-	M_EX(PRESS_HIP_HASGAM_ZDQ, EXF_EXZD, 0),
+	M_EX(PRESS_HIP_VBE21_ZD, EXF_VBE21, ENT_PLAIN),
+	M_EX(PRESS_HIP_VBBE21_ZD, EXF_VBBE21, ENT_PLAIN),
+	M_EX(PRESS_HIP_VBSBE21_ZD, EXF_VBSBE21, ENT_PLAIN),
+	M_EX(PRESS_HIP_VBSSE21_ZD, EXF_VBSSE21, ENT_PLAIN),
+	M_EX(PRESS_HIP_SHUFF_VBE21_ZD, EXF_VBE21, ENT_SHUFF),
+	M_EX(PRESS_HIP_SHUFF_VBBE21_ZD, EXF_VBBE21, ENT_SHUFF),
+	M_EX(PRESS_HIP_SHUFF_VBSBE21_ZD, EXF_VBSBE21, ENT_SHUFF),
+	M_EX(PRESS_HIP_SHUFF_VBSSE21_ZD, EXF_VBSSE21, ENT_SHUFF),
+	M_EX(PRESS_HIP_HASGAM_ZDQ, EXF_EXZD, ENT_PLAIN),
 	M_ZSTD(PRESS_HIP_ZSTD_HASGAM_ZDQ, PRESS_HIP_HASGAM_ZDQ, 0),
 	M_SVB(PRESS_HIP_SLOW5_SVB_ZD, true, true, true),
-	M_EX(PRESS_HIP_RC_VBE21_ZD, EXF_VBE21, 2),
-	M_EX(PRESS_HIP_RCC_VBE21_ZD, EXF_VBE21, 3),
-	M_EX(PRESS_HIP_RCCM_VBBE21_ZD, EXF_VBBE21, 4),
+	M_EX(PRESS_HIP_RC_VBE21_ZD, EXF_VBE21, ENT_RC),
+	M_EX(PRESS_HIP_RCC_VBE21_ZD, EXF_VBE21, ENT_RCC),
+	M_EX(PRESS_HIP_RCCM_VBBE21_ZD, EXF_VBBE21, ENT_RCM),
 };
 constexpr bool methods_in_order()
 {
@@ -223,8 +224,11 @@ constexpr bool methods_in_order()
 static_assert(sizeof METHODS / sizeof METHODS[0] == PRESS_HIP_NMETHODS, "one row per method id");
 static_assert(methods_in_order(), "METHODS[i].id == i, and a zstd composition wraps a plain method");
 inline bool method_ok(int m) { return m >= 0 && m < PRESS_HIP_NMETHODS; }
-inline bool is_shuff(const Method &m) { return m.family == FAM_EX && m.ent == 1; }
-inline bool is_rc(const Method &m) { return m.family == FAM_EX && m.ent >= 2; }
+inline bool is_shuff(const Method &m) { return m.family == FAM_EX && m.ent == ENT_SHUFF; }
+// questions to the method's row of EX_STAGES: a stage codes the one-byte values out of a temporary (Ctx::low); the size the
+// packed press announces is a bound, not the stream's length
+inline bool uses_low_tmp(const Method &m) { return m.family == FAM_EX && EX_STAGES[m.ent].low_tmp; }
+inline bool packed_is_bound(const Method &m) { return m.family == FAM_EX && EX_STAGES[m.ent].pay == PAY_CODER; }
 
 // ---- the range-coder family (press_hip_rcf_*): every coder on every layout.  Rows of its own behind the public ids,
 // where method_ok does not reach them; the three pairs that are public methods go through the public rows.
@@ -233,7 +237,7 @@ constexpr int RCF_PRIVATE = PRESS_HIP_NMETHODS; // private id = RCF_PRIVATE + 4 
 	M_EX(RCF_PRIVATE + 4 * coder + 0, EXF_VBE21, ent), M_EX(RCF_PRIVATE + 4 * coder + 1, EXF_VBBE21, ent), \
 		M_EX(RCF_PRIVATE + 4 * coder + 2, EXF_VBSBE21, ent), M_EX(RCF_PRIVATE + 4 * coder + 3, EXF_VBSSE21, ent)
 constexpr Method RCF_METHODS[PRESS_HIP_NRCF_CODERS * PRESS_HIP_NRCF_LAYOUTS] = {
-	M_RCF(PRESS_HIP_RCF_RC, 2), M_RCF(PRESS_HIP_RCF_RCC, 3), M_RCF(PRESS_HIP_RCF_RCCM, 4), M_RCF(PRESS_HIP_RCF_RCCDF, 5),
+	M_RCF(PRESS_HIP_RCF_RC, ENT_RC), M_RCF(PRESS_HIP_RCF_RCC, ENT_RCC), M_RCF(PRESS_HIP_RCF_RCCM, ENT_RCM), M_RCF(PRESS_HIP_RCF_RCCDF, ENT_CDF),
 };
 static_assert((int) EXF_VBE21 == (int) PRESS_HIP_RCF_VBE21 && (int) EXF_VBBE21 == (int) PRESS_HIP_RCF_VBBE21 &&
 		      (int) EXF_VBSBE21 == (int) PRESS_HIP_RCF_VBSBE21 && (int) EXF_VBSSE21 == (int) PRESS_HIP_RCF_VBSSE21,
@@ -254,19 +258,19 @@ inline const Method &rcf_method(int coder, int layout)
 // ---- the Rice family (press_hip_rice_*): Golomb-Rice coding of the one-byte values on every layout; rows of its own again
 constexpr int RICE_PRIVATE = RCF_PRIVATE + PRESS_HIP_NRCF_CODERS * PRESS_HIP_NRCF_LAYOUTS; // private id = RICE_PRIVATE + layout
 constexpr Method RICE_METHODS[PRESS_HIP_NRCF_LAYOUTS] = {
-	M_EX(RICE_PRIVATE + 0, EXF_VBE21, 6), M_EX(RICE_PRIVATE + 1, EXF_VBBE21, 6), M_EX(RICE_PRIVATE + 2, EXF_VBSBE21, 6),
-	M_EX(RICE_PRIVATE + 3, EXF_VBSSE21, 6),
+	M_EX(RICE_PRIVATE + 0, EXF_VBE21, ENT_RICE), M_EX(RICE_PRIVATE + 1, EXF_VBBE21, ENT_RICE), M_EX(RICE_PRIVATE + 2, EXF_VBSBE21, ENT_RICE),
+	M_EX(RICE_PRIVATE + 3, EXF_VBSSE21, ENT_RICE),
 };
-inline bool is_rice(const Method &m) { return m.family == FAM_EX && m.ent == 6; }
+inline bool is_rice(const Method &m) { return m.family == FAM_EX && m.ent == ENT_RICE; }
 inline bool rice_ok(int layout) { return layout >= 0 && layout < PRESS_HIP_NRCF_LAYOUTS; }
 
 // ---- the per-read Huffman family (press_hip_huffman_*): a Huffman code from each read's own one-byte values, on every layout
 constexpr int DHUF_PRIVATE = RICE_PRIVATE + PRESS_HIP_NRCF_LAYOUTS; // private id = DHUF_PRIVATE + layout
 constexpr Method DHUF_METHODS[PRESS_HIP_NRCF_LAYOUTS] = {
-	M_EX(DHUF_PRIVATE + 0, EXF_VBE21, 7), M_EX(DHUF_PRIVATE + 1, EXF_VBBE21, 7), M_EX(DHUF_PRIVATE + 2, EXF_VBSBE21, 7),
-	M_EX(DHUF_PRIVATE + 3, EXF_VBSSE21, 7),
+	M_EX(DHUF_PRIVATE + 0, EXF_VBE21, ENT_DHUF), M_EX(DHUF_PRIVATE + 1, EXF_VBBE21, ENT_DHUF), M_EX(DHUF_PRIVATE + 2, EXF_VBSBE21, ENT_DHUF),
+	M_EX(DHUF_PRIVATE + 3, EXF_VBSSE21, ENT_DHUF),
 };
-inline bool is_dhuf(const Method &m) { return m.family == FAM_EX && m.ent == 7; }
+inline bool is_dhuf(const Method &m) { return m.family == FAM_EX && m.ent == ENT_DHUF; }
 
 // ---- bounds: the reference's formulas ----
 inline uint32_t svb16_keylen(uint32_t n) { return (n >> 3) + (((n & 7) + 7) >> 3); }

@@ -54,6 +54,7 @@
 
 #include "press_internal.h"
 #include "press_packed.h"
+#include "press_wave.h"
 #include <cstddef>
 #include <type_traits>
 
@@ -92,18 +93,6 @@ constexpr int HT = HUF_HT;
 
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t) __builtin_amdgcn_readfirstlane((int) v); }
 __device__ __forceinline__ bool any64(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0; }
-
-// inclusive scan over the 64 lanes of a wave (DPP row shifts + row broadcasts)
-__device__ __forceinline__ uint32_t wave_scan(uint32_t v)
-{
-	v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x111, 0xf, 0xf, true); // row_shr:1
-	v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x112, 0xf, 0xf, true); // row_shr:2
-	v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x114, 0xf, 0xf, true); // row_shr:4
-	v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x118, 0xf, 0xf, true); // row_shr:8
-	v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x142, 0xa, 0xf, false); // row_bcast:15 -> rows 1,3
-	v += (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x143, 0xc, 0xf, false); // row_bcast:31 -> rows 2,3
-	return v;
-}
 
 // A code beyond the second-level tables (prefixes past the first HUF_L2_IDS, tables that do not
 // fit): the trie in global memory.  wnd = 32 stream bits.  -> a one-code lut32 entry, or 0 if the
@@ -403,15 +392,6 @@ __device__ __forceinline__ uint32_t len_scan(const uint32_t *col_, const LenTabs
 	return bad ? HEND : (p >= nb && p < lim ? HEND : p);
 }
 
-// make the LDS writes of this wave visible to its other lanes (DS ops of a wave execute in
-// order; this only stops the compiler from moving them)
-__device__ __forceinline__ void wave_lds_sync()
-{
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // ------------------------------------------------------------------ one tile
 
 // ------------------------------------------------------------------ first pass
@@ -609,7 +589,7 @@ __global__ __launch_bounds__(WGS, 2 * HUF_SYNC_PER_CU * 2) void k_huf_sync(Decod
 		const uint32_t eB = len_scan<TRIE, S>(col, &lds.tabs, a.huff, fB, OWN, nbB, cB, dB);
 		HSTAMP(4); // own pass B
 		const uint32_t eA8 = eA == HEND ? R_END : eA - OWN, eB8 = eB == HEND ? R_END : eB - OWN;
-		const uint32_t cw = wave_scan(cA + cB), dw = wave_scan(dA + dB);
+		const uint32_t cw = wave_incl_scan_dpp(cA + cB), dw = wave_incl_scan_dpp(dA + dB);
 		// ---- whose start is not where the subsequence in front ended
 		const uint32_t fA8 = fA == HEND ? R_END : fA, fB8 = fB == HEND ? R_END : fB;
 		const uint32_t pe8 = (uint32_t) __shfl_up((int) eB8, 1, 64);
@@ -651,7 +631,7 @@ __global__ __launch_bounds__(LIST_WG) void k_huf_list(DecodeArgs a)
 	const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 	unsigned long long bm = u < n ? a.hbits[u] : 0ull;
 	const uint32_t cnt = (uint32_t) __popcll(bm);
-	const uint32_t inc = wave_scan(cnt);
+	const uint32_t inc = wave_incl_scan_dpp(cnt);
 	if (lane == 63)
 		s_w[w] = inc;
 	__syncthreads();
@@ -871,7 +851,7 @@ __global__ __launch_bounds__(HT) void k_huf_chain(DecodeArgs a)
 		const uint32_t e = b + tid;
 		const uint32_t z = e < nex ? (val[e] & 0xFFFFu) : 0u;
 		const uint32_t dl = e < nex ? unzz16(z) : 0u;
-		const uint32_t inc = wave_scan(dl);
+		const uint32_t inc = wave_incl_scan_dpp(dl);
 		if ((tid & 63) == 63)
 			s_w[tid >> 6] = inc;
 		__syncthreads();
@@ -950,8 +930,8 @@ __global__ __launch_bounds__(HT) void k_huf_chain(DecodeArgs a)
 			c = w.x;
 			dt = w.y & 0xFFFFu;
 		}
-		const uint32_t inc = wave_scan(c);
-		const uint32_t dinc = wave_scan(dt);
+		const uint32_t inc = wave_incl_scan_dpp(c);
+		const uint32_t dinc = wave_incl_scan_dpp(dt);
 		if ((tid & 63) == 63) {
 			s_w[tid >> 6] = inc;
 			s_wd[tid >> 6] = dinc;
@@ -1501,7 +1481,7 @@ __global__ __launch_bounds__(WGE) void k_huf_emit(DecodeArgs a)
 		const uint32_t obase = U.obase;
 		const uint64_t roff = U.roff;
 		const uint32_t cnt = (rec >> 8) & 0xFFu;
-		const uint32_t inc = wave_scan(cnt);
+		const uint32_t inc = wave_incl_scan_dpp(cnt);
 		const bool fused = U.fused != 0;
 		const uint32_t ex = inc - cnt; // codes of the wave in front of this lane
 		const uint32_t f = rec & 0xFFu;
@@ -1718,10 +1698,10 @@ static void run_huff_decode_t(const DecodeArgs &a, bool trie, hipStream_t s)
 
 // Huffman stage of the exception-split decoders: payload of every read -> a.low.  minlen: the table's shortest code
 // (selects the subsequence size) | HUF_NEEDS_TRIE if some code is beyond the second-level tables
-void launch_huff_decode(const DecodeArgs &a0, uint32_t minlen, hipStream_t s)
+void launch_huff_decode(const DecodeArgs &a0, hipStream_t s)
 {
-	const bool trie = (minlen & HUF_NEEDS_TRIE) != 0;
-	minlen &= ~HUF_NEEDS_TRIE;
+	const bool trie = (a0.huf_minlen & HUF_NEEDS_TRIE) != 0;
+	const uint32_t minlen = a0.huf_minlen & ~HUF_NEEDS_TRIE;
 	DecodeArgs a = a0;
 	a.ctl = a0.ctl + 1; // the decoder's own control block (cleared by k_ex_parse, the first kernel of the call)
 	hipLaunchKernelGGL(k_huff_tiles, dim3((a.nreads + TILES_RPW - 1) / TILES_RPW), dim3(64), 0, s, a);

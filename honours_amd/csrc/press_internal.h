@@ -15,6 +15,26 @@ enum ExFmt : int {
 	EXF_VBSSE21 = 3, // svb32 position deltas, svb16 (value-256)
 	EXF_EXZD = 4     // svb32 position deltas, svb32 (value-256); one exception = 2 x u32
 };
+// The entropy stage of an exception-split method: what codes the one-byte values behind the section.  The numbers stand in
+// the rows of METHODS[] (press_host.h) and index EX_STAGES[] below.
+enum ExEnt : int {
+	ENT_PLAIN, // none: the values themselves
+	ENT_SHUFF, // the static Huffman table (press_huffman.hip)
+	ENT_RC,    // range coder of order 0 (press_rc.hip)
+	ENT_RCC,   // ... of order 1
+	ENT_RCM,   // ... mixing orders 1 and 0
+	ENT_CDF,   // the adaptive nibble-CDF coder (press_cdf.hip)
+	ENT_RICE,  // Golomb-Rice (press_rice.hip)
+	ENT_DHUF,  // a Huffman code per read (press_dhuf.hip)
+	ENT_COUNT
+};
+// ... and what k_ex_section, k_ex_sizes and k_ex_parse have to know about that stream
+enum ExPayload : int {
+	PAY_INLINE, // the one-byte values, behind the section
+	PAY_SHUFF,  // u32 symbol count (big endian) + the static-Huffman payload
+	PAY_CODER,  // a coder that sizes its own stream and stores no count: the slot's size is a bound, nlow the room's rest
+	PAY_STAGED  // staged and sized by the stage (k_rice_pick, k_dh_tree), spliced behind the section; no count either
+};
 
 // Per-read record shared by the passes of the exception-split methods (device memory).
 struct ReadMeta {
@@ -374,9 +394,7 @@ void launch_pack_patch(const BatchArgs &a, const uint64_t *slot, hipStream_t s);
 // packed recode: need[] = FAILED for the reads the source refused (out_n), then - with pk.layout - the scan, and a slot
 // table in which such a read has no byte whatever lies behind it
 void launch_pack_scan_refused(const PackArgs &pk, const uint32_t *out_n, uint32_t nreads, hipStream_t s);
-void launch_ex_sizes(const BatchArgs &a, int fmt, int ent, uint64_t *need, hipStream_t s); // press_sections.hip
 void launch_svb_encode_packed(const BatchArgs &a, bool key2bit, bool zd, bool slow5, const PackArgs &pk, int phases, hipStream_t s);
-void launch_ex_encode_packed(const BatchArgs &a, int fmt, int ent, const PackArgs &pk, int phases, hipStream_t s);
 void launch_zstd_encode_packed(const BatchArgs &a, const ZsBufs &z, const PackArgs &pk, int phases, hipStream_t s);
 // decode in two steps: frames -> svb-zd streams in ztmp (reads the device leaves to libzstd
 // are counted in dctl->nhost and patched in by the caller), then the svb-zd decode
@@ -399,10 +417,10 @@ struct FuseArgs {
 };
 constexpr uint32_t RECODE_KEEP = 64; // bytes of a refused read's slot kept aside (an empty read's stream is 4 / 16 bytes)
 // bits > 0: the decode kernel applies D_bits to the samples it holds, and pass A's results are those of the degraded read
-void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent, hipStream_t s,
+void launch_recode_fused(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, ExFmt fmt, ExEnt ent, hipStream_t s,
 			 uint32_t bits = 0);
 // the packed form (press_hip_recode_sizes / press_hip_recode_packed): phases as launch_ex_encode_packed, p.out_off == pk.slot
-void launch_recode_fused_packed(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, int fmt, int ent,
+void launch_recode_fused_packed(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, ExFmt fmt, ExEnt ent,
 				 const PackArgs &pk, int phases, hipStream_t s, uint32_t bits = 0);
 void launch_recode_counts(const uint32_t *out_n, uint32_t *n, uint32_t nreads, hipStream_t s);
 void launch_recode_refused(const uint32_t *out_n, const BatchArgs &p, uint8_t *keep, bool save, hipStream_t s);
@@ -543,30 +561,69 @@ void launch_stall_parse(const uint8_t *in, const uint64_t *in_off, const uint64_
 			const StallBufs &b, hipStream_t s);
 void launch_stall_scatter(int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint32_t *out_n,
 			  hipStream_t s);
-void launch_ex_encode_chunked(const BatchArgs &a, int fmt, int ent, hipStream_t s); // ent: 0 plain, 1 Huffman, 2 / 3 / 4 range coder of order 0 / 1 / 1-0 mixing, 5 nibble-CDF coder, 6 Golomb-Rice, 7 a Huffman code per read
-void launch_ex_decode_chunked(const DecodeArgs &a, int fmt, int ent, hipStream_t s);
-void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s); // press_sections.hip
-void launch_huff_decode(const DecodeArgs &a, uint32_t minlen, hipStream_t s);      // press_huffman.hip
-void launch_ex_section(const BatchArgs &a, int fmt, int ent, hipStream_t s);        // press_sections.hip
-void launch_rcs_encode(const BatchArgs &a, hipStream_t s);  // press_rc.hip
+// ---- the exception-split pipeline (press_exsplit.hip, press_sections.hip) and its stages
+// A stage's press: the read's one-byte values -> its stream behind the section.  need != NULL (the stages with
+// sizes_only, press_hip_{rice, huffman}_press_sizes): the stage's sizing kernels alone, need[r] += the bytes of its
+// stream; every other stage is given NULL.  Its depress: the stream -> a.low.
+typedef void (*ExPressFn)(const BatchArgs &a, uint64_t *need, hipStream_t s);
+typedef void (*ExDepressFn)(const DecodeArgs &a, hipStream_t s);
+void launch_low_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);   // press_exsplit.hip: pass B, k_low_encode_chunked
+void launch_shuff_encode(const BatchArgs &a, uint64_t *need, hipStream_t s); // ... k_huff_encode_chunked
+void launch_huff_decode(const DecodeArgs &a, hipStream_t s);                 // press_huffman.hip (the subsequence size: a.huf_minlen)
+void launch_rcs_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);   // press_rc.hip
 void launch_rcs_decode(const DecodeArgs &a, hipStream_t s);
-void launch_rcc_encode(const BatchArgs &a, hipStream_t s);  // order 1 (rcc_vbe21_zd)
+void launch_rcc_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);
 void launch_rcc_decode(const DecodeArgs &a, hipStream_t s);
-void launch_rcm_encode(const BatchArgs &a, hipStream_t s);  // order 1-0 context mixing (rccm_vbbe21_zd)
+void launch_rcm_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);
 void launch_rcm_decode(const DecodeArgs &a, hipStream_t s);
-void launch_cdf_encode(const BatchArgs &a, hipStream_t s);  // ent 5: the adaptive nibble-CDF coder (rccdf_*_zd), press_cdf.hip
+void launch_cdf_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);   // press_cdf.hip
 void launch_cdf_decode(const DecodeArgs &a, hipStream_t s);
-// ent 6: Golomb-Rice (rice_*_zd), press_rice.hip.  need != NULL: k_rice_count and k_rice_pick alone, need[r] += the payload's bytes
-void launch_rice_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);
+void launch_rice_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);  // press_rice.hip; sizes: k_rice_count and k_rice_pick
 void launch_rice_decode(const DecodeArgs &a, hipStream_t s);
-// ent 7: a Huffman code per read (huffman_*_zd), press_dhuf.hip.  need != NULL: k_dh_hist and k_dh_tree alone, need[r] += the
-// bytes of table and payload
-void launch_dhuf_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);
+void launch_dhuf_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);  // press_dhuf.hip; sizes: k_dh_hist and k_dh_tree
 void launch_dhuf_decode(const DecodeArgs &a, hipStream_t s);
-// press_hip_{rice, huffman}_press_sizes: the press chain of ent 6 or 7 as far as the sizes; a.out_off: nreads + 1 zeros,
-// a.out_len == need
-void launch_ex_prefix_sizes(const BatchArgs &a, int fmt, int ent, uint64_t *need, hipStream_t s); // press_chunked.hip
-// behind the encode of a range-coder method (ent >= 2): raw[r] = 1 where the coder gave up and stored the one-byte values
+struct ExStage {
+	ExEnt id;
+	ExPayload pay;
+	ExPressFn press;
+	ExDepressFn depress; // NULL: the merge reads the values where they lie
+	bool low_tmp;        // press: k_low_encode_chunked leaves the one-byte values in a.low_tmp for the stage (else it IS the stage, or
+	                     // the stage reads the samples); the scratch plan gives such a method Ctx::low
+	bool sizes_only;     // press(need != NULL) exists
+};
+constexpr ExStage EX_STAGES[ENT_COUNT] = {
+	{ ENT_PLAIN, PAY_INLINE, launch_low_encode, nullptr, false, false },
+	{ ENT_SHUFF, PAY_SHUFF, launch_shuff_encode, launch_huff_decode, false, false },
+	{ ENT_RC, PAY_CODER, launch_rcs_encode, launch_rcs_decode, true, false },
+	{ ENT_RCC, PAY_CODER, launch_rcc_encode, launch_rcc_decode, true, false },
+	{ ENT_RCM, PAY_CODER, launch_rcm_encode, launch_rcm_decode, true, false },
+	{ ENT_CDF, PAY_CODER, launch_cdf_encode, launch_cdf_decode, true, false },
+	{ ENT_RICE, PAY_STAGED, launch_rice_encode, launch_rice_decode, true, true },
+	{ ENT_DHUF, PAY_STAGED, launch_dhuf_encode, launch_dhuf_decode, true, true },
+};
+constexpr bool ex_stages_in_order()
+{
+	for (int i = 0; i < ENT_COUNT; i++)
+		if (EX_STAGES[i].id != i)
+			return false;
+	return true;
+}
+static_assert(ex_stages_in_order(), "EX_STAGES[i].id == i");
+
+// the chain of a press: chunk table and ReadMeta; pass A; the exceptions counted and listed; the section and the stage
+void ex_encode_prep(const BatchArgs &a, hipStream_t s);
+void ex_encode_lists(const BatchArgs &a, ExFmt fmt, hipStream_t s);
+void ex_encode_streams(const BatchArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s);
+void launch_ex_encode_chunked(const BatchArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s);
+void launch_ex_encode_packed(const BatchArgs &a, ExFmt fmt, ExEnt ent, const PackArgs &pk, int phases, hipStream_t s);
+// press_hip_{rice, huffman}_press_sizes: the press chain of a stage with sizes_only as far as the sizes; a.out_off:
+// nreads + 1 zeros, a.out_len == need
+void launch_ex_prefix_sizes(const BatchArgs &a, ExFmt fmt, ExEnt ent, uint64_t *need, hipStream_t s);
+void launch_ex_decode_chunked(const DecodeArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s);
+void launch_ex_section(const BatchArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s);               // press_sections.hip
+void launch_ex_sizes(const BatchArgs &a, ExFmt fmt, ExEnt ent, uint64_t *need, hipStream_t s);
+void launch_ex_parse_huff(const DecodeArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s);           // ... k_ex_parse, then the stage's depress
+// behind the encode of a range-coder method (PAY_CODER): raw[r] = 1 where the coder gave up and stored the one-byte values
 void launch_rcf_raw(const BatchArgs &a, uint8_t *raw, hipStream_t s);
 // symbol counts of a batch for fitting a Huffman table (press_train.hip): adds into counts[257]; chunks takes
 // train_scratch_bytes(max_chunks), nchunks is one device word (zeroed here)

@@ -136,7 +136,7 @@ ScratchPlan make_plan(const Method &method, uint64_t total_samples, uint32_t nre
 	p.need(&Ctx::ex_pos, (total_samples + 64) * 4).need(&Ctx::ex_val, (total_samples + 64) * 4);
 	if (!decode && is_shuff(k))
 		p.need(&Ctx::cbits, mc * sizeof(ChunkBits));
-	if (is_rc(k))
+	if (uses_low_tmp(k))
 		p.need(&Ctx::low, total_samples + 64); // the one-byte values between the two stages
 	if ((is_rice(k) || is_dhuf(k)) && !decode) {
 		// press_prefix.h: 32 units per chunk; a staged payload never takes more than nine bits a value, the reads' stagings
@@ -715,7 +715,7 @@ extern "C" int press_hip_pa_cal(const double *dor, uint32_t nreads, float *cal)
 	return 0;
 }
 
-extern "C" int press_hip_packed_exact(int method) { return method_ok(method) && !is_rc(METHODS[method]) ? 1 : 0; }
+extern "C" int press_hip_packed_exact(int method) { return method_ok(method) && !packed_is_bound(METHODS[method]) ? 1 : 0; }
 
 extern "C" int press_hip_recode_fused(int src_method, int dst_method) { return recode_fused(src_method, dst_method) ? 1 : 0; }
 

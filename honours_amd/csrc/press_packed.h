@@ -1,4 +1,4 @@
-// press_packed.h - packed 16-bit helpers of the sample-value kernels (press_chunked.hip, press_huffman.hip):
+// press_packed.h - packed 16-bit helpers of the sample-value kernels (press_svb.hip, press_exsplit.hip, press_huffman.hip):
 // two samples per register, zig-zag, running sums.  Device code only.
 #pragma once
 

@@ -1,7 +1,7 @@
 // press_packed.hip - the kernels that only the packed press has (press_hip_press_sizes / press_hip_press_packed):
 // the exact size of an svb stream without writing it, the read-level scan that turns sizes into offsets, and the
 // patch of the chunk table with those offsets.  The size halves that need a family's static helpers live next to
-// them (k_ex_sizes: press_sections.hip, k_zs_plan<true>: press_zstd.hip, k_chunk_prep<.., true>: press_chunked.hip).
+// them (k_ex_sizes: press_sections.hip, k_zs_plan<true>: press_zstd.hip, k_chunk_prep<.., true>: press_svb.hip).
 
 #include "press_internal.h"
 #include "press_wave.h"

@@ -748,7 +748,7 @@ __global__ __launch_bounds__(RCC_WG) void k_rcm_decode(DecodeArgs a)
 	}
 }
 
-void launch_rcm_encode(const BatchArgs &a, hipStream_t s)
+void launch_rcm_encode(const BatchArgs &a, uint64_t *, hipStream_t s)
 {
 	(void) hipMemsetAsync(&a.ctl->ticket2, 0, 4, s);
 	hipLaunchKernelGGL(k_rcm_encode, dim3(a.nreads < 256u ? a.nreads : 256u), dim3(RCC_WG), 0, s, a);
@@ -760,7 +760,7 @@ void launch_rcm_decode(const DecodeArgs &a, hipStream_t s)
 	hipLaunchKernelGGL(k_rcm_decode, dim3(a.nreads < 256u ? a.nreads : 256u), dim3(RCC_WG), 0, s, a);
 }
 
-void launch_rcc_encode(const BatchArgs &a, hipStream_t s)
+void launch_rcc_encode(const BatchArgs &a, uint64_t *, hipStream_t s)
 {
 	(void) hipMemsetAsync(&a.ctl->ticket2, 0, 4, s);
 	hipLaunchKernelGGL(k_rcc_encode, dim3(a.nreads < 256u ? a.nreads : 256u), dim3(RCC_WG), 0, s, a);
@@ -772,7 +772,7 @@ void launch_rcc_decode(const DecodeArgs &a, hipStream_t s)
 	hipLaunchKernelGGL(k_rcc_decode, dim3(a.nreads < 256u ? a.nreads : 256u), dim3(RCC_WG), 0, s, a);
 }
 
-void launch_rcs_encode(const BatchArgs &a, hipStream_t s)
+void launch_rcs_encode(const BatchArgs &a, uint64_t *, hipStream_t s)
 {
 	hipLaunchKernelGGL(k_rcs_encode, dim3((a.nreads + 63) / 64), dim3(64), 0, s, a);
 }

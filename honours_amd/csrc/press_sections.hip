@@ -3,7 +3,7 @@
 // the same bytes back into a sorted exception list on the decode side.  Both are a few dozen
 // bytes per read on NA12878 (4.85 exceptions per read, thesis/plots/ex-tab.tex:14) - a wave per
 // read, 64 exceptions per round, so that reads with thousands of exceptions cost microseconds too;
-// the sample streams themselves are press_chunked.hip's business.
+// the sample streams themselves are the business of press_svb.hip and press_exsplit.hip.
 // All arithmetic is integer (u8/u16/u32).
 
 #include <stdlib.h>
@@ -180,7 +180,7 @@ __device__ void w_svb16_write(uint8_t *o, uint32_t nex, const uint32_t *val, uin
 	}
 }
 
-__global__ __launch_bounds__(64) void k_ex_section(BatchArgs a, int fmt, int huff)
+__global__ __launch_bounds__(64) void k_ex_section(BatchArgs a, ExFmt fmt, ExPayload pay)
 {
 	__shared__ uint32_t s_buf[66];
 	const uint32_t r = blockIdx.x;
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64) void k_ex_section(BatchArgs a, int fmt, int huf
 	}
 	if (n == 0)
 		return; // the reference reads zd[0] of an empty array: outside its domain
-	if (huff == 2 && (ored >> 31))
+	if (pay == PAY_SHUFF && (ored >> 31))
 		return; // a one-byte value the table has no code for (huffman.c:860 dereferences a NULL code there)
 
 	uint32_t len_pos = 0, len_val = 0, bits_pos = 0, bits_val = 0;
@@ -220,13 +220,13 @@ __global__ __launch_bounds__(64) void k_ex_section(BatchArgs a, int fmt, int huf
 	}
 	const uint64_t nlow = (uint64_t) (n - 1) - nex;
 	// one-byte stream: raw, or at least the 4-byte count of the Huffman stream
-	// (huff: 0 plain, 1 / 2 static Huffman (v1 / chunked pass B), 3 range coder: its stream is sized by k_rcs_encode,
-	// 4 Golomb-Rice: sized by k_rice_pick, and the splice holds for a section of any length)
-	const uint64_t need = hdr + seclen + (huff >= 3 ? 0 : huff ? 4 : nlow);
+	// (a range coder sizes its own stream; a staged one is sized by k_rice_pick / k_dh_tree, and its splice holds for a
+	// section of any length)
+	const uint64_t need = hdr + seclen + (pay == PAY_INLINE ? nlow : pay == PAY_SHUFF ? 4 : 0);
 	if (need > cap)
 		return;
 	// press.c:4520,4636,4752: the b/sb/ss Huffman variants keep the section length in a uint16_t
-	if (huff && huff != 4 && fmt != EXF_VBE21 && seclen > 65535) // (the entropy-coded b/sb/ss forms keep this length in a uint16_t: press.c:4520, 6917)
+	if ((pay == PAY_SHUFF || pay == PAY_CODER) && fmt != EXF_VBE21 && seclen > 65535) // (the entropy-coded b/sb/ss forms keep this length in a uint16_t: press.c:4520, 6917)
 		return;
 	// ex_zd.c:411: the reference works in a 2n+1024-byte buffer
 	if (fmt == EXF_EXZD && need > 2ull * n + 1024)
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(64) void k_ex_section(BatchArgs a, int fmt, int huf
 		return;
 	m->seclen = (uint32_t) seclen;
 	m->nlow = (uint32_t) nlow;
-	if (huff == 2) { // chunked Huffman pass B: the payload follows the symbol count (huffman.c:1203: htonl)
+	if (pay == PAY_SHUFF) { // chunked Huffman pass B: the payload follows the symbol count (huffman.c:1203: htonl)
 		uint8_t *h = out + hdr + seclen;
 		h[0] = (uint8_t) (nlow >> 24);
 		h[1] = (uint8_t) (nlow >> 16);
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64) void k_ex_section(BatchArgs a, int fmt, int huf
 		h[3] = (uint8_t) nlow;
 	}
 	m->status = 0;
-	if (!huff)
+	if (pay == PAY_INLINE)
 		a.out_len[r] = (uint64_t) hdr + seclen + nlow; // the Huffman pass B knows its own length
 }
 
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(64) void k_ex_section(BatchArgs a, int fmt, int huf
 //   range coders   hdr + seclen + nlow + RC_PACK_SLACK: the smallest slot certain to hold the coded stream
 //   Golomb-Rice    hdr + seclen: k_rice_pick adds the payload's exact length
 // One wave per read, after k_ex_list.
-__global__ __launch_bounds__(64) void k_ex_sizes(BatchArgs a, int fmt, int huff, uint64_t *need)
+__global__ __launch_bounds__(64) void k_ex_sizes(BatchArgs a, ExFmt fmt, ExPayload pay, uint64_t *need)
 {
 	const uint32_t r = blockIdx.x;
 	const uint32_t lane = threadIdx.x;
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(64) void k_ex_sizes(BatchArgs a, int fmt, int huff,
 	const uint32_t nex = m->nex, ored = m->ored;
 	const uint32_t hdr = (fmt == EXF_EXZD) ? 12u : 2u;
 	uint64_t size = FAIL64;
-	if (n != 0 && !(huff == 2 && (ored >> 31))) { // (the empty read; a value the table has no code for)
+	if (n != 0 && !(pay == PAY_SHUFF && (ored >> 31))) { // (the empty read; a value the table has no code for)
 		uint32_t len_pos = 0, len_val = 0, bits_pos = 0, bits_val = 0;
 		uint64_t seclen = 4;
 		if (fmt == EXF_VBE21) {
@@ -321,17 +321,17 @@ __global__ __launch_bounds__(64) void k_ex_sizes(BatchArgs a, int fmt, int huff,
 		}
 		const uint64_t nlow = (uint64_t) (n - 1) - nex;
 		size = hdr + seclen + nlow;
-		if (huff == 2) {
+		if (pay == PAY_SHUFF) {
 			const uint32_t last = a.first_chunk[r] + (n + CHUNK - 1) / CHUNK - 1;
 			const ChunkBits *cb = a.cbits + last;
 			const uint64_t bits = cb->before + cb->q[0] + cb->q[1] + cb->q[2] + cb->q[3];
 			size = hdr + seclen + 4 + (bits + 7) / 8;
-		} else if (huff == 3) {
+		} else if (pay == PAY_CODER) {
 			size += RC_PACK_SLACK;
-		} else if (huff == 4) {
+		} else if (pay == PAY_STAGED) {
 			size = hdr + seclen; // k_rice_pick adds the payload
 		}
-		if (huff && huff != 4 && fmt != EXF_VBE21 && seclen > 65535) // the uint16_t section length (press.c:4520, 6917)
+		if ((pay == PAY_SHUFF || pay == PAY_CODER) && fmt != EXF_VBE21 && seclen > 65535) // the uint16_t section length (press.c:4520, 6917)
 			size = FAIL64;
 		if (fmt == EXF_EXZD && hdr + seclen + nlow > 2ull * n + 1024) // ex_zd.c:411
 			size = FAIL64;
@@ -425,7 +425,7 @@ __device__ __forceinline__ uint32_t block_round(BlockReader &b, uint32_t k, bool
 	return v;
 }
 
-__global__ __launch_bounds__(64) void k_ex_parse(DecodeArgs a, int fmt, int huff)
+__global__ __launch_bounds__(64) void k_ex_parse(DecodeArgs a, ExFmt fmt, ExPayload pay)
 {
 	const uint32_t r = blockIdx.x;
 	const uint32_t lane = threadIdx.x;
@@ -548,10 +548,11 @@ __global__ __launch_bounds__(64) void k_ex_parse(DecodeArgs a, int fmt, int huff
 	m->nex = nex;
 	m->seclen = (uint32_t) seclen;
 	uint64_t nlow;
-	if (huff == 3) {
+	const bool rest = pay == PAY_CODER || pay == PAY_STAGED; // the coders of the one-byte values that store no count
+	if (rest) {
 		// press.c:5465: the caller passes the exact sample count, the rest are one-byte values
 		nlow = (uint64_t) cap - 1 - nex;
-	} else if (huff) {
+	} else if (pay == PAY_SHUFF) {
 		// huffman.c:1236 + :704: at least one payload byte behind the 4-byte count
 		const uint64_t hl = len - hdr - seclen;
 		if (hl <= 4)
@@ -568,7 +569,7 @@ __global__ __launch_bounds__(64) void k_ex_parse(DecodeArgs a, int fmt, int huff
 	// k_chunk_prep_meta repeats the test with what the payload delivered.  Range coders: nlow is the room's rest, so a
 	// position inside zd[1..cap) is always reached - the range test above is the whole test for them.)
 	// (vbe21: k_ex_parse_fill_vbe21 reads the list and applies the same line to its last position)
-	if (huff != 3 && nex && fmt != EXF_VBE21 && (uint64_t) last + 1 > (uint64_t) nlow + nex)
+	if (!rest && nex && fmt != EXF_VBE21 && (uint64_t) last + 1 > (uint64_t) nlow + nex)
 		return;
 	m->nlow = (uint32_t) nlow;
 	m->status = 0;
@@ -605,41 +606,27 @@ __global__ __launch_bounds__(64) void k_ex_parse_fill_vbe21(DecodeArgs a)
 
 // ------------------------------------------------------------------ launchers
 
-void launch_ex_section(const BatchArgs &a, int fmt, int ent, hipStream_t s)
+void launch_ex_section(const BatchArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s)
 {
-	hipLaunchKernelGGL(k_ex_section, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent >= 6 ? 4 : ent >= 2 ? 3 : 0);
+	hipLaunchKernelGGL(k_ex_section, dim3(a.nreads), dim3(64), 0, s, a, fmt, EX_STAGES[ent].pay);
 	if (fmt == EXF_VBE21)
 		hipLaunchKernelGGL(k_ex_fill_vbe21, dim3(a.nreads), dim3(64), 0, s, a);
 }
 
-void launch_ex_sizes(const BatchArgs &a, int fmt, int ent, uint64_t *need, hipStream_t s)
+void launch_ex_sizes(const BatchArgs &a, ExFmt fmt, ExEnt ent, uint64_t *need, hipStream_t s)
 {
-	hipLaunchKernelGGL(k_ex_sizes, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent == 1 ? 2 : ent >= 6 ? 4 : ent >= 2 ? 3 : 0, need);
+	hipLaunchKernelGGL(k_ex_sizes, dim3(a.nreads), dim3(64), 0, s, a, fmt, EX_STAGES[ent].pay, need);
 }
 
-// k_ex_parse and, for the Huffman variants, the stream decode into a.low (timed as the
-// dominant kernel of those methods)
-void launch_ex_parse_huff(const DecodeArgs &a, int fmt, int ent, hipStream_t s)
+// k_ex_parse and the stage's decode of the one-byte stream into a.low (timed as the dominant kernel of those methods)
+void launch_ex_parse_huff(const DecodeArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s)
 {
-	hipLaunchKernelGGL(k_ex_parse, dim3(a.nreads), dim3(64), 0, s, a, fmt, ent >= 2 ? 3 : ent);
+	hipLaunchKernelGGL(k_ex_parse, dim3(a.nreads), dim3(64), 0, s, a, fmt, EX_STAGES[ent].pay);
 	if (fmt == EXF_VBE21)
 		hipLaunchKernelGGL(k_ex_parse_fill_vbe21, dim3(a.nreads), dim3(64), 0, s, a);
-	if (ent) {
+	if (EX_STAGES[ent].depress) {
 		ktime_begin(1, s);
-		if (ent == 2)
-			launch_rcs_decode(a, s);
-		else if (ent == 3)
-			launch_rcc_decode(a, s);
-		else if (ent == 4)
-			launch_rcm_decode(a, s);
-		else if (ent == 5)
-			launch_cdf_decode(a, s);
-		else if (ent == 6)
-			launch_rice_decode(a, s);
-		else if (ent == 7)
-			launch_dhuf_decode(a, s);
-		else
-			launch_huff_decode(a, a.huf_minlen, s);
+		EX_STAGES[ent].depress(a, s);
 		ktime_end(1, s);
 	}
 }

@@ -92,6 +92,15 @@ __device__ __forceinline__ uint32_t max32(uint32_t v)
 	return v;
 }
 
+// make the LDS writes of this wave visible to its other lanes (DS ops of a wave execute in
+// order; this only stops the compiler from moving them)
+__device__ __forceinline__ void wave_lds_sync()
+{
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // zig-zag delta of the two samples packed in `cur`, given the dword holding the two
 // samples before them (trans.c:75,215 on packed 16-bit lanes)
 __device__ __forceinline__ uint32_t zd_pair(uint32_t cur, uint32_t prevdw)

@@ -14,10 +14,11 @@
 // serial model that must give the same bytes.
 //
 // Kernels (encode): k_zs_layout -> [the inner stream into ztmp; its encoder counts the data bytes per read and (svb) counts
-// and lists the key bytes that are not zero: press_chunked.hip, HIST] -> k_zs_blocks -> k_zs_blockmap -> k_zs_table ->
+// and lists the key bytes that are not zero: press_svb.hip, HIST] -> k_zs_blocks -> k_zs_blockmap -> k_zs_table ->
 // k_zs_bits -> k_zs_plan -> k_zs_encode (+ k_zs_rawframes for reads that do not shrink).
 
 #include "press_internal.h"
+#include "press_wave.h"
 #include "zs_table.h"
 #include <type_traits>
 
@@ -29,27 +30,7 @@ constexpr uint32_t ZB = zs::BLOCK_LITS;
 constexpr uint32_t RLE_MAX = 131072; // Block_Maximum_Size
 constexpr uint64_t ZFAIL = ~0ull;
 
-__device__ __forceinline__ uint64_t wave_incl64(uint64_t v, int lane)
-{
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint64_t o = __shfl_up(v, d);
-		if (lane >= d)
-			v += o;
-	}
-	return v;
-}
-__device__ __forceinline__ uint32_t wave_incl32(uint32_t v, int lane)
-{
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint32_t o = __shfl_up(v, d);
-		if (lane >= d)
-			v += o;
-	}
-	return v;
-}
-// 16 bytes at any byte address with the non-temporal policy (streams that are read once: press_chunked.hip's ld16_stream
+// 16 bytes at any byte address with the non-temporal policy (streams that are read once: press_wave.h's ld16_stream
 // wants alignment)
 __device__ __forceinline__ uint4 ld16_nt_any(const uint8_t *p)
 {
@@ -70,7 +51,7 @@ __device__ __forceinline__ uint32_t wave_sum32(uint32_t v)
 __device__ __forceinline__ uint64_t wg_excl_scan64(uint64_t v, uint64_t *wsum, uint64_t *total)
 {
 	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-	const uint64_t inc = wave_incl64(v, lane);
+	const uint64_t inc = wave_incl_scan64(v, lane);
 	__syncthreads();
 	if (lane == 63)
 		wsum[w] = inc;
@@ -474,7 +455,7 @@ __global__ __launch_bounds__(256) void k_zs_plan(BatchArgs a, ZsBufs z)
 			if (bi + 1 == nblk)
 				flag |= 4u;
 		}
-		const uint64_t inc = wave_incl64(size, lane);
+		const uint64_t inc = wave_incl_scan64(size, lane);
 		if (i + lane < nblk) {
 			z.bpos[b0 + i + lane] = (uint32_t) (total + inc - size);
 			z.bflag[b0 + i + lane] = (uint8_t) flag;
@@ -527,7 +508,7 @@ __global__ __launch_bounds__(256) void k_zs_plan(BatchArgs a, ZsBufs z)
 			gap = i + lane ? p - kpos[i + lane - 1] - 1 : p;
 			blocks = (gap + RLE_MAX - 1) / RLE_MAX + 1;
 		}
-		const uint32_t inc = wave_incl32(blocks, lane);
+		const uint32_t inc = scan32(blocks, lane);
 		if (i + lane < knz) {
 			uint8_t *p = out + kbase0 + 4ull * (kb + inc - blocks);
 			for (uint32_t at = 0; at < gap; at += RLE_MAX, p += 4)
@@ -641,7 +622,7 @@ __global__ __launch_bounds__(256) void k_zs_encode(BatchArgs a, ZsBufs z)
 				if ((uint32_t) (4 * w4 + e) < nmine)
 					mybits += enc[(run[w4] >> (8 * e)) & 0xFFu] >> 16;
 	}
-	const uint32_t inc = wave_incl32(mybits, lane);
+	const uint32_t inc = scan32(mybits, lane);
 	const uint32_t totalb = __shfl(inc, 63);
 	uint32_t pos = totalb - inc; // bits of the lanes behind this one
 	{
@@ -747,7 +728,7 @@ static void zs_encode_front(const BatchArgs &a, const ZsBufs &z, hipStream_t s)
 	if (z.kdiv)
 		launch_svb_encode_chunked(sv, z.kdiv == 4, true, s);
 	else
-		launch_ex_encode_chunked(sv, EXF_EXZD, 0, s);
+		launch_ex_encode_chunked(sv, EXF_EXZD, ENT_PLAIN, s);
 	ktime_mute(false);
 	hipLaunchKernelGGL(k_zs_blocks, dim3(1), dim3(1024), 0, s, a.nsamp, z.zlen, a.nreads, z.first_blk, z.rd, z.nblocks,
 			   z.max_blocks, z.kdiv, z.ztmp, z.zoff, a.meta);
@@ -1223,7 +1204,7 @@ __device__ __forceinline__ bool hd_build_table(uint16_t *dt, const ZsTree *t, in
 				rank[i] = mine;
 			mine += w4[i] == x;
 		}
-		const uint32_t inc = wave_incl32(mine, lane);
+		const uint32_t inc = scan32(mine, lane);
 		for (int i = 0; i < 4; i++)
 			if (w4[i] == x)
 				rank[i] += inc - mine;
@@ -1722,7 +1703,7 @@ __device__ __forceinline__ void hd_long(const DecodeArgs &a, const ZsBufs &z, ui
 			run(redo, nullptr);
 		}
 		// ---- the codes in front of the lane's, in its stream; the stream's codes must be k and its last code end at bit 0
-		const uint32_t inc = wave_incl32(ok ? ncodes : 0u, lane);
+		const uint32_t inc = scan32(ok ? ncodes : 0u, lane);
 		const uint32_t excl = inc - (ok ? ncodes : 0u);
 		const uint32_t base = (uint32_t) __shfl((int) excl, (int) (qw * ZSEG));
 		const uint32_t sum = (uint32_t) __shfl((int) inc, (int) (qw * ZSEG + ZSEG - 1)) - base;
@@ -1898,7 +1879,7 @@ void launch_zstd_decode_streams(const DecodeArgs &a, const ZsBufs &z, hipStream_
 	if (z.kdiv)
 		launch_svb_decode_chunked(sv, z.kdiv == 4, true, s);
 	else
-		launch_ex_decode_chunked(sv, EXF_EXZD, 0, s);
+		launch_ex_decode_chunked(sv, EXF_EXZD, ENT_PLAIN, s);
 	ktime_mute(false);
 }
 

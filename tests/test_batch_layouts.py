@@ -454,7 +454,7 @@ def test_d_argument_checks(lib):
 # ------------------------------------------------------------------ B: slots at the limit
 
 def svb_worst(m, n):
-    """the svb kinds' up-front worst case (press_chunked.hip k_chunk_prep): count + keys + 2 bytes a value
+    """the svb kinds' up-front worst case (press_svb.hip k_chunk_prep): count + keys + 2 bytes a value
     (slow5: 3, a 32-bit delta may take 17 bits)"""
     hdr = 4 if m == "slow5_svb_zd" else 0
     klen = (n + 3) // 4 if m in ("svb_zd", "slow5_svb_zd") else (n + 7) // 8
