@@ -25,6 +25,12 @@ STALL_METHODS = {"rccm_svbbe21_zd": 0, "dstall_fz_1500": 1, "dstall_fz": 2}
 # layout (ids of its own again; "rccdf" on "vbe21" is the reference's rccdf_vbe21_zd)
 RCF_CODERS = {"rc": 0, "rcc": 1, "rccm": 2, "rccdf": 3}
 RCF_LAYOUTS = {"vbe21": 0, "vbbe21": 1, "vbsbe21": 2, "vbsse21": 3}
+# include/press_hip.h enum press_hip_xstage and (2w): the ids the generic calls take for every stage_layout_zd method of the
+# three families - PRESS_HIP_XMETHOD_BASE + 4 * stage + layout, the three pairs that are public methods under their public id
+XSTAGES = {"rc": 0, "rcc": 1, "rccm": 2, "rccdf": 3, "rice": 4, "huffman": 5}
+XMETHOD_BASE = 64
+XMETHODS = {"%s_%s_zd" % (s, l): METHODS.get("%s_%s_zd" % (s, l), XMETHOD_BASE + 4 * si + li)
+            for s, si in XSTAGES.items() for l, li in RCF_LAYOUTS.items()}
 
 # method -> (bound symbol, press symbol, depress symbol, calling convention)
 #   "svb"    void press(in, n, out, &nout64);  void depress(in, nsamples, out, &nout64)
@@ -154,6 +160,8 @@ PROTOS = {
     "press_hip_huffman_press_sizes": (I, [I] + SIG + [P, P, I]),
     "press_hip_huffman_depress_batch": (I, [I] + IN + [P, P, P, Q, P, I]),
     "press_hip_huffman_repairs": (I, [P]),
+    "press_hip_xmethod": (I, [I, I]),
+    "press_hip_xmethod_parts": (I, [I, P, P]),
     "press_hip_blow5_open": (I, [S, P]),
     "press_hip_blow5_close": (None, [P]),
     "press_hip_blow5_methods": (I, [P, P, P]),
@@ -203,7 +211,7 @@ for _plain, (_deg, _at) in DEGRADED.items():
 HEADER_SYMBOLS = sorted(PROTOS)
 
 # exported for the tests only, not in the header
-_UNDECLARED = {"press_hip_debug_pass_a_launches": (Q, [])}
+_UNDECLARED = {"press_hip_debug_pass_a_launches": (Q, []), "press_hip_debug_stage_sizing_launches": (Q, [])}
 # what HuffmanTable needs of libc, and what the tests and bench.py need of libzstd
 _LIBC = {"fopen": (P, [S, S]), "fclose": (I, [P]), "malloc": (P, [Z])}
 ZSTD = {"ZSTD_decompress": (Z, [P, Z, P, Z]), "ZSTD_compress": (Z, [P, Z, P, Z, I]), "ZSTD_isError": (I, [Z])}

@@ -368,7 +368,7 @@ extern "C" int press_hip_depress_batch(int method, const uint8_t *in, const uint
 	API_LOCK;
 	const int rc = args_ok(method, NONE, nreads && (!in || !in_off || !in_len || !sig || !off || !n || !out_n), nreads,
 			       device_resident ? sig : nullptr, "sig");
-	return rc ? rc : row_depress(METHODS[method], method, { in, in_off, in_len, off, n, out_n, sig }, nreads, total_samples, device_resident);
+	return rc ? rc : row_depress(method_row(method), method, { in, in_off, in_len, off, n, out_n, sig }, nreads, total_samples, device_resident);
 }
 
 // Picoamperes: press_hip_depress_batch with the float arena `pa` in the place of sig.  A fused method's decode kernel

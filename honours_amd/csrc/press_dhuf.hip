@@ -27,6 +27,7 @@
 //   dh_code      one code by look-up: the decoder's state is the read's DhTab, which the workgroup of a tile kernel loads
 //                to LDS (k_dh_fix: only if a lane has work); the walk reads it in scratch
 // PRESS: hist, tree, count, scan, write, copy (behind section and table).  PRESS SIZES (need != NULL): hist and tree alone.
+// PACKED PRESS: the sizes, and once the arena is laid out k_dh_place (the slot check and the table), count, scan, write, copy.
 // DEPRESS: table, dplan (the reads whose table says there is a payload to decode), sync, fix x 4 (the first round counts
 // into ri_ctl[1], the later ones into ri_ctl[2]), check, dscan, emit, walk.  Bits that are no code end a record early
 // (end = PFX_SAT) with the codes in front of them kept; in the walk they, or a code that runs past the payload's end,
@@ -313,6 +314,64 @@ __global__ __launch_bounds__(64) void k_dh_tree(BatchArgs a, uint64_t *need)
 		a.ri_k[r] = ok ? (uint8_t) maxlen : (uint8_t) 0;
 }
 
+// The packed press's write half (launch_dhuf_write_sized), one wave per read; lane l owns the symbols 4 l .. 4 l + 3.
+// Behind k_dh_tree's sizes mode, which left the codes and counts in dh_tab and the lengths in ri_rd, and behind
+// k_ex_section against the laid-out slot.  What k_dh_tree's press mode does last: the slot check, out_len, ok, and the
+// table behind the section - from the codes as they lie, no tree is built again.
+__global__ __launch_bounds__(64) void k_dh_place(BatchArgs a)
+{
+	const uint32_t r = blockIdx.x, lane = threadIdx.x;
+	const ReadMeta *m = a.meta + r;
+	PfxRead *rd = a.ri_rd + r;
+	if (!uni(rd->ok))
+		return; // (refused by the size half: k_ex_section has refused it too)
+	if (uni(m->status) != 0) { // a slot of no bytes: the read does not fit out_cap
+		if (lane == 0)
+			rd->ok = 0;
+		return;
+	}
+	const uint32_t tablen = uni(rd->tablen), nlow = uni(rd->nlow), nsym = uni(rd->nsym);
+	const uint64_t total = (uint64_t) m->hdr + m->seclen + tablen + uni64(rd->paylen);
+	const bool ok = total <= a.out_off[r + 1] - a.out_off[r];
+	if (ok) {
+		const uint64_t *codes = press_codes(a, r);
+		const uint32_t *hist = press_hist(a, r);
+		uint32_t c[4], len[4], tbytes = 0;
+		uint64_t bits[4];
+#pragma unroll
+		for (uint32_t j = 0; j < 4; j++) {
+			const uint64_t cw = codes[lane * 4 + j];
+			c[j] = hist[lane * 4 + j];
+			len[j] = (uint32_t) (cw >> 56);
+			bits[j] = cw & 0x00FFFFFFFFFFFFFFull;
+			if (c[j])
+				tbytes += 2 + (len[j] + 7) / 8;
+		}
+		const uint32_t inc = scan32(tbytes, lane);
+		uint8_t *t = a.out + a.out_off[r] + m->hdr + m->seclen;
+		if (lane == 0) {
+			t[0] = (uint8_t) ((nsym - 1) & 255u);
+			t[1] = (uint8_t) (nlow >> 24);
+			t[2] = (uint8_t) (nlow >> 16);
+			t[3] = (uint8_t) (nlow >> 8);
+			t[4] = (uint8_t) nlow;
+		}
+		uint8_t *e = t + 5 + (inc - tbytes);
+		for (uint32_t j = 0; j < 4; j++) {
+			if (!c[j])
+				continue;
+			*e++ = (uint8_t) (lane * 4 + j);
+			*e++ = (uint8_t) len[j];
+			for (uint32_t b = 0; b < (len[j] + 7) / 8; b++)
+				*e++ = (uint8_t) (bits[j] >> (8 * b));
+		}
+	}
+	if (lane)
+		return;
+	a.out_len[r] = ok ? total : PFX_FAIL64;
+	rd->ok = ok ? 1 : 0;
+}
+
 __global__ __launch_bounds__(256) void k_dh_count(BatchArgs a)
 {
 	__shared__ uint8_t s_len[4][256];
@@ -546,11 +605,24 @@ __global__ __launch_bounds__(64) void k_dh_walk(DecodeArgs a) { prefix_walk<Dhuf
 void launch_dhuf_encode(const BatchArgs &a, uint64_t *need, hipStream_t s)
 {
 	const uint32_t grid = (uint32_t) (((uint64_t) a.max_chunks * PFX_UPC + 3) / 4);
+	ex_stage_sized();
 	(void) hipMemsetAsync(a.dh_tab, 0, (size_t) a.nreads * DH_PRESS_TAB, s);
 	hipLaunchKernelGGL(k_dh_hist, dim3(grid), dim3(256), 0, s, a);
 	hipLaunchKernelGGL(k_dh_tree, dim3(a.nreads), dim3(64), 0, s, a, need);
 	if (need)
 		return;
+	hipLaunchKernelGGL(k_dh_count, dim3(grid), dim3(256), 0, s, a);
+	hipLaunchKernelGGL(k_dh_scan, dim3(a.nreads), dim3(64), 0, s, a);
+	(void) hipMemsetAsync(a.ri_pay, 0, a.ri_pay_bytes, s);
+	hipLaunchKernelGGL(k_dh_write, dim3(grid), dim3(256), 0, s, a);
+	hipLaunchKernelGGL(k_dh_copy, dim3(grid), dim3(256), 0, s, a);
+}
+
+// the packed press's write half: behind launch_dhuf_encode(need != NULL) and k_ex_section; no histogram, no tree
+void launch_dhuf_write_sized(const BatchArgs &a, hipStream_t s)
+{
+	const uint32_t grid = (uint32_t) (((uint64_t) a.max_chunks * PFX_UPC + 3) / 4);
+	hipLaunchKernelGGL(k_dh_place, dim3(a.nreads), dim3(64), 0, s, a);
 	hipLaunchKernelGGL(k_dh_count, dim3(grid), dim3(256), 0, s, a);
 	hipLaunchKernelGGL(k_dh_scan, dim3(a.nreads), dim3(64), 0, s, a);
 	(void) hipMemsetAsync(a.ri_pay, 0, a.ri_pay_bytes, s);

@@ -1063,6 +1063,9 @@ __global__ __launch_bounds__(CWG) void k_low_decode_chunked(DecodeArgs a)
 
 static uint64_t n_pass_a = 0; // launches of k_ex_scan_chunked<false, ..> so far (press_hip_debug_pass_a_launches)
 extern "C" uint64_t press_hip_debug_pass_a_launches(void) { return n_pass_a; }
+static uint64_t n_stage_sized = 0; // launches of a stage's sizing kernels so far: count and pick, or hist and tree
+extern "C" uint64_t press_hip_debug_stage_sizing_launches(void) { return n_stage_sized; }
+void ex_stage_sized() { n_stage_sized++; }
 #ifdef DEC_STAMPS
 int ex_stamps_read(uint64_t *dst, uint32_t nwords) { return stamps_read(dst, nwords); }
 #endif
@@ -1095,7 +1098,30 @@ void launch_ex_encode_chunked(const BatchArgs &a, ExFmt fmt, ExEnt ent, hipStrea
 // still all zeros (k_chunk_prep only notes a base it is given; the family's kernels do not look at cap_ok); k_ex_sizes -
 // the size half of k_ex_section - then knows every stream's length (the range coders': a bound), the scan lays the
 // arena out and the chunks learn their read's base.  PACK_WRITE: the section and the encoder as they are, against
-// pk.slot.  Pass A runs once.
+// pk.slot.  Pass A runs once.  A PAY_STAGED stage sizes its own payload: PACK_SIZE ends with pass B into a.low_tmp and
+// the stage's sizing kernels, as launch_ex_prefix_sizes runs them, and PACK_WRITE goes on from what they left
+// (ExStage::write_sized): the values are counted once.
+void ex_packed_sizes(const BatchArgs &a, ExFmt fmt, ExEnt ent, uint64_t *need, hipStream_t s)
+{
+	const ExStage &st = EX_STAGES[ent];
+	launch_ex_sizes(a, fmt, ent, need, s);
+	if (st.pay != PAY_STAGED)
+		return;
+	hipLaunchKernelGGL(k_low_encode_chunked<false>, dim3(a.max_chunks), dim3(CWG), 0, s, a);
+	st.press(a, need, s);
+}
+
+void ex_packed_streams(const BatchArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s)
+{
+	const ExStage &st = EX_STAGES[ent];
+	if (st.pay != PAY_STAGED)
+		return ex_encode_streams(a, fmt, ent, s);
+	launch_ex_section(a, fmt, ent, s);
+	ktime_begin(0, s);
+	st.write_sized(a, s);
+	ktime_end(0, s);
+}
+
 void launch_ex_encode_packed(const BatchArgs &a, ExFmt fmt, ExEnt ent, const PackArgs &pk, int phases, hipStream_t s)
 {
 	if (!a.nreads || !a.max_chunks)
@@ -1105,14 +1131,14 @@ void launch_ex_encode_packed(const BatchArgs &a, ExFmt fmt, ExEnt ent, const Pac
 		ex_encode_prep(a, s);
 		ex_pass_a(a, ent, s);
 		ex_encode_lists(a, fmt, s);
-		launch_ex_sizes(a, fmt, ent, pk.need, s);
+		ex_packed_sizes(a, fmt, ent, pk.need, s);
 		if (pk.layout) {
 			launch_pack_scan(pk, a.nreads, s);
 			launch_pack_patch(a, pk.slot, s);
 		}
 	}
 	if (phases & PACK_WRITE)
-		ex_encode_streams(a, fmt, ent, s);
+		ex_packed_streams(a, fmt, ent, s);
 }
 
 // press_hip_rice_press_sizes, press_hip_huffman_press_sizes (a stage with sizes_only): the chain up to the exception lists

@@ -223,7 +223,7 @@ constexpr bool methods_in_order()
 }
 static_assert(sizeof METHODS / sizeof METHODS[0] == PRESS_HIP_NMETHODS, "one row per method id");
 static_assert(methods_in_order(), "METHODS[i].id == i, and a zstd composition wraps a plain method");
-inline bool method_ok(int m) { return m >= 0 && m < PRESS_HIP_NMETHODS; }
+inline bool public_ok(int m) { return m >= 0 && m < PRESS_HIP_NMETHODS; }
 inline bool is_shuff(const Method &m) { return m.family == FAM_EX && m.ent == ENT_SHUFF; }
 // questions to the method's row of EX_STAGES: a stage codes the one-byte values out of a temporary (Ctx::low); the size the
 // packed press announces is a bound, not the stream's length
@@ -231,7 +231,7 @@ inline bool uses_low_tmp(const Method &m) { return m.family == FAM_EX && EX_STAG
 inline bool packed_is_bound(const Method &m) { return m.family == FAM_EX && EX_STAGES[m.ent].pay == PAY_CODER; }
 
 // ---- the range-coder family (press_hip_rcf_*): every coder on every layout.  Rows of its own behind the public ids,
-// where method_ok does not reach them; the three pairs that are public methods go through the public rows.
+// where public_ok does not reach them; the three pairs that are public methods go through the public rows.
 constexpr int RCF_PRIVATE = PRESS_HIP_NMETHODS; // private id = RCF_PRIVATE + 4 * coder + layout
 #define M_RCF(coder, ent)                                                                                    \
 	M_EX(RCF_PRIVATE + 4 * coder + 0, EXF_VBE21, ent), M_EX(RCF_PRIVATE + 4 * coder + 1, EXF_VBBE21, ent), \
@@ -272,6 +272,24 @@ constexpr Method DHUF_METHODS[PRESS_HIP_NRCF_LAYOUTS] = {
 };
 inline bool is_dhuf(const Method &m) { return m.family == FAM_EX && m.ent == ENT_DHUF; }
 
+// ---- the ids the generic calls take (include/press_hip.h 2w): the public ids, and PRESS_HIP_XMETHOD_BASE + 4 * stage + layout
+// for every row of the three families.  method_row resolves an id once; the calls go on with the row.
+static_assert((int) PRESS_HIP_XSTAGE_RC == (int) PRESS_HIP_RCF_RC && (int) PRESS_HIP_XSTAGE_RCC == (int) PRESS_HIP_RCF_RCC &&
+		      (int) PRESS_HIP_XSTAGE_RCCM == (int) PRESS_HIP_RCF_RCCM && (int) PRESS_HIP_XSTAGE_RCCDF == (int) PRESS_HIP_RCF_RCCDF &&
+		      (int) PRESS_HIP_XSTAGE_RICE == (int) PRESS_HIP_NRCF_CODERS && (int) PRESS_HIP_XSTAGE_HUFFMAN == (int) PRESS_HIP_NRCF_CODERS + 1,
+	      "the first four extended stages are the family's coders");
+static_assert(PRESS_HIP_XMETHOD_BASE >= DHUF_PRIVATE + PRESS_HIP_NRCF_LAYOUTS, "the extended ids lie behind the private ones");
+inline bool xmethod_ok(int m) { return m >= PRESS_HIP_XMETHOD_BASE && m < PRESS_HIP_XMETHOD_BASE + PRESS_HIP_NXSTAGES * PRESS_HIP_NRCF_LAYOUTS; }
+inline bool method_ok(int m) { return public_ok(m) || xmethod_ok(m); }
+inline const Method &xstage_row(int stage, int layout) // stage and layout in range
+{
+	return stage < PRESS_HIP_NRCF_CODERS ? rcf_method(stage, layout) : stage == PRESS_HIP_XSTAGE_RICE ? RICE_METHODS[layout] : DHUF_METHODS[layout];
+}
+inline const Method &method_row(int m) // method_ok(m)
+{
+	return public_ok(m) ? METHODS[m] : xstage_row((m - PRESS_HIP_XMETHOD_BASE) / 4, (m - PRESS_HIP_XMETHOD_BASE) % 4);
+}
+
 // ---- bounds: the reference's formulas ----
 inline uint32_t svb16_keylen(uint32_t n) { return (n >> 3) + (((n & 7) + 7) >> 3); }
 inline uint64_t bound_svb32(uint32_t n) { return (uint64_t) (n + 3) / 4 + (uint64_t) n * 4 + 16; }    // streamvbyte.h:35
@@ -304,7 +322,7 @@ struct ScratchPlan {
 	ZsBufs zs() const;                 // z with its pointers
 };
 ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool decode);
-ScratchPlan make_plan(const Method &method, uint64_t total_samples, uint32_t nreads, bool decode); // ... or a row of RCF_METHODS / RICE_METHODS / DHUF_METHODS
+ScratchPlan make_plan(const Method &method, uint64_t total_samples, uint32_t nreads, bool decode); // ... or the row itself
 // The calls that decode nothing and walk samples by launch_pa_tiles' table: make_plan's max_chunks, and the table
 ScratchPlan make_tiles_plan(uint64_t total_samples, uint32_t nreads);
 

@@ -567,6 +567,9 @@ void launch_stall_scatter(int16_t *sig, const uint64_t *off, const uint32_t *n, 
 // stream; every other stage is given NULL.  Its depress: the stream -> a.low.
 typedef void (*ExPressFn)(const BatchArgs &a, uint64_t *need, hipStream_t s);
 typedef void (*ExDepressFn)(const DecodeArgs &a, hipStream_t s);
+// The write half of a PAY_STAGED stage in the packed press, behind press(need != NULL) of the size half and k_ex_section
+// against the laid-out slots: the slot check, then the stage's writing kernels.  Nothing is counted a second time.
+typedef void (*ExWriteFn)(const BatchArgs &a, hipStream_t s);
 void launch_low_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);   // press_exsplit.hip: pass B, k_low_encode_chunked
 void launch_shuff_encode(const BatchArgs &a, uint64_t *need, hipStream_t s); // ... k_huff_encode_chunked
 void launch_huff_decode(const DecodeArgs &a, hipStream_t s);                 // press_huffman.hip (the subsequence size: a.huf_minlen)
@@ -579,9 +582,12 @@ void launch_rcm_decode(const DecodeArgs &a, hipStream_t s);
 void launch_cdf_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);   // press_cdf.hip
 void launch_cdf_decode(const DecodeArgs &a, hipStream_t s);
 void launch_rice_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);  // press_rice.hip; sizes: k_rice_count and k_rice_pick
+void launch_rice_write_sized(const BatchArgs &a, hipStream_t s);            // ... k_rice_place, then write and copy
 void launch_rice_decode(const DecodeArgs &a, hipStream_t s);
 void launch_dhuf_encode(const BatchArgs &a, uint64_t *need, hipStream_t s);  // press_dhuf.hip; sizes: k_dh_hist and k_dh_tree
+void launch_dhuf_write_sized(const BatchArgs &a, hipStream_t s);            // ... k_dh_place, then count, scan, write and copy
 void launch_dhuf_decode(const DecodeArgs &a, hipStream_t s);
+void ex_stage_sized(); // a stage's sizing kernels are launched once more (press_hip_debug_stage_sizing_launches)
 struct ExStage {
 	ExEnt id;
 	ExPayload pay;
@@ -590,16 +596,17 @@ struct ExStage {
 	bool low_tmp;        // press: k_low_encode_chunked leaves the one-byte values in a.low_tmp for the stage (else it IS the stage, or
 	                     // the stage reads the samples); the scratch plan gives such a method Ctx::low
 	bool sizes_only;     // press(need != NULL) exists
+	ExWriteFn write_sized; // PAY_STAGED: the packed press's write half; NULL for the others
 };
 constexpr ExStage EX_STAGES[ENT_COUNT] = {
-	{ ENT_PLAIN, PAY_INLINE, launch_low_encode, nullptr, false, false },
-	{ ENT_SHUFF, PAY_SHUFF, launch_shuff_encode, launch_huff_decode, false, false },
-	{ ENT_RC, PAY_CODER, launch_rcs_encode, launch_rcs_decode, true, false },
-	{ ENT_RCC, PAY_CODER, launch_rcc_encode, launch_rcc_decode, true, false },
-	{ ENT_RCM, PAY_CODER, launch_rcm_encode, launch_rcm_decode, true, false },
-	{ ENT_CDF, PAY_CODER, launch_cdf_encode, launch_cdf_decode, true, false },
-	{ ENT_RICE, PAY_STAGED, launch_rice_encode, launch_rice_decode, true, true },
-	{ ENT_DHUF, PAY_STAGED, launch_dhuf_encode, launch_dhuf_decode, true, true },
+	{ ENT_PLAIN, PAY_INLINE, launch_low_encode, nullptr, false, false, nullptr },
+	{ ENT_SHUFF, PAY_SHUFF, launch_shuff_encode, launch_huff_decode, false, false, nullptr },
+	{ ENT_RC, PAY_CODER, launch_rcs_encode, launch_rcs_decode, true, false, nullptr },
+	{ ENT_RCC, PAY_CODER, launch_rcc_encode, launch_rcc_decode, true, false, nullptr },
+	{ ENT_RCM, PAY_CODER, launch_rcm_encode, launch_rcm_decode, true, false, nullptr },
+	{ ENT_CDF, PAY_CODER, launch_cdf_encode, launch_cdf_decode, true, false, nullptr },
+	{ ENT_RICE, PAY_STAGED, launch_rice_encode, launch_rice_decode, true, true, launch_rice_write_sized },
+	{ ENT_DHUF, PAY_STAGED, launch_dhuf_encode, launch_dhuf_decode, true, true, launch_dhuf_write_sized },
 };
 constexpr bool ex_stages_in_order()
 {
@@ -616,6 +623,10 @@ void ex_encode_lists(const BatchArgs &a, ExFmt fmt, hipStream_t s);
 void ex_encode_streams(const BatchArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s);
 void launch_ex_encode_chunked(const BatchArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s);
 void launch_ex_encode_packed(const BatchArgs &a, ExFmt fmt, ExEnt ent, const PackArgs &pk, int phases, hipStream_t s);
+// the two halves of the packed press behind the exception lists: need[] (k_ex_sizes, and for a PAY_STAGED stage pass B into
+// a.low_tmp and the stage's sizing kernels); the streams (such a stage: the section, then write_sized)
+void ex_packed_sizes(const BatchArgs &a, ExFmt fmt, ExEnt ent, uint64_t *need, hipStream_t s);
+void ex_packed_streams(const BatchArgs &a, ExFmt fmt, ExEnt ent, hipStream_t s);
 // press_hip_{rice, huffman}_press_sizes: the press chain of a stage with sizes_only as far as the sizes; a.out_off:
 // nreads + 1 zeros, a.out_len == need
 void launch_ex_prefix_sizes(const BatchArgs &a, ExFmt fmt, ExEnt ent, uint64_t *need, hipStream_t s);

@@ -13,7 +13,7 @@ extern "C" uint64_t press_hip_bound(int method, uint32_t n)
 {
 	if (!method_ok(method))
 		return 0;
-	const Method &m = METHODS[method];
+	const Method &m = method_row(method);
 	switch (m.family) {
 	case FAM_SVB:
 		if (m.slow5)
@@ -84,7 +84,7 @@ ScratchPlan make_tiles_plan(uint64_t total_samples, uint32_t nreads)
 
 ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool decode)
 {
-	return make_plan(METHODS[method], total_samples, nreads, decode);
+	return make_plan(method_row(method), total_samples, nreads, decode);
 }
 
 // (a row of METHODS, or a private one of RCF_METHODS)
@@ -225,7 +225,7 @@ StallBufs StallPlan::bufs() const
 
 // The svb family's decode kernel writes picoamperes itself; the zstd compositions over it take the general path (their
 // second stage is launched by press_zstd.hip with arguments of its own).
-bool depress_pa_fused(int method) { return method_ok(method) && METHODS[method].family == FAM_SVB; }
+bool depress_pa_fused(int method) { return method_ok(method) && method_row(method).family == FAM_SVB; }
 
 ScratchPlan make_pa_plan(int method, uint64_t total_samples, uint32_t nreads, bool host)
 {
@@ -348,7 +348,7 @@ bool recode_fused(int src, int dst)
 {
 	if (!method_ok(src) || !method_ok(dst))
 		return false;
-	return METHODS[src].family == FAM_SVB && METHODS[src].zd && METHODS[dst].family == FAM_EX;
+	return method_row(src).family == FAM_SVB && method_row(src).zd && method_row(dst).family == FAM_EX;
 }
 
 // bits > 0 (press_hip_recode_degraded_*): a fused pair's decode kernel degrades the samples it holds and the plan is that
@@ -360,7 +360,7 @@ RecodePlan make_recode_plan(int src, int dst, uint64_t total_samples, uint32_t n
 	r.p = make_plan(dst, total_samples, nreads, false);
 	r.fused = recode_fused(src, dst);
 	r.bits = bits;
-	const Method &m = METHODS[dst];
+	const Method &m = method_row(dst);
 	r.keep_heads = (m.family == FAM_SVB && m.slow5) || (m.family == FAM_ZSTD && m.kdiv);
 	r.all = r.d;
 	r.all.merge(r.p).merge(make_plan(src, total_samples, nreads, false)).merge(make_plan(dst, total_samples, nreads, true));
@@ -438,7 +438,7 @@ static uint64_t plan_bytes(const ScratchPlan &p, bool huffman)
 		b += p.rows[i].bytes;
 	return b;
 }
-static bool is_shuff(int method) { return is_shuff(METHODS[method]); }
+static bool is_shuff(int method) { return is_shuff(method_row(method)); }
 
 // the larger of what press and depress ask of every buffer
 extern "C" uint64_t press_hip_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads)
@@ -715,15 +715,37 @@ extern "C" int press_hip_pa_cal(const double *dor, uint32_t nreads, float *cal)
 	return 0;
 }
 
-extern "C" int press_hip_packed_exact(int method) { return method_ok(method) && !packed_is_bound(METHODS[method]) ? 1 : 0; }
+extern "C" int press_hip_packed_exact(int method) { return method_ok(method) && !packed_is_bound(method_row(method)) ? 1 : 0; }
 
 extern "C" int press_hip_recode_fused(int src_method, int dst_method) { return recode_fused(src_method, dst_method) ? 1 : 0; }
+
+// The id the generic calls take for stage_layout_zd: the public id of the three pairs that have one, else the extended id
+extern "C" int press_hip_xmethod(int stage, int layout)
+{
+	if (stage < 0 || stage >= PRESS_HIP_NXSTAGES || !rice_ok(layout))
+		return -1;
+	const Method &m = xstage_row(stage, layout);
+	return public_ok(m.id) && &m == &METHODS[m.id] ? m.id : PRESS_HIP_XMETHOD_BASE + 4 * stage + layout;
+}
+
+extern "C" int press_hip_xmethod_parts(int id, int *stage, int *layout)
+{
+	if (!stage || !layout)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	if (!method_ok(id) || (public_ok(id) && id < PRESS_HIP_RC_VBE21_ZD))
+		return set_error(PRESS_HIP_EARG, "method %d is not a stage_layout_zd method of the families", id);
+	const Method &m = method_row(id);
+	*stage = m.ent == ENT_RC ? PRESS_HIP_XSTAGE_RC : m.ent == ENT_RCC ? PRESS_HIP_XSTAGE_RCC : m.ent == ENT_RCM ? PRESS_HIP_XSTAGE_RCCM
+		 : m.ent == ENT_CDF ? PRESS_HIP_XSTAGE_RCCDF : m.ent == ENT_RICE ? PRESS_HIP_XSTAGE_RICE : PRESS_HIP_XSTAGE_HUFFMAN;
+	*layout = (int) m.exfmt;
+	return 0;
+}
 
 int ph::check_method(int method)
 {
 	if (!method_ok(method))
 		return set_error(PRESS_HIP_EARG, "method %d is not available in the batch API", method);
-	if (is_shuff(METHODS[method]) && !g.have_table)
+	if (is_shuff(method_row(method)) && !g.have_table)
 		return set_error(PRESS_HIP_ENOTABLE, "static-Huffman method without a table (press_hip_load_table_file)");
 	return 0;
 }
@@ -827,7 +849,7 @@ static int zs_host_frames(const DecodeArgs &a, const ZsBufs &z, hipStream_t s, b
 int ph::launch_depress_pa(const ScratchPlan &p, const DecodeArgs &a, float *pa, const float *cal, hipStream_t s)
 {
 	const Method &m = *p.m;
-	if (depress_pa_fused(m.id)) {
+	if (m.family == FAM_SVB) { // (depress_pa_fused)
 		launch_svb_decode_pa(a, pa, cal, m.key2, m.zd, m.slow5, s);
 		return launch_status();
 	}

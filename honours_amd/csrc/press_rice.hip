@@ -20,6 +20,7 @@
 //   rice_code      one code by arithmetic: the decoder's state is k alone, from the payload's first byte (k_rice_dplan),
 //                  and the tile kernels use no LDS for it
 // PRESS: count, pick, write, copy.  PRESS SIZES (need != NULL): count and pick alone, nothing else is written.
+// PACKED PRESS: the sizes, and once the arena is laid out k_rice_place (the slot check), write, copy.
 // DEPRESS: dplan, sync, fix x 2, check, dscan, emit, walk.  A run of more than RICE_RUNCAP ones makes sync and fix give
 // the subsequence up (the walk reads it a dword per step), so no lane spends more than a bounded time on bits that are
 // not its own.  The walk stops at the payload's end: behind it every value is 0.
@@ -180,6 +181,28 @@ __global__ __launch_bounds__(64) void k_rice_pick(BatchArgs a, uint64_t *need)
 		a.ri_k[r] = (uint8_t) best;
 }
 
+// The packed press's write half (launch_rice_write_sized), one lane per read: behind k_rice_pick's sizes mode, which left
+// k, the lengths and the units' first bits in ri_rd / ri_start, and behind k_ex_section against the laid-out slot.  What
+// k_rice_pick's press mode decides last: the slot check, out_len, ok.
+__global__ __launch_bounds__(256) void k_rice_place(BatchArgs a)
+{
+	const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+	if (r >= a.nreads)
+		return;
+	const ReadMeta *m = a.meta + r;
+	PfxRead *rd = a.ri_rd + r;
+	if (!rd->ok)
+		return; // (refused by the size half: k_ex_section has refused it too)
+	if (m->status != 0) { // a slot of no bytes: the read does not fit out_cap
+		rd->ok = 0;
+		return;
+	}
+	const uint64_t total = (uint64_t) m->hdr + m->seclen + rd->paylen;
+	const bool ok = total <= a.out_off[r + 1] - a.out_off[r];
+	a.out_len[r] = ok ? total : PFX_FAIL64;
+	rd->ok = ok ? 1 : 0;
+}
+
 __global__ __launch_bounds__(256) void k_rice_write(BatchArgs a)
 {
 	__shared__ uint32_t s_bits[4][PFX_WIN];
@@ -231,10 +254,21 @@ __global__ __launch_bounds__(64) void k_rice_walk(DecodeArgs a) { prefix_walk<Ri
 void launch_rice_encode(const BatchArgs &a, uint64_t *need, hipStream_t s)
 {
 	const uint32_t grid = (uint32_t) (((uint64_t) a.max_chunks * PFX_UPC + 3) / 4);
+	ex_stage_sized();
 	hipLaunchKernelGGL(k_rice_count, dim3(grid), dim3(256), 0, s, a);
 	hipLaunchKernelGGL(k_rice_pick, dim3(a.nreads), dim3(64), 0, s, a, need);
 	if (need)
 		return;
+	(void) hipMemsetAsync(a.ri_pay, 0, a.ri_pay_bytes, s);
+	hipLaunchKernelGGL(k_rice_write, dim3(grid), dim3(256), 0, s, a);
+	hipLaunchKernelGGL(k_rice_copy, dim3(grid), dim3(256), 0, s, a);
+}
+
+// the packed press's write half: behind launch_rice_encode(need != NULL) and k_ex_section; no count, no pick
+void launch_rice_write_sized(const BatchArgs &a, hipStream_t s)
+{
+	const uint32_t grid = (uint32_t) (((uint64_t) a.max_chunks * PFX_UPC + 3) / 4);
+	hipLaunchKernelGGL(k_rice_place, dim3((a.nreads + 255) / 256), dim3(256), 0, s, a);
 	(void) hipMemsetAsync(a.ri_pay, 0, a.ri_pay_bytes, s);
 	hipLaunchKernelGGL(k_rice_write, dim3(grid), dim3(256), 0, s, a);
 	hipLaunchKernelGGL(k_rice_copy, dim3(grid), dim3(256), 0, s, a);

@@ -1263,14 +1263,18 @@ static void run_recode(const DecodeArgs &d, const BatchArgs &p, ExFmt fmt, ExEnt
 		run_decode_fused<KEY2, S5>(d, f, ent, bits, s);
 		ex_encode_lists(p, fmt, s);
 		if (pk) {
-			launch_ex_sizes(p, fmt, ent, pk->need, s);
+			ex_packed_sizes(p, fmt, ent, pk->need, s);
 			launch_pack_scan_refused(*pk, d.out_n, d.nreads, s);
 			if (pk->layout)
 				launch_pack_patch(p, pk->slot, s);
 		}
 	}
-	if (phases & PACK_WRITE)
-		ex_encode_streams(p, fmt, ent, s);
+	if (phases & PACK_WRITE) {
+		if (pk)
+			ex_packed_streams(p, fmt, ent, s);
+		else
+			ex_encode_streams(p, fmt, ent, s);
+	}
 }
 
 static void recode(const DecodeArgs &d, const BatchArgs &p, bool key2bit, bool slow5, ExFmt fmt, ExEnt ent, const PackArgs *pk, int phases,

@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from .abi import (HEADER_SYMBOLS, LIB_PATH, METHODS, RCF_CODERS, RCF_LAYOUTS, STALL_METHODS, _SYMS,  # noqa: F401
+from .abi import (HEADER_SYMBOLS, LIB_PATH, METHODS, RCF_CODERS, RCF_LAYOUTS, STALL_METHODS, XMETHODS, _SYMS,  # noqa: F401
                   PressError, load_library)
 from . import abi
 
@@ -57,7 +57,10 @@ def _ptr(x):
 
 
 def _mid(method):
-    return METHODS[method] if isinstance(method, str) else int(method)
+    """a method's id: a name of METHODS or of XMETHODS (the families' methods in the generic calls), or the id itself"""
+    if isinstance(method, str):
+        return METHODS[method] if method in METHODS else XMETHODS[method]
+    return int(method)
 
 
 class HuffmanTable:
@@ -144,7 +147,9 @@ def _depress_16(name, comp, nin, n, kind="vb", table=None):
 
 
 def bound(method, n):
-    """X_bound(n): what press/test.c mallocs for the compressed read."""
+    """X_bound(n): what press/test.c mallocs for the compressed read (a family's method of XMETHODS: press_hip_bound)."""
+    if method not in _SYMS and method in XMETHODS:
+        return int(load_library().press_hip_bound(XMETHODS[method], n))
     return int(getattr(load_library(), _SYMS[method][0])(n))
 
 
@@ -1177,9 +1182,9 @@ def _prefix_repairs(prefix):
 
 
 def __getattr__(name):
-    """press.rice_name, press.huffman_press_batch ...: the functions of honours_amd.rice and honours_amd.huffman
-    (PEP 562; a module is imported on first use, it imports this one)"""
-    if name.startswith("rice_") or name.startswith("huffman_"):
+    """press.rice_name, press.huffman_press_batch, press.xmethod_id ...: the functions of honours_amd.rice,
+    honours_amd.huffman and honours_amd.xmethod (PEP 562; a module is imported on first use, it imports this one)"""
+    if name.startswith("rice_") or name.startswith("huffman_") or name.startswith("xmethod_"):
         import importlib
         mod = importlib.import_module("." + name.split("_")[0], __package__)
         if hasattr(mod, name):

@@ -1210,7 +1210,8 @@ uint64_t press_hip_stall_workspace_bytes(int stall_method, uint64_t total_sample
  * methods {rc, rcc, rccm, rccdf}_{vbe21, vbbe21, vbsbe21, vbsse21}_zd.  A stream is the layout's header and exception
  * section as the plain method L_zd writes them, then the read's one-byte values through the coder.  Three of the pairs are
  * public methods (rc_vbe21_zd, rcc_vbe21_zd, rccm_vbbe21_zd: the same kernels, the same bytes); the family reaches all
- * sixteen, with ids of its own: enum press_hip_method, PRESS_HIP_NMETHODS and the generic batch calls do not know them.
+ * sixteen, with ids of its own: enum press_hip_method and PRESS_HIP_NMETHODS do not know them, and the generic batch calls
+ * do not accept the family's own ids - (2w) gives the id of every pair that they do take.
  *
  *   rc      TurboRC's order-0 binary coder (rcsenc), rcc its order-1 coder (rccsenc), rccm its order 1-0 context mixing
  *           (rcmsenc) - as in the three public methods
@@ -1237,9 +1238,10 @@ uint64_t press_hip_stall_workspace_bytes(int stall_method, uint64_t total_sample
  * depress: n[r] is the read's exact sample count (the streams do not carry it).  A bad coder or layout id or a NULL
  * argument (raw excepted) is PRESS_HIP_EARG before any device call; nreads == 0 is PRESS_HIP_OK.
  *
- * The family's ids are accepted by these calls alone: the recode, picoampere, normalise, chunk-row, verify, CRC, sizes
- * and packed calls do not learn them, and neither do the calls of the Rice family (2u), which takes the layout ids
- * alone.  Not built: rccm_svb_zd, rccm_svb12_zd, the range-coder methods without zd, jumps.
+ * The family's own ids (coder, layout) are accepted by these calls alone: the recode, picoampere, normalise, chunk-row,
+ * verify, CRC, sizes and packed calls do not learn them - they take the pair's extended method id of (2w) - and
+ * neither do the calls of the Rice family (2u), which takes the layout ids alone.  Not built: rccm_svb_zd,
+ * rccm_svb12_zd, the range-coder methods without zd, jumps.
  */
 enum press_hip_rcf_coder {
 	PRESS_HIP_RCF_RC      = 0,
@@ -1313,8 +1315,9 @@ void rccdf_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32
  * Golomb-Rice coding of the read's one-byte values behind the layout's header and exception section.  No table, no
  * adaptive state: a code's length is a function of the value and of one parameter k per read, so press is a count, a scan
  * and a bit scatter and depress a self-synchronising prefix code, both parallel within a read.  A family with ids of its
- * own like (2t): the layout ids are enum press_hip_rcf_layout; enum press_hip_method, PRESS_HIP_NMETHODS and the generic
- * batch calls, the recode, picoampere, normalise, chunk-row, verify, CRC and packed calls do not know these methods.
+ * own like (2t): the layout ids are enum press_hip_rcf_layout; enum press_hip_method and PRESS_HIP_NMETHODS do not know
+ * these methods, and the generic batch calls, the recode, picoampere, normalise, chunk-row, verify, CRC and packed calls
+ * do not accept the family's own ids: (2w) gives the method id that they take.
  *
  * The stream.  With P(L) the plain stream of L_zd, nex its exception count, nlow = n - 1 - nex and
  * sec(L) = P(L)[: len - nlow], the stream of rice_L_zd is sec(L) + rice(low), low being the read's nlow one-byte values
@@ -1392,8 +1395,9 @@ void rice_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_
  * code is built from each read's own one-byte values and written in front of the payload.  No adaptive state: press is a
  * histogram, a tree per read, a scan and a bit scatter, depress a self-synchronising prefix code, both parallel within a
  * read.  A family with ids of its own like (2t) and (2u): the layout ids are enum press_hip_rcf_layout; enum
- * press_hip_method, PRESS_HIP_NMETHODS and the generic batch calls, the recode, picoampere, normalise, chunk-row, verify,
- * CRC and packed calls do not know these methods.
+ * press_hip_method and PRESS_HIP_NMETHODS do not know these methods, and the generic batch calls, the recode, picoampere,
+ * normalise, chunk-row, verify, CRC and packed calls do not accept the family's own ids: (2w) gives the method id that
+ * they take.
  *
  * The stream.  With P(L), nex, nlow and sec(L) as in (2u), the stream of huffman_L_zd is sec(L) + huffman(low):
  *   counts   the symbols present are ordered ascending by count, ties by ascending symbol value
@@ -1464,6 +1468,59 @@ int huffman_vbsbe21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint3
 uint64_t huffman_vbsse21_zd_bound_16(uint32_t nin);
 int huffman_vbsse21_zd_press_16(const int16_t *in, uint32_t nin, uint8_t *out, uint64_t *nout);
 int huffman_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint32_t *nout);
+
+/* ======================================================================= (2w) the families in the generic calls */
+
+/*
+ * Extended method ids.  Every stage_layout_zd method of (2t), (2u) and (2v) has an id that every call taking an `int
+ * method` (or src_method / dst_method) accepts beside the ids of enum press_hip_method:
+ *   stage    enum press_hip_xstage: the four coders of (2t) with the values of enum press_hip_rcf_coder, then Rice (2u) and
+ *            the per-read Huffman code (2v)
+ *   layout   enum press_hip_rcf_layout
+ *   id       PRESS_HIP_XMETHOD_BASE + 4 * stage + layout, 64 .. 87.  press_hip_xmethod(stage, layout) gives it - for the
+ *            three pairs that are public methods (rc_vbe21_zd, rcc_vbe21_zd, rccm_vbbe21_zd) the public id 16 / 17 / 18,
+ *            which is the same method; 64, 68 and 73 are accepted as well and mean those three - or -1 for a bad stage or
+ *            layout.  press_hip_xmethod_parts is the inverse, for 16 / 17 / 18 too; PRESS_HIP_EARG for any other id.
+ *            Both are host arithmetic and need no device.
+ * enum press_hip_method and PRESS_HIP_NMETHODS are what they were, every id outside 0 .. 18 and 64 .. 87 is
+ * PRESS_HIP_EARG (0 from the _workspace_bytes, _fused and _exact questions) as before, and the families' own calls take
+ * their own coder / layout ids and nothing else.  The stall methods (2s) stay a family apart.
+ *
+ * What the calls do with an extended id:
+ *   press_hip_bound                  the family's bound (the plain layouts' X_bound_16)
+ *   press_hip_press_batch,           out, out_len, sig and out_n byte for byte what the family's own press / depress call
+ *   press_hip_depress_batch          gives with its optional table (raw, k, maxlen) NULL.  depress: n[r] is the read's
+ *                                    exact sample count, as for the three public range-coder methods
+ *   press_hip_press_sizes,           Rice and per-read Huffman: need[r] is the exact length (press_hip_packed_exact = 1),
+ *   press_hip_press_packed           the arena has no gaps beyond the alignment, a read is written iff it fits out_cap;
+ *                                    the stage's sizes are taken once, the write half goes on from them.  The four coders:
+ *                                    need[r] = header + section + nlow + 32 and the gaps of the three public ones
+ *                                    (press_hip_packed_exact = 0)
+ *   press_hip_recode_*               every pair of the 19 + 21 ids, as source and as destination: byte for byte depress
+ *                                    followed by press.  press_hip_recode_fused is 1 for svb12_zd / svb_zd / slow5_svb_zd
+ *                                    into any extended id, as into the public exception-split methods
+ *   press_hip_recode_degraded_*,     as for the public exception-split methods: a fused source rounds in its decode kernel,
+ *   press_hip_verify_degraded_batch  every other pair runs the degrade kernel between the halves
+ *   press_hip_depress_pa_batch,      the streams are decoded into library scratch, then the converter, compare and CRC
+ *   _norm_batch, _chunks_batch,      kernels of the public methods run: floats, rows, first_bad and CRCs are bit for bit
+ *   press_hip_verify_batch,          those of the same reads held in any public method (press_hip_depress_pa_fused = 0)
+ *   press_hip_depress_crc_batch
+ *   every *_workspace_bytes          the figure of the method's row, by the rules of the public methods
+ * A range-coder read whose payload was stored raw (2t) decodes wrongly here as everywhere; press_hip_verify_batch
+ * reports it, as it does for the public three.
+ */
+enum press_hip_xstage {
+	PRESS_HIP_XSTAGE_RC      = 0,
+	PRESS_HIP_XSTAGE_RCC     = 1,
+	PRESS_HIP_XSTAGE_RCCM    = 2,
+	PRESS_HIP_XSTAGE_RCCDF   = 3,
+	PRESS_HIP_XSTAGE_RICE    = 4,
+	PRESS_HIP_XSTAGE_HUFFMAN = 5,
+	PRESS_HIP_NXSTAGES       = 6
+};
+enum { PRESS_HIP_XMETHOD_BASE = 64 };
+int press_hip_xmethod(int stage, int layout);
+int press_hip_xmethod_parts(int id, int *stage, int *layout);
 
 /* ======================================================================= (3) BLOW5 files (host) */
 
