@@ -19,8 +19,11 @@ METHODS = {
     "shuffman_vbsse21_zd": 12, "hasgam_vbsse21_zdq": 13, "zstd_hasgam_vbsse21_zdq": 14,
     "slow5_svb_zd": 15, "rc_vbe21_zd": 16, "rcc_vbe21_zd": 17, "rccm_vbbe21_zd": 18,
 }
-# include/press_hip.h enum press_hip_stall_method: a family of its own (the generic batch calls do not take these ids)
+# include/press_hip.h enum press_hip_stall_method: a family of its own (the generic batch calls do not take these ids) ...
 STALL_METHODS = {"rccm_svbbe21_zd": 0, "dstall_fz_1500": 1, "dstall_fz": 2}
+# ... and (2x): the ids they do take for the three, PRESS_HIP_SMETHOD_BASE + the stall method
+SMETHOD_BASE = 96
+SMETHODS = {name: SMETHOD_BASE + sm for name, sm in STALL_METHODS.items()}
 # include/press_hip.h enum press_hip_rcf_coder / press_hip_rcf_layout: the range-coder family, every coder on every
 # layout (ids of its own again; "rccdf" on "vbe21" is the reference's rccdf_vbe21_zd)
 RCF_CODERS = {"rc": 0, "rcc": 1, "rccm": 2, "rccdf": 3}
@@ -162,6 +165,8 @@ PROTOS = {
     "press_hip_huffman_repairs": (I, [P]),
     "press_hip_xmethod": (I, [I, I]),
     "press_hip_xmethod_parts": (I, [I, P, P]),
+    "press_hip_smethod": (I, [I]),
+    "press_hip_smethod_parts": (I, [I, P]),
     "press_hip_blow5_open": (I, [S, P]),
     "press_hip_blow5_close": (None, [P]),
     "press_hip_blow5_methods": (I, [P, P, P]),
@@ -211,7 +216,8 @@ for _plain, (_deg, _at) in DEGRADED.items():
 HEADER_SYMBOLS = sorted(PROTOS)
 
 # exported for the tests only, not in the header
-_UNDECLARED = {"press_hip_debug_pass_a_launches": (Q, []), "press_hip_debug_stage_sizing_launches": (Q, [])}
+_UNDECLARED = {"press_hip_debug_pass_a_launches": (Q, []), "press_hip_debug_stage_sizing_launches": (Q, []),
+               "press_hip_debug_stall_inner_presses": (Q, [])}
 # what HuffmanTable needs of libc, and what the tests and bench.py need of libzstd
 _LIBC = {"fopen": (P, [S, S]), "fclose": (I, [P]), "malloc": (P, [Z])}
 ZSTD = {"ZSTD_decompress": (Z, [P, Z, P, Z]), "ZSTD_compress": (Z, [P, Z, P, Z, I]), "ZSTD_isError": (I, [Z])}

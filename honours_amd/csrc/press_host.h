@@ -180,7 +180,7 @@ uint64_t zstd_bound_(uint64_t n);
 
 // ------------------------------------------------------------------ methods (dispatch and bounds: press_methods.hip)
 
-enum Family : uint8_t { FAM_SVB, FAM_EX, FAM_ZSTD };
+enum Family : uint8_t { FAM_SVB, FAM_EX, FAM_ZSTD, FAM_STALL };
 struct Method {
 	int id;
 	Family family;
@@ -189,10 +189,11 @@ struct Method {
 	ExEnt ent;            // ... and the entropy stage, a row of EX_STAGES
 	int inner;            // FAM_ZSTD: the method whose streams the frames hold ...
 	uint32_t kdiv;        // ... and its samples per key byte (ZsBufs::kdiv)
+	int stall;            // FAM_STALL: the stall method (press_hip_stall_method); `inner` presses and depresses its pieces
 };
-#define M_SVB(id, key2, zd, slow5) { id, FAM_SVB, key2, zd, slow5, EXF_VBE21, ENT_PLAIN, 0, 0 }
-#define M_EX(id, fmt, ent) { id, FAM_EX, false, false, false, fmt, ent, 0, 0 }
-#define M_ZSTD(id, inner, kdiv) { id, FAM_ZSTD, false, false, false, EXF_VBE21, ENT_PLAIN, inner, kdiv }
+#define M_SVB(id, key2, zd, slow5) { id, FAM_SVB, key2, zd, slow5, EXF_VBE21, ENT_PLAIN, 0, 0, 0 }
+#define M_EX(id, fmt, ent) { id, FAM_EX, false, false, false, fmt, ent, 0, 0, 0 }
+#define M_ZSTD(id, inner, kdiv) { id, FAM_ZSTD, false, false, false, EXF_VBE21, ENT_PLAIN, inner, kdiv, 0 }
 constexpr Method METHODS[] = {
 	M_SVB(PRESS_HIP_SVB12, false, false, false),
 	M_SVB(PRESS_HIP_SVB12_ZD, false, true, false),
@@ -280,13 +281,23 @@ static_assert((int) PRESS_HIP_XSTAGE_RC == (int) PRESS_HIP_RCF_RC && (int) PRESS
 	      "the first four extended stages are the family's coders");
 static_assert(PRESS_HIP_XMETHOD_BASE >= DHUF_PRIVATE + PRESS_HIP_NRCF_LAYOUTS, "the extended ids lie behind the private ones");
 inline bool xmethod_ok(int m) { return m >= PRESS_HIP_XMETHOD_BASE && m < PRESS_HIP_XMETHOD_BASE + PRESS_HIP_NXSTAGES * PRESS_HIP_NRCF_LAYOUTS; }
-inline bool method_ok(int m) { return public_ok(m) || xmethod_ok(m); }
+// ---- the stall methods (press_hip_stall_*, include/press_hip.h 2x): PRESS_HIP_SMETHOD_BASE + the stall method.  Rows of a
+// family of its own: the read's pieces go through `inner`'s kernels as the reads of a larger batch (press_stall.hip)
+#define M_STALL(sm) { PRESS_HIP_SMETHOD_BASE + sm, FAM_STALL, false, false, false, EXF_VBBE21, ENT_RCM, PRESS_HIP_RCCM_VBBE21_ZD, 0, sm }
+constexpr Method STALL_METHODS[PRESS_HIP_NSTALL] = {
+	M_STALL(PRESS_HIP_STALL_RCCM_SVBBE21_ZD), M_STALL(PRESS_HIP_STALL_DSTALL_FZ_1500), M_STALL(PRESS_HIP_STALL_DSTALL_FZ),
+};
+static_assert(PRESS_HIP_SMETHOD_BASE >= PRESS_HIP_XMETHOD_BASE + PRESS_HIP_NXSTAGES * PRESS_HIP_NRCF_LAYOUTS + 8, "ids 88 .. 95 stay unused");
+inline bool smethod_ok(int m) { return m >= PRESS_HIP_SMETHOD_BASE && m < PRESS_HIP_SMETHOD_BASE + PRESS_HIP_NSTALL; }
+inline bool method_ok(int m) { return public_ok(m) || xmethod_ok(m) || smethod_ok(m); }
 inline const Method &xstage_row(int stage, int layout) // stage and layout in range
 {
 	return stage < PRESS_HIP_NRCF_CODERS ? rcf_method(stage, layout) : stage == PRESS_HIP_XSTAGE_RICE ? RICE_METHODS[layout] : DHUF_METHODS[layout];
 }
 inline const Method &method_row(int m) // method_ok(m)
 {
+	if (smethod_ok(m))
+		return STALL_METHODS[m - PRESS_HIP_SMETHOD_BASE];
 	return public_ok(m) ? METHODS[m] : xstage_row((m - PRESS_HIP_XMETHOD_BASE) / 4, (m - PRESS_HIP_XMETHOD_BASE) % 4);
 }
 
@@ -308,10 +319,18 @@ struct ScratchPlan {
 	uint32_t ri_max_tiles;                      // Rice decode, else 0
 	uint64_t ri_pay_bytes;                      // Rice press, else 0
 	ZsBufs z; // zstd frames: kdiv, max_blocks, lit_base and the cap_* (else 0); bind() adds the pointers
+	// a stall method (FAM_STALL), else 0: the pieces as a batch of `inner` - their count, their samples, the chunks of that
+	// batch (max_chunks is the READS' figure, as for every method: the sample walkers behind a decode are sized by it) -
+	// and the bytes of the pieces' streams (press)
+	struct {
+		uint32_t npieces, max_chunks;
+		uint64_t piece_samples, arena_bytes;
+	} sl;
+	static constexpr int MAXROWS = 64; // a degraded packed recode from a stall method into zstd_svb_zd names 48
 	struct Row {
 		DevBuf Ctx::*buf;
 		size_t bytes;
-	} rows[48]; // at most one per scratch DevBuf of Ctx
+	} rows[MAXROWS]; // at most one per scratch DevBuf of Ctx
 	int nrows;
 	ScratchPlan &need(DevBuf Ctx::*buf, size_t bytes); // a buffer named twice keeps the larger size
 	ScratchPlan &merge(const ScratchPlan &o);          // every row of o: the larger size of every buffer
@@ -400,6 +419,11 @@ StallPlan make_stall_plan(int stall_method, uint64_t total_samples, uint32_t nre
 // a.sig / off / nsamp: the caller's samples, a.out / out_off / out_len: its slots; stall: NULL or 2 * nreads words
 int launch_stall_press(int stall_method, const StallPlan &p, const BatchArgs &a, uint32_t *stall, hipStream_t s);
 int launch_stall_depress(const StallPlan &p, const DecodeArgs &a, hipStream_t s);
+// the press in its two halves: the pieces pressed into the library's own arena (segments, plan, gather, the inner press),
+// and what reads the finished pieces - the assemble above, or the sizes and the packed assemble of launch_press_packed
+void launch_stall_pieces(int stall_method, const StallPlan &p, const BatchArgs &a, hipStream_t s);
+// make_plan's ScratchPlan of a FAM_STALL row (the generic calls) as the StallPlan the launchers above take
+StallPlan stall_plan_of(const ScratchPlan &p);
 
 int check_method(int method); // EARG / ENOTABLE
 int launch_status();          // EHIP if a kernel launch since the last call failed

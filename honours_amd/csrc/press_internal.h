@@ -556,6 +556,11 @@ void launch_stall_plan(int stall_method, const uint32_t *n, uint32_t nreads, con
 void launch_stall_gather(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const StallBufs &b, hipStream_t s);
 void launch_stall_assemble(int stall_method, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint8_t *out, const uint64_t *out_off,
 			   uint64_t *out_len, uint32_t *stall, hipStream_t s);
+// behind the inner press: need[r] = the exact length of read r's stream (PRESS_HIP_FAILED: refused), and the assemble into
+// a laid-out arena: read r at slot[r], written where it ends at or in front of out_cap (PackArgs)
+void launch_stall_sizes(int stall_method, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint64_t *need, hipStream_t s);
+void launch_stall_assemble_packed(int stall_method, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint8_t *out, const uint64_t *slot,
+				  uint64_t out_cap, uint64_t *out_len, hipStream_t s);
 // depress: headers -> piece table (behind it: the inner depress of the pieces) -> the samples in place
 void launch_stall_parse(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, const uint32_t *n, uint32_t nreads,
 			const StallBufs &b, hipStream_t s);

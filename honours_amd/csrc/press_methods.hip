@@ -1,6 +1,8 @@
 // press_methods.hip - everything that interprets a row of the method table (press_host.h): the reference's X_bound,
 // the scratch plan of a batch and its dispatch to the kernel launchers of press_*.hip.
 
+#include <stdlib.h>
+
 #include <cmath>
 #include <vector>
 
@@ -25,6 +27,8 @@ extern "C" uint64_t press_hip_bound(int method, uint32_t n)
 		return bound_vbzd(n);                                         // press.c:3411,4409
 	case FAM_ZSTD: // the inner stream, the svb kinds' behind its u32 count (press.c:1860, 2020, 8549)
 		return zstd_bound_((m.kdiv ? 4 : 0) + press_hip_bound(m.inner, n));
+	case FAM_STALL: // the inner method's (press.c:7723, 7893, 7981)
+		return press_hip_bound(m.inner, n);
 	}
 	return 0;
 }
@@ -42,8 +46,11 @@ ScratchPlan &ScratchPlan::need(DevBuf Ctx::*buf, size_t bytes)
 	int i = 0;
 	while (i < nrows && rows[i].buf != buf)
 		i++;
-	if (i == nrows)
+	if (i == nrows) {
+		if (nrows == MAXROWS) // (a plan is a union of a few calls' buffers: MAXROWS is above every one)
+			abort();
 		rows[nrows++] = { buf, 0 };
+	}
 	rows[i].bytes = bytes > rows[i].bytes ? bytes : rows[i].bytes;
 	return *this;
 }
@@ -90,6 +97,16 @@ ScratchPlan make_plan(int method, uint64_t total_samples, uint32_t nreads, bool 
 // (a row of METHODS, or a private one of RCF_METHODS)
 ScratchPlan make_plan(const Method &method, uint64_t total_samples, uint32_t nreads, bool decode)
 {
+	if (method.family == FAM_STALL) {
+		// the family's own plan (make_stall_plan): the inner method's over the pieces and the piece table.  max_chunks is
+		// the reads' figure, the pieces' is kept aside for the inner launch (stall_plan_of)
+		const StallPlan sp = make_stall_plan(method.stall, total_samples, nreads, decode, false);
+		ScratchPlan p = sp.all;
+		p.m = &method;
+		p.sl = { sp.npieces, sp.inner.max_chunks, sp.piece_samples, sp.arena_bytes };
+		p.max_chunks = plan_max_chunks(total_samples, nreads);
+		return p;
+	}
 	ScratchPlan p{};
 	p.m = &method;
 	const bool zs = p.m->family == FAM_ZSTD;
@@ -204,6 +221,13 @@ StallPlan make_stall_plan(int stall_method, uint64_t total_samples, uint32_t nre
 	if (host && !decode)
 		p.all.need(&Ctx::sl_stall, nr * 8);
 	return p;
+}
+
+StallPlan stall_plan_of(const ScratchPlan &p)
+{
+	StallPlan sp{ p, p, p.sl.npieces, p.sl.piece_samples, p.sl.arena_bytes };
+	sp.inner.max_chunks = p.sl.max_chunks;
+	return sp;
 }
 
 StallBufs StallPlan::bufs() const
@@ -583,8 +607,13 @@ extern "C" uint64_t press_hip_stall_workspace_bytes(int stall_method, uint64_t t
 	return plan_bytes(p.merge(make_stall_plan(stall_method, total_samples, nreads, true, false).all), false);
 }
 
-// segs[0] of jnn_raw under JNNV1_CDNA_PARAM (press.c:7734), the plan, the pieces, rccm_vbbe21_zd over them, the streams
-int ph::launch_stall_press(int stall_method, const StallPlan &p, const BatchArgs &a, uint32_t *stall, hipStream_t s)
+// launches of the inner press of the stall methods: one per press, sizes or packed call, whatever its phases
+static uint64_t n_stall_inner;
+extern "C" uint64_t press_hip_debug_stall_inner_presses(void) { return n_stall_inner; }
+
+// segs[0] of jnn_raw under JNNV1_CDNA_PARAM (press.c:7734), the plan, the pieces, rccm_vbbe21_zd over them: every piece's
+// stream and its length lie in the library's arena (sl_parena, polen[]) before a byte reaches the caller
+void ph::launch_stall_pieces(int stall_method, const StallPlan &p, const BatchArgs &a, hipStream_t s)
 {
 	const StallBufs b = p.bufs();
 	const SegParams cdna = { 0.75f, 50, 50, 150, 0.25f, 5, 0.0f, 0.0f }; // jnn.h:40-49 (press_hip_jnn_params_preset(0))
@@ -602,8 +631,31 @@ int ph::launch_stall_press(int stall_method, const StallPlan &p, const BatchArgs
 	in.out_len = b.polen;
 	const Method &m = METHODS[PRESS_HIP_RCCM_VBBE21_ZD];
 	launch_ex_encode_chunked(in, m.exfmt, m.ent, s);
-	launch_stall_assemble(stall_method, a.nsamp, a.nreads, b, a.out, a.out_off, a.out_len, stall, s);
+	n_stall_inner++;
+}
+
+// ... and the streams
+int ph::launch_stall_press(int stall_method, const StallPlan &p, const BatchArgs &a, uint32_t *stall, hipStream_t s)
+{
+	launch_stall_pieces(stall_method, p, a, s);
+	launch_stall_assemble(stall_method, a.nsamp, a.nreads, p.bufs(), a.out, a.out_off, a.out_len, stall, s);
 	return launch_status();
+}
+
+// Packed press of a stall method.  PACK_SIZE: the pieces, k_stall_sizes - the streams' exact lengths out of polen[] - and
+// with a layout the scan; PACK_WRITE: the assemble against the laid-out offsets and out_cap.  The inner coder runs in
+// PACK_SIZE alone: the write half copies what it left in the library's arena.
+static void launch_stall_press_packed(int stall_method, const StallPlan &p, const BatchArgs &a, const PackArgs &pk, int phases, hipStream_t s)
+{
+	const StallBufs b = p.bufs();
+	if (phases & PACK_SIZE) {
+		launch_stall_pieces(stall_method, p, a, s);
+		launch_stall_sizes(stall_method, a.nsamp, a.nreads, b, pk.need, s);
+		if (pk.layout)
+			launch_pack_scan(pk, a.nreads, s);
+	}
+	if (phases & PACK_WRITE)
+		launch_stall_assemble_packed(stall_method, a.nsamp, a.nreads, b, a.out, pk.slot, pk.out_cap, a.out_len, s);
 }
 
 int ph::launch_stall_depress(const StallPlan &p, const DecodeArgs &a, hipStream_t s)
@@ -732,12 +784,25 @@ extern "C" int press_hip_xmethod_parts(int id, int *stage, int *layout)
 {
 	if (!stage || !layout)
 		return set_error(PRESS_HIP_EARG, "NULL argument");
-	if (!method_ok(id) || (public_ok(id) && id < PRESS_HIP_RC_VBE21_ZD))
+	if (!(public_ok(id) || xmethod_ok(id)) || (public_ok(id) && id < PRESS_HIP_RC_VBE21_ZD))
 		return set_error(PRESS_HIP_EARG, "method %d is not a stage_layout_zd method of the families", id);
 	const Method &m = method_row(id);
 	*stage = m.ent == ENT_RC ? PRESS_HIP_XSTAGE_RC : m.ent == ENT_RCC ? PRESS_HIP_XSTAGE_RCC : m.ent == ENT_RCM ? PRESS_HIP_XSTAGE_RCCM
 		 : m.ent == ENT_CDF ? PRESS_HIP_XSTAGE_RCCDF : m.ent == ENT_RICE ? PRESS_HIP_XSTAGE_RICE : PRESS_HIP_XSTAGE_HUFFMAN;
 	*layout = (int) m.exfmt;
+	return 0;
+}
+
+// The id the generic calls take for a stall method, and back
+extern "C" int press_hip_smethod(int stall_method) { return stall_ok(stall_method) ? PRESS_HIP_SMETHOD_BASE + stall_method : -1; }
+
+extern "C" int press_hip_smethod_parts(int id, int *stall_method)
+{
+	if (!stall_method)
+		return set_error(PRESS_HIP_EARG, "NULL argument");
+	if (!smethod_ok(id))
+		return set_error(PRESS_HIP_EARG, "method %d is not a stall method's id", id);
+	*stall_method = method_row(id).stall;
 	return 0;
 }
 
@@ -763,6 +828,8 @@ int ph::launch_press(const ScratchPlan &p, const BatchArgs &a, hipStream_t s)
 		launch_svb_encode_chunked(a, m.key2, m.zd, s, m.slow5);
 	} else if (m.family == FAM_EX) {
 		launch_ex_encode_chunked(a, m.exfmt, m.ent, s);
+	} else if (m.family == FAM_STALL) {
+		return launch_stall_press(m.stall, stall_plan_of(p), a, nullptr, s);
 	} else {
 		const ZsBufs z = p.zs();
 		launch_zstd_encode(a, z, s);
@@ -777,6 +844,8 @@ int ph::launch_press_packed(const ScratchPlan &p, const BatchArgs &a, const Pack
 		launch_svb_encode_packed(a, m.key2, m.zd, m.slow5, pk, phases, s);
 	} else if (m.family == FAM_EX) {
 		launch_ex_encode_packed(a, m.exfmt, m.ent, pk, phases, s);
+	} else if (m.family == FAM_STALL) {
+		launch_stall_press_packed(m.stall, stall_plan_of(p), a, pk, phases, s);
 	} else {
 		const ZsBufs z = p.zs();
 		launch_zstd_encode_packed(a, z, pk, phases, s);
@@ -932,6 +1001,8 @@ int ph::launch_depress(const ScratchPlan &p, const DecodeArgs &a, hipStream_t s)
 		launch_svb_decode_chunked(a, m.key2, m.zd, s, m.slow5);
 	} else if (m.family == FAM_EX) {
 		launch_ex_decode_chunked(a, m.exfmt, m.ent, s);
+	} else if (m.family == FAM_STALL) {
+		return launch_stall_depress(stall_plan_of(p), a, s);
 	} else {
 		const ZsBufs z = p.zs();
 		launch_zstd_decode_frames(a, z, s);

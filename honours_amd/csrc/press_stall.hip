@@ -14,6 +14,8 @@
 //            k_stall_gather          one wave per piece: the samples of the piece
 //            (the inner press)
 //            k_stall_assemble        one wave per read: the form, the header, the pieces' streams into the slot
+//   sizes    ... the inner press, then k_stall_sizes: the form's length per read, nothing of the caller's written
+//   packed   ... k_stall_sizes, the layout scan (press_packed.hip), k_stall_assemble<PACKED> against the laid-out offsets
 //   depress  k_stall_parse           one wave: every header checked before a byte of a piece is read; the piece table
 //            (the inner depress)
 //            k_stall_scatter         one wave per read: the two spans of the rest and the stall into place
@@ -223,39 +225,68 @@ __global__ __launch_bounds__(64) void k_stall_gather(const int16_t *sig, const u
 	}
 }
 
-// One wave per read: which form, its length against the slot, then the bytes.  dstall_fz keeps the stall form only where
-// the WHOLE stall stream is strictly shorter than the bare rccm_vbbe21_zd stream of the read (press.c:8006).  A stall
-// piece beyond 65535 bytes (the u16 count): the read is refused, dstall_fz takes the other form.
+// The form of a read's stream, the one definition of it (k_stall_sizes and k_stall_assemble).  Form 1: the stall stream;
+// form 0: [0][u32][a bare stream] of piece `bare`.  dstall_fz keeps the stall form only where the WHOLE stall stream is
+// strictly shorter than the bare rccm_vbbe21_zd stream of the read (press.c:8006).  A stall piece beyond 65535 bytes (the
+// u16 count): the read is refused, dstall_fz takes the other form.  L0, L1, L2: polen[] of the read's three pieces.
+struct StallForm {
+	bool fail, form1;
+	uint32_t bare;
+	uint64_t len; // of the stream; form 0: 5 + the bare piece's
+};
+__device__ __forceinline__ StallForm stall_form(int method, uint32_t n, uint32_t ex, uint32_t ok, uint64_t L0, uint64_t L1, uint64_t L2)
+{
+	StallForm f;
+	f.form1 = ex && L0 != SFAIL64 && L0 <= 0xFFFFFFFFull && L1 != SFAIL64 && L1 <= 65535;
+	const uint64_t len1 = 11 + L1 + L0;
+	f.bare = 0;
+	f.fail = !ok || n == 0;
+	if (ex && method == PRESS_STALL_FZ) {
+		f.bare = 2;
+		if (f.form1 && L2 != SFAIL64 && !(len1 < L2))
+			f.form1 = false;
+	} else if (ex && !f.form1) {
+		f.fail = true;
+	}
+	const uint64_t Lb = f.bare ? L2 : L0;
+	if (!f.form1 && (Lb == SFAIL64 || Lb > 0xFFFFFFFFull))
+		f.fail = true;
+	f.len = f.form1 ? len1 : 5 + Lb;
+	return f;
+}
+
+// Grid-stride, 64 reads a wave round: need[r] = the exact length of the read's stream, SFAIL64 for a refused read
+__global__ __launch_bounds__(64) void k_stall_sizes(int method, const uint32_t *nsamp, uint32_t nreads, StallBufs b, uint64_t *need)
+{
+	for (uint64_t r = (uint64_t) blockIdx.x * 64 + threadIdx.x; r < nreads; r += (uint64_t) gridDim.x * 64) {
+		const uint64_t p0 = (uint64_t) STALL_PIECES * r;
+		const StallRead rd = b.rd[r];
+		const StallForm f = stall_form(method, nsamp[r], rd.exists, rd.ok, b.polen[p0], b.polen[p0 + 1], b.polen[p0 + 2]);
+		need[r] = f.fail ? SFAIL64 : f.len;
+	}
+}
+
+// One wave per read: the form, its length against the room, then the bytes.  The room is the caller's slot
+// [out_off[r], out_off[r + 1]), or - PACKED, the laid-out arena of press_hip_press_packed, where neither an aligned next
+// offset nor the last read's end says how far a stream may go - what lies between out_off[r] and out_cap.
+template <bool PACKED>
 __global__ __launch_bounds__(64) void k_stall_assemble(int method, const uint32_t *nsamp, StallBufs b, uint8_t *out, const uint64_t *out_off,
-							uint64_t *out_len, uint32_t *stall)
+							uint64_t *out_len, uint32_t *stall, uint64_t out_cap)
 {
 	const uint32_t r = blockIdx.x, lane = threadIdx.x;
 	const uint64_t p0 = (uint64_t) STALL_PIECES * r;
 	const StallRead rd = b.rd[r];
 	const uint32_t ss = uni(rd.start), sl = uni(rd.len), ex = uni(rd.exists), ok = uni(rd.ok);
 	const uint64_t L0 = uni64(b.polen[p0]), L1 = uni64(b.polen[p0 + 1]), L2 = uni64(b.polen[p0 + 2]);
-	const uint64_t base = uni64(out_off[r]), cap = uni64(out_off[r + 1]) - base;
+	const uint64_t base = uni64(out_off[r]);
+	const uint64_t cap = PACKED ? (base < out_cap ? out_cap - base : 0ull) : uni64(out_off[r + 1]) - base;
 	uint8_t *o = out + base;
-	// form 1: the stall stream; form 0: [0][u32][a bare stream] of piece `bare`
-	bool form1 = ex && L0 != SFAIL64 && L0 <= 0xFFFFFFFFull && L1 != SFAIL64 && L1 <= 65535;
-	const uint64_t len1 = 11 + L1 + L0;
-	uint32_t bare = 0;
-	bool fail = !ok || uni(nsamp[r]) == 0;
-	if (ex && method == PRESS_STALL_FZ) {
-		bare = 2;
-		if (form1 && L2 != SFAIL64 && !(len1 < L2))
-			form1 = false;
-	} else if (ex && !form1) {
-		fail = true;
-	}
+	const StallForm f = stall_form(method, uni(nsamp[r]), ex, ok, L0, L1, L2);
+	const bool form1 = f.form1, fail = f.fail || f.len > cap;
+	const uint32_t bare = f.bare;
 	const uint64_t Lb = bare ? L2 : L0;
-	if (!form1 && (Lb == SFAIL64 || Lb > 0xFFFFFFFFull))
-		fail = true;
-	const uint64_t len = form1 ? len1 : 5 + Lb;
-	if (!fail && len > cap)
-		fail = true;
 	if (lane == 0) {
-		out_len[r] = fail ? SFAIL64 : len;
+		out_len[r] = fail ? SFAIL64 : f.len;
 		if (stall) {
 			stall[2 * (uint64_t) r] = (!fail && form1) ? ss : 0u;
 			stall[2 * (uint64_t) r + 1] = (!fail && form1) ? sl : 0u;
@@ -405,7 +436,19 @@ void launch_stall_gather(const int16_t *sig, const uint64_t *off, const uint32_t
 void launch_stall_assemble(int stall_method, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint8_t *out, const uint64_t *out_off,
 			   uint64_t *out_len, uint32_t *stall, hipStream_t s)
 {
-	hipLaunchKernelGGL(k_stall_assemble, dim3(nreads), dim3(64), 0, s, stall_method, n, b, out, out_off, out_len, stall);
+	hipLaunchKernelGGL(k_stall_assemble<false>, dim3(nreads), dim3(64), 0, s, stall_method, n, b, out, out_off, out_len, stall, 0ull);
+}
+
+void launch_stall_sizes(int stall_method, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint64_t *need, hipStream_t s)
+{
+	const uint32_t rounds = (nreads + 63) / 64;
+	hipLaunchKernelGGL(k_stall_sizes, dim3(rounds < 256u ? rounds : 256u), dim3(64), 0, s, stall_method, n, nreads, b, need);
+}
+
+void launch_stall_assemble_packed(int stall_method, const uint32_t *n, uint32_t nreads, const StallBufs &b, uint8_t *out, const uint64_t *slot,
+				  uint64_t out_cap, uint64_t *out_len, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_stall_assemble<true>, dim3(nreads), dim3(64), 0, s, stall_method, n, b, out, slot, out_len, (uint32_t *) nullptr, out_cap);
 }
 
 void launch_stall_parse(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, const uint32_t *n, uint32_t nreads,

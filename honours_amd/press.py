@@ -13,8 +13,8 @@ import os
 
 import numpy as np
 
-from .abi import (HEADER_SYMBOLS, LIB_PATH, METHODS, RCF_CODERS, RCF_LAYOUTS, STALL_METHODS, XMETHODS, _SYMS,  # noqa: F401
-                  PressError, load_library)
+from .abi import (HEADER_SYMBOLS, LIB_PATH, METHODS, RCF_CODERS, RCF_LAYOUTS, SMETHODS, STALL_METHODS, XMETHODS,  # noqa: F401
+                  _SYMS, PressError, load_library)
 from . import abi
 
 TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "NA12878_zd.huffman")
@@ -57,9 +57,10 @@ def _ptr(x):
 
 
 def _mid(method):
-    """a method's id: a name of METHODS or of XMETHODS (the families' methods in the generic calls), or the id itself"""
+    """a method's id: a name of METHODS, of XMETHODS (the families' methods in the generic calls) or of SMETHODS (the stall
+    methods there), or the id itself"""
     if isinstance(method, str):
-        return METHODS[method] if method in METHODS else XMETHODS[method]
+        return METHODS[method] if method in METHODS else SMETHODS[method] if method in SMETHODS else XMETHODS[method]
     return int(method)
 
 
@@ -148,8 +149,8 @@ def _depress_16(name, comp, nin, n, kind="vb", table=None):
 
 def bound(method, n):
     """X_bound(n): what press/test.c mallocs for the compressed read (a family's method of XMETHODS: press_hip_bound)."""
-    if method not in _SYMS and method in XMETHODS:
-        return int(load_library().press_hip_bound(XMETHODS[method], n))
+    if method not in _SYMS and (method in XMETHODS or method in SMETHODS):
+        return int(load_library().press_hip_bound(_mid(method), n))
     return int(getattr(load_library(), _SYMS[method][0])(n))
 
 
@@ -1182,9 +1183,10 @@ def _prefix_repairs(prefix):
 
 
 def __getattr__(name):
-    """press.rice_name, press.huffman_press_batch, press.xmethod_id ...: the functions of honours_amd.rice,
-    honours_amd.huffman and honours_amd.xmethod (PEP 562; a module is imported on first use, it imports this one)"""
-    if name.startswith("rice_") or name.startswith("huffman_") or name.startswith("xmethod_"):
+    """press.rice_name, press.huffman_press_batch, press.xmethod_id, press.smethod_id ...: the functions of honours_amd.rice,
+    honours_amd.huffman, honours_amd.xmethod and honours_amd.smethod (PEP 562; a module is imported on first use, it imports
+    this one)"""
+    if name.split("_")[0] in ("rice", "huffman", "xmethod", "smethod") and "_" in name:
         import importlib
         mod = importlib.import_module("." + name.split("_")[0], __package__)
         if hasattr(mod, name):

@@ -367,7 +367,8 @@ int press_hip_press_sizes(int method, const int16_t *sig, const uint64_t *off, c
 int press_hip_press_packed(int method, const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
 			   uint64_t total_samples, uint8_t *out, uint64_t out_cap, uint32_t align,
 			   uint64_t *out_off, uint64_t *out_len, int device_resident);
-int press_hip_packed_exact(int method); /* 1: need == stream length (16 methods); 0: range coders, bad ids */
+int press_hip_packed_exact(int method); /* 1: need == stream length (16 of the 19 methods, Rice and per-read Huffman of
+                                         * (2w), the stall methods of (2x)); 0: range coders, bad ids */
 uint64_t press_hip_packed_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads);
 
 /*
@@ -1138,7 +1139,8 @@ int press_hip_scratch_fill(int byte);
 /*
  * rccm_svbbe21_zd, dstall_fz_1500 and dstall_fz (press.c:7716-8148): the read is cut at a stall - the first segment
  * (x, y) that sigtk's jnn_raw finds under JNNV1_CDNA_PARAM - and the stall and the rest are coded apart.  A family of
- * its own with ids of its own; enum press_hip_method, PRESS_HIP_NMETHODS and the generic batch calls do not know them.
+ * its own with ids of its own; enum press_hip_method and PRESS_HIP_NMETHODS do not know them, and the generic batch calls
+ * do not accept the family's own ids 0 .. 2 - (2x) gives the method id that they take.
  *
  *   stream   [exists u8]  exists: [stall_start u16][stall_len u16][nstall u16][stall piece]  always: [nrest u32][rest piece]
  *   rest     rccm_vbbe21_zd of the read without the samples [stall_start, stall_start + stall_len)
@@ -1482,9 +1484,9 @@ int huffman_vbsse21_zd_depress_16(uint8_t *in, uint64_t nin, int16_t *out, uint3
  *            which is the same method; 64, 68 and 73 are accepted as well and mean those three - or -1 for a bad stage or
  *            layout.  press_hip_xmethod_parts is the inverse, for 16 / 17 / 18 too; PRESS_HIP_EARG for any other id.
  *            Both are host arithmetic and need no device.
- * enum press_hip_method and PRESS_HIP_NMETHODS are what they were, every id outside 0 .. 18 and 64 .. 87 is
+ * enum press_hip_method and PRESS_HIP_NMETHODS are what they were, every id outside 0 .. 18, 64 .. 87 and 96 .. 98 is
  * PRESS_HIP_EARG (0 from the _workspace_bytes, _fused and _exact questions) as before, and the families' own calls take
- * their own coder / layout ids and nothing else.  The stall methods (2s) stay a family apart.
+ * their own coder / layout ids and nothing else.  The stall methods (2s) have ids of their own, 96 .. 98: (2x).
  *
  * What the calls do with an extended id:
  *   press_hip_bound                  the family's bound (the plain layouts' X_bound_16)
@@ -1521,6 +1523,48 @@ enum press_hip_xstage {
 enum { PRESS_HIP_XMETHOD_BASE = 64 };
 int press_hip_xmethod(int stage, int layout);
 int press_hip_xmethod_parts(int id, int *stage, int *layout);
+
+/* ======================================================================= (2x) the stall methods in the generic calls */
+
+/*
+ * The three stall methods of (2s) have a method id that every call taking an `int method` (or src_method / dst_method)
+ * accepts beside the ids of enum press_hip_method and the extended ids of (2w):
+ *   id       PRESS_HIP_SMETHOD_BASE + stall method: 96 rccm_svbbe21_zd, 97 dstall_fz_1500, 98 dstall_fz.
+ *            press_hip_smethod(stall_method) gives it, -1 for a stall method out of range; press_hip_smethod_parts is the
+ *            inverse, PRESS_HIP_EARG for every other id or a NULL pointer.  Host arithmetic, no device.
+ * 88 .. 95 and everything from 99 on stay PRESS_HIP_EARG before any device call (0 from the _workspace_bytes, _fused and
+ * _exact questions), press_hip_xmethod_parts refuses 96 .. 98, and the family's own calls (press_hip_stall_*) keep their
+ * ids 0 .. 2 and refuse 96 .. 98.  enum press_hip_method and PRESS_HIP_NMETHODS are what they were.
+ *
+ * What the calls do with such an id (both device_resident forms; the device-resident form only enqueues on the current
+ * stream):
+ *   press_hip_bound                  press_hip_stall_bound
+ *   press_hip_press_batch            out and out_len byte for byte those of press_hip_stall_press_batch with stall = NULL
+ *   press_hip_depress_batch          one decoder reads all three ids; n[r] is the exact sample count; out_n[r] = UINT32_MAX
+ *                                    for a stream refused by rule 3 of (2s), whose room is not written
+ *   press_hip_press_sizes            need[r] is the EXACT stream length (press_hip_packed_exact = 1), PRESS_HIP_FAILED for
+ *                                    a refused read: an empty one, or rule 2 for the two methods that are not dstall_fz.
+ *                                    A stall stream's length is known only once its pieces are coded: the call runs the
+ *                                    inner range coder, all of a press but the last copy - that is its cost
+ *   press_hip_press_packed           the layout rules of (2) unchanged: out_off is written, no gaps beyond align, a read is
+ *                                    written iff out_off[r] + need[r] <= out_cap, nothing at or beyond out_cap.  The inner
+ *                                    coder runs once per call: the pieces' streams lie in library scratch, their lengths
+ *                                    give the layout, and the last kernel copies them to the laid-out offsets
+ *   press_hip_recode_*               every pair of the 19 + 24 + 3 ids, as source and as destination, the three among
+ *                                    themselves included: byte for byte depress followed by press.  press_hip_recode_fused
+ *                                    = 0 in both positions: the pieces are gathered from whole samples
+ *   press_hip_recode_degraded_*,     the degrade kernel runs between the halves; the stall is found on the DEGRADED
+ *   press_hip_verify_degraded_batch  samples; verify compares with D_bits of the originals, as for every method
+ *   press_hip_depress_pa_batch,      the streams are decoded into library scratch, then the converter, compare and CRC
+ *   _norm_batch, _chunks_batch,      kernels of the public methods run: floats, rows, first_bad and CRCs are bit for bit
+ *   press_hip_verify_batch,          those of the same reads held in any public method (press_hip_depress_pa_fused = 0)
+ *   press_hip_depress_crc_batch
+ *   every *_workspace_bytes          by the rules of the public methods, exact; press_hip_workspace_bytes(id) is never
+ *                                    below press_hip_stall_workspace_bytes(id - 96)
+ */
+enum { PRESS_HIP_SMETHOD_BASE = 96 };
+int press_hip_smethod(int stall_method);
+int press_hip_smethod_parts(int id, int *stall_method);
 
 /* ======================================================================= (3) BLOW5 files (host) */
 

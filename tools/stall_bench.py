@@ -2,7 +2,7 @@
 """The stall methods (press_hip_stall_press_batch / press_hip_stall_depress_batch), device resident, on bench.py's
 8192-read batch.
 
-    python3 tools/stall_bench.py [--reads 8192] [--calls 5] [--out FILE]
+    python3 tools/stall_bench.py [--reads 8192] [--calls 5] [--legs all|family|generic] [--out FILE]
 
 Whole calls between two HIP events.  Per stall method: the median press and depress times, the compressed total and ratio,
 the share of reads whose stream has a stall, the round trip checked.  In the same process and with the legs alternated
@@ -10,6 +10,14 @@ the share of reads whose stream has a stall, the round trip checked.  In the sam
 coder the stall methods are made of, and press_hip_signal_segments (cDNA preset) as a pure count, the segment pass.
 "sums" holds what the parts add up to: rccm_vbbe21_zd + the segment pass for rccm_svbbe21_zd and dstall_fz_1500, twice the
 coder + the segment pass for dstall_fz; "spread_ms" is the largest max - min of any leg over the rounds.  One JSON line.
+
+The generic calls with dstall_fz's method id (include/press_hip.h 2x), each against the route a caller had without it
+("generic": medians in "median_ms", bytes in "generic"):
+  recode_packed         press_hip_recode_packed(slow5_svb_zd -> dstall_fz) into an arena of the streams' own size, against
+  route_today           press_hip_depress_batch, press_hip_stall_press_batch into press_hip_stall_bound slots and a torch gather
+                        of the streams into a dense arena; arena bytes of both
+  press_sizes           press_hip_press_sizes(dstall_fz), against dstall_fz/press (press_hip_stall_press_batch)
+  verify_batch          press_hip_verify_batch(dstall_fz), against depress_equal: press_hip_stall_depress_batch and torch.equal
 """
 import argparse
 import json
@@ -51,10 +59,70 @@ def raw_piece(stream, n):
     return stored_raw(stream[pos + 4:pos + 4 + l0], n - sl - 1)
 
 
+def generic_legs(torch, press, b, legs, outs, lens, d_out_off, d_in_off):
+    """the legs of the generic calls with dstall_fz's id and of the routes they replace -> {name: fn}, "_bytes": the arena
+    figures, "_check": what the warm-up must have left"""
+    m, src = "dstall_fz", "slow5_svb_zd"
+    dev, R, total = b.dev, b.R, b.sig.numel()
+    # the BLOW5 fields of the batch
+    _, s_out, s_off, s_in = b.arena(torch, press, src)
+    s_len = torch.zeros(R, dtype=torch.int64, device=dev)
+    press.press_batch(src, b.sig, b.d_off, b.d_n, s_out, s_off, s_len)
+    # the generic route: the arena is as large as the streams (press_hip_recode_sizes says how large)
+    outn = torch.zeros(R, dtype=torch.int32, device=dev)
+    need = press.recode_sizes(src, m, s_out, s_in, s_len, b.d_n, b.d_off, outn, total_samples=total)
+    torch.cuda.synchronize()
+    assert bool((need > 0).all())
+    packed_bytes = int(need.sum())
+    p_out = torch.empty(packed_bytes, dtype=torch.uint8, device=dev)
+    p_off = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+    p_len = torch.zeros(R, dtype=torch.int64, device=dev)
+    # the route without it: samples, slots of press_hip_stall_bound bytes, a gather
+    caps = np.array([press.stall_bound(m, int(x)) for x in b.n], dtype=np.int64)
+    t_off_h = np.concatenate([[0], np.cumsum(caps)])
+    t_out = torch.empty(int(t_off_h[-1]) + 64, dtype=torch.uint8, device=dev)
+    t_off = torch.from_numpy(t_off_h).to(dev)
+    t_len = torch.zeros(R, dtype=torch.int64, device=dev)
+    dense = {}
+
+    def route_today():
+        press.depress_batch(src, s_out, s_in, s_len, b.d_back, b.d_off, b.d_n, b.d_outn)
+        press.stall_press_batch(m, b.d_back, b.d_off, b.d_n, t_out, t_off, t_len, None)
+        ends = torch.cumsum(t_len, 0)
+        shift = torch.repeat_interleave(t_off[:-1] - (ends - t_len), t_len)  # (the sum of t_len: a device-to-host read)
+        dense["out"] = t_out[torch.arange(shift.numel(), device=dev) + shift]
+        dense["off"] = ends - t_len
+
+    fb, von, nbad = (torch.zeros(k, dtype=torch.int32, device=dev) for k in (R, R, 1))
+    same = {}
+
+    def depress_equal():
+        press.stall_depress_batch(outs[m], d_in_off, lens[m], b.d_back, b.d_off, b.d_n, b.d_outn)
+        same["ok"] = torch.equal(b.d_back, b.sig) and torch.equal(b.d_outn, b.d_n)
+
+    def check():
+        assert int(p_off[-1]) == packed_bytes == dense["out"].numel(), "the two routes' arenas differ"
+        assert torch.equal(p_off[:-1], dense["off"]) and torch.equal(p_len, t_len) and torch.equal(p_out, dense["out"])
+        assert torch.equal(sizes["need"], lens[m]) and torch.equal(need, p_len)
+        assert int(nbad[0]) == 0 and bool((fb == -1).all()) and same["ok"]
+
+    sizes = {}
+    return {"recode_packed": lambda: press.recode_packed(src, m, s_out, s_in, s_len, b.d_n, b.d_off, p_out, p_off, p_len, outn,
+                                                         total_samples=total),
+            "route_today": route_today,
+            "press_sizes": lambda: sizes.__setitem__("need", press.press_sizes(m, b.sig, b.d_off, b.d_n)),
+            "verify_batch": lambda: press.verify_batch(m, outs[m], d_in_off, lens[m], b.sig, b.d_off, b.d_n, fb, von, nbad),
+            "depress_equal": depress_equal,
+            "_check": check,
+            "_bytes": {"source_bytes": int(s_len.sum()), "recode_packed_arena_bytes": packed_bytes,
+                       "route_today_arena_bytes": int(t_off_h[-1]) + packed_bytes, "route_today_slot_bytes": int(t_off_h[-1])}}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reads", type=int, default=8192)
     ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--legs", choices=("all", "family", "generic"), default="all")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -90,6 +158,12 @@ def main():
     for m in press.STALL_METHODS:
         legs[m + "/press"] = lambda m=m: press.stall_press_batch(m, b.sig, b.d_off, b.d_n, outs[m], d_out_off, lens[m], stall)
         legs[m + "/depress"] = lambda m=m: press.stall_depress_batch(outs[m], d_in_off, lens[m], b.d_back, b.d_off, b.d_n, b.d_outn)
+
+    if a.legs == "generic":  # (what the generic legs are compared with stays)
+        legs = {k: v for k, v in legs.items() if k in ("dstall_fz/press", "dstall_fz/depress")}
+    generic = {}
+    if a.legs != "family":
+        generic = generic_legs(torch, press, b, legs, outs, lens, d_out_off, d_in_off)
 
     result = {"reads": R, "samples": b.total_samples, "raw_bytes": b.raw_bytes, "calls": a.calls,
               "workspace_bytes": {m: press.stall_workspace_bytes(m, total, R) for m in press.STALL_METHODS}, "methods": {}}
@@ -136,6 +210,13 @@ def main():
                     lost += 1
             result["methods"][m]["reads_with_a_raw_piece_not_given_back"] = lost
 
+    if generic:
+        result["generic"] = generic.pop("_bytes")
+        for name, fn in generic.items():  # warm-up: every buffer reserved, the results checked
+            fn()
+            torch.cuda.synchronize()
+        generic.pop("_check")()
+        legs.update(generic)
     ms = {name: [] for name in legs}
     for _ in range(a.calls):
         for name, fn in legs.items():
@@ -148,10 +229,11 @@ def main():
     med = {name: float(np.median(np.array(v))) for name, v in ms.items()}
     result["median_ms"] = med
     result["spread_ms"] = max(float(max(v) - min(v)) for v in ms.values())
-    seg = med["segments_count"]
-    result["sums"] = {"rccm_svbbe21_zd/press": med[INNER + "/press"] + seg, "dstall_fz_1500/press": med[INNER + "/press"] + seg,
-                      "dstall_fz/press": 2 * med[INNER + "/press"] + seg,
-                      "depress": med[INNER + "/depress"]}
+    if a.legs != "generic":
+        seg = med["segments_count"]
+        result["sums"] = {"rccm_svbbe21_zd/press": med[INNER + "/press"] + seg, "dstall_fz_1500/press": med[INNER + "/press"] + seg,
+                          "dstall_fz/press": 2 * med[INNER + "/press"] + seg,
+                          "depress": med[INNER + "/depress"]}
     line = json.dumps(result)
     print(line)
     if a.out:
