@@ -115,6 +115,10 @@ PROTOS = {
     "press_hip_chunk_plan": (I, [P, U, U, U, P, P, P]),
     "press_hip_depress_chunks_batch": (I, [I] + IN + [P, Q, I, U, U, P, P, P, Q, P, P, P, I]),
     "press_hip_depress_chunks_workspace_bytes": (Q, [I, Q, U, U, U]),
+    "press_hip_signal_quantiles_ranged": (I, SIG + [P, P, P, U, P, I]),
+    "press_hip_signal_stats_ranged": (I, SIG + [P, P, I]),
+    "press_hip_depress_chunks_trimmed_batch": (I, [I] + IN + [P, Q, I, U, U, P, P, P, P, P, Q, P, P, P, P, P, P, P, I]),
+    "press_hip_depress_chunks_trimmed_workspace_bytes": (Q, [I, Q, U, U, U, I]),
     "press_hip_recode_batch": (I, RECODE + [P, P, P, P, P, I]),
     "press_hip_recode_workspace_bytes": (Q, [I, I, Q, U, I]),
     "press_hip_recode_fused": (I, [I, I]),

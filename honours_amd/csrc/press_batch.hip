@@ -31,6 +31,23 @@ static int args_ok(int m1, int m2, bool null_arg, uint32_t nreads, const void *d
 	return 0;
 }
 
+// The parameter checks of the two detectors, for every call that takes their parameters (segments, adaptor, prefix, the
+// trimmed chunk rows): 0, or EARG with the text in last_error
+static int jnn_params_ok(const press_hip_jnn_params &p)
+{
+	if (p.window < 1 || p.corrector < 0 || p.error < 0 || p.seg_dist < 0 || !std::isfinite(p.stall_len))
+		return set_error(PRESS_HIP_EARG, "jnn parameters: window %d >= 1, corrector %d, error %d, seg_dist %d >= 0, a finite stall_len",
+				 p.window, p.corrector, p.error, p.seg_dist);
+	return 0;
+}
+
+static int jnn2_params_ok(const press_hip_jnn2_params &p)
+{
+	if (p.window < 1 || p.window > 8192)
+		return set_error(PRESS_HIP_EARG, "window = %d: 1 .. 8192 (the window sums stay below 2^24)", p.window);
+	return 0;
+}
+
 static int align_ok(uint32_t align)
 {
 	if (align == 0 || align > 4096 || (align & (align - 1)))
@@ -510,19 +527,137 @@ extern "C" int press_hip_depress_chunks_batch(int method, const uint8_t *in, con
 	return 0;
 }
 
+// Trimmed chunk rows (include/press_hip.h 2y): the chunk call with a range per read - the caller's, or one a detector finds
+// in the decoded samples - and the row plan made on the device (launch_depress_chunks_trimmed).  Host pointers: the
+// rows of the untrimmed plan bound what can be written, so the arena and the row tables are staged at min(that,
+// nrows_cap); row_first comes back first and says how much of them to fetch.
+static_assert((int) PRESS_HIP_TRIM_RANGE == (int) PRESS_TRIM_RANGE && (int) PRESS_HIP_TRIM_ADAPTOR == (int) PRESS_TRIM_ADAPTOR &&
+		      (int) PRESS_HIP_TRIM_SEGMENT == (int) PRESS_TRIM_SEGMENT,
+	      "the trim modes");
+
+extern "C" int press_hip_depress_chunks_trimmed_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+						      uint32_t nreads, void *rows, uint64_t nrows_cap, int dtype, uint32_t T, uint32_t overlap,
+						      uint64_t *row_first, uint32_t *row_read, uint32_t *row_start, const uint64_t *off,
+						      const uint32_t *n, uint64_t total_samples, const press_hip_trim *trim, const uint32_t *range,
+						      const float *seg_cal, uint32_t *cut, const press_hip_scale_rule *rule, int32_t *q,
+						      uint32_t *out_n, int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(method, NONE, !row_first || (nreads && (!in || !in_off || !in_len || !off || !n || !out_n)) || (!rows && nrows_cap),
+			 nreads, device_resident ? rows : nullptr, "rows");
+	if (rc)
+		return rc;
+	if (dtype != PRESS_HIP_F32 && dtype != PRESS_HIP_F16 && dtype != PRESS_HIP_BF16)
+		return set_error(PRESS_HIP_EARG, "dtype %d: PRESS_HIP_F32, PRESS_HIP_F16 or PRESS_HIP_BF16", dtype);
+	if (T == 0 || T % 8 || overlap >= T)
+		return set_error(PRESS_HIP_EARG, "T must be a positive multiple of 8 and overlap below T");
+	if (rule && !scale_rule_ok(rule))
+		return set_error(PRESS_HIP_EARG, "the scale rule is not valid (ranks num <= den, den > 0; finite floats; scale_min > 0)");
+	TrimArgs t = {};
+	t.mode = trim ? trim->mode : PRESS_TRIM_RANGE;
+	if (t.mode == PRESS_TRIM_ADAPTOR) {
+		const press_hip_jnn2_params &p = trim->adaptor;
+		if ((rc = jnn2_params_ok(p)))
+			return rc;
+		t.adaptor = { p.std_scale, p.seg_dist, p.window, p.hi_thresh, p.lo_thresh };
+	} else if (t.mode == PRESS_TRIM_SEGMENT) {
+		const press_hip_jnn_params &p = trim->seg;
+		if ((rc = jnn_params_ok(p)))
+			return rc;
+		t.seg = { p.std_scale, p.corrector, p.seg_dist, p.window, p.stall_len, p.error, p.top, p.bot };
+	} else if (t.mode != PRESS_TRIM_RANGE) {
+		return set_error(PRESS_HIP_EARG, "trim mode %d: PRESS_HIP_TRIM_RANGE, _ADAPTOR or _SEGMENT", t.mode);
+	}
+	t.min_keep = trim && t.mode != PRESS_TRIM_RANGE ? trim->min_keep : 0;
+	if ((rc = device_ready(method, NONE)))
+		return rc;
+	hipStream_t s = g.stream();
+	if (nreads == 0) { // (the plan of no reads: one zero)
+		if (device_resident)
+			HIPCHK(hipMemsetAsync(row_first, 0, 8, s));
+		else
+			row_first[0] = 0;
+		return 0;
+	}
+	const size_t es = dtype == PRESS_HIP_F32 ? 4 : 2;
+	uint64_t staged = 0; // host pointers: the rows that can be written
+	if (!device_resident) {
+		for (uint32_t r = 0; r < nreads; r++)
+			staged += chunk_rows_of(n[r], T, T - overlap);
+		staged = staged < nrows_cap ? staged : nrows_cap;
+	}
+	const ScratchPlan plan = make_chunks_trimmed_plan(method, total_samples, nreads, t.mode, !device_resident, staged * T * es, staged);
+	if ((rc = plan.reserve()))
+		return rc;
+	DecodeArgs a;
+	plan.bind(a);
+	a.nreads = nreads;
+	ChunkArgs c = { rows, nrows_cap, dtype, T, overlap, row_first, total_samples, rule, q };
+	t.range = t.mode == PRESS_TRIM_RANGE ? range : nullptr;
+	t.seg_cal = t.mode == PRESS_TRIM_SEGMENT ? seg_cal : nullptr;
+	t.cut = cut;
+	t.row_read = row_read;
+	t.row_start = row_start;
+	const StreamsIn host = { in, in_off, in_len, off, n, out_n, (int16_t *) plan.ptr(&Ctx::rsig) };
+	StreamsIn io = host;
+	Staged st(nreads, s);
+	if (!device_resident) {
+		if ((rc = st.streams(host, total_samples, false, g.arena, g.arena_off, io)))
+			return rc;
+		if (t.range) {
+			HIPCHK(hipMemcpyAsync(g.px_range.p, t.range, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+			t.range = (const uint32_t *) g.px_range.p;
+		}
+		if (t.seg_cal) {
+			HIPCHK(hipMemcpyAsync(g.sg_cal.p, t.seg_cal, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+			t.seg_cal = (const float *) g.sg_cal.p;
+		}
+		c.rows = g.ch_rows.p;
+		c.nrows_cap = staged;
+		c.row_first = (const uint64_t *) g.tr_first.p;
+		c.q = (int32_t *) g.st_stats.p;
+		t.cut = (uint32_t *) g.tr_user.p;
+		t.row_read = (uint32_t *) g.tr_read.p;
+		t.row_start = (uint32_t *) g.tr_start.p;
+	}
+	bind_io(a, io);
+	if ((rc = launch_depress_chunks_trimmed(plan, a, c, t, s)) || device_resident)
+		return rc;
+	// the plan first: it says how many rows were written; then they, the row tables, the cuts, q and out_n in one go
+	HIPCHK(hipMemcpyAsync(row_first, g.tr_first.p, ((size_t) nreads + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	const uint64_t written = row_first[nreads] < staged ? row_first[nreads] : staged;
+	if (q)
+		HIPCHK(hipMemcpyAsync(q, g.st_stats.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	if (cut)
+		HIPCHK(hipMemcpyAsync(cut, g.tr_user.p, (size_t) nreads * 8, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(out_n, g.outn.p, (size_t) nreads * 4, hipMemcpyDeviceToHost, s));
+	if (written) {
+		HIPCHK(hipMemcpyAsync(rows, g.ch_rows.p, written * T * es, hipMemcpyDeviceToHost, s));
+		if (row_read)
+			HIPCHK(hipMemcpyAsync(row_read, g.tr_read.p, written * 4, hipMemcpyDeviceToHost, s));
+		if (row_start)
+			HIPCHK(hipMemcpyAsync(row_start, g.tr_start.p, written * 4, hipMemcpyDeviceToHost, s));
+	}
+	HIPCHK(hipStreamSynchronize(s));
+	return 0;
+}
+
 // ------------------------------------------------------------------ statistics of samples that are already there
 
 // What the stats calls share: the scratch of a call that decodes nothing (rows_bytes / state_bytes: its count rows and
 // pick state), the samples - staged, with result_bytes of g.st_stats for what comes back, unless device resident - the
 // argument block, and the tile table enqueued.
 static int stats_begin(const SamplesIn &host, uint64_t total_samples, bool device_resident, size_t rows_bytes, size_t state_bytes,
-		       size_t result_bytes, Staged &st, DecodeArgs &a)
+		       size_t result_bytes, Staged &st, DecodeArgs &a, bool with_range = false)
 {
 	int rc;
 	ScratchPlan plan = make_tiles_plan(total_samples, st.nreads);
 	plan.need(&Ctx::st_rows, rows_bytes).need(&Ctx::st_read, state_bytes);
 	if (!device_resident)
 		plan.need(&Ctx::st_stats, result_bytes);
+	if (!device_resident && with_range) // (the ranged forms: the caller's ranges, staged)
+		plan.need(&Ctx::px_range, (size_t) st.nreads * 8);
 	if ((rc = plan.reserve()))
 		return rc;
 	plan.bind(a);
@@ -589,6 +724,84 @@ extern "C" int press_hip_signal_quantiles(const int16_t *sig, const uint64_t *of
 		return rc;
 	launch_signal_quantiles(a, (const uint2 *) g.pa_tile.p, (const uint32_t *) g.pa_ctl.p, g.st_read.p, (uint32_t *) g.st_rows.p, rank_num,
 				rank_den, nq, device_resident ? q : (int32_t *) g.st_stats.p, nullptr, nullptr, s);
+	if ((rc = launch_status()) || device_resident)
+		return rc;
+	return st.fetch_tables({ { q, g.st_stats.p, (size_t) nreads * nq * 4 } });
+}
+
+// The ranged forms (include/press_hip.h 2y): the same checks, staging and launch counts; the kernels clamp the range.
+// Host pointers: the range is staged in g.px_range (stats_begin with_range).  *drange: what the kernels read (NULL: whole reads)
+static int stage_range(const uint32_t *range, uint32_t nreads, bool device_resident, hipStream_t s, const uint32_t **drange)
+{
+	*drange = range;
+	if (device_resident || !range)
+		return 0;
+	HIPCHK(hipMemcpyAsync(g.px_range.p, range, (size_t) nreads * 8, hipMemcpyHostToDevice, s));
+	*drange = (const uint32_t *) g.px_range.p;
+	return 0;
+}
+
+extern "C" int press_hip_signal_stats_ranged(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+					     uint64_t total_samples, const uint32_t *range, int32_t *stats, int device_resident)
+{
+	API_LOCK;
+	int rc = args_ok(NONE, NONE, nreads && (!sig || !off || !n || !stats), nreads, device_resident ? sig : nullptr, "sig");
+	if (rc || (rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	Staged st(nreads, s);
+	DecodeArgs a;
+	const uint32_t *dr;
+	if ((rc = stats_begin({ sig, off, n }, total_samples, device_resident, stat_rows_bytes(nreads), stat_state_bytes(nreads),
+			      (size_t) nreads * 8, st, a, range != nullptr)) ||
+	    (rc = stage_range(range, nreads, device_resident, s, &dr)))
+		return rc;
+	int32_t *out = device_resident ? stats : (int32_t *) g.st_stats.p;
+	if (dr)
+		launch_signal_stats_ranged(a, dr, (const uint2 *) g.pa_tile.p, (const uint32_t *) g.pa_ctl.p, g.st_read.p, (uint32_t *) g.st_rows.p,
+					   out, nullptr, s);
+	else
+		stats_launch(a, out, nullptr, s);
+	if ((rc = launch_status()) || device_resident)
+		return rc;
+	return st.fetch_tables({ { stats, g.st_stats.p, (size_t) nreads * 8 } });
+}
+
+extern "C" int press_hip_signal_quantiles_ranged(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+						 uint64_t total_samples, const uint32_t *range, const uint32_t *rank_num,
+						 const uint32_t *rank_den, uint32_t nq, int32_t *q, int device_resident)
+{
+	API_LOCK;
+	if (nq < 1 || nq > QMAX) // (it sizes the ranks' tables: before them)
+		return set_error(PRESS_HIP_EARG, "nq = %u: 1 .. %u quantiles", nq, QMAX);
+	int rc = args_ok(NONE, NONE, !rank_num || !rank_den || (nreads && (!sig || !off || !n || !q)), nreads,
+			 device_resident ? sig : nullptr, "sig");
+	if (rc)
+		return rc;
+	for (uint32_t i = 0; i < nq; i++)
+		if (rank_den[i] == 0 || rank_num[i] > rank_den[i])
+			return set_error(PRESS_HIP_EARG, "rank %u: %u / %u is not in [0, 1]", i, rank_num[i], rank_den[i]);
+	if ((rc = device_ready(NONE, NONE)))
+		return rc;
+	if (nreads == 0)
+		return 0;
+	hipStream_t s = g.stream();
+	Staged st(nreads, s);
+	DecodeArgs a;
+	const uint32_t *dr;
+	if ((rc = stats_begin({ sig, off, n }, total_samples, device_resident, std::max(stat_rows_bytes(nreads), quant_rows_bytes(nreads, nq)),
+			      std::max(stat_state_bytes(nreads), quant_state_bytes(nreads)), (size_t) nreads * nq * 4, st, a, range != nullptr)) ||
+	    (rc = stage_range(range, nreads, device_resident, s, &dr)))
+		return rc;
+	int32_t *out = device_resident ? q : (int32_t *) g.st_stats.p;
+	if (dr)
+		launch_signal_quantiles_ranged(a, dr, (const uint2 *) g.pa_tile.p, (const uint32_t *) g.pa_ctl.p, g.st_read.p,
+					       (uint32_t *) g.st_rows.p, rank_num, rank_den, nq, out, nullptr, nullptr, s);
+	else
+		launch_signal_quantiles(a, (const uint2 *) g.pa_tile.p, (const uint32_t *) g.pa_ctl.p, g.st_read.p, (uint32_t *) g.st_rows.p,
+					rank_num, rank_den, nq, out, nullptr, nullptr, s);
 	if ((rc = launch_status()) || device_resident)
 		return rc;
 	return st.fetch_tables({ { q, g.st_stats.p, (size_t) nreads * nq * 4 } });
@@ -777,9 +990,8 @@ extern "C" int press_hip_signal_segments(const int16_t *sig, const uint64_t *off
 			 device_resident ? sig : nullptr, "sig");
 	if (rc)
 		return rc;
-	if (prm->window < 1 || prm->corrector < 0 || prm->error < 0 || prm->seg_dist < 0 || !std::isfinite(prm->stall_len))
-		return set_error(PRESS_HIP_EARG, "jnn parameters: window %d >= 1, corrector %d, error %d, seg_dist %d >= 0, a finite stall_len",
-				 prm->window, prm->corrector, prm->error, prm->seg_dist);
+	if ((rc = jnn_params_ok(*prm)))
+		return rc;
 	if ((rc = device_ready(NONE, NONE)))
 		return rc;
 	const SegParams p = { prm->std_scale, prm->corrector, prm->seg_dist, prm->window, prm->stall_len, prm->error, prm->top, prm->bot };
@@ -803,8 +1015,8 @@ extern "C" int press_hip_signal_adaptor(const int16_t *sig, const uint64_t *off,
 	int rc = args_ok(NONE, NONE, !prm || (nreads && (!sig || !off || !n || !pair)), nreads, device_resident ? sig : nullptr, "sig");
 	if (rc)
 		return rc;
-	if (prm->window < 1 || prm->window > 8192)
-		return set_error(PRESS_HIP_EARG, "window = %d: 1 .. 8192 (the window sums stay below 2^24)", prm->window);
+	if ((rc = jnn2_params_ok(*prm)))
+		return rc;
 	if ((rc = device_ready(NONE, NONE)))
 		return rc;
 	if (nreads == 0)
@@ -891,11 +1103,8 @@ extern "C" int press_hip_signal_prefix(const int16_t *sig, const uint64_t *off, 
 	if (rc)
 		return rc;
 	const press_hip_jnn_params &pa = prm->polya;
-	if (pa.window < 1 || pa.corrector < 0 || pa.error < 0 || pa.seg_dist < 0 || !std::isfinite(pa.stall_len))
-		return set_error(PRESS_HIP_EARG, "jnn parameters: window %d >= 1, corrector %d, error %d, seg_dist %d >= 0, a finite stall_len",
-				 pa.window, pa.corrector, pa.error, pa.seg_dist);
-	if (prm->adaptor.window < 1 || prm->adaptor.window > 8192)
-		return set_error(PRESS_HIP_EARG, "window = %d: 1 .. 8192 (the window sums stay below 2^24)", prm->adaptor.window);
+	if ((rc = jnn_params_ok(pa)) || (rc = jnn2_params_ok(prm->adaptor)))
+		return rc;
 	if (stat && nreads > 0x7FFFFFFFu)
 		return set_error(PRESS_HIP_EARG, "nreads = %u with stat: at most 2^31 - 1 (two ranges per read)", nreads);
 	if ((rc = device_ready(NONE, NONE)))

@@ -71,6 +71,7 @@ struct Ctx {
 	DevBuf pa_tile, pa_ctl, pa_cal, pa_out; // picoamperes: the converter's tile table and its count; host path: the staged calibration, the float arena
 	DevBuf st_rows, st_read, st_cal, st_stats; // median / MAD: the reads' count rows, the pick state, the normaliser's two floats; host path: stats
 	DevBuf ch_rows, ch_first; // chunk rows, host path: the row arena, the staged row_first
+	DevBuf tr_cut, tr_cnt, tr_det, tr_first, tr_read, tr_start, tr_user; // trimmed chunk rows: the cuts, the detectors' sample counts and results; host path: row_first, row_read, row_start, the caller's cut
 	DevBuf vf_raw, vf_out; // verify / CRC-32: a word per read between the two kernels; host path: the staged crc or first_bad, and nbad
 	DevBuf ev_state, ev_cal, ev_first, ev_cnt, ev_out; // events: count and path per read; host path: the staged calibration, ev_first, ev_count, the records
 	DevBuf sg_state, sg_cal, sg_first, sg_cnt, sg_thr, sg_out; // jnn segments: count and thresholds per read; host path: the staged calibration, seg_first, seg_count, thr, the records (the adaptor: the pairs)
@@ -378,6 +379,13 @@ ScratchPlan make_norm_plan(int method, uint64_t total_samples, uint32_t nreads, 
 // of the float arena
 ScratchPlan make_chunks_plan(int method, uint64_t total_samples, uint32_t nreads, bool host, uint64_t rows_bytes);
 
+// press_hip_depress_chunks_trimmed_batch: make_chunks_plan's rows (never less: the workspace figure rests on it), the cuts,
+// the scan's two tables and, in a detector mode, the counts the detector walks, its results and (SEGMENT) its state; host
+// pointers: the row arena at rows_bytes, the three row tables at table_rows entries, row_first, the staged range and
+// seg_cal, the cuts on their way back
+ScratchPlan make_chunks_trimmed_plan(int method, uint64_t total_samples, uint32_t nreads, int mode, bool host, uint64_t rows_bytes,
+				     uint64_t table_rows);
+
 // press_hip_verify_batch / press_hip_depress_crc_batch: the decode plan of the method, the samples, the tile table and a
 // word per read; host pointers: the staged per-read result and nbad (vf_out: nreads words, then nbad).  method < 0
 // (press_hip_signal_crc32): no decode and no samples, the tile table and the words alone
@@ -445,6 +453,19 @@ struct ChunkArgs {
 	int32_t *q;                       // 2 per read, or NULL
 };
 int launch_depress_chunks(const ScratchPlan &p, const DecodeArgs &a, const ChunkArgs &c, hipStream_t s);
+// p from make_chunks_trimmed_plan; c.row_first is WRITTEN (device memory, nreads + 1).  What the caller has checked: the
+// mode and the detector's parameters.  Every pointer is device memory
+struct TrimArgs {
+	int mode;             // PRESS_TRIM_*
+	uint32_t min_keep;
+	Seg2Params adaptor;   // mode ADAPTOR
+	SegParams seg;        // mode SEGMENT
+	const uint32_t *range; // mode RANGE: 2 per read, or NULL
+	const float *seg_cal;  // mode SEGMENT: 2 per read, or NULL (the raw domain)
+	uint32_t *cut;         // 2 per read, or NULL
+	uint32_t *row_read, *row_start; // c.nrows_cap each, or NULL
+};
+int launch_depress_chunks_trimmed(const ScratchPlan &p, const DecodeArgs &a, const ChunkArgs &c, const TrimArgs &t, hipStream_t s);
 // p from make_verify_plan.  launch_signal_crc: a.sig the caller's samples, a.out_n their counts.  launch_depress_crc and
 // launch_verify: a.sig the samples' scratch; sig: the samples the streams are meant to hold, at a.off[]
 int launch_signal_crc(const ScratchPlan &p, const DecodeArgs &a, uint32_t *crc, hipStream_t s);

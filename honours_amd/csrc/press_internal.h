@@ -447,6 +447,10 @@ uint64_t stat_rows_bytes(uint32_t nreads);
 uint64_t stat_state_bytes(uint32_t nreads);
 void launch_signal_stats(const DecodeArgs &a, const uint2 *tiles, const uint32_t *ntiles, void *state, uint32_t *rows,
 			 int32_t *stats, float *cal, hipEvent_t *ev, hipStream_t s);
+// ... of the samples [a', b') of each read alone: range is 2 words per read in device memory, clamped by the kernels
+// (include/press_hip.h 2y); the same eight launches
+void launch_signal_stats_ranged(const DecodeArgs &a, const uint32_t *range, const uint2 *tiles, const uint32_t *ntiles, void *state,
+				uint32_t *rows, int32_t *stats, float *cal, hipStream_t s);
 // press_quant.hip: nq (1 .. QMAX) quantiles of a.out_n[r] samples at a.sig + a.off[r] over launch_pa_tiles' table (four
 // launches whatever nq is); q: nq int32 per read, may be NULL; cal (nq == 2, else ignored): NULL, or the two floats per
 // read that `rule` makes of {q[0], q[1]} (press_hip_scale_cal)
@@ -459,11 +463,26 @@ uint64_t quant_state_bytes(uint32_t nreads);
 void launch_signal_quantiles(const DecodeArgs &a, const uint2 *tiles, const uint32_t *ntiles, void *state, uint32_t *rows,
 			     const uint32_t *num, const uint32_t *den, uint32_t nq, int32_t *q, float *cal, const ScaleRule *rule,
 			     hipStream_t s);
+void launch_signal_quantiles_ranged(const DecodeArgs &a, const uint32_t *range, const uint2 *tiles, const uint32_t *ntiles, void *state,
+				    uint32_t *rows, const uint32_t *num, const uint32_t *den, uint32_t nq, int32_t *q, float *cal,
+				    const ScaleRule *rule, hipStream_t s);
 // press_rows.hip: the planned rows below nrows_cap, [*, T] of dtype, from the samples at a.sig + a.off[r] (a.nsamp: the
 // rooms the plan was made of, a.out_n: the decoded counts) and two floats per read
 enum { PRESS_ROWS_F32 = 0, PRESS_ROWS_F16 = 1, PRESS_ROWS_BF16 = 2 }; // PRESS_HIP_F32 / F16 / BF16
 void launch_chunk_rows(const DecodeArgs &a, const float *cal, const uint64_t *row_first, void *rows, uint64_t nrows_cap, int dtype,
 		       uint32_t T, uint32_t overlap, uint64_t total_samples, hipStream_t s);
+// ... of press_hip_depress_chunks_trimmed_batch: cut (2 words per read, launch_trim_plan's) and row_first in device memory;
+// row_read / row_start: NULL, or nrows_cap words each
+void launch_chunk_rows_ranged(const DecodeArgs &a, const uint32_t *cut, const float *cal, const uint64_t *row_first, void *rows,
+			      uint64_t nrows_cap, int dtype, uint32_t T, uint32_t overlap, uint64_t total_samples, uint32_t *row_read,
+			      uint32_t *row_start, hipStream_t s);
+// press_trim.hip: cnt[r] = min(a.out_n[r], a.nsamp[r]), 0 for a refused read; and the cuts, then the row plan over their
+// lengths (det: launch_adaptor's pairs or launch_segments_first's records, unused in mode RANGE; need, slot: nreads + 1
+// words of 64 bits)
+enum { PRESS_TRIM_RANGE = 0, PRESS_TRIM_ADAPTOR = 1, PRESS_TRIM_SEGMENT = 2 }; // PRESS_HIP_TRIM_*
+void launch_trim_counts(const DecodeArgs &a, uint32_t *cnt, hipStream_t s);
+void launch_trim_plan(const DecodeArgs &a, int mode, const uint32_t *range, const void *det, uint32_t min_keep, uint32_t T, uint32_t overlap,
+		      uint32_t *cut, uint32_t *user, uint64_t *need, uint64_t *slot, uint64_t *row_first, hipStream_t s);
 // press_verify.hip, over launch_pa_tiles' table of the same batch (a.nsamp: the rooms, a.out_n: the counts):
 // crc[r] = zlib's CRC-32 of the a.out_n[r] samples at a.sig + a.off[r], 0 for a refused read; raw: one word per read
 void launch_crc(const DecodeArgs &a, const uint2 *tiles, const uint32_t *ntiles, uint32_t *raw, uint32_t *crc, hipStream_t s);
@@ -517,7 +536,7 @@ void launch_adaptor(const int16_t *sig, const uint64_t *off, const uint32_t *n, 
 		    float *thr, hipStream_t s);
 // ... and segs[0] alone, in one launch (the stall methods): first[r] = { start, end }, start = STALL_NOSEG: no segment
 void launch_segments_first(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const SegParams &p, void *state,
-			   void *first, hipStream_t s);
+			   void *first, hipStream_t s, const float *cal = nullptr);
 // press_ranges.hip: mean, deviation and median (12 bytes) of range i of read i >> shift, a wave per range (include/press_hip.h,
 // press_hip_signal_range_stats); range NULL (whole reads), or 2 * nranges words; cal NULL: the raw domain.  launch_prefix,
 // behind launch_adaptor on the same stream (press_hip_signal_prefix): out 16 bytes per read, thr NULL or 2 * nreads, and

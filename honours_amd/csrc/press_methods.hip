@@ -284,6 +284,25 @@ ScratchPlan make_chunks_plan(int method, uint64_t total_samples, uint32_t nreads
 	return p;
 }
 
+// Trimmed chunk rows: the chunk call's plan, the cuts and the tables of the scan that makes row_first; a detector mode adds
+// what its kernel reads and writes
+ScratchPlan make_chunks_trimmed_plan(int method, uint64_t total_samples, uint32_t nreads, int mode, bool host, uint64_t rows_bytes,
+				     uint64_t table_rows)
+{
+	ScratchPlan p = make_chunks_plan(method, total_samples, nreads, false, 0);
+	const size_t nr = (size_t) nreads + 1;
+	p.need(&Ctx::tr_cut, nr * 8).need(&Ctx::pneed, nr * 8).need(&Ctx::pslot, nr * 8);
+	if (mode != PRESS_TRIM_RANGE)
+		p.need(&Ctx::tr_cnt, nr * 4).need(&Ctx::tr_det, nr * 8);
+	if (mode == PRESS_TRIM_SEGMENT)
+		p.need(&Ctx::sg_state, segments_state_bytes(nreads));
+	if (host)
+		p.need(&Ctx::st_stats, (size_t) nreads * 8).need(&Ctx::tr_first, nr * 8).need(&Ctx::ch_rows, rows_bytes + 64)
+			.need(&Ctx::tr_read, table_rows * 4 + 4).need(&Ctx::tr_start, table_rows * 4 + 4).need(&Ctx::tr_user, nr * 8)
+			.need(&Ctx::px_range, nr * 8).need(&Ctx::sg_cal, nr * 8);
+	return p;
+}
+
 // Verify and CRC-32: the general picoampere plan (decode, samples, tile table) for every method, and a word per read
 ScratchPlan make_verify_plan(int method, uint64_t total_samples, uint32_t nreads, bool host)
 {
@@ -552,6 +571,17 @@ extern "C" uint64_t press_hip_depress_chunks_workspace_bytes(int method, uint64_
 	if (!method_ok(method) || T == 0 || T % 8 || overlap >= T)
 		return 0;
 	return plan_bytes(make_chunks_plan(method, total_samples, nreads, false, 0).merge(make_plan(method, total_samples, nreads, false)),
+			  is_shuff(method));
+}
+
+// ... and what the device-resident press_hip_depress_chunks_trimmed_batch keeps in `mode`
+extern "C" uint64_t press_hip_depress_chunks_trimmed_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads, uint32_t T,
+								     uint32_t overlap, int mode)
+{
+	API_LOCK;
+	if (!method_ok(method) || T == 0 || T % 8 || overlap >= T || mode < PRESS_TRIM_RANGE || mode > PRESS_TRIM_SEGMENT)
+		return 0;
+	return plan_bytes(make_chunks_trimmed_plan(method, total_samples, nreads, mode, false, 0, 0).merge(make_plan(method, total_samples, nreads, false)),
 			  is_shuff(method));
 }
 
@@ -962,6 +992,42 @@ int ph::launch_depress_chunks(const ScratchPlan &p, const DecodeArgs &a, const C
 		launch_signal_stats(a, tiles, ntiles, p.ptr(&Ctx::st_read), (uint32_t *) p.ptr(&Ctx::st_rows), c.q, cal, nullptr, s);
 	}
 	launch_chunk_rows(a, cal, c.row_first, c.rows, c.nrows_cap, c.dtype, c.T, c.overlap, c.total_samples, s);
+	return launch_status();
+}
+
+// The decode and the tile table; the detector of the mode over the decoded counts; the cuts and the row plan; the
+// calibration over the cuts (launch_depress_chunks' two ways, ranged); the ranged row writer.  Nothing waits for the host
+// beyond what launch_depress does for the zstd kinds.
+int ph::launch_depress_chunks_trimmed(const ScratchPlan &p, const DecodeArgs &a, const ChunkArgs &c, const TrimArgs &t, hipStream_t s)
+{
+	const int rc = launch_depress(p, a, s);
+	if (rc)
+		return rc;
+	uint2 *tiles = (uint2 *) p.ptr(&Ctx::pa_tile);
+	uint32_t *ntiles = (uint32_t *) p.ptr(&Ctx::pa_ctl);
+	float *cal = (float *) p.ptr(&Ctx::st_cal);
+	uint32_t *cut = (uint32_t *) p.ptr(&Ctx::tr_cut);
+	void *det = p.ptr(&Ctx::tr_det);
+	launch_pa_tiles(a, tiles, ntiles, s);
+	if (t.mode != PRESS_TRIM_RANGE) {
+		uint32_t *cnt = (uint32_t *) p.ptr(&Ctx::tr_cnt);
+		launch_trim_counts(a, cnt, s);
+		if (t.mode == PRESS_TRIM_ADAPTOR)
+			launch_adaptor(a.sig, a.off, cnt, a.nreads, t.adaptor, (int32_t *) det, nullptr, s);
+		else
+			launch_segments_first(a.sig, a.off, cnt, a.nreads, t.seg, p.ptr(&Ctx::sg_state), det, s, t.seg_cal);
+	}
+	launch_trim_plan(a, t.mode, t.range, det, t.min_keep, c.T, c.overlap, cut, t.cut, (uint64_t *) p.ptr(&Ctx::pneed),
+			 (uint64_t *) p.ptr(&Ctx::pslot), (uint64_t *) c.row_first, s);
+	if (c.rule) {
+		const uint32_t num[2] = { c.rule->lo_num, c.rule->hi_num }, den[2] = { c.rule->lo_den, c.rule->hi_den };
+		const ScaleRule ru = { c.rule->shift_mul, c.rule->shift_min, c.rule->scale_mul, c.rule->scale_min };
+		launch_signal_quantiles_ranged(a, cut, tiles, ntiles, p.ptr(&Ctx::st_read), (uint32_t *) p.ptr(&Ctx::st_rows), num, den, 2, c.q, cal,
+					       &ru, s);
+	} else {
+		launch_signal_stats_ranged(a, cut, tiles, ntiles, p.ptr(&Ctx::st_read), (uint32_t *) p.ptr(&Ctx::st_rows), c.q, cal, s);
+	}
+	launch_chunk_rows_ranged(a, cut, cal, c.row_first, c.rows, c.nrows_cap, c.dtype, c.T, c.overlap, c.total_samples, t.row_read, t.row_start, s);
 	return launch_status();
 }
 

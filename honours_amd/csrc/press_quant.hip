@@ -36,10 +36,14 @@ struct QRead { // per read, between the launches
 // runs of one digit and adds a run with one ds_add per row; lanes pick a copy of the counters by their id.  LOW: NQ rows
 // (1, 2 or 4; nq = 3 runs as 4 with a row nobody matches) and 16 / NQ copies of each; a run is one of equal low digit
 // AND equal set of matching ranks.
-template <int NQ, bool LOW>
+// RANGED (press_hip_signal_quantiles_ranged, the trimmed chunk call): the samples [a', b') of the read alone, as
+// k_stat_count's - the room's tiles and groups, the two edge groups masked per sample (the range: a trailing
+// parameter pack, empty or one `const uint32_t *`, as there).
+template <int NQ, bool LOW, class... R>
 __global__ __launch_bounds__(256) void k_q_count(const int16_t *sig, const uint64_t *off, const uint32_t *out_n, const uint2 *tiles,
-						  const uint32_t *ntiles, const QRead *st, uint32_t *rows, uint32_t nq)
+						  const uint32_t *ntiles, const QRead *st, uint32_t *rows, uint32_t nq, R... range)
 {
+	constexpr bool RANGED = sizeof...(R) != 0;
 	constexpr uint32_t COPIES = Q_ROWCOPIES / NQ;
 	__shared__ uint32_t s_h[Q_ROWCOPIES * Q_STRIDE];
 	if (blockIdx.x >= uni(*ntiles))
@@ -49,7 +53,16 @@ __global__ __launch_bounds__(256) void k_q_count(const int16_t *sig, const uint6
 	const uint64_t first = (uint64_t) j * CHUNK;
 	if (on == Q_FAIL || first >= on)
 		return;
-	const uint64_t end = first + CHUNK < on ? first + CHUNK : on;
+	uint64_t end = first + CHUNK < on ? first + CHUNK : on;
+	uint32_t lo = 0;
+	if constexpr (RANGED) {
+		const uint2 ab = range_clamp(range..., r, on);
+		lo = uni(ab.x);
+		const uint32_t hi = uni(ab.y);
+		if (lo >= hi || first >= hi || first + CHUNK <= lo)
+			return;
+		end = first + CHUNK < hi ? first + CHUNK : hi;
+	}
 	for (uint32_t i = threadIdx.x; i < Q_ROWCOPIES * Q_STRIDE; i += 256)
 		s_h[i] = 0;
 	__syncthreads();
@@ -70,9 +83,12 @@ __global__ __launch_bounds__(256) void k_q_count(const int16_t *sig, const uint6
 				atomicAdd(&my[i * Q_STRIDE + (tok & 255u)], cnt);
 	};
 	for (uint64_t i = first + threadIdx.x * 8; i < end; i += 256 * 8) {
+		if (RANGED && i + 8 <= lo)
+			continue;
 		const uint4 q = ld16_stream(in + i);
 		const uint32_t v[4] = { q.x, q.y, q.z, q.w };
 		const uint32_t nv = end - i < 8 ? (uint32_t) (end - i) : 8u;
+		const uint32_t skip = RANGED && lo > i ? (uint32_t) (lo - i) : 0u; // (the group that holds a')
 		uint32_t cur = Q_NONE, cnt = 0;
 #pragma unroll
 		for (int e = 0; e < 8; e++) {
@@ -88,7 +104,7 @@ __global__ __launch_bounds__(256) void k_q_count(const int16_t *sig, const uint6
 			} else {
 				d = key >> 8;
 			}
-			if ((uint32_t) e >= nv)
+			if ((uint32_t) e >= nv || (RANGED && (uint32_t) e < skip))
 				d = Q_NONE;
 			if (d != cur) {
 				if (cur != Q_NONE)
@@ -156,8 +172,10 @@ struct QRanks {
 // One wave per read.  Stage 0 reads (and clears) row 0 and leaves every rank's high digit; stage 1 reads all nq rows and
 // writes q[nq * r + i] (the memset in front of the next call clears them).  cal (stage 1, nq = 2): press_hip_scale_cal's
 // two floats of {q[0], q[1]}, every operation rounded once and none fused.
-__global__ __launch_bounds__(256) void k_q_pick(int stage, const uint32_t *out_n, uint32_t nreads, QRead *st, uint32_t *rows, uint32_t nq,
-						 QRanks rk, int32_t *q, float *cal, ScaleRule rule)
+// RANGED: the read's count is L = b' - a' of its clamped range.
+template <bool RANGED>
+__device__ __forceinline__ void q_pick(int stage, const uint32_t *out_n, const uint32_t *range, uint32_t nreads, QRead *st, uint32_t *rows,
+				       uint32_t nq, const QRanks &rk, int32_t *q, float *cal, const ScaleRule &rule)
 {
 	const uint32_t r = uni(blockIdx.x * 4 + (threadIdx.x >> 6));
 	if (r >= nreads)
@@ -168,6 +186,10 @@ __global__ __launch_bounds__(256) void k_q_pick(int stage, const uint32_t *out_n
 	if (stage == 0) {
 		const uint32_t on = uni(out_n[r]);
 		t.c = on == Q_FAIL ? 0u : on;
+		if (RANGED) {
+			const uint2 ab = range_clamp(range, r, t.c);
+			t.c = uni(ab.y - ab.x);
+		}
 	} else {
 		t.c = uni(st[r].c);
 	}
@@ -219,6 +241,18 @@ __global__ __launch_bounds__(256) void k_q_pick(int stage, const uint32_t *out_n
 	}
 }
 
+__global__ __launch_bounds__(256) void k_q_pick(int stage, const uint32_t *out_n, uint32_t nreads, QRead *st, uint32_t *rows, uint32_t nq,
+						 QRanks rk, int32_t *q, float *cal, ScaleRule rule)
+{
+	q_pick<false>(stage, out_n, nullptr, nreads, st, rows, nq, rk, q, cal, rule);
+}
+
+__global__ __launch_bounds__(256) void k_q_pick_ranged(int stage, const uint32_t *out_n, const uint32_t *range, uint32_t nreads, QRead *st,
+							uint32_t *rows, uint32_t nq, QRanks rk, int32_t *q, float *cal, ScaleRule rule)
+{
+	q_pick<true>(stage, out_n, range, nreads, st, rows, nq, rk, q, cal, rule);
+}
+
 uint64_t quant_rows_bytes(uint32_t nreads, uint32_t nq) { return (uint64_t) nreads * nq * Q_NB * sizeof(uint32_t); }
 uint64_t quant_state_bytes(uint32_t nreads) { return (uint64_t) nreads * sizeof(QRead); }
 
@@ -250,6 +284,35 @@ void launch_signal_quantiles(const DecodeArgs &a, const uint2 *tiles, const uint
 	else
 		hipLaunchKernelGGL((k_q_count<4, true>), gc, b, 0, s, sig, a.off, on, tiles, ntiles, (const QRead *) st, rows, nq);
 	hipLaunchKernelGGL(k_q_pick, gp, b, 0, s, 1, on, a.nreads, st, rows, nq, rk, q, nq == 2 ? cal : nullptr, ru);
+}
+
+// ... of the samples [a', b') of every read alone (range: 2 words per read, device memory, clamped by the kernels)
+void launch_signal_quantiles_ranged(const DecodeArgs &a, const uint32_t *range, const uint2 *tiles, const uint32_t *ntiles, void *state,
+				    uint32_t *rows, const uint32_t *num, const uint32_t *den, uint32_t nq, int32_t *q, float *cal,
+				    const ScaleRule *rule, hipStream_t s)
+{
+	if (!a.nreads || !a.max_chunks || !nq || nq > QMAX)
+		return;
+	QRanks rk = {};
+	for (uint32_t i = 0; i < nq; i++) {
+		rk.num[i] = num[i];
+		rk.den[i] = den[i];
+	}
+	const ScaleRule ru = rule ? *rule : ScaleRule{};
+	QRead *st = (QRead *) state;
+	const dim3 gc(a.max_chunks), gp((a.nreads + 3) / 4), b(256);
+	const int16_t *sig = a.sig;
+	const uint32_t *on = a.out_n;
+	(void) hipMemsetAsync(rows, 0, quant_rows_bytes(a.nreads, nq), s);
+	hipLaunchKernelGGL((k_q_count<1, false, const uint32_t *>), gc, b, 0, s, sig, a.off, on, tiles, ntiles, (const QRead *) st, rows, nq, range);
+	hipLaunchKernelGGL(k_q_pick_ranged, gp, b, 0, s, 0, on, range, a.nreads, st, rows, nq, rk, (int32_t *) nullptr, (float *) nullptr, ru);
+	if (nq == 1)
+		hipLaunchKernelGGL((k_q_count<1, true, const uint32_t *>), gc, b, 0, s, sig, a.off, on, tiles, ntiles, (const QRead *) st, rows, nq, range);
+	else if (nq == 2)
+		hipLaunchKernelGGL((k_q_count<2, true, const uint32_t *>), gc, b, 0, s, sig, a.off, on, tiles, ntiles, (const QRead *) st, rows, nq, range);
+	else
+		hipLaunchKernelGGL((k_q_count<4, true, const uint32_t *>), gc, b, 0, s, sig, a.off, on, tiles, ntiles, (const QRead *) st, rows, nq, range);
+	hipLaunchKernelGGL(k_q_pick_ranged, gp, b, 0, s, 1, on, range, a.nreads, st, rows, nq, rk, q, nq == 2 ? cal : nullptr, ru);
 }
 
 } // namespace ph

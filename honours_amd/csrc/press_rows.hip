@@ -159,6 +159,96 @@ __global__ __launch_bounds__(256) void k_chunk_rows(const int16_t *sig, const ui
 	}
 }
 
+// The rows of press_hip_depress_chunks_trimmed_batch: read r gives the L = b' - a' samples [a', b') of cut[2r], cut[2r + 1]
+// (clamped by k_trim_cut: b' is at most the decoded count), row_first is the plan over the L[r] and lies in device memory
+// like the cuts.  A row's source start is a' + the plan's start for a read of L samples, its decoded bound b'; the room
+// and its groups are the read's, as above.  The lane that makes a row's first columns writes its row_read / row_start.
+__device__ __forceinline__ RowSrc row_src_ranged(const int16_t *sig, const uint64_t *off, const uint32_t *nsamp, const uint32_t *cut,
+						  const float *cal, const uint64_t *row_first, uint32_t r, uint64_t row, uint32_t T, uint32_t S)
+{
+	RowSrc s;
+	const uint32_t a = cut[2 * (size_t) r], b = cut[2 * (size_t) r + 1];
+	const uint32_t L = b - a;
+	const bool last = row + 1 == row_first[r + 1];
+	s.start = a + (last && L > T ? (uint64_t) (L - T) : (row - row_first[r]) * S);
+	s.on = b;
+	s.cnt8 = (nsamp[r] + 7u) & ~7u;
+	s.in = sig + off[r];
+	s.c0 = cal[2 * (size_t) r];
+	s.c1 = cal[2 * (size_t) r + 1];
+	return s;
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void k_chunk_rows_ranged(const int16_t *sig, const uint64_t *off, const uint32_t *nsamp, const uint32_t *cut,
+							    const float *cal, const uint64_t *row_first, uint32_t nreads, uint8_t *rows,
+							    uint64_t nrows_cap, uint32_t T, uint32_t S, uint32_t *row_read, uint32_t *row_start)
+{
+	constexpr uint32_t ES = DT == PRESS_ROWS_F32 ? 4 : 2;
+	const uint64_t planned = uni64(row_first[nreads]);
+	const uint64_t nrows = planned < nrows_cap ? planned : nrows_cap;
+	if (T >= ROW_COLS) {
+		for (uint64_t row = blockIdx.x; row < nrows; row += gridDim.x) {
+			const uint32_t r = uni(row_read_of(row_first, nreads, row));
+			const RowSrc s = row_src_ranged(sig, off, nsamp, cut, cal, row_first, r, row, T, S);
+			uint8_t *out = rows + row * T * ES;
+			for (uint64_t col = threadIdx.x * 8; col < T; col += ROW_COLS)
+				row_cols<DT>(s, col, out);
+			if (threadIdx.x == 0) {
+				if (row_read)
+					row_read[row] = r;
+				if (row_start)
+					row_start[row] = (uint32_t) s.start;
+			}
+		}
+		return;
+	}
+	const uint32_t rpb = ROW_COLS / T; // rows of a workgroup
+	const uint64_t nblocks = (nrows + rpb - 1) / rpb;
+	const uint32_t lr = threadIdx.x * 8 / T, col = threadIdx.x * 8 - lr * T;
+	if (lr >= rpb)
+		return;
+	for (uint64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+		const uint64_t row = blk * rpb + lr;
+		if (row >= nrows)
+			continue;
+		const uint32_t r = row_read_of(row_first, nreads, row);
+		const RowSrc s = row_src_ranged(sig, off, nsamp, cut, cal, row_first, r, row, T, S);
+		row_cols<DT>(s, col, rows + row * T * ES);
+		if (col == 0) {
+			if (row_read)
+				row_read[row] = r;
+			if (row_start)
+				row_start[row] = (uint32_t) s.start;
+		}
+	}
+}
+
+// ... of the trimmed call: the grid is the same bound, as L[r] <= n[r]
+void launch_chunk_rows_ranged(const DecodeArgs &a, const uint32_t *cut, const float *cal, const uint64_t *row_first, void *rows,
+			      uint64_t nrows_cap, int dtype, uint32_t T, uint32_t overlap, uint64_t total_samples, uint32_t *row_read,
+			      uint32_t *row_start, hipStream_t s)
+{
+	const uint32_t S = T - overlap;
+	uint64_t bound = (uint64_t) a.nreads + total_samples / S;
+	if (bound > nrows_cap)
+		bound = nrows_cap;
+	if (!a.nreads || !bound)
+		return;
+	const uint64_t nb = T >= ROW_COLS ? bound : (bound + ROW_COLS / T - 1) / (ROW_COLS / T);
+	const dim3 g((uint32_t) (nb < 0x7FFFFFFFull ? nb : 0x7FFFFFFFull)), b(256);
+	const int16_t *sig = a.sig;
+	if (dtype == PRESS_ROWS_F32)
+		hipLaunchKernelGGL((k_chunk_rows_ranged<PRESS_ROWS_F32>), g, b, 0, s, sig, a.off, a.nsamp, cut, cal, row_first, a.nreads,
+				   (uint8_t *) rows, nrows_cap, T, S, row_read, row_start);
+	else if (dtype == PRESS_ROWS_F16)
+		hipLaunchKernelGGL((k_chunk_rows_ranged<PRESS_ROWS_F16>), g, b, 0, s, sig, a.off, a.nsamp, cut, cal, row_first, a.nreads,
+				   (uint8_t *) rows, nrows_cap, T, S, row_read, row_start);
+	else
+		hipLaunchKernelGGL((k_chunk_rows_ranged<PRESS_ROWS_BF16>), g, b, 0, s, sig, a.off, a.nsamp, cut, cal, row_first, a.nreads,
+				   (uint8_t *) rows, nrows_cap, T, S, row_read, row_start);
+}
+
 // rows of the batch: every planned row below nrows_cap.  The grid is what the host knows: no read has more than
 // 1 + n[r] / S rows and the rooms lie within total_samples, so nreads + total_samples / S bounds the planned rows.
 void launch_chunk_rows(const DecodeArgs &a, const float *cal, const uint64_t *row_first, void *rows, uint64_t nrows_cap, int dtype,

@@ -286,12 +286,13 @@ void launch_segments_write(const int16_t *sig, const uint64_t *off, const uint32
 	ktime_end(1, s);
 }
 
-// The first record of every read in one launch (first: 8 bytes per read, start = 0xFFFFFFFF: none); state as above
+// The first record of every read in one launch (first: 8 bytes per read, start = 0xFFFFFFFF: none); state as above;
+// cal NULL: the raw domain
 void launch_segments_first(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads, const SegParams &p, void *state,
-			   void *first, hipStream_t s)
+			   void *first, hipStream_t s, const float *cal)
 {
 	ktime_begin(1, s);
-	hipLaunchKernelGGL((k_segments<false, true>), dim3(nreads), dim3(64), 0, s, sig, off, n, (const float *) nullptr, p,
+	hipLaunchKernelGGL((k_segments<false, true>), dim3(nreads), dim3(64), 0, s, sig, off, n, cal, p,
 			   (SegState *) state, (float *) nullptr, (SegRec *) first, (uint64_t) 0, (const uint64_t *) nullptr);
 	ktime_end(1, s);
 }

@@ -50,10 +50,17 @@ template <int BITS> struct StatLds {
 // adjacent values and a lane's 8 samples are neighbours in time, so a lane first merges runs of one digit (typically
 // all 8) and adds a run with ONE ds_add; lanes pick a copy of the counters by their id, so that a wave's 64 lanes
 // spread over all of them.  A tile beyond the decoded count, or of a refused read, ends at once.
-template <int BITS, bool LOW, bool MAD>
+//
+// RANGED (press_hip_signal_stats_ranged, the trimmed chunk call): only the samples [a', b') of the read take part - range[2r],
+// range[2r + 1] clamped as include/press_hip.h 2y says.  The tiles and the aligned 16-byte groups are the room's, as
+// without a range: a tile wholly outside the range ends at once, a group in front of a' is not loaded, and the groups at
+// the two edges are masked per sample.  The range is a trailing parameter pack - empty, or one `const uint32_t *` - so
+// that the kernel without a range keeps its arguments and its code.
+template <int BITS, bool LOW, bool MAD, class... R>
 __global__ __launch_bounds__(256) void k_stat_count(const int16_t *sig, const uint64_t *off, const uint32_t *out_n,
-						     const uint2 *tiles, const uint32_t *ntiles, const StatRead *st, uint32_t *rows)
+						     const uint2 *tiles, const uint32_t *ntiles, const StatRead *st, uint32_t *rows, R... range)
 {
+	constexpr bool RANGED = sizeof...(R) != 0;
 	typedef StatLds<BITS> L;
 	__shared__ uint32_t s_h[L::COPIES * L::STRIDE];
 	if (blockIdx.x >= uni(*ntiles))
@@ -63,7 +70,16 @@ __global__ __launch_bounds__(256) void k_stat_count(const int16_t *sig, const ui
 	const uint64_t first = (uint64_t) j * CHUNK;
 	if (on == STAT_FAIL || first >= on)
 		return;
-	const uint64_t end = first + CHUNK < on ? first + CHUNK : on;
+	uint64_t end = first + CHUNK < on ? first + CHUNK : on;
+	uint32_t lo = 0;
+	if constexpr (RANGED) {
+		const uint2 ab = range_clamp(range..., r, on);
+		lo = uni(ab.x);
+		const uint32_t hi = uni(ab.y);
+		if (lo >= hi || first >= hi || first + CHUNK <= lo)
+			return;
+		end = first + CHUNK < hi ? first + CHUNK : hi;
+	}
 	for (uint32_t i = threadIdx.x; i < L::COPIES * L::STRIDE; i += 256)
 		s_h[i] = 0;
 	__syncthreads();
@@ -72,16 +88,19 @@ __global__ __launch_bounds__(256) void k_stat_count(const int16_t *sig, const ui
 	uint32_t *my = s_h + (threadIdx.x & (L::COPIES - 1)) * L::STRIDE;
 	const int16_t *in = sig + uni64(off[r]);
 	for (uint64_t i = first + threadIdx.x * 8; i < end; i += 256 * 8) {
+		if (RANGED && i + 8 <= lo)
+			continue;
 		const uint4 q = ld16_stream(in + i);
 		const uint32_t v[4] = { q.x, q.y, q.z, q.w };
 		const uint32_t nv = end - i < 8 ? (uint32_t) (end - i) : 8u;
+		const uint32_t skip = RANGED && lo > i ? (uint32_t) (lo - i) : 0u; // (the group that holds a')
 		uint32_t cur = STAT_NONE, cnt = 0;
 #pragma unroll
 		for (int e = 0; e < 8; e++) {
 			const int32_t s = (e & 1) ? (int32_t) v[e >> 1] >> 16 : (int32_t) (int16_t) (v[e >> 1] & 0xFFFFu);
 			const uint32_t key = MAD ? (uint32_t) (s >= med ? s - med : med - s) : (uint32_t) (s + 32768);
 			uint32_t d = LOW ? key & (L::NB - 1) : key >> (16 - BITS);
-			if ((uint32_t) e >= nv || (LOW && (key >> BITS) != hi))
+			if ((uint32_t) e >= nv || (LOW && (key >> BITS) != hi) || (RANGED && (uint32_t) e < skip))
 				d = STAT_NONE;
 			if (d != cur) {
 				if (cur != STAT_NONE)
@@ -116,8 +135,10 @@ __device__ __forceinline__ uint32_t stat_rank(uint32_t c, uint32_t num, uint32_t
 // time for the digit that holds the rank, and cleared for the next counting pass.  The rank is floor(c * num / den)
 // (num / den = 1 / 2: sigtk's n / 2).  Stage 3 writes stats[2r] = med, stats[2r + 1] = mad and cal[2r] = (float) -med,
 // cal[2r + 1] = 1 / ((float) mad * 1.4826f), or 1 for mad = 0; an empty or refused read gets {0, 0} and {0, 1}.
-__global__ __launch_bounds__(256) void k_stat_pick(int stage, const uint32_t *out_n, uint32_t nreads, StatRead *st, uint32_t *rows,
-						    uint32_t num, uint32_t den, int32_t *stats, float *cal)
+// RANGED: the read's count is L = b' - a' of its clamped range.
+template <bool RANGED>
+__device__ __forceinline__ void stat_pick(int stage, const uint32_t *out_n, const uint32_t *range, uint32_t nreads, StatRead *st, uint32_t *rows,
+					  uint32_t num, uint32_t den, int32_t *stats, float *cal)
 {
 	const uint32_t r = uni(blockIdx.x * 4 + (threadIdx.x >> 6));
 	if (r >= nreads)
@@ -128,6 +149,10 @@ __global__ __launch_bounds__(256) void k_stat_pick(int stage, const uint32_t *ou
 	if (stage == 0) {
 		const uint32_t on = uni(out_n[r]);
 		t.c = on == STAT_FAIL ? 0u : on;
+		if (RANGED) {
+			const uint2 ab = range_clamp(range, r, t.c);
+			t.c = uni(ab.y - ab.x);
+		}
 		t.k = stat_rank(t.c, num, den);
 	} else {
 		t.c = uni(st[r].c);
@@ -191,8 +216,34 @@ __global__ __launch_bounds__(256) void k_stat_pick(int stage, const uint32_t *ou
 	}
 }
 
+__global__ __launch_bounds__(256) void k_stat_pick(int stage, const uint32_t *out_n, uint32_t nreads, StatRead *st, uint32_t *rows,
+						    uint32_t num, uint32_t den, int32_t *stats, float *cal)
+{
+	stat_pick<false>(stage, out_n, nullptr, nreads, st, rows, num, den, stats, cal);
+}
+
+__global__ __launch_bounds__(256) void k_stat_pick_ranged(int stage, const uint32_t *out_n, const uint32_t *range, uint32_t nreads,
+							   StatRead *st, uint32_t *rows, uint32_t num, uint32_t den, int32_t *stats, float *cal)
+{
+	stat_pick<true>(stage, out_n, range, nreads, st, rows, num, den, stats, cal);
+}
+
 uint64_t stat_rows_bytes(uint32_t nreads) { return (uint64_t) nreads * STAT_ROW * sizeof(uint32_t); }
 uint64_t stat_state_bytes(uint32_t nreads) { return (uint64_t) nreads * sizeof(StatRead); }
+
+template <bool MAD>
+static void stat_round_ranged(const DecodeArgs &a, const uint32_t *range, const uint2 *tiles, const uint32_t *ntiles, StatRead *st,
+			      uint32_t *rows, int32_t *stats, float *cal, hipStream_t s)
+{
+	const dim3 gc(a.max_chunks), gp((a.nreads + 3) / 4), b(256);
+	const int16_t *sig = a.sig;
+	const uint32_t *on = a.out_n;
+	hipLaunchKernelGGL((k_stat_count<STAT_HI, false, MAD, const uint32_t *>), gc, b, 0, s, sig, a.off, on, tiles, ntiles, (const StatRead *) st, rows, range);
+	hipLaunchKernelGGL(k_stat_pick_ranged, gp, b, 0, s, MAD ? 2 : 0, on, range, a.nreads, st, rows, 1u, 2u, (int32_t *) nullptr, (float *) nullptr);
+	hipLaunchKernelGGL((k_stat_count<STAT_LO, true, MAD, const uint32_t *>), gc, b, 0, s, sig, a.off, on, tiles, ntiles, (const StatRead *) st, rows, range);
+	hipLaunchKernelGGL(k_stat_pick_ranged, gp, b, 0, s, MAD ? 3 : 1, on, range, a.nreads, st, rows, 1u, 2u, MAD ? stats : nullptr,
+			   MAD ? cal : nullptr);
+}
 
 template <bool MAD>
 static void stat_round(const DecodeArgs &a, const uint2 *tiles, const uint32_t *ntiles, StatRead *st, uint32_t *rows,
@@ -229,6 +280,17 @@ void launch_signal_stats(const DecodeArgs &a, const uint2 *tiles, const uint32_t
 		(void) hipEventRecord(ev[0], s);
 	stat_round<false>(a, tiles, ntiles, (StatRead *) state, rows, stats, cal, ev, s);
 	stat_round<true>(a, tiles, ntiles, (StatRead *) state, rows, stats, cal, ev, s);
+}
+
+// ... of the samples [a', b') of every read alone (range: 2 words per read, device memory, clamped by the kernels)
+void launch_signal_stats_ranged(const DecodeArgs &a, const uint32_t *range, const uint2 *tiles, const uint32_t *ntiles, void *state,
+				uint32_t *rows, int32_t *stats, float *cal, hipStream_t s)
+{
+	if (!a.nreads || !a.max_chunks)
+		return;
+	(void) hipMemsetAsync(rows, 0, stat_rows_bytes(a.nreads), s);
+	stat_round_ranged<false>(a, range, tiles, ntiles, (StatRead *) state, rows, stats, cal, s);
+	stat_round_ranged<true>(a, range, tiles, ntiles, (StatRead *) state, rows, stats, cal, s);
 }
 
 } // namespace ph

@@ -17,6 +17,17 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v)
 	return ((uint64_t) uni((uint32_t) (v >> 32)) << 32) | uni((uint32_t) v);
 }
 
+// The clamped range of a read of c samples (include/press_hip.h 2y): b' = min(b, c), a' = min(a, b') of range[2r],
+// range[2r + 1]; range NULL: [0, c)
+__device__ __forceinline__ uint2 range_clamp(const uint32_t *range, uint32_t r, uint32_t c)
+{
+	if (!range)
+		return make_uint2(0u, c);
+	const uint32_t a = range[2 * (size_t) r], b = range[2 * (size_t) r + 1];
+	const uint32_t hi = b < c ? b : c;
+	return make_uint2(a < hi ? a : hi, hi);
+}
+
 // 16 bytes of a stream that is read once: non-temporal policy (tools/ubench_stream.hip: a read-only sweep reaches
 // 7.1 TB/s with it against 6.3 TB/s with the default policy, a copy 6.0 against 5.2-5.6)
 #ifndef PRESS_NO_NT

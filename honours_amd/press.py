@@ -1191,6 +1191,11 @@ def __getattr__(name):
         mod = importlib.import_module("." + name.split("_")[0], __package__)
         if hasattr(mod, name):
             return getattr(mod, name)
+    if not name.startswith("_"):  # honours_amd.trim's __all__: the ranged statistics and the trimmed chunk rows (header 2y)
+        import importlib
+        mod = importlib.import_module(".trim", __package__)
+        if name in mod.__all__:
+            return getattr(mod, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 

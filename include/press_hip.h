@@ -1566,6 +1566,73 @@ enum { PRESS_HIP_SMETHOD_BASE = 96 };
 int press_hip_smethod(int stall_method);
 int press_hip_smethod_parts(int id, int *stall_method);
 
+/*
+ * (2y) Trimmed chunk rows: a range per read, the scaling statistics over it, the row plan on the device.
+ *
+ * Range.  press_hip_signal_range_stats' convention: `range` is 2 * nreads uint32 words a, b in samples from the read's
+ * start.  With c the read's sample count: b' = min(b, c), a' = min(a, b'), L = b' - a'.  range == NULL is [0, c).  No
+ * alignment is asked of off[r] + a.  The SLICED BATCH of a batch and its clamped ranges is the batch whose read r is the
+ * L samples [a', b') of read r; every "equals" below means bit for bit against the existing call on the sliced batch.
+ *
+ * press_hip_signal_quantiles_ranged / press_hip_signal_stats_ranged: q and stats equal press_hip_signal_quantiles /
+ * press_hip_signal_stats on the sliced batch - k = min(L - 1, floor(L * num / den)), med and mad at L / 2, 0 and {0, 0}
+ * for L == 0.  Checks, forms (host pointers: staged and synchronous; device resident: only enqueued, `range` a device
+ * pointer) and launch counts (four and eight) are the unranged calls'.  Loads stay inside the read's room
+ * [off[r], off[r] + roundup8(n[r])); what lies outside [a', b') does not take part.
+ *
+ * press_hip_depress_chunks_trimmed_batch: press_hip_depress_chunks_batch (in / in_off / in_len / off / n / total_samples /
+ * out_n / dtype / T / overlap / rule / q mean what they mean there: every method id of the generic calls, the same checks,
+ * room rules, PRESS_HIP_ENOTABLE and host wait of the zstd kinds; the WHOLE read is decoded into library scratch) with a
+ * range per read.  c = min(out_n[r], n[r]) for a decoded read, 0 for a refused one; out_n reports the full decode.
+ *   mode RANGE (and trim == NULL)  the caller's `range`, or the whole read when it is NULL
+ *   mode ADAPTOR                   a = the second word (end) of press_hip_signal_adaptor's pair under trim->adaptor over
+ *                                  the decoded samples [0, c) where end > 0, else 0 (the pairs (-1, -1), (0, 0)); b = c
+ *   mode SEGMENT                   a = the end of the first record press_hip_signal_segments defines for the read under
+ *                                  trim->seg with seg_cal as its cal (NULL: the raw domain), 0 without a record; b = c
+ * Both detector modes: if b' - a' < min_keep then a' = 0; the two detector calls' parameter checks apply before any device
+ * call; reads of 2^31 samples and more are outside their definition.  cut (may be NULL) receives a', b' of every read in
+ * every mode, (0, 0) for a refused read.
+ *   Scaling: with a rule q = {q_lo, q_hi} over [a', b') and y press_hip_scale_cal's; without one median and MAD over
+ * [a', b'); q is {0, 0} for L == 0.
+ *   Row plan: row_first (nreads + 1, WRITTEN) is press_hip_chunk_plan over the L[r], computed on the device and always
+ * written in full: row_first[nreads] says what the batch needs whatever nrows_cap is; a read with L == 0 takes no row.
+ * Row row_first[r] + j holds at column t round_to_dtype(y[a' + start_j + t]), start_j the plan's start for a read of L
+ * samples; a column at or beyond L is +0.  row_read[row] = r and row_start[row] = a' + start_j (a position in the read,
+ * for stitching a model's output); both may be NULL.  Never written: rows, row_read or row_start entries at or beyond
+ * nrows_cap, anything at or beyond row_first[nreads], any byte outside the written prefix.  rows == NULL with
+ * nrows_cap == 0 is a pure plan: no row kernel runs.
+ *   Equivalence: rows, q and row_first equal what press_hip_chunk_plan and press_hip_depress_chunks_batch give for the
+ * sliced batch (pressed by any method that takes it) under the same T, overlap, dtype and rule.
+ *   Forms.  Device resident: the call only enqueues on the current stream and never waits; row_first, range, cut,
+ * row_read, row_start and seg_cal are device pointers, trim and rule host pointers read before the call returns.  Host
+ * pointers: staged, synchronous; the written prefix of rows comes back in one transfer, with the small tables.
+ *   Refusals: a bad id, mode, T, overlap, dtype, rule or detector parameter is PRESS_HIP_EARG before any device call, so
+ * is a NULL argument other than those named optional.  nreads == 0 is PRESS_HIP_OK and writes row_first[0] = 0.
+ * press_hip_depress_chunks_trimmed_workspace_bytes is exact, never below press_hip_depress_chunks_workspace_bytes, and 0
+ * for a bad id, T, overlap or mode.
+ */
+int press_hip_signal_quantiles_ranged(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				      uint64_t total_samples, const uint32_t *range, const uint32_t *rank_num,
+				      const uint32_t *rank_den, uint32_t nq, int32_t *q, int device_resident);
+int press_hip_signal_stats_ranged(const int16_t *sig, const uint64_t *off, const uint32_t *n, uint32_t nreads,
+				  uint64_t total_samples, const uint32_t *range, int32_t *stats, int device_resident);
+enum { PRESS_HIP_TRIM_RANGE = 0, PRESS_HIP_TRIM_ADAPTOR = 1, PRESS_HIP_TRIM_SEGMENT = 2 };
+typedef struct {
+	int32_t mode;
+	uint32_t min_keep;             /* detector modes: a cut that leaves fewer samples is not made (a' = 0); 0: off */
+	press_hip_jnn2_params adaptor; /* mode ADAPTOR */
+	press_hip_jnn_params seg;      /* mode SEGMENT */
+} press_hip_trim;
+int press_hip_depress_chunks_trimmed_batch(int method, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+					   uint32_t nreads, void *rows, uint64_t nrows_cap, int dtype, uint32_t T, uint32_t overlap,
+					   uint64_t *row_first /* nreads + 1, WRITTEN */, uint32_t *row_read,
+					   uint32_t *row_start /* nrows_cap each, may be NULL */, const uint64_t *off, const uint32_t *n,
+					   uint64_t total_samples, const press_hip_trim *trim, const uint32_t *range,
+					   const float *seg_cal, uint32_t *cut /* 2 * nreads, may be NULL */,
+					   const press_hip_scale_rule *rule, int32_t *q, uint32_t *out_n, int device_resident);
+uint64_t press_hip_depress_chunks_trimmed_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads, uint32_t T,
+							  uint32_t overlap, int mode);
+
 /* ======================================================================= (3) BLOW5 files (host) */
 
 /*
