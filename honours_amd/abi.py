@@ -184,6 +184,10 @@ PROTOS = {
     "press_hip_blow5_index": (I, [P, I]),
     "press_hip_blow5_threads": (I, [P, I]),
     "press_hip_blow5_finish": (I, [P]),
+    "press_hip_blow5_deflate_sizes": (I, [P, P, Q, P, P, P, Q, U, Q, I, P, I]),
+    "press_hip_blow5_deflate_batch": (I, [P, P, Q, P, P, P, Q, U, Q, I, P, Q, P, P, I]),
+    "press_hip_blow5_deflate_workspace_bytes": (Q, [Q, U]),
+    "press_hip_blow5_write_image": (I, [P, P, Q, U, P, P, P]),
 }
 for _fam in ("", "packed_", "depress_pa_", "depress_norm_", "verify_", "stall_"):  # (method, total_samples, nreads)
     PROTOS["press_hip_%sworkspace_bytes" % _fam] = (Q, [I, Q, U])

@@ -633,6 +633,44 @@ int press_hip_blow5_write_batch(press_hip_blow5_writer *w, uint32_t n, const uin
 	return 0;
 }
 
+// n records deflated elsewhere (press_hip_blow5_deflate_batch): the image is what put_record would have written for them
+int press_hip_blow5_write_image(press_hip_blow5_writer *w, const uint8_t *image, uint64_t bytes, uint32_t n, const uint64_t *rec_off,
+				const uint8_t *const *pre, const uint64_t *pre_len)
+{
+	if (!w || (n && (!image || !rec_off || !pre || !pre_len)))
+		return b5_fail(PRESS_HIP_EARG, "BLOW5 writer: NULL argument");
+	if (w->record_method != 1)
+		return b5_fail(PRESS_HIP_EARG, "BLOW5 writer: an image of zlib streams needs a writer with record method zlib");
+	if (n == 0)
+		return bytes ? b5_fail(PRESS_HIP_EARG, "BLOW5 writer: an image without records") : 0;
+	if (rec_off[0] != 0 || rec_off[n] != bytes)
+		return b5_fail(PRESS_HIP_EARG, "BLOW5 writer: rec_off does not span the image");
+	for (uint32_t i = 0; i < n; i++) {
+		uint64_t len;
+		if (rec_off[i + 1] < rec_off[i] + 8 || rec_off[i + 1] > bytes)
+			return b5_fail(PRESS_HIP_EARG, "BLOW5 writer: rec_off does not ascend by whole records");
+		memcpy(&len, image + rec_off[i], 8);
+		if (len != rec_off[i + 1] - rec_off[i] - 8)
+			return b5_fail(PRESS_HIP_EARG, "BLOW5 writer: a record's length field is not its extent in the image");
+		uint16_t idl = 0;
+		if (pre_len[i] >= 2)
+			memcpy(&idl, pre[i], 2);
+		if (w->want_index && (!pre[i] || (uint64_t) idl + 2 > pre_len[i]))
+			return b5_fail(PRESS_HIP_EARG, "BLOW5 writer: the record's read id runs past its front part");
+	}
+	if (fwrite(image, 1, bytes, w->fp) != bytes)
+		return b5_fail(PRESS_HIP_EARG, "BLOW5 writer: write failed");
+	if (w->want_index) {
+		for (uint32_t i = 0; i < n; i++) {
+			uint16_t idl;
+			memcpy(&idl, pre[i], 2);
+			w->index.push_back({ std::string((const char *) pre[i] + 2, idl), w->at + rec_off[i], rec_off[i + 1] - rec_off[i] });
+		}
+	}
+	w->at += bytes;
+	return 0;
+}
+
 int press_hip_blow5_finish(press_hip_blow5_writer *w)
 {
 	if (!w)

@@ -80,6 +80,7 @@ struct Ctx {
 	DevBuf ri_sum, ri_start, ri_rd, ri_pay, ri_drd, ri_tile, ri_rec, ri_tbase, ri_ctl, ri_k; // Rice methods: the units' sums and first bits, the reads' records, the staged payloads; depress: reads, tiles, subsequence records, tile bases, counters; host path: k[]
 	DevBuf dh_tab; // per-read Huffman methods: codes and counts (press), decode tables (depress); the other buffers are the Rice methods'
 	DevBuf tl_chunks, tl_ctl, tl_tab, tl_mom; // dataset tallies: the chunk list and its count; host path: the three tables in a row, the moments
+	DevBuf df_rec, df_unit, df_tab, df_need, df_side, df_sig, df_tabs, df_img, df_out; // BLOW5 record deflate (press_deflate.hip): the records, the units' tables, counts / codes / block headers, the sizes; host path: the side arena, the signal arena, the three tables, the image, rec_off and raw
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams
@@ -149,6 +150,7 @@ struct Staged {
 	// layout() of the rooms, then the streams dense in `arena`, their table in `offs` -> d; d.sig: g.sig with sig_room,
 	// else h.sig as it is
 	int streams(const StreamsIn &h, uint64_t total_samples, bool sig_room, DevBuf &arena, DevBuf &offs, StreamsIn &d);
+	int push(void *dev, const void *src, size_t bytes); // plain bytes up; returns when src may be reused, unless it is page-locked
 	// the tails; all but fetch_prefix end with the stream synchronised
 	struct Table { // a per-read result table on its way back; dst NULL: the caller did not ask for it
 		void *dst;

@@ -365,6 +365,8 @@ int Staged::streams(const StreamsIn &h, uint64_t total_samples, bool sig_room, D
 }
 
 // The tail of a host-pointer call whose results are per-read tables and nothing else
+int Staged::push(void *dev, const void *src, size_t bytes) { return h2d(dev, src, bytes, s); }
+
 int Staged::fetch_tables(std::initializer_list<Table> tables)
 {
 	for (const Table &t : tables)

@@ -1191,11 +1191,12 @@ def __getattr__(name):
         mod = importlib.import_module("." + name.split("_")[0], __package__)
         if hasattr(mod, name):
             return getattr(mod, name)
-    if not name.startswith("_"):  # honours_amd.trim's __all__: the ranged statistics and the trimmed chunk rows (header 2y)
-        import importlib
-        mod = importlib.import_module(".trim", __package__)
-        if name in mod.__all__:
-            return getattr(mod, name)
+    if not name.startswith("_"):  # honours_amd.trim's __all__: the ranged statistics and the trimmed chunk rows (header 2y);
+        import importlib          # honours_amd.deflate's: BLOW5 records deflated on the device (header 2z)
+        for sub in (".trim", ".deflate"):
+            mod = importlib.import_module(sub, __package__)
+            if name in mod.__all__:
+                return getattr(mod, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -1841,11 +1842,83 @@ def _blow5_write_batch(w, pres, sigs, posts):
     _blow5_call("press_hip_blow5_write_batch", w, n, pre_p, pre_l, sig_p, sig_l, post_p, post_l)
 
 
-def blow5_write_like(dst, like, fields, record_method=1, signal_method=1, index=False, ids=None):
+# ---------------------------------------------------------------------------- BLOW5 records deflated on the device
+# (the calls themselves: honours_amd.deflate, whose names are attributes of this module too - __getattr__ above)
+
+def _deflate():
+    import importlib
+    return importlib.import_module(".deflate", __package__)
+
+
+def _blow5_write_image(w, image, rec_off, pres):
+    """press_hip_blow5_write_image: image and rec_off as numpy arrays, pres the records' front parts"""
+    n = len(pres)
+    pre_p, pre_l = (ctypes.c_void_p * n)(), (ctypes.c_uint64 * n)()
+    for k in range(n):
+        pre_p[k], pre_l[k] = pres[k].ctypes.data, pres[k].size
+    rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    _blow5_call("press_hip_blow5_write_image", w, _ptr(image), int(rec_off[n]), n, _ptr(rec_off), pre_p, pre_l)
+
+
+def _blow5_fields_deflated(src_signal_method, fields, ns, pres, posts, degrade_bits, who):
+    """One batch of a transcode with deflate="device": the source's signal fields (svb-zd streams, or int16 samples as
+    bytes) become svb-zd fields in a device arena - recoded, or pressed - and the deflate call reads them there; only the
+    image comes back.  -> (image, rec_off) as numpy arrays"""
+    import torch
+
+    n = len(fields)
+    dev = torch.device("cuda")
+
+    def up(a, view=None):
+        return torch.from_numpy(a if view is None else a.view(view)).to(dev)
+    ns = np.asarray(ns, dtype=np.uint32)
+    bound = sum(int(load_library().press_hip_bound(METHODS["slow5_svb_zd"], int(x))) for x in ns)
+    arena = torch.empty((bound + 3) // 4 * 4 + 64, dtype=torch.uint8, device=dev)
+    out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    if src_signal_method == 1:
+        comp, in_off, in_len, ns, off, total = _decode_batch(fields, ns)
+        out_n = torch.empty(n, dtype=torch.int32, device=dev)
+        recode_packed("slow5_svb_zd", "slow5_svb_zd", up(comp), up(in_off, np.int64), up(in_len, np.int64), up(ns, np.int32),
+                      up(off, np.int64), arena, out_off, out_len, out_n, total_samples=total, degrade_bits=degrade_bits)
+    else:
+        sig, off, ns, total = _host_batch([np.frombuffer(f, dtype=np.int16) for f in fields])
+        d_sig, d_off, d_n = up(sig), up(off, np.int64), up(ns, np.int32)
+        if degrade_bits:
+            degrade_batch(d_sig, d_off, d_n, degrade_bits)
+        press_packed("slow5_svb_zd", d_sig, d_off, d_n, arena, out_off, out_len)
+    dfl = _deflate()
+    side, tab = dfl.side_arena(pres, posts)
+    record_bytes = side.size + 8 * n + bound
+    image = torch.empty(dfl.blow5_deflate_image_cap(record_bytes, n), dtype=torch.uint8, device=dev)
+    rec_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    raw = torch.empty(n, dtype=torch.uint8, device=dev)
+    d_side, d_tab = up(side if side.size else np.zeros(4, dtype=np.uint8)), up(tab.reshape(-1), np.int64)
+    torch.cuda.current_stream().synchronize()  # (the library may enqueue on a stream of its own)
+    dfl.blow5_deflate_batch(d_side, d_tab, arena, out_off[:n], out_len, record_bytes, image, rec_off, raw)
+    _call("press_hip_synchronize")
+    raw = raw.cpu().numpy()
+    if np.any(raw == dfl.DEFLATE_REFUSED):
+        raise PressError("%s: the signal of record %d does not press or recode" % (who, int(np.flatnonzero(raw == dfl.DEFLATE_REFUSED)[0])))
+    rec_off = rec_off.cpu().numpy().view(np.uint64)
+    return image[:int(rec_off[n])].cpu().numpy(), rec_off
+
+
+def _deflate_mode(deflate, record_method):
+    if deflate not in ("host", "device"):
+        raise PressError('deflate = %r: "host" or "device"' % (deflate,))
+    if deflate == "device" and record_method != 1:
+        raise PressError('deflate="device" makes zlib streams: it needs record_method 1')
+    return deflate == "device"
+
+
+def blow5_write_like(dst, like, fields, record_method=1, signal_method=1, index=False, ids=None, deflate="host"):
     """A BLOW5 file with the header of `like` and one record per entry of `fields` (signal fields in the given
     signal method: svb-zd streams or int16 samples as bytes); every record takes the fixed fields and auxiliary
     fields of `like`'s first record and a read id of its own (ids, default "read-%08d" padded to the template's
-    length).  For benchmarks and tests: a file of any size with realistic framing.  -> the read ids"""
+    length).  For benchmarks and tests: a file of any size with realistic framing.  deflate="device": the records'
+    zlib streams are made on the device (blow5_deflate_batch_host) instead of by zlib on host threads.  -> the read ids"""
+    on_device = _deflate_mode(deflate, record_method)
     lib = load_library()
     rd = Blow5Reader(like)
     cap = 1 << 26
@@ -1880,14 +1953,18 @@ def blow5_write_like(dst, like, fields, record_method=1, signal_method=1, index=
                 f = fields[k]
                 sigs.append(f if isinstance(f, np.ndarray) else np.frombuffer(f, dtype=np.uint8))
                 posts.append(post)
-            _blow5_write_batch(w, pres, sigs, posts)
+            if on_device:
+                image, rec_off, _ = _deflate().blow5_deflate_batch_host(pres, sigs, posts, signal_method)
+                _blow5_write_image(w, image, rec_off, pres)
+            else:
+                _blow5_write_batch(w, pres, sigs, posts)
     finally:
         _blow5_call("press_hip_blow5_finish", w)
     return out_ids
 
 
 def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, passthrough=False, index=False, verify=False,
-                    degrade_bits=0):
+                    degrade_bits=0, deflate="host"):
     """BLOW5 -> BLOW5 with the signal fields re-coded: codec(list of int16 arrays) -> list of svb-zd
     streams (default: the device, press_batch_host("slow5_svb_zd")); signal_method 0 writes the raw
     samples.  Signals of the source are decoded on the device when it stores them as svb-zd.
@@ -1902,7 +1979,12 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
     file is still plain BLOW5.  A source that stores svb-zd is decoded, degraded and pressed in one device call
     (recode_batch_host) unless a codec is given; verify then compares the fields with D_bits of the source's samples
     on the device (verify_batch_host(..., degrade_bits)).  Not with passthrough.
+    deflate="device" (record_method 1): the records' zlib streams are made on the device and a batch goes to the file as
+    one image (press_hip_blow5_write_image).  With signal_method 1, no codec, no verify and no passthrough the fields stay
+    on the device between the recode or press call and the deflate call, and only the image comes back; otherwise the
+    fields made as above are deflated through blow5_deflate_batch_host.
     Returns the number of reads written."""
+    on_device = _deflate_mode(deflate, record_method)
     degrade_bits = int(degrade_bits)
     if not 0 <= degrade_bits <= 8:
         raise PressError("blow5_transcode: degrade_bits = %d is not in 0 .. 8" % degrade_bits)
@@ -1932,6 +2014,13 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
                 break
             recs = [arena[int(ro[k]):int(ro[k]) + int(rl[k])] for k in range(got.value)]
             fields = [r[int(sp[k]):int(sp[k]) + int(sl[k])].tobytes() for k, r in enumerate(recs)]
+            pres = [r[:int(sp[k]) - 8] for k, r in enumerate(recs)]
+            posts = [r[int(sp[k]) + int(sl[k]):] for k, r in enumerate(recs)]
+            if on_device and signal_method == 1 and codec is None and not passthrough and not verify:
+                image, rec_off = _blow5_fields_deflated(rd.signal_method, fields, ns[:got.value], pres, posts, degrade_bits, src)
+                _blow5_write_image(w, image, rec_off, pres)
+                total += got.value
+                continue
             if passthrough:
                 if rd.signal_method != signal_method:
                     raise PressError("passthrough needs the same signal method on both sides")
@@ -1964,9 +2053,12 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
             else:
                 out = [np.ascontiguousarray(s, dtype=np.int16).tobytes()
                        for s in (degrade_batch_host(sigs, degrade_bits) if degrade_bits else sigs)]
-            _blow5_write_batch(w, [r[:int(sp[k]) - 8] for k, r in enumerate(recs)],
-                               [np.frombuffer(out[k], dtype=np.uint8) for k in range(got.value)],
-                               [r[int(sp[k]) + int(sl[k]):] for k, r in enumerate(recs)])
+            outs = [np.frombuffer(out[k], dtype=np.uint8) for k in range(got.value)]
+            if on_device:
+                image, rec_off, _ = _deflate().blow5_deflate_batch_host(pres, outs, posts, signal_method)
+                _blow5_write_image(w, image, rec_off, pres)
+            else:
+                _blow5_write_batch(w, pres, outs, posts)
             total += got.value
     finally:
         rd.close()

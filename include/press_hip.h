@@ -1633,6 +1633,61 @@ int press_hip_depress_chunks_trimmed_batch(int method, const uint8_t *in, const 
 uint64_t press_hip_depress_chunks_trimmed_workspace_bytes(int method, uint64_t total_samples, uint32_t nreads, uint32_t T,
 							  uint32_t overlap, int mode);
 
+/* ======================================================================= (2z) BLOW5 records deflated on the device */
+
+/*
+ * The write side of a BLOW5 file with record compression zlib (its default): a record is
+ *     R = pre | u64 length | signal | post         (press_hip_blow5_write; length = sig_len, or sig_len / 2 samples for
+ *                                                   signal method 0)
+ * and the file holds, per record, a u64 size and a zlib stream of R.  These calls make the streams on the device; the
+ * record is never put together.  A stream need not be what zlib would write, only what it reads: slow5lib, slow5tools and
+ * pyslow5 inflate it.  tests/_deflate.py is the serial model of every byte below.
+ *
+ * The stream of a record of m bytes:  78 01 | one final DEFLATE block (RFC 1951) | Adler-32 of R, big endian (RFC 1950).
+ *   Tokens.  A byte that is not zero is a literal.  A maximal run of L zero bytes is the literal 0, then matches at
+ * distance 1 over the remaining L - 1 bytes in pieces of min(rest, 258) while rest >= 3, and what is left (0, 1 or 2 bytes)
+ * as literal zeros.  Then end-of-block.
+ *   Code lengths.  The counts: every literal / length symbol as often as it is a token, end-of-block once.  The symbols
+ * with a count stand in a list ascending by (count, symbol); until one node is left the first two nodes become a parent
+ * with the sum of their counts, which goes back in front of the first remaining node whose count is not smaller.  A
+ * symbol's length is its depth; one symbol alone has length 1.  If a length exceeds 15: the same from max(1, c >> k) for
+ * k = 1, 2, ... until none does (the rule of press_hip_table_from_counts).  Codes are the canonical ones of RFC 1951
+ * 3.2.2, written first bit first into the stream's bits (bit i of the stream is bit i % 8 of byte i / 8), extra bits
+ * lowest bit first.
+ *   Block header.  BFINAL 1, BTYPE 2, HLIT = highest symbol with a length - 256 (at least 0), HDIST = 0: one distance
+ * code, of length 1, so that a match costs one 0 bit behind its length's extra bits.  The sequence of the HLIT + 257
+ * lengths and that 1 is written in runs of equal lengths - zeros: code 18 for min(run, 138) while the run has 11 or more,
+ * then code 17 for a rest of 3 .. 10, else the zeros themselves; another length: itself once, then code 16 for
+ * min(rest, 6) while the rest has 3 or more, then the rest themselves.  The code over these 19 symbols is built as above
+ * with the limit 7; HCLEN drops the trailing symbols without a length of the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2
+ * 14 1 15, but keeps four.
+ *   Stored.  Where the block's bytes are not fewer than m + 5 * max(1, ceil(m / 65535)), the record is written as stored
+ * blocks of 65 535 bytes, the last one shorter and final; raw[r] = 1 says so, 0: the dynamic block.
+ *
+ * Inputs.  side: an arena with the records' pre and post; side_tab: 4 words per record { pre_off, pre_len, post_off,
+ * post_len } into it; sig: the arena of the signal fields (e.g. press_hip_press_packed's out), sig_off / sig_len per
+ * record (its out_off / out_len); side_bytes, sig_bytes: the arenas' sizes; record_bytes: the records' bytes together, or
+ * more (the device-resident form sizes its launches by it; the host form counts itself).  A record whose part leaves its
+ * arena, whose sig_len is PRESS_HIP_FAILED, or that has 0xFFFF0000 bytes or more is REFUSED: need[r] = PRESS_HIP_FAILED,
+ * it takes no byte of the image and raw[r] = 0xFF.  With record_bytes too small every record is refused.
+ *   press_hip_blow5_deflate_sizes: need[r] = 8 + the stream's exact length, nothing written.
+ *   press_hip_blow5_deflate_batch: the file image - per record u64 stream length | stream, back to back in the order given
+ * - with rec_off[r] its first byte and rec_off[nrec] the image's size, whatever image_cap is.  A record that ends beyond
+ * image_cap is not written and has raw[r] = 0xFF.
+ *   Forms.  Device resident: every pointer is device memory; image and image_cap are multiples of 4 and all image_cap
+ * bytes are written (zeros where no record lies); the calls only enqueue on the current stream.  Host pointers: staged
+ * and synchronous; the image is made at its exact size and min(rec_off[nrec], image_cap) bytes of `image` are written.
+ * press_hip_blow5_deflate_workspace_bytes: the scratch of the device-resident form (0: more than a call takes).
+ */
+int press_hip_blow5_deflate_sizes(const uint8_t *side, const uint64_t *side_tab, uint64_t side_bytes, const uint8_t *sig,
+				  const uint64_t *sig_off, const uint64_t *sig_len, uint64_t sig_bytes, uint32_t nrec,
+				  uint64_t record_bytes, int signal_method, uint64_t *need, int device_resident);
+int press_hip_blow5_deflate_batch(const uint8_t *side, const uint64_t *side_tab, uint64_t side_bytes, const uint8_t *sig,
+				  const uint64_t *sig_off, const uint64_t *sig_len, uint64_t sig_bytes, uint32_t nrec,
+				  uint64_t record_bytes, int signal_method, uint8_t *image, uint64_t image_cap,
+				  uint64_t *rec_off /* nrec + 1, WRITTEN */, uint8_t *raw /* nrec */, int device_resident);
+uint64_t press_hip_blow5_deflate_workspace_bytes(uint64_t record_bytes, uint32_t nrec);
+
 /* ======================================================================= (3) BLOW5 files (host) */
 
 /*
@@ -1682,6 +1737,12 @@ int press_hip_blow5_write_batch(press_hip_blow5_writer *w, uint32_t n, const uin
 int press_hip_blow5_index(press_hip_blow5_writer *w, int enable);
 /* host threads that inflate records (reader; 0 = as many as the host offers, at most 32) */
 int press_hip_blow5_threads(press_hip_blow5 *f, int threads);
+/* n records that are deflated already: the image of press_hip_blow5_deflate_batch (2z) - `bytes` = rec_off[n], every
+ * record written - goes to the file in one piece, with the index entries press_hip_blow5_write would add (pre[r]: the
+ * record's front part, which holds its read id).  Refused with PRESS_HIP_EARG, and nothing written: a writer whose record
+ * method is not zlib, rec_off that does not ascend from 0 to `bytes`, a record whose u64 length is not its extent. */
+int press_hip_blow5_write_image(press_hip_blow5_writer *w, const uint8_t *image, uint64_t bytes, uint32_t n,
+				const uint64_t *rec_off, const uint8_t *const *pre, const uint64_t *pre_len);
 int press_hip_blow5_finish(press_hip_blow5_writer *w); /* end marker, the index if asked for, close, free */
 
 #ifdef __cplusplus
