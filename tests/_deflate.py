@@ -183,7 +183,7 @@ def dynamic_block(rec, info=None):
     clh = [0] * 19
     for s, _, _ in cls:
         clh[s] += 1
-    cll, _ = huff_lengths(clh, 7)
+    cll, cl_k = huff_lengths(clh, 7)
     clc = canonical(cll)
     ncl = max(4, max(i for i, s in enumerate(CL_ORDER) if cll[s]) + 1)
     b = Bits()
@@ -209,8 +209,35 @@ def dynamic_block(rec, info=None):
             b.put(0, 1)  # the one distance code
     b.put(rev[EOB], lens[EOB])
     if info is not None:
-        info.update(k=k, maxlen=max(lens), lens=lens, nlit=nlit, header_bits=hbits, hist=hist)
+        info.update(k=k, maxlen=max(lens), lens=lens, nlit=nlit, header_bits=hbits, hist=hist, cl_k=cl_k, ncl=ncl, cl_hist=clh,
+                    cl_syms=cls)
     return b.bytes()
+
+
+def unit_bits(rec, lens, unit=1024):
+    """-> the bits of the tokens of every `unit` bytes of the record under the code lengths `lens`; a token counts for the
+    unit in which it opens, a match with its extra bits and its one distance bit; end-of-block counts for none"""
+    out = [0] * ((len(rec) + unit - 1) // unit)
+    pos = 0
+    for kind, v in tokens(rec):
+        if kind == "lit":
+            out[pos // unit] += lens[v]
+            pos += 1
+        else:
+            s, eb, _ = length_code(v)
+            out[pos // unit] += lens[s] + eb + 1
+            pos += v
+    return out
+
+
+def unit_starts(rec, lens, header_bits, unit=1024):
+    """-> the bit at which every unit's first token stands, counted from the first byte of the record's place in the image:
+    80 bits (the u64 length and 78 01), the block header, and the bits of the units before it"""
+    out, at = [], 80 + header_bits
+    for b in unit_bits(rec, lens, unit):
+        out.append(at)
+        at += b
+    return out
 
 
 def stored_blocks(rec):
