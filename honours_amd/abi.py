@@ -188,6 +188,12 @@ PROTOS = {
     "press_hip_blow5_deflate_batch": (I, [P, P, Q, P, P, P, Q, U, Q, I, P, Q, P, P, I]),
     "press_hip_blow5_deflate_workspace_bytes": (Q, [Q, U]),
     "press_hip_blow5_write_image": (I, [P, P, Q, U, P, P, P]),
+    "press_hip_blow5_inflate_batch": (I, [P, P, P, Q, U, P, P, P, P, I]),
+    "press_hip_blow5_inflate_sizes": (I, [P, P, P, Q, U, P, P, I]),
+    "press_hip_blow5_inflate_packed": (I, [P, P, P, Q, U, P, Q, U, P, P, P, I]),
+    "press_hip_blow5_record_fields": (I, [P, P, P, Q, U, I, P, P, P, P, P, I]),
+    "press_hip_blow5_inflate_workspace_bytes": (Q, [Q, U]),
+    "press_hip_blow5_next_stored": (I, [P, U, P, Q, P, P, P]),
 }
 for _fam in ("", "packed_", "depress_pa_", "depress_norm_", "verify_", "stall_"):  # (method, total_samples, nreads)
     PROTOS["press_hip_%sworkspace_bytes" % _fam] = (Q, [I, Q, U])

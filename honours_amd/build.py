@@ -12,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpress_hip.so")
 SOURCES = ["press_sections.hip", "press_svb.hip", "press_exsplit.hip", "press_pa.hip", "press_huffman.hip", "press_rc.hip", "press_zstd.hip", "press_train.hip", "press_packed.hip", "press_stats.hip", "press_quant.hip", "press_rows.hip", "press_trim.hip", "press_verify.hip", "press_degrade.hip", "press_events.hip", "press_segments.hip", "press_ranges.hip", "press_stall.hip",
-           "press_ctx.hip", "press_methods.hip", "press_staging.hip", "press_batch.hip", "press_table.hip", "press_dropin.hip", "blow5_reader.cpp", "press_crc.cpp", "press_tally.hip", "press_rice.hip", "press_dhuf.hip", "press_deflate.hip", "press_cdf.hip"]
-HEADERS = ["press_internal.h", "press_host.h", "press_packed.h", "press_chunk.h", "press_wave.h", "press_segwalk.h", "zs_table.h", "press_crc.h", "press_rice_walk.h", "press_dhuf_walk.h", "press_prefix.h", os.path.join("..", "..", "include", "press_hip.h")]
+           "press_ctx.hip", "press_methods.hip", "press_staging.hip", "press_batch.hip", "press_table.hip", "press_dropin.hip", "blow5_reader.cpp", "press_crc.cpp", "press_tally.hip", "press_rice.hip", "press_dhuf.hip", "press_deflate.hip", "press_inflate.hip", "press_cdf.hip"]
+HEADERS = ["press_internal.h", "press_host.h", "press_packed.h", "press_chunk.h", "press_wave.h", "press_segwalk.h", "zs_table.h", "press_crc.h", "press_rice_walk.h", "press_dhuf_walk.h", "press_inflate_walk.h", "press_prefix.h", os.path.join("..", "..", "include", "press_hip.h")]
 
 
 def _stale():

@@ -101,6 +101,8 @@ struct press_hip_blow5 {
 	// after the other on one thread fed the device at ~0.3 GB/s): what is inflated waits here in file order
 	std::deque<std::vector<uint8_t>> ready;
 	int threads = 0;                // 0: as many as the host offers, at most 32
+	std::vector<uint8_t> stored;    // press_hip_blow5_next_stored: the record that did not fit the last arena
+	bool have_stored = false;
 };
 
 namespace {
@@ -408,6 +410,52 @@ int press_hip_blow5_next(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena,
 	if (!f || !arena || !sig_off || !sig_len || !n_samples || !got)
 		return b5_fail(PRESS_HIP_EARG, "BLOW5: NULL argument");
 	return next_signals(f, max_reads, arena, arena_cap, sig_off, sig_len, n_samples, read_ids, nullptr, got);
+}
+
+// Records as stored: fill_ready's reading of the file (sizes, end marker, a file without one) without its inflate
+int press_hip_blow5_next_stored(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena, uint64_t arena_cap,
+				uint64_t *comp_off, uint64_t *comp_len, uint32_t *got)
+{
+	if (!f || !arena || !comp_off || !comp_len || !got)
+		return b5_fail(PRESS_HIP_EARG, "BLOW5: NULL argument");
+	uint32_t k = 0;
+	uint64_t used = 0;
+	while (k < max_reads) {
+		if (!f->have_stored) {
+			if (f->at_eof)
+				break;
+			uint8_t sz[8];
+			const size_t n8 = fread(sz, 1, 8, f->fp);
+			if ((n8 >= 5 && !memcmp(sz, "5WOLB", 5)) || (n8 == 0 && feof(f->fp))) {
+				f->at_eof = true;
+				break;
+			}
+			if (n8 != 8)
+				return b5_fail(PRESS_HIP_EARG, "BLOW5: truncated record size");
+			uint64_t n;
+			memcpy(&n, sz, 8);
+			if (n == 0 || n > (1ull << 34))
+				return b5_fail(PRESS_HIP_EARG, "BLOW5: implausible record size");
+			f->stored.resize(n);
+			if (fread(f->stored.data(), 1, n, f->fp) != n)
+				return b5_fail(PRESS_HIP_EARG, "BLOW5: truncated record");
+			f->have_stored = true;
+		}
+		const uint64_t at = (used + 15) & ~15ull;
+		if (at + f->stored.size() > arena_cap) {
+			if (k == 0)
+				return b5_fail(PRESS_HIP_EARG, "BLOW5: the arena cannot hold even one record");
+			break; // this record opens the next batch
+		}
+		memcpy(arena + at, f->stored.data(), f->stored.size());
+		comp_off[k] = at;
+		comp_len[k] = f->stored.size();
+		used = at + f->stored.size();
+		f->have_stored = false;
+		k++;
+	}
+	*got = k;
+	return 0;
 }
 
 // ... and the calibration of every read: dor[3k ..] = digitisation, offset, range of read k as the record stores them

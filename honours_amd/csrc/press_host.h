@@ -81,6 +81,7 @@ struct Ctx {
 	DevBuf dh_tab; // per-read Huffman methods: codes and counts (press), decode tables (depress); the other buffers are the Rice methods'
 	DevBuf tl_chunks, tl_ctl, tl_tab, tl_mom; // dataset tallies: the chunk list and its count; host path: the three tables in a row, the moments
 	DevBuf df_rec, df_unit, df_tab, df_need, df_side, df_sig, df_tabs, df_img, df_out; // BLOW5 record deflate (press_deflate.hip): the records, the units' tables, counts / codes / block headers, the sizes; host path: the side arena, the signal arena, the three tables, the image, rec_off and raw
+	DevBuf if_need, if_slot, if_comp, if_tabs, if_out, if_res; // BLOW5 record inflate (press_inflate.hip): the packed form's sizes and slot table; host path: the streams, their tables (and the slots), the arena, out_len and status
 	// staging for host-pointer calls
 	DevBuf sig, off, nsamp, arena, arena_off, lens, lens2, outn, dense, dense_off;
 	DevBuf rin, rin_off; // ... of recode: the source streams

@@ -1192,8 +1192,8 @@ def __getattr__(name):
         if hasattr(mod, name):
             return getattr(mod, name)
     if not name.startswith("_"):  # honours_amd.trim's __all__: the ranged statistics and the trimmed chunk rows (header 2y);
-        import importlib          # honours_amd.deflate's: BLOW5 records deflated on the device (header 2z)
-        for sub in (".trim", ".deflate"):
+        import importlib          # honours_amd.deflate's: BLOW5 records deflated on the device (header 2z);
+        for sub in (".trim", ".deflate", ".inflate"):  # honours_amd.inflate's: ... and inflated there (header 2zb)
             mod = importlib.import_module(sub, __package__)
             if name in mod.__all__:
                 return getattr(mod, name)
@@ -1650,7 +1650,7 @@ def moments_stats(mom, dor=None):
     return out
 
 
-def _report_batches(src, max_reads, arena_bytes, dev):
+def _report_batches(src, max_reads, arena_bytes, dev, inflate="host"):
     """the reads of a BLOW5 file or of a list of int16 arrays as device batches -> (d_sig, d_off, d_n, ids, dor rows)"""
     import torch
 
@@ -1664,6 +1664,20 @@ def _report_batches(src, max_reads, arena_bytes, dev):
     path = os.fspath(src)
     rd = Blow5Reader(path)
     try:
+        while inflate == "device" and rd.record_method == 1 and rd.signal_method == 1:
+            # zlib records of svb-zd fields: inflated, parsed and decoded on the device; no field exists on the host
+            b = rd.next_batch_device(max_reads, arena_bytes, dev)
+            if b is None:
+                return
+            ns = b["n_samples"].cpu().numpy().view(np.uint32)
+            off, total = _layout(ns)
+            d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+            d_sig = torch.zeros(total + 64, dtype=torch.int16, device=dev)
+            d_out_n = torch.zeros(ns.size, dtype=torch.int32, device=dev)
+            depress_batch("slow5_svb_zd", b["rec"], b["sig_off"], b["sig_len"], d_sig, d_off, b["n_samples"], d_out_n)
+            if not torch.equal(d_out_n, b["n_samples"]):
+                raise PressError("a signal of %s does not decode" % path)
+            yield d_sig, d_off, b["n_samples"], b["ids"], b["dor"].cpu().numpy()
         arena = np.empty(arena_bytes, dtype=np.uint8)
         boff = np.zeros(max_reads, dtype=np.uint64)
         blen = np.zeros(max_reads, dtype=np.uint64)
@@ -1704,7 +1718,7 @@ def _report_batches(src, max_reads, arena_bytes, dev):
         rd.close()
 
 
-def dataset_report(src, max_reads=4096, arena_bytes=1 << 28):
+def dataset_report(src, max_reads=4096, arena_bytes=1 << 28, inflate="host"):
     """What the data looks like, tallied on the device: src is the path of a BLOW5 file or a list of int16 arrays.  The
     reads go through in batches (svb-zd signal fields are decoded on the device), one press_hip_signal_tally per batch
     with all four outputs; only the tables and the moments come back.  -> dict:
@@ -1716,16 +1730,20 @@ def dataset_report(src, max_reads=4096, arena_bytes=1 << 28):
       ratio                  16 / bits for each of them (inf where the entropy is 0)
       mom, ids, dor, stats   the per-read moments, the read ids, [nreads, 3] digitisation / offset / range (None for a list
                              of arrays) and moments_stats(mom, dor)
-      reads, samples         counts"""
+      reads, samples         counts
+    inflate="device": a file with record method zlib and signal method svb-zd is inflated on the device too
+    (Blow5Reader.next_batch_device), so that no field of a batch exists on the host; record methods none and zstd, and
+    files of int16 samples, keep the host path."""
     import torch
 
+    _inflate_mode(inflate)
     use_torch_stream()
     dev = torch.device("cuda", torch.cuda.current_device())
     raw = torch.zeros(TALLY_BINS, dtype=torch.int64, device=dev)
     delta = torch.zeros(TALLY_BINS, dtype=torch.int64, device=dev)
     trans = torch.zeros(TALLY_SYMS * TALLY_SYMS, dtype=torch.int64, device=dev)
     moms, ids, dors = [], [], []
-    for d_sig, d_off, d_n, batch_ids, dor in _report_batches(src, max_reads, arena_bytes, dev):
+    for d_sig, d_off, d_n, batch_ids, dor in _report_batches(src, max_reads, arena_bytes, dev, inflate):
         mom = torch.zeros(4 * d_off.numel(), dtype=torch.int64, device=dev)
         signal_tally(d_sig, d_off, d_n, raw, delta, trans, mom)
         moms.append(mom.cpu().numpy().view(MOMENTS_DTYPE))
@@ -1808,6 +1826,82 @@ class Blow5Reader:
             out.append((rid, int(ns[k]), arena[int(off[k]):int(off[k]) + int(ln[k])].tobytes(),
                         (float(dor[k, 0]), float(dor[k, 1]), float(dor[k, 2]))))
         return out
+
+    def next_stored(self, max_reads=4096, arena_bytes=1 << 28, arena=None):
+        """press_hip_blow5_next_stored: the next records AS THE FILE STORES THEM, with no inflate (record method zlib: the
+        zlib streams blow5_inflate_batch reads) -> (arena uint8, comp_off uint64, comp_len uint64), the tables `got`
+        long: 0 at the end of the file.  Every record starts on a 16-byte boundary.  arena: a numpy uint8 array to fill
+        (e.g. page-locked memory) in the place of a new one.  No GPU is needed.  One kind of call per reader: records
+        the inflating calls have read ahead are not handed out again."""
+        if arena is None:
+            arena = np.empty(arena_bytes, dtype=np.uint8)
+        off = np.zeros(max_reads, dtype=np.uint64)
+        ln = np.zeros(max_reads, dtype=np.uint64)
+        got = ctypes.c_uint32()
+        _blow5_call("press_hip_blow5_next_stored", self._h, max_reads, _ptr(arena), arena.size, _ptr(off), _ptr(ln), ctypes.byref(got))
+        return arena, off[:got.value], ln[:got.value]
+
+    def next_batch_device(self, max_reads=4096, arena_bytes=1 << 28, device="cuda"):
+        """The next records of a file with record method zlib, inflated and parsed ON THE DEVICE: the stored records go up
+        as they are (next_stored), blow5_inflate_batch inflates them - a first round with slots of 4 * comp_len + 4096
+        bytes, the host reader's own first guess, and a second one with the exact length for the records that answer
+        ROOM - and blow5_record_fields finds the fields.  -> dict of CUDA tensors rec (uint8: the record arena), rec_off /
+        rec_len (int64: the records in it), sig_off
+        / sig_len (int64: depress_batch's in_off / in_len over rec), n_samples (int32), dor (float64 (n, 3)), and ids, a
+        list of str on the host; None at the end of the file.  A record with any other failure status raises PressError
+        with the status name."""
+        import importlib
+
+        import torch
+
+        if self.record_method != 1:
+            raise PressError("next_batch_device inflates zlib records: this file's record method is %d" % self.record_method)
+        ifl = importlib.import_module(".inflate", __package__)
+        if getattr(self, "_stored_arena", None) is None or self._stored_arena.size < arena_bytes:
+            self._stored_arena = np.empty(arena_bytes, dtype=np.uint8)  # kept: one allocation per reader, not per batch
+        arena, off, ln = self.next_stored(max_reads, arena=self._stored_arena[:arena_bytes])
+        n = off.size
+        if n == 0:
+            return None
+        used = int(off[-1] + ln[-1])
+        comp = torch.from_numpy(arena[:used]).to(device)
+        d_off = torch.from_numpy(off.view(np.int64)).to(device)
+        d_ln = torch.from_numpy(ln.view(np.int64)).to(device)
+        slots = _slots(4 * ln + 4096)
+        out_off = torch.from_numpy(slots.view(np.int64)).to(device)
+        # the second round's records go behind the first round's slots: a spare eighth is there for them, so that the
+        # arena is not copied (only a batch whose ROOM records need more gets a larger arena)
+        first = int(slots[-1])
+        rec = torch.empty(first + max(first // 8, 1 << 20), dtype=torch.uint8, device=device)
+        out_len = torch.empty(n, dtype=torch.int64, device=device)
+        status = torch.empty(n, dtype=torch.uint8, device=device)
+        ifl.blow5_inflate_batch(comp, d_off, d_ln, rec, out_off, out_len, status)
+        st = status.cpu().numpy()
+        rec_off = out_off[:n]
+        again = np.flatnonzero(st == ifl.INFLATE_STATUS.index("ROOM"))
+        if again.size:  # the second round: exact slots behind the first round's
+            idx = torch.from_numpy(again).to(device)
+            need = out_len[idx].cpu().numpy().astype(np.uint64)
+            slots2 = _slots(need) + np.uint64(first)
+            if int(slots2[-1]) > rec.numel():
+                rec = torch.cat([rec[:first], torch.empty(int(slots2[-1]) - first, dtype=torch.uint8, device=device)])
+            len2 = torch.empty(again.size, dtype=torch.int64, device=device)
+            st2 = torch.empty(again.size, dtype=torch.uint8, device=device)
+            ifl.blow5_inflate_batch(comp, d_off[idx].contiguous(), d_ln[idx].contiguous(), rec,
+                                    torch.from_numpy(slots2.view(np.int64)).to(device), len2, st2)
+            rec_off = rec_off.clone()
+            rec_off[idx] = torch.from_numpy(slots2[:-1].view(np.int64).copy()).to(device)
+            out_len[idx] = len2
+            st[again] = st2.cpu().numpy()
+        if st.any():
+            k = int(np.flatnonzero(st)[0])
+            raise PressError("next_batch_device: record %d does not inflate: %s" % (k, ifl.INFLATE_STATUS[st[k]]))
+        sig_off, sig_len, ns, dor, ids = ifl.blow5_record_fields(rec, rec_off, out_len, self.signal_method)
+        if bool((sig_len < 0).any()):
+            raise PressError("next_batch_device: record %d is not a BLOW5 record" % int(torch.nonzero(sig_len < 0)[0]))
+        names = [bytes(r).split(b"\0")[0].decode() for r in ids.cpu().numpy()]
+        return {"rec": rec, "rec_off": rec_off, "rec_len": out_len, "sig_off": sig_off, "sig_len": sig_len, "n_samples": ns, "dor": dor,
+                "ids": names}
 
     def set_threads(self, n):
         """host threads that inflate records (0: as many as the host offers, at most 32)"""
@@ -1904,6 +1998,64 @@ def _blow5_fields_deflated(src_signal_method, fields, ns, pres, posts, degrade_b
     return image[:int(rec_off[n])].cpu().numpy(), rec_off
 
 
+def _blow5_batch_deflated(batch, src_signal_method, degrade_bits, who):
+    """One batch of a transcode with inflate="device" and deflate="device": what Blow5Reader.next_batch_device made - the
+    inflated records in a device arena and their fields - is recoded (svb-zd fields) or pressed (int16 samples) into
+    svb-zd fields in another device arena, and the deflate call takes the records' front parts and auxiliary fields out
+    of the record arena itself; only the front parts (for the index) and the image come back.
+    -> (image, rec_off, pres) as numpy arrays"""
+    import torch
+
+    rec, ro, rl, so, sl, d_n = (batch[k] for k in ("rec", "rec_off", "rec_len", "sig_off", "sig_len", "n_samples"))
+    n = ro.numel()
+    dev = rec.device
+    ns = d_n.cpu().numpy().view(np.uint32)
+    off, total = _layout(ns)
+    d_off = torch.from_numpy(off.view(np.int64)).to(dev)
+    bound = sum(int(load_library().press_hip_bound(METHODS["slow5_svb_zd"], int(x))) for x in ns)
+    arena = torch.empty((bound + 3) // 4 * 4 + 64, dtype=torch.uint8, device=dev)
+    out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    out_len = torch.empty(n, dtype=torch.int64, device=dev)
+    if src_signal_method == 1:
+        out_n = torch.empty(n, dtype=torch.int32, device=dev)
+        recode_packed("slow5_svb_zd", "slow5_svb_zd", rec, so, sl, d_n, d_off, arena, out_off, out_len, out_n, total_samples=total,
+                      degrade_bits=degrade_bits)
+    else:  # int16 samples at any byte offset of the record arena: gathered into an aligned sample arena on the device
+        d_sig = torch.zeros(total + 64, dtype=torch.int16, device=dev)
+        h_so = so.cpu().numpy()
+        for k in range(n):
+            d_sig[int(off[k]):int(off[k]) + int(ns[k])] = rec[int(h_so[k]):int(h_so[k]) + 2 * int(ns[k])].clone().view(torch.int16)
+        if degrade_bits:
+            degrade_batch(d_sig, d_off, d_n, degrade_bits)
+        press_packed("slow5_svb_zd", d_sig, d_off, d_n, arena, out_off, out_len)
+    pre_len = so - 8 - ro
+    post_off = so + sl
+    d_tab = torch.stack([ro, pre_len, post_off, ro + rl - post_off], dim=1).contiguous().reshape(-1)
+    width = int(pre_len.max())
+    idx = (ro[:, None] + torch.arange(width, device=dev)[None, :]).clamp_(max=rec.numel() - 1)
+    h_pre, h_len = rec[idx].cpu().numpy(), pre_len.cpu().numpy()
+    pres = [np.ascontiguousarray(h_pre[k, :int(h_len[k])]) for k in range(n)]
+    dfl = _deflate()
+    record_bytes = int(rl.sum()) - int(sl.sum()) + bound
+    image = torch.empty(dfl.blow5_deflate_image_cap(record_bytes, n), dtype=torch.uint8, device=dev)
+    rec_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    raw = torch.empty(n, dtype=torch.uint8, device=dev)
+    torch.cuda.current_stream().synchronize()  # (the library may enqueue on a stream of its own)
+    dfl.blow5_deflate_batch(rec, d_tab, arena, out_off[:n], out_len, record_bytes, image, rec_off, raw)
+    _call("press_hip_synchronize")
+    raw = raw.cpu().numpy()
+    if np.any(raw == dfl.DEFLATE_REFUSED):
+        raise PressError("%s: the signal of record %d does not press or recode" % (who, int(np.flatnonzero(raw == dfl.DEFLATE_REFUSED)[0])))
+    rec_off = rec_off.cpu().numpy().view(np.uint64)
+    return image[:int(rec_off[n])].cpu().numpy(), rec_off, pres
+
+
+def _inflate_mode(inflate):
+    if inflate not in ("host", "device"):
+        raise PressError('inflate = %r: "host" or "device"' % (inflate,))
+    return inflate == "device"
+
+
 def _deflate_mode(deflate, record_method):
     if deflate not in ("host", "device"):
         raise PressError('deflate = %r: "host" or "device"' % (deflate,))
@@ -1964,7 +2116,7 @@ def blow5_write_like(dst, like, fields, record_method=1, signal_method=1, index=
 
 
 def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, passthrough=False, index=False, verify=False,
-                    degrade_bits=0, deflate="host"):
+                    degrade_bits=0, deflate="host", inflate="host"):
     """BLOW5 -> BLOW5 with the signal fields re-coded: codec(list of int16 arrays) -> list of svb-zd
     streams (default: the device, press_batch_host("slow5_svb_zd")); signal_method 0 writes the raw
     samples.  Signals of the source are decoded on the device when it stores them as svb-zd.
@@ -1983,8 +2135,14 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
     one image (press_hip_blow5_write_image).  With signal_method 1, no codec, no verify and no passthrough the fields stay
     on the device between the recode or press call and the deflate call, and only the image comes back; otherwise the
     fields made as above are deflated through blow5_deflate_batch_host.
+    inflate="device": a source with record method zlib is inflated and parsed on the device
+    (Blow5Reader.next_batch_device).  Together with the conditions under which deflate="device" keeps the fields on the
+    device, no field of a batch exists on the host: the records go up as stored and come back as the image.  In every
+    other combination the inflated records are copied to the host and go on as above.  Sources with record method none or
+    zstd keep the host path whatever `inflate` says.
     Returns the number of reads written."""
     on_device = _deflate_mode(deflate, record_method)
+    inflate_device = _inflate_mode(inflate)
     degrade_bits = int(degrade_bits)
     if not 0 <= degrade_bits <= 8:
         raise PressError("blow5_transcode: degrade_bits = %d is not in 0 .. 8" % degrade_bits)
@@ -2007,9 +2165,25 @@ def blow5_transcode(src, dst, record_method=1, signal_method=1, codec=None, pass
         ro, rl, sp, sl = (np.zeros(maxr, dtype=np.uint64) for _ in range(4))
         ns = np.zeros(maxr, dtype=np.uint32)
         got = ctypes.c_uint32()
+        inflate_device = inflate_device and rd.record_method == 1
         while True:
-            _blow5_call("press_hip_blow5_next_records", rd._h, maxr, _ptr(arena), cap, _ptr(ro), _ptr(rl), _ptr(sp), _ptr(sl),
-                        _ptr(ns), ctypes.byref(got))
+            if inflate_device:
+                batch = rd.next_batch_device(maxr, cap)
+                if batch is None:
+                    break
+                got.value = len(batch["ids"])
+                if on_device and signal_method == 1 and codec is None and not passthrough and not verify:
+                    image, rec_off, pres = _blow5_batch_deflated(batch, rd.signal_method, degrade_bits, src)
+                    _blow5_write_image(w, image, rec_off, pres)
+                    total += got.value
+                    continue
+                arena = batch["rec"].cpu().numpy()  # the other combinations work on the host from here on
+                ro[:got.value], rl[:got.value] = batch["rec_off"].cpu().numpy(), batch["rec_len"].cpu().numpy()
+                sp[:got.value] = (batch["sig_off"] - batch["rec_off"]).cpu().numpy()
+                sl[:got.value], ns[:got.value] = batch["sig_len"].cpu().numpy(), batch["n_samples"].cpu().numpy().view(np.uint32)
+            else:
+                _blow5_call("press_hip_blow5_next_records", rd._h, maxr, _ptr(arena), cap, _ptr(ro), _ptr(rl), _ptr(sp), _ptr(sl),
+                            _ptr(ns), ctypes.byref(got))
             if got.value == 0:
                 break
             recs = [arena[int(ro[k]):int(ro[k]) + int(rl[k])] for k in range(got.value)]

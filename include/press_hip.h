@@ -1688,6 +1688,85 @@ int press_hip_blow5_deflate_batch(const uint8_t *side, const uint64_t *side_tab,
 				  uint64_t *rec_off /* nrec + 1, WRITTEN */, uint8_t *raw /* nrec */, int device_resident);
 uint64_t press_hip_blow5_deflate_workspace_bytes(uint64_t record_bytes, uint32_t nrec);
 
+/* ======================================================================= (2zb) BLOW5 records inflated on the device */
+
+/*
+ * The read side of a BLOW5 file with record compression zlib: the file holds, per record, a u64 size and a zlib stream
+ * (press_hip_blow5_next_stored hands them out as they are stored), and these calls inflate the streams on the device, one
+ * wave per record.  The decoder reads EVERY zlib stream that zlib's uncompress reads (RFC 1950 around RFC 1951), not only
+ * the streams of section 2z:
+ *   the header CMF FLG with CM = 8, CINFO <= 7, the FCHECK rule and FDICT = 0; any number of blocks in any order - stored,
+ * fixed Huffman, dynamic Huffman - among them the empty stored blocks of a sync or full flush and an empty final block;
+ * code lengths 1 .. 15; the repeat codes 16 / 17 / 18, also across the boundary between the literal / length and the
+ * distance lengths; up to 286 literal / length and 30 distance codes; a set of codes that is complete or - as zlib allows
+ * it - has one code of one bit (the one distance code of 2z; a literal / length set that is end-of-block alone), and no
+ * distance code at all; lengths 3 .. 258, 258 also as symbol 284 with extra bits 31; distances 1 .. 32768 whatever CINFO
+ * says; a match that overlaps itself; the Adler-32, checked on the device; bytes behind the Adler-32 are ignored.
+ *
+ * status[r]: PRESS_HIP_INFLATE_OK, or the FIRST failure met in stream order -
+ *   HEADER     CM, CINFO, FCHECK or FDICT
+ *   TRUNCATED  the stream needs a bit beyond comp_len (a Huffman code counts bit by bit: one that ends behind the end)
+ *   BTYPE      block type 3
+ *   STORED     LEN is not the complement of NLEN
+ *   CODES      more than 286 / 30 codes; a repeat with nothing before it or past the end; an over-subscribed set; an
+ *              incomplete set other than the single code of one bit (the code-length code must be complete); no
+ *              end-of-block code
+ *   SYMBOL     literal / length 286 or 287, distance 30 or 31, 15 bits that are no code of an incomplete set
+ *   DISTANCE   a match reaches in front of the record's first byte (found before a byte of it is copied)
+ *   ADLER      the Adler-32 of the bytes is not the stored one
+ *   ROOM       well formed to its end, but longer than its slot (the packed form: it ends behind out_cap)
+ *   REFUSED    comp_off[r] + comp_len[r] leaves comp_bytes, or comp_len[r] is 4 GiB or more
+ * tests/_inflate.py is the serial model of this classification; honours_amd/csrc/press_inflate_walk.h holds the rules as
+ * plain C++ for the host and the device (ph::inflate_serial: one stream on one host thread).
+ *
+ *   press_hip_blow5_inflate_batch: the caller's slots, as press_hip_press_batch's - record r into out[out_off[r] ..
+ * out_off[r + 1]), any byte offset.  Nothing outside a slot is written and a failed record leaves its neighbours alone.
+ * out_len[r] is the record's exact inflated length whenever the stream is well formed to its end: OK, and ROOM - there the
+ * walk goes on as a count without writing, and the Adler-32 is not judged.  Otherwise out_len[r] = PRESS_HIP_FAILED.  Of
+ * a failed record's slot any byte may have been written.  One walk per record.
+ *   press_hip_blow5_inflate_sizes: the counting walk alone - need[r] as out_len[r] above with slots of any size, status[r]
+ * OK for a stream that is well formed to its end.  No arena, and NO Adler-32 check: the bytes are never made.
+ *   press_hip_blow5_inflate_packed: the sizes walk, the layout (rules and align as press_hip_press_packed: out_off WRITTEN,
+ * nrec + 1, whatever out_cap is), then the writing walk.  A failed record takes no byte and has out_len[r] =
+ * PRESS_HIP_FAILED, one that ends behind out_cap too, with status ROOM.  One failure is found only by the writing walk:
+ * a stream that is well formed to its end but whose Adler-32 is wrong keeps its room in the layout (the sizes walk makes
+ * no bytes), its bytes are written there, and it has status ADLER and out_len[r] = PRESS_HIP_FAILED.  A device `out` must
+ * be a multiple of 4 bytes.
+ *   press_hip_blow5_record_fields: parse_record's rules (the host reader's) over inflated records, one lane per record:
+ * sig_off[r] (from the arena's first byte) and sig_len[r] are what the depress / recode / pa / chunk calls take as in_off
+ * / in_len, n_samples[r] the read's samples (signal method 1: the svb-zd stream's count), dor[3r ..] digitisation, offset
+ * and range (may be NULL), read_ids (may be NULL) nrec x PRESS_HIP_BLOW5_ID_LEN chars, NUL padded.  A record that
+ * parse_record refuses, or whose rec_len is PRESS_HIP_FAILED, gets sig_len = PRESS_HIP_FAILED and n_samples = 0.
+ *   Forms.  Device resident: every pointer is device memory; the calls only enqueue on the current stream and depend on
+ * nothing an earlier call left in scratch.  Host pointers: staged and synchronous; out_off must not descend.  Arguments are
+ * checked before the device is asked for (NULL, align, a device `out` of the packed form); nrec == 0 is PRESS_HIP_OK.
+ * press_hip_blow5_inflate_workspace_bytes: the scratch of the device-resident forms.
+ */
+#define PRESS_HIP_INFLATE_OK        0
+#define PRESS_HIP_INFLATE_HEADER    1
+#define PRESS_HIP_INFLATE_TRUNCATED 2
+#define PRESS_HIP_INFLATE_BTYPE     3
+#define PRESS_HIP_INFLATE_STORED    4
+#define PRESS_HIP_INFLATE_CODES     5
+#define PRESS_HIP_INFLATE_SYMBOL    6
+#define PRESS_HIP_INFLATE_DISTANCE  7
+#define PRESS_HIP_INFLATE_ADLER     8
+#define PRESS_HIP_INFLATE_ROOM      9
+#define PRESS_HIP_INFLATE_REFUSED   10
+#define PRESS_HIP_INFLATE_DRAIN     4096 /* bytes a wave produces between two writes of its LDS window to the slot */
+int press_hip_blow5_inflate_batch(const uint8_t *comp, const uint64_t *comp_off, const uint64_t *comp_len, uint64_t comp_bytes,
+				  uint32_t nrec, uint8_t *out, const uint64_t *out_off /* nrec + 1 */, uint64_t *out_len,
+				  uint8_t *status, int device_resident);
+int press_hip_blow5_inflate_sizes(const uint8_t *comp, const uint64_t *comp_off, const uint64_t *comp_len, uint64_t comp_bytes,
+				  uint32_t nrec, uint64_t *need, uint8_t *status, int device_resident);
+int press_hip_blow5_inflate_packed(const uint8_t *comp, const uint64_t *comp_off, const uint64_t *comp_len, uint64_t comp_bytes,
+				   uint32_t nrec, uint8_t *out, uint64_t out_cap, uint32_t align, uint64_t *out_off /* WRITTEN */,
+				   uint64_t *out_len, uint8_t *status, int device_resident);
+int press_hip_blow5_record_fields(const uint8_t *rec, const uint64_t *rec_off, const uint64_t *rec_len, uint64_t rec_bytes,
+				  uint32_t nrec, int signal_method, uint64_t *sig_off, uint64_t *sig_len, uint32_t *n_samples,
+				  double *dor /* may be NULL */, char *read_ids /* may be NULL */, int device_resident);
+uint64_t press_hip_blow5_inflate_workspace_bytes(uint64_t comp_bytes, uint32_t nrec);
+
 /* ======================================================================= (3) BLOW5 files (host) */
 
 /*
@@ -1719,6 +1798,12 @@ const char *press_hip_blow5_last_error(void);
 int press_hip_blow5_next_records(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena, uint64_t arena_cap,
 				 uint64_t *rec_off, uint64_t *rec_len, uint64_t *sig_pos, uint64_t *sig_len,
 				 uint32_t *n_samples, uint32_t *got);
+/* Records AS THE FILE STORES THEM, with no inflate (for press_hip_blow5_inflate_batch, 2zb): up to max_reads records
+ * copied into arena, each on a 16-byte boundary; comp_off / comp_len in bytes (the u64 size in front of a record is not
+ * copied).  File order and the end marker as the calls above; a record that does not fit arena_cap opens the next batch.
+ * Records the calls above have read ahead and inflated are not handed out again: use one kind of call per handle. */
+int press_hip_blow5_next_stored(press_hip_blow5 *f, uint32_t max_reads, uint8_t *arena, uint64_t arena_cap,
+				uint64_t *comp_off, uint64_t *comp_len, uint32_t *got);
 /* Writer (slow5_write / slow5_rec_to_mem, slow5.c:3903-4010): header copied from `like`; records
  * framed and - record_method 1 - deflated; signal_method says what `sig` holds (0: int16 samples,
  * 1: svb-zd, e.g. the output of press_hip_press_batch(PRESS_HIP_SLOW5_SVB_ZD, ...)). */
